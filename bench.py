@@ -2,11 +2,14 @@
 """bench.py -- throughput of the hot path on N MI355X GPUs of one node (contract in the task statement).
 
 Workload at N=1 (BASELINE.json configs[1]): synthetic 640x480 frames -- three drawn cuboids over a band-limited texture, so that ORB, LSD and
-Canny see real content (asserted: >= 800 key points and >= 100 line segments per frame) -- with 3 boxes each, `--frames` frames resident in
+Canny see real content (asserted with --full: >= 800 key points and >= 100 line segments per frame) -- with 3 boxes each, `--frames` frames resident in
 HBM per GPU; one step = one pass of the front-end over that batch: ORBextractor (1000 features, 8 levels, FAST 20/7) + LSD line detection
 with LBD descriptors (line_lbd defaults) + detect_3d_cuboid with a 180-yaw x 3-VP proposal sweep (yaw step 0.5 deg over +-45 deg; Canny +
 distance transform + line merge + VP support + sweep / score + selection).  N>1: every rank owns its own block of frames (no data-path
-collective, weak scaling).  The same JSON line carries, measured in the same run on rank 0 at N=1:
+collective, weak scaling).  A plain run sets up, warms up, times --steps steps and prints the headline line (`value`, `ms_per_step`, the
+per-kernel times of the timed region and the score kernel's `roofline` from them); --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs).  With --full the same JSON line also carries the checks of the batch's results, the parts of `roofline` that take runs
+of their own and, measured in the same run on rank 0 at N=1:
   "ba"   the second half of BASELINE's metric (LM iterations/s of the object BA at 1000 key frames),
   "c3"   config 3: the 1241x376 stream, 2000 ORB features + LSD/LBD + frame-to-frame SearchByProjection, with the matcher's own roofline,
   "c4"   config 4's per-GPU share: 64 frames x 8 boxes through the cuboid path,
@@ -642,6 +645,63 @@ def pcie_inclusive(ctx, scenes, yaw_step, nfeat, n=24, local_rank=0):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- outputs of the timed path
+DUMP_FRAMES = 64           # frames of the batch whose results are written at most (a fixed, seeded sample)
+DUMP_SEED = 0
+DUMP_MAX_BYTES = 64 << 20  # the sample is cut short where the next frame's results would not fit
+
+
+def _rows(rec):
+    """A structured array -> (n, columns) float64, its fields flattened in dtype order (every f4 / i4 value is exact in f64)."""
+    cols = [rec[k].reshape(len(rec), int(np.prod(rec.dtype[k].shape, dtype=np.int64))).astype(np.float64) for k in rec.dtype.names]
+    return np.concatenate(cols, axis=1)
+
+
+def _tagged(tags, rec):
+    """_rows(rec) behind the columns `tags` (one row of tags per record, or one row for all)."""
+    return np.concatenate([np.broadcast_to(np.asarray(tags, np.float64), (len(rec), np.shape(tags)[-1])), _rows(rec)], axis=1)
+
+
+def dump_outputs(out_dir, scenes, batch, orb, lsd):
+    """What a caller of the front-end receives after the last timed step, for up to DUMP_FRAMES frames drawn with DUMP_SEED, as out_dir/<name>.npy:
+      frames.npy           the sampled frame indices (ascending)
+      orb_keypoints.npy    (n, 8)  float64: frame, then KEYPOINT_DTYPE's fields (x y size angle response octave class_id), in the extractor's order
+      orb_descriptors.npy  (n, 32) float32: the descriptor bytes of those key points
+      lsd_keylines.npy     (n, 18) float64: frame, then KEYLINE_DTYPE's fields (pt as two columns)
+      lbd_descriptors.npy  (n, 32) float32: the LBD bytes of those KeyLines
+      cuboids.npy          (n, 3 + 60) float64: frame, box of the frame, rank in the box's list, then CUBOID_DTYPE's fields flattened
+    The frames are taken in the order of the draw for as long as their results fit in DUMP_MAX_BYTES, so the same outputs give the same sample.
+    The line detectors alternate steps over the same resident frames, so every detector that ran holds the line results of every step; detector 0
+    always runs the first pass and is the one read."""
+    from cube_slam_amd.cuboid import CUBOID_DTYPE
+    F = len(scenes)
+    drawn = np.random.default_rng(DUMP_SEED).choice(F, size=min(F, DUMP_FRAMES), replace=False)
+    per_orb = orb.read() if orb is not None else None
+    got = batch.read()
+    first = np.concatenate([[0], np.cumsum([len(s["boxes"]) for s in scenes])])
+    pieces, total = {}, 0
+    for f in drawn:
+        p = {"frames": np.array([f], np.float64)}
+        if per_orb is not None:
+            k, d = per_orb[f]
+            p["orb_keypoints"], p["orb_descriptors"] = _tagged([f], k), d.astype(np.float32)
+        if lsd is not None:
+            k, d = lsd.read(int(f))
+            p["lsd_keylines"], p["lbd_descriptors"] = _tagged([f], k), d.astype(np.float32)
+        p["cuboids"] = np.concatenate([_tagged(np.array([[f, b, r] for r in range(len(c))], np.float64).reshape(-1, 3), c) for b, c in enumerate(got[first[f]:first[f + 1]])] +
+                                      [_tagged(np.zeros((0, 3)), np.zeros(0, CUBOID_DTYPE))])
+        size = sum(a.nbytes for a in p.values())
+        if total + size > DUMP_MAX_BYTES:
+            break
+        total += size
+        pieces[int(f)] = p
+    frames = sorted(pieces)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in pieces[frames[0]] if frames else ():
+        np.save(os.path.join(out_dir, name + ".npy"), np.concatenate([pieces[f][name] for f in frames]))
+    return {"dir": out_dir, "frames": len(frames), "bytes": total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -664,6 +724,10 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the c3 / c4 / pcie_inclusive / traffic blocks")
     ap.add_argument("--ba-iters", type=int, default=10)
     ap.add_argument("--orb-features", type=int, default=1000)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the checks of the batch's results, the parts of `roofline` that take runs of their own (the score "
+                    "kernel alone and under the phased runner, PMC traffic), c3 / c4 / chained / streamed / pcie_inclusive, the object BA and the CPU baselines; --no-extra / --no-ba / --no-cpu leave blocks out of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed as DIR/<name>.npy for a seeded sample of frames (dump_outputs); the line "
+                    "results are read from the first line detector, which holds the same results as the one that ran the last step: every detector runs over the same resident frames")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # `python bench.py --gpus N` launches its own ranks (the driver uses torch.distributed.run directly)
@@ -773,6 +837,7 @@ def main():
     ctx.timing(False)
     for c in side_ctxs:
         c.timing(False)
+    dumped = dump_outputs(args.dump_outputs, scenes, batch, orb, lsd) if args.dump_outputs and rank == 0 else None
     variants = None
     if args.sweep and rank == 0 and world == 1 and lsd is not None:
         variants = []
@@ -794,7 +859,7 @@ def main():
         fe.set_cuboid_ctx(ctx_cub)
     # the phased runner on the same objects, shortly: its throughput and the score kernel's time in ITS timed region (the kernel never meets a region walk there)
     phased_alt = None
-    if lsd is not None and not args.phased and args.frames >= 512 and os.environ.get("CUBESLAM_LSD_REGIONS", "seq") == "seq" and len(ctx_lines) >= 2 and rank == 0 and world == 1:
+    if args.full and lsd is not None and not args.phased and args.frames >= 512 and os.environ.get("CUBESLAM_LSD_REGIONS", "seq") == "seq" and len(ctx_lines) >= 2 and rank == 0 and world == 1:
         fe.set_phased(True)
         for _ in range(len(ctx_lines)):
             fe.step()
@@ -813,31 +878,34 @@ def main():
         fe.set_phased(False)
     # the same kernel without kernels of the other paths sharing the GPU: in the launch shape of the timed region, and in the 512-thread shape it has when it owns the CUs
     iso = {}
-    for shared in ((True, False) if (lsd is not None and not args.phased) else (False,)):
-        batch.set_shared_gpu(shared)
-        batch.run(); ctx.sync()
-        ctx.timing(True); ctx.timing_reset()
-        for _ in range(10):
-            batch.run()
-        ctx.sync()
-        iso[shared] = ctx.timing_get("cuboid_sweep_score")
-        ctx.timing(False)
-    iso_ms, iso_n = iso[False]
-    batch.set_shared_gpu(lsd is not None and not args.phased)
+    if args.full:
+        for shared in ((True, False) if (lsd is not None and not args.phased) else (False,)):
+            batch.set_shared_gpu(shared)
+            batch.run(); ctx.sync()
+            ctx.timing(True); ctx.timing_reset()
+            for _ in range(10):
+                batch.run()
+            ctx.sync()
+            iso[shared] = ctx.timing_get("cuboid_sweep_score")
+            ctx.timing(False)
+        iso_ms, iso_n = iso[False]
+        batch.set_shared_gpu(lsd is not None and not args.phased)
     st = batch.stats()
     ss = batch.score_stats()
-    got = batch.read()
-    assert sum(len(g) for g in got) > 0
-    n_kp = sum(len(k) for k, _ in orb.read()) if orb is not None else 0
-    n_lines = sum(len(lsd.read(f, with_desc=False)) for f in range(args.frames)) if lsd is not None else 0
-    if orb is not None and BG_TEXTURE > 0 and args.orb_features >= 1000:
-        assert n_kp >= 800 * args.frames, "the frames are too empty for the ORB quota: %d key points per frame" % (n_kp // args.frames)
-    if lsd is not None and BG_TEXTURE > 0:
-        assert n_lines >= 100 * args.frames, "the frames are too empty for LSD: %d segments per frame" % (n_lines // args.frames)
+    n_kp = n_lines = None
+    if args.full:
+        got = batch.read()
+        assert sum(len(g) for g in got) > 0
+        n_kp = sum(len(k) for k, _ in orb.read()) if orb is not None else 0
+        n_lines = sum(len(lsd.read(f, with_desc=False)) for f in range(args.frames)) if lsd is not None else 0
+        if orb is not None and BG_TEXTURE > 0 and args.orb_features >= 1000:
+            assert n_kp >= 800 * args.frames, "the frames are too empty for the ORB quota: %d key points per frame" % (n_kp // args.frames)
+        if lsd is not None and BG_TEXTURE > 0:
+            assert n_lines >= 100 * args.frames, "the frames are too empty for LSD: %d segments per frame" % (n_lines // args.frames)
 
     solo = rank == 0 and world == 1
     extra = {}
-    if solo and not args.no_extra:
+    if args.full and solo and not args.no_extra:
         tr = measure_traffic("cuboid_sweep_score", "pmc_run.py", [args.frames, args.boxes, args.yaw_step, BG_TEXTURE])
         if not args.no_cpu:
             native_oracle()  # the c3 / c4 CPU legs use the -march=native build too
@@ -862,7 +930,7 @@ def main():
     else:
         tr = None
     ba_out = None
-    if not args.no_ba:
+    if args.full and not args.no_ba:
         try:
             ba_out = ba_bench(ctx, rank, world, args.ba_iters, with_cpu=(solo and not args.no_cpu), with_traffic=solo and not args.no_extra)
         except Exception as e:  # (the BA block stands beside the headline: with world > 1 its in-library RCCL all-reduce runs for the first time on the driver's node -- a failure there must not cost the front-end's line)
@@ -878,7 +946,7 @@ def main():
         alg_bytes = 4.0 * st["roi_pixels"] + 200.0 * st["n_valid"]
         k_us = kernels["cuboid_sweep_score"]["avg_us"]
         achieved = alg_bytes / (k_us * 1e-6) / 1e9 if k_us > 0 else 0.0
-        iso_us = 1e3 * iso_ms / max(iso_n, 1)
+        iso_us = 1e3 * iso_ms / max(iso_n, 1) if args.full else None
         out = {
             "metric": "frames/sec front-end (%s%scuboid: Canny+DT+sweep+score+select) @640x480" % ("ORB extract + " if orb is not None else "", "LSD+LBD lines + " if lsd is not None else ""),
             "value": total_frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -887,9 +955,9 @@ def main():
             "config": {"workload": "front-end per frame: ORB extract + LSD/LBD lines + detect_3d_cuboid: 640x480 frames (3 drawn cuboids over a 1/f texture, amplitude %.2f) x %d boxes, "
                                    "180-yaw x 3-VP sweep (yaw step %.2f deg), %d frames resident per GPU; detect_cuboid is fed the scene's own edge list (cuboid edges + 40 clutter "
                                    "segments), not this step's LSD output (decoupled, SURVEY 8d C2)" % (BG_TEXTURE, args.boxes, args.yaw_step, args.frames),
-                       "lines": None if lsd is None else {"keylines_per_step": n_lines, "keylines_per_frame": n_lines / args.frames, "descriptor": "LBD 32 B", "detectors_in_flight": len(ctx_lines), "runner": "phased" if args.phased else "alternating",
+                       "lines": None if lsd is None else {"keylines_per_step": n_lines, "keylines_per_frame": None if n_lines is None else n_lines / args.frames, "descriptor": "LBD 32 B", "detectors_in_flight": len(ctx_lines), "runner": "phased" if args.phased else "alternating",
                                                                 "region_stage": ("device: one wave per frame (lsd_rg_seq)" if lsd.region_stats()["device"] else "host: %d OpenMP threads" % _lib.lib().cs_host_thread_count())},
-                       "orb": None if orb is None else {"nfeatures": args.orb_features, "levels": 8, "keypoints_per_step": n_kp, "keypoints_per_frame": n_kp / args.frames},
+                       "orb": None if orb is None else {"nfeatures": args.orb_features, "levels": 8, "keypoints_per_step": n_kp, "keypoints_per_frame": None if n_kp is None else n_kp / args.frames},
                        "frames_per_gpu": args.frames, "boxes_per_frame": args.boxes,
                        "hypotheses_per_step": st["n_hypotheses"], "valid_proposals_per_step": st["n_valid"],
                        "roi_pixels_per_step": st["roi_pixels"], "score_kernels": ss, "parallelism": "frames sharded, no collective"},
@@ -908,7 +976,7 @@ def main():
                              "edge_scoring_stage_filter_plus_score": {"us": k_us + kernels["cuboid_sweep_filter"]["avg_us"],
                                                                       "frac": alg_bytes / ((k_us + kernels["cuboid_sweep_filter"]["avg_us"]) * 1e-6) / 1e9 / HBM_PEAK_GBS if k_us > 0 else None,
                                                                       "note": "the same bytes over cuboid_sweep_filter (reject tests of all hypotheses) + cuboid_sweep_score: everything between the distance transform and the selection"}},
-                         "isolated": {"avg_kernel_us": iso_us, "frac": (alg_bytes / (iso_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if iso_n else None, "threads_per_workgroup": 512,
+                         "isolated": None if not iso else {"avg_kernel_us": iso_us, "frac": (alg_bytes / (iso_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if iso_n else None, "threads_per_workgroup": 512,
                                       "note": "cuboid path alone on the GPU, the kernel in the shape it has when it owns the CUs (512 threads, 2 waves per SIMD)"},
                          "isolated_shared_shape": None if True not in iso else {"avg_kernel_us": 1e3 * iso[True][0] / max(iso[True][1], 1), "threads_per_workgroup": 256,
                                                                                   "frac": alg_bytes / (1e3 * iso[True][0] / max(iso[True][1], 1) * 1e-6) / 1e9 / HBM_PEAK_GBS,
@@ -933,7 +1001,7 @@ def main():
         out.update(extra)
         if variants is not None:
             out["runner_variants"] = variants
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             flags = native_oracle()
             cores = _lib.lib().cs_host_thread_count()
             out["cpu_baseline"] = cpu_baseline(scenes[:16], args.yaw_step, flags, with_orb=orb is not None, nfeat=args.orb_features, with_lines=lsd is not None)
@@ -948,6 +1016,8 @@ def main():
                 out["cpu_baseline_ref"] = rb
         if ba_out is not None:
             out["ba"] = ba_out
+        if dumped is not None:
+            out["outputs"] = dumped
         print(json.dumps(out))
     batch.close()
     if world > 1:

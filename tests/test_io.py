@@ -7,8 +7,8 @@ import pytest
 
 from cube_slam_amd import io as cio
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DATA = os.path.join(ROOT, "tests", "golden", "ref_data")
 
 
 def test_number_matrix_semantics(tmp_path):
@@ -49,15 +49,16 @@ def test_edge_round_trip_and_poses(tmp_path):
     assert T[2, 2] < -0.6  # camera looks down (pitch about the x axis)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_reference_data_files():
-    e = cio.read_edge_txt(os.path.join(REF, "detect_3d_cuboid/data/edge_detection/LSD/0000_edge.txt"))
+    """The reference's own data files, stored unchanged under tests/golden/ref_data/ (detect_3d_cuboid/data/edge_detection/LSD/0000_edge.txt,
+    object_slam/data/filter_2d_obj_txts/0000_yolo2_0.15.txt, object_slam/data/pop_cam_poses_saved.txt, object_slam/data/detect_cuboids_saved.txt)."""
+    e = cio.read_edge_txt(os.path.join(DATA, "0000_edge.txt"))
     assert e.shape == (271, 4) and np.isclose(e[0, 0], 467.435)
-    b = cio.read_yolo_boxes(os.path.join(REF, "object_slam/data/filter_2d_obj_txts/0000_yolo2_0.15.txt"))
+    b = cio.read_yolo_boxes(os.path.join(DATA, "0000_yolo2_0.15.txt"))
     assert b.shape[1] == 5 and b[0, 0] == 174
-    poses = cio.read_cam_poses(os.path.join(REF, "object_slam/data/pop_cam_poses_saved.txt"))
+    poses = cio.read_cam_poses(os.path.join(DATA, "pop_cam_poses_saved.txt"))
     assert poses.shape[1] == 8 and len(poses) >= 50
-    cub = cio.read_all_number_txt(os.path.join(REF, "object_slam/data/detect_cuboids_saved.txt"), cols=9)
+    cub = cio.read_all_number_txt(os.path.join(DATA, "detect_cuboids_saved.txt"), cols=9)
     assert cub.shape == (51, 9)
 
 

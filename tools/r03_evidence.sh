@@ -8,7 +8,7 @@ out=$R/gpurun_out/$tag
 mkdir -p $out
 cd /tmp
 # 1. the bench command with every block (nested rocprofv3 --pmc passes of the bench are switched off under the tracer)
-CUBESLAM_BENCH_NO_TRAFFIC=1 rocprofv3 --kernel-trace --stats -d /tmp/prof_${tag}_full -o res -- python $R/bench.py --steps 8 --warmup 2 --no-cpu > $out/bench_full.json 2> $out/bench_full.err
+CUBESLAM_BENCH_NO_TRAFFIC=1 rocprofv3 --kernel-trace --stats -d /tmp/prof_${tag}_full -o res -- python $R/bench.py --steps 8 --warmup 2 --no-cpu --full > $out/bench_full.json 2> $out/bench_full.err
 python $R/tools/rocpd_summary.py $(find /tmp/prof_${tag}_full -name "*.db" | head -1) > $out/full_kernel_stats.csv
 # 2. matcher + pose-only optimisation at config-3 size (tests/test_match_gpu.py, test_pose_gpu.py are the only callers at that size)
 rocprofv3 --kernel-trace --stats -d /tmp/prof_${tag}_mp -o res -- python -m pytest -q -x -m gpu $R/tests/test_match_gpu.py $R/tests/test_pose_gpu.py > $out/match_pose.log 2>&1

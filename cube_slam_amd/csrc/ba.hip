@@ -7,9 +7,10 @@
 // (thread per landmark, wave per pose block / Schur block with shuffle trees), no floating-point atomics.
 //
 //   ba_err_*          computeActiveErrors: reprojection / cuboid bbox / point-in-cuboid residuals + robust chi2 partials
-//   ba_lin_lm         thread per landmark: analytic 2x3 / 2x6 Jacobians of its observations, Hll, bl, Hpl blocks
-//   ba_lin_pose       wave per pose block: sum_obs Jj^T W Jj and Jj^T W r (lane = observation, shuffle-tree reduce)
-//   ba_num_cols       thread per (cuboid edge, perturbed dimension): central difference with delta 1e-9 through the same
+//   ba_build_abc      one grid of three parts that read nothing of each other:
+//     _lin_lm_body    thread per landmark: analytic 2x3 / 2x6 Jacobians of its observations, Hll, bl, Hpl blocks
+//     _lin_pose_body  wave per pose block: sum_obs Jj^T W Jj and Jj^T W r (lane = observation, shuffle-tree reduce)
+//     _num_cols_body  thread per (cuboid edge, perturbed dimension): central difference with delta 1e-9 through the same
 //                     oplus (exp map, exptwist_norollpitch) as g2o's numeric linearizeOplus
 //   ba_lin_pose_edges lane per element of a pose block: camera-cuboid and point-cuboid terms into Hpp / b
 //   ba_lm_dinv        thread per landmark: (Hll + lambda I)^-1 and D^-1 b_l
@@ -183,7 +184,6 @@ __device__ __forceinline__ void ba_lin_lm_body(const Params &G, const int bid) {
     for (int k = 0; k < 9; k++) G.Hll[(long)li * 9 + k] = H[k];
     for (int k = 0; k < 3; k++) G.bl[(long)li * 3 + k] = b[k];
 }
-__global__ void __launch_bounds__(256) ba_lin_lm(Params G) { ba_lin_lm_body(G, (int)blockIdx.x); }
 
 // workgroup per pose block (four waves share the camera's observation list: a thousand single waves leave the SIMDs one wave deep and the
 // Jacobian chain exposed): observations of this rank that involve the camera (CSR pose_off / pose_obs); wave sums by shuffles, then in wave order
@@ -213,7 +213,6 @@ __device__ __forceinline__ void ba_lin_pose_body(const Params &G, const int *pos
         if (k < 36) G.Hpp[(long)pi * 36 + k] = v; else G.bp[(long)pi * 6 + k - 36] = v;
     }
 }
-__global__ void __launch_bounds__(256) ba_lin_pose(Params G, const int *pose_off, const int *pose_obs) { ba_lin_pose_body(G, pose_off, pose_obs, (int)blockIdx.x); }
 
 // numeric Jacobian columns (base_binary_edge.hpp:216-320, base_unary_edge.hpp:82-123): delta = 1e-9, central difference.  A lane per (edge, column,
 // SIGN): the even lane evaluates the error at +delta, its odd neighbour at -delta (the two evaluations are the whole cost: se3 exponential, cuboid
@@ -251,7 +250,6 @@ __device__ __forceinline__ void ba_num_cols_body(const Params &G, const int bid)
     if (kind == 1) for (int k = 0; k < 4; k++) G.Jc[((long)o * 12 + d) * 4 + k] = scalar * (ev[k] - em[k]);
     else if (kind == 2) for (int k = 0; k < 3; k++) G.Jp[((long)o * 6 + d) * 3 + k] = scalar * (ev[k] - em[k]);
 }
-__global__ void __launch_bounds__(256) ba_num_cols(Params G) { ba_num_cols_body(G, (int)blockIdx.x); }
 // The three launches of buildSystem that read nothing of each other, as ONE grid: workgroups [0, n_pose) are ba_lin_pose's, the next n_cols ba_num_cols', the rest
 // ba_lin_lm's (the longest first).  At 1 000 key frames each of them fills part of the chip for 30 - 65 us; in a row they were 141 us, side by side they are the longest
 // of them.  (Two more streams with event joins were measured first: a join costs more than the kernels it orders, 1 040 -> 544 it/s.)
@@ -1475,13 +1473,7 @@ static int ba_build_system(cs_ctx *ctx, cs_ba *b) { // BlockSolver::buildSystem
     const int nl = G.lm_e - G.lm_b;
     const bool edges = G.pose_edges && G.n_cobs + G.n_pc > 0;
     const int n_pose = G.P, n_cols = edges ? (2 * (G.n_cobs * 12 + G.n_pc * 6) + 255) / 256 : 0, n_lm = (nl + 255) / 256;
-    static const bool fused = !(getenv("CUBESLAM_BA_FUSED") && atoi(getenv("CUBESLAM_BA_FUSED")) == 0); // (0: a launch per kernel, the cross-check)
-    if (fused && n_pose + n_cols + n_lm > 0) CS_LAUNCH(ctx, "ba_build_abc", ba_build_abc, dim3(n_pose + n_cols + n_lm), dim3(256), 0, G, b->d_pose_off, b->d_pose_obs, n_pose, n_cols);
-    else {
-        if (nl > 0) CS_LAUNCH(ctx, "ba_lin_lm", ba_lin_lm, dim3(n_lm), dim3(256), 0, G);
-        if (G.P > 0) CS_LAUNCH(ctx, "ba_lin_pose", ba_lin_pose, dim3(G.P), dim3(256), 0, G, b->d_pose_off, b->d_pose_obs);
-        if (edges) CS_LAUNCH(ctx, "ba_num_cols", ba_num_cols, dim3(n_cols), dim3(256), 0, G); // a lane per (edge, column, sign)
-    }
+    if (n_pose + n_cols + n_lm > 0) CS_LAUNCH(ctx, "ba_build_abc", ba_build_abc, dim3(n_pose + n_cols + n_lm), dim3(256), 0, G, b->d_pose_off, b->d_pose_obs, n_pose, n_cols);
     if (edges) CS_LAUNCH(ctx, "ba_lin_pose_edges", ba_lin_pose_edges, dim3((G.P + G.n_cobs + 3) / 4), dim3(256), 0, G, b->d_pe_off, b->d_pe_list); // a wave per pose block / per camera-cuboid edge: adds to what ba_lin_pose left
     return CS_OK;
 }

@@ -17,7 +17,7 @@
 // Cholesky factor and G^-1 applied to everything right of it.  One broadcast LDS read per multiply-add, one barrier per pivot.  The three
 // NB x NB products run on the matrix cores (v_mfma_f64_16x16x4_f64 tiles over the scaled panel staged in LDS).  A block reads its
 // diagonal as the assembled D minus every update earlier levels left for it (two per level), so there is no separate "apply" pass:
-// levels + 1 launches forward, levels + 1 back.
+// levels + 1 launches forward, one back (ba_cr_back_chain).
 #include "ba_cr.h"
 
 #include <algorithm>
@@ -36,7 +36,6 @@ struct CrView { // device buffers; every per-node array is indexed by the super-
     const double *zero, *one;   // a 0.0 and a 1.0 in device memory (branch-free panel loads)
     int *status;
     int *done; int epoch;    // the chained way back: done[i] == epoch once x of node i is in memory (this solve)
-    unsigned long long *dbg; // CUBESLAM_CR_PROF: wall-clock stamps of block 0 at the phase boundaries of every level (100 MHz)
 };
 
 __global__ void __launch_bounds__(256) ba_cr_assemble(CrView W) {
@@ -78,7 +77,6 @@ template <int BC> __global__ void __launch_bounds__(256) ba_cr_eliminate(CrView 
     const int tid = threadIdx.x, nb2 = NB * NB, tc = tid & (TC - 1), tr = tid / TC;
     const int step = 1 << level, i = root ? 0 : step * (2 * (int)blockIdx.x + 1);
     const int a = root ? -1 : i - step, b = (root || i + step >= W.M) ? -1 : i + step;
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 0] = wall_clock64();
     // ---- this thread's elements of the panel [D | L | R^T | r | I] (NB rows): every global read runs along a row
     double P[RPT][CPT];
     // every element is  s1 * p1[o1] - p2[o2] - p3[o3]  with the pointers chosen per region and aimed at a zero word where a term is absent:
@@ -106,12 +104,18 @@ template <int BC> __global__ void __launch_bounds__(256) ba_cr_eliminate(CrView 
             p1[ri][ci] = q1; p2[ri][ci] = q2; p3[ri][ci] = q3; s1[ri][ci] = sg;
         }
     }
+    double x1[RPT][CPT], x2[RPT][CPT], x3[RPT][CPT];
 #pragma unroll
     for (int ri = 0; ri < RPT; ri++)
 #pragma unroll
-        for (int ci = 0; ci < CPT; ci++) P[ri][ci] = s1[ri][ci] * *p1[ri][ci] - *p2[ri][ci] - *p3[ri][ci];
+        for (int ci = 0; ci < CPT; ci++) { x1[ri][ci] = *p1[ri][ci]; x2[ri][ci] = *p2[ri][ci]; x3[ri][ci] = *p3[ri][ci]; }
     __syncthreads();
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 1] = wall_clock64();
+    // the terms are combined behind the barrier, not waited for one by one in front of it (43.2 against 44.5 us a launch at Bc = 10)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ri = 0; ri < RPT; ri++)
+#pragma unroll
+        for (int ci = 0; ci < CPT; ci++) P[ri][ci] = s1[ri][ci] * x1[ri][ci] - x2[ri][ci] - x3[ri][ci];
     // ---- elimination (LDL^T, rows scaled afterwards): step k publishes row k and column k of the running Schur complement, one barrier, then the
     // rank-one update of every element below row k.  8 + 8 values read per thread and step for 64 multiply-adds.
     // Two pivots per barrier: rows / columns k and k+1 are published as they stand before step k; every thread derives row k+1 and column k+1
@@ -156,7 +160,6 @@ template <int BC> __global__ void __launch_bounds__(256) ba_cr_eliminate(CrView 
         }
     }
     if (fail && tid == 0) *W.status = 1;
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 2] = wall_clock64();
     // ---- scale the rows by 1 / sqrt(pivot): [G^T | Xa | Xb | y | Ginv]; stage Xa, Xb, y in LDS for the products; Ginv and y go out (streaming stores:
     // only the way back reads them)
     for (int t = tid; t < NBP * LDW; t += NT) Wx[t] = 0.0;
@@ -180,14 +183,12 @@ template <int BC> __global__ void __launch_bounds__(256) ba_cr_eliminate(CrView 
         }
     }
     __syncthreads();
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 3] = wall_clock64();
     if (root) return;
     // ---- the way back reads Xa, Xb by columns: stored transposed ([c][k]), coalesced, from the staged copy
     for (int t = tid; t < 2 * nb2; t += NT) {
         const int m = t >= nb2, e = t - m * nb2, c = e / NB, k = e - c * NB;
         __builtin_nontemporal_store(Wx[k * LDW + m * NBP + c], &(m ? W.XbT : W.XaT)[(long)i * nb2 + e]);
     }
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 4] = wall_clock64();
     // ---- r_a -= Xa^T y, r_b -= Xb^T y (accumulated: one producer per array, target and level)
     if (tid < 2 * NB) {
         const int m = tid >= NB, c = tid - m * NB, tgt = m ? b : a;
@@ -200,7 +201,6 @@ template <int BC> __global__ void __launch_bounds__(256) ba_cr_eliminate(CrView 
             *dst = was + (v + v2);
         }
     }
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 5] = wall_clock64();
     // ---- D_a -= Xa^T Xa, D_b -= Xb^T Xb (accumulated in accL[a] / accR[b]), V = Xb^T Xa (and its transpose) on the matrix cores: 16x16 tiles, K = NBP
     // A operand: lane l holds A[row = l & 15][k = l >> 4]; B operand: B[k = l >> 4][col = l & 15]; result reg g: row = (l >> 4) + 4 g, col = l & 15
     constexpr int TL = NBP / 16, NTILE = 3 * TL * TL, NW = NT / 64, TPW = (NTILE + NW - 1) / NW;
@@ -236,37 +236,9 @@ template <int BC> __global__ void __launch_bounds__(256) ba_cr_eliminate(CrView 
         }
     }
     __syncthreads();
-    if (W.dbg && blockIdx.x == 0 && tid == 0) W.dbg[(root ? 31 : level) * 8 + 6] = wall_clock64();
 }
 
-// x_i = Ginv^T (y - Xa x_a - Xb x_b) for the nodes eliminated at `level` (root: node 0).  Everything that does not depend on the neighbours'
-// solutions is requested first.
-template <int BC> __global__ void __launch_bounds__(64 * ((6 * BC + 63) / 64)) ba_cr_back(CrView W, int level, int root) {
-    constexpr int NB = 6 * BC;
-    __shared__ double tv[NB], xn[2 * NB];
-    const int tid = threadIdx.x, nb2 = NB * NB;
-    const int step = 1 << level, i = root ? 0 : step * (2 * (int)blockIdx.x + 1);
-    const int a = root ? -1 : i - step, b = (root || i + step >= W.M) ? -1 : i + step;
-    const int t = min(tid, NB - 1);
-    double xa_col[NB], xb_col[NB], g_col[NB];
-    const double *XA = W.XaT + (long)i * nb2 + t, *XB = W.XbT + (long)i * nb2 + t, *G = W.Ginv + (long)i * nb2 + t;
-    const double y = W.y[(long)i * NB + t];
-#pragma unroll
-    for (int c = 0; c < NB; c++) { xa_col[c] = a >= 0 ? XA[c * NB] : 0.0; xb_col[c] = b >= 0 ? XB[c * NB] : 0.0; g_col[c] = c >= t ? G[(long)c * NB] : 0.0; }
-    if (tid < NB) { xn[tid] = a >= 0 ? W.x[(long)a * NB + tid] : 0.0; xn[NB + tid] = b >= 0 ? W.x[(long)b * NB + tid] : 0.0; }
-    __syncthreads();
-    double v = y, v2 = 0;
-#pragma unroll
-    for (int c = 0; c < NB; c++) { v -= xa_col[c] * xn[c]; v2 -= xb_col[c] * xn[NB + c]; }
-    if (tid < NB) tv[tid] = v + v2;
-    __syncthreads();
-    double x0 = 0, x1 = 0;
-#pragma unroll
-    for (int k = 0; k < NB; k += 2) { x0 += g_col[k] * tv[k]; x1 += g_col[k + 1] * tv[k + 1]; } // Ginv is lower triangular (zeros loaded above the diagonal)
-    if (tid < NB) W.x[(long)i * NB + tid] = x0 + x1;
-}
-
-// The whole way back as ONE launch: a workgroup per node, in dependency order (root, then the levels from the top: a node's two neighbours were eliminated later
+// The way back, x_i = Ginv^T (y - Xa x_a - Xb x_b), as ONE launch: a workgroup per node, in dependency order (root, then the levels from the top: a node's two neighbours were eliminated later
 // than it, so their workgroups have smaller indices and never wait for a larger one -- no deadlock whatever the GPU holds at a time).  A node requests everything
 // of its own first, then waits for done[a] / done[b] to show this solve's epoch, reads the neighbours' solutions past the caches (another XCD's L2 may have
 // written them), and publishes its own behind an agent-scope fence.  Nine dependent launches of ~11 us become one whose levels cost a flag round trip each.
@@ -345,16 +317,7 @@ template <int BC> int cr_run(cs_ctx *ctx, const CrView &W) {
     }
     CS_LAUNCH(ctx, "ba_cr_eliminate", ba_cr_eliminate<BC>, dim3(1), dim3(NT), lds, W, levels, 1);
     constexpr int BT = 64 * ((NB + 63) / 64);
-    static const bool chain = !(getenv("CUBESLAM_CR_CHAIN") && atoi(getenv("CUBESLAM_CR_CHAIN")) == 0);
-    if (chain) { // (CUBESLAM_CR_CHAIN=0: a launch per level, the cross-check)
-        CS_LAUNCH(ctx, "ba_cr_back", ba_cr_back_chain<BC>, dim3(W.M), dim3(BT), 0, W, levels);
-        return CS_OK;
-    }
-    CS_LAUNCH(ctx, "ba_cr_back", ba_cr_back<BC>, dim3(1), dim3(BT), 0, W, levels, 1);
-    for (int l = levels - 1; l >= 0; l--) {
-        const int step = 1 << l, n = (W.M - step + 2 * step - 1) / (2 * step);
-        if (n > 0) CS_LAUNCH(ctx, "ba_cr_back", ba_cr_back<BC>, dim3(n), dim3(BT), 0, W, l, 0);
-    }
+    CS_LAUNCH(ctx, "ba_cr_back", ba_cr_back_chain<BC>, dim3(W.M), dim3(BT), 0, W, levels);
     return CS_OK;
 }
 } // namespace
@@ -402,11 +365,6 @@ int ba_cr_solve(cs_ctx *ctx, BaCr **handle, int C, int Bc, const double *d_bandA
     V.D = p; p += nb2 * M; V.E = p; p += nb2 * M; V.ET = p; p += nb2 * M; V.VT = p; p += nb2 * M; V.Ginv = p; p += nb2 * M; V.XaT = p; p += nb2 * M; V.XbT = p; p += nb2 * M; V.V = p; p += nb2 * M;
     V.r = p; p += (size_t)NB * M; V.y = p; p += (size_t)NB * M; V.x = p;
     CS_HIP(ctx, hipMemsetAsync(w->buf, 0, zero_bytes, ctx->stream));
-    static unsigned long long *d_dbg = nullptr;
-    const bool prof = getenv("CUBESLAM_CR_PROF") != nullptr;
-    if (prof && !d_dbg) { hipMalloc((void **)&d_dbg, 32 * 8 * sizeof(unsigned long long)); }
-    if (prof) hipMemsetAsync(d_dbg, 0, 32 * 8 * sizeof(unsigned long long), ctx->stream);
-    V.dbg = prof ? d_dbg : nullptr;
     V.zero = V.accrR; // (zeroed above; the first entry belongs to node 0, which has no left neighbour and is never written)
     V.one = p + (size_t)NB * M;
     { static const double one = 1.0; CS_HIP(ctx, hipMemcpyAsync((void *)V.one, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream)); }
@@ -421,10 +379,5 @@ int ba_cr_solve(cs_ctx *ctx, BaCr **handle, int C, int Bc, const double *d_bandA
     }
     if (rc) return rc;
     CS_HIP(ctx, hipMemcpyAsync(d_x, V.x, sizeof(double) * (size_t)C * 6, hipMemcpyDeviceToDevice, ctx->stream));
-    if (prof) {
-        unsigned long long h[32 * 8];
-        hipMemcpy(h, d_dbg, sizeof h, hipMemcpyDeviceToHost);
-        for (int l = 0; l < 32; l++) if (h[l * 8]) { fprintf(stderr, "[cr prof] level %2d:", l); for (int q = 1; q < 7; q++) fprintf(stderr, " %6.2f", h[l * 8 + q] ? (h[l * 8 + q] - h[l * 8 + q - 1]) / 100.0 : 0.0); fprintf(stderr, " us (load, eliminate, scale+stage, transposed store, rhs, products)\n"); }
-    }
     return CS_OK;
 }

@@ -14,8 +14,7 @@
 //   badyn_chol_diag / badyn_chol_panel / badyn_chol_update / badyn_chol_tri   blocked right-looking Cholesky of S (32 columns per step:
 //                     one workgroup factors the 32x32 pivot block in LDS, the rows of the panel are solved against it one per thread, then
 //                     32x32 tiles of the trailing matrix are updated by independent workgroups), then one workgroup for both triangular solves (a single-workgroup
-//                     column-by-column version -- badyn_chol_solve, CUBESLAM_BADYN_CHOL=simple -- took 26 ms at 840 unknowns: every
-//                     trailing update waits for its own global load)
+//                     column-by-column version took 26 ms at 840 unknowns: every trailing update waits for its own global load)
 //   badyn_backsub     thread per landmark, badyn_update thread per vertex (oplus), badyn_diag gathers diag(H) for computeLambdaInit
 // The windows this runs on are small (10-30 key frames, a few object tracks): the pose system has a few hundred to a few thousand scalars,
 // so everything is latency-bound; the dense factorisation is the only super-linear step and stays on one CU.
@@ -32,7 +31,9 @@
 
 namespace {
 
-constexpr int DYN_MAX_NP = 4000; // two LDS vectors of NP doubles in badyn_chol_solve
+// the largest pose system accepted (the limit the C-ABI documents); badyn_chol_tri keeps NP doubles and a pivot block in LDS,
+// 40 KB at this bound, within the default 64 KB per workgroup
+constexpr int DYN_MAX_NP = 4000;
 
 __device__ inline void dyn_block_sum_store(double v, double *partials) {
     __shared__ double s[4];
@@ -137,48 +138,6 @@ __global__ void __launch_bounds__(256) badyn_diag(DynG G, double *diag) {
     if (i < G.NP) diag[i] = G.Hpp[(long)i * G.NP + i];
     else if (i < G.NP + 3 * G.L) { const int l = (i - G.NP) / 3, k = (i - G.NP) % 3; diag[i] = G.Hll[(long)l * 9 + k * 4]; }
 }
-
-// A (n x n, row-major, lower triangle used) -> L in place; x: right-hand side -> solution.  Column j is scaled into LDS, the trailing rows are
-// updated one row per wave (contiguous in k), and the forward substitution y_j = b_j / L_jj, b_i -= L_ij y_j rides on the same column; the
-// backward substitution walks the rows of L upwards: x_i = y_i / L_ii, y_k -= L_ik x_i (k < i).
-__global__ void __launch_bounds__(1024) badyn_chol_solve(int n, double *A, double *x, int *status) {
-    extern __shared__ double lds[];
-    double *col = lds, *rhs = lds + n;
-    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
-    for (int i = tid; i < n; i += T) rhs[i] = x[i];
-    __syncthreads();
-    for (int j = 0; j < n; j++) {
-        const double d = A[(long)j * n + j];
-        if (!(d > 0)) { if (tid == 0) *status = 1; return; } // uniform: every thread reads the same pivot
-        const double r = sqrt(d);
-        for (int i = j + tid; i < n; i += T) {
-            const double v = (i == j) ? r : A[(long)i * n + j] / r;
-            A[(long)i * n + j] = v;
-            col[i] = v;
-        }
-        __syncthreads();
-        const double yj = rhs[j] / r;
-        for (int i = j + 1 + wave; i < n; i += nw) {
-            const double lij = col[i];
-            double *row = A + (long)i * n;
-            for (int k = j + 1 + lane; k <= i; k += 64) row[k] -= lij * col[k];
-            if (lane == 0) rhs[i] -= lij * yj;
-        }
-        __syncthreads();
-        if (tid == 0) rhs[j] = yj;
-    }
-    __syncthreads();
-    for (int i = n - 1; i >= 0; i--) {
-        const double *row = A + (long)i * n;
-        const double xi = rhs[i] / row[i];
-        __syncthreads();
-        for (int k = tid; k < i; k += T) rhs[k] -= row[k] * xi;
-        if (tid == 0) rhs[i] = xi;
-        __syncthreads();
-    }
-    for (int i = tid; i < n; i += T) x[i] = rhs[i];
-}
-
 
 // ---- blocked Cholesky: A (n x n row-major, lower triangle) -> strictly-lower panels in place, pivot blocks in Dg (one 32x32 row-major
 // block per step, the upper part zero).
@@ -321,7 +280,7 @@ struct cs_ba_dyn {
     DynG G;
     const volatile unsigned char *stop8 = nullptr; // the caller's bool (setForceStopFlag)
     std::vector<void *> bufs;
-    int n_edges = 0, n_vertices = 0, max_part = 0, n_slots = 0, simple_chol = 0;
+    int n_edges = 0, n_vertices = 0, max_part = 0, n_slots = 0;
     double *d_Dg = nullptr, *d_rd = nullptr;
     size_t state_doubles = 0;
     double *d_state = nullptr, *d_bak = nullptr, *d_partials = nullptr, *d_diag = nullptr;
@@ -388,18 +347,14 @@ int dyn_solve(cs_ctx *ctx, cs_ba_dyn *b, double lambda) { // BlockSolver::solve:
     if (r) return r;
     if (G.NP > 0) {
         CS_HIP(ctx, hipMemcpyAsync(G.xp, G.bs, sizeof(double) * G.NP, hipMemcpyDeviceToDevice, ctx->stream));
-        if (b->simple_chol) {
-            CS_LAUNCH(ctx, "badyn_chol_solve", badyn_chol_solve, dim3(1), dim3(1024), sizeof(double) * 2 * (size_t)G.NP, G.NP, G.S, G.xp, b->d_status);
-        } else {
-            const int n = G.NP;
-            for (int jb = 0; jb < n; jb += CB) {
-                const int nb = std::min(CB, n - jb), m = n - jb - nb; // rows behind the panel
-                CS_LAUNCH(ctx, "badyn_chol_diag", badyn_chol_diag, dim3(1), dim3(CB * CB), 0, n, jb, G.S, b->d_Dg, b->d_rd, b->d_status);
-                if (m > 0) CS_LAUNCH(ctx, "badyn_chol_panel", badyn_chol_panel, dim3((m + CP_T - 1) / CP_T), dim3(CP_T), 0, n, jb, G.S, b->d_Dg, b->d_rd);
-                if (m > 0) { const int T = (m + CB - 1) / CB; CS_LAUNCH(ctx, "badyn_chol_update", badyn_chol_update, dim3(T, T), dim3(256), 0, n, jb, G.S); }
-            }
-            CS_LAUNCH(ctx, "badyn_chol_tri", badyn_chol_tri, dim3(1), dim3(1024), sizeof(double) * ((size_t)n + CB * (CB + 1)), n, G.S, b->d_Dg, G.xp);
+        const int n = G.NP;
+        for (int jb = 0; jb < n; jb += CB) {
+            const int nb = std::min(CB, n - jb), m = n - jb - nb; // rows behind the panel
+            CS_LAUNCH(ctx, "badyn_chol_diag", badyn_chol_diag, dim3(1), dim3(CB * CB), 0, n, jb, G.S, b->d_Dg, b->d_rd, b->d_status);
+            if (m > 0) CS_LAUNCH(ctx, "badyn_chol_panel", badyn_chol_panel, dim3((m + CP_T - 1) / CP_T), dim3(CP_T), 0, n, jb, G.S, b->d_Dg, b->d_rd);
+            if (m > 0) { const int T = (m + CB - 1) / CB; CS_LAUNCH(ctx, "badyn_chol_update", badyn_chol_update, dim3(T, T), dim3(256), 0, n, jb, G.S); }
         }
+        CS_LAUNCH(ctx, "badyn_chol_tri", badyn_chol_tri, dim3(1), dim3(1024), sizeof(double) * ((size_t)n + CB * (CB + 1)), n, G.S, b->d_Dg, G.xp);
     }
     if (G.L > 0) CS_LAUNCH(ctx, "badyn_backsub", badyn_backsub, dim3((G.L + 63) / 64), dim3(64), 0, G);
     return CS_OK;
@@ -449,7 +404,6 @@ int cs_ba_dyn_create(cs_ctx *ctx, const cs_ba_dyn_problem *p, cs_ba_dyn **out) {
     G.NP = NP; G.L = X.L;
     const int n_slots = b->n_slots = X.n_slots;
     G.n_blocks = (int)X.blk_ou.size(); G.n_vtx = (int)X.vtx_off.size();
-    { const char *ce = getenv("CUBESLAM_BADYN_CHOL"); b->simple_chol = ce && !strcmp(ce, "simple"); }
     b->n_edges = p->n_obs + p->n_dobs + p->n_mot + p->n_cobs + p->n_pc + p->n_dpoints;
     b->n_vertices = p->n_cams + p->n_objs + p->n_vels + p->n_points + p->n_dpoints;
     b->max_part = std::max(1, (b->n_edges + 255) / 256);
@@ -515,10 +469,6 @@ int cs_ba_dyn_create(cs_ctx *ctx, const cs_ba_dyn_problem *p, cs_ba_dyn **out) {
     D_(dyn_upload(ctx, b, &b->d_diag, (const double *)nullptr, (size_t)NP + 3 * (size_t)G.L));
     D_(dyn_upload(ctx, b, &b->d_status, (const int *)nullptr, 1));
 #undef D_
-    if (2 * (size_t)NP * sizeof(double) > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(badyn_chol_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * (size_t)NP * sizeof(double)));
-        if (e != hipSuccess) { ctx->err = hipGetErrorString(e); cs_ba_dyn_destroy(ctx, b); return CS_ERR_HIP; }
-    }
     hipError_t e = hipStreamSynchronize(ctx->stream); // the host vectors above go out of scope
     if (e != hipSuccess) { ctx->err = hipGetErrorString(e); cs_ba_dyn_destroy(ctx, b); return CS_ERR_HIP; }
     *out = b;

@@ -1259,11 +1259,8 @@ template <int CFG, bool HYB, bool LEAN> __device__ __forceinline__ void sc_score
 // registers and the whole LDS -- the score kernel of the alternating runner, where region walks hold most CUs all the time.
 template <int NT>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 256 ? 4 : 1, NT == 256 ? 4 : 8))) cuboid_sweep_score(const Unit *units, const int *order, int n_items, int n_slices, int *cursor, const VPEntry *vpt, const float *dist,
-                                                         const int *vcount, const int *vlist, int *uflag, double *derr, double *aerr, unsigned long long *prof) {
+                                                         const int *vcount, const int *vlist, int *uflag, double *derr, double *aerr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sc_mem[];
-    // (development, CUBESLAM_SCORE_PROF) wall-clock ticks of this wave in the three parts of a unit: copy + encode, scoring tasks, waiting at the barriers
-    unsigned long long t_copy = 0, t_task = 0, t_wait = 0, t_mark = prof ? wall_clock64() : 0, n_task = 0;
-    auto lap = [&](unsigned long long &acc) { if (prof) { const unsigned long long t = wall_clock64(); acc += t - t_mark; t_mark = t; } };
     int *ctrl = reinterpret_cast<int *>(sc_mem); // control words, see the loop
     unsigned short *lut = reinterpret_cast<unsigned short *>(sc_mem + SC_CTRL_BYTES);
     unsigned short *lmap = reinterpret_cast<unsigned short *>(sc_mem + SC_MAP_OFF);
@@ -1327,9 +1324,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
             if (fits) for (int k = 8 * A8 + tid; k < A + max(U.roi_w + 2, 8); k += NT) lmap[k] = (unsigned short)lastc;
             if (esc) atomicOr(&ctrl[2 + (it & 1)], 1);
         }
-        lap(t_copy);
         __syncthreads();
-        lap(t_wait);
         const int next = __builtin_amdgcn_readfirstlane(ctrl[4 + (it & 1)]);
         const bool escape = __builtin_amdgcn_readfirstlane(ctrl[2 + (it & 1)]) != 0; // a pixel without a code: the whole unit samples the float map
         if (work) {
@@ -1345,7 +1340,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
                 if (lane == 0) t = atomicAdd(&ctrl[0], n_slices);
                 t = __builtin_amdgcn_readfirstlane(t);
                 if (t >= nt) break;
-                n_task++;
                 if (!hyb) {
                     if (t < n1) sc_score_task<1, false, LEAN>(U, t << 6, c1, lane, vpt, vlist, lmap, gdist, n_res, derr, aerr);
                     else sc_score_task<2, false, LEAN>(U, (t - n1) << 6, c2, lane, vpt, vlist, lmap, gdist, n_res, derr, aerr);
@@ -1354,13 +1348,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
                     else sc_score_task<2, true, LEAN>(U, (t - n1) << 6, c2, lane, vpt, vlist, lmap, gdist, n_res, derr, aerr);
                 }
             }
-            lap(t_task);
             __syncthreads(); // every wave is done with this unit's map
-            lap(t_wait);
         }
         item = next;
     }
-    if (prof && lane == 0) { unsigned long long *o = prof + ((size_t)blockIdx.x * (NT / 64) + (tid >> 6)) * 4; o[0] = t_copy; o[1] = t_task; o[2] = t_wait; o[3] = n_task; }
 }
 
 // ------------------------------------------------------------------------------------------------ selection
@@ -1819,7 +1810,6 @@ struct cs_cuboid_batch {
     int *d_dttmp = nullptr; long *d_dttmp_off = nullptr;
     int *d_order = nullptr, *d_cursor = nullptr; // cuboid_sweep_score: units by falling cost estimate, the work cursor
     int *d_uflag = nullptr;                      // per unit: 1 = a pixel without a 16-bit code (scored from the float map)
-    unsigned long long *d_prof = nullptr;        // CUBESLAM_SCORE_PROF: per wave {copy, tasks, barrier wait} ticks and task count of the last launch
     int score_G = 256;      // workgroups of cuboid_sweep_score (one per CU)
     int score_T = 512;      // threads per workgroup (CUBESLAM_SCORE_THREADS = 256 | 512 | 768 | 1024: 1 / 2 / 3 / 4 waves per SIMD with 128 / 256 / 168 / 128 registers)
     bool score_T_forced = false; // set by the environment: cs_cuboid_batch_set_shared_gpu leaves it alone
@@ -1969,7 +1959,7 @@ void cs_cuboid_batch_destroy(cs_ctx *ctx, cs_cuboid_batch *b) {
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
     void *ptrs[] = {b->d_gray, b->d_emap, b->d_flag, b->d_dist, b->d_dttmp, b->d_dttmp_off, b->d_fi, b->d_fd, b->d_cam, b->d_yaw, b->d_lines_in, b->d_lines_al,
                     b->d_mlines, b->d_mangle, b->d_mmid, b->d_units, b->d_ud, b->d_box_first, b->d_status, b->d_counts, b->d_carry, b->d_vp,
-                    b->d_derr, b->d_aerr, b->d_score, b->d_nscore, b->d_ckd, b->d_cka, b->d_cidx, b->d_out, b->d_vcount, b->d_vlist, b->d_order, b->d_cursor, b->d_uflag, b->d_prof, b->d_wgmap};
+                    b->d_derr, b->d_aerr, b->d_score, b->d_nscore, b->d_ckd, b->d_cka, b->d_cidx, b->d_out, b->d_vcount, b->d_vlist, b->d_order, b->d_cursor, b->d_uflag, b->d_wgmap};
     for (void *p : ptrs) cs_dfree(ctx, p);
     for (int k = 0; k < 2; k++) { if (b->h_stage[k]) hipHostFree(b->h_stage[k]); if (b->stage_ev[k]) hipEventDestroy(b->stage_ev[k]); }
     if (b->ev_fork) hipEventDestroy(b->ev_fork);
@@ -2048,7 +2038,6 @@ int cs_cuboid_batch_create(cs_ctx *ctx, int n_frames, int width, int height, con
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the two vectors are locals)
         A_(cs_dalloc(ctx, &b->d_cursor, (size_t)1));
         A_(cs_dalloc(ctx, &b->d_uflag, (size_t)std::max(1, b->n_units)));
-        if (getenv("CUBESLAM_SCORE_PROF")) A_(cs_dalloc(ctx, &b->d_prof, (size_t)b->score_G * 16 * 4));
     }
     A_(cs_dalloc(ctx, &b->d_dist, (size_t)b->pix_total));
     CS_HIP(ctx, hipMemsetAsync(b->d_dist, 0, sizeof(float) * (size_t)b->pix_total, ctx->stream)); // the slices' padding (to 64 pixels) stays zero: cuboid_sweep_score encodes whole groups of 8
@@ -2296,16 +2285,16 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
         const int items = U * b->score_slices, grid = std::min(b->score_G, items);
         if (b->score_T == 256)
             CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<256>, dim3(grid), dim3(256), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr, b->d_prof);
+                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
         else if (b->score_T == 512)
             CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<512>, dim3(grid), dim3(512), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr, b->d_prof);
+                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
         else if (b->score_T == 768)
             CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<768>, dim3(grid), dim3(768), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr, b->d_prof);
+                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
         else
             CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<1024>, dim3(grid), dim3(1024), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr, b->d_prof);
+                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
     }
     CS_LAUNCH(ctx, "cuboid_select", cuboid_select, dim3(b->n_boxes), dim3(256), 0, b->d_units, b->d_ud, b->d_box_first, b->d_fd, b->d_fi,
               b->d_cam, b->d_yaw, b->cal, b->o, b->d_flag, b->d_derr, b->d_aerr, b->d_vp, b->d_score, b->d_nscore,
@@ -2359,17 +2348,6 @@ int cs_cuboid_batch_stats(cs_ctx *ctx, cs_cuboid_batch *b, long *n_units, long *
 
 int cs_cuboid_batch_score_stats(cs_ctx *ctx, cs_cuboid_batch *b, long out[6]) {
     if (!ctx || !b || !out) return CS_ERR_BAD_ARG;
-    if (b->d_prof) { // (development) where the waves of the last cuboid_sweep_score launch spent their time
-        const int grid = std::min(b->score_G, b->n_units * b->score_slices), nw = grid * (b->score_T / 64);
-        std::vector<unsigned long long> h((size_t)nw * 4);
-        hipStreamSynchronize(ctx->stream);
-        if (hipMemcpy(h.data(), b->d_prof, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            double c = 0, t = 0, w = 0, n = 0, mx = 0;
-            for (int i = 0; i < nw; i++) { c += (double)h[4 * i]; t += (double)h[4 * i + 1]; w += (double)h[4 * i + 2]; n += (double)h[4 * i + 3]; mx = std::max(mx, (double)(h[4 * i] + h[4 * i + 1] + h[4 * i + 2])); }
-            fprintf(stderr, "[score prof] %d waves: copy %.1f us, tasks %.1f us (%.1f tasks, %.2f us each), barrier wait %.1f us per wave; longest wave %.1f us\n", nw, c / nw / 100, t / nw / 100, n / nw,
-                    n > 0 ? t / n / 100 : 0.0, w / nw / 100, mx / 100);
-        }
-    }
     std::vector<int> vc(2 * (size_t)b->n_units + 1), uf((size_t)b->n_units + 1);
     int r = cs_d2h(ctx, vc.data(), b->d_vcount, 2 * (size_t)b->n_units); if (r) return r;
     r = cs_d2h(ctx, uf.data(), b->d_uflag, (size_t)b->n_units); if (r) return r;

@@ -595,7 +595,7 @@ struct cs_lsd {
     bool have_desc = false;
     LsdSeq *seq = nullptr;           // device buffers of the region stage (lsd_regions.hip)
     int seq_wpb = 16; // frames per workgroup of the device region stage (cs_lsd_set_shared_gpu)
-    bool walk_bg = false; // the region walk on the context's background stream (cs_lsd_set_shared_gpu; CUBESLAM_LSD_WALK_BG=0 keeps it on the context's own)
+    bool walk_bg = false; // the region walk on the context's background stream (cs_lsd_set_shared_gpu)
     void (*gate_wait)(void *) = nullptr; void (*gate_done)(void *) = nullptr; void *gate_arg = nullptr; // the front-end runner's phase gate around the region stage (frontend.hip)
     long rg_stats[5] = {0, 0, 0, 0, 0}; // last batch: 1 = device stage asked for, region_grow calls, rectangles at rect_improve, 1 = fell back to the host stage, window fetches
 };
@@ -623,11 +623,6 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     CS_HIP(ctx, hipSetDevice(ctx->device));
     const int W = l->W, H = l->H, w = l->w, h = l->h, F = l->n_frames;
     l->have_desc = false; l->scaled_kept = true;
-    // CUBESLAM_LSD_HOSTPROF: wall clock of a pass's phases as the calling thread sees them (maps + counts back | region stage | KeyLines on the host | LBD)
-    static const bool hostprof = getenv("CUBESLAM_LSD_HOSTPROF") != nullptr;
-    double tp[5] = {0, 0, 0, 0, 0};
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    tp[0] = now_ms();
     // d_blur and d_scaled (doubles: 2.5 + 1.6 MB per frame) only live from one kernel to the next: they are the two halves of one arena (d_tmp) that the device region stage
     // takes over for its pixel records once lsd_gradient is through, and the LBD blur for its one-kernel life (see below): 4.0 MB per frame that are not allocated twice
     CS_LAUNCH(ctx, "lsd_blur_hv", lsd_blur_hv, dim3(((W + 63) / 64) * ((H + LSD_ROWS - 1) / LSD_ROWS), 1, F), dim3(64), 0, l->d_gray, W, H, l->gk, l->d_blur);
@@ -643,7 +638,6 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     CS_HIP(ctx, hipMemcpy2DAsync(l->frame_base.data(), sizeof(int), l->d_seg_base, sizeof(int) * (size_t)h * nbx, sizeof(int), (size_t)F + 1, hipMemcpyDeviceToHost, ctx->stream));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t total = (size_t)l->frame_base[F];
-    tp[1] = now_ms();
     int r;
     if (total > l->ccap) {
         void *old[] = {l->d_caddr, l->d_cdeg, l->d_ccs, l->d_cmod};
@@ -669,7 +663,7 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     const int grp_p = strcmp(mode, "wlk") == 0 ? 65 : 0; // lsd_rg_wlk: walker waves with one lane per frame + rectangle waves
     const bool use_seq = total > 0 && (strcmp(mode, "seq") == 0 || grp_p);
     // lsd_rg_seq's records are written by the emit kernel itself when they live in the arena (always, unless a caller's frames outgrew it): no fill, no scatter
-    const bool pix_by_emit = use_seq && grp_p == 0 && l->pix_bytes >= (size_t)F * w * h * 4 + 64 && !(getenv("CUBESLAM_LSD_EMIT_PIX") && atoi(getenv("CUBESLAM_LSD_EMIT_PIX")) == 0);
+    const bool pix_by_emit = use_seq && grp_p == 0 && l->pix_bytes >= (size_t)F * w * h * 4 + 64;
     auto emit = [&](bool with_norms) -> int { // the compacted norms (8 B per defined pixel) are the host stage's: the device stage reads the dense map
         if (with_norms && !l->d_cmod) { const int q = cs_dalloc(ctx, &l->d_cmod, l->ccap); if (q) return q; }
         if (pix_by_emit && !with_norms)
@@ -679,28 +673,23 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
         return CS_OK;
     };
     if (total > 0) { r = emit(!use_seq); if (r) return r; }
-    const bool late_maps = [&] { const char *e = getenv("CUBESLAM_LBD_MAPS"); return !(e && !strcmp(e, "early")); }();
     auto lbd_maps = [&]() -> int { // the derivative maps only depend on the gray frames
-        // device region stage: the Sobel map (4 B per pixel) is made once the stage is through, in the arena it has left -- [dxy | ... | blurred frames behind the pixel records' place];
-        // CUBESLAM_LBD_MAPS=early makes it ahead of the stage in a buffer of its own (the phased runner wants every map kernel of a batch on the GPU before its gate)
+        // device region stage: the Sobel map (4 B per pixel) is made once the stage is through, in the arena it has left -- [dxy | ... | blurred frames behind the pixel records' place]
         uint8_t *lblur = l->d_lblur;
         uint32_t *dxy = l->d_dxy;
         if (use_seq) lblur = reinterpret_cast<uint8_t *>(l->d_tmp) + std::max(l->pix_bytes, (size_t)W * H * l->max_frames * 4); // the blurred frames are the Sobel kernel's input and nothing else; behind the walk's map AND behind the Sobel map that is written at the arena's head while they are read (4 B per pixel)
         else if (!lblur) { const int q = cs_dalloc(ctx, &l->d_lblur, (size_t)W * H * l->max_frames); if (q) return q; lblur = l->d_lblur; }
-        if (use_seq && late_maps) dxy = reinterpret_cast<uint32_t *>(l->d_tmp);
+        if (use_seq) dxy = reinterpret_cast<uint32_t *>(l->d_tmp);
         else if (!dxy) { const int q = cs_dalloc(ctx, &l->d_dxy, (size_t)W * H * l->max_frames); if (q) return q; dxy = l->d_dxy; }
         l->dxy_cur = dxy;
         return cs_lbd_batch_maps(ctx, l->d_gray, W, H, F, lblur, dxy);
     };
-    bool maps_done = false;
-    if (use_seq && with_lbd && !late_maps) { r = lbd_maps(); if (r) return r; maps_done = true; } // ahead of the region stage: every map kernel of the batch is on the GPU before the phase gate
     if (l->gate_wait && !use_seq) l->gate_wait(l->gate_arg); // (phased front-end: the region stage starts when the caller's own GPU work of the phase is done; the device stage waits inside lsd_seq_run, in front of its one long kernel)
     if (use_seq) {
         long st[4] = {0, 0, 0, 0};
         l->scaled_kept = false; // the arena is the region stage's from here on
         r = lsd_seq_run(ctx, &l->seq, F, w, h, l->d_ang, l->d_mod, l->d_caddr, l->d_cdeg, l->d_ccs, l->frame_base.data(), dev_lines, st, l->gate_wait, l->gate_done, l->gate_arg, grp_p, l->seq_wpb,
                         l->d_tmp, l->pix_bytes, pix_by_emit, l->walk_bg);
-        tp[2] = now_ms();
         l->rg_stats[0] = 1; l->rg_stats[1] = st[0]; l->rg_stats[2] = st[2]; l->rg_stats[3] = r == CS_OK ? 0 : 1; l->rg_stats[4] = st[1];
         if (r == CS_OK) on_device = true;
         else if (r != CS_ERR_CAPACITY) return r; // a region outgrew the wave's list: the host stage takes the batch
@@ -723,7 +712,7 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     }
     hipEvent_t ev = ctx->get_event();
     CS_HIP(ctx, hipEventRecord(ev, ctx->stream));
-    if (with_lbd && !maps_done && !(use_seq && late_maps && on_device)) { r = lbd_maps(); if (r) return r; maps_done = true; } // they run while the host grows regions
+    if (with_lbd && !on_device) { r = lbd_maps(); if (r) return r; } // they run while the host grows regions
     CS_HIP(ctx, hipEventSynchronize(ev));
     ctx->pool.push_back(ev);
     // one BATCHED host stage at a time per process: two line detectors that alternate batches (bench.py) overlap their GPU phases with
@@ -771,7 +760,6 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
 #pragma omp parallel for schedule(static) num_threads(std::max(1, std::min(ctx->host_threads, F)))
         for (int f = 0; f < F; f++) to_keylines(dev_lines[f], W, H, l->keylines[f]);
     }
-    tp[3] = now_ms();
     l->line_off.assign((size_t)F + 1, 0);
     for (int f = 0; f < F; f++) l->line_off[f + 1] = l->line_off[f] + (int)l->keylines[f].size();
     if (with_lbd) {
@@ -795,14 +783,13 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
             r = cs_h2d(ctx, l->d_kl, kl.data(), (size_t)nl); if (r) return r;
             r = cs_h2d(ctx, l->d_line_frame, lf.data(), (size_t)nl); if (r) return r;
             CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // kl, lf are locals
-            if (!maps_done) { r = lbd_maps(); if (r) return r; } // (device region stage: its pixel records are dead now, the Sobel map takes their place)
+            if (on_device) { r = lbd_maps(); if (r) return r; } // (device region stage: its pixel records are dead now, the Sobel map takes their place)
             r = cs_lbd_batch_desc(ctx, l->d_kl, l->d_line_frame, nl, l->dxy_cur, W, H, l->d_desc, nullptr); if (r) return r;
             r = cs_d2h(ctx, l->h_desc.data(), l->d_desc, (size_t)nl * 32); if (r) return r;
         }
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         l->have_desc = true;
     }
-    if (hostprof) { tp[4] = now_ms(); fprintf(stderr, "[lsd pass %p] maps+counts %.1f  regions %.1f  keylines %.1f  lbd %.1f  total %.1f ms\n", (void *)l, tp[1] - tp[0], tp[2] ? tp[2] - tp[1] : 0.0, tp[3] - (tp[2] ? tp[2] : tp[1]), tp[4] - tp[3], tp[4] - tp[0]); }
     return CS_OK;
 }
 
@@ -991,5 +978,5 @@ void cs_lsd_set_gate(cs_lsd *l, void (*wait)(void *), void (*done)(void *), void
 // shared: other detectors' walks and the other streams' kernels keep every CU busy anyway (the alternating front-end runner): the region stage spreads over the chip
 void cs_lsd_set_shared_gpu(cs_lsd *l, int shared) {
     l->seq_wpb = shared ? 4 : 16;
-    l->walk_bg = shared && !(getenv("CUBESLAM_LSD_WALK_BG") && atoi(getenv("CUBESLAM_LSD_WALK_BG")) == 0);
+    l->walk_bg = shared != 0;
 }

@@ -79,14 +79,6 @@ __device__ double rg_nfa(int n, int k, double p, double LOG_NT, const double *lg
     }
     return -log10(bin_tail) - LOG_NT;
 }
-#if defined(RGI_PROF)
-__device__ unsigned long long g_rgi_prof[4]; // ticks in rectangle walks, in nfa(), calls of each
-#define RGI_T0 const unsigned long long rgi_t0 = wall_clock64()
-#define RGI_T1(k) do { if ((threadIdx.x & 63) == 0) { atomicAdd(&g_rgi_prof[k], wall_clock64() - rgi_t0); atomicAdd(&g_rgi_prof[2 + (k)], 1ull); } } while (0)
-#else
-#define RGI_T0
-#define RGI_T1(k)
-#endif
 // What rect_nfa's row walk needs of a rectangle: the first and last row inside the image and, per row, the closed form of the reference's stepping limits.
 struct RectSpan {
     int mnX, lmY, rmY, flstep, slstep, frstep, srstep, y_first, y_hi;
@@ -150,7 +142,6 @@ template <int NP> __device__ __forceinline__ void rg_row_count(const float *row,
 // tolerances share a walk: rect_improve's first and last loop only halve the tolerance of an unchanged rectangle).  Every lane gets the sums.  The counts are
 // integers, so the pixels may be visited in any order: G = 64 / rows lanes share a row (the rectangles that reach this stage hold 28 pixels in 7 rows on average).
 template <int NP> __device__ void rg_rect_count(const AngMap &F, const rg::Rect &rec, const double *precs, int lane, int &total, int *algs) {
-    RGI_T0;
     RectSpan S; S.set(rec, F.h);
     int total_pts = 0, alg_pts[NP];
     for (int k = 0; k < NP; k++) alg_pts[k] = 0;
@@ -170,13 +161,11 @@ template <int NP> __device__ void rg_rect_count(const AngMap &F, const rg::Rect 
     }
     total = total_pts;
     for (int k = 0; k < NP; k++) algs[k] = alg_pts[k];
-    RGI_T1(0);
 }
 // The walks of up to five rectangles at once (rect_improve's loops try five variants of a rectangle that do not depend on each other): eight lanes per rectangle,
 // lane s of them takes the rows y_first + s, y_first + s + 8, ...  One preamble, one round trip and one (three-step) reduction instead of five of each -- with 28
 // pixels per rectangle a walk is all fixed cost.  rs: this lane's copy of the variants (every lane holds the same five).
 __device__ void rg_rect_count_five(const AngMap &F, const rg::Rect *rs, int cnt, int lane, int *tot, int *alg) {
-    RGI_T0;
     const int grp = lane >> 3, sub = lane & 7;
     const bool on = grp < cnt;
     const rg::Rect rec = rs[on ? grp : 0];
@@ -191,7 +180,6 @@ __device__ void rg_rect_count_five(const AngMap &F, const rg::Rect *rs, int cnt,
         }
     for (int off = 1; off < 8; off <<= 1) { total_pts += __shfl_xor(total_pts, off); alg_pts[0] += __shfl_xor(alg_pts[0], off); }
     for (int n = 0; n < 5; n++) { tot[n] = __shfl(total_pts, 8 * n); alg[n] = __shfl(alg_pts[0], 8 * n); }
-    RGI_T1(0);
 }
 // nfa() of up to five (n, k, p) triples at once: lane v computes triple v -- the loops inside nfa are sequential, the triples independent
 __device__ void rg_nfa5(const int *n, const int *k, const double *p, int cnt, double LOG_NT, const double *lgt, int lane, double *out) {
@@ -216,9 +204,7 @@ __device__ double rg_rect_improve(const AngMap &F, rg::Rect &rec, double LOG_NT,
         cnt = 5;
     };
     auto take_best = [&]() {
-        RGI_T0;
         rg_nfa5(tot, alg, ps, cnt, LOG_NT, lgt, lane, v);
-        RGI_T1(1);
         for (int n = 0; n < cnt; ++n) if (v[n] > log_nfa) { log_nfa = v[n]; rec = rs[n]; }
     };
     auto walks = [&]() { if (cnt) rg_rect_count_five(F, rs, cnt, lane, tot, alg); for (int n = 0; n < cnt; ++n) ps[n] = rs[n].p; };
@@ -251,7 +237,6 @@ struct SeqParams {
     const int *caddr; const int *frame_base; const float *cdeg; const float2 *ccs; const double *mod; const float *ang;
     float *ang32; float *seed_cs; int *glist; double *rect; size_t rect_stride; int cand_cap; int *cand_cnt; int *status;
     int min_reg_size, list_cap;
-    unsigned long long *prof;
     size_t pix_stride; // elements from one frame's map (ang32: the walk's own copy of the angles, a float per pixel: the angle while the pixel is defined and unused) to the next
 };
 __global__ void __launch_bounds__(256) lsd_rg_fill32(float4 *ang, size_t n4) { // lsd_rg_wlk's map: one float per pixel
@@ -283,7 +268,7 @@ __device__ __forceinline__ void lsd_rg_seq_body(const SeqParams &P) {
     Fr.w = P.w; Fr.h = P.h; Fr.ne = P.frame_base[f + 1] - base;
     Fr.caddr = P.caddr + base; Fr.fre = P.ang32 + (size_t)f * P.pix_stride; Fr.ang = P.ang + (size_t)f * P.w * P.h; Fr.mod = P.mod + (size_t)f * P.w * P.h; Fr.seed_cs = P.seed_cs + 2 * (size_t)base;
     Fr.rect = P.rect + (size_t)f * P.rect_stride; Fr.cand_cap = P.cand_cap; Fr.cand_cnt = P.cand_cnt + f;
-    Fr.status = P.status + 4 * f; Fr.min_reg_size = P.min_reg_size; Fr.list_cap = P.list_cap; Fr.prof = P.prof ? P.prof + 16 * (size_t)f : nullptr;
+    Fr.status = P.status + 4 * f; Fr.min_reg_size = P.min_reg_size; Fr.list_cap = P.list_cap;
     rgs::List L;
     L.glob = P.glist + (size_t)f * rgs::CAP; L.ring[0] = 0;
     rgs::run_frame<rgs::Wave>(Fr, L);
@@ -323,13 +308,7 @@ template <int WK, int NWAVES, int ACC> __global__ void __launch_bounds__(64 * NW
         if (lane == 0) rgw::lds_add(&mail.walkers_done, 1);
         return;
     }
-#if defined(RGW_PROF)
-    unsigned long long rgw_job = 0, rgw_jobs = 0, rgw_idle = 0;
-#endif
     for (;;) { // a rectangle wave: the next ticket, its region, the answer
-#if defined(RGW_PROF)
-        const unsigned long long rgw_t0 = clock64();
-#endif
         int t = 0;
         if (lane == 0) t = rgw::lds_add(&mail.head, 1);
         t = __builtin_amdgcn_readfirstlane(t);
@@ -339,17 +318,8 @@ template <int WK, int NWAVES, int ACC> __global__ void __launch_bounds__(64 * NW
             __builtin_amdgcn_s_sleep(4);
         }
         if (quit) break;
-#if defined(RGW_PROF)
-        const unsigned long long rgw_t1 = clock64();
-#endif
         rgw::serve_ticket<rgs::Wave, NS>(B, mail, t);
-#if defined(RGW_PROF)
-        rgw_idle += rgw_t1 - rgw_t0; rgw_job += clock64() - rgw_t1; rgw_jobs++;
-#endif
     }
-#if defined(RGW_PROF)
-    if (lane == 0) { atomicAdd(&rgw::g_rgw_prof[8], rgw_job); atomicAdd(&rgw::g_rgw_prof[9], rgw_jobs); atomicAdd(&rgw::g_rgw_prof[10], rgw_idle); }
-#endif
 }
 // the frames' rectangle lists one after the other (frames in order, seeds in order): cand_base[f] = rectangles of the frames before f
 __global__ void __launch_bounds__(1024) lsd_rg_cand_scan(const int *cand_cnt, int F, int *cand_base) {
@@ -394,7 +364,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMP
     load_rect(on ? mine : n_cand - 1, f1, r1);
     double log1;
     {
-        RGI_T0;
         RectSpan S; S.set(r1, P.h);
         const float *deg = P.ang + (size_t)f1 * P.w * P.h;
         int tot = 0, alg[1] = {0};
@@ -406,8 +375,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMP
                 rg_row_count<1>(deg + (size_t)y * P.w, lx, rx, 0, 1, r1.theta, &r1.prec, alg);
             }
         for (int off = 1; off < 8; off <<= 1) { tot += __shfl_xor(tot, off); alg[0] += __shfl_xor(alg[0], off); }
-        RGI_T1(0);
-        { RGI_T0; log1 = rg_nfa(tot, alg[0], r1.p, LOG_NT, lgt); RGI_T1(1); }
+        log1 = rg_nfa(tot, alg[0], r1.p, LOG_NT, lgt);
     }
     if (on && sub == 0 && log1 > LOG_EPS) emit(mine, r1, log1);
     // ---- the others, one at a time
@@ -485,13 +453,6 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     const bool grp = grp_p == 65, pad = grp; // walker + rectangle waves (lsd_rg_wlk.h): a float per pixel, 8-byte list entries, padded strides
     const size_t rect_stride = (size_t)r->cand_cap * 12 + (pad ? PAD_RECT : 0), list_stride = (size_t)rgl::CAP + (pad ? PAD_LIST : 0);
     S.pix_stride = (size_t)w * h + (pad ? PAD_PX : 0); S.rect_stride = rect_stride;
-    S.prof = nullptr;
-#if defined(RGS_PROFILE)
-    static unsigned long long *d_prof = nullptr;
-    if (!d_prof) hipMalloc((void **)&d_prof, 4096 * 16 * sizeof(unsigned long long));
-    hipMemsetAsync(d_prof, 0, 4096 * 16 * sizeof(unsigned long long), ctx->stream);
-    S.prof = d_prof;
-#endif
     const size_t npx = (size_t)F * S.pix_stride;
     if (grp) {
         const size_t head = (size_t)((w + 8 + 3) & ~3); // undefined pixels in front of frame 0 (the walkers read "row -1" without a test)
@@ -511,7 +472,6 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     }
     if (!pix_ready) CS_LAUNCH(ctx, "lsd_rg_scatter", lsd_rg_scatter, dim3((max_ne + 255) / 256, F), dim3(256), 0, S);
     int wpb = std::max(1, std::min(16, waves_per_workgroup)); // waves (= frames) per workgroup
-    if (const char *e = getenv("CUBESLAM_LSD_SEQ_WPB")) wpb = std::max(1, std::min(16, atoi(e)));
     if (before_seq) before_seq(gate_arg);
     if (grp) {
         const size_t npx = (size_t)w * h, head = (size_t)((w + 8 + 3) & ~3);
@@ -542,15 +502,9 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
             const int bps = (L.waves_per_slice + wk - 1) / wk, groups = L.n_slices * bps;
 #define WLK_(WK, NW, AC) else if (wk == WK && nw == NW && acc == AC) CS_LAUNCH(ctx, "lsd_rg_wlk", (lsd_rg_wlk<WK, NW, AC>), dim3(groups), dim3(64 * NW), 0, L, bps)
             if (false) {}
-            WLK_(1, 8, 1); WLK_(1, 8, 2); WLK_(1, 4, 1); WLK_(2, 8, 1); WLK_(2, 16, 1); WLK_(4, 16, 1); WLK_(8, 16, 1);
+            WLK_(1, 8, 1); WLK_(1, 8, 2); WLK_(2, 8, 1); WLK_(8, 16, 1);
             else { ctx->err = "CUBESLAM_LSD_WLK: no such shape (walkers,waves,accepts)"; return CS_ERR_BAD_ARG; }
 #undef WLK_
-#if defined(RGW_PROF)
-            { unsigned long long h[16]; hipDeviceSynchronize(); hipMemcpyFromSymbol(h, HIP_SYMBOL(rgw::g_rgw_prof), sizeof h); unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(rgw::g_rgw_prof), z, sizeof z);
-              const double it = (double)std::max<unsigned long long>(h[5], 1);
-              fprintf(stderr, "[rgw prof] walker iterations %.0f (all waves); clocks per iteration: issue %.0f wait %.0f grow %.0f seed %.0f mail %.0f = %.0f; rectangle waves: %.0f jobs, %.0f clocks each, waiting %.0f clocks per job\n", it, h[0] / it, h[1] / it, h[2] / it,
-                      h[3] / it, h[4] / it, (h[0] + h[1] + h[2] + h[3] + h[4]) / it, (double)h[9], h[9] ? (double)h[8] / h[9] : 0.0, h[9] ? (double)h[10] / h[9] : 0.0); }
-#endif
         }
     } else if (walk_bg) {
         CS_HIP(ctx, ctx->bg_begin());
@@ -567,12 +521,6 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     RA_(cs_d2h(ctx, r->h_status.data(), r->d_status, (size_t)F * 4));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (after_seq) after_seq(gate_arg);
-#if defined(RGS_PROFILE)
-    { std::vector<unsigned long long> all((size_t)F * 16); hipMemcpy(all.data(), S.prof, all.size() * 8, hipMemcpyDeviceToHost);
-      unsigned long long hp[16] = {0}; for (int f = 0; f < F; f++) for (int k = 0; k < 16; k++) hp[k] += all[(size_t)f * 16 + k];
-      const char *nm[6] = {"fetch", "expand", "grow", "rect+refine", "seed batch", "frame"};
-      for (int k = 0; k < 6; k++) fprintf(stderr, "[rgs prof] %-12s entries/frame %9.0f  ms/frame %8.2f  us/entry %6.2f\n", nm[k], double(hp[2 * k + 1]) / F, hp[2 * k] / 1e5 / F, hp[2 * k + 1] ? hp[2 * k] / 100.0 / hp[2 * k + 1] : 0.0); }
-#endif
     long grows = 0, fetches = 0, nreg = 0;
     bool bad = false;
     for (int f = 0; f < F; f++) { grows += r->h_status[4 * f]; bad = bad || r->h_status[4 * f + 1] != 0; nreg += r->h_status[4 * f + 2]; fetches += r->h_status[4 * f + 3]; }
@@ -589,11 +537,6 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
         r->cap_lines = cap;
     }
     CS_LAUNCH(ctx, "lsd_rg_improve", lsd_rg_improve, dim3((n_cand + 31) / 32), dim3(256), 0, S, r->d_cand_base, n_cand, r->d_lgt, r->d_line, r->d_has); // eight rectangles per wave
-#if defined(RGI_PROF)
-    { unsigned long long h[4]; hipDeviceSynchronize(); hipMemcpyFromSymbol(h, HIP_SYMBOL(g_rgi_prof), sizeof h); unsigned long long z[4] = {0, 0, 0, 0}; hipMemcpyToSymbol(HIP_SYMBOL(g_rgi_prof), z, sizeof z);
-      fprintf(stderr, "[rgi prof] %d rectangles: walks %.0f calls %.2f us each = %.1f us per rectangle; nfa %.0f calls %.2f us each = %.1f us per rectangle\n", n_cand, (double)h[2], h[2] ? h[0] / 100.0 / h[2] : 0.0,
-              h[0] / 100.0 / n_cand, (double)h[3], h[3] ? h[1] / 100.0 / h[3] : 0.0, h[1] / 100.0 / n_cand); }
-#endif
     r->h_has.resize((size_t)n_cand); r->h_line.resize((size_t)n_cand);
     RA_(cs_d2h(ctx, r->h_has.data(), r->d_has, (size_t)n_cand));
     RA_(cs_d2h(ctx, r->h_line.data(), r->d_line, (size_t)n_cand));

@@ -75,7 +75,6 @@ struct Frame {
     const double *mod;  // dense gradient norms
     const float *seed_cs; // per rank: float(cos(angle)), float(sin(angle)) of the pixel's angle as a double -- what a seed starts its sums with (:651-652)
     double *rect; int cand_cap; int *cand_cnt; // the rectangles (12 doubles each, rg::Rect) that reach rect_improve, in seed order
-    unsigned long long *prof; // RGS_PROFILE
     int *status;        // [0] region_grow calls, [1] failure (capacity), [2] regions at the rectangle stage, [3] window fetches
     int min_reg_size;
     int list_cap;       // pixels of one region before the frame gives up (<= CAP)
@@ -157,15 +156,6 @@ RGS_FN bool aligned_rad(double a, double theta, double prec) {
     return (d > rg::M_3_2_PI_ ? d2 : d) <= prec;
 }
 
-#if defined(RGS_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
-// (development) wall-clock ticks (10 ns) and entries per part, added up over all frames without waiting for the result
-#define RGS_T0(k) const unsigned long long rgs_t_##k = wall_clock64()
-#define RGS_T1(k) do { if ((threadIdx.x & 63) == 0) { atomicAdd(&F.prof[2 * (k)], wall_clock64() - rgs_t_##k); atomicAdd(&F.prof[2 * (k) + 1], 1ull); } } while (0)
-#else
-#define RGS_T0(k)
-#define RGS_T1(k)
-#endif
-
 struct Seeds { // the 64 seeds the seed loop is looking at
     PerLane<int> sa; // address, -1 past the end
     u64 freem;       // defined and unused, kept current while regions grow
@@ -206,9 +196,6 @@ template <class W> RGS_FN void win_fetch(const Frame &F, Win &w, int wx, int wy)
             w.ar[l] = fr ? a : FAR; w.pc[l] = cc; w.ps[l] = sn;
         }
     });
-#if defined(RGS_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
-    { PerLane<bool> z; W::each([&](int l) { z[l] = w.ar[l] == 12345.0; }); if (W::ballot(z)) w.wx = WIN_NONE; } // (the data has to arrive inside the timed part)
-#endif
 }
 template <class W> RGS_FN void win_strike(Win &w, int x, int y) { // pixel (x, y) is used now
     const int lx = x - w.wx, ly = y - w.wy;
@@ -274,16 +261,12 @@ template <class W> RGS_FN void grow(const Frame &F, Wins &V, List &L, int &n, do
         if (!win_covers(V.a, px, py)) {
             if (!win_covers(V.b, px, py)) { // fetch around the pixel, leaning away from the seed (the region grows outwards), over the window used longest ago
                 const int ox = px > sx ? 2 : (px < sx ? 5 : (i == 0 ? 2 : 3)), oy = py > sy ? 2 : (py < sy ? 5 : 3);
-                RGS_T0(0);
                 win_fetch<W>(F, V.b, px - ox, py - oy);
-                RGS_T1(0);
                 fetches++;
             }
             win_swap<W>(V);
         }
-        RGS_T0(1);
         expand<W>(F, V.a, V.b, px, py, L, n, reg_angle, prec, sumdx, sumdy, S, overflow);
-        RGS_T1(1);
     }
 }
 
@@ -404,9 +387,7 @@ template <class W> RGS_FN void run_frame(const Frame &F, List &L) {
     Wins V;
     V.a.wx = WIN_NONE; V.a.wy = 0; V.b.wx = WIN_NONE; V.b.wy = 0; V.a.am = 0; V.b.am = 0; V.a.am_ok = false; V.b.am_ok = false;
     W::each([&](int l) { V.a.ar[l] = FAR; V.a.pc[l] = 0; V.a.ps[l] = 0; V.b.ar[l] = FAR; V.b.pc[l] = 0; V.b.ps[l] = 0; });
-    RGS_T0(5);
     for (int i0 = 0; i0 < F.ne && !overflow; i0 += 64) {
-        RGS_T0(4);
         Seeds S;
         PerLane<int> iso, sxy; PerLane<float> dg, sc, ss; PerLane<bool> fr;
         W::each([&](int l) {
@@ -415,7 +396,6 @@ template <class W> RGS_FN void run_frame(const Frame &F, List &L) {
             if (idx < F.ne) { const int ca = F.caddr[idx]; S.sa[l] = ca & 0x7fffffff; iso[l] = ca < 0; { const int yy = S.sa[l] / F.w; sxy[l] = xy_pack(S.sa[l] - yy * F.w, yy); } sc[l] = F.seed_cs[2 * idx]; ss[l] = F.seed_cs[2 * idx + 1]; dg[l] = F.ang[S.sa[l]]; fr[l] = ld_free(&F.fre[S.sa[l]]) != NOTDEF_F; }
         });
         S.freem = W::ballot(fr);
-        RGS_T1(4);
         bool reload = false;
         int pos = 0;
         while (pos < 64) {
@@ -437,20 +417,16 @@ template <class W> RGS_FN void run_frame(const Frame &F, List &L) {
             }
             const float sdeg = W::bc(dg, j), scos = W::bc(sc, j), ssin = W::bc(ss, j);
             int n; double reg_angle;
-            RGS_T0(2);
             grow<W>(F, V, L, n, reg_angle, prec, sx, sy, sdeg, scos, ssin, S, overflow, fetches);
-            RGS_T1(2);
             n_grow++;
             if (overflow) break;
             if (n < F.min_reg_size) continue;
             n_reg++;
             rg::Rect rec;
-            RGS_T0(3);
             to_rect<W>(F, L, n, reg_angle, prec, p, rec);
             bool released = false;
             const bool ok = refine<W>(F, V, L, n, reg_angle, prec, p, rec, sx, sy, sdeg, scos, ssin, S, overflow, fetches, released);
             if (released) reload = true;
-            RGS_T1(3);
             if (overflow) break;
             if (!ok) continue;
             if (n_cand >= F.cand_cap) { overflow = true; break; }
@@ -460,7 +436,6 @@ template <class W> RGS_FN void run_frame(const Frame &F, List &L) {
             ++n_cand;
         }
     }
-    RGS_T1(5);
     W::each([&](int l) { if (l == 0) { F.status[0] = n_grow; F.status[1] = overflow ? 1 : 0; F.status[2] = n_reg; F.status[3] = fetches; *F.cand_cnt = n_cand; } });
 }
 } // namespace rgs

@@ -132,17 +132,6 @@ RGS_FN void wg_acquire() {}
 RGS_FN void wg_release_lds() {}
 #endif
 
-#if defined(RGW_PROF) && defined(__HIPCC__)
-// (development) shader-clock ticks per part of a walker iteration, summed over all walker waves: [0] issuing the loads, [1] waiting for them, [2] growth, [3] seeds, [4] mailbox, [5] iterations;
-// rectangle waves: [8] ticks in jobs, [9] jobs, [10] ticks waiting for a ticket
-__device__ unsigned long long g_rgw_prof[16];
-#endif
-#if defined(RGW_PROF) && defined(__HIP_DEVICE_COMPILE__)
-#define RGW_TICK(k) do { const unsigned long long rgw_now = clock64(); rgw_acc[k] += rgw_now - rgw_t; rgw_t = rgw_now; } while (0)
-#else
-#define RGW_TICK(k)
-#endif
-
 // =========================================================================================================================================
 // The rectangle stage of one parked region, by a whole wave (W = rgs::Wave: the lanes of the calling wave / loops on the host)
 // =========================================================================================================================================
@@ -420,9 +409,6 @@ template <class W, int ACC, class MP> RGS_FN void run_walker(const Batch &B, int
     __builtin_amdgcn_s_waitcnt(0x0f70); // (the first seed addresses: nothing is in flight when the loop starts, or every iteration would carry the waits of the first)
 #endif
     int iters = 0;
-#if defined(RGW_PROF) && defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long rgw_acc[6] = {0, 0, 0, 0, 0, 0}, rgw_t = clock64();
-#endif
     for (;;) {
         {
             PerLane<bool> on;
@@ -476,11 +462,9 @@ template <class W, int ACC, class MP> RGS_FN void run_walker(const Batch &B, int
                 }
             }
         });
-        RGW_TICK(0);
 #if defined(__HIP_DEVICE_COMPILE__)
         __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0): nothing is in flight across the back edge
 #endif
-        RGW_TICK(1);
 
         PerLane<bool> park;
         W::each([&](int l) { park[l] = false; });
@@ -546,7 +530,6 @@ template <class W, int ACC, class MP> RGS_FN void run_walker(const Batch &B, int
             });
         }
 
-        RGW_TICK(2);
         // ---- the seed loop :477-487: four candidates
         if (rgl::LWave::any(seeding)) {
             W::each([&](int l) {
@@ -576,7 +559,6 @@ template <class W, int ACC, class MP> RGS_FN void run_walker(const Batch &B, int
             });
         }
 
-        RGW_TICK(3);
         // ---- parked regions: the answers that have arrived, then this iteration's new posts
         if (rgl::LWave::any(waiting)) {
             PerLane<bool> got;
@@ -617,12 +599,7 @@ template <class W, int ACC, class MP> RGS_FN void run_walker(const Batch &B, int
             });
         }
         mp.after_iteration(B);
-        RGW_TICK(4);
     }
-#if defined(RGW_PROF) && defined(__HIP_DEVICE_COMPILE__)
-    rgw_acc[5] = (unsigned long long)iters;
-    if ((threadIdx.x & 63) == 0) for (int k = 0; k < 6; k++) atomicAdd(&g_rgw_prof[k], rgw_acc[k]);
-#endif
     W::each([&](int l) {
         const WSt &s = st[l];
         if (s.valid) { int *o = B.status + 4 * (size_t)s.fl; o[0] = s.n_grow; o[1] = s.fail; o[2] = s.n_reg; o[3] = s.it_done; B.cand_cnt[s.fl] = s.n_cand;

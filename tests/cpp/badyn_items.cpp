@@ -84,7 +84,7 @@ int badyn_items_reduced(const cs_ba_dyn_problem *p, double lambda, double *chi, 
     std::memcpy(bs, h.bs.data(), sizeof(double) * h.G.NP);
     return h.G.NP;
 }
-// one linear step: reduce, dense solve (plain Cholesky here; the product uses badyn_chol_solve), back substitution items, update items
+// one linear step: reduce, dense solve (plain Cholesky here; the product uses the blocked badyn_chol_* kernels), back substitution items, update items
 int badyn_items_step(const cs_ba_dyn_problem *p, double lambda, double *state_out) {
     Host h(p);
     h.errors();

@@ -27,7 +27,7 @@ if "--kernels" in sys.argv:  # event pairs around every launch: they add the lau
     ba = DynamicBundleAdjuster(d, ctx=ctx)
     ba.optimize(10)
     for k in ("badyn_errors", "badyn_linearize", "badyn_schur_init", "badyn_dinv", "badyn_bd", "badyn_schur_blocks", "badyn_schur_rhs", "badyn_chol_panel", "badyn_chol_update",
-              "badyn_chol_tri", "badyn_chol_solve", "badyn_backsub", "badyn_update", "badyn_diag"):
+              "badyn_chol_tri", "badyn_backsub", "badyn_update", "badyn_diag"):
         t = ctx.timing_get(k)
         if t[1]:
             print("  %-18s %8.1f us/call x %d" % (k, t[0] / t[1] * 1e3, t[1]))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # (development) a second build of the library with extra compiler flags for ONE source, beside the product library:
-#   tools/build_variant.sh prof lsd_regions.hip "-DRGW_PROF"   ->  cube_slam_amd/variants/libcubeslam_prof.so   (use: CUBESLAM_LIB=$PWD/cube_slam_amd/variants/libcubeslam_prof.so)
+#   tools/build_variant.sh fence ba_cr.hip "-DCR_BACK_FENCE"   ->  cube_slam_amd/variants/libcubeslam_fence.so   (use: CUBESLAM_LIB=$PWD/cube_slam_amd/variants/libcubeslam_fence.so)
 set -e
 cd "$(dirname "$0")/../cube_slam_amd/csrc"
 name=$1; src=$2; extra=$3

@@ -1,5 +1,5 @@
 """(development) BASELINE config 4's share of one GPU (64 frames x 8 boxes) under the score kernel's launch knobs: python tools/c4_probe.py [setting ...], a setting is
-`default` or KEY=VALUE[,KEY=VALUE] over CUBESLAM_SCORE_THREADS / CUBESLAM_SCORE_SEGMENTS / CUBESLAM_SCORE_SLICES; CUBESLAM_SCORE_PROF=1 prints the in-kernel phase profile."""
+`default` or KEY=VALUE[,KEY=VALUE] over CUBESLAM_SCORE_THREADS / CUBESLAM_SCORE_SEGMENTS / CUBESLAM_SCORE_SLICES."""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # (development, on the GPU box) the headline under runner settings, one line per variant.  Every argument is "name|VAR=value VAR=value|bench.py flags", e.g.
-#   tools/r04_sweep.sh "default||" "five|BENCH_PRIO_LINES=0|--line-workers 5" "q4|GPU_MAX_HW_QUEUES=4 CUBESLAM_LSD_WALK_BG=0|"
+#   tools/r04_sweep.sh "default||" "five|BENCH_PRIO_LINES=0|--line-workers 5" "q4|GPU_MAX_HW_QUEUES=4|"
 # prints frames/s, ms per step, cuboid_sweep_score's fraction in the timed region and the in-run ms per launch of a few kernels (profiles/r04_c_runner_sweeps.txt was made with it).
 mkdir -p gpurun_out
 for v in "$@"; do

@@ -4,3 +4,4 @@ The compute lives in libcubeslam_hip.so (hand-written HIP for gfx950, C-ABI in i
 package is the thin host-side mirror of the reference interfaces used by tests and bench.py.
 """
 from . import _lib  # noqa: F401
+from .stereo import ComputeStereoMatches, StereoMatcher  # noqa: F401

@@ -24,6 +24,20 @@ void cs_omp_prepare();
 struct cs_orb;
 int cs_orb_device_frame(const cs_orb *e, int frame, const cs_keypoint **d_kps, const unsigned long long **d_desc, int *n);  // ctx.hip: call before an OpenMP region of a host stage
 
+// orb.hip: the resident pyramid (mvImagePyramid, ORBextractor.h:85) and the scale tables of an extractor, for stereo.hip.  Level l of frame f is
+// d_pyr + f * frame_stride + off[l], w[l] x h[l] bytes, rows w[l] apart.
+constexpr int CS_ORB_MAX_LEVELS = 16;
+struct cs_orb_pyramid_view {
+    const uint8_t *d_pyr;
+    long frame_stride;
+    int nlevels, n_frames, W, H;
+    long off[CS_ORB_MAX_LEVELS];
+    int w[CS_ORB_MAX_LEVELS], h[CS_ORB_MAX_LEVELS];
+    float scale[CS_ORB_MAX_LEVELS], inv_scale[CS_ORB_MAX_LEVELS]; // mvScaleFactor / mvInvScaleFactor
+    float scale_factor;
+};
+int cs_orb_device_pyramid(const cs_orb *e, cs_orb_pyramid_view *out);
+
 struct cs_ctx {
     int device = 0;
     hipStream_t stream = nullptr;

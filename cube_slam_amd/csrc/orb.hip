@@ -959,6 +959,18 @@ int cs_orb_device_frame(const cs_orb *e, int frame, const cs_keypoint **d_kps, c
     return CS_OK;
 }
 
+int cs_orb_device_pyramid(const cs_orb *e, cs_orb_pyramid_view *out) {
+    static_assert(CS_ORB_MAX_LEVELS == MAXL, "cs_orb_pyramid_view holds every level");
+    if (!e || !out) return CS_ERR_BAD_ARG;
+    out->d_pyr = e->d_pyr; out->frame_stride = e->P.frame_stride; out->nlevels = e->nlevels; out->n_frames = e->n_frames; out->W = e->W; out->H = e->H;
+    out->scale_factor = e->scaleFactor;
+    for (int l = 0; l < e->nlevels; l++) {
+        out->off[l] = e->P.l[l].off; out->w[l] = e->P.l[l].w; out->h[l] = e->P.l[l].h;
+        out->scale[l] = e->mvScaleFactor[l]; out->inv_scale[l] = e->mvInvScaleFactor[l];
+    }
+    return CS_OK;
+}
+
 extern "C" {
 
 void cs_orb_destroy(cs_ctx *ctx, cs_orb *e) {

@@ -3,6 +3,8 @@
 // plain arrays where the reference passes cv::Mat / KeyFrame*.  The adapters with the reference's exact signatures
 // are thin wrappers around these and compile only in a tree that provides OpenCV / Eigen / the ORB-SLAM2 map classes.
 //   cubeslam::ORBextractor      ORB_SLAM2::ORBextractor      (orb_object_slam/include/ORBextractor.h:44-112)
+//   cubeslam::Frame             ORB_SLAM2::Frame, the stereo members (orb_object_slam/include/Frame.h, src/Frame.cc:94-144, :611-783):
+//                               ComputeStereoMatches over two extractors, mvuRight / mvDepth
 //   cubeslam::line_lbd_detect   line_lbd_detect              (line_lbd/include/line_lbd/line_lbd_allclass.h:22-70)
 //   cubeslam::Optimizer         ORB_SLAM2::Optimizer         (orb_object_slam/include/Optimizer.h:39-62): BundleAdjustment over the
 //                               flattened graph (cs_ba_problem), PoseOptimization over flattened matches,
@@ -53,6 +55,43 @@ class ORBextractor {
     Context &ctx_;
     cs_orb *e_ = nullptr;
     int nfeatures_, nlevels_, W_, H_;
+};
+
+// The stereo part of ORB_SLAM2::Frame: what the stereo constructor (Frame.cc:94-144) does between the two extractions (:106-110) and
+// AssignFeaturesToGrid: ComputeStereoMatches (:118, :611-783) on the device, from what the two extractors' last operator() left there.
+class Frame {
+  public:
+    // Frame(..., ORBextractor *extractorLeft, ORBextractor *extractorRight, ..., const float &bf, ...).  mb: the reference's constructor sets
+    // mb = mbf / fx at :141, after ComputeStereoMatches ran at :118, so its first frame runs with whatever the member held; set mb to the value meant.
+    Frame(Context &c, ORBextractor *extractorLeft, ORBextractor *extractorRight, float bf, float b, int max_keypoints)
+        : mbf(bf), mb(b), mpORBextractorLeft(extractorLeft), mpORBextractorRight(extractorRight), ctx_(c) {
+        check(ctx_.ctx, cs_stereo_create(ctx_.ctx, max_keypoints, 1, &s_), "cs_stereo_create");
+    }
+    ~Frame() { cs_stereo_destroy(ctx_.ctx, s_); }
+    Frame(const Frame &) = delete;
+    Frame &operator=(const Frame &) = delete;
+    // void Frame::ComputeStereoMatches(): fills mvuRight / mvDepth (N values, -1 where unmatched); returns the number of matches kept
+    int ComputeStereoMatches() {
+        check(ctx_.ctx, cs_stereo_match_from_orb(ctx_.ctx, s_, mpORBextractorLeft->handle(), 0, mpORBextractorRight->handle(), 0, 1, mbf, mb), "cs_stereo_match_from_orb");
+        int first[2] = {0, 0}, n_matched = 0;
+        long total = 0;
+        check(ctx_.ctx, cs_stereo_read_packed(ctx_.ctx, s_, nullptr, nullptr, 0, first, &total, nullptr), "cs_stereo_read_packed");
+        N = (int)total;
+        mvuRight.assign((size_t)N + 1, -1.0f); mvDepth.assign((size_t)N + 1, -1.0f);
+        check(ctx_.ctx, cs_stereo_read_packed(ctx_.ctx, s_, mvuRight.data(), mvDepth.data(), total, first, &total, &n_matched), "cs_stereo_read_packed");
+        mvuRight.resize((size_t)N); mvDepth.resize((size_t)N);
+        return n_matched;
+    }
+    // mvuRight / mvDepth where they were computed, for cs_match_fuse / cs_pose_optimization callers that keep them on the device
+    void device(const float **d_uRight, const float **d_depth) const { int n = 0; check(ctx_.ctx, cs_stereo_device_pair(s_, 0, d_uRight, d_depth, &n), "cs_stereo_device_pair"); }
+    int N = 0;
+    std::vector<float> mvuRight, mvDepth;
+    float mbf, mb;
+    ORBextractor *mpORBextractorLeft, *mpORBextractorRight;
+
+  private:
+    Context &ctx_;
+    cs_stereo *s_ = nullptr;
 };
 
 class line_lbd_detect {

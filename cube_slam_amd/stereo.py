@@ -1,0 +1,91 @@
+"""Python host-side mirror of ORB_SLAM2::Frame::ComputeStereoMatches (reference orb_object_slam/src/Frame.cc:611-783) over the C-ABI: the association of
+rectified stereo pairs on the device, from what the extractors' last run left there."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+class StereoMatcher:
+    """cs_stereo wrapper: room for max_pairs pairs of at most max_keypoints_per_frame key points per image."""
+
+    def __init__(self, max_keypoints_per_frame, max_pairs=1, ctx=None, device=0):
+        self.ctx = ctx or _lib.Context(device)
+        self.cap, self.max_pairs, self.n_pairs = int(max_keypoints_per_frame), int(max_pairs), 0
+        self._s = C.c_void_p()
+        check(self.ctx.ptr, lib().cs_stereo_create(self.ctx.ptr, self.cap, self.max_pairs, C.byref(self._s)), "cs_stereo_create")
+
+    def match(self, left, right, bf, b, left_first=0, right_first=0, n_pairs=None):
+        """Queue the association of n_pairs pairs: frame left_first + p of `left`'s last run against frame right_first + p of `right`'s
+        (ORBextractor objects; the same object twice for one run that holds both halves).  Returns at once; results stay on the device."""
+        if n_pairs is None:
+            n_pairs = left.n_frames - left_first
+        check(self.ctx.ptr, lib().cs_stereo_match_from_orb(self.ctx.ptr, self._s, left._e, int(left_first), right._e, int(right_first), int(n_pairs),
+                                                           C.c_float(bf), C.c_float(b)), "cs_stereo_match_from_orb")
+        self.n_pairs = int(n_pairs)
+
+    def read(self):
+        """[(mvuRight, mvDepth)] per pair and n_matched[n_pairs]."""
+        P = self.n_pairs
+        ur = np.zeros((P, self.cap), np.float32)
+        dep = np.zeros((P, self.cap), np.float32)
+        counts = np.zeros(P, np.int32)
+        nm = np.zeros(P, np.int32)
+        check(self.ctx.ptr, lib().cs_stereo_read(self.ctx.ptr, self._s, _p(ur, C.c_float), _p(dep, C.c_float), self.cap, _p(counts, C.c_int), _p(nm, C.c_int)),
+              "cs_stereo_read")
+        return [(ur[p, :counts[p]].copy(), dep[p, :counts[p]].copy()) for p in range(P)], nm
+
+    def read_packed(self):
+        """(mvuRight of every pair one behind the other, mvDepth likewise, first[n_pairs + 1], n_matched) -- two device-to-host copies for the batch."""
+        P = self.n_pairs
+        first = np.zeros(P + 1, np.int32)
+        total = C.c_long()
+        check(self.ctx.ptr, lib().cs_stereo_read_packed(self.ctx.ptr, self._s, None, None, C.c_long(0), _p(first, C.c_int), C.byref(total), None), "cs_stereo_read_packed")
+        ur = np.zeros(max(total.value, 1), np.float32)
+        dep = np.zeros(max(total.value, 1), np.float32)
+        nm = np.zeros(P, np.int32)
+        check(self.ctx.ptr, lib().cs_stereo_read_packed(self.ctx.ptr, self._s, _p(ur, C.c_float), _p(dep, C.c_float), C.c_long(len(ur)), _p(first, C.c_int), C.byref(total),
+                                                        _p(nm, C.c_int)), "cs_stereo_read_packed")
+        return ur[:total.value], dep[:total.value], first, nm
+
+    def device_pair(self, pair):
+        """(device address of mvuRight, of mvDepth, n) of one pair, for cs_match_fuse / cs_pose_optimization callers that keep it on the device."""
+        u, d, n = C.c_void_p(), C.c_void_p(), C.c_int()
+        check(self.ctx.ptr, lib().cs_stereo_device_pair(self._s, int(pair), C.byref(u), C.byref(d), C.byref(n)), "cs_stereo_device_pair")
+        return u.value, d.value, n.value
+
+    def close(self):
+        if self._s:
+            lib().cs_stereo_destroy(self.ctx.ptr, self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ComputeStereoMatches(left, right, bf, b, left_first=0, right_first=0, n_pairs=None, matcher=None):
+    """Frame::ComputeStereoMatches over two cube_slam_amd.orb.ORBextractor objects after their run(): (mvuRight, mvDepth) as numpy arrays for a single
+    pair, a list of such tuples for a batch (n_pairs given, or extractors that hold more than one frame).  `right` may be `left` itself with
+    right_first = the first right frame.  bf = mbf, b = mb: the reference sets mb = mbf / fx only after its first call (Frame.cc:141 against :118);
+    pass the value meant.  `matcher`: a StereoMatcher to reuse (otherwise one is created for the call)."""
+    single = n_pairs is None
+    if n_pairs is None:
+        n_pairs = left.n_frames - left_first if left is not right else right_first - left_first
+    single = single and n_pairs == 1
+    m = matcher or StereoMatcher(max(left.cap, right.cap), n_pairs, ctx=left.ctx)
+    try:
+        m.match(left, right, bf, b, left_first, right_first, n_pairs)
+        res, _ = m.read()
+    finally:
+        if matcher is None:
+            m.close()
+    return res[0] if single else res

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define CS_VERSION 107 /* 107: cs_match_by_projection_stream takes n_queries / n_train, cs_cuboid_batch_set_boxes, the matchers' claim passes run on the device; 106: cs_cuboid_batch_n_frames, cs_frontend_queues, cs_match_by_projection_stream, cs_frontend_stream_*, cs_*_set_frames_device, cs_orb_read_packed; 105: cs_frontend_set_backlog; 104: cs_frontend_set_cuboid_ctx; 103: cs_lsd_read_filter_lines takes the caller's frame count, cs_frontend_set_chain; 102: cs_cuboid_batch_set_lines, cs_cuboid_batch_set_shared_gpu, cs_lsd_read_filter_lines; 101: cs_ba_set_stop_flag_bool / cs_ba_dyn_set_stop_flag_bool; cs_match_by_projection_frame takes train_blocked */
+#define CS_VERSION 108 /* 108: cs_stereo_* (Frame::ComputeStereoMatches on the extractor's resident buffers); 107: cs_match_by_projection_stream takes n_queries / n_train, cs_cuboid_batch_set_boxes, the matchers' claim passes run on the device; 106: cs_cuboid_batch_n_frames, cs_frontend_queues, cs_match_by_projection_stream, cs_frontend_stream_*, cs_*_set_frames_device, cs_orb_read_packed; 105: cs_frontend_set_backlog; 104: cs_frontend_set_cuboid_ctx; 103: cs_lsd_read_filter_lines takes the caller's frame count, cs_frontend_set_chain; 102: cs_cuboid_batch_set_lines, cs_cuboid_batch_set_shared_gpu, cs_lsd_read_filter_lines; 101: cs_ba_set_stop_flag_bool / cs_ba_dyn_set_stop_flag_bool; cs_match_by_projection_frame takes train_blocked */
 
 typedef enum cs_status {
     CS_OK = 0,
@@ -215,6 +215,34 @@ int cs_orb_read_packed(cs_ctx *ctx, cs_orb *e, cs_keypoint *kps, uint8_t *desc, 
  * the FAST keypoints handed to DistributeOctTree (x, y, response; cell-major order). */
 int cs_orb_get_level(cs_ctx *ctx, cs_orb *e, int frame, int level, int blurred, uint8_t *out, int *w, int *h);
 int cs_orb_get_candidates(cs_ctx *ctx, cs_orb *e, int frame, int level, float *xyr, int cap, int *n);
+
+/* ===================================================================== Stereo association
+ * Replaces ORB_SLAM2::Frame::ComputeStereoMatches (orb_object_slam/src/Frame.cc:611-783, called at :118 after the two extractions of the stereo
+ * constructor, :106-110): fills mvuRight / mvDepth for rectified stereo pairs from what cs_orb_run left on the device (key points, descriptors and
+ * mvImagePyramid of both extractors), bit-identical to the reference's arithmetic.  GPU: row / octave / disparity-range tests and 256-bit Hamming
+ * distances (:639-692), the 11 x 11 SAD search over 11 shifts at the left key point's level with the parabola fit (:696-765), the median cut (:769-782).
+ * What is undefined in the reference (a row index outside the image, a patch that leaves its level, zero accepted matches) is guarded and ends as
+ * unmatched; it cannot occur for key points that come from the extractor. */
+typedef struct cs_stereo cs_stereo;
+/* Room for max_pairs pairs of at most max_keypoints_per_frame key points per image (left and right). */
+int cs_stereo_create(cs_ctx *ctx, int max_keypoints_per_frame, int max_pairs, cs_stereo **out);
+void cs_stereo_destroy(cs_ctx *ctx, cs_stereo *s);
+/* Frame::ComputeStereoMatches (Frame.cc:611-783) for n_pairs pairs: pair p = frame left_first + p of `left`'s last cs_orb_run against frame
+ * right_first + p of `right`'s.  left == right is allowed (one extractor run over 2F images, left_first = 0, right_first = F).  Both extractors
+ * must agree in image size, nlevels and scaleFactor (CS_ERR_BAD_ARG otherwise, as for n_pairs outside either run or above max_pairs, bf <= 0, b <= 0);
+ * CS_ERR_CAPACITY when a frame has more key points than the handle was created for.  bf = mbf, b = mb (minZ = mb, maxD = mbf / mb, :639-641): the
+ * reference's stereo constructor sets mb = mbf / fx at Frame.cc:141, after the call at :118, so the caller passes the value it means.  Queues the
+ * kernels on the context's stream and returns; the results stay on the device. */
+int cs_stereo_match_from_orb(cs_ctx *ctx, cs_stereo *s, const cs_orb *left, int left_first, const cs_orb *right, int right_first, int n_pairs, float bf, float b);
+/* mvuRight / mvDepth of the last call: pair p's counts[p] values at u_right[p * cap_per_frame ...] / depth[...], -1 where unmatched (:613-614);
+ * n_matched[p] = matches left after the cut.  CS_ERR_CAPACITY (nothing copied) when a pair has more than cap_per_frame left key points. */
+int cs_stereo_read(cs_ctx *ctx, cs_stereo *s, float *u_right, float *depth, int cap_per_frame, int *counts, int *n_matched);
+/* The same packed like cs_orb_read_packed: pair p = first[p] .. first[p + 1] (n_pairs + 1 entries), two copies for the whole batch.  u_right / depth NULL:
+ * only *total and first are filled (size query); CS_ERR_CAPACITY when cap_total < *total.  n_matched may be NULL. */
+int cs_stereo_read_packed(cs_ctx *ctx, cs_stereo *s, float *u_right, float *depth, long cap_total, int *first, long *total, int *n_matched);
+/* Device pointers of pair `pair`'s mvuRight / mvDepth (*n floats each, valid until the next call on this handle) for a caller that feeds
+ * cs_match_fuse / cs_pose_optimization next; work queued on the context's stream after the call sees the results. */
+int cs_stereo_device_pair(const cs_stereo *s, int pair, const float **d_u_right, const float **d_depth, int *n);
 
 /* ===================================================================== ORBmatcher
  * Replaces the Hamming searches of ORB_SLAM2::ORBmatcher (orb_object_slam/include/ORBmatcher.h:43-89, src/ORBmatcher.cc)

@@ -1,0 +1,250 @@
+"""GPU parity of the stereo association (cs_stereo_*, Frame::ComputeStereoMatches, Frame.cc:611-783) through the C-ABI: mvuRight / mvDepth byte for byte
+against tests/stereo_restatement.py fed with what cs_orb_read and cs_orb_get_level return for the same run.  No tolerance anywhere: the arithmetic is
+integer or single float operations in a fixed order.  Every pair generated is compared whole, and its matched share is asserted so that an all -1 result on
+both sides cannot pass as agreement (floors: 40 % for the fixed bands, 35 % for the batch; the checker on the CPU oracle's key points gives 48.0 - 50.7 % and
+41.2 - 57.2 %, tests/test_stereo_restatement.py)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from cube_slam_amd import _lib
+from cube_slam_amd.orb import ORBextractor
+from cube_slam_amd.stereo import ComputeStereoMatches, StereoMatcher
+from tests import stereo_restatement as sr
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+B = sr.BF / sr.FX
+BAD_ARG, CAPACITY = -2, -4
+
+
+def _extract(ctx, images, nfeat, W, H):
+    ext = ORBextractor(nfeat, 1.2, 8, 20, 7, W, H, max_frames=len(images), ctx=ctx)
+    ext.upload(np.stack(images))
+    ext.run()
+    return ext, ext.read()
+
+
+def _restate(extL, resL, fL, extR, resR, fR, bf=sr.BF, b=B, stats=None):
+    kl, dl = resL[fL]
+    kr, dr = resR[fR]
+    return sr.compute_stereo_matches(kl, dl, kr, dr, [extL.level(fL, l) for l in range(8)], [extR.level(fR, l) for l in range(8)],
+                                     extL.GetScaleFactors(), extL.GetInverseScaleFactors(), bf, b, stats=stats)
+
+
+def _same(got, want):
+    (gu, gd), (wu, wd) = got, want[:2]
+    assert gu.dtype == np.float32 and gd.dtype == np.float32 and len(gu) == len(wu)
+    assert gu.tobytes() == wu.tobytes(), "mvuRight: %d of %d differ" % (int((gu != wu).sum()), len(gu))
+    assert gd.tobytes() == wd.tobytes(), "mvDepth: %d of %d differ" % (int((gd != wd).sum()), len(gd))
+
+
+def _pairs_on_device(ctx, lefts, rights, nfeat, W, H, bf=sr.BF, b=B):
+    """Two extractors, one association call over all pairs; returns what the device gave and what the checker gives for the same extraction."""
+    extL, resL = _extract(ctx, lefts, nfeat, W, H)
+    extR, resR = _extract(ctx, rights, nfeat, W, H)
+    m = StereoMatcher(max(extL.cap, extR.cap), len(lefts), ctx=ctx)
+    m.match(extL, extR, bf, b)
+    got, nm = m.read()
+    out = []
+    for p in range(len(lefts)):
+        st = {}
+        want = _restate(extL, resL, p, extR, resR, p, bf, b, stats=st)
+        out.append((got[p], int(nm[p]), want, st, resL[p][0]))
+    m.close(); extL.close(); extR.close()
+    return out
+
+
+@pytest.mark.parametrize("W,H,nfeat,seed", [(1241, 376, 2000, 1), (1241, 376, 2000, 2), (1241, 376, 2000, 3), (640, 480, 1000, 1), (640, 480, 1000, 2), (640, 480, 1000, 3),
+                                            (752, 480, 1000, 1)])
+def test_fixed_bands_equal_restatement(ctx, W, H, nfeat, seed):
+    left, right, truth = sr.pair(seed, W, H, sr.FIXED_BANDS)
+    (got, nm, want, st, kl), = _pairs_on_device(ctx, [left], [right], nfeat, W, H)
+    print(W, H, seed, len(kl), st, nm)
+    _same(got, want)
+    assert nm == want[2] == int((got[1] > 0).sum())
+    assert nm >= 0.40 * len(kl)
+    assert np.median(sr.disparity_error(kl, got[0], truth)) <= 0.5
+
+
+def test_wide_bands_equal_restatement(ctx):
+    """Bands 300, 500, 650, 10 at 1241 x 376: minU = uL - mbf / mb cuts the candidates of the wide bands (maxD = 718.856), and the right image shares only
+    W - d columns with the left one.  The column exit of Frame.cc:716-719 stays unreached: an extractor key point is never within 11 level pixels of a border."""
+    left, right, truth = sr.pair(1, 1241, 376, [300.0, 500.0, 650.0, 10.0])
+    (got, nm, want, st, kl), = _pairs_on_device(ctx, [left], [right], 2000, 1241, 376)
+    print(st, nm)
+    _same(got, want)
+    assert nm == want[2] and nm >= 0.25 * len(kl)  # the checker on the CPU oracle's key points keeps 808 of 2006
+
+
+def test_batch_of_64_equals_single_calls_and_restatement(ctx):
+    W, H, nfeat, seeds = 640, 480, 1000, list(range(100, 164))
+    imgs = [sr.pair(s, W, H, sr.batch_bands(s)) for s in seeds]
+    lefts, rights = [i[0] for i in imgs], [i[1] for i in imgs]
+    extL, resL = _extract(ctx, lefts, nfeat, W, H)
+    extR, resR = _extract(ctx, rights, nfeat, W, H)
+    m = StereoMatcher(extL.cap, 64, ctx=ctx)
+    m.match(extL, extR, sr.BF, B)
+    batch, nm = m.read()
+    pu, pd, first, pnm = m.read_packed()
+    assert np.array_equal(pnm, nm) and first[0] == 0 and first[-1] == len(pu) == sum(len(k) for k, _ in resL)
+    for p in range(64):
+        assert pu[first[p]:first[p + 1]].tobytes() == batch[p][0].tobytes() and pd[first[p]:first[p + 1]].tobytes() == batch[p][1].tobytes()
+    # the 64 single calls
+    for p in range(64):
+        m.match(extL, extR, sr.BF, B, left_first=p, right_first=p, n_pairs=1)
+        (one,), nm1 = m.read()
+        assert one[0].tobytes() == batch[p][0].tobytes() and one[1].tobytes() == batch[p][1].tobytes() and nm1[0] == nm[p], p
+    # one extractor that holds the left and the right halves
+    ext2, res2 = _extract(ctx, lefts + rights, nfeat, W, H)
+    m2 = StereoMatcher(ext2.cap, 64, ctx=ctx)
+    m2.match(ext2, ext2, sr.BF, B, left_first=0, right_first=64, n_pairs=64)
+    both, nm2 = m2.read()
+    assert np.array_equal(nm2, nm)
+    for p in range(64):
+        assert both[p][0].tobytes() == batch[p][0].tobytes() and both[p][1].tobytes() == batch[p][1].tobytes(), p
+    # the Python mirror's batch form
+    mirror = ComputeStereoMatches(ext2, ext2, sr.BF, B, left_first=0, right_first=64)
+    assert len(mirror) == 64 and all(mirror[p][0].tobytes() == batch[p][0].tobytes() for p in range(64))
+    # ... and the checker, pair by pair
+    shares = []
+    for p in range(64):
+        want = _restate(extL, resL, p, extR, resR, p)
+        _same(batch[p], want)
+        assert nm[p] == want[2]
+        n = len(resL[p][0])
+        shares.append(nm[p] / n)
+        assert nm[p] >= 0.35 * n, (seeds[p], nm[p], n)
+        assert np.median(sr.disparity_error(resL[p][0], batch[p][0], imgs[p][2])) <= 0.5
+    print("matched share %.3f - %.3f" % (min(shares), max(shares)))
+    m.close(); m2.close(); extL.close(); extR.close(); ext2.close()
+
+
+def test_identical_images(ctx):
+    left = sr.pair(1, 640, 480, [0.0], noise=0.0)[0]
+    (got, nm, want, st, kl), = _pairs_on_device(ctx, [left], [left], 1000, 640, 480)
+    _same(got, want)
+    assert st["accepted"] > 100 and nm == 0 and np.all(got[0] == -1) and np.all(got[1] == -1)  # found, then every one removed by the median SAD of 0
+
+
+def test_empty_sides(ctx):
+    left = sr.pair(1, 640, 480, [5.0])[0]
+    flat = np.full_like(left, 90)
+    res = _pairs_on_device(ctx, [left, flat], [flat, left], 1000, 640, 480)  # Nr = 0, then N = 0, in one batch
+    (got, nm, want, st, kl) = res[0]
+    _same(got, want)
+    assert len(kl) > 0 and len(got[0]) == len(kl) and nm == 0 and np.all(got[0] == -1) and np.all(got[1] == -1)
+    (got, nm, want, st, kl) = res[1]
+    assert len(kl) == 0 and len(got[0]) == 0 and len(got[1]) == 0 and nm == 0
+    # a run in which every image is empty
+    (got, nm, want, st, kl), = _pairs_on_device(ctx, [flat], [flat], 1000, 640, 480)
+    assert len(got[0]) == 0 and nm == 0
+
+
+def test_zero_disparity_reaches_the_clamp(ctx):
+    """Seeds 1-24 in one call; the clamp (Frame.cc:757-761) is reached in a few pairs of the set (see the CPU test of the same name)."""
+    imgs = [sr.pair(s, 640, 480, [0.0]) for s in range(1, 25)]
+    res = _pairs_on_device(ctx, [i[0] for i in imgs], [i[1] for i in imgs], 1000, 640, 480)
+    seen = 0
+    for got, nm, want, st, kl in res:
+        _same(got, want)
+        assert nm == want[2] and nm >= 0.25 * len(kl)  # the checker on the CPU oracle's key points keeps 333 - 403 of ~1004
+        clamped = got[1] == f32(f32(sr.BF) / f32(0.01))
+        assert np.array_equal(got[0][clamped], (kl["x"][clamped].astype(np.float64) - 0.01).astype(f32))
+        seen += int(clamped.sum())
+    assert seen >= 1
+
+
+def test_negative_disparities_are_rejected(ctx):
+    left, right, truth = sr.pair(1, 640, 480, [-2.0, -1.0, 0.0, 0.5])
+    (got, nm, want, st, kl), = _pairs_on_device(ctx, [left], [right], 1000, 640, 480)
+    print(st, nm)
+    _same(got, want)
+    assert st["disparity"] > 100 and nm == want[2] and nm >= 100  # the checker on the CPU oracle's key points: 496 rejected, 181 kept
+    m = got[0] >= 0
+    assert np.all(kl["x"][m] - got[0][m] > 0)
+
+
+def test_capacity(ctx):
+    """A handle made for exactly the larger key-point count of the run works; one below it is CS_ERR_CAPACITY."""
+    nfeat = int(np.random.default_rng(7).integers(700, 1300))
+    left, right, truth = sr.pair(5, 640, 480, sr.FIXED_BANDS)
+    extL, resL = _extract(ctx, [left], nfeat, 640, 480)
+    extR, resR = _extract(ctx, [right], nfeat, 640, 480)
+    n = max(len(resL[0][0]), len(resR[0][0]))
+    m = StereoMatcher(n, 1, ctx=ctx)
+    m.match(extL, extR, sr.BF, B)
+    (got,), nm = m.read()
+    want = _restate(extL, resL, 0, extR, resR, 0)
+    _same(got, want)
+    assert nm[0] == want[2] and nm[0] >= 0.40 * len(resL[0][0])
+    # cap_per_frame of the read one below the pair's count
+    lib = _lib.lib()
+    k = len(resL[0][0])
+    u, d = np.zeros(k, np.float32), np.zeros(k, np.float32)
+    cnt, nmb = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    pf = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    assert lib.cs_stereo_read(ctx.ptr, m._s, pf(u), pf(d), k - 1, pi(cnt), pi(nmb)) == CAPACITY
+    assert lib.cs_stereo_read(ctx.ptr, m._s, pf(u), pf(d), k, pi(cnt), pi(nmb)) == 0 and u.tobytes() == got[0].tobytes()
+    m.close()
+    small = StereoMatcher(n - 1, 1, ctx=ctx)
+    assert lib.cs_stereo_match_from_orb(ctx.ptr, small._s, extL._e, 0, extR._e, 0, 1, C.c_float(sr.BF), C.c_float(B)) == CAPACITY
+    small.close(); extL.close(); extR.close()
+
+
+def test_bad_arguments(ctx):
+    lib = _lib.lib()
+    left, right, _ = sr.pair(1, 640, 480, sr.FIXED_BANDS)
+    extL, _ = _extract(ctx, [left], 1000, 640, 480)
+    extR, _ = _extract(ctx, [right], 1000, 640, 480)
+    m = StereoMatcher(extL.cap, 2, ctx=ctx)
+    call = lambda l, lf, r, rf, n, bf, b: lib.cs_stereo_match_from_orb(ctx.ptr, m._s, l._e, lf, r._e, rf, n, C.c_float(bf), C.c_float(b))
+    assert call(extL, 0, extR, 0, 1, sr.BF, B) == 0
+    assert call(extL, 0, extR, 0, 2, sr.BF, B) == BAD_ARG  # outside the last run
+    assert call(extL, 1, extR, 0, 1, sr.BF, B) == BAD_ARG
+    assert call(extL, 0, extR, 1, 1, sr.BF, B) == BAD_ARG
+    assert call(extL, 0, extR, 0, 3, sr.BF, B) == BAD_ARG  # above max_pairs
+    assert call(extL, 0, extR, 0, 0, sr.BF, B) == BAD_ARG
+    assert call(extL, 0, extR, 0, 1, 0.0, B) == BAD_ARG and call(extL, 0, extR, 0, 1, sr.BF, 0.0) == BAD_ARG and call(extL, 0, extR, 0, 1, sr.BF, -1.0) == BAD_ARG
+    assert lib.cs_stereo_match_from_orb(ctx.ptr, m._s, None, 0, extR._e, 0, 1, C.c_float(sr.BF), C.c_float(B)) == BAD_ARG
+    fresh = ORBextractor(1000, 1.2, 8, 20, 7, 640, 480, ctx=ctx)  # no run yet
+    assert lib.cs_stereo_match_from_orb(ctx.ptr, m._s, fresh._e, 0, extR._e, 0, 1, C.c_float(sr.BF), C.c_float(B)) == BAD_ARG
+    for other in (ORBextractor(1000, 1.2, 8, 20, 7, 752, 480, ctx=ctx), ORBextractor(1000, 1.2, 7, 20, 7, 640, 480, ctx=ctx), ORBextractor(1000, 1.25, 8, 20, 7, 640, 480, ctx=ctx)):
+        other.upload(np.zeros((other.H, other.W), np.uint8))
+        other.run()
+        assert call(extL, 0, other, 0, 1, sr.BF, B) == BAD_ARG  # geometry differs
+        other.close()
+    u, d, n = C.c_void_p(), C.c_void_p(), C.c_int()
+    assert lib.cs_stereo_device_pair(m._s, 1, C.byref(u), C.byref(d), C.byref(n)) == BAD_ARG
+    assert lib.cs_stereo_device_pair(m._s, 0, C.byref(u), C.byref(d), C.byref(n)) == 0 and n.value > 0
+    with pytest.raises(_lib.CubeSlamError):
+        m.match(extL, extR, -1.0, B)
+    fresh.close(); m.close(); extL.close(); extR.close()
+
+
+def test_device_hand_over(ctx):
+    """cs_stereo_device_pair: what a caller that feeds cs_match_fuse / cs_pose_optimization next reads on the device is what cs_stereo_read returns."""
+    import torch
+    imgs = [sr.pair(s, 640, 480, sr.FIXED_BANDS) for s in (11, 12, 13)]
+    extL, resL = _extract(ctx, [i[0] for i in imgs], 1000, 640, 480)
+    extR, resR = _extract(ctx, [i[1] for i in imgs], 1000, 640, 480)
+    m = StereoMatcher(extL.cap, 3, ctx=ctx)
+    m.match(extL, extR, sr.BF, B)
+    ctx.sync()
+
+    class _Dev:
+        def __init__(self, ptr, n):
+            self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False), "version": 3}
+
+    res, nm = m.read()
+    for p in range(3):
+        pu, pd, n = m.device_pair(p)
+        assert n == len(resL[p][0]) > 0
+        assert torch.as_tensor(_Dev(pu, n), device="cuda").cpu().numpy().tobytes() == res[p][0].tobytes()
+        assert torch.as_tensor(_Dev(pd, n), device="cuda").cpu().numpy().tobytes() == res[p][1].tobytes()
+        assert nm[p] >= 0.40 * n
+    single = ComputeStereoMatches(extL, extR, sr.BF, B, left_first=1, right_first=1, n_pairs=1)
+    assert single[0][0].tobytes() == res[1][0].tobytes()
+    m.close(); extL.close(); extR.close()

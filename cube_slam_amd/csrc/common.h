@@ -166,6 +166,24 @@ template <class T> static inline int cs_d2h(cs_ctx *ctx, T *h, const T *d, size_
     CS_HIP(ctx, hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
     return CS_OK;
 }
+// A host buffer in pinned memory for a recurring hand-over: the copy engine reads / writes it directly, where a pageable std::vector costs the
+// runtime a second copy through its staging buffer while the calling thread waits.  It only grows (a request beyond the capacity reallocates
+// and does not keep the contents); the owner calls release().  A copy into or out of it is asynchronous: synchronise before the host reads it
+// or writes it again.
+template <class T> struct cs_pinned {
+    T *p = nullptr;
+    size_t cap = 0;
+    int reserve(cs_ctx *ctx, size_t n) {
+        if (n <= cap) return CS_OK;
+        release();
+        const size_t c = n + n / 4 + 256;
+        void *q = nullptr;
+        CS_HIP(ctx, hipHostMalloc(&q, c * sizeof(T), hipHostMallocDefault));
+        p = static_cast<T *>(q); cap = c;
+        return CS_OK;
+    }
+    void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
+};
 
 // ---- device helpers -------------------------------------------------------------------------------------------
 // 64-lane inclusive min-scan with DPP (row_shr 1/2/4/8 inside 16-lane rows, then row_bcast:15 / row_bcast:31).

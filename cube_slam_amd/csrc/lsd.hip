@@ -2,9 +2,9 @@
 //
 // Replaces line_lbd_detect::detect_raw_lines / detect_filter_lines (reference line_lbd/class/line_lbd_allclass.cpp:125-148,
 // 200-221) -> LSDDetector::detectImpl (libs/LSDDetector.cpp:153-287) -> LineSegmentDetectorImpl::flsd (libs/lsd.cpp:440-536).
-//   lsd_blur_hv               GaussianBlur(7x7, sigma 0.75) u8 -> double, REFLECT_101, symmetric summation order, both passes fused
-//   lsd_resize                cv::resize(0.8, 0.8, INTER_LINEAR) on CV_64F with float coefficients (tables from the host)
-//   lsd_gradient              ll_angle (:538-585): 2x2 gradient, norm, level-line angle via cv::fastAtan2, NOTDEF below rho
+//   lsd_maps                  in one row-streaming pass: GaussianBlur(7x7, sigma 0.75) u8 -> double, REFLECT_101, symmetric summation order;
+//                             cv::resize(0.8, 0.8, INTER_LINEAR) on CV_64F with float coefficients (tables from the host);
+//                             ll_angle (:538-585): 2x2 gradient, norm, level-line angle via cv::fastAtan2, NOTDEF below rho
 // Host, per frame (OpenMP across frames): the sequential part of the algorithm, seeds in address order (see LsdHost::run) --
 // region_grow (each accepted pixel updates the region angle that the next test uses, :665-683), region2rect, refine,
 // rect_improve, rect_nfa, nfa -- which has no order-preserving parallel form.  Double precision as in the reference.
@@ -38,106 +38,119 @@ __device__ __forceinline__ int reflect101d(int p, int len) { if (len == 1) retur
 
 struct GK { double k[2 * KH + 1]; };
 
-// GaussianBlur(7x7, sigma 0.75) of the u8 frame into doubles, both passes in one row-streaming kernel: one wave per 64-column
-// strip and LSD_ROWS output rows, one column per lane.  Every input row is loaded once (8 rows in flight), filtered horizontally
-// from an LDS line of bytes, and the last seven horizontal results stay in registers for the vertical pass -- the double
-// intermediate image (8 B written + 8 B x 7 read per pixel in the two-kernel version) never exists.  Summation order of both
-// passes as in OpenCV's symmetric filters: centre tap first, then k[t] * (left + right) for t = 1..3.
-constexpr int LSD_ROWS = 64;
-__global__ void __launch_bounds__(64) lsd_blur_hv(const uint8_t *gray, int W, int H, GK g, double *blur) {
-    const int strips = (W + 63) / 64;
-    const int sx = (blockIdx.x % strips) * 64, y0 = (blockIdx.x / strips) * LSD_ROWS, tid = threadIdx.x;
-    if (y0 >= H) return;
-    const int rows = min(LSD_ROWS, H - y0);
-    __shared__ uint8_t line[64 + 8]; // column sx + c at byte 3 + c
+// From the gray frame to the level-line maps in one row-streaming kernel: GaussianBlur(7x7, sigma 0.75, u8 -> double), cv::resize(0.8, INTER_LINEAR) and
+// ll_angle's 2x2 gradient -- neither the blurred frame (8 B per pixel) nor the scaled one (8 B per scaled pixel) makes the round trip through memory.
+// One wave per strip of 64 scaled columns and LSD_ROWS scaled rows.  The strip's blurred columns start at xofs[d0] and stay below 128 of them (83 at
+// scale 0.8, checked by cs_lsd_create): two per lane, lane j holds columns xofs[d0] + j and + 64 + j.  The gray rows are streamed downwards (8 in
+// flight), filtered horizontally from an LDS line of bytes, and the last seven horizontal results stay in registers for the vertical pass; the last two
+// blurred rows stay for the resize, whose taps reach the neighbouring columns by lane reads; the last scaled row stays for the gradient, the column
+// right of the strip computed by every lane.  A strip that starts a block re-reads three gray rows above and below and one scaled row below (halo).
+//   * blur: the summation order of OpenCV's symmetric filters, centre tap first, then k[t] * (left + right) for t = 1..3; REFLECT_101 borders
+//   * resize: (src[sy0][sx0] * ax0 + src[sy0][sx1] * ax1) * ay0 + (src[sy1][sx0] * ax0 + src[sy1][sx1] * ax1) * ay1, float coefficients from the host's tables
+//   * gradient: ll_angle :538-585; the level-line angle is kept as what ll_angle computes it from: cv::fastAtan2's FLOAT DEGREES (NOTDEF_DEG where
+//     undefined).  The map value of the reference is that float times DEG_TO_RADS in double (:566), which every reader forms itself.
+// Also counts the defined pixels of each (frame, row, strip): seg_cnt[(frame * h + y) * strips + strip].  scaled: the scaled frames, written only when
+// asked for (the host region stage's batches, whose maps cs_lsd_get_maps returns).
+constexpr int LSD_ROWS = 64, LSD_SPAN = 128;
+struct MapTabs { const int *xofs, *yofs; const float *ax, *ay; };
+__device__ __forceinline__ double strip_col(double s0, double s1, int p) { const double a = __shfl(s0, p & 63), b = __shfl(s1, p & 63); return p >= 64 ? b : a; } // blurred column p (0..127) of the strip
+__global__ void __launch_bounds__(64) lsd_maps(const uint8_t *gray, int W, int H, int w, int h, GK g, MapTabs T, double threshold, double *modgrad, float *angles, int *seg_cnt, double *scaled) {
+    const int strips = (w + 63) / 64;
+    const int strip = blockIdx.x % strips, d0 = strip * 64, y0 = (blockIdx.x / strips) * LSD_ROWS, lane = threadIdx.x;
+    if (y0 >= h) return;
+    const int dy_last = min(y0 + LSD_ROWS, h - 1); // scaled rows y0 .. dy_last: gradient rows y0 .. dy_last - 1
+    auto sy1_of = [&](int dy) { return min(T.yofs[dy] + 1, H - 1); };
+    const int b0 = T.xofs[d0], r_first = T.yofs[y0], r_last = sy1_of(dy_last); // blurred columns b0 + 0..127, blurred rows r_first .. r_last
+    const int dx = d0 + lane, dxc = min(dx, w - 1), de = min(d0 + 64, w - 1); // this lane's scaled column; the one right of the strip
+    const int p0 = T.xofs[dxc] - b0, p1 = min(T.xofs[dxc] + 1, W - 1) - b0, pe0 = T.xofs[de] - b0, pe1 = min(T.xofs[de] + 1, W - 1) - b0;
+    const double ax0 = T.ax[2 * dxc], ax1 = T.ax[2 * dxc + 1], ae0 = T.ax[2 * de], ae1 = T.ax[2 * de + 1];
+    __shared__ uint8_t line[LSD_SPAN + 8]; // gray column reflect101(b0 - 3 + i) at byte i
     const uint8_t *img = gray + (long)blockIdx.z * W * H;
-    double *out = blur + (long)blockIdx.z * W * H;
-    const int xc = reflect101d(sx + tid, W);
-    const int xh = tid < 3 ? reflect101d(sx - 3 + tid, W) : reflect101d(sx + 64 + (tid - 3), W); // halo columns, lanes 0..5
-    const int x = sx + tid;
-    double ring[7] = {0, 0, 0, 0, 0, 0, 0};
+    const int c0 = reflect101d(b0 - 3 + lane, W), c1 = reflect101d(b0 + 61 + lane, W), c2 = reflect101d(b0 + 125 + min(lane, 5), W); // bytes lane, 64 + lane, 128 + lane (lanes 0..5)
+    const long frame_px = (long)blockIdx.z * h;
+    double ra[7] = {0, 0, 0, 0, 0, 0, 0}, rb[7] = {0, 0, 0, 0, 0, 0, 0}; // horizontal results of the last seven gray rows, columns j / 64 + j
+    double pa = 0, pb = 0, qa = 0, qb = 0; // blurred rows r - 1 and r
+    double sp = 0, spn = 0;                // scaled row dy - 1 at this lane's column and the next one
+    int dy = y0;
+    auto grad_row = [&](int y, double top, double top_r, double bot, double bot_r) { // ll_angle of row y (< h - 1) from scaled rows y and y + 1
+        bool def = false;
+        if (dx < w) {
+            const long o = (frame_px + y) * w + dx;
+            if (dx >= w - 1) { modgrad[o] = 0; angles[o] = NOTDEF_DEG; } // right boundary undefined (:553-554)
+            else {
+                const double DA = bot_r - top, BC = top_r - bot;
+                const double gx = DA + BC, gy = DA - BC;
+                const double norm = sqrt((gx * gx + gy * gy) / 4);
+                modgrad[o] = norm;
+                def = !(norm <= threshold);
+                angles[o] = def ? fast_atan2f_(float(gx), float(-gy)) : NOTDEF_DEG;
+            }
+        }
+        const unsigned long long m = __ballot(def);
+        if (lane == 0) seg_cnt[(frame_px + y) * strips + strip] = __popcll(m);
+    };
+    auto row = [&](int k, uint8_t a, uint8_t b, uint8_t c) { // gray row r_first - 3 + k
+        line[lane] = a; line[64 + lane] = b;
+        if (lane < 6) line[128 + lane] = c;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        double xa[7], xb[7];
+#pragma unroll
+        for (int t = 0; t < 7; t++) { xa[t] = (double)line[lane + t]; xb[t] = (double)line[64 + lane + t]; } // columns -3 .. +3
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        double ha = g.k[KH] * xa[3], hb = g.k[KH] * xb[3];
+#pragma unroll
+        for (int t = 1; t <= KH; t++) { ha += g.k[KH + t] * (xa[3 - t] + xa[3 + t]); hb += g.k[KH + t] * (xb[3 - t] + xb[3 + t]); }
+#pragma unroll
+        for (int t = 0; t < 6; t++) { ra[t] = ra[t + 1]; rb[t] = rb[t + 1]; }
+        ra[6] = ha; rb[6] = hb;
+        if (k < 6) return;
+        const int r = r_first + k - 6;
+        double va = g.k[KH] * ra[3], vb = g.k[KH] * rb[3];
+#pragma unroll
+        for (int t = 1; t <= KH; t++) { va += g.k[KH + t] * (ra[3 - t] + ra[3 + t]); vb += g.k[KH + t] * (rb[3 - t] + rb[3 + t]); }
+        pa = qa; pb = qb; qa = va; qb = vb;
+        while (dy <= dy_last && sy1_of(dy) == r) { // the scaled rows whose lower tap row is r (sy1 never decreases; its upper tap row is r - 1, or r at the bottom clamp)
+            const bool same = T.yofs[dy] == r;
+            const double ua = same ? qa : pa, ub = same ? qb : pb, ay0 = T.ay[2 * dy], ay1 = T.ay[2 * dy + 1];
+            auto resize = [&](int q0, int q1, double w0, double w1) {
+                const double r0 = strip_col(ua, ub, q0) * w0 + strip_col(ua, ub, q1) * w1;
+                const double r1 = strip_col(qa, qb, q0) * w0 + strip_col(qa, qb, q1) * w1;
+                return r0 * ay0 + r1 * ay1;
+            };
+            const double s = resize(p0, p1, ax0, ax1), se = resize(pe0, pe1, ae0, ae1);
+            const double sr = __shfl(s, (lane + 1) & 63), sn = lane == 63 ? se : sr; // (the lane read outside the select: a lane left out of it would read as 0)
+            if (scaled && dx < w && dy < y0 + LSD_ROWS) scaled[(frame_px + dy) * w + dx] = s; // (row y0 + LSD_ROWS is the next block's)
+            if (dy > y0) grad_row(dy - 1, sp, spn, s, sn);
+            sp = s; spn = sn; dy++;
+        }
+    };
     constexpr int G = 8;
-    const int total = rows + 6;
-    uint8_t cur[G], nxt[G], curh[G], nxth[G];
-    auto fetch = [&](int r0, uint8_t (&a)[G], uint8_t (&hh)[G]) {
+    const int total = r_last - r_first + 7; // gray rows r_first - 3 .. r_last + 3
+    uint8_t ca[G], cb[G], cc[G], na[G], nb[G], nc[G];
+    auto fetch = [&](int k0, uint8_t (&a)[G], uint8_t (&b)[G], uint8_t (&c)[G]) {
 #pragma unroll
         for (int u = 0; u < G; u++) {
-            a[u] = 0; hh[u] = 0;
-            if (r0 + u < total) {
-                const uint8_t *row = img + (long)reflect101d(y0 + r0 + u - 3, H) * W;
-                a[u] = row[xc];
-                if (tid < 6) hh[u] = row[xh];
+            a[u] = 0; b[u] = 0; c[u] = 0;
+            if (k0 + u < total) {
+                const uint8_t *src = img + (long)reflect101d(r_first - 3 + k0 + u, H) * W;
+                a[u] = src[c0]; b[u] = src[c1];
+                if (lane < 6) c[u] = src[c2];
             }
         }
     };
-    fetch(0, cur, curh);
-    for (int r0 = 0; r0 < total; r0 += G) {
-        fetch(r0 + G, nxt, nxth);
+    fetch(0, ca, cb, cc);
+    for (int k0 = 0; k0 < total; k0 += G) {
+        fetch(k0 + G, na, nb, nc);
 #pragma unroll
-        for (int u = 0; u < G; u++) {
-            const int r = r0 + u;
-            if (r < total) {
-                line[3 + tid] = cur[u];
-                if (tid < 3) line[tid] = curh[u];
-                else if (tid < 6) line[3 + 64 + (tid - 3)] = curh[u];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                double pix[7];
+        for (int u = 0; u < G; u++)
+            if (k0 + u < total) row(k0 + u, ca[u], cb[u], cc[u]);
 #pragma unroll
-                for (int t = 0; t < 7; t++) pix[t] = (double)line[tid + t]; // columns x-3 .. x+3
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                double h = g.k[KH] * pix[3];
-#pragma unroll
-                for (int t = 1; t <= KH; t++) h += g.k[KH + t] * (pix[3 - t] + pix[3 + t]);
-#pragma unroll
-                for (int t = 0; t < 6; t++) ring[t] = ring[t + 1];
-                ring[6] = h;
-                if (r >= 6 && x < W) {
-                    double v = g.k[KH] * ring[3];
-#pragma unroll
-                    for (int t = 1; t <= KH; t++) v += g.k[KH + t] * (ring[3 - t] + ring[3 + t]);
-                    out[(long)(y0 + r - 6) * W + x] = v;
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < G; u++) { cur[u] = nxt[u]; curh[u] = nxth[u]; }
+        for (int u = 0; u < G; u++) { ca[u] = na[u]; cb[u] = nb[u]; cc[u] = nc[u]; }
     }
-}
-__global__ void __launch_bounds__(256) lsd_resize(const double *blur, int W, int H, int w, int h, const int *xofs, const float *ax, const int *yofs, const float *ay,
-                                                  double *scaled) {
-    const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
-    if (dx >= w) return;
-    const double *src = blur + (long)blockIdx.z * H * W;
-    const int sx0 = xofs[dx], sx1 = min(sx0 + 1, W - 1), sy0 = yofs[dy], sy1 = min(sy0 + 1, H - 1);
-    const double r0 = src[(long)sy0 * W + sx0] * ax[dx * 2] + src[(long)sy0 * W + sx1] * ax[dx * 2 + 1];
-    const double r1 = src[(long)sy1 * W + sx0] * ax[dx * 2] + src[(long)sy1 * W + sx1] * ax[dx * 2 + 1];
-    scaled[((long)blockIdx.z * h + dy) * w + dx] = r0 * ay[dy * 2] + r1 * ay[dy * 2 + 1];
-}
-// also counts the defined pixels of its 256-pixel row segment: seg_cnt[(frame * h + y) * gridDim.x + blockIdx.x]
-// The level-line angle is kept as what ll_angle computes it from: cv::fastAtan2's FLOAT DEGREES (NOTDEF_DEG where undefined).  The map value of the reference is that float times
-// DEG_TO_RADS in double (:566), which every reader forms itself -- 4 bytes per pixel instead of 8, and lsd_emit no longer has to divide its way back to the float.
-__global__ void __launch_bounds__(256) lsd_gradient(const double *scaled, int w, int h, double threshold, double *modgrad, float *angles, int *seg_cnt) {
-    __shared__ int wc[4];
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    bool def = false;
-    if (x < w) {
-        const double *img = scaled + (long)blockIdx.z * w * h;
-        const long o = ((long)blockIdx.z * h + y) * w + x;
-        if (x >= w - 1 || y >= h - 1) { modgrad[o] = 0; angles[o] = NOTDEF_DEG; } // down / right boundaries undefined (:553-554)
-        else {
-            const int addr = y * w + x;
-            const double DA = img[addr + w + 1] - img[addr], BC = img[addr + 1] - img[addr + w];
-            const double gx = DA + BC, gy = DA - BC;
-            const double norm = sqrt((gx * gx + gy * gy) / 4);
-            modgrad[o] = norm;
-            def = !(norm <= threshold);
-            angles[o] = def ? fast_atan2f_(float(gx), float(-gy)) : NOTDEF_DEG;
-        }
+    if (dy_last == h - 1 && y0 + LSD_ROWS >= h) { // the bottom row: undefined (:553-554)
+        if (dx < w) { const long o = (frame_px + h - 1) * w + dx; modgrad[o] = 0; angles[o] = NOTDEF_DEG; }
+        if (lane == 0) seg_cnt[(frame_px + h - 1) * strips + strip] = 0;
     }
-    const unsigned long long m = __ballot(def);
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) seg_cnt[((long)blockIdx.z * h + y) * gridDim.x + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 // exclusive scan of n ints (out has n + 1 entries, out[n] = total) in three coalesced passes: 1024-element blocks, their totals, add
 __global__ void __launch_bounds__(1024) lsd_scan_blocks(const int *in, int n, int *out, int *block_tot) {
@@ -215,7 +228,7 @@ template <bool PIX> __global__ void __launch_bounds__(256) lsd_emit(const double
     const float d = s_a[threadIdx.x];
     const double a = double(d) * DEG_TO_RADS; // the map value (:566)
     const long o = row + x;
-    const int pos = seg_base[((long)blockIdx.z * h + y) * gridDim.x + blockIdx.x] + threadIdx.x;
+    const int pos = seg_base[((long)blockIdx.z * h + y) * ((w + 63) / 64) + blockIdx.x * 4] + threadIdx.x; // (the counts are per 64-column strip of lsd_maps: this segment's first of four)
     // bit 31 of the address: no neighbour is aligned with this pixel's own angle (angles never change), so as a seed it stays alone -- region_grow's
     // first nine tests use exactly that angle -- and the host marks it used without testing anything (12 k of 25 k seeds on a textured frame are single)
     bool alone = true;
@@ -234,7 +247,8 @@ template <bool PIX> __global__ void __launch_bounds__(256) lsd_emit(const double
         }
     c_addr[pos] = (y * w + x) | (alone ? (int)0x80000000 : 0);
     if (PIX) { // (the device walk computes cos / sin of float(angle) at its window fetches; a seed starts its sums with cos / sin of the angle as a double :651-652)
-        c_cs[pos] = make_float2(float(cos(a)), float(sin(a)));
+        // a seed flagged alone never starts a sum (lsd_rg_seq marks it used without growing): no double cos / sin for it, half the defined pixels of a textured frame
+        c_cs[pos] = alone ? make_float2(0.f, 0.f) : make_float2(float(cos(a)), float(sin(a)));
     } else {
         const float pc = glibc_sincosf::cosf_(float(a)), ps = glibc_sincosf::sinf_(float(a));
         c_deg[pos] = d;
@@ -576,11 +590,11 @@ struct cs_lsd {
     int region_stage = 0; // cs_lsd_set_region_stage: CS_LSD_REGIONS_AUTO / _HOST / _WAVE_PER_FRAME / _BACKLOG
     GK gk{};
     double threshold = 0;
-    size_t pix_bytes = 0; bool scaled_kept = true;           // the arena d_tmp = [d_blur | d_scaled], later [region stage's pixel records (pix_bytes) | LBD blur]
-    uint8_t *d_gray = nullptr; double *d_tmp = nullptr, *d_blur = nullptr, *d_scaled = nullptr, *d_mod = nullptr; float *d_ang = nullptr; // d_ang: float degrees (see lsd_gradient)
+    size_t pix_bytes = 0; bool scaled_kept = true;           // the arena d_tmp = [(unused) | d_scaled] while lsd_maps runs, later [region stage's pixel records (pix_bytes) | LBD blur]
+    uint8_t *d_gray = nullptr; double *d_tmp = nullptr, *d_scaled = nullptr, *d_mod = nullptr; float *d_ang = nullptr; // d_ang: float degrees (see lsd_maps)
     int *d_xofs = nullptr, *d_yofs = nullptr; float *d_ax = nullptr, *d_ay = nullptr;
-    int nbx = 0;                                            // 256-pixel segments per scaled row
-    int *d_seg_cnt = nullptr, *d_seg_base = nullptr;        // per (frame, row, segment) defined-pixel count / exclusive scan
+    int nbx = 0, nsx = 0;                                   // 256-pixel segments (lsd_emit) / 64-pixel strips (lsd_maps) per scaled row
+    int *d_seg_cnt = nullptr, *d_seg_base = nullptr;        // per (frame, row, strip) defined-pixel count / exclusive scan
     int *d_blk_tot = nullptr;                               // totals of the 1024-segment scan blocks
     int *d_caddr = nullptr; float *d_cdeg = nullptr; float2 *d_ccs = nullptr; double *d_cmod = nullptr; size_t ccap = 0;   // compacted defined pixels (device): address, angle, cos / sin, norm
     int *h_caddr = nullptr; float *h_cdeg = nullptr; float2 *h_ccs = nullptr; double *h_cmod = nullptr; size_t hcap = 0;   // same, pinned host
@@ -591,7 +605,8 @@ struct cs_lsd {
     cs_keyline *d_kl = nullptr; int *d_line_frame = nullptr; uint8_t *d_desc = nullptr;
     size_t line_cap = 0;
     std::vector<int> line_off;       // per frame offset into the concatenated line list
-    std::vector<uint8_t> h_desc;     // concatenated n x 32
+    cs_pinned<uint8_t> h_desc;       // concatenated n x 32 (pinned, as the KeyLine upload and its frame index below: cs_lsd_destroy frees them)
+    cs_pinned<cs_keyline> h_kl; cs_pinned<int> h_lf;
     bool have_desc = false;
     LsdSeq *seq = nullptr;           // device buffers of the region stage (lsd_regions.hip)
     int seq_wpb = 16; // frames per workgroup of the device region stage (cs_lsd_set_shared_gpu)
@@ -622,20 +637,33 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     if (!ctx || !l || l->n_frames < 1) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     const int W = l->W, H = l->H, w = l->w, h = l->h, F = l->n_frames;
-    l->have_desc = false; l->scaled_kept = true;
-    // d_blur and d_scaled (doubles: 2.5 + 1.6 MB per frame) only live from one kernel to the next: they are the two halves of one arena (d_tmp) that the device region stage
-    // takes over for its pixel records once lsd_gradient is through, and the LBD blur for its one-kernel life (see below): 4.0 MB per frame that are not allocated twice
-    CS_LAUNCH(ctx, "lsd_blur_hv", lsd_blur_hv, dim3(((W + 63) / 64) * ((H + LSD_ROWS - 1) / LSD_ROWS), 1, F), dim3(64), 0, l->d_gray, W, H, l->gk, l->d_blur);
-    CS_LAUNCH(ctx, "lsd_resize", lsd_resize, dim3((w + 255) / 256, h, F), dim3(256), 0, l->d_blur, W, H, w, h, l->d_xofs, l->d_ax, l->d_yofs, l->d_ay, l->d_scaled);
-    const int nbx = l->nbx, n_seg = F * h * nbx;
-    CS_LAUNCH(ctx, "lsd_gradient", lsd_gradient, dim3(nbx, h, F), dim3(256), 0, l->d_scaled, w, h, l->threshold, l->d_mod, l->d_ang, l->d_seg_cnt);
+    l->have_desc = false;
+    // region growing / rectangles / NFA (a15): interchangeable stages with byte-identical KeyLines (tests/test_lsd_gpu.py).
+    //   seq    one wave per frame (lsd_rg_seq.h): ~110 ms per frame, 36 k frames/s with the chip full of them -- the default from 512 frames on;
+    //   wlk    a walker wave with one lane per frame that seeds and grows + rectangle waves for the regions it parks, one workgroup (lsd_rg_wlk.h): 64 frames per
+    //          wave slot instead of one, ~450 ms per frame -- for a backlog nobody waits for, by name only (DESIGN 7.3c; round 4's grp / grp2 / lpf are gone);
+    //   host   the OpenMP stage below, one frame per thread -- the default for smaller batches (one frame: 4 ms).
+    // cs_lsd_set_region_stage picks one per detector (a caller with a backlog nobody waits for takes wlk: 3.7 x seq's frames/s with the chip full of it); the
+    // development override CUBESLAM_LSD_REGIONS = seq | wlk | host comes first (tests, tools).  Decided before the maps: only a batch for the host stage keeps
+    // its scaled frames (cs_lsd_get_maps); the device stages take their buffer over (d_tmp, below).
+    const char *mode = getenv("CUBESLAM_LSD_REGIONS");
+    if (!mode || !*mode) mode = l->region_stage == CS_LSD_REGIONS_HOST ? "host" : l->region_stage == CS_LSD_REGIONS_WAVE_PER_FRAME ? "seq" : l->region_stage == CS_LSD_REGIONS_BACKLOG ? "wlk" : (F >= 512 ? "seq" : "host");
+    const int grp_p = strcmp(mode, "wlk") == 0 ? 65 : 0; // lsd_rg_wlk: walker waves with one lane per frame + rectangle waves
+    const bool device_mode = strcmp(mode, "seq") == 0 || grp_p;
+    l->scaled_kept = !device_mode;
+    // The scaled frames (doubles, 1.6 MB per frame) are the second part of an arena (d_tmp) that the device region stage takes over for its pixel records once
+    // lsd_maps is through, and the LBD blur for its one-kernel life (see below); a device-stage batch does not write them at all.
+    const int nbx = l->nbx, nsx = l->nsx, n_seg = F * h * nsx;
+    // (timed as "lsd_gradient": the stage that leaves the gradient maps, once per pass -- the blur and the resize in front of it have no launch of their own)
+    CS_LAUNCH(ctx, "lsd_gradient", lsd_maps, dim3(nsx * ((h + LSD_ROWS - 1) / LSD_ROWS), 1, F), dim3(64), 0, l->d_gray, W, H, w, h, l->gk, (MapTabs{l->d_xofs, l->d_yofs, l->d_ax, l->d_ay}), l->threshold,
+              l->d_mod, l->d_ang, l->d_seg_cnt, device_mode ? (double *)nullptr : l->d_scaled);
     const int nblk = (n_seg + 1023) / 1024;
     CS_LAUNCH(ctx, "lsd_scan", lsd_scan_blocks, dim3(nblk), dim3(1024), 0, l->d_seg_cnt, n_seg, l->d_seg_base, l->d_blk_tot);
     CS_LAUNCH(ctx, "lsd_scan", lsd_scan_top, dim3(1), dim3(1024), 0, l->d_blk_tot, nblk, l->d_seg_base + n_seg);
     CS_LAUNCH(ctx, "lsd_scan", lsd_scan_add, dim3(nblk), dim3(1024), 0, l->d_seg_base, n_seg, l->d_blk_tot);
     // only the defined pixels (gradient above rho) go to the host: frame bases first, then the compacted (address, angle, norm) lists
     l->frame_base.assign((size_t)F + 1, 0);
-    CS_HIP(ctx, hipMemcpy2DAsync(l->frame_base.data(), sizeof(int), l->d_seg_base, sizeof(int) * (size_t)h * nbx, sizeof(int), (size_t)F + 1, hipMemcpyDeviceToHost, ctx->stream));
+    CS_HIP(ctx, hipMemcpy2DAsync(l->frame_base.data(), sizeof(int), l->d_seg_base, sizeof(int) * (size_t)h * nsx, sizeof(int), (size_t)F + 1, hipMemcpyDeviceToHost, ctx->stream));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t total = (size_t)l->frame_base[F];
     int r;
@@ -649,19 +677,9 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
         r = cs_dalloc(ctx, &l->d_ccs, cap); if (r) return r;
         l->ccap = cap;
     }
-    // region growing / rectangles / NFA (a15): interchangeable stages with byte-identical KeyLines (tests/test_lsd_gpu.py).
-    //   seq    one wave per frame (lsd_rg_seq.h): ~110 ms per frame, 36 k frames/s with the chip full of them -- the default from 512 frames on;
-    //   wlk    a walker wave with one lane per frame that seeds and grows + rectangle waves for the regions it parks, one workgroup (lsd_rg_wlk.h): 64 frames per
-    //          wave slot instead of one, ~450 ms per frame -- for a backlog nobody waits for, by name only (DESIGN 7.3c; round 4's grp / grp2 / lpf are gone);
-    //   host   the OpenMP stage below, one frame per thread -- the default for smaller batches (one frame: 4 ms).
-    // cs_lsd_set_region_stage picks one per detector (a caller with a backlog nobody waits for takes wlk: 3.7 x seq's frames/s with the chip full of it); the
-    // development override CUBESLAM_LSD_REGIONS = seq | wlk | host comes first (tests, tools).
     std::vector<std::vector<float>> dev_lines;
     bool on_device = false;
-    const char *mode = getenv("CUBESLAM_LSD_REGIONS");
-    if (!mode || !*mode) mode = l->region_stage == CS_LSD_REGIONS_HOST ? "host" : l->region_stage == CS_LSD_REGIONS_WAVE_PER_FRAME ? "seq" : l->region_stage == CS_LSD_REGIONS_BACKLOG ? "wlk" : (F >= 512 ? "seq" : "host");
-    const int grp_p = strcmp(mode, "wlk") == 0 ? 65 : 0; // lsd_rg_wlk: walker waves with one lane per frame + rectangle waves
-    const bool use_seq = total > 0 && (strcmp(mode, "seq") == 0 || grp_p);
+    const bool use_seq = total > 0 && device_mode;
     // lsd_rg_seq's records are written by the emit kernel itself when they live in the arena (always, unless a caller's frames outgrew it): no fill, no scatter
     const bool pix_by_emit = use_seq && grp_p == 0 && l->pix_bytes >= (size_t)F * w * h * 4 + 64;
     auto emit = [&](bool with_norms) -> int { // the compacted norms (8 B per defined pixel) are the host stage's: the device stage reads the dense map
@@ -687,7 +705,6 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     if (l->gate_wait && !use_seq) l->gate_wait(l->gate_arg); // (phased front-end: the region stage starts when the caller's own GPU work of the phase is done; the device stage waits inside lsd_seq_run, in front of its one long kernel)
     if (use_seq) {
         long st[4] = {0, 0, 0, 0};
-        l->scaled_kept = false; // the arena is the region stage's from here on
         r = lsd_seq_run(ctx, &l->seq, F, w, h, l->d_ang, l->d_mod, l->d_caddr, l->d_cdeg, l->d_ccs, l->frame_base.data(), dev_lines, st, l->gate_wait, l->gate_done, l->gate_arg, grp_p, l->seq_wpb,
                         l->d_tmp, l->pix_bytes, pix_by_emit, l->walk_bg);
         l->rg_stats[0] = 1; l->rg_stats[1] = st[0]; l->rg_stats[2] = st[2]; l->rg_stats[3] = r == CS_OK ? 0 : 1; l->rg_stats[4] = st[1];
@@ -764,7 +781,6 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     for (int f = 0; f < F; f++) l->line_off[f + 1] = l->line_off[f] + (int)l->keylines[f].size();
     if (with_lbd) {
         const int nl = l->line_off[F];
-        l->h_desc.assign((size_t)nl * 32, 0);
         if (nl > 0) {
             if ((size_t)nl > l->line_cap) {
                 lsd_free_lines(l);
@@ -774,18 +790,19 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
                 r = cs_dalloc(ctx, &l->d_desc, cap * 32); if (r) return r;
                 l->line_cap = cap;
             }
-            std::vector<int> lf((size_t)nl);
-            std::vector<cs_keyline> kl((size_t)nl); // one upload for the whole batch (128 per-frame copies cost more than the descriptors)
+            r = l->h_kl.reserve(ctx, (size_t)nl); if (r) return r;
+            r = l->h_lf.reserve(ctx, (size_t)nl); if (r) return r;
+            r = l->h_desc.reserve(ctx, (size_t)nl * 32); if (r) return r;
+            cs_keyline *kl = l->h_kl.p; int *lf = l->h_lf.p; // one upload for the whole batch (128 per-frame copies cost more than the descriptors), assembled in place
             for (int f = 0; f < F; f++) {
-                std::copy(l->keylines[f].begin(), l->keylines[f].end(), kl.begin() + l->line_off[f]);
+                std::copy(l->keylines[f].begin(), l->keylines[f].end(), kl + l->line_off[f]);
                 for (int i = l->line_off[f]; i < l->line_off[f + 1]; i++) lf[i] = f;
             }
-            r = cs_h2d(ctx, l->d_kl, kl.data(), (size_t)nl); if (r) return r;
-            r = cs_h2d(ctx, l->d_line_frame, lf.data(), (size_t)nl); if (r) return r;
-            CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // kl, lf are locals
+            r = cs_h2d(ctx, l->d_kl, kl, (size_t)nl); if (r) return r;
+            r = cs_h2d(ctx, l->d_line_frame, lf, (size_t)nl); if (r) return r; // (the host writes these buffers again after the synchronisation at the end of this call)
             if (on_device) { r = lbd_maps(); if (r) return r; } // (device region stage: its pixel records are dead now, the Sobel map takes their place)
             r = cs_lbd_batch_desc(ctx, l->d_kl, l->d_line_frame, nl, l->dxy_cur, W, H, l->d_desc, nullptr); if (r) return r;
-            r = cs_d2h(ctx, l->h_desc.data(), l->d_desc, (size_t)nl * 32); if (r) return r;
+            r = cs_d2h(ctx, l->h_desc.p, l->d_desc, (size_t)nl * 32); if (r) return r;
         }
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         l->have_desc = true;
@@ -808,6 +825,7 @@ void cs_lsd_destroy(cs_ctx *ctx, cs_lsd *l) {
     if (l->h_cdeg) hipHostFree(l->h_cdeg);
     if (l->h_ccs) hipHostFree(l->h_ccs);
     if (l->h_cmod) hipHostFree(l->h_cmod);
+    l->h_desc.release(); l->h_kl.release(); l->h_lf.release();
     delete l;
 }
 
@@ -831,14 +849,16 @@ int cs_lsd_create(cs_ctx *ctx, int width, int height, int max_frames, cs_lsd **o
     for (int dy = 0; dy < l->h; dy++) { float fy = (float)((dy + 0.5) * sx - 0.5); int s = fl(fy); fy -= s; if (s < 0) { fy = 0; s = 0; } if (s >= height - 1) { fy = 0; s = height - 1; } yofs[dy] = s; ay[dy * 2] = 1.f - fy; ay[dy * 2 + 1] = fy; }
     const size_t N = (size_t)width * height * max_frames, n = (size_t)l->w * l->h * max_frames;
 #define A_(call) do { int r__ = (call); if (r__ != CS_OK) { cs_lsd_destroy(ctx, l); return r__; } } while (0)
-    // one arena for [blurred | scaled] frames; afterwards [the device region stage's own copy of the angle map (4 B per scaled pixel) | LBD blur (1 B per pixel)]: 4 n + N <= 8 N + 8 n bytes
+    // one arena: [8 N bytes | scaled frames (a host-stage batch's, lsd_maps)]; afterwards [the device region stage's own copy of the angle map (4 B per scaled pixel) | LBD blur (1 B per pixel)] or [Sobel map (4 B per pixel) | LBD blur]: 4 n + N, 5 N <= 8 N + 8 n bytes
     l->pix_bytes = (n * 4 + 64 + 255) / 256 * 256;
-    A_(cs_dalloc(ctx, &l->d_gray, N)); A_(cs_dalloc(ctx, &l->d_tmp, N + n)); l->d_blur = l->d_tmp; l->d_scaled = l->d_tmp + N;
+    A_(cs_dalloc(ctx, &l->d_gray, N)); A_(cs_dalloc(ctx, &l->d_tmp, N + n)); l->d_scaled = l->d_tmp + N;
     A_(cs_dalloc(ctx, &l->d_mod, n)); A_(cs_dalloc(ctx, &l->d_ang, n));
     A_(cs_dalloc(ctx, &l->d_xofs, xofs.size())); A_(cs_dalloc(ctx, &l->d_yofs, yofs.size())); A_(cs_dalloc(ctx, &l->d_ax, ax.size())); A_(cs_dalloc(ctx, &l->d_ay, ay.size()));
-    l->nbx = (l->w + 255) / 256;
-    A_(cs_dalloc(ctx, &l->d_seg_cnt, (size_t)max_frames * l->h * l->nbx)); A_(cs_dalloc(ctx, &l->d_seg_base, (size_t)max_frames * l->h * l->nbx + 1));
-    A_(cs_dalloc(ctx, &l->d_blk_tot, ((size_t)max_frames * l->h * l->nbx + 1023) / 1024 + 1));
+    l->nbx = (l->w + 255) / 256; l->nsx = (l->w + 63) / 64;
+    for (int d0 = 0; d0 < l->w; d0 += 64) // lsd_maps: a strip's resize taps stay inside its 128 blurred columns (83 at scale 0.8)
+        if (std::min(xofs[std::min(d0 + 64, l->w - 1)] + 1, width - 1) - xofs[d0] >= LSD_SPAN) { cs_lsd_destroy(ctx, l); return CS_ERR_BAD_ARG; }
+    A_(cs_dalloc(ctx, &l->d_seg_cnt, (size_t)max_frames * l->h * l->nsx)); A_(cs_dalloc(ctx, &l->d_seg_base, (size_t)max_frames * l->h * l->nsx + 1));
+    A_(cs_dalloc(ctx, &l->d_blk_tot, ((size_t)max_frames * l->h * l->nsx + 1023) / 1024 + 1));
     A_(cs_h2d(ctx, l->d_xofs, xofs.data(), xofs.size())); A_(cs_h2d(ctx, l->d_yofs, yofs.data(), yofs.size()));
     A_(cs_h2d(ctx, l->d_ax, ax.data(), ax.size())); A_(cs_h2d(ctx, l->d_ay, ay.data(), ay.size()));
 #undef A_
@@ -938,7 +958,7 @@ int cs_lsd_read(cs_ctx *ctx, cs_lsd *l, int frame, cs_keyline *out, int cap, int
     if (!out) return CS_OK; // size query
     if (n > cap) return CS_ERR_CAPACITY;
     memcpy(out, l->keylines[frame].data(), sizeof(cs_keyline) * (size_t)n);
-    if (desc) memcpy(desc, l->h_desc.data() + (size_t)l->line_off[frame] * 32, (size_t)n * 32);
+    if (desc && n > 0) memcpy(desc, l->h_desc.p + (size_t)l->line_off[frame] * 32, (size_t)n * 32);
     return CS_OK;
 }
 
@@ -948,7 +968,7 @@ int cs_lsd_get_maps(cs_ctx *ctx, cs_lsd *l, int frame, double *scaled, double *m
     const size_t n = (size_t)l->w * l->h;
     int r;
     if (scaled) {
-        if (!l->scaled_kept) { ctx->err = "cs_lsd_get_maps: the scaled frames are gone once the device region stage ran (it takes their buffer over); modgrad and angles are kept"; return CS_ERR_BAD_ARG; }
+        if (!l->scaled_kept) { ctx->err = "cs_lsd_get_maps: the scaled frames are only kept for a batch of the host region stage (a device stage takes their buffer over); modgrad and angles are kept"; return CS_ERR_BAD_ARG; }
         r = cs_d2h(ctx, scaled, l->d_scaled + n * frame, n); if (r) return r;
     }
     if (modgrad) { r = cs_d2h(ctx, modgrad, l->d_mod + n * frame, n); if (r) return r; }

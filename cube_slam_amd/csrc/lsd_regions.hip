@@ -39,11 +39,12 @@
 namespace {
 constexpr int PAD_PX = 272, PAD_LIST = 272, PAD_RECT = 34; // (lsd_rg_wlk) 1088 / 2176 / 272 bytes between the frames' maps / lists / rectangles: the strides are not multiples of a large power of two (64 lanes, 64 frames: one channel otherwise)
 constexpr double PI_ = rg::PI_, LOG_EPS = 0.0, LSD_SCALE = 0.8;
-struct AngMap { int w, h; const float *deg; }; // a frame's level-line angles as lsd_gradient leaves them: float degrees, NOTDEF_F where the gradient is below the threshold; the map value is deg * DEG_TO_RADS in double
+struct AngMap { int w, h; const float *deg; }; // a frame's level-line angles as lsd_maps leaves them: float degrees, NOTDEF_F where the gradient is below the threshold; the map value is deg * DEG_TO_RADS in double
 
 // ---- rect_improve / rect_nfa / nfa: one wave per rectangle -------------------------------------------------------------------------------
+__device__ __forceinline__ double rg_log_gamma_windschitl(double x) { return 0.918938533204673 + (x - 0.5) * log(x) - x + 0.5 * x * log(x * sinh(1 / x) + 1 / (810.0 * pow(x, 6.0))); }
 __device__ double rg_log_gamma(double x) { // lsd.cpp:70,124-160
-    if (x > 15.0) return 0.918938533204673 + (x - 0.5) * log(x) - x + 0.5 * x * log(x * sinh(1 / x) + 1 / (810.0 * pow(x, 6.0)));
+    if (x > 15.0) return rg_log_gamma_windschitl(x);
     const double q[7] = {75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705, 1168.92649479, 83.8676043424, 2.50662827511};
     double a = (x + 0.5) * log(x + 5.5) - (x + 5.5), b = 0;
     for (int n = 0; n < 7; ++n) { a -= log(x + double(n)); b += q[n] * pow(x, double(n)); }
@@ -56,7 +57,8 @@ __device__ double rg_log_gamma(double x) { // lsd.cpp:70,124-160
 #endif
 constexpr int LG_N = 32768; // log_gamma of the integers below this: a table filled by the same function (its arguments are pixel counts; each call costs 16 log + 14 pow)
 __global__ void __launch_bounds__(256) lsd_rg_lgamma_table(double *t) { const int i = blockIdx.x * 256 + threadIdx.x; if (i < LG_N) t[i] = i > 0 ? rg_log_gamma(double(i)) : 0.0; }
-__device__ __forceinline__ double rg_lgam_int(int x, const double *lgt) { return (lgt && x > 0 && x < LG_N) ? lgt[x] : rg_log_gamma(double(x)); }
+// (nfa() asks for k + 1 and n - k + 1 with 0 <= k <= n: x >= 1, and beyond the table x > 15, where log_gamma is the closed form -- no call: rg_nfa stays a leaf without a stack)
+__device__ __forceinline__ double rg_lgam_int(int x, const double *lgt) { return x < LG_N ? lgt[x] : rg_log_gamma_windschitl(double(x)); }
 __device__ double rg_nfa(int n, int k, double p, double LOG_NT, const double *lgt) { // :1100-1136
     if (n == 0 || k == 0) return -LOG_NT;
     if (n == k) return -LOG_NT - double(n) * log10(p);
@@ -164,11 +166,8 @@ template <int NP> __device__ void rg_rect_count(const AngMap &F, const rg::Rect 
 }
 // The walks of up to five rectangles at once (rect_improve's loops try five variants of a rectangle that do not depend on each other): eight lanes per rectangle,
 // lane s of them takes the rows y_first + s, y_first + s + 8, ...  One preamble, one round trip and one (three-step) reduction instead of five of each -- with 28
-// pixels per rectangle a walk is all fixed cost.  rs: this lane's copy of the variants (every lane holds the same five).
-__device__ void rg_rect_count_five(const AngMap &F, const rg::Rect *rs, int cnt, int lane, int *tot, int *alg) {
-    const int grp = lane >> 3, sub = lane & 7;
-    const bool on = grp < cnt;
-    const rg::Rect rec = rs[on ? grp : 0];
+// pixels per rectangle a walk is all fixed cost.  rec: the variant of this lane's group (on: the group has one); tot / alg: its counts, in every lane of the group.
+__device__ __forceinline__ void rg_rect_count_group(const AngMap &F, const rg::Rect &rec, bool on, int sub, int &tot, int &alg) {
     RectSpan S; S.set(rec, F.h);
     int total_pts = 0, alg_pts[1] = {0};
     if (on)
@@ -179,55 +178,70 @@ __device__ void rg_rect_count_five(const AngMap &F, const rg::Rect *rs, int cnt,
             rg_row_count<1>(F.deg + (size_t)y * F.w, lx, rx, 0, 1, rec.theta, &rec.prec, alg_pts);
         }
     for (int off = 1; off < 8; off <<= 1) { total_pts += __shfl_xor(total_pts, off); alg_pts[0] += __shfl_xor(alg_pts[0], off); }
-    for (int n = 0; n < 5; n++) { tot[n] = __shfl(total_pts, 8 * n); alg[n] = __shfl(alg_pts[0], 8 * n); }
+    tot = total_pts; alg = alg_pts[0];
 }
-// nfa() of up to five (n, k, p) triples at once: lane v computes triple v -- the loops inside nfa are sequential, the triples independent
-__device__ void rg_nfa5(const int *n, const int *k, const double *p, int cnt, double LOG_NT, const double *lgt, int lane, double *out) {
-    int nn = n[0], kk = k[0]; double pp = p[0];
-    for (int v = 1; v < 5; v++) if (v < cnt && lane == v) { nn = n[v]; kk = k[v]; pp = p[v]; }
-    const double r = rg_nfa(nn, kk, pp, LOG_NT, lgt);
-    for (int v = 0; v < 5; v++) out[v] = __shfl(r, v);
+__device__ __forceinline__ rg::Rect rg_rect_shfl(const rg::Rect &r, int src) {
+    rg::Rect o;
+    o.x1 = __shfl(r.x1, src); o.y1 = __shfl(r.y1, src); o.x2 = __shfl(r.x2, src); o.y2 = __shfl(r.y2, src); o.width = __shfl(r.width, src); o.x = __shfl(r.x, src);
+    o.y = __shfl(r.y, src); o.theta = __shfl(r.theta, src); o.dx = __shfl(r.dx, src); o.dy = __shfl(r.dy, src); o.prec = __shfl(r.prec, src); o.p = __shfl(r.p, src);
+    return o;
 }
 // rect_improve lsd.cpp:873-975.  The five variants of each of its loops do not depend on each other's result (only the best is remembered), so
-// their pixel walks run one after the other -- or as one walk where only the tolerance changes -- and their five nfa() side by side in five lanes.
+// their pixel walks run side by side -- or as one walk where only the tolerance changes -- and their five nfa() too.  Lane group g (eight lanes) holds
+// variant g and nothing else: every lane runs the reference loop's cumulative updates in its order and keeps the rectangle of the g-th variant, and the
+// best is picked by reading the groups' nfa() in variant order with the reference's strict `>`.  No array is indexed at run time (such arrays live in
+// scratch memory: 688 bytes per lane and ~490 store instructions per wave before).
 // log_nfa: rect_nfa of the rectangle as it comes (the kernel computes it for eight rectangles at once).
 __device__ double rg_rect_improve(const AngMap &F, rg::Rect &rec, double LOG_NT, int lane, const double *lgt, double log_nfa) {
     const double delta = 0.5, delta_2 = delta / 2.0;
     if (log_nfa > LOG_EPS) return log_nfa;
-    rg::Rect rs[5];
-    int tot[5], alg[5], cnt; double ps[5], v[5];
-    auto tolerances = [&]() { // r.p /= 2 five times on the rectangle `rec`: one walk, five counts
-        rg::Rect r = rec; double precs[5];
-        for (int n = 0; n < 5; ++n) { r.p /= 2; r.prec = r.p * PI_; rs[n] = r; precs[n] = r.prec; ps[n] = r.p; }
-        int t; rg_rect_count<5>(F, rec, precs, lane, t, alg);
-        for (int n = 0; n < 5; ++n) tot[n] = t;
+    const int g = lane >> 3, sub = lane & 7;
+    rg::Rect mine; // variant g of the current loop
+    int tot = 0, al = 0, cnt = 0;
+    // Variant g of a loop is its rectangle after the loop's (g + 1)-th update; an update happens while its condition holds, and the condition only depends
+    // on the width, which only an update changes: the variants are a prefix of the loop, cnt of them, and every lane takes the updates up to its own.
+    // Loops in rect_improve's order: 0 the tolerances (r.p /= 2 five times: the rectangle and its walk stay, one walk gives the five counts), 1 the width,
+    // 2 / 3 one side / the other, 4 the tolerances again (the width does not change there: all five or none).
+    auto tolerances = [&]() {
+        mine = rec;
+        double p = rec.p, precs[5];
+#pragma unroll
+        for (int n = 0; n < 5; ++n) { p /= 2; precs[n] = p * PI_; if (n <= g) { mine.p = p; mine.prec = precs[n]; } }
+        int t, alg[5]; rg_rect_count<5>(F, rec, precs, lane, t, alg);
+        tot = t; al = alg[0];
+#pragma unroll
+        for (int n = 1; n < 5; ++n) if (g == n) al = alg[n];
         cnt = 5;
     };
-    auto take_best = [&]() {
-        rg_nfa5(tot, alg, ps, cnt, LOG_NT, lgt, lane, v);
-        for (int n = 0; n < cnt; ++n) if (v[n] > log_nfa) { log_nfa = v[n]; rec = rs[n]; }
+    auto shrink = [&](int side) { // side 0: the width, 1 / 2: one side / the other
+        mine = rec; cnt = 0;
+        double wd = rec.width;
+#pragma unroll
+        for (int n = 0; n < 5; ++n) if ((wd - delta) >= 0.5) { wd -= delta; cnt++; }
+#pragma unroll
+        for (int n = 0; n < 5; ++n) if (n <= g && (mine.width - delta) >= 0.5) {
+            if (side == 1) { mine.x1 += -mine.dy * delta_2; mine.y1 += mine.dx * delta_2; mine.x2 += -mine.dy * delta_2; mine.y2 += mine.dx * delta_2; }
+            else if (side == 2) { mine.x1 -= -mine.dy * delta_2; mine.y1 -= mine.dx * delta_2; mine.x2 -= -mine.dy * delta_2; mine.y2 -= mine.dx * delta_2; }
+            mine.width -= delta;
+        }
+        if (cnt) rg_rect_count_group(F, mine, g < cnt, sub, tot, al);
     };
-    auto walks = [&]() { if (cnt) rg_rect_count_five(F, rs, cnt, lane, tot, alg); for (int n = 0; n < cnt; ++n) ps[n] = rs[n].p; };
+    auto take_best = [&]() { // the best variant: nfa() of each group, read in variant order with the reference's strict `>`
+        const bool on = g < cnt;
+        const double mv = rg_nfa(on ? tot : 0, on ? al : 0, mine.p, LOG_NT, lgt); // (n = 0: an immediate return in the groups without a variant)
+        int best = -1;
+#pragma unroll
+        for (int n = 0; n < 5; ++n) { const double vn = __shfl(mv, 8 * n); if (n < cnt && vn > log_nfa) { log_nfa = vn; best = n; } }
+        if (best >= 0) rec = rg_rect_shfl(mine, 8 * best);
+    };
     tolerances(); take_best();
     if (log_nfa > LOG_EPS) return log_nfa;
-    rg::Rect r = rec;
-    cnt = 0;
-    for (int n = 0; n < 5; ++n) if ((r.width - delta) >= 0.5) { r.width -= delta; rs[cnt++] = r; }
-    walks(); if (cnt) take_best();
-    if (log_nfa > LOG_EPS) return log_nfa;
-    for (int side = 0; side < 2; side++) {
-        r = rec;
-        cnt = 0;
-        for (int n = 0; n < 5; ++n) if ((r.width - delta) >= 0.5) {
-            if (side == 0) { r.x1 += -r.dy * delta_2; r.y1 += r.dx * delta_2; r.x2 += -r.dy * delta_2; r.y2 += r.dx * delta_2; }
-            else { r.x1 -= -r.dy * delta_2; r.y1 -= r.dx * delta_2; r.x2 -= -r.dy * delta_2; r.y2 -= r.dx * delta_2; }
-            r.width -= delta;
-            rs[cnt++] = r;
-        }
-        walks(); if (cnt) take_best();
+    for (int side = 0; side < 3; side++) {
+        shrink(side);
+        if (cnt) take_best();
         if (log_nfa > LOG_EPS) return log_nfa;
     }
-    if ((rec.width - delta) >= 0.5) { tolerances(); take_best(); } // (the width does not change in the last loop: all five or none)
+    if ((rec.width - delta) >= 0.5) { tolerances(); take_best(); }
     return log_nfa;
 }
 
@@ -403,12 +417,13 @@ struct LsdSeq {
     double *d_rect = nullptr, *d_lgt = nullptr;
     uint8_t *d_has = nullptr;
     float4 *d_line = nullptr;
-    std::vector<int> h_base, h_status; std::vector<uint8_t> h_has; std::vector<float4> h_line;
+    cs_pinned<int> h_base, h_status; cs_pinned<uint8_t> h_has; cs_pinned<float4> h_line; // the hand-overs to the host, pinned (lsd_seq_destroy frees them)
 };
 void lsd_seq_destroy(LsdSeq *r) {
     if (!r) return;
     void *ptrs[] = {r->d_elist, r->d_ang32, r->d_order, r->pix_borrowed ? nullptr : r->d_pix, r->d_glist, r->d_cand_cnt, r->d_cand_base, r->d_status, r->d_frame_base, r->d_rect, r->d_lgt, r->d_has, r->d_line};
     for (void *p : ptrs) if (p) hipFree(p);
+    r->h_base.release(); r->h_status.release(); r->h_has.release(); r->h_line.release();
     delete r;
 }
 // The region stage of F frames, one wave per frame.  lines[f] = x1 y1 x2 y2 floats in the reference's emission order.  CS_ERR_CAPACITY: a region
@@ -516,15 +531,15 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     } else
     CS_LAUNCH(ctx, "lsd_rg_seq", lsd_rg_seq, dim3((F + wpb - 1) / wpb), dim3(64 * wpb), 0, S);
     CS_LAUNCH(ctx, "lsd_rg_cand_scan", lsd_rg_cand_scan, dim3(1), dim3(1024), 0, r->d_cand_cnt, F, r->d_cand_base);
-    r->h_base.resize((size_t)F + 1); r->h_status.resize((size_t)F * 4);
-    RA_(cs_d2h(ctx, r->h_base.data(), r->d_cand_base, (size_t)F + 1));
-    RA_(cs_d2h(ctx, r->h_status.data(), r->d_status, (size_t)F * 4));
+    RA_(r->h_base.reserve(ctx, (size_t)F + 1)); RA_(r->h_status.reserve(ctx, (size_t)F * 4));
+    RA_(cs_d2h(ctx, r->h_base.p, r->d_cand_base, (size_t)F + 1));
+    RA_(cs_d2h(ctx, r->h_status.p, r->d_status, (size_t)F * 4));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (after_seq) after_seq(gate_arg);
     long grows = 0, fetches = 0, nreg = 0;
     bool bad = false;
-    for (int f = 0; f < F; f++) { grows += r->h_status[4 * f]; bad = bad || r->h_status[4 * f + 1] != 0; nreg += r->h_status[4 * f + 2]; fetches += r->h_status[4 * f + 3]; }
-    const int n_cand = r->h_base[F];
+    for (int f = 0; f < F; f++) { grows += r->h_status.p[4 * f]; bad = bad || r->h_status.p[4 * f + 1] != 0; nreg += r->h_status.p[4 * f + 2]; fetches += r->h_status.p[4 * f + 3]; }
+    const int n_cand = r->h_base.p[F];
     if (stats) { stats[0] = grows; stats[1] = fetches; stats[2] = n_cand; stats[3] = nreg; }
     if (bad) return CS_ERR_CAPACITY;
     lines.assign((size_t)F, {});
@@ -537,14 +552,14 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
         r->cap_lines = cap;
     }
     CS_LAUNCH(ctx, "lsd_rg_improve", lsd_rg_improve, dim3((n_cand + 31) / 32), dim3(256), 0, S, r->d_cand_base, n_cand, r->d_lgt, r->d_line, r->d_has); // eight rectangles per wave
-    r->h_has.resize((size_t)n_cand); r->h_line.resize((size_t)n_cand);
-    RA_(cs_d2h(ctx, r->h_has.data(), r->d_has, (size_t)n_cand));
-    RA_(cs_d2h(ctx, r->h_line.data(), r->d_line, (size_t)n_cand));
+    RA_(r->h_has.reserve(ctx, (size_t)n_cand)); RA_(r->h_line.reserve(ctx, (size_t)n_cand));
+    RA_(cs_d2h(ctx, r->h_has.p, r->d_has, (size_t)n_cand));
+    RA_(cs_d2h(ctx, r->h_line.p, r->d_line, (size_t)n_cand));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
 #undef RA_
 #pragma omp parallel for schedule(static) num_threads(std::max(1, std::min(ctx->host_threads, F)))
     for (int f = 0; f < F; f++)
-        for (int k = r->h_base[f]; k < r->h_base[f + 1]; k++)
-            if (r->h_has[k]) { const float4 v = r->h_line[k]; lines[f].push_back(v.x); lines[f].push_back(v.y); lines[f].push_back(v.z); lines[f].push_back(v.w); }
+        for (int k = r->h_base.p[f]; k < r->h_base.p[f + 1]; k++)
+            if (r->h_has.p[k]) { const float4 v = r->h_line.p[k]; lines[f].push_back(v.x); lines[f].push_back(v.y); lines[f].push_back(v.z); lines[f].push_back(v.w); }
     return CS_OK;
 }

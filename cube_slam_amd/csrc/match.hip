@@ -1,18 +1,23 @@
 // match.hip -- ORB_SLAM2::ORBmatcher Hamming searches on MI355X (gfx950).
 //
-// Replaces ORBmatcher::SearchByProjection (both overloads), SearchForInitialization and DescriptorDistance
-// (reference orb_object_slam/src/ORBmatcher.cc:50-142, :429-542, :1373-1522, :1905-1921) and the Frame grid
-// (src/Frame.cc:303-318, :404-459, :525-535).
+// Replaces ORBmatcher::SearchByProjection (both overloads), SearchForInitialization, SearchByBoW (both overloads), SearchForTriangulation, Fuse's search and
+// DescriptorDistance (reference orb_object_slam/src/ORBmatcher.cc:50-142, :171-310, :429-542, :544-677, :679-850, :934-981, :1373-1522, :1905-1921) and the Frame grid
+// (src/Frame.cc:303-318, :404-459, :525-535, :546-609).
 //
-//   match_grid        counting sort of the keypoints into the 64x48 grid, per-cell lists in keypoint order
-//   match_project     per last-frame map point: Rcw*x+tcw (cv::gemm: double accumulate, one rounding), pinhole projection,
-//                     window radius th*scale[octave]
-//   match_candidates  one wave per query: lane = grid cell of the window (ix outer, iy inner = the reference's candidate
-//                     order), level + |dx|<r,|dy|<r filters, ordered compaction by a wave prefix sum, 256-bit Hamming
-//                     distance as 4 x popcount(u64).  pass 0 counts, pass 1 fills a CSR list (idx, dist).
-//   match_knn2        all-pairs best / second best, train descriptors staged through LDS
-// The greedy claim / ratio / rotation-histogram logic of the reference is sequential over the queries (a candidate claimed by
-// an earlier query is skipped by later ones); it runs on the host over the CSR lists.
+//   match_grid           counting sort of the keypoints into the 64x48 grid, per-cell lists in keypoint order; one workgroup per frame (one frame or a window's frames)
+//   match_undistort      Frame::UndistortKeyPoints: cv::undistortPoints with P = K, a thread per key point
+//   match_project        per last-frame map point: Rcw*x+tcw (cv::gemm: double accumulate, one rounding), pinhole projection,
+//                        window radius th*scale[octave]; one pose or one pose per pair of a window
+//   match_candidates     MC_G lanes per query: lane = grid cell of the window (ix outer, iy inner = the reference's candidate
+//                        order), level + |dx|<r,|dy|<r filters, ordered compaction by a prefix sum, 256-bit Hamming
+//                        distance as 4 x popcount(u64).  It counts, takes a slice of the candidate arena, fills it with (idx, dist).
+//   match_resolve<V>     the greedy claim / best-second / ratio / rotation-histogram logic of the reference, which is sequential over the queries (a candidate
+//                        claimed by an earlier query is skipped by later ones): one wave per search, 64 queries at a time, over the candidate lists
+//   match_fuse_best      Fuse: per map point the best key point after the chi-square tests
+//   match_triangulation  SearchForTriangulation: one wave per key point of KF1 over the KF2 features of its vocabulary node
+//   match_orient_cut     the rotation cut of a search whose matches are independent of each other
+//   match_bow_dists      SearchByBoW: the distances of a feature to its node's features, as candidate lists for match_resolve
+//   match_knn2           all-pairs best / second best, train descriptors staged through LDS
 #include "common.h"
 
 #include <algorithm>
@@ -30,13 +35,18 @@ struct FrameP { int N; float minX, maxX, minY, maxY, wInv, hInv; };
 // other): a window's walk streams 16-byte records instead of chasing cell list -> index -> 28-byte key point record
 struct CellRec { float x, y; int id, octave; };
 
-__global__ void __launch_bounds__(1024) match_grid(FrameP F, const cs_keypoint *keys, int *cell_start /*NCELL+1*/, int *cell_items, int *kp_cell, CellRec *cell_recs) {
+// AssignFeaturesToGrid (Frame.cc:303-318), one workgroup per frame.  kfirst == NULL: one frame, key points 0 .. F.N.  Otherwise workgroup p takes key points
+// kfirst[p] .. kfirst[p + 1] of `keys`; its cell lists (relative to the frame) lie at p x (NCELL + 1) / kfirst[p] of the outputs.
+__global__ void __launch_bounds__(1024) match_grid(FrameP F, const cs_keypoint *keys_all, const int *kfirst, int *cell_start_all /*P x (NCELL+1)*/, int *cell_items_all, int *kp_cell_all, CellRec *cell_recs_all) {
     __shared__ int cnt[NCELL];
     __shared__ int s_part[1024];
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, p = blockIdx.x, kb = kfirst ? kfirst[p] : 0, N = kfirst ? kfirst[p + 1] - kb : F.N;
+    const cs_keypoint *keys = keys_all + kb;
+    int *cell_start = cell_start_all + (size_t)p * (NCELL + 1), *cell_items = cell_items_all + kb, *kp_cell = kp_cell_all + kb;
+    CellRec *cell_recs = cell_recs_all + kb;
     for (int c = tid; c < NCELL; c += 1024) cnt[c] = 0;
     __syncthreads();
-    for (int i = tid; i < F.N; i += 1024) { // PosInGrid, Frame.cc:525-535
+    for (int i = tid; i < N; i += 1024) { // PosInGrid, Frame.cc:525-535
         int px = (int)roundf((keys[i].x - F.minX) * F.wInv), py = (int)roundf((keys[i].y - F.minY) * F.hInv);
         int c = (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
         kp_cell[i] = c;
@@ -59,7 +69,7 @@ __global__ void __launch_bounds__(1024) match_grid(FrameP F, const cs_keypoint *
     __syncthreads();
     cnt[tid * 3] = base; cnt[tid * 3 + 1] = base + c0; cnt[tid * 3 + 2] = base + c0 + c1; // running fill positions
     __syncthreads();
-    for (int i = tid; i < F.N; i += 1024) { int c = kp_cell[i]; if (c >= 0) cell_items[atomicAdd(&cnt[c], 1)] = i; }
+    for (int i = tid; i < N; i += 1024) { int c = kp_cell[i]; if (c >= 0) cell_items[atomicAdd(&cnt[c], 1)] = i; }
     __syncthreads();
     // mGrid[x][y] holds the indices in push_back order = ascending keypoint index: sort each (tiny) cell list
     for (int c = tid; c < NCELL; c += 1024) {
@@ -108,27 +118,32 @@ __global__ void match_undistort(int n, const cs_keypoint *in, UndP U, cs_keypoin
 // A window query.  `pair`: which train frame of a window it searches (0 for the one-frame calls).
 struct QueryS { float x, y, r; int minLevel, maxLevel, valid, pair; };
 
-__global__ void match_project(int n, const float *world_pos, const uint8_t *valid, const int *octave, const float *T, float fx, float fy, float cx,
-                              float cy, const float *scale_factors, float th, FrameP F, QueryS *q) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    QueryS Q{0, 0, 0, 0, 0, 0, 0};
+// The queries of a SearchByProjection (ORBmatcher.cc:1397-1430).  Query i belongs to pair p with qfirst[p] <= i < qfirst[p + 1] and is projected with the pose
+// T_all + 12 * p; qfirst == NULL: one pair, no bisection.  Its level is octave[i] or, with octave == NULL, the key point record's okeys[i].octave (:1424); a level outside the
+// scale table raises *err and leaves the query invalid.
+__global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const int *qfirst, const float *world_pos, const uint8_t *valid, const int *octave, const cs_keypoint *okeys,
+                                                    const float *T_all, float fx, float fy, float cx, float cy, const float *scale_factors, int n_levels, float th, FrameP F, QueryS *q, int *err) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    int lo = 0, hi = qfirst ? n_pairs : 1; // qfirst[lo] <= i < qfirst[hi]
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (qfirst[mid] <= i) lo = mid; else hi = mid; }
+    const float *T = T_all + 12 * lo;
+    QueryS Q{0, 0, 0, 0, 0, 0, lo};
     if (valid[i]) {
+        const int o = octave ? octave[i] : okeys[i].octave;
+        if (o < 0 || o >= n_levels) { *err = 1; q[i] = Q; return; }
         float x3Dc[3];
         for (int r = 0; r < 3; r++) {
-            double s = 0;
-            for (int k = 0; k < 3; k++) s += (double)T[r * 4 + k] * (double)world_pos[i * 3 + k];
-            x3Dc[r] = (float)(s * 1.0 + (double)T[r * 4 + 3] * 1.0);
+            double sacc = 0;
+            for (int k = 0; k < 3; k++) sacc += (double)T[r * 4 + k] * (double)world_pos[(size_t)i * 3 + k];
+            x3Dc[r] = (float)(sacc * 1.0 + (double)T[r * 4 + 3] * 1.0);
         }
         const float xc = x3Dc[0], yc = x3Dc[1];
         const float invzc = (float)(1.0 / x3Dc[2]);
         if (!(invzc < 0)) {
             float u = fx * xc * invzc + cx;
             float v = fy * yc * invzc + cy;
-            if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) {
-                int o = octave[i];
-                Q.x = u; Q.y = v; Q.r = th * scale_factors[o]; Q.minLevel = o - 1; Q.maxLevel = o + 1; Q.valid = 1;
-            }
+            if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) { Q.x = u; Q.y = v; Q.r = th * scale_factors[o]; Q.minLevel = o - 1; Q.maxLevel = o + 1; Q.valid = 1; }
         }
     }
     q[i] = Q;
@@ -553,106 +568,92 @@ __global__ void __launch_bounds__(256) match_bow_dists(int NK, const unsigned lo
     for (int p = lane; p < n; p += 64) { const int iF = node_items[b + p]; cands[out_off[ik] + p] = make_int2(iF, hamming256(descF + (long)iF * 4, a0, a1, a2, a3)); }
 }
 
-
-// ---- a whole window of a stream at once (cs_match_by_projection_stream): pair p = (last frame f0 + p, current frame f0 + p + 1) of the frames an extractor holds in HBM.
-// Frame post-processing of every current frame and the searches of all pairs in a handful of launches.  Same arithmetic, same candidate order, same claims as the per-frame calls.
-// AssignFeaturesToGrid of the current frames: one workgroup per frame, key points kfirst[p] .. kfirst[p + 1] of `keys`; cell lists relative to the frame
-__global__ void __launch_bounds__(1024) match_grid_batch(FrameP F, const cs_keypoint *keys, const int *kfirst, int *cell_start_all /*P x (NCELL+1)*/, int *cell_items_all, int *kp_cell_all, CellRec *cell_recs_all) {
-    __shared__ int cnt[NCELL];
-    __shared__ int s_part[1024];
-    const int tid = threadIdx.x, p = blockIdx.x, kb = kfirst[p], N = kfirst[p + 1] - kb;
-    const cs_keypoint *k = keys + kb;
-    int *cell_start = cell_start_all + (size_t)p * (NCELL + 1), *cell_items = cell_items_all + kb, *kp_cell = kp_cell_all + kb;
-    for (int c = tid; c < NCELL; c += 1024) cnt[c] = 0;
-    __syncthreads();
-    for (int i = tid; i < N; i += 1024) { // PosInGrid, Frame.cc:525-535
-        int px = (int)roundf((k[i].x - F.minX) * F.wInv), py = (int)roundf((k[i].y - F.minY) * F.hInv);
-        int c = (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
-        kp_cell[i] = c;
-        if (c >= 0) atomicAdd(&cnt[c], 1);
-    }
-    __syncthreads();
-    int c0 = cnt[tid * 3], c1 = cnt[tid * 3 + 1], c2 = cnt[tid * 3 + 2];
-    s_part[tid] = c0 + c1 + c2;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int v = tid >= off ? s_part[tid - off] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    int base = s_part[tid] - (c0 + c1 + c2);
-    cell_start[tid * 3] = base; cell_start[tid * 3 + 1] = base + c0; cell_start[tid * 3 + 2] = base + c0 + c1;
-    if (tid == 1023) cell_start[NCELL] = s_part[1023];
-    __syncthreads();
-    cnt[tid * 3] = base; cnt[tid * 3 + 1] = base + c0; cnt[tid * 3 + 2] = base + c0 + c1;
-    __syncthreads();
-    for (int i = tid; i < N; i += 1024) { int c = kp_cell[i]; if (c >= 0) cell_items[atomicAdd(&cnt[c], 1)] = i; }
-    __syncthreads();
-    for (int c = tid; c < NCELL; c += 1024) { // mGrid[x][y] holds the indices in ascending key point order
-        int b = cell_start[c], e = cnt[c];
-        for (int i = b + 1; i < e; i++) {
-            int v = cell_items[i], j = i - 1;
-            while (j >= b && cell_items[j] > v) { cell_items[j + 1] = cell_items[j]; j--; }
-            cell_items[j + 1] = v;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < cell_start[NCELL]; i += 1024) { const int id = cell_items[i]; const cs_keypoint kk = k[id]; cell_recs_all[kb + i] = CellRec{kk.x, kk.y, id, kk.octave}; }
-}// the queries of all pairs: query j belongs to pair p with qfirst[p] <= j < qfirst[p + 1]; its level is the last frame's key point's (ORBmatcher.cc:1424)
-__global__ void __launch_bounds__(256) match_project_stream(int nq, int n_pairs, const int *qfirst, const float *world_pos, const uint8_t *valid, const cs_keypoint *last_keys /* raw key points of frame f0 on: query j = last_keys[j] */,
-                                                           const float *T_all, float fx, float fy, float cx, float cy, const float *scale_factors, int n_levels, float th, FrameP F, QueryS *q, int *err) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nq) return;
-    int lo = 0, hi = n_pairs; // qfirst[lo] <= i < qfirst[hi]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (qfirst[mid] <= i) lo = mid; else hi = mid; }
-    const float *T = T_all + 12 * lo;
-    QueryS Q{0, 0, 0, 0, 0, 0, lo};
-    if (valid[i]) {
-        const int o = last_keys[i].octave;
-        if (o < 0 || o >= n_levels) { *err = 1; q[i] = Q; return; }
-        float x3Dc[3];
-        for (int r = 0; r < 3; r++) {
-            double sacc = 0;
-            for (int k = 0; k < 3; k++) sacc += (double)T[r * 4 + k] * (double)world_pos[(size_t)i * 3 + k];
-            x3Dc[r] = (float)(sacc * 1.0 + (double)T[r * 4 + 3] * 1.0);
-        }
-        const float xc = x3Dc[0], yc = x3Dc[1];
-        const float invzc = (float)(1.0 / x3Dc[2]);
-        if (!(invzc < 0)) {
-            float u = fx * xc * invzc + cx;
-            float v = fy * yc * invzc + cy;
-            if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) { Q.x = u; Q.y = v; Q.r = th * scale_factors[o]; Q.minLevel = o - 1; Q.maxLevel = o + 1; Q.valid = 1; }
-        }
-    }
-    q[i] = Q;
-}
 } // namespace
 
+// The features of one set by vocabulary node: the node ids that occur, compacted to 0 .. n_nodes - 1 in ascending order, and per node the features in ascending index
+// (a counting sort): node k's features are items[start[k]] .. items[start[k + 1]].
+struct NodeLists {
+    std::vector<int> ids, start, items; int n_nodes = 0;
+    int compact(int nd) const { if (nd < 0) return -1; auto it = std::lower_bound(ids.begin(), ids.end(), nd); return (it != ids.end() && *it == nd) ? (int)(it - ids.begin()) : -1; }
+    NodeLists(const int *node, int N) {
+        for (int i = 0; i < N; i++) if (node[i] >= 0) ids.push_back(node[i]);
+        std::sort(ids.begin(), ids.end()); ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        n_nodes = (int)ids.size();
+        std::vector<int> nc((size_t)N);
+        start.assign((size_t)n_nodes + 1, 0);
+        for (int i = 0; i < N; i++) { nc[i] = compact(node[i]); if (nc[i] >= 0) start[nc[i] + 1]++; }
+        for (int k = 0; k < n_nodes; k++) start[k + 1] += start[k];
+        items.resize((size_t)std::max(start[n_nodes], 1));
+        std::vector<int> pos(start.begin(), start.end() - 1);
+        for (int i = 0; i < N; i++) if (nc[i] >= 0) items[pos[nc[i]]++] = i;
+    }
+};
+
+#define MT_TRY(call) do { const int r__ = (call); if (r__ != CS_OK) return r__; } while (0)
+
+// The device blocks of a handle or of one call.  Every block is allocated through alloc() and released by free_all(): there is no second list to keep.  The stream that
+// may still use a block must have drained before free_all() -- the destroy functions synchronise first, a call's scratch goes through MtScratch.
+struct MtOwner {
+    std::vector<void *> blocks;
+    template <class T> int alloc(cs_ctx *ctx, T **p, size_t n) {
+        MT_TRY(cs_dalloc(ctx, p, n));
+        blocks.push_back(*p);
+        return CS_OK;
+    }
+    void free_one(cs_ctx *ctx, void *p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); cs_dfree(ctx, p); }
+    void free_all(cs_ctx *ctx) { for (void *p : blocks) cs_dfree(ctx, p); blocks.clear(); }
+};
+// the scratch of one call: released on every way out of the call, after the stream has drained (drain() is the call's own wait for its results)
+struct MtScratch : MtOwner {
+    cs_ctx *ctx; bool drained = false;
+    explicit MtScratch(cs_ctx *c) : ctx(c) {}
+    int drain() { drained = true; CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); return CS_OK; }
+    ~MtScratch() { if (!drained) hipStreamSynchronize(ctx->stream); free_all(ctx); }
+};
 // a device array that grows to what a call needs (each array has its OWN capacity: ADVICE r5 -- one cap shared by arrays of different needs let the smaller one overflow)
 template <class T> struct DBuf {
     T *p = nullptr; size_t cap = 0;
-    int grow(cs_ctx *ctx, size_t need) {
+    int grow(cs_ctx *ctx, MtOwner &own, size_t need) {
         if (p && need <= cap) return CS_OK;
-        if (p) { cs_dfree(ctx, p); p = nullptr; cap = 0; }
+        if (p) { own.free_one(ctx, p); p = nullptr; cap = 0; }
         const size_t c = need + need / 4 + 64;
-        const int r = cs_dalloc(ctx, &p, c);
-        if (r == CS_OK) cap = c;
-        return r;
+        MT_TRY(own.alloc(ctx, &p, c));
+        cap = c;
+        return CS_OK;
     }
-    void release(cs_ctx *ctx) { if (p) cs_dfree(ctx, p); p = nullptr; cap = 0; }
 };
+
+static FrameP make_frame(int N, float minX, float maxX, float minY, float maxY) {
+    FrameP F; F.N = N; F.minX = minX; F.maxX = maxX; F.minY = minY; F.maxY = maxY;
+    F.wInv = static_cast<float>(GRID_COLS) / static_cast<float>(maxX - minX); // Frame.cc:285-286
+    F.hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(maxY - minY);
+    return F;
+}
+// What a search left in the two cursor words ([0] what the candidate arena should have held, [1] an error flag in its low word), after a wait for everything queued before.
+static int mt_cursor(cs_ctx *ctx, const unsigned long long *d_cursor, long cap, long *last_c) {
+    unsigned long long cur[2] = {0, 0};
+    MT_TRY(cs_d2h(ctx, cur, d_cursor, 2));
+    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *last_c = (long)cur[0];
+    if ((long)cur[0] > cap) { ctx->err = "matcher candidate capacity exceeded"; return CS_ERR_CAPACITY; }
+    if ((int)(cur[1] & 0xffffffffu)) return CS_ERR_BAD_ARG; // a level outside the scale / sigma table
+    return CS_OK;
+}
 
 struct cs_matcher {
     int max_kp = 0, max_q = 0; long max_cand = 0;
     FrameP F{};
+    MtOwner own;
     std::vector<cs_keypoint> keys; // host copy of mvKeysUn (what set_frame_from_orb hands back; the vbPrevMatched update of SearchForInitialization)
-    cs_keypoint *d_keys = nullptr; unsigned long long *d_desc = nullptr, *d_qdesc = nullptr;
-    int *d_cell_start = nullptr, *d_cell_items = nullptr, *d_kp_cell = nullptr, *d_ccount = nullptr; CellRec *d_cell_recs = nullptr;
-    long *d_cstart = nullptr; unsigned long long *d_cursor = nullptr; // [0] the arena's cursor, [1] an error flag (its low word)
-    QueryS *d_q = nullptr; int2 *d_cands = nullptr;
-    int *d_qrec = nullptr, *d_tm = nullptr /* max_kp + 1: train_match, nmatches behind its N entries */, *d_qm = nullptr /* max_q + 1 */;
-    float *d_f = nullptr, *d_ang = nullptr, *d_ur = nullptr; uint8_t *d_u8 = nullptr /* 2 x max_q: valid | blocks */, *d_tb = nullptr /* max_kp */; int *d_i = nullptr;
+    // the frame: per key point (max_kp) and its grid
+    cs_keypoint *d_keys = nullptr; unsigned long long *d_desc = nullptr; float *d_ur = nullptr; uint8_t *d_tb = nullptr;
+    int *d_cell_start = nullptr, *d_cell_items = nullptr, *d_kp_cell = nullptr, *d_tm = nullptr /* max_kp + 1: train_match, nmatches behind its N entries */; CellRec *d_cell_recs = nullptr;
+    // the queries: per query (max_q)
+    QueryS *d_q = nullptr; unsigned long long *d_qdesc = nullptr; long *d_cstart = nullptr;
+    int *d_ccount = nullptr, *d_qrec = nullptr, *d_qm = nullptr /* max_q + 1 */, *d_level = nullptr;
+    float *d_wp = nullptr /* x 3 */, *d_uv = nullptr /* x 2 */, *d_qur = nullptr, *d_ang = nullptr; uint8_t *d_valid = nullptr, *d_blocks = nullptr;
+    float *d_T = nullptr /* 12 */, *d_sf = nullptr /* 32 */, *d_inv = nullptr /* 32 */; // a pose and the per-level tables (n_levels <= 32)
+    int2 *d_cands = nullptr; unsigned long long *d_cursor = nullptr; // [0] the arena's cursor, [1] an error flag (its low word)
     std::vector<int> h_res;
     long last_q = 0, last_c = 0;
 };
@@ -675,18 +676,29 @@ template <int V> static int mt_resolve(cs_ctx *ctx, const ResolveP &P, int n_pro
 // results (n_res ints and the match count behind them) + the cursor, one wait
 static int mt_finish(cs_ctx *ctx, cs_matcher *m, const int *d_res, int n_res, int *out, int *nmatches) {
     m->h_res.resize((size_t)n_res + 1);
-    unsigned long long cur[2] = {0, 0};
-    int r = cs_d2h(ctx, m->h_res.data(), d_res, (size_t)n_res + 1); if (r) return r;
-    r = cs_d2h(ctx, cur, m->d_cursor, 2); if (r) return r;
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m->last_c = (long)cur[0];
-    if ((long)cur[0] > m->max_cand) { ctx->err = "matcher candidate capacity exceeded"; return CS_ERR_CAPACITY; }
+    MT_TRY(cs_d2h(ctx, m->h_res.data(), d_res, (size_t)n_res + 1));
+    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
     if (n_res) memcpy(out, m->h_res.data(), sizeof(int) * (size_t)n_res);
     *nmatches = m->h_res[(size_t)n_res];
     return CS_OK;
 }
+static int mt_alloc(cs_ctx *ctx, cs_matcher *m) {
+    const size_t nk = (size_t)m->max_kp, nq = (size_t)m->max_q;
+    MtOwner &o = m->own;
+    MT_TRY(o.alloc(ctx, &m->d_keys, nk)); MT_TRY(o.alloc(ctx, &m->d_desc, nk * 4)); MT_TRY(o.alloc(ctx, &m->d_ur, nk)); MT_TRY(o.alloc(ctx, &m->d_tb, nk));
+    MT_TRY(o.alloc(ctx, &m->d_cell_start, (size_t)NCELL + 1)); MT_TRY(o.alloc(ctx, &m->d_cell_items, nk)); MT_TRY(o.alloc(ctx, &m->d_kp_cell, nk)); MT_TRY(o.alloc(ctx, &m->d_tm, nk + 1));
+    MT_TRY(o.alloc(ctx, &m->d_cell_recs, nk));
+    MT_TRY(o.alloc(ctx, &m->d_q, nq)); MT_TRY(o.alloc(ctx, &m->d_qdesc, nq * 4)); MT_TRY(o.alloc(ctx, &m->d_cstart, nq));
+    MT_TRY(o.alloc(ctx, &m->d_ccount, nq)); MT_TRY(o.alloc(ctx, &m->d_qrec, nq + 1)); MT_TRY(o.alloc(ctx, &m->d_qm, nq + 1)); MT_TRY(o.alloc(ctx, &m->d_level, nq));
+    MT_TRY(o.alloc(ctx, &m->d_wp, nq * 3)); MT_TRY(o.alloc(ctx, &m->d_uv, nq * 2)); MT_TRY(o.alloc(ctx, &m->d_qur, nq)); MT_TRY(o.alloc(ctx, &m->d_ang, nq));
+    MT_TRY(o.alloc(ctx, &m->d_valid, nq)); MT_TRY(o.alloc(ctx, &m->d_blocks, nq));
+    MT_TRY(o.alloc(ctx, &m->d_T, (size_t)12)); MT_TRY(o.alloc(ctx, &m->d_sf, (size_t)32)); MT_TRY(o.alloc(ctx, &m->d_inv, (size_t)32));
+    MT_TRY(o.alloc(ctx, &m->d_cands, (size_t)m->max_cand)); MT_TRY(o.alloc(ctx, &m->d_cursor, (size_t)2));
+    return CS_OK;
+}
 
 struct cs_match_stream {
+    MtOwner own;
     DBuf<cs_keypoint> keys; DBuf<int> cell_start, cell_items, kp_cell, kfirst, qfirst, ccount, qrec, tm, nm; DBuf<CellRec> cell_recs; DBuf<long> cstart; DBuf<QueryS> q; DBuf<int2> cands;
     DBuf<float> wp, T; DBuf<uint8_t> valid, blocks; DBuf<unsigned long long> qdesc;
     float *d_sf = nullptr; unsigned long long *d_cursor = nullptr;
@@ -698,9 +710,7 @@ extern "C" {
 void cs_matcher_destroy(cs_ctx *ctx, cs_matcher *m) {
     if (!m) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    void *ptrs[] = {m->d_keys, m->d_desc, m->d_qdesc, m->d_cell_start, m->d_cell_items, m->d_cell_recs, m->d_kp_cell, m->d_ccount, m->d_cstart, m->d_cursor, m->d_q, m->d_cands,
-                    m->d_qrec, m->d_tm, m->d_qm, m->d_f, m->d_ang, m->d_ur, m->d_u8, m->d_tb, m->d_i};
-    for (void *p : ptrs) if (p) cs_dfree(ctx, p);
+    m->own.free_all(ctx);
     delete m;
 }
 
@@ -718,29 +728,8 @@ int cs_matcher_create(cs_ctx *ctx, int max_keypoints, int max_queries, long max_
     cs_matcher *m = new (std::nothrow) cs_matcher();
     if (!m) return CS_ERR_NOMEM;
     m->max_kp = max_keypoints; m->max_q = max_queries; m->max_cand = max_candidates;
-#define A_(call) do { int r__ = (call); if (r__ != CS_OK) { cs_matcher_destroy(ctx, m); return r__; } } while (0)
-    A_(cs_dalloc(ctx, &m->d_keys, (size_t)max_keypoints));
-    A_(cs_dalloc(ctx, &m->d_desc, (size_t)max_keypoints * 4));
-    A_(cs_dalloc(ctx, &m->d_qdesc, (size_t)max_queries * 4));
-    A_(cs_dalloc(ctx, &m->d_cell_start, (size_t)NCELL + 1));
-    A_(cs_dalloc(ctx, &m->d_cell_items, (size_t)max_keypoints));
-    A_(cs_dalloc(ctx, &m->d_cell_recs, (size_t)max_keypoints));
-    A_(cs_dalloc(ctx, &m->d_kp_cell, (size_t)max_keypoints));
-    A_(cs_dalloc(ctx, &m->d_ccount, (size_t)max_queries));
-    A_(cs_dalloc(ctx, &m->d_cstart, (size_t)max_queries));
-    A_(cs_dalloc(ctx, &m->d_cursor, (size_t)2));
-    A_(cs_dalloc(ctx, &m->d_q, (size_t)max_queries));
-    A_(cs_dalloc(ctx, &m->d_cands, (size_t)max_candidates));
-    A_(cs_dalloc(ctx, &m->d_qrec, (size_t)max_queries + 1));
-    A_(cs_dalloc(ctx, &m->d_tm, (size_t)max_keypoints + 1));
-    A_(cs_dalloc(ctx, &m->d_qm, (size_t)max_queries + 1));
-    A_(cs_dalloc(ctx, &m->d_f, (size_t)max_queries * 3 + 64));
-    A_(cs_dalloc(ctx, &m->d_ang, (size_t)max_queries));
-    A_(cs_dalloc(ctx, &m->d_ur, (size_t)max_keypoints));
-    A_(cs_dalloc(ctx, &m->d_u8, (size_t)max_queries * 2));
-    A_(cs_dalloc(ctx, &m->d_tb, (size_t)max_keypoints));
-    A_(cs_dalloc(ctx, &m->d_i, (size_t)max_queries));
-#undef A_
+    const int r = mt_alloc(ctx, m);
+    if (r != CS_OK) { cs_matcher_destroy(ctx, m); return r; }
     *out = m;
     return CS_OK;
 }
@@ -749,13 +738,11 @@ int cs_matcher_set_frame(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *keysUn, 
                          float maxY) {
     if (!ctx || !m || !keysUn || !desc || N < 0 || N > m->max_kp || !(maxX > minX) || !(maxY > minY)) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    m->F.N = N; m->F.minX = minX; m->F.maxX = maxX; m->F.minY = minY; m->F.maxY = maxY;
-    m->F.wInv = static_cast<float>(GRID_COLS) / static_cast<float>(maxX - minX); // Frame.cc:285-286
-    m->F.hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(maxY - minY);
+    m->F = make_frame(N, minX, maxX, minY, maxY);
     m->keys.assign(keysUn, keysUn + N);
-    int r = cs_h2d(ctx, m->d_keys, keysUn, (size_t)N); if (r) return r;
-    r = cs_h2d(ctx, (uint8_t *)m->d_desc, desc, (size_t)N * 32); if (r) return r;
-    CS_LAUNCH(ctx, "match_grid", match_grid, dim3(1), dim3(1024), 0, m->F, m->d_keys, m->d_cell_start, m->d_cell_items, m->d_kp_cell, m->d_cell_recs);
+    MT_TRY(cs_h2d(ctx, m->d_keys, keysUn, (size_t)N));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_desc, desc, (size_t)N * 32));
+    CS_LAUNCH(ctx, "match_grid", match_grid, dim3(1), dim3(1024), 0, m->F, m->d_keys, (const int *)nullptr, m->d_cell_start, m->d_cell_items, m->d_kp_cell, m->d_cell_recs);
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
@@ -780,23 +767,21 @@ int cs_matcher_set_frame_from_orb(cs_ctx *ctx, cs_matcher *m, const cs_orb *orb,
                                   float maxY, cs_keypoint *keysUn_out, int *n_out) {
     if (!ctx || !m || !orb || !K4 || !(maxX > minX) || !(maxY > minY)) return CS_ERR_BAD_ARG;
     const cs_keypoint *d_k = nullptr; const unsigned long long *d_d = nullptr; int N = 0;
-    int r = cs_orb_device_frame(orb, frame, &d_k, &d_d, &N); if (r) return r;
+    MT_TRY(cs_orb_device_frame(orb, frame, &d_k, &d_d, &N));
     if (N > m->max_kp) return CS_ERR_CAPACITY;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    m->F.N = N; m->F.minX = minX; m->F.maxX = maxX; m->F.minY = minY; m->F.maxY = maxY;
-    m->F.wInv = static_cast<float>(GRID_COLS) / static_cast<float>(maxX - minX); // Frame.cc:285-286
-    m->F.hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(maxY - minY);
+    m->F = make_frame(N, minX, maxX, minY, maxY);
     // UndistortKeyPoints + the descriptors, device to device; AssignFeaturesToGrid on the undistorted keypoints
     if (N > 0) {
         CS_LAUNCH(ctx, "match_undistort", match_undistort, dim3((N + 255) / 256), dim3(256), 0, N, d_k, make_undp(K4, dist5), m->d_keys);
         CS_HIP(ctx, hipMemcpyAsync(m->d_desc, d_d, (size_t)N * 32, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    CS_LAUNCH(ctx, "match_grid", match_grid, dim3(1), dim3(1024), 0, m->F, m->d_keys, m->d_cell_start, m->d_cell_items, m->d_kp_cell, m->d_cell_recs);
+    CS_LAUNCH(ctx, "match_grid", match_grid, dim3(1), dim3(1024), 0, m->F, m->d_keys, (const int *)nullptr, m->d_cell_start, m->d_cell_items, m->d_kp_cell, m->d_cell_recs);
     // mvKeysUn for the caller (and for SearchForInitialization's vbPrevMatched update); a caller that wants neither passes NULL and the frame stays on the device:
     // every search takes what it needs of a train key point from the device copy
     if (keysUn_out) {
         m->keys.resize((size_t)N);
-        r = cs_d2h(ctx, m->keys.data(), m->d_keys, (size_t)N); if (r) return r;
+        MT_TRY(cs_d2h(ctx, m->keys.data(), m->d_keys, (size_t)N));
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(keysUn_out, m->keys.data(), sizeof(cs_keypoint) * (size_t)N);
     } else m->keys.clear();
@@ -808,19 +793,16 @@ int cs_matcher_features_in_area(cs_ctx *ctx, cs_matcher *m, float x, float y, fl
     if (!ctx || !m || !n) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     QueryS Q{x, y, r, minLevel, maxLevel, 1, 0};
-    int rr = cs_h2d(ctx, m->d_q, &Q, 1); if (rr) return rr;
-    rr = mt_candidates(ctx, m, 1, false); if (rr) return rr;
-    long start = 0; int cnt = 0; unsigned long long cur[2] = {0, 0};
-    rr = cs_d2h(ctx, &start, m->d_cstart, 1); if (rr) return rr;
-    rr = cs_d2h(ctx, &cnt, m->d_ccount, 1); if (rr) return rr;
-    rr = cs_d2h(ctx, cur, m->d_cursor, 2); if (rr) return rr;
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m->last_c = (long)cur[0];
-    if ((long)cur[0] > m->max_cand) { ctx->err = "matcher candidate capacity exceeded"; return CS_ERR_CAPACITY; }
+    MT_TRY(cs_h2d(ctx, m->d_q, &Q, 1));
+    MT_TRY(mt_candidates(ctx, m, 1, false));
+    long start = 0; int cnt = 0;
+    MT_TRY(cs_d2h(ctx, &start, m->d_cstart, 1));
+    MT_TRY(cs_d2h(ctx, &cnt, m->d_ccount, 1));
+    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
     *n = cnt;
     if (out && cnt > 0 && cap > 0) {
         std::vector<int2> c((size_t)cnt);
-        rr = cs_d2h(ctx, c.data(), m->d_cands + start, (size_t)cnt); if (rr) return rr;
+        MT_TRY(cs_d2h(ctx, c.data(), m->d_cands + start, (size_t)cnt));
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < cnt && i < cap; i++) out[i] = c[i].x & 0xffffff;
     }
@@ -838,25 +820,24 @@ int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const f
     const int N = m->F.N;
     *nmatches = 0;
     if (n_last == 0) { for (int i = 0; i < N; i++) train_match[i] = -1; return CS_OK; }
-    float *d_T = m->d_f + (size_t)m->max_q * 3, *d_sf = d_T + 12;
-    uint8_t *d_blocks = m->d_u8 + m->max_q;
-    int r = cs_h2d(ctx, m->d_f, world_pos, (size_t)n_last * 3); if (r) return r;
-    r = cs_h2d(ctx, d_T, Tcw, 12); if (r) return r;
-    r = cs_h2d(ctx, d_sf, scale_factors, (size_t)n_levels); if (r) return r;
-    r = cs_h2d(ctx, m->d_u8, valid, (size_t)n_last); if (r) return r;
-    r = cs_h2d(ctx, d_blocks, blocks, (size_t)n_last); if (r) return r;
-    r = cs_h2d(ctx, m->d_i, last_octave, (size_t)n_last); if (r) return r;
-    r = cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_last * 32); if (r) return r;
-    if (check_orientation) { r = cs_h2d(ctx, m->d_ang, last_angle, (size_t)n_last); if (r) return r; }
-    if (train_blocked) { r = cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N); if (r) return r; } // map point from before the call / KeysStatic[i2] == false, :1451-1457
-    CS_LAUNCH(ctx, "match_project", match_project, dim3((n_last + 255) / 256), dim3(256), 0, n_last, m->d_f, m->d_u8, m->d_i, d_T, fx, fy, cx, cy, d_sf, th,
-              m->F, m->d_q);
-    r = mt_candidates(ctx, m, n_last, true); if (r) return r;
+    MT_TRY(cs_h2d(ctx, m->d_wp, world_pos, (size_t)n_last * 3));
+    MT_TRY(cs_h2d(ctx, m->d_T, Tcw, 12));
+    MT_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
+    MT_TRY(cs_h2d(ctx, m->d_valid, valid, (size_t)n_last));
+    MT_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_last));
+    MT_TRY(cs_h2d(ctx, m->d_level, last_octave, (size_t)n_last));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_last * 32));
+    if (check_orientation) MT_TRY(cs_h2d(ctx, m->d_ang, last_angle, (size_t)n_last));
+    if (train_blocked) MT_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N)); // map point from before the call / KeysStatic[i2] == false, :1451-1457
+    // (the levels were checked above, before anything was queued; the kernel's own check only keeps its read of the scale table in range)
+    CS_LAUNCH(ctx, "match_project", match_project, dim3((n_last + 255) / 256), dim3(256), 0, n_last, 1, (const int *)nullptr, m->d_wp, m->d_valid, m->d_level, (const cs_keypoint *)nullptr,
+              m->d_T, fx, fy, cx, cy, m->d_sf, n_levels, th, m->F, m->d_q, reinterpret_cast<int *>(m->d_cursor + 1));
+    MT_TRY(mt_candidates(ctx, m, n_last, true));
     // the greedy pass (:1397-1494) and the rotation cut (:1496-1517), on the device
     ResolveP P{};
-    P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_last; P.n_train = N; P.tkeys = m->d_keys; P.qangle = m->d_ang; P.blocks = d_blocks;
+    P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_last; P.n_train = N; P.tkeys = m->d_keys; P.qangle = m->d_ang; P.blocks = m->d_blocks;
     P.tblocked = train_blocked ? m->d_tb : nullptr; P.check_orientation = check_orientation; P.train_match = m->d_tm; P.q_rec = m->d_qrec; P.nmatches = m->d_tm + N;
-    r = mt_resolve<RV_PROJ>(ctx, P, 1, N); if (r) return r;
+    MT_TRY(mt_resolve<RV_PROJ>(ctx, P, 1, N));
     return mt_finish(ctx, m, m->d_tm, N, train_match, nmatches);
 }
 
@@ -866,10 +847,7 @@ int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const f
 void cs_match_stream_destroy(cs_ctx *ctx, cs_match_stream *m) {
     if (!m) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    m->keys.release(ctx); m->cell_start.release(ctx); m->cell_items.release(ctx); m->cell_recs.release(ctx); m->kp_cell.release(ctx); m->kfirst.release(ctx); m->qfirst.release(ctx); m->ccount.release(ctx); m->qrec.release(ctx);
-    m->tm.release(ctx); m->nm.release(ctx); m->cstart.release(ctx); m->q.release(ctx); m->cands.release(ctx); m->wp.release(ctx); m->T.release(ctx); m->valid.release(ctx); m->blocks.release(ctx); m->qdesc.release(ctx);
-    if (m->d_sf) cs_dfree(ctx, m->d_sf);
-    if (m->d_cursor) cs_dfree(ctx, m->d_cursor);
+    m->own.free_all(ctx);
     delete m;
 }
 int cs_match_stream_create(cs_match_stream **out) {
@@ -891,10 +869,10 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
     // the frames f0 .. f0 + n_pairs lie one behind the other in the extractor's buffers
     std::vector<int> first((size_t)n_pairs + 2);
     const cs_keypoint *d_k0 = nullptr; const unsigned long long *d_d0 = nullptr;
-    { int n0 = 0; int r = cs_orb_device_frame(orb, f0, &d_k0, &d_d0, &n0); if (r) return r; first[0] = 0; first[1] = n0; }
+    { int n0 = 0; MT_TRY(cs_orb_device_frame(orb, f0, &d_k0, &d_d0, &n0)); first[0] = 0; first[1] = n0; }
     for (int p = 1; p <= n_pairs; p++) {
         const cs_keypoint *dk; const unsigned long long *dd; int n = 0;
-        int r = cs_orb_device_frame(orb, f0 + p, &dk, &dd, &n); if (r) return r;
+        MT_TRY(cs_orb_device_frame(orb, f0 + p, &dk, &dd, &n));
         if (dk != d_k0 + first[p]) { ctx->err = "cs_match_by_projection_stream: the extractor's frames are not contiguous"; return CS_ERR_BAD_ARG; }
         first[p + 1] = first[p] + n;
     }
@@ -907,58 +885,51 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
     m->last_q = nq; m->last_c = 0;
     if (nq == 0 || nk == 0) return CS_OK;
     if (nk_all >= (1 << 24)) { int nmax = 0; for (int p = 1; p <= n_pairs; p++) nmax = std::max(nmax, first[p + 1] - first[p]); if (nmax >= (1 << 24)) return CS_ERR_CAPACITY; }
-    FrameP F; F.N = 0; F.minX = minX; F.maxX = maxX; F.minY = minY; F.maxY = maxY;
-    F.wInv = static_cast<float>(GRID_COLS) / static_cast<float>(maxX - minX); F.hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(maxY - minY);
-    int r;
-#define G_(call) do { r = (call); if (r != CS_OK) return r; } while (0)
-    G_(m->keys.grow(ctx, (size_t)nk_all)); G_(m->cell_items.grow(ctx, (size_t)nk_all)); G_(m->cell_recs.grow(ctx, (size_t)nk_all)); G_(m->kp_cell.grow(ctx, (size_t)nk_all)); G_(m->tm.grow(ctx, (size_t)nk));
-    G_(m->cell_start.grow(ctx, (size_t)n_pairs * (NCELL + 1))); G_(m->kfirst.grow(ctx, (size_t)n_pairs + 2)); G_(m->qfirst.grow(ctx, (size_t)n_pairs + 2)); G_(m->T.grow(ctx, (size_t)n_pairs * 12)); G_(m->nm.grow(ctx, (size_t)n_pairs));
-    G_(m->ccount.grow(ctx, (size_t)nq)); G_(m->cstart.grow(ctx, (size_t)nq)); G_(m->qrec.grow(ctx, (size_t)nq)); G_(m->q.grow(ctx, (size_t)nq)); G_(m->wp.grow(ctx, (size_t)nq * 3)); G_(m->valid.grow(ctx, (size_t)nq));
-    G_(m->blocks.grow(ctx, (size_t)nq)); if (mp_desc) G_(m->qdesc.grow(ctx, (size_t)nq * 4));
-    if (!m->d_sf) G_(cs_dalloc(ctx, &m->d_sf, (size_t)32));
-    if (!m->d_cursor) G_(cs_dalloc(ctx, &m->d_cursor, (size_t)2));
-    if (!m->cands.p) G_(m->cands.grow(ctx, std::max((size_t)nq * 12, (size_t)1 << 16))); // (5.6 candidates per query at th 15 on the bench stream; the cursor says what a window really needs)
+    const FrameP F = make_frame(0, minX, maxX, minY, maxY);
+    MT_TRY(m->keys.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->cell_items.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->cell_recs.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->kp_cell.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->tm.grow(ctx, m->own, (size_t)nk));
+    MT_TRY(m->cell_start.grow(ctx, m->own, (size_t)n_pairs * (NCELL + 1))); MT_TRY(m->kfirst.grow(ctx, m->own, (size_t)n_pairs + 2)); MT_TRY(m->qfirst.grow(ctx, m->own, (size_t)n_pairs + 2)); MT_TRY(m->T.grow(ctx, m->own, (size_t)n_pairs * 12)); MT_TRY(m->nm.grow(ctx, m->own, (size_t)n_pairs));
+    MT_TRY(m->ccount.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->cstart.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->qrec.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->q.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->wp.grow(ctx, m->own, (size_t)nq * 3)); MT_TRY(m->valid.grow(ctx, m->own, (size_t)nq));
+    MT_TRY(m->blocks.grow(ctx, m->own, (size_t)nq)); if (mp_desc) MT_TRY(m->qdesc.grow(ctx, m->own, (size_t)nq * 4));
+    if (!m->d_sf) MT_TRY(m->own.alloc(ctx, &m->d_sf, (size_t)32));
+    if (!m->d_cursor) MT_TRY(m->own.alloc(ctx, &m->d_cursor, (size_t)2));
+    if (!m->cands.p) MT_TRY(m->cands.grow(ctx, m->own, std::max((size_t)nq * 12, (size_t)1 << 16))); // (5.6 candidates per query at th 15 on the bench stream; the cursor says what a window really needs)
     // UndistortKeyPoints of every frame of the window (device to device), AssignFeaturesToGrid of the current frames
     CS_LAUNCH(ctx, "match_undistort", match_undistort, dim3((nk_all + 255) / 256), dim3(256), 0, nk_all, d_k0, make_undp(K4, dist5), m->keys.p);
     std::vector<int> kfirst((size_t)n_pairs + 1);
     int n2max = 0;
     for (int p = 0; p <= n_pairs; p++) { kfirst[p] = first[p + 1]; if (p < n_pairs) n2max = std::max(n2max, first[p + 2] - first[p + 1]); } // train frame of pair p: key points kfirst[p] .. kfirst[p + 1] of the window's list
-    G_(cs_h2d(ctx, m->kfirst.p, kfirst.data(), (size_t)n_pairs + 1));
-    G_(cs_h2d(ctx, m->qfirst.p, first.data(), (size_t)n_pairs + 1));
-    G_(cs_h2d(ctx, m->T.p, Tcw, (size_t)n_pairs * 12));
-    G_(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
-    G_(cs_h2d(ctx, m->wp.p, world_pos, (size_t)nq * 3));
-    G_(cs_h2d(ctx, m->valid.p, valid, (size_t)nq));
-    G_(cs_h2d(ctx, m->blocks.p, blocks, (size_t)nq));
-    if (mp_desc) G_(cs_h2d(ctx, (uint8_t *)m->qdesc.p, mp_desc, (size_t)nq * 32));
+    MT_TRY(cs_h2d(ctx, m->kfirst.p, kfirst.data(), (size_t)n_pairs + 1));
+    MT_TRY(cs_h2d(ctx, m->qfirst.p, first.data(), (size_t)n_pairs + 1));
+    MT_TRY(cs_h2d(ctx, m->T.p, Tcw, (size_t)n_pairs * 12));
+    MT_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
+    MT_TRY(cs_h2d(ctx, m->wp.p, world_pos, (size_t)nq * 3));
+    MT_TRY(cs_h2d(ctx, m->valid.p, valid, (size_t)nq));
+    MT_TRY(cs_h2d(ctx, m->blocks.p, blocks, (size_t)nq));
+    if (mp_desc) MT_TRY(cs_h2d(ctx, (uint8_t *)m->qdesc.p, mp_desc, (size_t)nq * 32));
     const unsigned long long *d_qdesc = mp_desc ? m->qdesc.p : d_d0; // NULL: a last frame's key point is matched with its own descriptor
     int *d_err = reinterpret_cast<int *>(m->d_cursor + 1);
     CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 16, ctx->stream));
-    CS_LAUNCH(ctx, "match_grid", match_grid_batch, dim3(n_pairs), dim3(1024), 0, F, m->keys.p, m->kfirst.p, m->cell_start.p, m->cell_items.p, m->kp_cell.p, m->cell_recs.p);
-    CS_LAUNCH(ctx, "match_project", match_project_stream, dim3((nq + 255) / 256), dim3(256), 0, nq, n_pairs, m->qfirst.p, m->wp.p, m->valid.p, d_k0, m->T.p, fx, fy, cx, cy, m->d_sf, n_levels, th, F, m->q.p, d_err);
+    CS_LAUNCH(ctx, "match_grid", match_grid, dim3(n_pairs), dim3(1024), 0, F, m->keys.p, m->kfirst.p, m->cell_start.p, m->cell_items.p, m->kp_cell.p, m->cell_recs.p);
+    CS_LAUNCH(ctx, "match_project", match_project, dim3((nq + 255) / 256), dim3(256), 0, nq, n_pairs, m->qfirst.p, m->wp.p, m->valid.p, (const int *)nullptr, d_k0 /* query j = raw key point j of frame f0 on */, m->T.p, fx, fy, cx, cy, m->d_sf, n_levels, th, F, m->q.p, d_err);
     // every pair's window enumeration (one launch) and its greedy pass + rotation cut (:1397-1517; one wave per pair): nothing of a candidate leaves the device.  The arena's
     // size is last call's need; a window that needs more says so through the cursor and the two launches run again on a larger one.
-    unsigned long long cur[2] = {0, 0};
     for (int attempt = 0;; attempt++) {
         CS_LAUNCH(ctx, "match_candidates", match_candidates, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, F, d_d0, m->kfirst.p, m->cell_start.p, m->cell_recs.p, nq, m->q.p, d_qdesc, m->d_cursor, (long)m->cands.cap,
                   m->cstart.p, m->ccount.p, m->cands.p);
         ResolveP P{};
         P.cstart = m->cstart.p; P.ccount = m->ccount.p; P.cands = m->cands.p; P.pfirst = m->qfirst.p; P.kfirst = m->kfirst.p; P.tkeys = m->keys.p; P.qkeys = m->keys.p; P.blocks = m->blocks.p;
         P.check_orientation = check_orientation; P.train_match = m->tm.p; P.q_rec = m->qrec.p; P.nmatches = m->nm.p;
-        G_(mt_resolve<RV_PROJ>(ctx, P, n_pairs, n2max));
-        G_(cs_d2h(ctx, cur, m->d_cursor, 2));
-        CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if ((int)(cur[1] & 0xffffffffu)) return CS_ERR_BAD_ARG; // a valid query whose key point's level is outside the scale table
-        if ((size_t)cur[0] <= m->cands.cap) break;
+        MT_TRY(mt_resolve<RV_PROJ>(ctx, P, n_pairs, n2max));
+        const int r = mt_cursor(ctx, m->d_cursor, (long)m->cands.cap, &m->last_c); // (BAD_ARG: a valid query whose key point's level is outside the scale table)
+        if (r == CS_OK) break;
+        if (r != CS_ERR_CAPACITY) return r;
         if (attempt) { ctx->err = "cs_match_by_projection_stream: candidate arena"; return CS_ERR_CAPACITY; }
-        G_(m->cands.grow(ctx, (size_t)cur[0]));
-        CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 16, ctx->stream));
+        MT_TRY(m->cands.grow(ctx, m->own, (size_t)m->last_c));
+        CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 8, ctx->stream)); // (the cursor; match_project's error flag behind it stays)
     }
-    m->last_c = (long)cur[0];
-    G_(cs_d2h(ctx, train_match, m->tm.p, (size_t)nk));
-    G_(cs_d2h(ctx, nmatches, m->nm.p, (size_t)n_pairs));
+    MT_TRY(cs_d2h(ctx, train_match, m->tm.p, (size_t)nk));
+    MT_TRY(cs_d2h(ctx, nmatches, m->nm.p, (size_t)n_pairs));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-#undef G_
     return CS_OK;
 }
 
@@ -985,16 +956,15 @@ int cs_match_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_x
         }
         q[i] = Q;
     }
-    uint8_t *d_blocks = m->d_u8 + m->max_q;
-    int r = cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp); if (r) return r;
-    r = cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32); if (r) return r;
-    r = cs_h2d(ctx, d_blocks, blocks, (size_t)n_mp); if (r) return r;
-    if (train_blocked) { r = cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N); if (r) return r; }
-    r = mt_candidates(ctx, m, n_mp, true); if (r) return r;
+    MT_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
+    MT_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_mp));
+    if (train_blocked) MT_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N));
+    MT_TRY(mt_candidates(ctx, m, n_mp, true));
     ResolveP P{}; // :86-140: best / second with their levels, the ratio rule, claims
-    P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_mp; P.n_train = N; P.tkeys = m->d_keys; P.blocks = d_blocks;
+    P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_mp; P.n_train = N; P.tkeys = m->d_keys; P.blocks = m->d_blocks;
     P.tblocked = train_blocked ? m->d_tb : nullptr; P.nnratio = nnratio; P.check_orientation = 0; P.train_match = m->d_tm; P.q_rec = m->d_qrec; P.nmatches = m->d_tm + N;
-    r = mt_resolve<RV_LOCAL>(ctx, P, 1, N); if (r) return r;
+    MT_TRY(mt_resolve<RV_LOCAL>(ctx, P, 1, N));
     return mt_finish(ctx, m, m->d_tm, N, train_match, nmatches);
 }
 
@@ -1012,15 +982,15 @@ int cs_match_for_initialization(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *k
         if (!(keys1[i].octave > 0)) { Q.x = prev[i * 2]; Q.y = prev[i * 2 + 1]; Q.r = (float)window_size; Q.minLevel = keys1[i].octave; Q.maxLevel = keys1[i].octave; Q.valid = 1; }
         q[i] = Q; ang[i] = keys1[i].angle;
     }
-    int r = cs_h2d(ctx, m->d_q, q.data(), (size_t)N1); if (r) return r;
-    r = cs_h2d(ctx, (uint8_t *)m->d_qdesc, desc1, (size_t)N1 * 32); if (r) return r;
-    r = cs_h2d(ctx, m->d_ang, ang.data(), (size_t)N1); if (r) return r;
-    r = mt_candidates(ctx, m, N1, true); if (r) return r;
+    MT_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)N1));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, desc1, (size_t)N1 * 32));
+    MT_TRY(cs_h2d(ctx, m->d_ang, ang.data(), (size_t)N1));
+    MT_TRY(mt_candidates(ctx, m, N1, true));
     ResolveP P{}; // :451-504 (vMatchedDistance, vnMatches21 and the displacement of an earlier match) and :506-527
     P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = N1; P.n_train = m->F.N; P.tkeys = m->d_keys; P.qangle = m->d_ang;
     P.nnratio = nnratio; P.check_orientation = check_orientation; P.q_match = m->d_qm; P.q_rec = m->d_qrec; P.nmatches = m->d_qm + N1;
-    r = mt_resolve<RV_INIT>(ctx, P, 1, m->F.N); if (r) return r;
-    r = mt_finish(ctx, m, m->d_qm, N1, vnMatches12, nmatches); if (r) return r;
+    MT_TRY(mt_resolve<RV_INIT>(ctx, P, 1, m->F.N));
+    MT_TRY(mt_finish(ctx, m, m->d_qm, N1, vnMatches12, nmatches));
     for (int i1 = 0; i1 < N1; i1++) // :529-532
         if (vnMatches12[i1] >= 0) { prev[i1 * 2] = m->keys[vnMatches12[i1]].x; prev[i1 * 2 + 1] = m->keys[vnMatches12[i1]].y; }
     return CS_OK;
@@ -1045,29 +1015,22 @@ int cs_match_fuse(cs_ctx *ctx, cs_matcher *m, const float *u_right, const float 
         }
         q[i] = Q;
     }
-    float *d_uv = m->d_f, *d_urq = m->d_f + (size_t)n_mp * 2, *d_inv = m->d_f + (size_t)m->max_q * 3 + 12;
-    int *d_err = reinterpret_cast<int *>(m->d_cursor + 1);
-    int r = cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp); if (r) return r;
-    r = cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32); if (r) return r;
-    r = cs_h2d(ctx, d_uv, uv, (size_t)n_mp * 2); if (r) return r;
-    r = cs_h2d(ctx, d_urq, ur, (size_t)n_mp); if (r) return r;
-    r = cs_h2d(ctx, d_inv, inv_level_sigma2, (size_t)n_levels); if (r) return r;
-    r = cs_h2d(ctx, m->d_i, pred_level, (size_t)n_mp); if (r) return r;
-    r = cs_h2d(ctx, m->d_u8, valid, (size_t)n_mp); if (r) return r;
-    r = cs_h2d(ctx, m->d_ur, u_right, (size_t)N); if (r) return r;
-    if (keys_static) { r = cs_h2d(ctx, m->d_tb, keys_static, (size_t)N); if (r) return r; }
-    r = mt_candidates(ctx, m, n_mp, true); if (r) return r;
+    MT_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
+    MT_TRY(cs_h2d(ctx, m->d_uv, uv, (size_t)n_mp * 2));
+    MT_TRY(cs_h2d(ctx, m->d_qur, ur, (size_t)n_mp));
+    MT_TRY(cs_h2d(ctx, m->d_inv, inv_level_sigma2, (size_t)n_levels));
+    MT_TRY(cs_h2d(ctx, m->d_level, pred_level, (size_t)n_mp));
+    MT_TRY(cs_h2d(ctx, m->d_valid, valid, (size_t)n_mp));
+    MT_TRY(cs_h2d(ctx, m->d_ur, u_right, (size_t)N));
+    if (keys_static) MT_TRY(cs_h2d(ctx, m->d_tb, keys_static, (size_t)N));
+    MT_TRY(mt_candidates(ctx, m, n_mp, true));
     // :934-981: the tests that need per-keypoint data of the key frame, first minimum wins
-    CS_LAUNCH(ctx, "match_fuse_best", match_fuse_best, dim3((n_mp + 255) / 256), dim3(256), 0, n_mp, m->d_cstart, m->d_ccount, m->d_cands, m->d_keys, m->d_ur, d_inv, n_levels,
-              keys_static ? m->d_tb : (const uint8_t *)nullptr, d_uv, d_urq, m->d_i, m->d_u8, m->d_qm, m->d_qrec, d_err);
-    unsigned long long cur[2] = {0, 0};
-    r = cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp); if (r) return r;
-    r = cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp); if (r) return r;
-    r = cs_d2h(ctx, cur, m->d_cursor, 2); if (r) return r;
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m->last_c = (long)cur[0];
-    if ((long)cur[0] > m->max_cand) { ctx->err = "matcher candidate capacity exceeded"; return CS_ERR_CAPACITY; }
-    if ((int)(cur[1] & 0xffffffffu)) return CS_ERR_BAD_ARG; // a candidate's level outside the sigma table
+    CS_LAUNCH(ctx, "match_fuse_best", match_fuse_best, dim3((n_mp + 255) / 256), dim3(256), 0, n_mp, m->d_cstart, m->d_ccount, m->d_cands, m->d_keys, m->d_ur, m->d_inv, n_levels,
+              keys_static ? m->d_tb : (const uint8_t *)nullptr, m->d_uv, m->d_qur, m->d_level, m->d_valid, m->d_qm, m->d_qrec, reinterpret_cast<int *>(m->d_cursor + 1));
+    MT_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
+    MT_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
+    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c)); // (BAD_ARG: a candidate's level outside the sigma table)
     int nf = 0;
     for (int i = 0; i < n_mp; i++) if (best_dist[i] <= TH_LOW) nf++;
     *n_fused = nf;
@@ -1086,47 +1049,28 @@ int cs_match_for_triangulation(cs_ctx *ctx, const cs_keypoint *keys1Un, const ui
     if (N1 == 0 || N2 == 0) return CS_OK;
     for (int i = 0; i < N2; i++) if (keys2Un[i].octave < 0 || keys2Un[i].octave >= n_levels) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    // KF2 features by node (counting sort keeps the ascending index order inside a node); node ids are compacted to 0..n_nodes-1
-    std::vector<int> ids;
-    for (int i = 0; i < N2; i++) if (node2[i] >= 0) ids.push_back(node2[i]);
-    std::sort(ids.begin(), ids.end()); ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    const int n_nodes = (int)ids.size();
-    auto compact = [&](int nd) { if (nd < 0) return -1; auto it = std::lower_bound(ids.begin(), ids.end(), nd); return (it != ids.end() && *it == nd) ? (int)(it - ids.begin()) : -1; };
-    std::vector<int> start((size_t)n_nodes + 1, 0), items, n1c((size_t)N1);
-    std::vector<int> n2c((size_t)N2);
-    for (int i = 0; i < N2; i++) { n2c[i] = compact(node2[i]); if (n2c[i] >= 0) start[n2c[i] + 1]++; }
-    for (int k = 0; k < n_nodes; k++) start[k + 1] += start[k];
-    items.resize((size_t)std::max(start[n_nodes], 1));
-    { std::vector<int> pos(start.begin(), start.end() - 1); for (int i = 0; i < N2; i++) if (n2c[i] >= 0) items[pos[n2c[i]]++] = i; }
-    for (int i = 0; i < N1; i++) n1c[i] = compact(node1[i]);
+    const NodeLists L(node2, N2);
+    std::vector<int> n1c((size_t)N1), res((size_t)N1 + 1);
+    for (int i = 0; i < N1; i++) n1c[i] = L.compact(node1[i]);
+    MtScratch sc(ctx); // (after the host arrays: it waits for the copies out of and into them before they go)
     cs_keypoint *d_k1 = nullptr, *d_k2 = nullptr; unsigned long long *d_d1 = nullptr, *d_d2 = nullptr; int *d_n1 = nullptr, *d_st = nullptr, *d_it = nullptr, *d_m = nullptr;
     uint8_t *d_s1 = nullptr, *d_s2 = nullptr; float *d_u1 = nullptr, *d_u2 = nullptr, *d_sc = nullptr, *d_sg = nullptr;
-    int r = cs_dalloc(ctx, &d_k1, (size_t)N1);
-#define TA_(call) if (!r) r = (call)
-    TA_(cs_dalloc(ctx, &d_k2, (size_t)N2)); TA_(cs_dalloc(ctx, &d_d1, (size_t)N1 * 4)); TA_(cs_dalloc(ctx, &d_d2, (size_t)N2 * 4));
-    TA_(cs_dalloc(ctx, &d_n1, (size_t)N1)); TA_(cs_dalloc(ctx, &d_st, (size_t)n_nodes + 1)); TA_(cs_dalloc(ctx, &d_it, items.size())); TA_(cs_dalloc(ctx, &d_m, (size_t)N1 + 1));
-    TA_(cs_dalloc(ctx, &d_s1, (size_t)N1)); TA_(cs_dalloc(ctx, &d_s2, (size_t)N2)); TA_(cs_dalloc(ctx, &d_u1, (size_t)N1)); TA_(cs_dalloc(ctx, &d_u2, (size_t)N2));
-    TA_(cs_dalloc(ctx, &d_sc, (size_t)n_levels)); TA_(cs_dalloc(ctx, &d_sg, (size_t)n_levels));
-    TA_(cs_h2d(ctx, d_k1, keys1Un, (size_t)N1)); TA_(cs_h2d(ctx, d_k2, keys2Un, (size_t)N2));
-    TA_(cs_h2d(ctx, (uint8_t *)d_d1, desc1, (size_t)N1 * 32)); TA_(cs_h2d(ctx, (uint8_t *)d_d2, desc2, (size_t)N2 * 32));
-    TA_(cs_h2d(ctx, d_n1, n1c.data(), (size_t)N1)); TA_(cs_h2d(ctx, d_st, start.data(), start.size())); TA_(cs_h2d(ctx, d_it, items.data(), items.size()));
-    TA_(cs_h2d(ctx, d_s1, skip1, (size_t)N1)); TA_(cs_h2d(ctx, d_s2, skip2, (size_t)N2)); TA_(cs_h2d(ctx, d_u1, u_right1, (size_t)N1)); TA_(cs_h2d(ctx, d_u2, u_right2, (size_t)N2));
-    TA_(cs_h2d(ctx, d_sc, scale_factors2, (size_t)n_levels)); TA_(cs_h2d(ctx, d_sg, level_sigma2_2, (size_t)n_levels));
-#undef TA_
-    std::vector<int> res((size_t)N1 + 1);
-    if (!r) {
-        TriP P; for (int k = 0; k < 9; k++) P.F12[k] = F12[k];
-        P.ex = ex; P.ey = ey; P.only_stereo = only_stereo;
-        CS_LAUNCH(ctx, "match_triangulation", match_triangulation, dim3((N1 + 3) / 4), dim3(256), 0, N1, d_k1, d_d1, d_n1, d_s1, d_u1, d_k2, d_d2, d_s2, d_u2, d_st, d_it, n_nodes, P,
-                  d_sc, d_sg, d_m);
-        CS_LAUNCH(ctx, "match_orient_cut", match_orient_cut, dim3(1), dim3(1024), 0, N1, d_k1, d_k2, d_m, check_orientation, d_m + N1); // :801-830
-        r = cs_d2h(ctx, res.data(), d_m, (size_t)N1 + 1);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_k1, d_k2, d_d1, d_d2, d_n1, d_st, d_it, d_m, d_s1, d_s2, d_u1, d_u2, d_sc, d_sg};
-    for (void *p : ptrs) if (p) cs_dfree(ctx, p);
-    if (r) return r;
+    MT_TRY(sc.alloc(ctx, &d_k1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_k2, (size_t)N2)); MT_TRY(sc.alloc(ctx, &d_d1, (size_t)N1 * 4)); MT_TRY(sc.alloc(ctx, &d_d2, (size_t)N2 * 4));
+    MT_TRY(sc.alloc(ctx, &d_n1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_st, L.start.size())); MT_TRY(sc.alloc(ctx, &d_it, L.items.size())); MT_TRY(sc.alloc(ctx, &d_m, (size_t)N1 + 1));
+    MT_TRY(sc.alloc(ctx, &d_s1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_s2, (size_t)N2)); MT_TRY(sc.alloc(ctx, &d_u1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_u2, (size_t)N2));
+    MT_TRY(sc.alloc(ctx, &d_sc, (size_t)n_levels)); MT_TRY(sc.alloc(ctx, &d_sg, (size_t)n_levels));
+    MT_TRY(cs_h2d(ctx, d_k1, keys1Un, (size_t)N1)); MT_TRY(cs_h2d(ctx, d_k2, keys2Un, (size_t)N2));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)d_d1, desc1, (size_t)N1 * 32)); MT_TRY(cs_h2d(ctx, (uint8_t *)d_d2, desc2, (size_t)N2 * 32));
+    MT_TRY(cs_h2d(ctx, d_n1, n1c.data(), (size_t)N1)); MT_TRY(cs_h2d(ctx, d_st, L.start.data(), L.start.size())); MT_TRY(cs_h2d(ctx, d_it, L.items.data(), L.items.size()));
+    MT_TRY(cs_h2d(ctx, d_s1, skip1, (size_t)N1)); MT_TRY(cs_h2d(ctx, d_s2, skip2, (size_t)N2)); MT_TRY(cs_h2d(ctx, d_u1, u_right1, (size_t)N1)); MT_TRY(cs_h2d(ctx, d_u2, u_right2, (size_t)N2));
+    MT_TRY(cs_h2d(ctx, d_sc, scale_factors2, (size_t)n_levels)); MT_TRY(cs_h2d(ctx, d_sg, level_sigma2_2, (size_t)n_levels));
+    TriP P; for (int k = 0; k < 9; k++) P.F12[k] = F12[k];
+    P.ex = ex; P.ey = ey; P.only_stereo = only_stereo;
+    CS_LAUNCH(ctx, "match_triangulation", match_triangulation, dim3((N1 + 3) / 4), dim3(256), 0, N1, d_k1, d_d1, d_n1, d_s1, d_u1, d_k2, d_d2, d_s2, d_u2, d_st, d_it, L.n_nodes, P,
+              d_sc, d_sg, d_m);
+    CS_LAUNCH(ctx, "match_orient_cut", match_orient_cut, dim3(1), dim3(1024), 0, N1, d_k1, d_k2, d_m, check_orientation, d_m + N1); // :801-830
+    MT_TRY(cs_d2h(ctx, res.data(), d_m, (size_t)N1 + 1));
+    MT_TRY(sc.drain());
     memcpy(matches12, res.data(), sizeof(int) * (size_t)N1);
     *nmatches = res[(size_t)N1];
     return CS_OK;
@@ -1141,18 +1085,10 @@ template <int V> static int bow_search(cs_ctx *ctx, const cs_keypoint *keysK, co
                                        const int *nodeF, const uint8_t *skipF, float nnratio, int check_orientation, int *out, int *nmatches) {
     CS_HIP(ctx, hipSetDevice(ctx->device));
     if (NF >= (1 << 24)) return CS_ERR_CAPACITY;
-    std::vector<int> ids;
-    for (int i = 0; i < NF; i++) if (nodeF[i] >= 0) ids.push_back(nodeF[i]);
-    std::sort(ids.begin(), ids.end()); ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-    const int n_nodes = (int)ids.size();
-    auto compact = [&](int nd) { if (nd < 0) return -1; auto it = std::lower_bound(ids.begin(), ids.end(), nd); return (it != ids.end() && *it == nd) ? (int)(it - ids.begin()) : -1; };
-    std::vector<int> start((size_t)n_nodes + 1, 0), items, nkc((size_t)NK, -1), nfc((size_t)NF), cnt((size_t)NK, 0);
+    const NodeLists L(nodeF, NF);
+    std::vector<int> nkc((size_t)NK, -1), cnt((size_t)NK, 0);
     std::vector<long> off((size_t)NK + 1, 0);
-    for (int i = 0; i < NF; i++) { nfc[i] = compact(nodeF[i]); if (nfc[i] >= 0) start[nfc[i] + 1]++; }
-    for (int k = 0; k < n_nodes; k++) start[k + 1] += start[k];
-    items.resize((size_t)std::max(start[n_nodes], 1));
-    { std::vector<int> pos(start.begin(), start.end() - 1); for (int i = 0; i < NF; i++) if (nfc[i] >= 0) items[pos[nfc[i]]++] = i; }
-    for (int i = 0; i < NK; i++) { nkc[i] = skipK[i] ? -1 : compact(nodeK[i]); cnt[i] = nkc[i] >= 0 ? start[nkc[i] + 1] - start[nkc[i]] : 0; off[i + 1] = off[i] + cnt[i]; }
+    for (int i = 0; i < NK; i++) { nkc[i] = skipK[i] ? -1 : L.compact(nodeK[i]); cnt[i] = nkc[i] >= 0 ? L.start[nkc[i] + 1] - L.start[nkc[i]] : 0; off[i + 1] = off[i] + cnt[i]; }
     const long total = off[NK];
     // the reference's order: nodes ascending (std::map), K features ascending inside a node
     std::vector<std::pair<int, int>> order;
@@ -1164,33 +1100,25 @@ template <int V> static int bow_search(cs_ctx *ctx, const cs_keypoint *keysK, co
     if (n_steps == 0 || total == 0) return CS_OK; // (out is pre-filled with -1 by the callers)
     std::vector<int> qlist((size_t)n_steps);
     for (int s = 0; s < n_steps; s++) qlist[s] = order[s].second;
+    std::vector<int> res((size_t)n_out + 1, -1);
+    MtScratch sc(ctx); // (after the host arrays: it waits for the copies out of and into them before they go)
     cs_keypoint *d_kk = nullptr, *d_kf = nullptr; unsigned long long *d_dk = nullptr, *d_df = nullptr; int *d_nk = nullptr, *d_st = nullptr, *d_it = nullptr, *d_cnt = nullptr, *d_ql = nullptr, *d_rec = nullptr, *d_out = nullptr;
     long *d_off = nullptr; int2 *d_ca = nullptr; uint8_t *d_sf = nullptr;
-    int r = cs_dalloc(ctx, &d_dk, (size_t)NK * 4);
-#define BA_(call) if (!r) r = (call)
-    BA_(cs_dalloc(ctx, &d_df, (size_t)NF * 4)); BA_(cs_dalloc(ctx, &d_nk, (size_t)NK)); BA_(cs_dalloc(ctx, &d_st, start.size())); BA_(cs_dalloc(ctx, &d_it, items.size()));
-    BA_(cs_dalloc(ctx, &d_off, off.size())); BA_(cs_dalloc(ctx, &d_ca, (size_t)total)); BA_(cs_dalloc(ctx, &d_cnt, (size_t)NK)); BA_(cs_dalloc(ctx, &d_ql, (size_t)n_steps)); BA_(cs_dalloc(ctx, &d_rec, (size_t)NK));
-    BA_(cs_dalloc(ctx, &d_out, (size_t)n_out + 1)); BA_(cs_dalloc(ctx, &d_kk, (size_t)NK)); BA_(cs_dalloc(ctx, &d_kf, (size_t)NF)); if (skipF) BA_(cs_dalloc(ctx, &d_sf, (size_t)NF));
-    BA_(cs_h2d(ctx, (uint8_t *)d_dk, descK, (size_t)NK * 32)); BA_(cs_h2d(ctx, (uint8_t *)d_df, descF, (size_t)NF * 32)); BA_(cs_h2d(ctx, d_nk, nkc.data(), (size_t)NK));
-    BA_(cs_h2d(ctx, d_st, start.data(), start.size())); BA_(cs_h2d(ctx, d_it, items.data(), items.size())); BA_(cs_h2d(ctx, d_off, off.data(), off.size()));
-    BA_(cs_h2d(ctx, d_cnt, cnt.data(), (size_t)NK)); BA_(cs_h2d(ctx, d_ql, qlist.data(), (size_t)n_steps)); BA_(cs_h2d(ctx, d_kk, keysK, (size_t)NK)); BA_(cs_h2d(ctx, d_kf, keysF, (size_t)NF));
-    if (skipF) BA_(cs_h2d(ctx, d_sf, skipF, (size_t)NF));
-    std::vector<int> res((size_t)n_out + 1, -1);
-    if (!r && V == RV_BOWKF) { hipError_t e = hipMemsetAsync(d_out, 0xff, sizeof(int) * (size_t)NK, ctx->stream); if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; } } // K features outside the visiting order have no match
-    if (!r) {
-        CS_LAUNCH(ctx, "match_bow_dists", match_bow_dists, dim3((NK + 3) / 4), dim3(256), 0, NK, d_dk, d_nk, d_df, d_st, d_it, d_off, d_ca);
-        ResolveP P{};
-        P.cstart = d_off; P.ccount = d_cnt; P.cands = d_ca; P.qlist = d_ql; P.n_steps = n_steps; P.n_train = NF; P.tkeys = d_kf; P.qkeys = d_kk; P.tblocked = d_sf; P.nnratio = nnratio;
-        P.check_orientation = check_orientation; P.train_match = d_out; P.q_match = d_out; P.q_rec = d_rec; P.nmatches = d_out + n_out;
-        r = mt_resolve<V>(ctx, P, 1, NF);
-    }
-    BA_(cs_d2h(ctx, res.data(), d_out, (size_t)n_out + 1));
-#undef BA_
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_kk, d_kf, d_dk, d_df, d_nk, d_st, d_it, d_cnt, d_ql, d_rec, d_out, d_off, d_ca, d_sf};
-    for (void *p : ptrs) if (p) cs_dfree(ctx, p);
-    if (r) return r;
+    MT_TRY(sc.alloc(ctx, &d_dk, (size_t)NK * 4)); MT_TRY(sc.alloc(ctx, &d_df, (size_t)NF * 4)); MT_TRY(sc.alloc(ctx, &d_nk, (size_t)NK)); MT_TRY(sc.alloc(ctx, &d_st, L.start.size())); MT_TRY(sc.alloc(ctx, &d_it, L.items.size()));
+    MT_TRY(sc.alloc(ctx, &d_off, off.size())); MT_TRY(sc.alloc(ctx, &d_ca, (size_t)total)); MT_TRY(sc.alloc(ctx, &d_cnt, (size_t)NK)); MT_TRY(sc.alloc(ctx, &d_ql, (size_t)n_steps)); MT_TRY(sc.alloc(ctx, &d_rec, (size_t)NK));
+    MT_TRY(sc.alloc(ctx, &d_out, (size_t)n_out + 1)); MT_TRY(sc.alloc(ctx, &d_kk, (size_t)NK)); MT_TRY(sc.alloc(ctx, &d_kf, (size_t)NF)); if (skipF) MT_TRY(sc.alloc(ctx, &d_sf, (size_t)NF));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)d_dk, descK, (size_t)NK * 32)); MT_TRY(cs_h2d(ctx, (uint8_t *)d_df, descF, (size_t)NF * 32)); MT_TRY(cs_h2d(ctx, d_nk, nkc.data(), (size_t)NK));
+    MT_TRY(cs_h2d(ctx, d_st, L.start.data(), L.start.size())); MT_TRY(cs_h2d(ctx, d_it, L.items.data(), L.items.size())); MT_TRY(cs_h2d(ctx, d_off, off.data(), off.size()));
+    MT_TRY(cs_h2d(ctx, d_cnt, cnt.data(), (size_t)NK)); MT_TRY(cs_h2d(ctx, d_ql, qlist.data(), (size_t)n_steps)); MT_TRY(cs_h2d(ctx, d_kk, keysK, (size_t)NK)); MT_TRY(cs_h2d(ctx, d_kf, keysF, (size_t)NF));
+    if (skipF) MT_TRY(cs_h2d(ctx, d_sf, skipF, (size_t)NF));
+    if (V == RV_BOWKF) CS_HIP(ctx, hipMemsetAsync(d_out, 0xff, sizeof(int) * (size_t)NK, ctx->stream)); // K features outside the visiting order have no match
+    CS_LAUNCH(ctx, "match_bow_dists", match_bow_dists, dim3((NK + 3) / 4), dim3(256), 0, NK, d_dk, d_nk, d_df, d_st, d_it, d_off, d_ca);
+    ResolveP P{};
+    P.cstart = d_off; P.ccount = d_cnt; P.cands = d_ca; P.qlist = d_ql; P.n_steps = n_steps; P.n_train = NF; P.tkeys = d_kf; P.qkeys = d_kk; P.tblocked = d_sf; P.nnratio = nnratio;
+    P.check_orientation = check_orientation; P.train_match = d_out; P.q_match = d_out; P.q_rec = d_rec; P.nmatches = d_out + n_out;
+    MT_TRY(mt_resolve<V>(ctx, P, 1, NF));
+    MT_TRY(cs_d2h(ctx, res.data(), d_out, (size_t)n_out + 1));
+    MT_TRY(sc.drain());
     memcpy(out, res.data(), sizeof(int) * (size_t)n_out);
     *nmatches = res[(size_t)n_out];
     return CS_OK;
@@ -1220,22 +1148,16 @@ int cs_hamming_knn2(cs_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int
     if (!ctx || !q || !t || nq < 0 || nt < 0 || !best_idx || !best_dist || !second_dist) return CS_ERR_BAD_ARG;
     if (nq == 0) return CS_OK;
     CS_HIP(ctx, hipSetDevice(ctx->device));
+    MtScratch sc(ctx);
     unsigned long long *dq = nullptr, *dt = nullptr; int *dres = nullptr;
-    int r = cs_dalloc(ctx, &dq, (size_t)nq * 4); if (r) return r;
-    r = cs_dalloc(ctx, &dt, (size_t)std::max(nt, 1) * 4); if (r) { cs_dfree(ctx, dq); return r; }
-    r = cs_dalloc(ctx, &dres, (size_t)nq * 3); if (r) { cs_dfree(ctx, dq); cs_dfree(ctx, dt); return r; }
-    r = cs_h2d(ctx, (uint8_t *)dq, q, (size_t)nq * 32);
-    if (!r) r = cs_h2d(ctx, (uint8_t *)dt, t, (size_t)nt * 32);
-    if (!r) {
-        CS_LAUNCH(ctx, "match_knn2", match_knn2, dim3((nq + 255) / 256), dim3(256), 0, dq, nq, dt, nt, dres, dres + nq, dres + 2 * nq);
-        r = cs_d2h(ctx, best_idx, dres, (size_t)nq);
-        if (!r) r = cs_d2h(ctx, best_dist, dres + nq, (size_t)nq);
-        if (!r) r = cs_d2h(ctx, second_dist, dres + 2 * nq, (size_t)nq);
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    }
-    cs_dfree(ctx, dq); cs_dfree(ctx, dt); cs_dfree(ctx, dres);
-    return r;
+    MT_TRY(sc.alloc(ctx, &dq, (size_t)nq * 4)); MT_TRY(sc.alloc(ctx, &dt, (size_t)std::max(nt, 1) * 4)); MT_TRY(sc.alloc(ctx, &dres, (size_t)nq * 3));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)dq, q, (size_t)nq * 32));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)dt, t, (size_t)nt * 32));
+    CS_LAUNCH(ctx, "match_knn2", match_knn2, dim3((nq + 255) / 256), dim3(256), 0, dq, nq, dt, nt, dres, dres + nq, dres + 2 * nq);
+    MT_TRY(cs_d2h(ctx, best_idx, dres, (size_t)nq));
+    MT_TRY(cs_d2h(ctx, best_dist, dres + nq, (size_t)nq));
+    MT_TRY(cs_d2h(ctx, second_dist, dres + 2 * nq, (size_t)nq));
+    return sc.drain();
 }
 
 } // extern "C"

@@ -920,6 +920,37 @@ __global__ void __launch_bounds__(256) orb_compact_sel(QtParams Q, const SelKP *
     for (int i = threadIdx.x; i < n; i += 256) sel[b + i] = src[i];
 }
 
+// The most candidates a child of a root node's first split can hold on a level (orb_quadtree packs the four child sizes of a split into 16 bits each; every later
+// child is part of one of these, roots are counted in ints).  orb_cells suppresses non-maxima inside a cell's own window, where everything outside the window scores
+// zero: survivors are never 8-adjacent INSIDE a cell -- a piece of s x t pixels of one cell holds at most ceil(s/2) * ceil(t/2) of them, one per 2 x 2 block -- but two
+// of them may touch across the seam of two cells.  Cell j emits the columns [3 + j * wCell, min(3 + (j + 1) * wCell, fw - 3)) of the level's candidate frame (rows
+// alike), so a box holds at most (sum over the cells of ceil(columns shared / 2)) * (the same over rows).  The boxes are DivideNode's, with a pixel of slack where a
+// root's float bucket x / hX and its integer box can differ.
+static int qt_half_span(int lo, int hi, int cell, int n_cells, int extent) {
+    int s = 0;
+    for (int j = 0; j < n_cells; j++) {
+        const int a = std::max(lo, 3 + j * cell), b = std::min(hi, std::min(3 + (j + 1) * cell, extent - 3));
+        if (b > a) s += (b - a + 1) / 2;
+    }
+    return s;
+}
+static long qt_first_split_child_bound(const Lvl &L) {
+    const int fw = L.maxBX - MINB, fh = L.maxBY - MINB;
+    if (L.nCols < 1 || L.nRows < 1) return 0; // a level without a cell has no candidate
+    const int nIni = (int)std::round(static_cast<float>(fw) / fh);
+    if (nIni < 1 || nIni > 4) return 0;       // the kernel leaves these to the host before it splits anything
+    const float hX = static_cast<float>(fw) / nIni;
+    const int my = (int)std::ceil(static_cast<float>(fh) / 2);
+    const long rows = std::max(qt_half_span(0, my, L.hCell, L.nRows, fh), qt_half_span(my, fh, L.hCell, L.nRows, fh));
+    long cols = 0;
+    for (int b = 0; b < nIni; b++) {
+        const int x0 = (int)(hX * static_cast<float>(b)), x1 = (int)(hX * static_cast<float>(b + 1)), mx = x0 + (int)std::ceil(static_cast<float>(x1 - x0) / 2);
+        cols = std::max<long>(cols, qt_half_span(std::max(x0 - 1, 0), mx, L.wCell, L.nCols, fw));
+        cols = std::max<long>(cols, qt_half_span(mx, b == nIni - 1 ? fw : x1 + 1, L.wCell, L.nCols, fw));
+    }
+    return cols * rows;
+}
+
 } // namespace
 
 struct cs_orb {
@@ -1103,6 +1134,7 @@ int cs_orb_create(cs_ctx *ctx, int nfeatures, float scaleFactor, int nlevels, in
             node_off += q.capn; slot_off += 4 * std::max(q.N, 1) + 16;
             maxN = std::max(maxN, q.N);
             if (L.maxBX >= 32768 || L.maxBY >= 32768) ok = false;
+            if (qt_first_split_child_bound(L) >= 65536) ok = false; // a child size would not fit its 16 bits of cnt64: the host quadtree takes such sizes
         }
         Q.nodes_per_frame = node_off; Q.slots_per_frame = slot_off;
         const int CAPL = 4 * std::max(maxN, 1) + 16, CAPV = std::max(maxN, 1) + 8, CAPN = 12 * std::max(maxN, 1) + 64;

@@ -36,6 +36,7 @@ constexpr int NMS_TW = 64, NMS_TH = 16;
 constexpr int DT_INIT = INT_MAX >> 2;
 constexpr int DT_HV = 62587;    // cvRound(0.955f * 65536)
 constexpr int DT_DIAG = 89738;  // cvRound(1.3693f * 65536)  (checked against the float product on the host at create())
+constexpr size_t DT_SERIAL_ROW_BYTES = 2 * 4 * sizeof(int); // cuboid_dt: LDS per column of the widest ROI (two row buffers for each of a workgroup's four waves)
 constexpr double PI = 3.14159265358979323846;
 // cuboid_sweep_score (corner construction + edge scoring, the unit's chamfer map resident in LDS as 16-bit codes), see the kernel
 constexpr int SC_LDS_BYTES = 160 * 1024;
@@ -2229,6 +2230,11 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
     CS_HIP(ctx, hipMemsetAsync(b->d_out, 0, sizeof(cs_cuboid) * (size_t)std::max(1, b->n_boxes * b->o.max_cuboid_num), ctx->stream));
     if (b->n_units == 0) return CS_OK;
     const int U = b->n_units;
+    if (!b->dt_C && b->max_roi_w > 1024) { // the serial distance transform keeps two rows per wave in LDS: past 64 KB (ROIs wider than 2 046) the kernel has to be told
+        const size_t lds = (size_t)(b->max_roi_w + 2) * DT_SERIAL_ROW_BYTES;
+        if (lds > (size_t)SC_LDS_BYTES) { ctx->err = "a box ROI is too wide for the distance transform"; return CS_ERR_CAPACITY; }
+        if (lds > 64 * 1024) CS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(cuboid_dt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
     int ul_cap = 1;
     for (const FrameInfo &fi_ : b->fi) ul_cap = std::max(ul_cap, std::min(fi_.n_lines, CS_MAX_ROI_LINES));
     // (per-kernel event timing reads one stream: a timed run keeps everything on it)
@@ -2269,8 +2275,8 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
     } else if (b->max_roi_w <= 1024) {
         CS_LAUNCH(ctx, "cuboid_dt", cuboid_dt_block, dim3(U), dim3(64 * ((b->max_roi_w + 63) / 64)), 0, b->d_units, b->d_emap, b->d_dist);
     } else { // very wide ROIs: one wave per ROI, segments scanned serially
-        const int wbuf = b->W + 2;
-        CS_LAUNCH(ctx, "cuboid_dt", cuboid_dt, dim3((U + 3) / 4), dim3(256), (size_t)wbuf * 2 * 4 * sizeof(int), b->d_units, U, b->d_emap, b->d_dist, wbuf);
+        const int wbuf = b->max_roi_w + 2;
+        CS_LAUNCH(ctx, "cuboid_dt", cuboid_dt, dim3((U + 3) / 4), dim3(256), (size_t)wbuf * DT_SERIAL_ROW_BYTES, b->d_units, U, b->d_emap, b->d_dist, wbuf);
     }
     if (fork) CS_HIP(ctx, hipStreamWaitEvent(ctx->stream, b->ev_join, 0));
     else

@@ -110,8 +110,10 @@ def test_edge_cases(ctx, oracle):
 
 @pytest.mark.parametrize("W,H", [(640, 480), (1241, 376)])
 def test_distance_transform_variants_agree(ctx, oracle, monkeypatch, W, H):
-    """The wave-per-ROI distance transform (default, ROI width <= 1280) and the workgroup-per-ROI one (CUBESLAM_DT=block) are the same
-    integer recurrence: identical maps, also for a wide ROI that needs more columns per lane, and both equal to the oracle."""
+    """The wave-per-ROI distance transform (default, ROI width <= 1280) and what CUBESLAM_DT=block runs instead are the same integer recurrence:
+    identical maps, also for a wide ROI that needs more columns per lane, and both equal to the oracle.  At 640 x 480 the widest ROI is 635 columns:
+    cuboid_dt_wave<10> against cuboid_dt_block with 10 waves.  At 1241 x 376 it is 1 236 columns, above cuboid_dt_block's 1 024: cuboid_dt_wave<20>
+    against the serial cuboid_dt.  (Every rung, cuboid_dt_block up to 16 waves and the hand-overs: tests/test_cuboid_edges_gpu.py.)"""
     det = detect_3d_cuboid(ctx)
     s = synth.cuboid_scene(42, n_boxes=3, W=W, H=H)
     boxes = np.array(s["boxes"], np.float64)

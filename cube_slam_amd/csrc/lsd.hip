@@ -40,41 +40,55 @@ struct GK { double k[2 * KH + 1]; };
 
 // From the gray frame to the level-line maps in one row-streaming kernel: GaussianBlur(7x7, sigma 0.75, u8 -> double), cv::resize(0.8, INTER_LINEAR) and
 // ll_angle's 2x2 gradient -- neither the blurred frame (8 B per pixel) nor the scaled one (8 B per scaled pixel) makes the round trip through memory.
-// One wave per strip of 64 scaled columns and LSD_ROWS scaled rows.  The strip's blurred columns start at xofs[d0] and stay below 128 of them (83 at
-// scale 0.8, checked by cs_lsd_create): two per lane, lane j holds columns xofs[d0] + j and + 64 + j.  The gray rows are streamed downwards (8 in
-// flight), filtered horizontally from an LDS line of bytes, and the last seven horizontal results stay in registers for the vertical pass; the last two
-// blurred rows stay for the resize, whose taps reach the neighbouring columns by lane reads; the last scaled row stays for the gradient, the column
-// right of the strip computed by every lane.  A strip that starts a block re-reads three gray rows above and below and one scaled row below (halo).
+// One wave per strip of LSD_COLS = 48 scaled columns and LSD_ROWS scaled rows.  The strip's blurred columns start at xofs[d0] and stay within LSD_SPAN = 64
+// of them (62 at scale 0.8, checked by cs_lsd_create): one per lane, lane j filters column xofs[d0] + j.  The state lives in LDS, which the region walks
+// beside this kernel do not use, and the registers hold what a lane alone reads:
+//   * a gray row is streamed in (5 rows in flight), each byte converted to double ONCE by the lane that loaded it and left in an LDS line; the seven taps
+//     of the horizontal pass are read from there;
+//   * the last seven horizontal results of the lane's column stay in registers (a ring indexed by the unrolled row number: no moves);
+//   * the last two blurred rows are an LDS ring, from which the resize reads its four taps;
+//   * lane 48 resizes the column right of the strip (once, not by every lane); the last two scaled rows are an LDS ring too, from which the gradient
+//     reads its upper, right and upper-right neighbours;
+//   * the row tables (yofs, ay) are read once, a scaled row per lane, and reach the loop by lane reads into scalars.
+// A single wave runs its LDS instructions in order, so a line written by all lanes is read by all lanes without a barrier; the compiler is kept from
+// moving the accesses across each other.  A strip that starts a block re-reads three gray rows above and below and one scaled row below (halo).
 //   * blur: the summation order of OpenCV's symmetric filters, centre tap first, then k[t] * (left + right) for t = 1..3; REFLECT_101 borders
 //   * resize: (src[sy0][sx0] * ax0 + src[sy0][sx1] * ax1) * ay0 + (src[sy1][sx0] * ax0 + src[sy1][sx1] * ax1) * ay1, float coefficients from the host's tables
 //   * gradient: ll_angle :538-585; the level-line angle is kept as what ll_angle computes it from: cv::fastAtan2's FLOAT DEGREES (NOTDEF_DEG where
 //     undefined).  The map value of the reference is that float times DEG_TO_RADS in double (:566), which every reader forms itself.
-// Also counts the defined pixels of each (frame, row, strip): seg_cnt[(frame * h + y) * strips + strip].  scaled: the scaled frames, written only when
+// Also counts the defined pixels of each (frame, row, strip): seg_cnt[(frame * h + y) * seg_stride + strip], the row's strips padded to a multiple of
+// EMIT_STRIPS by entries that stay zero, so that the scan reads the counts of one lsd_emit segment as one int4.  scaled: the scaled frames, written only when
 // asked for (the host region stage's batches, whose maps cs_lsd_get_maps returns).
-constexpr int LSD_ROWS = 64, LSD_SPAN = 128;
+constexpr int LSD_ROWS = 64, LSD_COLS = 48, LSD_SPAN = 64;
+constexpr int EMIT_STRIPS = 4, EMIT_COLS = EMIT_STRIPS * LSD_COLS, EMIT_ROWS = 4; // lsd_emit: a workgroup's share is 192 columns (four strips of lsd_maps) of four rows
 struct MapTabs { const int *xofs, *yofs; const float *ax, *ay; };
-__device__ __forceinline__ double strip_col(double s0, double s1, int p) { const double a = __shfl(s0, p & 63), b = __shfl(s1, p & 63); return p >= 64 ? b : a; } // blurred column p (0..127) of the strip
-__global__ void __launch_bounds__(64) lsd_maps(const uint8_t *gray, int W, int H, int w, int h, GK g, MapTabs T, double threshold, double *modgrad, float *angles, int *seg_cnt, double *scaled) {
-    const int strips = (w + 63) / 64;
-    const int strip = blockIdx.x % strips, d0 = strip * 64, y0 = (blockIdx.x / strips) * LSD_ROWS, lane = threadIdx.x;
+#define LSD_LDS_ORDER() asm volatile("" ::: "memory")
+__global__ void __launch_bounds__(64) lsd_maps(const uint8_t *gray, int W, int H, int w, int h, GK g, MapTabs T, double threshold, double *modgrad, float *angles, int *seg_cnt, int seg_stride, double *scaled) {
+    const int strips = (w + LSD_COLS - 1) / LSD_COLS;
+    const int strip = blockIdx.x % strips, d0 = strip * LSD_COLS, y0 = (blockIdx.x / strips) * LSD_ROWS, lane = threadIdx.x;
     if (y0 >= h) return;
     const int dy_last = min(y0 + LSD_ROWS, h - 1); // scaled rows y0 .. dy_last: gradient rows y0 .. dy_last - 1
-    auto sy1_of = [&](int dy) { return min(T.yofs[dy] + 1, H - 1); };
-    const int b0 = T.xofs[d0], r_first = T.yofs[y0], r_last = sy1_of(dy_last); // blurred columns b0 + 0..127, blurred rows r_first .. r_last
-    const int dx = d0 + lane, dxc = min(dx, w - 1), de = min(d0 + 64, w - 1); // this lane's scaled column; the one right of the strip
-    const int p0 = T.xofs[dxc] - b0, p1 = min(T.xofs[dxc] + 1, W - 1) - b0, pe0 = T.xofs[de] - b0, pe1 = min(T.xofs[de] + 1, W - 1) - b0;
-    const double ax0 = T.ax[2 * dxc], ax1 = T.ax[2 * dxc + 1], ae0 = T.ax[2 * de], ae1 = T.ax[2 * de + 1];
-    __shared__ uint8_t line[LSD_SPAN + 8]; // gray column reflect101(b0 - 3 + i) at byte i
+    // the row tables of scaled row y0 + lane (row y0 + 64, the next block's first, apart): upper tap row, lower tap row, coefficients
+    const int ty = min(y0 + lane, h - 1), ty64 = min(y0 + 64, h - 1);
+    const int t_yofs = T.yofs[ty], t_ay0 = __float_as_int(T.ay[2 * ty]), t_ay1 = __float_as_int(T.ay[2 * ty + 1]);
+    const int e_yofs = T.yofs[ty64], e_ay0 = __float_as_int(T.ay[2 * ty64]), e_ay1 = __float_as_int(T.ay[2 * ty64 + 1]);
+    auto tab = [&](int v, int e, int dy) { return dy - y0 < 64 ? __builtin_amdgcn_readlane(v, dy - y0) : e; }; // (dy is uniform)
+    const int b0 = T.xofs[d0], r_first = __builtin_amdgcn_readfirstlane(t_yofs), r_last = min(tab(t_yofs, e_yofs, dy_last) + 1, H - 1); // blurred columns b0 + 0..63, blurred rows r_first .. r_last
+    const int dx = d0 + lane, dxc = min(dx, w - 1); // this lane's scaled column; lane 48 has the one right of the strip (clamped like the reference's last column)
+    const bool mine = lane < LSD_COLS && dx < w;
+    const int p0 = (T.xofs[dxc] - b0) & (LSD_SPAN - 1), p1 = (min(T.xofs[dxc] + 1, W - 1) - b0) & (LSD_SPAN - 1); // (the lanes behind 48 have no column: their taps are kept inside the ring and never used)
+    const float fx0 = T.ax[2 * dxc], fx1 = T.ax[2 * dxc + 1];
+    __shared__ double line[LSD_SPAN + 8];   // gray column reflect101(b0 - 3 + i) at entry i, as a double
+    __shared__ double ring[2][LSD_SPAN];    // blurred rows r (at r & 1) and r - 1
+    __shared__ double srow[2][LSD_SPAN + 1]; // scaled rows dy (at dy & 1) and dy - 1: the strip's columns and, from lane 48, the one right of it
     const uint8_t *img = gray + (long)blockIdx.z * W * H;
-    const int c0 = reflect101d(b0 - 3 + lane, W), c1 = reflect101d(b0 + 61 + lane, W), c2 = reflect101d(b0 + 125 + min(lane, 5), W); // bytes lane, 64 + lane, 128 + lane (lanes 0..5)
+    const int c0 = reflect101d(b0 - 3 + lane, W), c1 = reflect101d(b0 + 61 + min(lane, 5), W); // entries lane and 64 + lane (lanes 0..5)
     const long frame_px = (long)blockIdx.z * h;
-    double ra[7] = {0, 0, 0, 0, 0, 0, 0}, rb[7] = {0, 0, 0, 0, 0, 0, 0}; // horizontal results of the last seven gray rows, columns j / 64 + j
-    double pa = 0, pb = 0, qa = 0, qb = 0; // blurred rows r - 1 and r
-    double sp = 0, spn = 0;                // scaled row dy - 1 at this lane's column and the next one
-    int dy = y0;
+    double hr[7] = {0, 0, 0, 0, 0, 0, 0}; // horizontal results of the last seven gray rows of this lane's column: row k at hr[k % 7]
+    int dy = y0, sy1 = min(r_first + 1, H - 1); // the next scaled row and its lower tap row
     auto grad_row = [&](int y, double top, double top_r, double bot, double bot_r) { // ll_angle of row y (< h - 1) from scaled rows y and y + 1
         bool def = false;
-        if (dx < w) {
+        if (mine) {
             const long o = (frame_px + y) * w + dx;
             if (dx >= w - 1) { modgrad[o] = 0; angles[o] = NOTDEF_DEG; } // right boundary undefined (:553-554)
             else {
@@ -87,76 +101,77 @@ __global__ void __launch_bounds__(64) lsd_maps(const uint8_t *gray, int W, int H
             }
         }
         const unsigned long long m = __ballot(def);
-        if (lane == 0) seg_cnt[(frame_px + y) * strips + strip] = __popcll(m);
+        if (lane == 0) seg_cnt[(frame_px + y) * seg_stride + strip] = __popcll(m);
     };
-    auto row = [&](int k, uint8_t a, uint8_t b, uint8_t c) { // gray row r_first - 3 + k
-        line[lane] = a; line[64 + lane] = b;
-        if (lane < 6) line[128 + lane] = c;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        double xa[7], xb[7];
+    constexpr int G = 7; // the row loop is unrolled by the filter's length: the unrolled position u of a row is k % 7, its slot in hr
+    auto row = [&](int k, int u, uint8_t a, uint8_t c) { // gray row r_first - 3 + k
+        LSD_LDS_ORDER();
+        line[lane] = (double)a;
+        if (lane < 6) line[64 + lane] = (double)c;
+        LSD_LDS_ORDER();
+        double x[7];
 #pragma unroll
-        for (int t = 0; t < 7; t++) { xa[t] = (double)line[lane + t]; xb[t] = (double)line[64 + lane + t]; } // columns -3 .. +3
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        double ha = g.k[KH] * xa[3], hb = g.k[KH] * xb[3];
+        for (int t = 0; t < 7; t++) x[t] = line[lane + t]; // columns -3 .. +3
+        LSD_LDS_ORDER();
+        double hv = g.k[KH] * x[3];
 #pragma unroll
-        for (int t = 1; t <= KH; t++) { ha += g.k[KH + t] * (xa[3 - t] + xa[3 + t]); hb += g.k[KH + t] * (xb[3 - t] + xb[3 + t]); }
-#pragma unroll
-        for (int t = 0; t < 6; t++) { ra[t] = ra[t + 1]; rb[t] = rb[t + 1]; }
-        ra[6] = ha; rb[6] = hb;
+        for (int t = 1; t <= KH; t++) hv += g.k[KH + t] * (x[3 - t] + x[3 + t]);
+        hr[u] = hv;
         if (k < 6) return;
-        const int r = r_first + k - 6;
-        double va = g.k[KH] * ra[3], vb = g.k[KH] * rb[3];
+        const int r = r_first + k - 6; // the blurred row whose seven gray rows are in: k - 6 .. k, the centre at hr[(u + 4) % 7]
+        double v = g.k[KH] * hr[(u + 4) % 7];
 #pragma unroll
-        for (int t = 1; t <= KH; t++) { va += g.k[KH + t] * (ra[3 - t] + ra[3 + t]); vb += g.k[KH + t] * (rb[3 - t] + rb[3 + t]); }
-        pa = qa; pb = qb; qa = va; qb = vb;
-        while (dy <= dy_last && sy1_of(dy) == r) { // the scaled rows whose lower tap row is r (sy1 never decreases; its upper tap row is r - 1, or r at the bottom clamp)
-            const bool same = T.yofs[dy] == r;
-            const double ua = same ? qa : pa, ub = same ? qb : pb, ay0 = T.ay[2 * dy], ay1 = T.ay[2 * dy + 1];
-            auto resize = [&](int q0, int q1, double w0, double w1) {
-                const double r0 = strip_col(ua, ub, q0) * w0 + strip_col(ua, ub, q1) * w1;
-                const double r1 = strip_col(qa, qb, q0) * w0 + strip_col(qa, qb, q1) * w1;
-                return r0 * ay0 + r1 * ay1;
-            };
-            const double s = resize(p0, p1, ax0, ax1), se = resize(pe0, pe1, ae0, ae1);
-            const double sr = __shfl(s, (lane + 1) & 63), sn = lane == 63 ? se : sr; // (the lane read outside the select: a lane left out of it would read as 0)
-            if (scaled && dx < w && dy < y0 + LSD_ROWS) scaled[(frame_px + dy) * w + dx] = s; // (row y0 + LSD_ROWS is the next block's)
-            if (dy > y0) grad_row(dy - 1, sp, spn, s, sn);
-            sp = s; spn = sn; dy++;
+        for (int t = 1; t <= KH; t++) v += g.k[KH + t] * (hr[(u + 4 - t + 7) % 7] + hr[(u + 4 + t) % 7]);
+        ring[r & 1][lane] = v;
+        LSD_LDS_ORDER();
+        while (dy <= dy_last && sy1 == r) { // the scaled rows whose lower tap row is r (sy1 never decreases; its upper tap row is r - 1, or r at the bottom clamp)
+            const int up = tab(t_yofs, e_yofs, dy) & 1;
+            const double ay0 = __int_as_float(tab(t_ay0, e_ay0, dy)), ay1 = __int_as_float(tab(t_ay1, e_ay1, dy)), ax0 = fx0, ax1 = fx1;
+            const double r0 = ring[up][p0] * ax0 + ring[up][p1] * ax1;
+            const double r1 = ring[r & 1][p0] * ax0 + ring[r & 1][p1] * ax1;
+            const double s = r0 * ay0 + r1 * ay1;
+            srow[dy & 1][lane] = s;
+            LSD_LDS_ORDER();
+            if (scaled && mine && dy < y0 + LSD_ROWS) scaled[(frame_px + dy) * w + dx] = s; // (row y0 + LSD_ROWS is the next block's)
+            if (dy > y0) grad_row(dy - 1, srow[(dy - 1) & 1][lane], srow[(dy - 1) & 1][lane + 1], s, srow[dy & 1][lane + 1]);
+            LSD_LDS_ORDER();
+            dy++;
+            sy1 = dy <= dy_last ? min(tab(t_yofs, e_yofs, dy) + 1, H - 1) : -1;
         }
+        LSD_LDS_ORDER();
     };
-    constexpr int G = 8;
     const int total = r_last - r_first + 7; // gray rows r_first - 3 .. r_last + 3
-    uint8_t ca[G], cb[G], cc[G], na[G], nb[G], nc[G];
-    auto fetch = [&](int k0, uint8_t (&a)[G], uint8_t (&b)[G], uint8_t (&c)[G]) {
-#pragma unroll
-        for (int u = 0; u < G; u++) {
-            a[u] = 0; b[u] = 0; c[u] = 0;
-            if (k0 + u < total) {
-                const uint8_t *src = img + (long)reflect101d(r_first - 3 + k0 + u, H) * W;
-                a[u] = src[c0]; b[u] = src[c1];
-                if (lane < 6) c[u] = src[c2];
-            }
+    constexpr int AHEAD = 5; // gray rows in flight: a row's pair of bytes is loaded into the slot that the row used five rows earlier has just left
+    uint8_t ca[G], cc[G];
+    auto fetch = [&](int k, uint8_t &a, uint8_t &c) {
+        a = 0; c = 0;
+        if (k < total) {
+            const uint8_t *src = img + (long)reflect101d(r_first - 3 + k, H) * W;
+            a = src[c0];
+            if (lane < 6) c = src[c1];
         }
     };
-    fetch(0, ca, cb, cc);
+#pragma unroll
+    for (int u = 0; u < AHEAD; u++) fetch(u, ca[u], cc[u]);
     for (int k0 = 0; k0 < total; k0 += G) {
-        fetch(k0 + G, na, nb, nc);
 #pragma unroll
         for (int u = 0; u < G; u++)
-            if (k0 + u < total) row(k0 + u, ca[u], cb[u], cc[u]);
-#pragma unroll
-        for (int u = 0; u < G; u++) { ca[u] = na[u]; cb[u] = nb[u]; cc[u] = nc[u]; }
+            if (k0 + u < total) { fetch(k0 + u + AHEAD, ca[(u + AHEAD) % G], cc[(u + AHEAD) % G]); row(k0 + u, u, ca[u], cc[u]); }
     }
     if (dy_last == h - 1 && y0 + LSD_ROWS >= h) { // the bottom row: undefined (:553-554)
-        if (dx < w) { const long o = (frame_px + h - 1) * w + dx; modgrad[o] = 0; angles[o] = NOTDEF_DEG; }
-        if (lane == 0) seg_cnt[(frame_px + h - 1) * strips + strip] = 0;
+        if (mine) { const long o = (frame_px + h - 1) * w + dx; modgrad[o] = 0; angles[o] = NOTDEF_DEG; }
+        if (lane == 0) seg_cnt[(frame_px + h - 1) * seg_stride + strip] = 0;
     }
 }
-// exclusive scan of n ints (out has n + 1 entries, out[n] = total) in three coalesced passes: 1024-element blocks, their totals, add
-__global__ void __launch_bounds__(1024) lsd_scan_blocks(const int *in, int n, int *out, int *block_tot) {
+// exclusive scan of the defined pixels per lsd_emit segment -- n sums of EMIT_STRIPS strip counts each; out has n + 1 entries, out[n] = total -- in two
+// coalesced passes: 1024-element blocks and their totals; then every block adds the sum of the totals in front of it (about a thousand ints, read by
+// every block from the cache), and the last block leaves the grand total
+static_assert(EMIT_STRIPS == 4, "lsd_scan_blocks reads a segment's strip counts as one int4");
+__global__ void __launch_bounds__(1024) lsd_scan_blocks(const int4 *in, int n, int *out, int *block_tot) {
     __shared__ int ws[16];
     const int i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int v = i < n ? in[i] : 0;
+    int v = 0;
+    if (i < n) { const int4 q = in[i]; v = q.x + q.y + q.z + q.w; }
     int sc = v;
     for (int d = 1; d < 64; d <<= 1) { int t = __shfl_up(sc, d); if (lane >= d) sc += t; }
     if (lane == 63) ws[wave] = sc;
@@ -166,30 +181,18 @@ __global__ void __launch_bounds__(1024) lsd_scan_blocks(const int *in, int n, in
     if (i < n) out[i] = base + sc - v;
     if (threadIdx.x == 1023) block_tot[blockIdx.x] = base + sc;
 }
-__global__ void __launch_bounds__(1024) lsd_scan_top(int *block_tot, int nblk, int *total_out) { // in place: exclusive scan of the block totals (nblk <= 1024 per pass chunk)
+__global__ void __launch_bounds__(1024) lsd_scan_add(int *out, int n, const int *block_tot) {
     __shared__ int ws[16];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
+    int part = 0;
+    for (int k = threadIdx.x; k < (int)blockIdx.x; k += 1024) part += block_tot[k];
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = part;
     __syncthreads();
-    for (int b0 = 0; b0 < nblk; b0 += 1024) {
-        const int i = b0 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int v = i < nblk ? block_tot[i] : 0;
-        int sc = v;
-        for (int d = 1; d < 64; d <<= 1) { int t = __shfl_up(sc, d); if (lane >= d) sc += t; }
-        if (lane == 63) ws[wave] = sc;
-        __syncthreads();
-        int base = carry;
-        for (int k = 0; k < wave; k++) base += ws[k];
-        if (i < nblk) block_tot[i] = base + sc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = base + sc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-__global__ void __launch_bounds__(1024) lsd_scan_add(int *out, int n, const int *block_base) {
+    int base = 0;
+    for (int k = 0; k < 16; k++) base += ws[k];
     const int i = blockIdx.x * 1024 + threadIdx.x;
-    if (i < n) out[i] += block_base[blockIdx.x];
+    if (i < n) out[i] += base;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = base + block_tot[blockIdx.x];
 }
 // ordered compaction of the defined pixels (address order inside a frame): address, level-line angle, gradient norm
 // c_deg: the angle as cv::fastAtan2 returned it (float degrees; the level-line angle is exactly double(c_deg) * DEG_TO_RADS, lsd.cpp:566), c_cs: cos / sin
@@ -197,63 +200,92 @@ __global__ void __launch_bounds__(1024) lsd_scan_add(int *out, int n, const int 
 // PIX (the device region stage one wave per frame, lsd_rg_seq): the kernel also leaves that stage's 16-byte record of EVERY pixel of its segment -- (angle while free, cos, sin, angle)
 // for a defined pixel, (NOTDEF, 0, 0, NOTDEF) for the others -- and the seeds' cos / sin (of the angle as a double, region_grow's start values :651-652) in place of the pixels'
 // own: what lsd_rg_fill + lsd_rg_scatter did in two more passes over the frame, from lists this kernel had just written (c_deg is not written then).
-template <bool PIX> __global__ void __launch_bounds__(256) lsd_emit(const double *modgrad, const float *angles, int w, int h, const int *seg_base, int *c_addr, float *c_deg, float2 *c_cs, double *c_mod, float *fre /* PIX: the region walk's own copy of the angle map, a float per pixel */) {
-    __shared__ int wc[4];
-    __shared__ short s_x[256];
-    __shared__ float s_a[256];
-    const int y = blockIdx.y;
-    const long row = ((long)blockIdx.z * h + y) * w;
-    {   // phase 1, a lane per pixel: which pixels of the segment are defined; they are packed (in address order) into the workgroup's list, so that the
-        // expensive part below -- an IEEE division, eight double alignment tests, the double-precision polynomial of glibc's cosf / sinf -- runs on full
-        // waves of defined pixels only (37 % of the pixels of a textured frame)
-        const int x = blockIdx.x * 256 + threadIdx.x;
-        float a = NOTDEF_DEG;
-        if (x < w) a = angles[row + x];
-        const bool def = a != NOTDEF_DEG;
-        const unsigned long long m = __ballot(def);
-        const int wv = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) wc[wv] = __popcll(m);
-        if (PIX && x < w) fre[row + x] = a;
-        __syncthreads();
-        if (def) {
-            int r = __popcll(m & ((1ull << (threadIdx.x & 63)) - 1));
-            for (int i = 0; i < wv; i++) r += wc[i];
-            s_x[r] = (short)x; s_a[r] = a;
-        }
-        __syncthreads();
+// A workgroup of three waves takes EMIT_COLS columns (four strips of lsd_maps: one seg_base entry per row) of EMIT_ROWS rows:
+//   0  the angles of its rows, the rows above and below and a column on either side go to LDS (NOTDEF_DEG outside the frame): the alignment tests read them there;
+//   1  a lane per column: which pixels are defined; they are packed, row after row in address order, into the workgroup's list;
+//   2  full waves of defined pixels: the eight alignment tests, the address with its flag; PIX: the pixels that are not alone are packed a second time,
+//   3  PIX: so that the double-precision cos / sin run on full waves of the pixels that need them (half the defined pixels of a textured frame are alone).
+template <bool PIX> __global__ void __launch_bounds__(EMIT_COLS) lsd_emit(const double *modgrad, const float *angles, int w, int h, const int *seg_base, int *c_addr, float *c_deg, float2 *c_cs, double *c_mod, float *fre /* PIX: the region walk's own copy of the angle map, a float per pixel */) {
+    constexpr int NW = EMIT_COLS / 64, LW = EMIT_COLS + 2;
+    __shared__ float s_ang[(EMIT_ROWS + 2) * LW];
+    __shared__ int s_list[EMIT_ROWS * EMIT_COLS], s_need[PIX ? EMIT_ROWS * EMIT_COLS : 1]; // defined pixels: column | row << 8 | rank in its row << 10; PIX: the list entries that are not alone
+    __shared__ int wc[EMIT_ROWS][NW], s_base[EMIT_ROWS], n_need;
+    const int tid = threadIdx.x, x0 = blockIdx.x * EMIT_COLS, y0 = blockIdx.y * EMIT_ROWS;
+    const long frame_row = (long)blockIdx.z * h;
+    for (int i = tid; i < (EMIT_ROWS + 2) * LW; i += EMIT_COLS) {
+        const int yy = y0 - 1 + i / LW, xx = x0 - 1 + i % LW;
+        s_ang[i] = xx >= 0 && xx < w && yy >= 0 && yy < h ? angles[(frame_row + yy) * w + xx] : NOTDEF_DEG;
     }
-    const int n_def = wc[0] + wc[1] + wc[2] + wc[3];
-    if ((int)threadIdx.x >= n_def) return;
-    const int x = s_x[threadIdx.x];
-    const float d = s_a[threadIdx.x];
-    const double a = double(d) * DEG_TO_RADS; // the map value (:566)
-    const long o = row + x;
-    const int pos = seg_base[((long)blockIdx.z * h + y) * ((w + 63) / 64) + blockIdx.x * 4] + threadIdx.x; // (the counts are per 64-column strip of lsd_maps: this segment's first of four)
-    // bit 31 of the address: no neighbour is aligned with this pixel's own angle (angles never change), so as a seed it stays alone -- region_grow's
-    // first nine tests use exactly that angle -- and the host marks it used without testing anything (12 k of 25 k seeds on a textured frame are single)
-    bool alone = true;
+    if (tid < EMIT_ROWS && y0 + tid < h) s_base[tid] = seg_base[(frame_row + y0 + tid) * gridDim.x + blockIdx.x];
+    if (tid == 0) n_need = 0;
+    __syncthreads();
+    const int wv = tid >> 6, ln = tid & 63;
+    unsigned long long m[EMIT_ROWS];
+#pragma unroll
+    for (int r = 0; r < EMIT_ROWS; r++) {
+        const float a = s_ang[(r + 1) * LW + tid + 1];
+        m[r] = __ballot(a != NOTDEF_DEG);
+        if (ln == 0) wc[r][wv] = __popcll(m[r]);
+        if (PIX && x0 + tid < w && y0 + r < h) fre[(frame_row + y0 + r) * w + x0 + tid] = a;
+    }
+    __syncthreads();
+    int n_def = 0;
+#pragma unroll
+    for (int r = 0; r < EMIT_ROWS; r++) {
+        int rank = __popcll(m[r] & ((1ull << ln) - 1)), cnt = 0;
+        for (int i = 0; i < NW; i++) { if (i < wv) rank += wc[r][i]; cnt += wc[r][i]; }
+        if ((m[r] >> ln) & 1) s_list[n_def + rank] = tid | r << 8 | rank << 10;
+        n_def += cnt;
+    }
+    __syncthreads();
     const double prec = PI_ * 22.5 / 180;
-    for (int dy = -1; dy <= 1; dy++)
-        for (int dx = -1; dx <= 1; dx++) {
-            const int xx = x + dx, yy = y + dy;
-            if ((dx == 0 && dy == 0) || xx < 0 || yy < 0 || xx >= w || yy >= h) continue;
-            const float bd = angles[((long)blockIdx.z * h + yy) * w + xx];
-            if (bd == NOTDEF_DEG) continue;
-            const double b = double(bd) * DEG_TO_RADS;
-            double n_theta = a - b; // isAligned(neighbour, a, prec) :1138-1154
-            if (n_theta < 0) n_theta = -n_theta;
-            if (n_theta > (3 * PI_) / 2) { n_theta -= 2 * PI_; if (n_theta < 0) n_theta = -n_theta; }
-            if (n_theta <= prec) alone = false;
+    for (int i0 = 0; i0 < n_def; i0 += EMIT_COLS) { // (whole waves stay in the loop: the second packing votes)
+        const int i = i0 + tid;
+        const bool on = i < n_def;
+        const int e = on ? s_list[i] : 0, c = e & 255, r = (e >> 8) & 3, pos = s_base[r] + (e >> 10), x = x0 + c, y = y0 + r;
+        const float *ctr = s_ang + (r + 1) * LW + c + 1;
+        const float d = *ctr;
+        const double a = double(d) * DEG_TO_RADS; // the map value (:566)
+        // bit 31 of the address: no neighbour is aligned with this pixel's own angle (angles never change), so as a seed it stays alone -- region_grow's
+        // first nine tests use exactly that angle -- and the host marks it used without testing anything (12 k of 25 k seeds on a textured frame are single)
+        bool alone = true;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                if (dx == 0 && dy == 0) continue;
+                const float bd = ctr[dy * LW + dx];
+                if (bd == NOTDEF_DEG) continue; // (undefined, or outside the frame)
+                const double b = double(bd) * DEG_TO_RADS;
+                double n_theta = a - b; // isAligned(neighbour, a, prec) :1138-1154
+                if (n_theta < 0) n_theta = -n_theta;
+                if (n_theta > (3 * PI_) / 2) { n_theta -= 2 * PI_; if (n_theta < 0) n_theta = -n_theta; }
+                if (n_theta <= prec) alone = false;
+            }
+        if (on) c_addr[pos] = (y * w + x) | (alone ? (int)0x80000000 : 0);
+        if (PIX) { // (the device walk computes cos / sin of float(angle) at its window fetches; a seed starts its sums with cos / sin of the angle as a double :651-652)
+            // a seed flagged alone never starts a sum (lsd_rg_seq marks it used without growing): no double cos / sin for it
+            if (on && alone) c_cs[pos] = make_float2(0.f, 0.f);
+            const unsigned long long need = __ballot(on && !alone);
+            int at = 0;
+            if (ln == 0 && need) at = atomicAdd(&n_need, __popcll(need));
+            at = __shfl(at, 0);
+            if (on && !alone) s_need[at + __popcll(need & ((1ull << ln) - 1))] = e;
+        } else if (on) {
+            const float pc = glibc_sincosf::cosf_(float(a)), ps = glibc_sincosf::sinf_(float(a));
+            c_deg[pos] = d;
+            if (c_mod) c_mod[pos] = modgrad[(frame_row + y) * w + x]; // (the host stage's copy of the norms; the device stage reads the dense map)
+            c_cs[pos] = make_float2(pc, ps);
         }
-    c_addr[pos] = (y * w + x) | (alone ? (int)0x80000000 : 0);
-    if (PIX) { // (the device walk computes cos / sin of float(angle) at its window fetches; a seed starts its sums with cos / sin of the angle as a double :651-652)
-        // a seed flagged alone never starts a sum (lsd_rg_seq marks it used without growing): no double cos / sin for it, half the defined pixels of a textured frame
-        c_cs[pos] = alone ? make_float2(0.f, 0.f) : make_float2(float(cos(a)), float(sin(a)));
-    } else {
-        const float pc = glibc_sincosf::cosf_(float(a)), ps = glibc_sincosf::sinf_(float(a));
-        c_deg[pos] = d;
-        if (c_mod) c_mod[pos] = modgrad[o]; // (the host stage's copy of the norms; the device stage reads the dense map)
-        c_cs[pos] = make_float2(pc, ps);
+    }
+    if (PIX) {
+        __syncthreads();
+        const int nn = n_need;
+        for (int i = tid; i < nn; i += EMIT_COLS) {
+            const int e = s_need[i], c = e & 255, r = (e >> 8) & 3;
+            const double a = double(s_ang[(r + 1) * LW + c + 1]) * DEG_TO_RADS;
+            c_cs[s_base[r] + (e >> 10)] = make_float2(float(cos(a)), float(sin(a)));
+        }
     }
 }
 
@@ -593,8 +625,8 @@ struct cs_lsd {
     size_t pix_bytes = 0; bool scaled_kept = true;           // the arena d_tmp = [(unused) | d_scaled] while lsd_maps runs, later [region stage's pixel records (pix_bytes) | LBD blur]
     uint8_t *d_gray = nullptr; double *d_tmp = nullptr, *d_scaled = nullptr, *d_mod = nullptr; float *d_ang = nullptr; // d_ang: float degrees (see lsd_maps)
     int *d_xofs = nullptr, *d_yofs = nullptr; float *d_ax = nullptr, *d_ay = nullptr;
-    int nbx = 0, nsx = 0;                                   // 256-pixel segments (lsd_emit) / 64-pixel strips (lsd_maps) per scaled row
-    int *d_seg_cnt = nullptr, *d_seg_base = nullptr;        // per (frame, row, strip) defined-pixel count / exclusive scan
+    int nbx = 0, nsx = 0;                                   // 192-pixel segments (lsd_emit) / 48-pixel strips (lsd_maps) per scaled row
+    int *d_seg_cnt = nullptr, *d_seg_base = nullptr;        // defined pixels per (frame, row, strip), the strips padded to whole segments / their exclusive scan per (frame, row, segment)
     int *d_blk_tot = nullptr;                               // totals of the 1024-segment scan blocks
     int *d_caddr = nullptr; float *d_cdeg = nullptr; float2 *d_ccs = nullptr; double *d_cmod = nullptr; size_t ccap = 0;   // compacted defined pixels (device): address, angle, cos / sin, norm
     int *h_caddr = nullptr; float *h_cdeg = nullptr; float2 *h_ccs = nullptr; double *h_cmod = nullptr; size_t hcap = 0;   // same, pinned host
@@ -653,17 +685,16 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     l->scaled_kept = !device_mode;
     // The scaled frames (doubles, 1.6 MB per frame) are the second part of an arena (d_tmp) that the device region stage takes over for its pixel records once
     // lsd_maps is through, and the LBD blur for its one-kernel life (see below); a device-stage batch does not write them at all.
-    const int nbx = l->nbx, nsx = l->nsx, n_seg = F * h * nsx;
+    const int nbx = l->nbx, nsx = l->nsx, n_seg = F * h * nbx; // (one scan entry per row and lsd_emit segment)
     // (timed as "lsd_gradient": the stage that leaves the gradient maps, once per pass -- the blur and the resize in front of it have no launch of their own)
     CS_LAUNCH(ctx, "lsd_gradient", lsd_maps, dim3(nsx * ((h + LSD_ROWS - 1) / LSD_ROWS), 1, F), dim3(64), 0, l->d_gray, W, H, w, h, l->gk, (MapTabs{l->d_xofs, l->d_yofs, l->d_ax, l->d_ay}), l->threshold,
-              l->d_mod, l->d_ang, l->d_seg_cnt, device_mode ? (double *)nullptr : l->d_scaled);
+              l->d_mod, l->d_ang, l->d_seg_cnt, nbx * EMIT_STRIPS, device_mode ? (double *)nullptr : l->d_scaled);
     const int nblk = (n_seg + 1023) / 1024;
-    CS_LAUNCH(ctx, "lsd_scan", lsd_scan_blocks, dim3(nblk), dim3(1024), 0, l->d_seg_cnt, n_seg, l->d_seg_base, l->d_blk_tot);
-    CS_LAUNCH(ctx, "lsd_scan", lsd_scan_top, dim3(1), dim3(1024), 0, l->d_blk_tot, nblk, l->d_seg_base + n_seg);
+    CS_LAUNCH(ctx, "lsd_scan", lsd_scan_blocks, dim3(nblk), dim3(1024), 0, reinterpret_cast<const int4 *>(l->d_seg_cnt), n_seg, l->d_seg_base, l->d_blk_tot);
     CS_LAUNCH(ctx, "lsd_scan", lsd_scan_add, dim3(nblk), dim3(1024), 0, l->d_seg_base, n_seg, l->d_blk_tot);
     // only the defined pixels (gradient above rho) go to the host: frame bases first, then the compacted (address, angle, norm) lists
     l->frame_base.assign((size_t)F + 1, 0);
-    CS_HIP(ctx, hipMemcpy2DAsync(l->frame_base.data(), sizeof(int), l->d_seg_base, sizeof(int) * (size_t)h * nsx, sizeof(int), (size_t)F + 1, hipMemcpyDeviceToHost, ctx->stream));
+    CS_HIP(ctx, hipMemcpy2DAsync(l->frame_base.data(), sizeof(int), l->d_seg_base, sizeof(int) * (size_t)h * nbx, sizeof(int), (size_t)F + 1, hipMemcpyDeviceToHost, ctx->stream));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t total = (size_t)l->frame_base[F];
     int r;
@@ -685,9 +716,9 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     auto emit = [&](bool with_norms) -> int { // the compacted norms (8 B per defined pixel) are the host stage's: the device stage reads the dense map
         if (with_norms && !l->d_cmod) { const int q = cs_dalloc(ctx, &l->d_cmod, l->ccap); if (q) return q; }
         if (pix_by_emit && !with_norms)
-            CS_LAUNCH(ctx, "lsd_emit", lsd_emit<true>, dim3(nbx, h, F), dim3(256), 0, l->d_mod, l->d_ang, w, h, l->d_seg_base, l->d_caddr, l->d_cdeg, l->d_ccs, (double *)nullptr, reinterpret_cast<float *>(l->d_tmp));
+            CS_LAUNCH(ctx, "lsd_emit", lsd_emit<true>, dim3(nbx, (h + EMIT_ROWS - 1) / EMIT_ROWS, F), dim3(EMIT_COLS), 0, l->d_mod, l->d_ang, w, h, l->d_seg_base, l->d_caddr, l->d_cdeg, l->d_ccs, (double *)nullptr, reinterpret_cast<float *>(l->d_tmp));
         else
-            CS_LAUNCH(ctx, "lsd_emit", lsd_emit<false>, dim3(nbx, h, F), dim3(256), 0, l->d_mod, l->d_ang, w, h, l->d_seg_base, l->d_caddr, l->d_cdeg, l->d_ccs, with_norms ? l->d_cmod : (double *)nullptr, (float *)nullptr);
+            CS_LAUNCH(ctx, "lsd_emit", lsd_emit<false>, dim3(nbx, (h + EMIT_ROWS - 1) / EMIT_ROWS, F), dim3(EMIT_COLS), 0, l->d_mod, l->d_ang, w, h, l->d_seg_base, l->d_caddr, l->d_cdeg, l->d_ccs, with_norms ? l->d_cmod : (double *)nullptr, (float *)nullptr);
         return CS_OK;
     };
     if (total > 0) { r = emit(!use_seq); if (r) return r; }
@@ -854,11 +885,13 @@ int cs_lsd_create(cs_ctx *ctx, int width, int height, int max_frames, cs_lsd **o
     A_(cs_dalloc(ctx, &l->d_gray, N)); A_(cs_dalloc(ctx, &l->d_tmp, N + n)); l->d_scaled = l->d_tmp + N;
     A_(cs_dalloc(ctx, &l->d_mod, n)); A_(cs_dalloc(ctx, &l->d_ang, n));
     A_(cs_dalloc(ctx, &l->d_xofs, xofs.size())); A_(cs_dalloc(ctx, &l->d_yofs, yofs.size())); A_(cs_dalloc(ctx, &l->d_ax, ax.size())); A_(cs_dalloc(ctx, &l->d_ay, ay.size()));
-    l->nbx = (l->w + 255) / 256; l->nsx = (l->w + 63) / 64;
-    for (int d0 = 0; d0 < l->w; d0 += 64) // lsd_maps: a strip's resize taps stay inside its 128 blurred columns (83 at scale 0.8)
-        if (std::min(xofs[std::min(d0 + 64, l->w - 1)] + 1, width - 1) - xofs[d0] >= LSD_SPAN) { cs_lsd_destroy(ctx, l); return CS_ERR_BAD_ARG; }
-    A_(cs_dalloc(ctx, &l->d_seg_cnt, (size_t)max_frames * l->h * l->nsx)); A_(cs_dalloc(ctx, &l->d_seg_base, (size_t)max_frames * l->h * l->nsx + 1));
-    A_(cs_dalloc(ctx, &l->d_blk_tot, ((size_t)max_frames * l->h * l->nsx + 1023) / 1024 + 1));
+    l->nsx = (l->w + LSD_COLS - 1) / LSD_COLS; l->nbx = (l->nsx + EMIT_STRIPS - 1) / EMIT_STRIPS;
+    for (int d0 = 0; d0 < l->w; d0 += LSD_COLS) // lsd_maps: a strip's resize taps, the column right of it included, stay inside its 64 blurred columns (62 at scale 0.8)
+        if (std::min(xofs[std::min(d0 + LSD_COLS, l->w - 1)] + 1, width - 1) - xofs[d0] >= LSD_SPAN) { cs_lsd_destroy(ctx, l); return CS_ERR_BAD_ARG; }
+    const size_t n_seg = (size_t)max_frames * l->h * l->nbx;
+    A_(cs_dalloc(ctx, &l->d_seg_cnt, n_seg * EMIT_STRIPS)); A_(cs_dalloc(ctx, &l->d_seg_base, n_seg + 1));
+    A_(cs_dalloc(ctx, &l->d_blk_tot, (n_seg + 1023) / 1024 + 1));
+    { hipError_t e = hipMemsetAsync(l->d_seg_cnt, 0, n_seg * EMIT_STRIPS * sizeof(int), ctx->stream); if (e != hipSuccess) { cs_lsd_destroy(ctx, l); return CS_ERR_HIP; } } // (the padding behind a row's last strip is never written)
     A_(cs_h2d(ctx, l->d_xofs, xofs.data(), xofs.size())); A_(cs_h2d(ctx, l->d_yofs, yofs.data(), yofs.size()));
     A_(cs_h2d(ctx, l->d_ax, ax.data(), ax.size())); A_(cs_h2d(ctx, l->d_ay, ay.data(), ay.size()));
 #undef A_

@@ -1,24 +1,29 @@
 // match.hip -- ORB_SLAM2::ORBmatcher Hamming searches on MI355X (gfx950).
 //
-// Replaces ORBmatcher::SearchByProjection (both overloads), SearchForInitialization, SearchByBoW (both overloads), SearchForTriangulation, Fuse's search and
-// DescriptorDistance (reference orb_object_slam/src/ORBmatcher.cc:50-142, :171-310, :429-542, :544-677, :679-850, :934-981, :1373-1522, :1905-1921) and the Frame grid
+// Replaces ORBmatcher::SearchByProjection (all four overloads), SearchForInitialization, SearchByBoW (both overloads), SearchForTriangulation, the search of both Fuse overloads,
+// SearchBySim3 and DescriptorDistance (reference orb_object_slam/src/ORBmatcher.cc:50-142, :171-310, :309-427, :429-542, :544-677, :679-850, :934-981, :1010-1139, :1141-1371,
+// :1373-1522, :1727-1858, :1905-1921) and the Frame grid
 // (src/Frame.cc:303-318, :404-459, :525-535, :546-609).
 //
 //   match_grid           counting sort of the keypoints into the 64x48 grid, per-cell lists in keypoint order; one workgroup per frame (one frame or a window's frames)
 //   match_undistort      Frame::UndistortKeyPoints: cv::undistortPoints with P = K, a thread per key point
 //   match_project        per last-frame map point: Rcw*x+tcw (cv::gemm: double accumulate, one rounding), pinhole projection,
 //                        window radius th*scale[octave]; one pose or one pose per pair of a window
+//   match_project_map<M> per map point of a Sim3 / relocalisation search (:309-427, :1010-1139, :1141-1371, :1727-1858) the whole preamble: transform, depth, image, distance and
+//                        viewing-angle tests, MapPoint::PredictScale (glibc's logf restated), radius -- the query and its level window, written where match_candidates reads them
 //   match_candidates     MC_G lanes per query: lane = grid cell of the window (ix outer, iy inner = the reference's candidate
 //                        order), level + |dx|<r,|dy|<r filters, ordered compaction by a prefix sum, 256-bit Hamming
 //                        distance as 4 x popcount(u64).  It counts, takes a slice of the candidate arena, fills it with (idx, dist).
 //   match_resolve<V>     the greedy claim / best-second / ratio / rotation-histogram logic of the reference, which is sequential over the queries (a candidate
 //                        claimed by an earlier query is skipped by later ones): one wave per search, 64 queries at a time, over the candidate lists
 //   match_fuse_best      Fuse: per map point the best key point after the chi-square tests
+//   match_map_best       Fuse(Scw) / SearchBySim3: per map point the first minimum of its candidate list; match_sim3_agree: SearchBySim3's agreement pass
 //   match_triangulation  SearchForTriangulation: one wave per key point of KF1 over the KF2 features of its vocabulary node
 //   match_orient_cut     the rotation cut of a search whose matches are independent of each other
 //   match_bow_dists      SearchByBoW: the distances of a feature to its node's features, as candidate lists for match_resolve
 //   match_knn2           all-pairs best / second best, train descriptors staged through LDS
 #include "common.h"
+#include "glibc_logf.h"
 
 #include <algorithm>
 #include <climits>
@@ -149,6 +154,74 @@ __global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const 
     q[i] = Q;
 }
 
+// The preamble of the searches that project map points through a Sim3 or a relocalisation pose, with the reference's float arithmetic statement by statement (a cv::Mat
+// product is one gemm per row: double accumulation over k ascending, one rounding; cv::norm and Mat::dot accumulate in double; 1 / z and 1.0 / z are a double division
+// rounded to float; everything else is float in the reference's association -- the library is built with -ffp-contract=off):
+//   PM_SIM3   SearchByProjection(pKF, Scw, ...) :346-382 and Fuse(pKF, Scw, ...) :1048-1085   p3Dc = Rcw p + tcw, z < 0, KeyFrame::IsInImage, dist = |p - Ow|, viewing angle
+//   PM_PAIR   SearchBySim3 :1198-1228 / :1281-1311   p1 = R1w p + t1w, p2 = sR21 p1 + t21 (two gemms, two roundings), z < 0, IsInImage, dist = |p2|
+//   PM_RELOC  SearchByProjection(CurrentFrame, pKF, sAlreadyFound, ...) :1755-1785   x3Dc = Rcw p + tcw, NO depth test, the Frame's bounds (both ends inclusive),
+//             u = fx * xc * invzc + cx (the other modes: fx * (X * invz) + cx), dist = |p - Ow|, window levels [L - 1, L + 1] (the other modes: [L - 1, L])
+// then MapPoint::PredictScale (MapPoint.cc:524-533) L = ceil(logf(mfMaxDistance / dist) / logScaleFactor) with glibc's logf, r = th * mvScaleFactors[L].
+// This fork's PredictScale does not clamp and 0.8 min <= dist <= 1.2 max allows L = -1, n_levels, n_levels + 1, where the reference reads past mvScaleFactors: such a point
+// (and one whose ratio is not a positive normal float) is an invalid query and is counted in *n_outside; the call goes on.
+enum { PM_SIM3 = 0, PM_PAIR = 1, PM_RELOC = 2 };
+struct MapP { float R[9], t[3], Ow[3], R2[9], t2[3]; float fx, fy, cx, cy, log_sf, th; int n_levels; };
+__device__ __forceinline__ void gemm3(const float *R, const float *p, const float *t, float *o) {
+    for (int r = 0; r < 3; r++) {
+        double sacc = 0;
+        for (int k = 0; k < 3; k++) sacc += (double)R[r * 3 + k] * (double)p[k];
+        o[r] = (float)(sacc * 1.0 + (double)t[r] * 1.0);
+    }
+}
+__device__ __forceinline__ float norm3(const float *v) { double s = 0; for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k]; return (float)sqrt(s); }
+template <int MODE> __global__ void __launch_bounds__(256) match_project_map(int n, const float *world_pos, const float *normal, const float *min_distance, const float *max_distance, const uint8_t *skip,
+                                                                             MapP P, const float *scale_factors, FrameP F, QueryS *q, int *level, int *n_outside) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    QueryS Q{0, 0, 0, 0, 0, 0, 0};
+    int L = -1;
+    do {
+        if (skip[i]) break;
+        const float p[3] = {world_pos[(size_t)i * 3], world_pos[(size_t)i * 3 + 1], world_pos[(size_t)i * 3 + 2]};
+        float pc[3];
+        gemm3(P.R, p, P.t, pc);
+        if (MODE == PM_PAIR) { float p2[3]; gemm3(P.R2, pc, P.t2, p2); pc[0] = p2[0]; pc[1] = p2[1]; pc[2] = p2[2]; }
+        float u, v;
+        if (MODE == PM_RELOC) {
+            const float xc = pc[0], yc = pc[1];
+            const float invzc = (float)(1.0 / (double)pc[2]);
+            u = P.fx * xc * invzc + P.cx;
+            v = P.fy * yc * invzc + P.cy;
+            if (u < F.minX || u > F.maxX) break;
+            if (v < F.minY || v > F.maxY) break;
+        } else {
+            if (pc[2] < 0.0f) break;
+            const float invz = (float)(1.0 / (double)pc[2]);
+            const float x = pc[0] * invz, y = pc[1] * invz;
+            u = P.fx * x + P.cx;
+            v = P.fy * y + P.cy;
+            if (!(u >= F.minX && u < F.maxX && v >= F.minY && v < F.maxY)) break; // KeyFrame::IsInImage (KeyFrame.cc:670-673)
+        }
+        const float maxDistance = 1.2f * max_distance[i], minDistance = 0.8f * min_distance[i]; // MapPoint::GetMax / GetMinDistanceInvariance (MapPoint.cc:512-522)
+        float PO[3] = {pc[0], pc[1], pc[2]}; // SearchBySim3 measures the camera-frame vector (:1218, :1301), the others p - Ow
+        if (MODE != PM_PAIR) for (int k = 0; k < 3; k++) PO[k] = p[k] - P.Ow[k];
+        const float dist = norm3(PO);
+        if (dist < minDistance || dist > maxDistance) break;
+        if (MODE == PM_SIM3) { // viewing angle below 60 degrees (:374-377, :1076-1079)
+            double dot = 0;
+            for (int k = 0; k < 3; k++) dot += (double)PO[k] * (double)normal[(size_t)i * 3 + k];
+            if (dot < 0.5 * (double)dist) break;
+        }
+        const float ratio = max_distance[i] / dist;
+        float lf = -1.0f;
+        if (glibc_logf::in_domain(ratio)) lf = ceilf(glibc_logf::logf_(ratio) / P.log_sf);
+        if (!(lf >= 0.0f && lf < (float)P.n_levels)) { atomicAdd(n_outside, 1); break; }
+        L = (int)lf;
+        Q.x = u; Q.y = v; Q.r = P.th * scale_factors[L]; Q.minLevel = L - 1; Q.maxLevel = MODE == PM_RELOC ? L + 1 : L; Q.valid = 1;
+    } while (0);
+    q[i] = Q; level[i] = L;
+}
+
 __device__ __forceinline__ int hamming256(const unsigned long long *a, unsigned long long b0, unsigned long long b1, unsigned long long b2,
                                           unsigned long long b3) {
     return __popcll(a[0] ^ b0) + __popcll(a[1] ^ b1) + __popcll(a[2] ^ b2) + __popcll(a[3] ^ b3);
@@ -247,7 +320,9 @@ __global__ void __launch_bounds__(256) match_candidates(FrameP F, const unsigned
 //   ~2 000 train key points touched).
 // Then the batch commits (the highest claiming lane of a key point owns it), records (claim, rotation bin) per query, and the next batch starts.  After the last batch:
 // the three-maxima cut over the histogram (:1860-1901) and the write-back.  Everything a query needs of a candidate (index, level, distance) is in the candidate list.
-enum { RV_PROJ = 0, RV_LOCAL = 1, RV_INIT = 2, RV_BOW = 3, RV_BOWKF = 4 };
+// RV_CLAIM: the loops of SearchByProjection(pKF, Scw, ...) (:392-423) and of the relocalisation search (:1792-1831) -- a key point that holds a map point, from before the call
+// (tblocked, which also carries !KeysStatic) or claimed by an earlier query, is skipped (RV_BOW's rule); first strict minimum; accepted at best <= accept_dist; no ratio test.
+enum { RV_PROJ = 0, RV_LOCAL = 1, RV_INIT = 2, RV_BOW = 3, RV_BOWKF = 4, RV_CLAIM = 5 };
 struct ResolveP {
     const long *cstart; const int *ccount; const int2 *cands; // per query
     const int *qlist;        // the visiting order (query index per step) or NULL: step = query index
@@ -263,6 +338,7 @@ struct ResolveP {
     int *q_match;            // RV_INIT, RV_BOWKF: per query, the matched train key point or -1
     int *q_rec;              // scratch, per query
     int *nmatches;           // per problem
+    int accept_dist;         // RV_CLAIM: TH_LOW (:419) or the caller's ORBdist (:1815)
 };
 constexpr int RS_NC = 8; // candidates of a query kept in registers over the rounds of its batch (the rest is re-read)
 
@@ -372,6 +448,7 @@ template <int V> __global__ void __launch_bounds__(64) match_resolve(ResolveP P)
             else if (V == RV_LOCAL) accept = best <= TH_HIGH && !(blev == blev2 && (float)best > P.nnratio * (float)best2);      // :126-131
             else if (V == RV_INIT) accept = best <= TH_LOW && (float)best < (float)best2 * P.nnratio;                            // :476-478
             else if (V == RV_BOW) accept = best <= TH_LOW && (float)best < P.nnratio * (float)best2;                             // :266-268
+            else if (V == RV_CLAIM) accept = best <= P.accept_dist;                                                              // :419, :1815
             else accept = best < TH_LOW && (float)best < P.nnratio * (float)best2;                                               // :625-627 (strict)
             const int nc = (accept && act && bidx >= 0) ? bidx : -1;
             const bool changed = nc != claim || (V == RV_INIT && nc >= 0 && best != cdist);
@@ -420,15 +497,15 @@ template <int V> __global__ void __launch_bounds__(64) match_resolve(ResolveP P)
         if (rec >= 0) {
             const int idx = rec & 0xffffff, bin = rec >> 24;
             const bool culled = cut && bin != ind1 && bin != ind2 && bin != ind3;
-            if (V == RV_PROJ || V == RV_LOCAL || V == RV_BOW) { if (culled) { owner[idx] = -1; n_cull++; } } // every claim of a cut bin clears the key point and counts (:1506-1512)
+            if (V == RV_PROJ || V == RV_LOCAL || V == RV_BOW || V == RV_CLAIM) { if (culled) { owner[idx] = -1; n_cull++; } } // every claim of a cut bin clears the key point and counts (:1506-1512)
             else if (owner[idx] == q - qsub && !culled) { res = idx; n_keep++; }                             // a displaced or cut query has no match (:487-491, :516-522)
         }
         if (V == RV_INIT || V == RV_BOWKF) P.q_match[q] = res;
     }
     __syncthreads();
     for (int off = 32; off > 0; off >>= 1) { n_cull += __shfl_xor(n_cull, off); n_keep += __shfl_xor(n_keep, off); }
-    if (V == RV_PROJ || V == RV_LOCAL || V == RV_BOW)
-        for (int i = lane; i < N2; i += 64) { const int o = owner[i]; P.train_match[out0 + i] = o >= 0 ? ((V == RV_BOW) ? o : (o >> 1)) : -1; }
+    if (V == RV_PROJ || V == RV_LOCAL || V == RV_BOW || V == RV_CLAIM)
+        for (int i = lane; i < N2; i += 64) { const int o = owner[i]; P.train_match[out0 + i] = o >= 0 ? ((V == RV_BOW || V == RV_CLAIM) ? o : (o >> 1)) : -1; }
     if (lane == 0) P.nmatches[p] = (V == RV_INIT || V == RV_BOWKF) ? n_keep : n_claims - n_cull;
 }
 
@@ -462,6 +539,33 @@ __global__ void __launch_bounds__(256) match_fuse_best(int n_mp, const long *cst
         }
     }
     best_idx[i] = bestIdx; best_dist[i] = bestDist;
+}
+
+// Fuse(pKF, Scw, ...) (:1096-1118) and both directions of SearchBySim3 (:1238-1266, :1321-1349): per map point the first strict minimum over its candidate list (the
+// window and the level filter are match_candidates'); a key point with tblocked set (!KeysStatic) is no candidate.  accept < 0: best_idx as found (-1 / INT_MAX: none);
+// otherwise best_idx = -1 unless best_dist <= accept.  A thread per map point.
+__global__ void __launch_bounds__(256) match_map_best(int n_mp, const long *cstart, const int *ccount, const int2 *cands, const uint8_t *tblocked, int accept, int *best_idx, int *best_dist) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    int bestDist = INT_MAX, bestIdx = -1;
+    const long b = cstart[i]; const int n = ccount[i];
+    for (int p = 0; p < n; p++) {
+        const int2 cd = cands[b + p];
+        const int idx = cd.x & 0xffffff;
+        if (tblocked && tblocked[idx]) continue;
+        if (cd.y < bestDist) { bestDist = cd.y; bestIdx = idx; }
+    }
+    best_idx[i] = (accept >= 0 && bestDist > accept) ? -1 : bestIdx;
+    if (best_dist) best_dist[i] = bestDist;
+}
+// SearchBySim3's agreement pass (:1353-1368): matches12[i1] = vnMatch1[i1] where vnMatch2[vnMatch1[i1]] == i1, else -1; *n_found (zeroed by the caller) counts them
+__global__ void __launch_bounds__(256) match_sim3_agree(int N1, const int *match1, int N2, const int *match2, int *matches12, int *n_found) {
+    const int i1 = blockIdx.x * 256 + threadIdx.x;
+    if (i1 >= N1) return;
+    const int idx2 = match1[i1];
+    const bool ok = idx2 >= 0 && idx2 < N2 && match2[idx2] == i1;
+    matches12[i1] = ok ? idx2 : -1;
+    if (ok) atomicAdd(n_found, 1);
 }
 
 // The orientation cut of a search whose matches are independent of each other (SearchForTriangulation, :801-830): histogram, three maxima, cut, count.  One workgroup.
@@ -653,8 +757,9 @@ struct cs_matcher {
     int *d_ccount = nullptr, *d_qrec = nullptr, *d_qm = nullptr /* max_q + 1 */, *d_level = nullptr;
     float *d_wp = nullptr /* x 3 */, *d_uv = nullptr /* x 2 */, *d_qur = nullptr, *d_ang = nullptr; uint8_t *d_valid = nullptr, *d_blocks = nullptr;
     float *d_T = nullptr /* 12 */, *d_sf = nullptr /* 32 */, *d_inv = nullptr /* 32 */; // a pose and the per-level tables (n_levels <= 32)
+    float *d_nrm = nullptr /* x 3 */, *d_mind = nullptr, *d_maxd = nullptr; int *d_nout = nullptr /* 2 */; // the Sim3 / relocalisation preamble: normals, distance ranges; points outside the scale table, nFound
     int2 *d_cands = nullptr; unsigned long long *d_cursor = nullptr; // [0] the arena's cursor, [1] an error flag (its low word)
-    std::vector<int> h_res;
+    std::vector<int> h_res; int h_nout[2] = {0, 0};
     long last_q = 0, last_c = 0;
 };
 
@@ -693,6 +798,7 @@ static int mt_alloc(cs_ctx *ctx, cs_matcher *m) {
     MT_TRY(o.alloc(ctx, &m->d_wp, nq * 3)); MT_TRY(o.alloc(ctx, &m->d_uv, nq * 2)); MT_TRY(o.alloc(ctx, &m->d_qur, nq)); MT_TRY(o.alloc(ctx, &m->d_ang, nq));
     MT_TRY(o.alloc(ctx, &m->d_valid, nq)); MT_TRY(o.alloc(ctx, &m->d_blocks, nq));
     MT_TRY(o.alloc(ctx, &m->d_T, (size_t)12)); MT_TRY(o.alloc(ctx, &m->d_sf, (size_t)32)); MT_TRY(o.alloc(ctx, &m->d_inv, (size_t)32));
+    MT_TRY(o.alloc(ctx, &m->d_nrm, nq * 3)); MT_TRY(o.alloc(ctx, &m->d_mind, nq)); MT_TRY(o.alloc(ctx, &m->d_maxd, nq)); MT_TRY(o.alloc(ctx, &m->d_nout, (size_t)2));
     MT_TRY(o.alloc(ctx, &m->d_cands, (size_t)m->max_cand)); MT_TRY(o.alloc(ctx, &m->d_cursor, (size_t)2));
     return CS_OK;
 }
@@ -1073,6 +1179,138 @@ int cs_match_for_triangulation(cs_ctx *ctx, const cs_keypoint *keys1Un, const ui
     MT_TRY(sc.drain());
     memcpy(matches12, res.data(), sizeof(int) * (size_t)N1);
     *nmatches = res[(size_t)N1];
+    return CS_OK;
+}
+
+} // extern "C"
+
+// ---- the searches that project map points through a Sim3 or a relocalisation pose: preamble, window enumeration and the loops, all on the device ----------------------------------
+struct MapIn { int n; const float *world_pos, *normal, *min_distance, *max_distance; const uint8_t *skip, *mp_desc, *train_blocked; };
+static MapP make_mapp(const float *R, const float *t, const float *Ow, const float *R2, const float *t2, float fx, float fy, float cx, float cy, float log_sf, float th, int n_levels) {
+    MapP P{};
+    for (int k = 0; k < 9; k++) { P.R[k] = R[k]; if (R2) P.R2[k] = R2[k]; }
+    for (int k = 0; k < 3; k++) { P.t[k] = t[k]; if (Ow) P.Ow[k] = Ow[k]; if (t2) P.t2[k] = t2[k]; }
+    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.log_sf = log_sf; P.th = th; P.n_levels = n_levels;
+    return P;
+}
+// uploads the map points, runs the preamble into m's query arrays (points outside the scale table add to *d_nout) and enumerates the windows in m's frame; nothing waits
+template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, int *d_nout) {
+    const int n = I.n, N = m->F.N;
+    MT_TRY(cs_h2d(ctx, m->d_wp, I.world_pos, (size_t)n * 3));
+    if (MODE == PM_SIM3) MT_TRY(cs_h2d(ctx, m->d_nrm, I.normal, (size_t)n * 3));
+    MT_TRY(cs_h2d(ctx, m->d_mind, I.min_distance, (size_t)n));
+    MT_TRY(cs_h2d(ctx, m->d_maxd, I.max_distance, (size_t)n));
+    MT_TRY(cs_h2d(ctx, m->d_valid, I.skip, (size_t)n));
+    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, I.mp_desc, (size_t)n * 32));
+    MT_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)P.n_levels));
+    if (I.train_blocked) MT_TRY(cs_h2d(ctx, m->d_tb, I.train_blocked, (size_t)N));
+    CS_LAUNCH(ctx, "match_project_map", match_project_map<MODE>, dim3((n + 255) / 256), dim3(256), 0, n, m->d_wp, m->d_nrm, m->d_mind, m->d_maxd, m->d_valid, P, m->d_sf, m->F, m->d_q, m->d_level, d_nout);
+    return mt_candidates(ctx, m, n, true);
+}
+static bool map_in_ok(const cs_matcher *m, const MapIn &I, bool need_normal) {
+    return I.n >= 0 && I.n <= m->max_q && (I.n == 0 || (I.world_pos && I.min_distance && I.max_distance && I.skip && I.mp_desc && (!need_normal || I.normal)));
+}
+// the order-dependent searches: RV_CLAIM over the queries in order, train_match + nmatches + the count of rule (d), one wait
+template <int MODE> static int mt_map_claim(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, const float *kf_angle, int accept_dist, int check_orientation,
+                                            int *train_match, int *nmatches, int *n_level_outside) {
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    const int N = m->F.N;
+    *nmatches = 0;
+    if (n_level_outside) *n_level_outside = 0;
+    if (I.n == 0) { for (int i = 0; i < N; i++) train_match[i] = -1; return CS_OK; }
+    CS_HIP(ctx, hipMemsetAsync(m->d_nout, 0, 2 * sizeof(int), ctx->stream));
+    if (check_orientation) MT_TRY(cs_h2d(ctx, m->d_ang, kf_angle, (size_t)I.n));
+    MT_TRY(mt_map_queries<MODE>(ctx, m, I, P, scale_factors, m->d_nout));
+    ResolveP R{};
+    R.cstart = m->d_cstart; R.ccount = m->d_ccount; R.cands = m->d_cands; R.n_steps = I.n; R.n_train = N; R.tkeys = m->d_keys; R.qangle = m->d_ang;
+    R.tblocked = I.train_blocked ? m->d_tb : nullptr; R.check_orientation = check_orientation; R.train_match = m->d_tm; R.q_rec = m->d_qrec; R.nmatches = m->d_tm + N; R.accept_dist = accept_dist;
+    MT_TRY(mt_resolve<RV_CLAIM>(ctx, R, 1, N));
+    int *nout = m->h_nout;
+    MT_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
+    MT_TRY(mt_finish(ctx, m, m->d_tm, N, train_match, nmatches));
+    if (n_level_outside) *n_level_outside = nout[0];
+    return CS_OK;
+}
+
+extern "C" {
+
+int cs_match_by_projection_reloc(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *min_distance,
+                                 const float *max_distance, const uint8_t *skip, const float *kf_angle, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx,
+                                 float cy, float log_scale_factor, const float *scale_factors, int n_levels, float th, int orb_dist, int check_orientation, int *train_match, int *nmatches,
+                                 int *n_level_outside) {
+    if (!ctx || !m) return CS_ERR_BAD_ARG;
+    const MapIn I{n_mp, world_pos, nullptr, min_distance, max_distance, skip, mp_desc, train_blocked};
+    if (!Rcw || !tcw || !Ow || !map_in_ok(m, I, false) || (n_mp && check_orientation && !kf_angle) || !scale_factors || n_levels < 1 || n_levels > 32 || !train_match || !nmatches) return CS_ERR_BAD_ARG;
+    return mt_map_claim<PM_RELOC>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, kf_angle, orb_dist, check_orientation,
+                                  train_match, nmatches, n_level_outside);
+}
+
+int cs_match_by_projection_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
+                                const float *max_distance, const uint8_t *skip, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx, float cy, float log_scale_factor,
+                                const float *scale_factors, int n_levels, float th, int *train_match, int *nmatches, int *n_level_outside) {
+    if (!ctx || !m) return CS_ERR_BAD_ARG;
+    const MapIn I{n_mp, world_pos, normal, min_distance, max_distance, skip, mp_desc, train_blocked};
+    if (!Rcw || !tcw || !Ow || !map_in_ok(m, I, true) || !scale_factors || n_levels < 1 || n_levels > 32 || !train_match || !nmatches) return CS_ERR_BAD_ARG;
+    return mt_map_claim<PM_SIM3>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, nullptr, TH_LOW, 0, train_match, nmatches,
+                                 n_level_outside);
+}
+
+int cs_match_fuse_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
+                       const float *max_distance, const uint8_t *skip, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx, float cy, float log_scale_factor,
+                       const float *scale_factors, int n_levels, float th, int *best_idx, int *best_dist, int *n_fused, int *n_level_outside) {
+    if (!ctx || !m) return CS_ERR_BAD_ARG;
+    const MapIn I{n_mp, world_pos, normal, min_distance, max_distance, skip, mp_desc, train_blocked};
+    if (!Rcw || !tcw || !Ow || !map_in_ok(m, I, true) || !scale_factors || n_levels < 1 || n_levels > 32 || !best_idx || !best_dist || !n_fused) return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    *n_fused = 0;
+    if (n_level_outside) *n_level_outside = 0;
+    if (n_mp == 0) return CS_OK;
+    CS_HIP(ctx, hipMemsetAsync(m->d_nout, 0, 2 * sizeof(int), ctx->stream));
+    MT_TRY(mt_map_queries<PM_SIM3>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m->d_nout));
+    CS_LAUNCH(ctx, "match_map_best", match_map_best, dim3((n_mp + 255) / 256), dim3(256), 0, n_mp, m->d_cstart, m->d_ccount, m->d_cands, train_blocked ? m->d_tb : (const uint8_t *)nullptr, -1, m->d_qm, m->d_qrec);
+    int *nout = m->h_nout;
+    MT_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
+    MT_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
+    MT_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
+    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
+    int nf = 0;
+    for (int i = 0; i < n_mp; i++) if (best_dist[i] <= TH_LOW) nf++; // :1121
+    *n_fused = nf;
+    if (n_level_outside) *n_level_outside = nout[0];
+    return CS_OK;
+}
+
+int cs_match_by_sim3(cs_ctx *ctx, cs_matcher *m1, cs_matcher *m2, const float *R1w, const float *t1w, const float *R2w, const float *t2w, const float *sR12, const float *t12, const float *sR21,
+                     const float *t21, int n1, const float *world_pos1, const float *min_distance1, const float *max_distance1, const uint8_t *skip1, const uint8_t *mp_desc1,
+                     const uint8_t *train_blocked1, int n2, const float *world_pos2, const float *min_distance2, const float *max_distance2, const uint8_t *skip2, const uint8_t *mp_desc2,
+                     const uint8_t *train_blocked2, float fx, float fy, float cx, float cy, float log_scale_factor, const float *scale_factors, int n_levels, float th, int *matches12, int *n_found,
+                     int *n_level_outside) {
+    if (!ctx || !m1 || !m2 || m1 == m2) return CS_ERR_BAD_ARG;
+    // the points of KF1 are searched in KF2 (m2's frame and query arrays) and the other way round
+    const MapIn I1{n1, world_pos1, nullptr, min_distance1, max_distance1, skip1, mp_desc1, train_blocked2}, I2{n2, world_pos2, nullptr, min_distance2, max_distance2, skip2, mp_desc2, train_blocked1};
+    if (!R1w || !t1w || !R2w || !t2w || !sR12 || !t12 || !sR21 || !t21 || !map_in_ok(m2, I1, false) || !map_in_ok(m1, I2, false) || !scale_factors || n_levels < 1 || n_levels > 32 ||
+        (n1 && !matches12) || !n_found)
+        return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    *n_found = 0;
+    if (n_level_outside) *n_level_outside = 0;
+    for (int i = 0; i < n1; i++) matches12[i] = -1;
+    if (n1 == 0 || n2 == 0) return CS_OK; // (no agreement without both directions)
+    CS_HIP(ctx, hipMemsetAsync(m2->d_nout, 0, 2 * sizeof(int), ctx->stream));
+    MT_TRY(mt_map_queries<PM_PAIR>(ctx, m2, I1, make_mapp(R1w, t1w, nullptr, sR21, t21, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m2->d_nout)); // :1187-1267
+    CS_LAUNCH(ctx, "match_map_best", match_map_best, dim3((n1 + 255) / 256), dim3(256), 0, n1, m2->d_cstart, m2->d_ccount, m2->d_cands, train_blocked2 ? m2->d_tb : (const uint8_t *)nullptr, TH_HIGH, m2->d_qm,
+              (int *)nullptr);
+    MT_TRY(mt_map_queries<PM_PAIR>(ctx, m1, I2, make_mapp(R2w, t2w, nullptr, sR12, t12, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m2->d_nout)); // :1270-1350
+    CS_LAUNCH(ctx, "match_map_best", match_map_best, dim3((n2 + 255) / 256), dim3(256), 0, n2, m1->d_cstart, m1->d_ccount, m1->d_cands, train_blocked1 ? m1->d_tb : (const uint8_t *)nullptr, TH_HIGH, m1->d_qm,
+              (int *)nullptr);
+    CS_LAUNCH(ctx, "match_sim3_agree", match_sim3_agree, dim3((n1 + 255) / 256), dim3(256), 0, n1, m2->d_qm, n2, m1->d_qm, m2->d_qrec, m2->d_nout + 1); // :1353-1368
+    int *nout = m2->h_nout;
+    MT_TRY(cs_d2h(ctx, nout, m2->d_nout, 2));
+    MT_TRY(cs_d2h(ctx, matches12, m2->d_qrec, (size_t)n1));
+    const int r2 = mt_cursor(ctx, m2->d_cursor, m2->max_cand, &m2->last_c), r1 = mt_cursor(ctx, m1->d_cursor, m1->max_cand, &m1->last_c); // (the first one waits; both arenas are checked)
+    if (r2 != CS_OK || r1 != CS_OK) { for (int i = 0; i < n1; i++) matches12[i] = -1; return r2 != CS_OK ? r2 : r1; }
+    *n_found = nout[1];
+    if (n_level_outside) *n_level_outside = nout[0];
     return CS_OK;
 }
 

@@ -101,6 +101,74 @@ class ORBmatcher:
                                                 _p(bi, C.c_int), _p(bd, C.c_int), C.byref(n)), "cs_match_fuse")
         return bi[:len(va)].copy(), bd[:len(va)].copy(), n.value
 
+    @staticmethod
+    def _map_points(world_pos, min_distance, max_distance, skip, mp_desc, normal=None):
+        a = [np.ascontiguousarray(world_pos, np.float32), np.ascontiguousarray(min_distance, np.float32), np.ascontiguousarray(max_distance, np.float32),
+             np.ascontiguousarray(skip, np.uint8), np.ascontiguousarray(mp_desc, np.uint8)]
+        if normal is not None:
+            a.append(np.ascontiguousarray(normal, np.float32))
+        return a
+
+    @staticmethod
+    def _f(a, n):
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        assert a.size == n
+        return a
+
+    def SearchByProjectionReloc(self, Rcw, tcw, Ow, world_pos, min_distance, max_distance, skip, kf_angle, mp_desc, fx, fy, cx, cy, log_scale_factor, scale_factors, th, ORBdist, train_blocked=None):
+        """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1727-1858) against the current frame given to set_frame: (train_match per
+        key point of the current frame = index of pKF's map point or -1, nmatches, points dropped because their predicted level is outside the scale table)."""
+        wp, mn, mx, sk, md = self._map_points(world_pos, min_distance, max_distance, skip, mp_desc)
+        R, t, O = self._f(Rcw, 9), self._f(tcw, 3), self._f(Ow, 3); ka = np.ascontiguousarray(kf_angle, np.float32); sf = np.ascontiguousarray(scale_factors, np.float32)
+        tb = None if train_blocked is None else np.ascontiguousarray(train_blocked, np.uint8)
+        tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int(); no = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_by_projection_reloc(self.ctx.ptr, self._m, _p(R, C.c_float), _p(t, C.c_float), _p(O, C.c_float), len(sk), _p(wp, C.c_float), _p(mn, C.c_float),
+                                                               _p(mx, C.c_float), _p(sk, C.c_uint8), _p(ka, C.c_float), _p(md, C.c_uint8), None if tb is None else _p(tb, C.c_uint8),
+                                                               C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.c_float(log_scale_factor), _p(sf, C.c_float), len(sf),
+                                                               C.c_float(th), int(ORBdist), int(self.mbCheckOrientation), _p(tm, C.c_int), C.byref(n), C.byref(no)),
+              "cs_match_by_projection_reloc")
+        return tm[:self.N].copy(), n.value, no.value
+
+    def SearchByProjectionSim3(self, Rcw, tcw, Ow, world_pos, normal, min_distance, max_distance, skip, mp_desc, fx, fy, cx, cy, log_scale_factor, scale_factors, th, train_blocked=None):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cc:309-427) against the key frame given to set_frame: (train_match per key point = index
+        into vpPoints or -1, nmatches, points outside the scale table).  train_blocked = vpMatched[idx] != NULL or not KeysStatic[idx]."""
+        wp, mn, mx, sk, md, nr = self._map_points(world_pos, min_distance, max_distance, skip, mp_desc, normal)
+        R, t, O = self._f(Rcw, 9), self._f(tcw, 3), self._f(Ow, 3); sf = np.ascontiguousarray(scale_factors, np.float32)
+        tb = None if train_blocked is None else np.ascontiguousarray(train_blocked, np.uint8)
+        tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int(); no = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_by_projection_sim3(self.ctx.ptr, self._m, _p(R, C.c_float), _p(t, C.c_float), _p(O, C.c_float), len(sk), _p(wp, C.c_float), _p(nr, C.c_float),
+                                                              _p(mn, C.c_float), _p(mx, C.c_float), _p(sk, C.c_uint8), _p(md, C.c_uint8), None if tb is None else _p(tb, C.c_uint8),
+                                                              C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.c_float(log_scale_factor), _p(sf, C.c_float), len(sf),
+                                                              C.c_float(th), _p(tm, C.c_int), C.byref(n), C.byref(no)), "cs_match_by_projection_sim3")
+        return tm[:self.N].copy(), n.value, no.value
+
+    def FuseSim3(self, Rcw, tcw, Ow, world_pos, normal, min_distance, max_distance, skip, mp_desc, fx, fy, cx, cy, log_scale_factor, scale_factors, th, train_blocked=None):
+        """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint), the search (ORBmatcher.cc:1033-1118), against the key frame given to set_frame: (best_idx, best_dist per map
+        point, nFused, points outside the scale table).  train_blocked = not KeysStatic[idx]."""
+        wp, mn, mx, sk, md, nr = self._map_points(world_pos, min_distance, max_distance, skip, mp_desc, normal)
+        R, t, O = self._f(Rcw, 9), self._f(tcw, 3), self._f(Ow, 3); sf = np.ascontiguousarray(scale_factors, np.float32)
+        tb = None if train_blocked is None else np.ascontiguousarray(train_blocked, np.uint8)
+        bi = np.zeros(max(len(sk), 1), np.int32); bd = np.zeros(max(len(sk), 1), np.int32); n = C.c_int(); no = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_fuse_sim3(self.ctx.ptr, self._m, _p(R, C.c_float), _p(t, C.c_float), _p(O, C.c_float), len(sk), _p(wp, C.c_float), _p(nr, C.c_float),
+                                                     _p(mn, C.c_float), _p(mx, C.c_float), _p(sk, C.c_uint8), _p(md, C.c_uint8), None if tb is None else _p(tb, C.c_uint8),
+                                                     C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.c_float(log_scale_factor), _p(sf, C.c_float), len(sf),
+                                                     C.c_float(th), _p(bi, C.c_int), _p(bd, C.c_int), C.byref(n), C.byref(no)), "cs_match_fuse_sim3")
+        return bi[:len(sk)].copy(), bd[:len(sk)].copy(), n.value, no.value
+
+    def SearchBySim3(self, other, R1w, t1w, R2w, t2w, sR12, t12, sR21, t21, points1, points2, fx, fy, cx, cy, log_scale_factor, scale_factors, th, train_blocked1=None, train_blocked2=None):
+        """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:1141-1371); self holds KF1, `other` KF2.  points_k = (world_pos, min_distance,
+        max_distance, skip, mp_desc) of KFk's map points, one per key point.  Returns (matches12 per key point of KF1 = key point of KF2 or -1, nFound, points outside the scale table)."""
+        a1 = self._map_points(*points1); a2 = self._map_points(*points2)
+        Ts = [self._f(x, k) for x, k in ((R1w, 9), (t1w, 3), (R2w, 9), (t2w, 3), (sR12, 9), (t12, 3), (sR21, 9), (t21, 3))]
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        tb1 = None if train_blocked1 is None else np.ascontiguousarray(train_blocked1, np.uint8); tb2 = None if train_blocked2 is None else np.ascontiguousarray(train_blocked2, np.uint8)
+        side = lambda a, tb: (len(a[3]), _p(a[0], C.c_float), _p(a[1], C.c_float), _p(a[2], C.c_float), _p(a[3], C.c_uint8), _p(a[4], C.c_uint8), None if tb is None else _p(tb, C.c_uint8))
+        m12 = np.zeros(max(len(a1[3]), 1), np.int32); n = C.c_int(); no = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_by_sim3(self.ctx.ptr, self._m, other._m, *[_p(x, C.c_float) for x in Ts], *side(a1, tb1), *side(a2, tb2), C.c_float(fx), C.c_float(fy), C.c_float(cx),
+                                                   C.c_float(cy), C.c_float(log_scale_factor), _p(sf, C.c_float), len(sf), C.c_float(th), _p(m12, C.c_int), C.byref(n), C.byref(no)),
+              "cs_match_by_sim3")
+        return m12[:len(a1[3])].copy(), n.value, no.value
+
     def SearchForTriangulation(self, keys1Un, desc1, node1, skip1, ur1, keys2Un, desc2, node2, skip2, ur2, F12, ex, ey, scale_factors2, level_sigma2_2, bOnlyStereo=False):
         """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cc:679-850): matches12 and nmatches."""
         k1 = np.ascontiguousarray(keys1Un, KEYPOINT_DTYPE); d1 = np.ascontiguousarray(desc1, np.uint8); k2 = np.ascontiguousarray(keys2Un, KEYPOINT_DTYPE)

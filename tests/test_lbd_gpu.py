@@ -32,7 +32,16 @@ def test_descriptors_bit_exact(ctx, oracle):
         rdesc, rfd = oracle.lbd_compute(img, kl, want_float=True)
         assert np.array_equal(fd.view(np.uint32), rfd.view(np.uint32)), "72-float LBD vectors"
         assert np.array_equal(desc, rdesc)
-        assert np.all(np.abs(np.linalg.norm(fd.astype(np.float64), axis=1) - 1) < 1e-5) and fd.max() <= 0.4 / 0.4  # unit vectors
+        assert np.all(np.abs(np.linalg.norm(fd.astype(np.float64), axis=1) - 1) < 1e-5)  # unit vectors
+        # Before the last normalisation no element exceeds float32(0.4) (computeLBD :1462-1470), so a row's elements are at most float32(0.4) / norm, norm that of the
+        # clipped vector.  A row with two or more elements at its maximum has them on the clip: there the maximum IS float32(0.4) / norm.  The two halves of the vector
+        # are unit vectors of non-negative elements before the clip and keep a norm of 0.4 at least under it, so 0.4 sqrt(2) <= norm <= sqrt(2) and no element of
+        # any row exceeds 1 / sqrt(2).
+        rowmax = fd.max(1)
+        on_clip = (fd == rowmax[:, None]).sum(1) >= 2
+        norm = np.float32(0.4) / rowmax[on_clip]
+        assert on_clip.sum() >= 10 and 0.4 * np.sqrt(2) * (1 - 1e-6) <= norm.min() and norm.max() <= np.sqrt(2) * (1 + 1e-6)
+        assert fd.min() >= 0 and fd.max() <= (1 + 1e-6) / np.sqrt(2)
     det.line_length_thres = 15.0
     kl2, d2 = det.detect_descrip_lines(_images()[0])
     assert len(kl2) == len(d2) and np.all(kl2["lineLength"] > 15.0)

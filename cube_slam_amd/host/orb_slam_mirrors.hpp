@@ -7,7 +7,7 @@
 //                               ComputeStereoMatches over two extractors, mvuRight / mvDepth
 //   cubeslam::line_lbd_detect   line_lbd_detect              (line_lbd/include/line_lbd/line_lbd_allclass.h:22-70)
 //   cubeslam::Optimizer         ORB_SLAM2::Optimizer         (orb_object_slam/include/Optimizer.h:39-62): BundleAdjustment over the
-//                               flattened graph (cs_ba_problem), PoseOptimization over flattened matches,
+//                               flattened graph (cs_ba_problem), PoseOptimization over flattened matches, OptimizeSim3 over flattened correspondences,
 //                               LocalBACameraPointObjectsDynamic over the flattened dynamic graph (cs_ba_dyn_problem)
 #pragma once
 #include <cstdint>
@@ -159,6 +159,20 @@ struct Optimizer {
         check(c.ctx, cs_pose_optimization(c.ctx, 1, off, Xw, obs, inv_sigma2, intr, pose_in, pose_out, mvbOutlier.data(), &n_inl), "cs_pose_optimization");
         mvbOutlier.resize((size_t)n);
         return n_inl;
+    }
+    // Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:2838-3033) over the n correspondences that survive its filter (:2893-2928):
+    // P1c / P2c (n x 3) are its float R * P + t products, obs1 / obs2 (n x 2) the undistorted key points, inv_sigma2_* their mvInvLevelSigma2[octave], intr
+    // (fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2), sim3 [t, qx qy qz qw, s] in / out (out = in where the reference returns before writing g2oS12); removed[c] = 1 where it sets
+    // vpMatches1[idx] = NULL; returns nIn
+    static int OptimizeSim3(Context &c, int n, const double *P1c, const double *P2c, const double *obs1, const double *obs2, const double *inv_sigma2_1, const double *inv_sigma2_2,
+                            const double intr[8], const double sim3_in[8], float th2, bool bFixScale, double sim3_out[8], std::vector<uint8_t> &removed) {
+        const int off[2] = {0, n};
+        const uint8_t fix = bFixScale ? 1 : 0;
+        int n_in = 0;
+        removed.assign((size_t)n + 1, 0);
+        check(c.ctx, cs_sim3_optimization(c.ctx, 1, off, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, intr, sim3_in, &th2, &fix, sim3_out, removed.data(), &n_in), "cs_sim3_optimization");
+        removed.resize((size_t)n);
+        return n_in;
     }
     // Optimizer::LocalBACameraPointObjectsDynamic (Optimizer.cc:2353-2415) on a graph the caller flattened from the map (:1684-2344):
     // optimize(5); reprojection edges with chi2 > 5.991 / 7.815 or a non-positive depth and dynamic-point edges with chi2 > 8 go to level 1

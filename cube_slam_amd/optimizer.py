@@ -1,4 +1,4 @@
-"""Python host-side mirror of ORB_SLAM2::Optimizer (reference orb_object_slam/include/Optimizer.h:36-52): PoseOptimization here,
+"""Python host-side mirror of ORB_SLAM2::Optimizer (reference orb_object_slam/include/Optimizer.h:36-52): PoseOptimization and OptimizeSim3 here,
 BundleAdjustment / LocalBACameraPointObjects in cube_slam_amd.ba."""
 import ctypes as C
 
@@ -31,6 +31,40 @@ def PoseOptimization(frames, ctx=None, device=0):
     check(ctx.ptr, lib().cs_pose_optimization(ctx.ptr, F, _p(off, C.c_int), _p(Xw, C.c_double), _p(obs, C.c_double), _p(w, C.c_double), _p(intr, C.c_double),
                                               _p(pin, C.c_double), _p(pout, C.c_double), _p(flags, C.c_uint8), _p(ninl, C.c_int)), "cs_pose_optimization")
     return [(pout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
+
+
+def OptimizeSim3(problems, ctx=None, device=0):
+    """Optimizer::OptimizeSim3 (Optimizer.cc:2838-3033) for one problem (a dict) or a batch (a list of dicts)
+    {P1c (n,3), P2c (n,3), obs1 (n,2), obs2 (n,2), inv_sigma2_1 (n,), inv_sigma2_2 (n,), intrinsics (fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2), sim3_in (tx ty tz qx qy qz qw s),
+    th2, fix_scale} over the correspondences that survive the reference's filter (:2893-2928), P1c / P2c being its float R * P + t products.
+    Returns (sim3_out (8,), removed (n,) u8, n_inliers) per problem: g2oS12 as the reference leaves it (sim3_in bit for bit where it returns 0 before writing it),
+    1 where it sets vpMatches1[idx] = NULL, and its return value.  A single dict gives a single tuple."""
+    single = isinstance(problems, dict)
+    if single:
+        problems = [problems]
+    ctx = ctx or _lib.Context(device)
+    F = len(problems)
+    if F == 0:
+        return []
+    off = np.zeros(F + 1, np.int32)
+    for f, pr in enumerate(problems):
+        off[f + 1] = off[f] + len(np.asarray(pr["inv_sigma2_1"]).reshape(-1))
+    ne = int(off[F])
+    cat = lambda k, w: np.ascontiguousarray(np.concatenate([np.asarray(pr[k], np.float64).reshape(-1, w) for pr in problems]) if ne else np.zeros((1, w)))
+    P1, P2, o1, o2, w1, w2 = cat("P1c", 3), cat("P2c", 3), cat("obs1", 2), cat("obs2", 2), cat("inv_sigma2_1", 1), cat("inv_sigma2_2", 1)
+    for a, w in ((P1, 3), (P2, 3), (o1, 2), (o2, 2), (w1, 1), (w2, 1)):
+        if a.shape != (max(ne, 1), w):
+            raise ValueError("OptimizeSim3: the arrays of a problem do not have one row per correspondence")
+    intr = np.ascontiguousarray(np.stack([np.asarray(pr["intrinsics"], np.float64).reshape(8) for pr in problems]))
+    sin = np.ascontiguousarray(np.stack([np.asarray(pr["sim3_in"], np.float64).reshape(8) for pr in problems]))
+    th2 = np.ascontiguousarray([pr["th2"] for pr in problems], np.float32)
+    fix = np.ascontiguousarray([1 if pr["fix_scale"] else 0 for pr in problems], np.uint8)
+    sout = np.zeros((F, 8)); flags = np.zeros(max(ne, 1), np.uint8); ninl = np.zeros(F, np.int32)
+    check(ctx.ptr, lib().cs_sim3_optimization(ctx.ptr, F, _p(off, C.c_int), _p(P1, C.c_double), _p(P2, C.c_double), _p(o1, C.c_double), _p(o2, C.c_double), _p(w1, C.c_double),
+                                              _p(w2, C.c_double), _p(intr, C.c_double), _p(sin, C.c_double), _p(th2, C.c_float), _p(fix, C.c_uint8), _p(sout, C.c_double),
+                                              _p(flags, C.c_uint8), _p(ninl, C.c_int)), "cs_sim3_optimization")
+    res = [(sout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
+    return res[0] if single else res
 
 
 def cuboid9_oplus(cub, upd, ctx=None, device=0):

@@ -553,6 +553,19 @@ int cs_lbd_maps(cs_ctx *ctx, const uint8_t *gray, int width, int height, int str
 int cs_pose_optimization(cs_ctx *ctx, int n_frames, const int *edge_off, const double *Xw, const double *obs, const double *inv_sigma2, const double *intrinsics,
                          const double *pose_in, double *pose_out, uint8_t *outlier, int *n_inliers);
 
+/* ===================================================================== Optimizer::OptimizeSim3
+ * Replaces ORB_SLAM2::Optimizer::OptimizeSim3(KeyFrame*, KeyFrame*, vector<MapPoint*>&, g2o::Sim3&, float, bool) (orb_object_slam/include/Optimizer.h,
+ * src/Optimizer.cc:2838-3033) for a batch of problems: problem f owns the correspondences [corr_off[f], corr_off[f+1]) that survive the filter of :2893-2928
+ * (vpMatches1[i] set, neither point bad, i2 >= 0), in the order of i.  P1c / P2c (3 each) are R1w * P3D1w + t1w and R2w * P3D2w + t2w as the reference's float
+ * cv::Mat computes them (:2910, :2918); obs1 / obs2 (2 each) are mvKeysUn[i].pt of pKF1 and mvKeysUn[i2].pt of pKF2; inv_sigma2_* are mvInvLevelSigma2[octave] of
+ * those key points; intrinsics n_problems x 8 = fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2; sim3_in n_problems x 8 = tx ty tz qx qy qz qw s, the coefficients g2o::Sim3 holds,
+ * NOT normalised; th2 and fix_scale per problem.  Out: sim3_out (g2oS12; equal to sim3_in bit for bit where the function returns before writing it, :3003-3004),
+ * removed[c] = 1 where the reference sets vpMatches1[idx] = NULL, n_inliers[f] = the return value.  One workgroup per problem runs optimize(5), the cut, and
+ * optimize(10 or 5) with g2o's numeric Jacobians and Levenberg-Marquardt schedule in one launch. */
+int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const double *P1c, const double *P2c, const double *obs1, const double *obs2,
+                         const double *inv_sigma2_1, const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2,
+                         const uint8_t *fix_scale, double *sim3_out, uint8_t *removed, int *n_inliers);
+
 /* ===================================================================== batch front-end runner
  * One pass of the per-frame path (ORBextractor::operator(), line_lbd_detect::detect_descrip_lines, detect_3d_cuboid::detect_cuboid --
  * what Tracking / main_obj.cpp call per frame, object_slam/src/main_obj.cpp:395-470) over a batch that is resident in HBM.  Handles

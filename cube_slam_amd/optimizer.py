@@ -1,4 +1,4 @@
-"""Python host-side mirror of ORB_SLAM2::Optimizer (reference orb_object_slam/include/Optimizer.h:36-52): PoseOptimization and OptimizeSim3 here,
+"""Python host-side mirror of ORB_SLAM2::Optimizer (reference orb_object_slam/include/Optimizer.h:36-52): PoseOptimization, OptimizeSim3 and OptimizeEssentialGraph here,
 BundleAdjustment / LocalBACameraPointObjects in cube_slam_amd.ba."""
 import ctypes as C
 
@@ -65,6 +65,153 @@ def OptimizeSim3(problems, ctx=None, device=0):
                                               _p(flags, C.c_uint8), _p(ninl, C.c_int)), "cs_sim3_optimization")
     res = [(sout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
     return res[0] if single else res
+
+
+MIN_FEAT = 100  # Optimizer.cc:2600
+
+
+def build_essential_graph(flat):
+    """The vertices and edges Optimizer::OptimizeEssentialGraph inserts (Optimizer.cc:2603-2776) from a flattened map:
+    flat = {"kfs": [per key frame, in the order of pMap->GetAllKeyFrames(): {"mnId", "parent" (mnId or None), "loop_edges" (GetLoopEdges() in its iteration order),
+    "covisibles" (GetCovisiblesByWeight(100) in its order), "children" (mnIds), "weights" ({mnId: GetWeight}, needed for the members of LoopConnections), "bad" (optional)}],
+    "bad" (mnIds of bad key frames that are not in kfs but may appear among covisibles), "loop_connections" ([(mnId, [mnId, ...]), ...] in std::map / std::set iteration order),
+    "loop_kf", "cur_kf" (mnIds), "Scw" ({mnId: 8 numbers}: CorrectedSim3 where the key frame has an entry, Sim3(Rcw, tcw, 1.0) otherwise), "non_corrected" ({mnId: 8 numbers})}.
+    Vertex v is kfs[v].  Returns {"mnId" (n,), "edge_i", "edge_j" (m,) int32, "edge_kind" (m,) u8, "fixed_vertex", "Scw" (n,8), "Snc" (n,8), "has_nc" (n,) u8}.
+    A bad key frame in kfs, or an edge to a key frame that is not in kfs, raises ValueError: the reference dereferences a null vertex there (:2791)."""
+    kfs = flat["kfs"]
+    index = {}
+    for v, kf in enumerate(kfs):
+        if kf.get("bad"):
+            raise ValueError("build_essential_graph: key frame %d is bad; the reference gives it no vertex and dereferences a null pointer at Optimizer.cc:2791" % kf["mnId"])
+        if kf["mnId"] in index:
+            raise ValueError("build_essential_graph: key frame %d appears twice" % kf["mnId"])
+        index[kf["mnId"]] = v
+    bad = set(flat.get("bad", ()))
+    loop_kf, cur_kf = flat["loop_kf"], flat["cur_kf"]
+
+    def vertex(mnId):
+        if mnId not in index:
+            raise ValueError("build_essential_graph: key frame %d is %s; an edge to it has a null vertex in the reference" % (mnId, "bad" if mnId in bad else "not in the map"))
+        return index[mnId]
+
+    vertex(loop_kf), vertex(cur_kf)
+    ei, ej, kind, inserted = [], [], [], set()
+    for i, conns in flat["loop_connections"]:  # :2645-2673
+        for j in conns:
+            if (i != cur_kf or j != loop_kf) and kfs[vertex(i)]["weights"].get(j, 0) < MIN_FEAT:
+                continue
+            ei.append(vertex(i)), ej.append(vertex(j)), kind.append(0)
+            inserted.add((min(i, j), max(i, j)))
+    for kf in kfs:  # :2676-2776
+        i, parent = kf["mnId"], kf["parent"]
+        if parent is not None:
+            ei.append(index[i]), ej.append(vertex(parent)), kind.append(1)
+        for l in kf["loop_edges"]:
+            if l < i:
+                ei.append(index[i]), ej.append(vertex(l)), kind.append(1)
+        for nb in kf["covisibles"]:
+            if nb is not None and nb != parent and nb not in kf["children"] and nb not in kf["loop_edges"]:
+                if nb not in bad and nb < i:
+                    if (min(i, nb), max(i, nb)) in inserted:
+                        continue
+                    ei.append(index[i]), ej.append(vertex(nb)), kind.append(1)
+    n = len(kfs)
+    Scw = np.ascontiguousarray([np.asarray(flat["Scw"][kf["mnId"]], np.float64).reshape(8) for kf in kfs]).reshape(n, 8)
+    Snc, has = np.zeros((n, 8)), np.zeros(n, np.uint8)
+    for mnId, S in flat["non_corrected"].items():
+        if mnId in index:
+            Snc[index[mnId]] = np.asarray(S, np.float64).reshape(8)
+            has[index[mnId]] = 1
+    return {"mnId": np.array([kf["mnId"] for kf in kfs], np.int64), "edge_i": np.array(ei, np.int32), "edge_j": np.array(ej, np.int32), "edge_kind": np.array(kind, np.uint8),
+            "fixed_vertex": index[loop_kf], "Scw": Scw, "Snc": Snc, "has_nc": has}
+
+
+class _EgStats(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("trials", C.c_int), ("accepted", C.c_int), ("rejected", C.c_int), ("levels", C.c_int), ("l_blocks", C.c_int), ("h_blocks", C.c_int),
+                ("launches_per_trial", C.c_int), ("chi2_first", C.c_double), ("chi2_last", C.c_double), ("lambda_last", C.c_double), ("trial_accepted", C.c_uint8 * 256)]
+
+
+class EssentialGraph:
+    """cs_essential_graph: the structure of one pose graph (a dict as build_essential_graph returns), analysed once; optimize() may run any number of times."""
+
+    def __init__(self, graph, fix_scale, ctx=None, device=0):
+        self.ctx = ctx or _lib.Context(device)
+        self.n = len(graph["Scw"])
+        ei, ej, kind = (np.ascontiguousarray(graph["edge_i"], np.int32), np.ascontiguousarray(graph["edge_j"], np.int32), np.ascontiguousarray(graph["edge_kind"], np.uint8))
+        if not (len(ei) == len(ej) == len(kind)):
+            raise ValueError("EssentialGraph: edge_i, edge_j and edge_kind differ in length")
+        self._h = C.c_void_p()
+        check(self.ctx.ptr, lib().cs_essential_graph_create(self.ctx.ptr, self.n, len(ei), _p(ei, C.c_int), _p(ej, C.c_int), _p(kind, C.c_uint8), int(graph["fixed_vertex"]),
+                                                            int(bool(fix_scale)), C.byref(self._h)), "cs_essential_graph_create")
+
+    def optimize(self, Scw, Snc, has_nc, iterations=20):
+        """-> (sim3_out (n,8), Tiw (n,3,4) float32, stats)"""
+        n = self.n
+        Scw, Snc, has = np.ascontiguousarray(Scw, np.float64).reshape(-1, 8), np.ascontiguousarray(Snc, np.float64).reshape(-1, 8), np.ascontiguousarray(has_nc, np.uint8).reshape(-1)
+        if not (len(Scw) == len(Snc) == len(has) == n):
+            raise ValueError("EssentialGraph.optimize: Scw, Snc and has_nc need one row per vertex")
+        out, Tiw, st = np.zeros((n, 8)), np.zeros((n, 3, 4), np.float32), _EgStats()
+        check(self.ctx.ptr, lib().cs_essential_graph_optimize(self.ctx.ptr, self._h, _p(Scw, C.c_double), _p(Snc, C.c_double), _p(has, C.c_uint8), int(iterations), _p(out, C.c_double),
+                                                              _p(Tiw, C.c_float), C.byref(st)), "cs_essential_graph_optimize")
+        stats = {k: getattr(st, k) for k, _ in _EgStats._fields_[:-1]}
+        stats["sequence"] = [int(st.trial_accepted[k]) for k in range(min(st.trials, 256))]
+        return out, Tiw, stats
+
+    def close(self):
+        if self._h:
+            lib().cs_essential_graph_destroy.restype = None
+            lib().cs_essential_graph_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def correct_points(P, ref_vertex, Scw, sim3_out, ctx=None, device=0):
+    """Optimizer.cc:2824-2831 for every point: (float) sim3_out[r].inverse().map(Scw[r].map(P)); P (np,3) = toVector3d of the float positions, ref_vertex (np,) the vertex of nIDr."""
+    ctx = ctx or _lib.Context(device)
+    P, ref = np.ascontiguousarray(P, np.float64).reshape(-1, 3), np.ascontiguousarray(ref_vertex, np.int32).reshape(-1)
+    Scw, out = np.ascontiguousarray(Scw, np.float64).reshape(-1, 8), np.ascontiguousarray(sim3_out, np.float64).reshape(-1, 8)
+    if len(P) != len(ref) or Scw.shape != out.shape:
+        raise ValueError("correct_points: one ref_vertex per point, one corrected Sim3 per Scw")
+    res = np.zeros((len(P), 3), np.float32)
+    check(ctx.ptr, lib().cs_sim3_correct_points(ctx.ptr, len(P), _p(P, C.c_double), _p(ref, C.c_int), len(Scw), _p(Scw, C.c_double), _p(out, C.c_double), _p(res, C.c_float)),
+          "cs_sim3_correct_points")
+    return res
+
+
+def sim3_log(S, ctx=None, device=0):
+    """g2o::Sim3::log of (n,8) transforms -> (n,7) (omega, upsilon, sigma), on the device."""
+    ctx = ctx or _lib.Context(device)
+    S = np.ascontiguousarray(S, np.float64).reshape(-1, 8)
+    out = np.zeros((len(S), 7))
+    check(ctx.ptr, lib().cs_sim3_log(ctx.ptr, len(S), _p(S, C.c_double), _p(out, C.c_double)), "cs_sim3_log")
+    return out
+
+
+def OptimizeEssentialGraph(flat, fix_scale, points=None, iterations=20, ctx=None, device=0):
+    """Optimizer::OptimizeEssentialGraph (Optimizer.cc:2575-2836) on a flattened map (see build_essential_graph).  points: optional (P (np,3), nIDr (np,) mnIds), the
+    float world positions and the reference key frame the caller chose per point (:2813-2822).
+    Returns {"graph", "sim3" (n,8), "Tiw" (n,3,4) float32 -- what the caller hands to SetPose --, "points" (np,3) float32 or None -- for SetWorldPos --, "stats"}."""
+    ctx = ctx or _lib.Context(device)
+    g = build_essential_graph(flat)
+    eg = EssentialGraph(g, fix_scale, ctx=ctx)
+    try:
+        sim3, Tiw, stats = eg.optimize(g["Scw"], g["Snc"], g["has_nc"], iterations)
+    finally:
+        eg.close()
+    corrected = None
+    if points is not None:
+        index = {int(m): v for v, m in enumerate(g["mnId"])}
+        try:
+            ref = np.array([index[int(r)] for r in np.asarray(points[1]).reshape(-1)], np.int32)
+        except KeyError as e:
+            raise ValueError("OptimizeEssentialGraph: a point's reference key frame %s is not in the map" % e)
+        corrected = correct_points(points[0], ref, g["Scw"], sim3, ctx=ctx)
+    return {"graph": g, "sim3": sim3, "Tiw": Tiw, "points": corrected, "stats": stats}
 
 
 def cuboid9_oplus(cub, upd, ctx=None, device=0):

@@ -566,6 +566,43 @@ int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const
                          const double *inv_sigma2_1, const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2,
                          const uint8_t *fix_scale, double *sim3_out, uint8_t *removed, int *n_inliers);
 
+/* ===================================================================== Optimizer::OptimizeEssentialGraph
+ * Replaces ORB_SLAM2::Optimizer::OptimizeEssentialGraph(Map*, KeyFrame*, KeyFrame*, const KeyFrameAndPose&, const KeyFrameAndPose&, const map<KeyFrame*,
+ * set<KeyFrame*>>&, const bool&) (orb_object_slam/include/Optimizer.h, src/Optimizer.cc:2575-2836): the 7-dof pose graph LoopClosing::CorrectLoop runs over every key
+ * frame once a loop is accepted, and the correction of every map point after it.  Sim3 layout as in cs_sim3_optimization: tx ty tz qx qy qz qw s, never normalised.
+ *
+ * cs_essential_graph_create: vertices are the dense indices 0 .. n_vertices - 1 (the caller maps mnId); edge e is an EdgeSim3 with vertex 0 = edge_i[e] (the key
+ * frame the reference is visiting) and vertex 1 = edge_j[e], in the order the reference inserts them; edge_kind[e] = 0 for a loop-connection edge (:2645-2673, the
+ * measurement from vScw on both ends), 1 for a spanning-tree, stored-loop or covisibility edge (:2676-2776, each end from NonCorrectedSim3 where it has an entry);
+ * fixed_vertex is pLoopKF (:2628-2629); fix_scale is bFixScale.  Everything that depends on the structure alone is done here, once, on the host: incidence lists in
+ * edge order, one slot per connected pair, a minimum-degree order, the elimination tree with its level sets and the structure of L.
+ * CS_ERR_BAD_ARG: n_vertices < 2, n_edges < 1, an index out of range, edge_i[e] == edge_j[e], edge_kind outside {0, 1}.
+ *
+ * cs_essential_graph_optimize: Scw = vScw, the initial estimates (:2612-2626); Snc / has_nc = NonCorrectedSim3 (rows without an entry are not read).  The
+ * measurements Sji = Sjw * Swi are computed by the library.  `iterations` Levenberg-Marquardt iterations (the reference runs 20) with setUserLambdaInit(1e-16), g2o's
+ * numeric Jacobians (delta 1e-9) and information I.  Out: sim3_out n x 8 (the estimates; the fixed vertex as it came), Tiw_out n x 12 floats = the rows of
+ * [R | t / s] that Converter::toCvSE3 stores (:2794-2800), stats (nullable).  Per LM trial the host reads one record of four doubles. */
+#define CS_EG_MAX_TRIALS 256
+typedef struct cs_essential_graph cs_essential_graph;
+typedef struct cs_essential_graph_stats {
+    int iterations, trials, accepted, rejected; /* iterations entered; LM trials; of those, accepted and undone */
+    int levels, l_blocks, h_blocks;             /* height of the elimination tree; 7 x 7 blocks of L and of the lower triangle of H, diagonal included */
+    int launches_per_trial;
+    double chi2_first, chi2_last, lambda_last;
+    uint8_t trial_accepted[CS_EG_MAX_TRIALS];   /* the first CS_EG_MAX_TRIALS trials in order: 1 accepted, 0 undone */
+} cs_essential_graph_stats;
+int cs_essential_graph_create(cs_ctx *ctx, int n_vertices, int n_edges, const int *edge_i, const int *edge_j, const uint8_t *edge_kind, int fixed_vertex, int fix_scale,
+                              cs_essential_graph **out);
+int cs_essential_graph_optimize(cs_ctx *ctx, cs_essential_graph *eg, const double *Scw, const double *Snc, const uint8_t *has_nc, int iterations, double *sim3_out,
+                                float *Tiw_out, cs_essential_graph_stats *stats);
+void cs_essential_graph_destroy(cs_essential_graph *eg);
+/* The point correction of :2824-2831: P_out[p] = (float) correctedSwr.map(Srw.map(P[p])) with Srw = Scw[ref_vertex[p]] and correctedSwr = sim3_out[ref_vertex[p]].inverse();
+ * P is Converter::toVector3d of the float position, ref_vertex the index of nIDr (:2813-2822, the caller's choice).  UpdateNormalAndDepth stays with the caller.
+ * CS_ERR_BAD_ARG and no launch where a ref_vertex is out of range. */
+int cs_sim3_correct_points(cs_ctx *ctx, int n_points, const double *P, const int *ref_vertex, int n_vertices, const double *Scw, const double *sim3_out, float *P_out);
+/* Sim3::log (sim3.h:148-230) of n transforms -> n x 7 (omega, upsilon, sigma): a probe of the device function under the pose graph's error, for tests. */
+int cs_sim3_log(cs_ctx *ctx, int n, const double *sim3, double *log_out);
+
 /* ===================================================================== batch front-end runner
  * One pass of the per-frame path (ORBextractor::operator(), line_lbd_detect::detect_descrip_lines, detect_3d_cuboid::detect_cuboid --
  * what Tracking / main_obj.cpp call per frame, object_slam/src/main_obj.cpp:395-470) over a batch that is resident in HBM.  Handles

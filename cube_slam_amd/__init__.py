@@ -5,3 +5,4 @@ package is the thin host-side mirror of the reference interfaces used by tests a
 """
 from . import _lib  # noqa: F401
 from .stereo import ComputeStereoMatches, StereoMatcher  # noqa: F401
+from .bow import KeyFrameDatabase, ORBVocabulary  # noqa: F401

@@ -364,7 +364,7 @@ int cs_match_by_sim3(cs_ctx *ctx, cs_matcher *m1, cs_matcher *m2, const float *R
                      const uint8_t *skip2, const uint8_t *mp_desc2, const uint8_t *train_blocked2 /* nullable */, float fx, float fy, float cx, float cy, float log_scale_factor,
                      const float *scale_factors, int n_levels, float th, int *matches12, int *n_found, int *n_level_outside /* nullable */);
 /* ORBmatcher::SearchForTriangulation (ORBmatcher.cc:679-850).  node1 / node2: vocabulary node of every feature (the DBoW2 FeatureVector
- * built by KeyFrame::ComputeBoW, -1 = none; DBoW2 itself is out of scope); skip = the feature already has a map point (or is
+ * built by KeyFrame::ComputeBoW, -1 = none: the `node` array of cs_bow_transform); skip = the feature already has a map point (or is
  * not static); u_right < 0 = monocular; F12 row-major 3x3 (float), (ex, ey) the epipole of KF1's centre in KF2 (:686-692).
  * matches12[N1] = index in KF2 or -1 (vMatchedPairs = the pairs with matches12 >= 0). */
 int cs_match_for_triangulation(cs_ctx *ctx, const cs_keypoint *keys1Un, const uint8_t *desc1, int N1, const int *node1, const uint8_t *skip1, const float *u_right1,
@@ -372,7 +372,7 @@ int cs_match_for_triangulation(cs_ctx *ctx, const cs_keypoint *keys1Un, const ui
                                const float *F12, float ex, float ey, const float *scale_factors2, const float *level_sigma2_2, int n_levels, int only_stereo,
                                int check_orientation, int *matches12, int *nmatches);
 /* ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:171-310): node = vocabulary node of every feature
- * (-1 none; DBoW2 is out of scope); skipKF = no usable map point (NULL / bad / dynamic / not static); skipF (nullable) = !KeysStatic.
+ * (-1 none: the `node` array of cs_bow_transform); skipKF = no usable map point (NULL / bad / dynamic / not static); skipF (nullable) = !KeysStatic.
  * matchesF[NF] = index of the key-frame feature whose map point the frame feature receives, -1 none. */
 int cs_match_by_bow(cs_ctx *ctx, const cs_keypoint *keysKF, const uint8_t *descKF, int NK, const int *nodeKF, const uint8_t *skipKF, const cs_keypoint *keysF,
                     const uint8_t *descF, int NF, const int *nodeF, const uint8_t *skipF, float nnratio, int check_orientation, int *matchesF, int *nmatches);
@@ -693,6 +693,48 @@ int cs_associate_keypoints(cs_ctx *ctx, int n_frames, const int *kp_off, const f
 int cs_associate_cuboids(int n_cand, const int *cand_id, const int *cand_off, const int *cand_pts, int n_landmarks, const int *landmark_id, const uint8_t *landmark_bad,
                          int n_points, const int *pobs_off, const int *pobs_obj, const int *pobs_cnt, int *best_object, int *max_vote, int largest_shared_num_points_thres,
                          int *assoc, uint8_t *created, int upd_cap, int *upd_point, int *upd_obj, int *upd_cnt, int *n_upd);
+
+/* ===================================================================== place recognition: DBoW2 transform and key-frame database
+ * Replaces what comes before the loop-closing and relocalisation searches: Frame::ComputeBoW / KeyFrame::ComputeBoW (orb_object_slam/src/Frame.cc:537-544,
+ * KeyFrame.cc:81-90: TemplatedVocabulary::transform(features, v, fv, 4), Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1139-1271), the scores of
+ * KeyFrameDatabase::DetectLoopCandidates / DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:74-305) and of LoopClosing::DetectLoop's minScore loop
+ * (LoopClosing.cc:126-140: L1Scoring::score, ScoringObject.cpp:23-68).  Bit-exact: words, nodes, values and scores are the reference's, doubles as 64-bit patterns.
+ * Only what the reference's ORBvoc uses is supported: TF_IDF weighting with L1 scoring. */
+enum { CS_BOW_TF_IDF = 0, CS_BOW_TF = 1, CS_BOW_IDF = 2, CS_BOW_BINARY = 3 };                                                          /* DBoW2::WeightingType */
+enum { CS_BOW_L1_NORM = 0, CS_BOW_L2_NORM = 1, CS_BOW_CHI_SQUARE = 2, CS_BOW_KL = 3, CS_BOW_BHATTACHARYYA = 4, CS_BOW_DOT_PRODUCT = 5 }; /* DBoW2::ScoringType */
+typedef struct cs_bow_vocab cs_bow_vocab;
+typedef struct cs_bow_db cs_bow_db;
+/* The tree as TemplatedVocabulary::loadFromTextFile (:1350-1437) leaves it in m_nodes: node 0 is the root, parent[i] < i, children keep file order, word ids go to the flagged
+ * leaves in node-id order, desc = n_nodes x 32 bytes (the root's is not read), levelsup = what transform() is called with (the reference: 4).  CS_ERR_BAD_ARG with *out = NULL
+ * for a weighting / scoring other than TF_IDF / L1 and for what leaves the reference undefined: a leaf flag that disagrees with the node having no children, a leaf above
+ * level L - levelsup (> 0), k outside 2..20 or L outside 1..10, a parent id that is not smaller than the node's own; also for a node with more than k children. */
+int cs_bow_vocab_create(cs_ctx *ctx, int k, int L, int n_nodes, const int *parent, const uint8_t *is_leaf, const uint8_t *desc, const double *weight, int levelsup, int weighting,
+                        int scoring, cs_bow_vocab **out);
+/* The refusals of cs_bow_vocab_create alone (host code, needs no device): CS_OK or CS_ERR_BAD_ARG. */
+int cs_bow_vocab_check(int k, int L, int n_nodes, const int *parent, const uint8_t *is_leaf, int levelsup, int weighting, int scoring);
+int cs_bow_vocab_info(const cs_bow_vocab *v, int *k, int *L, int *n_nodes, int *n_words, int *levelsup); /* any pointer may be NULL */
+void cs_bow_vocab_destroy(cs_bow_vocab *v);
+/* transform() for a batch of frames: the features of frame f are desc[32 * offsets[f]] .. desc[32 * offsets[f + 1]) (offsets[0] = 0, at most 8192 per frame: CS_ERR_CAPACITY).
+ * Per feature: word[i] and node[i] (the node at level L - levelsup, the root where that is <= 0), both -1 where the word's weight is not > 0 ("stopped", :1169); node is the
+ * array cs_match_by_bow, cs_match_by_bow_kf and cs_match_for_triangulation take.  Per frame: the BowVector as bow_count[f] entries at offsets[f] of bow_word (ascending) and
+ * bow_value; the entries behind them, up to offsets[f + 1], are word -1, value 0. */
+int cs_bow_transform(cs_ctx *ctx, const cs_bow_vocab *v, int n_frames, const int *offsets, const uint8_t *desc, int *word, int *node, int *bow_count, int *bow_word,
+                     double *bow_value);
+/* L1Scoring::score(v1 = vector pair_a[p], v2 = vector pair_b[p]) of n_vec BowVectors given as off[n_vec + 1] / word (strictly ascending inside a vector) / value. */
+int cs_bow_score(cs_ctx *ctx, int n_vec, const int *off, const int *word, const double *value, int n_pairs, const int *pair_a, const int *pair_b, double *score);
+/* The BowVectors of the key frames, resident on the device, each with its id and the order in which it was added (KeyFrameDatabase::add / erase, KeyFrameDatabase.cc:38-66:
+ * erasing and adding again moves a key frame to the end of that order).  add of an id that is in the database is CS_ERR_BAD_ARG; erase of one that is not changes nothing. */
+int cs_bow_db_create(cs_ctx *ctx, cs_bow_db **out);
+int cs_bow_db_add(cs_ctx *ctx, cs_bow_db *db, long id, int n, const int *word, const double *value);
+int cs_bow_db_erase(cs_bow_db *db, long id);
+int cs_bow_db_clear(cs_bow_db *db);
+int cs_bow_db_size(const cs_bow_db *db, int *n_keyframes);
+/* For every (query, key frame) that share at least one word, queries ascending and key frames in add order inside a query: the key frame's id and its add-order number, the
+ * number of common words, the smallest common word id, and L1Scoring::score(query, key frame).  *n_out = their number; more than `cap`: CS_ERR_CAPACITY (*n_out is still set;
+ * n_query * cs_bow_db_size always suffices). */
+int cs_bow_db_query(cs_ctx *ctx, cs_bow_db *db, int n_query, const int *q_off, const int *q_word, const double *q_value, long cap, long *n_out, int *out_query, long *out_id,
+                    long *out_order, int *out_common, int *out_minword, double *out_score);
+void cs_bow_db_destroy(cs_bow_db *db);
 
 #ifdef __cplusplus
 }

@@ -69,29 +69,26 @@ int cs_associate_keypoints(cs_ctx *ctx, int n_frames, const int *kp_off, const f
     if (nk < 0 || nb < 0 || (nk && !kp_xy) || (nb && !boxes)) return CS_ERR_BAD_ARG;
     for (int f = 0; f < n_frames; f++) if (box_off[f + 1] - box_off[f] > MAX_BOXES || kp_off[f + 1] < kp_off[f] || box_off[f + 1] < box_off[f]) return CS_ERR_CAPACITY;
     CS_HIP(ctx, hipSetDevice(ctx->device));
+    cs_scratch sc(ctx);
     int *d_ko = nullptr, *d_bo = nullptr, *d_bx = nullptr, *d_as = nullptr; float *d_xy = nullptr; uint8_t *d_in = nullptr, *d_ov = nullptr;
-    int r = cs_dalloc(ctx, &d_ko, (size_t)n_frames + 1);
-    if (!r) r = cs_dalloc(ctx, &d_bo, (size_t)n_frames + 1);
-    if (!r) r = cs_dalloc(ctx, &d_bx, (size_t)std::max(nb, 1) * 4);
-    if (!r) r = cs_dalloc(ctx, &d_as, (size_t)std::max(nk, 1));
-    if (!r) r = cs_dalloc(ctx, &d_xy, (size_t)std::max(nk, 1) * 2);
-    if (!r) r = cs_dalloc(ctx, &d_in, (size_t)std::max(nk, 1));
-    if (!r) r = cs_dalloc(ctx, &d_ov, (size_t)std::max(nb, 1));
-    if (!r) r = cs_h2d(ctx, d_ko, kp_off, (size_t)n_frames + 1);
-    if (!r) r = cs_h2d(ctx, d_bo, box_off, (size_t)n_frames + 1);
-    if (!r && nb) r = cs_h2d(ctx, d_bx, boxes, (size_t)nb * 4);
-    if (!r && nk) r = cs_h2d(ctx, d_xy, kp_xy, (size_t)nk * 2);
-    if (!r) {
-        CS_LAUNCH(ctx, "assoc_keypoints", assoc_keypoints, dim3(n_frames), dim3(256), 0, d_ko, d_xy, d_bo, d_bx, enable_ground_height_scale, d_as, d_in, d_ov);
-        if (nk) r = cs_d2h(ctx, assoc, d_as, (size_t)nk);
-        if (!r && nk && inany) r = cs_d2h(ctx, inany, d_in, (size_t)nk);
-        if (!r && nb && overlapped) r = cs_d2h(ctx, overlapped, d_ov, (size_t)nb);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_ko, d_bo, d_bx, d_as, d_xy, d_in, d_ov};
-    for (void *p : ptrs) if (p) hipFree(p);
-    return r;
+    CS_TRY(sc.alloc(ctx, &d_ko, (size_t)n_frames + 1));
+    CS_TRY(sc.alloc(ctx, &d_bo, (size_t)n_frames + 1));
+    CS_TRY(sc.alloc(ctx, &d_bx, (size_t)std::max(nb, 1) * 4));
+    CS_TRY(sc.alloc(ctx, &d_as, (size_t)std::max(nk, 1)));
+    CS_TRY(sc.alloc(ctx, &d_xy, (size_t)std::max(nk, 1) * 2));
+    CS_TRY(sc.alloc(ctx, &d_in, (size_t)std::max(nk, 1)));
+    CS_TRY(sc.alloc(ctx, &d_ov, (size_t)std::max(nb, 1)));
+    CS_TRY(cs_h2d(ctx, d_ko, kp_off, (size_t)n_frames + 1));
+    CS_TRY(cs_h2d(ctx, d_bo, box_off, (size_t)n_frames + 1));
+    if (nb) CS_TRY(cs_h2d(ctx, d_bx, boxes, (size_t)nb * 4));
+    if (nk) CS_TRY(cs_h2d(ctx, d_xy, kp_xy, (size_t)nk * 2));
+    CS_LAUNCH(ctx, "assoc_keypoints", assoc_keypoints, dim3(n_frames), dim3(256), 0, d_ko, d_xy, d_bo, d_bx, enable_ground_height_scale, d_as, d_in, d_ov);
+    if (nk) CS_TRY(cs_d2h(ctx, assoc, d_as, (size_t)nk));
+    if (nk && inany) CS_TRY(cs_d2h(ctx, inany, d_in, (size_t)nk));
+    if (nb && overlapped) CS_TRY(cs_d2h(ctx, overlapped, d_ov, (size_t)nb));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 int cs_associate_cuboids(int n_cand, const int *cand_id, const int *cand_off, const int *cand_pts, int n_landmarks, const int *landmark_id, const uint8_t *landmark_bad,

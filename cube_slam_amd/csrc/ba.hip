@@ -1400,7 +1400,7 @@ struct cs_ba {
     int rank = 0, world = 1, n_slots = 0, max_col = 0, max_part = 0;
     cs_allreduce_fn allreduce = nullptr; void *ar_user = nullptr;
     const volatile unsigned char *stop8 = nullptr; // the caller's bool (setForceStopFlag)
-    std::vector<void *> owned;
+    cs_owner own;
     int *d_pose_off = nullptr, *d_pose_obs = nullptr, *d_pe_off = nullptr, *d_pe_list = nullptr, *d_slot_off = nullptr, *d_slot_perm = nullptr, *d_slot_dst = nullptr, *d_col_off = nullptr,
         *d_rows = nullptr, *d_pair_off = nullptr, *d_upd_tgt = nullptr, *d_pos = nullptr, *d_status = nullptr;
     int2 *d_trips = nullptr; uint8_t *d_slot_tr = nullptr;
@@ -1421,10 +1421,7 @@ struct cs_ba {
 
 namespace {
 template <class T> int dalloc_copy(cs_ctx *ctx, cs_ba *b, T **d, const T *h, size_t n) {
-    int r = cs_dalloc(ctx, d, n); if (r) return r;
-    b->owned.push_back(*d);
-    if (h && n) { r = cs_h2d(ctx, *d, h, n); if (r) return r; }
-    return CS_OK;
+    return h ? b->own.upload(ctx, d, h, n) : b->own.alloc(ctx, d, n); // no host array: a work block, not initialised
 }
 static double sum_partials(cs_ctx *ctx, cs_ba *b, int n, bool is_max = false) {
     b->h_partials.resize((size_t)std::max(n, 1));
@@ -1552,7 +1549,7 @@ extern "C" {
 void cs_ba_destroy(cs_ctx *ctx, cs_ba *b) {
     if (!b) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    for (void *p : b->owned) if (p) hipFree(p);
+    b->own.free_all(ctx);
     if (b->h_pin) hipHostFree(b->h_pin);
     if (b->ev_trial) hipEventDestroy(b->ev_trial);
     ba_cr_destroy(b->cr);
@@ -2107,39 +2104,37 @@ int cs_pose_optimization(cs_ctx *ctx, int n_frames, const int *edge_off, const d
     for (int f = 0; f < n_frames; f++) { fr[f].e0 = edge_off[f]; fr[f].e1 = edge_off[f + 1]; fr[f].fx = intrinsics[f * 5]; fr[f].fy = intrinsics[f * 5 + 1]; fr[f].cx = intrinsics[f * 5 + 2]; fr[f].cy = intrinsics[f * 5 + 3]; fr[f].bf = intrinsics[f * 5 + 4]; }
     PoseFrame *d_fr = nullptr; double *d_X = nullptr, *d_o = nullptr, *d_w = nullptr, *d_pi = nullptr, *d_po = nullptr, *d_err = nullptr; uint8_t *d_out = nullptr; int *d_ni = nullptr;
     const size_t ne1 = (size_t)std::max(ne, 1);
-    int r = cs_dalloc(ctx, &d_fr, (size_t)n_frames);
-    if (!r) r = cs_dalloc(ctx, &d_X, ne1 * 3); if (!r) r = cs_dalloc(ctx, &d_o, ne1 * 3); if (!r) r = cs_dalloc(ctx, &d_w, ne1); if (!r) r = cs_dalloc(ctx, &d_err, ne1 * 3);
-    if (!r) r = cs_dalloc(ctx, &d_pi, (size_t)n_frames * 7); if (!r) r = cs_dalloc(ctx, &d_po, (size_t)n_frames * 7); if (!r) r = cs_dalloc(ctx, &d_out, ne1); if (!r) r = cs_dalloc(ctx, &d_ni, (size_t)n_frames);
-    if (!r) r = cs_h2d(ctx, d_fr, fr.data(), fr.size());
-    if (!r && ne) { r = cs_h2d(ctx, d_X, Xw, (size_t)ne * 3); if (!r) r = cs_h2d(ctx, d_o, obs, (size_t)ne * 3); if (!r) r = cs_h2d(ctx, d_w, inv_sigma2, (size_t)ne); }
-    if (!r) r = cs_h2d(ctx, d_pi, pose_in, (size_t)n_frames * 7);
-    if (!r) {
-        ctx->begin("pose_opt_kernel");
-        hipLaunchKernelGGL(pose_opt_kernel, dim3(n_frames), dim3(256), 0, ctx->stream, d_fr, d_X, d_o, d_w, d_pi, d_po, d_out, d_ni, d_err);
-        ctx->end();
-        r = cs_d2h(ctx, pose_out, d_po, (size_t)n_frames * 7);
-        if (!r && ne) r = cs_d2h(ctx, outlier, d_out, (size_t)ne);
-        if (!r) r = cs_d2h(ctx, n_inliers, d_ni, (size_t)n_frames);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_fr, d_X, d_o, d_w, d_pi, d_po, d_err, d_out, d_ni};
-    for (void *q : ptrs) if (q) hipFree(q);
-    return r;
+    cs_scratch sc(ctx); // (after the host array: it waits for the copy out of it before it goes)
+    CS_TRY(sc.alloc(ctx, &d_fr, (size_t)n_frames));
+    CS_TRY(sc.alloc(ctx, &d_X, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_o, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_w, ne1)); CS_TRY(sc.alloc(ctx, &d_err, ne1 * 3));
+    CS_TRY(sc.alloc(ctx, &d_pi, (size_t)n_frames * 7)); CS_TRY(sc.alloc(ctx, &d_po, (size_t)n_frames * 7)); CS_TRY(sc.alloc(ctx, &d_out, ne1)); CS_TRY(sc.alloc(ctx, &d_ni, (size_t)n_frames));
+    CS_TRY(cs_h2d(ctx, d_fr, fr.data(), fr.size()));
+    if (ne) { CS_TRY(cs_h2d(ctx, d_X, Xw, (size_t)ne * 3)); CS_TRY(cs_h2d(ctx, d_o, obs, (size_t)ne * 3)); CS_TRY(cs_h2d(ctx, d_w, inv_sigma2, (size_t)ne)); }
+    CS_TRY(cs_h2d(ctx, d_pi, pose_in, (size_t)n_frames * 7));
+    ctx->begin("pose_opt_kernel");
+    hipLaunchKernelGGL(pose_opt_kernel, dim3(n_frames), dim3(256), 0, ctx->stream, d_fr, d_X, d_o, d_w, d_pi, d_po, d_out, d_ni, d_err);
+    ctx->end();
+    CS_TRY(cs_d2h(ctx, pose_out, d_po, (size_t)n_frames * 7));
+    if (ne) CS_TRY(cs_d2h(ctx, outlier, d_out, (size_t)ne));
+    CS_TRY(cs_d2h(ctx, n_inliers, d_ni, (size_t)n_frames));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 int cs_cuboid9_oplus(cs_ctx *ctx, int n, const double *cub, const double *upd, double *out) {
     if (!ctx || n < 0 || (n && (!cub || !upd || !out))) return CS_ERR_BAD_ARG;
     if (n == 0) return CS_OK;
     CS_HIP(ctx, hipSetDevice(ctx->device));
+    cs_scratch sc(ctx);
     double *d_c = nullptr, *d_u = nullptr, *d_o = nullptr;
-    int r = cs_dalloc(ctx, &d_c, (size_t)n * 10); if (!r) r = cs_dalloc(ctx, &d_u, (size_t)n * 9); if (!r) r = cs_dalloc(ctx, &d_o, (size_t)n * 10);
-    if (!r) r = cs_h2d(ctx, d_c, cub, (size_t)n * 10); if (!r) r = cs_h2d(ctx, d_u, upd, (size_t)n * 9);
-    if (!r) { hipLaunchKernelGGL(cub9_oplus_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, d_c, d_u, d_o); r = cs_d2h(ctx, out, d_o, (size_t)n * 10); }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    if (d_c) hipFree(d_c); if (d_u) hipFree(d_u); if (d_o) hipFree(d_o);
-    return r;
+    CS_TRY(sc.alloc(ctx, &d_c, (size_t)n * 10)); CS_TRY(sc.alloc(ctx, &d_u, (size_t)n * 9)); CS_TRY(sc.alloc(ctx, &d_o, (size_t)n * 10));
+    CS_TRY(cs_h2d(ctx, d_c, cub, (size_t)n * 10)); CS_TRY(cs_h2d(ctx, d_u, upd, (size_t)n * 9));
+    hipLaunchKernelGGL(cub9_oplus_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, d_c, d_u, d_o);
+    CS_TRY(cs_d2h(ctx, out, d_o, (size_t)n * 10));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 int cs_cuboid9_edge_linearize(cs_ctx *ctx, int n, const double *cam_Tcw, const double *cub_global, const double *cub_meas_local, double *err, double *Jcam, double *Jcub) {
@@ -2148,20 +2143,17 @@ int cs_cuboid9_edge_linearize(cs_ctx *ctx, int n, const double *cam_Tcw, const d
     CS_HIP(ctx, hipSetDevice(ctx->device));
     const int with_jac = Jcam != nullptr;
     double *d_T = nullptr, *d_g = nullptr, *d_m = nullptr, *d_e = nullptr, *d_jc = nullptr, *d_jq = nullptr;
-    int r = cs_dalloc(ctx, &d_T, (size_t)n * 7); if (!r) r = cs_dalloc(ctx, &d_g, (size_t)n * 10); if (!r) r = cs_dalloc(ctx, &d_m, (size_t)n * 10); if (!r) r = cs_dalloc(ctx, &d_e, (size_t)n * 9);
-    if (!r && with_jac) { r = cs_dalloc(ctx, &d_jc, (size_t)n * 54); if (!r) r = cs_dalloc(ctx, &d_jq, (size_t)n * 81); }
-    if (!r) r = cs_h2d(ctx, d_T, cam_Tcw, (size_t)n * 7); if (!r) r = cs_h2d(ctx, d_g, cub_global, (size_t)n * 10); if (!r) r = cs_h2d(ctx, d_m, cub_meas_local, (size_t)n * 10);
-    if (!r) {
-        const int nt = n * (with_jac ? 16 : 1);
-        hipLaunchKernelGGL(cub9_edge_kernel, dim3((nt + 63) / 64), dim3(64), 0, ctx->stream, n, with_jac, d_T, d_g, d_m, d_e, d_jc, d_jq);
-        r = cs_d2h(ctx, err, d_e, (size_t)n * 9);
-        if (!r && with_jac) { r = cs_d2h(ctx, Jcam, d_jc, (size_t)n * 54); if (!r) r = cs_d2h(ctx, Jcub, d_jq, (size_t)n * 81); }
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_T, d_g, d_m, d_e, d_jc, d_jq};
-    for (void *q : ptrs) if (q) hipFree(q);
-    return r;
+    cs_scratch sc(ctx);
+    CS_TRY(sc.alloc(ctx, &d_T, (size_t)n * 7)); CS_TRY(sc.alloc(ctx, &d_g, (size_t)n * 10)); CS_TRY(sc.alloc(ctx, &d_m, (size_t)n * 10)); CS_TRY(sc.alloc(ctx, &d_e, (size_t)n * 9));
+    if (with_jac) { CS_TRY(sc.alloc(ctx, &d_jc, (size_t)n * 54)); CS_TRY(sc.alloc(ctx, &d_jq, (size_t)n * 81)); }
+    CS_TRY(cs_h2d(ctx, d_T, cam_Tcw, (size_t)n * 7)); CS_TRY(cs_h2d(ctx, d_g, cub_global, (size_t)n * 10)); CS_TRY(cs_h2d(ctx, d_m, cub_meas_local, (size_t)n * 10));
+    const int nt = n * (with_jac ? 16 : 1);
+    hipLaunchKernelGGL(cub9_edge_kernel, dim3((nt + 63) / 64), dim3(64), 0, ctx->stream, n, with_jac, d_T, d_g, d_m, d_e, d_jc, d_jq);
+    CS_TRY(cs_d2h(ctx, err, d_e, (size_t)n * 9));
+    if (with_jac) { CS_TRY(cs_d2h(ctx, Jcam, d_jc, (size_t)n * 54)); CS_TRY(cs_d2h(ctx, Jcub, d_jq, (size_t)n * 81)); }
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 } // extern "C"

@@ -323,11 +323,12 @@ template <int BC> int cr_run(cs_ctx *ctx, const CrView &W) {
 } // namespace
 
 struct BaCr {
+    cs_ctx *ctx = nullptr; cs_owner own;
     int C = 0, Bc = 0, BCT = 0, M = 0;
     double *buf = nullptr;
     int *done = nullptr; int epoch = 0; // ba_cr_back_chain's flags (zeroed once; a solve's epoch never repeats)
 };
-void ba_cr_destroy(BaCr *w) { if (w) { if (w->buf) hipFree(w->buf); if (w->done) hipFree(w->done); delete w; } }
+void ba_cr_destroy(BaCr *w) { if (w) { w->own.free_all(w->ctx); delete w; } }
 // the elimination kernel of the super-block size the solve would instantiate keeps NBP * LDW + ... doubles in dynamic LDS (77 KB at 10 cameras per
 // super-block): a device that does not offer that much per workgroup takes the band solver instead
 bool ba_cr_supported(int C, int Bc) {
@@ -351,9 +352,9 @@ int ba_cr_solve(cs_ctx *ctx, BaCr **handle, int C, int Bc, const double *d_bandA
     if (!w || w->C != C || w->Bc != Bc) {
         ba_cr_destroy(w);
         w = new BaCr(); *handle = w;
-        w->C = C; w->Bc = Bc; w->BCT = BCT; w->M = M;
-        int rc = cs_dalloc(ctx, &w->buf, per * (size_t)M + 64); if (rc) return rc;
-        rc = cs_dalloc(ctx, &w->done, (size_t)M + 1); if (rc) return rc;
+        w->ctx = ctx; w->C = C; w->Bc = Bc; w->BCT = BCT; w->M = M;
+        CS_TRY(w->own.alloc(ctx, &w->buf, per * (size_t)M + 64));
+        CS_TRY(w->own.alloc(ctx, &w->done, (size_t)M + 1));
         CS_HIP(ctx, hipMemsetAsync(w->done, 0, sizeof(int) * ((size_t)M + 1), ctx->stream));
     }
     CrView V;

@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(1024) badyn_chol_tri(int n, const double *A, c
 struct cs_ba_dyn {
     DynG G;
     const volatile unsigned char *stop8 = nullptr; // the caller's bool (setForceStopFlag)
-    std::vector<void *> bufs;
+    cs_owner own;
     int n_edges = 0, n_vertices = 0, max_part = 0, n_slots = 0;
     double *d_Dg = nullptr, *d_rd = nullptr;
     size_t state_doubles = 0;
@@ -291,14 +291,11 @@ struct cs_ba_dyn {
 namespace {
 
 template <class T> int dyn_upload(cs_ctx *ctx, cs_ba_dyn *b, T **d, const T *h, size_t n) {
-    T *p = nullptr;
-    int r = cs_dalloc(ctx, &p, n);
-    if (r) return r;
-    b->bufs.push_back(p);
-    if (h && n) r = cs_h2d(ctx, p, h, n);
-    else if (!h) { hipError_t e = hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(T), ctx->stream); if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; } }
-    *d = p;
-    return r;
+    if (h) return b->own.upload(ctx, d, h, n);
+    CS_TRY(b->own.alloc(ctx, d, n)); // no host array: the block starts as zeros
+    const hipError_t e = hipMemsetAsync(*d, 0, std::max<size_t>(n, 1) * sizeof(T), ctx->stream);
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 template <class T> int dyn_upload(cs_ctx *ctx, cs_ba_dyn *b, const T **d, const T *h, size_t n) { return dyn_upload(ctx, b, const_cast<T **>(d), h, n); }
 
@@ -367,7 +364,7 @@ extern "C" {
 void cs_ba_dyn_destroy(cs_ctx *ctx, cs_ba_dyn *b) {
     if (!b) return;
     if (ctx) hipSetDevice(ctx->device);
-    for (void *p : b->bufs) if (p) hipFree(p);
+    b->own.free_all(ctx);
     delete b;
 }
 

@@ -203,6 +203,7 @@ bool csr_ok(int n, const int *off, const int *word) { // offsets from 0, not dec
 
 struct cs_bow_vocab {
     cs_ctx *ctx = nullptr;
+    cs_owner own;
     int k = 0, L = 0, n_nodes = 0, n_words = 0, levelsup = 0, max_children = 0;
     uint4 *d_slot_desc = nullptr;
     int *d_slot_node = nullptr, *d_node_first = nullptr, *d_node_nchild = nullptr, *d_node_word = nullptr;
@@ -212,6 +213,7 @@ struct cs_bow_vocab {
 struct cs_bow_db {
     struct entry { long id; long seq; long off; int cnt; };
     cs_ctx *ctx = nullptr;
+    cs_owner own;
     std::vector<entry> live; // in add order
     long next_seq = 0, used = 0, cap = 0, dead = 0;
     int *d_word = nullptr;
@@ -222,8 +224,7 @@ extern "C" {
 
 void cs_bow_vocab_destroy(cs_bow_vocab *v) {
     if (!v) return;
-    cs_dfree(v->ctx, v->d_slot_desc); cs_dfree(v->ctx, v->d_slot_node); cs_dfree(v->ctx, v->d_node_first); cs_dfree(v->ctx, v->d_node_nchild);
-    cs_dfree(v->ctx, v->d_node_word); cs_dfree(v->ctx, v->d_node_weight); cs_dfree(v->ctx, v->d_word_weight);
+    v->own.free_all(v->ctx);
     delete v;
 }
 
@@ -278,13 +279,13 @@ int cs_bow_vocab_create(cs_ctx *ctx, int k, int L, int n_nodes, const int *paren
     cs_bow_vocab *v = new cs_bow_vocab;
     v->ctx = ctx; v->k = k; v->L = L; v->n_nodes = n_nodes; v->n_words = n_words; v->levelsup = levelsup; v->max_children = max_children;
     const size_t ns = slot_node.size();
-    int r = cs_dalloc(ctx, &v->d_slot_desc, ns * 2);
-    if (r == CS_OK) r = cs_dalloc(ctx, &v->d_slot_node, ns);
-    if (r == CS_OK) r = cs_dalloc(ctx, &v->d_node_first, (size_t)n_nodes);
-    if (r == CS_OK) r = cs_dalloc(ctx, &v->d_node_nchild, (size_t)n_nodes);
-    if (r == CS_OK) r = cs_dalloc(ctx, &v->d_node_word, (size_t)n_nodes);
-    if (r == CS_OK) r = cs_dalloc(ctx, &v->d_node_weight, (size_t)n_nodes);
-    if (r == CS_OK) r = cs_dalloc(ctx, &v->d_word_weight, word_weight.size());
+    int r = v->own.alloc(ctx, &v->d_slot_desc, ns * 2);
+    if (r == CS_OK) r = v->own.alloc(ctx, &v->d_slot_node, ns);
+    if (r == CS_OK) r = v->own.alloc(ctx, &v->d_node_first, (size_t)n_nodes);
+    if (r == CS_OK) r = v->own.alloc(ctx, &v->d_node_nchild, (size_t)n_nodes);
+    if (r == CS_OK) r = v->own.alloc(ctx, &v->d_node_word, (size_t)n_nodes);
+    if (r == CS_OK) r = v->own.alloc(ctx, &v->d_node_weight, (size_t)n_nodes);
+    if (r == CS_OK) r = v->own.alloc(ctx, &v->d_word_weight, word_weight.size());
     if (r == CS_OK) r = cs_h2d(ctx, (uint8_t *)v->d_slot_desc, slot_desc.data(), slot_desc.size());
     if (r == CS_OK) r = cs_h2d(ctx, v->d_slot_node, slot_node.data(), ns);
     if (r == CS_OK) r = cs_h2d(ctx, v->d_node_first, first.data(), (size_t)n_nodes);
@@ -308,6 +309,39 @@ int cs_bow_vocab_info(const cs_bow_vocab *v, int *k, int *L, int *n_nodes, int *
     return CS_OK;
 }
 
+// the device part of cs_bow_transform; its blocks are released on every way out, after the stream has drained
+static int bow_transform_dev(cs_ctx *ctx, const cs_bow_vocab *v, int n_frames, const int *offsets, const uint8_t *desc, int max_n, long n, int *word, int *node, int *bow_count,
+                             int *bow_word, double *bow_value) {
+    cs_scratch sc(ctx);
+    uint4 *d_desc = nullptr;
+    int *d_off = nullptr, *d_word = nullptr, *d_node = nullptr, *d_cnt = nullptr, *d_bw = nullptr;
+    double *d_bv = nullptr;
+    CS_TRY(sc.alloc(ctx, &d_desc, (size_t)n * 2)); CS_TRY(sc.alloc(ctx, &d_off, (size_t)n_frames + 1)); CS_TRY(sc.alloc(ctx, &d_word, (size_t)n)); CS_TRY(sc.alloc(ctx, &d_node, (size_t)n));
+    CS_TRY(sc.alloc(ctx, &d_cnt, (size_t)n_frames)); CS_TRY(sc.alloc(ctx, &d_bw, (size_t)n)); CS_TRY(sc.alloc(ctx, &d_bv, (size_t)n));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)d_desc, desc, (size_t)n * 32)); CS_TRY(cs_h2d(ctx, d_off, offsets, (size_t)n_frames + 1));
+    if (n > 0) {
+        CS_HIP(ctx, hipMemsetAsync(d_bw, 0xff, (size_t)n * sizeof(int), ctx->stream)); // entries behind bow_count[f]: word -1, value 0
+        CS_HIP(ctx, hipMemsetAsync(d_bv, 0, (size_t)n * sizeof(double), ctx->stream));
+        const int nid_level = v->L - v->levelsup;
+        if (v->max_children <= 16) {
+            const unsigned grid = (unsigned)((n * 16 + 255) / 256);
+            CS_LAUNCH(ctx, "bow_descend", bow_descend<16>, dim3(grid), dim3(256), 0, v->d_slot_desc, v->d_slot_node, v->d_node_first, v->d_node_nchild, v->d_node_word,
+                      v->d_node_weight, nid_level, n, d_desc, d_word, d_node);
+        } else {
+            const unsigned grid = (unsigned)((n * 32 + 255) / 256);
+            CS_LAUNCH(ctx, "bow_descend", bow_descend<32>, dim3(grid), dim3(256), 0, v->d_slot_desc, v->d_slot_node, v->d_node_first, v->d_node_nchild, v->d_node_word,
+                      v->d_node_weight, nid_level, n, d_desc, d_word, d_node);
+        }
+    }
+    int P = 256;
+    while (P < max_n) P <<= 1;
+    CS_LAUNCH(ctx, "bow_accumulate", bow_accumulate, dim3(n_frames), dim3(256), (size_t)(P + 256) * sizeof(int), d_off, d_word, v->d_word_weight, P, d_cnt, d_bw, d_bv);
+    CS_HIP(ctx, hipGetLastError());
+    CS_TRY(cs_d2h(ctx, word, d_word, (size_t)n)); CS_TRY(cs_d2h(ctx, node, d_node, (size_t)n)); CS_TRY(cs_d2h(ctx, bow_count, d_cnt, (size_t)n_frames));
+    CS_TRY(cs_d2h(ctx, bow_word, d_bw, (size_t)n)); CS_TRY(cs_d2h(ctx, bow_value, d_bv, (size_t)n));
+    return sc.drain();
+}
+
 int cs_bow_transform(cs_ctx *ctx, const cs_bow_vocab *v, int n_frames, const int *offsets, const uint8_t *desc, int *word, int *node, int *bow_count, int *bow_word,
                      double *bow_value) {
     if (!ctx || !v || n_frames < 0 || !offsets || !word || !node || !bow_count || !bow_word || !bow_value) return CS_ERR_BAD_ARG;
@@ -321,45 +355,24 @@ int cs_bow_transform(cs_ctx *ctx, const cs_bow_vocab *v, int n_frames, const int
     const long n = offsets[n_frames];
     if (n_frames == 0) return CS_OK;
     if (n > 0 && !desc) return CS_ERR_BAD_ARG;
-    uint4 *d_desc = nullptr;
-    int *d_off = nullptr, *d_word = nullptr, *d_node = nullptr, *d_cnt = nullptr, *d_bw = nullptr;
-    double *d_bv = nullptr;
-    auto body = [&]() -> int {
-        int r;
-        if ((r = cs_dalloc(ctx, &d_desc, (size_t)n * 2)) != CS_OK || (r = cs_dalloc(ctx, &d_off, (size_t)n_frames + 1)) != CS_OK || (r = cs_dalloc(ctx, &d_word, (size_t)n)) != CS_OK ||
-            (r = cs_dalloc(ctx, &d_node, (size_t)n)) != CS_OK || (r = cs_dalloc(ctx, &d_cnt, (size_t)n_frames)) != CS_OK || (r = cs_dalloc(ctx, &d_bw, (size_t)n)) != CS_OK ||
-            (r = cs_dalloc(ctx, &d_bv, (size_t)n)) != CS_OK)
-            return r;
-        if ((r = cs_h2d(ctx, (uint8_t *)d_desc, desc, (size_t)n * 32)) != CS_OK || (r = cs_h2d(ctx, d_off, offsets, (size_t)n_frames + 1)) != CS_OK) return r;
-        if (n > 0) {
-            CS_HIP(ctx, hipMemsetAsync(d_bw, 0xff, (size_t)n * sizeof(int), ctx->stream)); // entries behind bow_count[f]: word -1, value 0
-            CS_HIP(ctx, hipMemsetAsync(d_bv, 0, (size_t)n * sizeof(double), ctx->stream));
-            const int nid_level = v->L - v->levelsup;
-            if (v->max_children <= 16) {
-                const unsigned grid = (unsigned)((n * 16 + 255) / 256);
-                CS_LAUNCH(ctx, "bow_descend", bow_descend<16>, dim3(grid), dim3(256), 0, v->d_slot_desc, v->d_slot_node, v->d_node_first, v->d_node_nchild, v->d_node_word,
-                          v->d_node_weight, nid_level, n, d_desc, d_word, d_node);
-            } else {
-                const unsigned grid = (unsigned)((n * 32 + 255) / 256);
-                CS_LAUNCH(ctx, "bow_descend", bow_descend<32>, dim3(grid), dim3(256), 0, v->d_slot_desc, v->d_slot_node, v->d_node_first, v->d_node_nchild, v->d_node_word,
-                          v->d_node_weight, nid_level, n, d_desc, d_word, d_node);
-            }
-        }
-        int P = 256;
-        while (P < max_n) P <<= 1;
-        CS_LAUNCH(ctx, "bow_accumulate", bow_accumulate, dim3(n_frames), dim3(256), (size_t)(P + 256) * sizeof(int), d_off, d_word, v->d_word_weight, P, d_cnt, d_bw, d_bv);
-        CS_HIP(ctx, hipGetLastError());
-        if ((r = cs_d2h(ctx, word, d_word, (size_t)n)) != CS_OK || (r = cs_d2h(ctx, node, d_node, (size_t)n)) != CS_OK || (r = cs_d2h(ctx, bow_count, d_cnt, (size_t)n_frames)) != CS_OK ||
-            (r = cs_d2h(ctx, bow_word, d_bw, (size_t)n)) != CS_OK || (r = cs_d2h(ctx, bow_value, d_bv, (size_t)n)) != CS_OK)
-            return r;
-        CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return CS_OK;
-    };
-    const int r = body();
-    if (r != CS_OK) (void)hipStreamSynchronize(ctx->stream);
-    cs_dfree(ctx, d_desc); cs_dfree(ctx, d_off); cs_dfree(ctx, d_word); cs_dfree(ctx, d_node); cs_dfree(ctx, d_cnt); cs_dfree(ctx, d_bw); cs_dfree(ctx, d_bv);
+    const int r = bow_transform_dev(ctx, v, n_frames, offsets, desc, max_n, n, word, node, bow_count, bow_word, bow_value);
     ctx->flush();
     return r;
+}
+
+static int bow_score_dev(cs_ctx *ctx, int n_vec, const int *off, const int *word, const double *value, int n_pairs, const int *pair_a, const int *pair_b, double *score) {
+    const size_t nw = (size_t)off[n_vec];
+    cs_scratch sc(ctx);
+    int *d_off = nullptr, *d_word = nullptr, *d_pa = nullptr, *d_pb = nullptr;
+    double *d_value = nullptr, *d_score = nullptr;
+    CS_TRY(sc.alloc(ctx, &d_off, (size_t)n_vec + 1)); CS_TRY(sc.alloc(ctx, &d_word, nw)); CS_TRY(sc.alloc(ctx, &d_value, nw));
+    CS_TRY(sc.alloc(ctx, &d_pa, (size_t)n_pairs)); CS_TRY(sc.alloc(ctx, &d_pb, (size_t)n_pairs)); CS_TRY(sc.alloc(ctx, &d_score, (size_t)n_pairs));
+    CS_TRY(cs_h2d(ctx, d_off, off, (size_t)n_vec + 1)); CS_TRY(cs_h2d(ctx, d_word, word, nw)); CS_TRY(cs_h2d(ctx, d_value, value, nw));
+    CS_TRY(cs_h2d(ctx, d_pa, pair_a, (size_t)n_pairs)); CS_TRY(cs_h2d(ctx, d_pb, pair_b, (size_t)n_pairs));
+    CS_LAUNCH(ctx, "bow_score_pairs", bow_score_pairs, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, d_off, d_word, d_value, n_pairs, d_pa, d_pb, d_score);
+    CS_HIP(ctx, hipGetLastError());
+    CS_TRY(cs_d2h(ctx, score, d_score, (size_t)n_pairs));
+    return sc.drain();
 }
 
 int cs_bow_score(cs_ctx *ctx, int n_vec, const int *off, const int *word, const double *value, int n_pairs, const int *pair_a, const int *pair_b, double *score) {
@@ -368,26 +381,7 @@ int cs_bow_score(cs_ctx *ctx, int n_vec, const int *off, const int *word, const 
     if (!pair_a || !pair_b || !score || (off[n_vec] > 0 && (!word || !value)) || !csr_ok(n_vec, off, word)) { ctx->err = "cs_bow_score: null array or unsorted vector"; return CS_ERR_BAD_ARG; }
     for (int p = 0; p < n_pairs; ++p)
         if (pair_a[p] < 0 || pair_a[p] >= n_vec || pair_b[p] < 0 || pair_b[p] >= n_vec) { ctx->err = "cs_bow_score: pair index outside the vectors"; return CS_ERR_BAD_ARG; }
-    const size_t nw = (size_t)off[n_vec];
-    int *d_off = nullptr, *d_word = nullptr, *d_pa = nullptr, *d_pb = nullptr;
-    double *d_value = nullptr, *d_score = nullptr;
-    auto body = [&]() -> int {
-        int r;
-        if ((r = cs_dalloc(ctx, &d_off, (size_t)n_vec + 1)) != CS_OK || (r = cs_dalloc(ctx, &d_word, nw)) != CS_OK || (r = cs_dalloc(ctx, &d_value, nw)) != CS_OK ||
-            (r = cs_dalloc(ctx, &d_pa, (size_t)n_pairs)) != CS_OK || (r = cs_dalloc(ctx, &d_pb, (size_t)n_pairs)) != CS_OK || (r = cs_dalloc(ctx, &d_score, (size_t)n_pairs)) != CS_OK)
-            return r;
-        if ((r = cs_h2d(ctx, d_off, off, (size_t)n_vec + 1)) != CS_OK || (r = cs_h2d(ctx, d_word, word, nw)) != CS_OK || (r = cs_h2d(ctx, d_value, value, nw)) != CS_OK ||
-            (r = cs_h2d(ctx, d_pa, pair_a, (size_t)n_pairs)) != CS_OK || (r = cs_h2d(ctx, d_pb, pair_b, (size_t)n_pairs)) != CS_OK)
-            return r;
-        CS_LAUNCH(ctx, "bow_score_pairs", bow_score_pairs, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, d_off, d_word, d_value, n_pairs, d_pa, d_pb, d_score);
-        CS_HIP(ctx, hipGetLastError());
-        if ((r = cs_d2h(ctx, score, d_score, (size_t)n_pairs)) != CS_OK) return r;
-        CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return CS_OK;
-    };
-    const int r = body();
-    if (r != CS_OK) (void)hipStreamSynchronize(ctx->stream);
-    cs_dfree(ctx, d_off); cs_dfree(ctx, d_word); cs_dfree(ctx, d_value); cs_dfree(ctx, d_pa); cs_dfree(ctx, d_pb); cs_dfree(ctx, d_score);
+    const int r = bow_score_dev(ctx, n_vec, off, word, value, n_pairs, pair_a, pair_b, score);
     ctx->flush();
     return r;
 }
@@ -403,8 +397,7 @@ int cs_bow_db_create(cs_ctx *ctx, cs_bow_db **out) {
 
 void cs_bow_db_destroy(cs_bow_db *db) {
     if (!db) return;
-    if (db->d_word) hipFree(db->d_word);
-    if (db->d_value) hipFree(db->d_value);
+    db->own.free_all(db->ctx);
     delete db;
 }
 
@@ -417,8 +410,8 @@ static int bow_db_reserve(cs_ctx *ctx, cs_bow_db *db, long extra) {
     const long cap = std::max(2 * need, 1L << 16);
     int *nw = nullptr;
     double *nv = nullptr;
-    CS_HIP(ctx, hipMalloc((void **)&nw, (size_t)cap * sizeof(int)));
-    if (hipMalloc((void **)&nv, (size_t)cap * sizeof(double)) != hipSuccess) { hipFree(nw); ctx->err = "cs_bow_db_add: out of device memory"; return CS_ERR_NOMEM; }
+    CS_TRY(db->own.alloc(ctx, &nw, (size_t)cap));
+    if (db->own.alloc(ctx, &nv, (size_t)cap) != CS_OK) { db->own.free_one(ctx, nw); ctx->err = "cs_bow_db_add: out of device memory"; return CS_ERR_NOMEM; }
     long at = 0;
     hipError_t e = hipSuccess;
     for (auto &en : db->live) {
@@ -428,8 +421,8 @@ static int bow_db_reserve(cs_ctx *ctx, cs_bow_db *db, long extra) {
         at += en.cnt;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (db->d_word) hipFree(db->d_word);
-    if (db->d_value) hipFree(db->d_value);
+    db->own.free_one(ctx, db->d_word); // (the copies out of the old pair have drained)
+    db->own.free_one(ctx, db->d_value);
     db->d_word = nw; db->d_value = nv; db->cap = cap; db->used = at; db->dead = 0;
     CS_HIP(ctx, e);
     return CS_OK;
@@ -477,6 +470,26 @@ int cs_bow_db_size(const cs_bow_db *db, int *n_keyframes) {
     return CS_OK;
 }
 
+// the device part of cs_bow_db_query: common words, smallest common word and score of every (query, key frame) pair into the host arrays
+static int bow_query_dev(cs_ctx *ctx, const cs_bow_db *db, int n_query, const int *q_off, const int *q_word, const double *q_value, const long *h_off, const int *h_cnt, int *h_common,
+                         int *h_min, double *h_score) {
+    const int nk = (int)db->live.size();
+    const size_t nw = (size_t)q_off[n_query], np = (size_t)n_query * nk;
+    cs_scratch sc(ctx);
+    int *d_qoff = nullptr, *d_qw = nullptr, *d_cnt = nullptr, *d_common = nullptr, *d_min = nullptr;
+    long *d_off = nullptr;
+    double *d_qv = nullptr, *d_score = nullptr;
+    CS_TRY(sc.alloc(ctx, &d_qoff, (size_t)n_query + 1)); CS_TRY(sc.alloc(ctx, &d_qw, nw)); CS_TRY(sc.alloc(ctx, &d_qv, nw)); CS_TRY(sc.alloc(ctx, &d_off, (size_t)nk));
+    CS_TRY(sc.alloc(ctx, &d_cnt, (size_t)nk)); CS_TRY(sc.alloc(ctx, &d_common, np)); CS_TRY(sc.alloc(ctx, &d_min, np)); CS_TRY(sc.alloc(ctx, &d_score, np));
+    CS_TRY(cs_h2d(ctx, d_qoff, q_off, (size_t)n_query + 1)); CS_TRY(cs_h2d(ctx, d_qw, q_word, nw)); CS_TRY(cs_h2d(ctx, d_qv, q_value, nw));
+    CS_TRY(cs_h2d(ctx, d_off, h_off, (size_t)nk)); CS_TRY(cs_h2d(ctx, d_cnt, h_cnt, (size_t)nk));
+    CS_LAUNCH(ctx, "bow_query", bow_query, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, n_query, d_qoff, d_qw, d_qv, nk, d_off, d_cnt, db->d_word, db->d_value, d_common, d_min,
+              d_score);
+    CS_HIP(ctx, hipGetLastError());
+    CS_TRY(cs_d2h(ctx, h_common, d_common, np)); CS_TRY(cs_d2h(ctx, h_min, d_min, np)); CS_TRY(cs_d2h(ctx, h_score, d_score, np));
+    return sc.drain();
+}
+
 int cs_bow_db_query(cs_ctx *ctx, cs_bow_db *db, int n_query, const int *q_off, const int *q_word, const double *q_value, long cap, long *n_out, int *out_query, long *out_id,
                     long *out_order, int *out_common, int *out_minword, double *out_score) {
     if (!ctx || !db || n_query < 0 || !q_off || !n_out || cap < 0) return CS_ERR_BAD_ARG;
@@ -485,35 +498,13 @@ int cs_bow_db_query(cs_ctx *ctx, cs_bow_db *db, int n_query, const int *q_off, c
     if (n_query == 0 || nk == 0) return CS_OK;
     if ((q_off[n_query] > 0 && (!q_word || !q_value)) || !csr_ok(n_query, q_off, q_word)) { ctx->err = "cs_bow_db_query: null array or unsorted query vector"; return CS_ERR_BAD_ARG; }
     if (cap > 0 && (!out_query || !out_id || !out_order || !out_common || !out_minword || !out_score)) return CS_ERR_BAD_ARG;
-    const size_t nw = (size_t)q_off[n_query], np = (size_t)n_query * nk;
+    const size_t np = (size_t)n_query * nk;
     std::vector<long> h_off(nk);
     std::vector<int> h_cnt(nk);
     for (int i = 0; i < nk; ++i) { h_off[i] = db->live[i].off; h_cnt[i] = db->live[i].cnt; }
     std::vector<int> h_common(np), h_min(np);
     std::vector<double> h_score(np);
-    int *d_qoff = nullptr, *d_qw = nullptr, *d_cnt = nullptr, *d_common = nullptr, *d_min = nullptr;
-    long *d_off = nullptr;
-    double *d_qv = nullptr, *d_score = nullptr;
-    auto body = [&]() -> int {
-        int r;
-        if ((r = cs_dalloc(ctx, &d_qoff, (size_t)n_query + 1)) != CS_OK || (r = cs_dalloc(ctx, &d_qw, nw)) != CS_OK || (r = cs_dalloc(ctx, &d_qv, nw)) != CS_OK ||
-            (r = cs_dalloc(ctx, &d_off, (size_t)nk)) != CS_OK || (r = cs_dalloc(ctx, &d_cnt, (size_t)nk)) != CS_OK || (r = cs_dalloc(ctx, &d_common, np)) != CS_OK ||
-            (r = cs_dalloc(ctx, &d_min, np)) != CS_OK || (r = cs_dalloc(ctx, &d_score, np)) != CS_OK)
-            return r;
-        if ((r = cs_h2d(ctx, d_qoff, q_off, (size_t)n_query + 1)) != CS_OK || (r = cs_h2d(ctx, d_qw, q_word, nw)) != CS_OK || (r = cs_h2d(ctx, d_qv, q_value, nw)) != CS_OK ||
-            (r = cs_h2d(ctx, d_off, h_off.data(), (size_t)nk)) != CS_OK || (r = cs_h2d(ctx, d_cnt, h_cnt.data(), (size_t)nk)) != CS_OK)
-            return r;
-        CS_LAUNCH(ctx, "bow_query", bow_query, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, n_query, d_qoff, d_qw, d_qv, nk, d_off, d_cnt, db->d_word, db->d_value, d_common, d_min,
-                  d_score);
-        CS_HIP(ctx, hipGetLastError());
-        if ((r = cs_d2h(ctx, h_common.data(), d_common, np)) != CS_OK || (r = cs_d2h(ctx, h_min.data(), d_min, np)) != CS_OK || (r = cs_d2h(ctx, h_score.data(), d_score, np)) != CS_OK)
-            return r;
-        CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return CS_OK;
-    };
-    const int r = body();
-    if (r != CS_OK) (void)hipStreamSynchronize(ctx->stream);
-    cs_dfree(ctx, d_qoff); cs_dfree(ctx, d_qw); cs_dfree(ctx, d_qv); cs_dfree(ctx, d_off); cs_dfree(ctx, d_cnt); cs_dfree(ctx, d_common); cs_dfree(ctx, d_min); cs_dfree(ctx, d_score);
+    const int r = bow_query_dev(ctx, db, n_query, q_off, q_word, q_value, h_off.data(), h_cnt.data(), h_common.data(), h_min.data(), h_score.data());
     ctx->flush();
     if (r != CS_OK) return r;
     long m = 0;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -149,13 +150,16 @@ struct cs_ctx {
         (ctx)->end();                                                                 \
     } while (0)
 
+// The rule for device blocks: a block is obtained only through cs_dalloc (or a cs_owner, which calls it) and returned only through cs_dfree (or the owner).
+// cs_dalloc may hand out a block of the context's pool, which only cs_dfree knows how to give back; no file but this one and ctx.hip calls hipMalloc / hipFree
+// for a device block (the ring of frontend.hip excepted, see there).
 template <class T> static inline int cs_dalloc(cs_ctx *ctx, T **p, size_t n) {
     if (n == 0) n = 1;
     if (ctx->pooling) CS_HIP(ctx, ctx->pool_alloc((void **)p, n * sizeof(T)));
     else CS_HIP(ctx, hipMalloc((void **)p, n * sizeof(T)));
     return CS_OK;
 }
-static inline void cs_dfree(cs_ctx *ctx, void *p) { if (!p) return; if (ctx && !ctx->pool_live.empty()) ctx->pool_release(p); else hipFree(p); }
+static inline void cs_dfree(cs_ctx *ctx, void *p) { if (!p) return; if (ctx) ctx->pool_release(p); else hipFree(p); } // (pool_release frees what the pool does not know)
 template <class T> static inline int cs_h2d(cs_ctx *ctx, T *d, const T *h, size_t n) {
     if (n == 0) return CS_OK;
     CS_HIP(ctx, hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
@@ -166,6 +170,44 @@ template <class T> static inline int cs_d2h(cs_ctx *ctx, T *h, const T *d, size_
     CS_HIP(ctx, hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
     return CS_OK;
 }
+#define CS_TRY(call) do { const int r__ = (call); if (r__ != CS_OK) return r__; } while (0)
+
+// The device blocks of a handle or of one call.  Every block is allocated through alloc() and released by free_all(): there is no second list to keep.  The stream that
+// may still use a block must have drained before free_all() -- the destroy functions synchronise first, a call's scratch goes through cs_scratch.
+struct cs_owner {
+    std::vector<void *> blocks;
+    template <class T> int alloc(cs_ctx *ctx, T **p, size_t n) {
+        CS_TRY(cs_dalloc(ctx, p, n));
+        blocks.push_back(*p);
+        return CS_OK;
+    }
+    template <class T> int upload(cs_ctx *ctx, T **p, const T *h, size_t n) { // alloc() + an asynchronous copy of n elements from the host
+        CS_TRY(alloc(ctx, p, n));
+        return cs_h2d(ctx, *p, h, n);
+    }
+    void free_one(cs_ctx *ctx, void *p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); cs_dfree(ctx, p); }
+    void free_all(cs_ctx *ctx) { for (void *p : blocks) cs_dfree(ctx, p); blocks.clear(); }
+};
+// the scratch of one call: released on every way out of the call, after the stream has drained (drain() is the call's own wait for its results;
+// a call that keeps a wait of its own, for the error text it reports, sets `drained` behind it)
+struct cs_scratch : cs_owner {
+    cs_ctx *ctx; bool drained = false;
+    explicit cs_scratch(cs_ctx *c) : ctx(c) {}
+    int drain() { drained = true; CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); return CS_OK; }
+    ~cs_scratch() { if (!drained) hipStreamSynchronize(ctx->stream); free_all(ctx); }
+};
+// a device array that grows to what a call needs (each array has its OWN capacity: ADVICE r5 -- one cap shared by arrays of different needs let the smaller one overflow)
+template <class T> struct cs_dbuf {
+    T *p = nullptr; size_t cap = 0;
+    int grow(cs_ctx *ctx, cs_owner &own, size_t need) {
+        if (p && need <= cap) return CS_OK;
+        if (p) { own.free_one(ctx, p); p = nullptr; cap = 0; }
+        const size_t c = need + need / 4 + 64;
+        CS_TRY(own.alloc(ctx, &p, c));
+        cap = c;
+        return CS_OK;
+    }
+};
 // A host buffer in pinned memory for a recurring hand-over: the copy engine reads / writes it directly, where a pageable std::vector costs the
 // runtime a second copy through its staging buffer while the calling thread waits.  It only grows (a request beyond the capacity reallocates
 // and does not keep the contents); the owner calls release().  A copy into or out of it is asynchronous: synchronise before the host reads it

@@ -2390,13 +2390,12 @@ int cs_cuboid_batch_unit(cs_ctx *ctx, cs_cuboid_batch *b, int unit, int dims[12]
         r = cs_d2h(ctx, de.data(), b->d_derr + U.hyp_off, (size_t)n_hyp); if (r) return r;
         r = cs_d2h(ctx, ae.data(), b->d_aerr + U.hyp_off, (size_t)n_hyp); if (r) return r;
         { // the corners are not stored anywhere: rebuilt for this unit by the function the kernels use
+            cs_scratch sc(ctx); // (on the way out of this block it waits for the copy into `co`, then releases d_co)
             double *d_co = nullptr;
-            CS_HIP(ctx, hipMalloc((void **)&d_co, sizeof(double) * 16 * (size_t)std::max(1, n_hyp)));
+            CS_TRY(sc.alloc(ctx, &d_co, 16 * (size_t)std::max(1, n_hyp)));
             hipMemsetAsync(d_co, 0, sizeof(double) * 16 * (size_t)std::max(1, n_hyp), ctx->stream);
             if (n_hyp > 0) hipLaunchKernelGGL(cuboid_unit_corners, dim3((n_hyp + 255) / 256), dim3(256), 0, ctx->stream, b->d_units, unit, n_hyp, b->d_vp, b->d_flag, d_co);
             r = cs_d2h(ctx, co.data(), d_co, (size_t)n_hyp * 16);
-            hipStreamSynchronize(ctx->stream);
-            hipFree(d_co);
             if (r) return r;
         }
         r = cs_d2h(ctx, yw.data(), b->d_yaw + (long)U.frame * b->o.yaw_cap, (size_t)b->o.yaw_cap); if (r) return r;
@@ -2431,9 +2430,10 @@ int cs_cuboid_detect(cs_ctx *ctx, const uint8_t *img, int width, int height, int
         for (int y = 0; y < height; y++) memcpy(&gray[(size_t)y * width], img + (size_t)y * stride, (size_t)width);
     } else {
         CS_HIP(ctx, hipSetDevice(ctx->device));
+        cs_scratch sc(ctx); // released on every way out of this branch
         uint8_t *d_bgr = nullptr, *d_g = nullptr;
-        CS_HIP(ctx, hipMalloc((void **)&d_bgr, (size_t)stride * height));
-        if (hipMalloc((void **)&d_g, (size_t)width * height) != hipSuccess) { hipFree(d_bgr); return CS_ERR_NOMEM; }
+        CS_TRY(sc.alloc(ctx, &d_bgr, (size_t)stride * height));
+        if (sc.alloc(ctx, &d_g, (size_t)width * height) != CS_OK) return CS_ERR_NOMEM;
         hipError_t e = hipMemcpyAsync(d_bgr, img, (size_t)stride * height, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
             ctx->begin("cuboid_bgr2gray");
@@ -2442,8 +2442,7 @@ int cs_cuboid_detect(cs_ctx *ctx, const uint8_t *img, int width, int height, int
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(gray.data(), d_g, (size_t)width * height, hipMemcpyDeviceToHost, ctx->stream);
-        const hipError_t es = hipStreamSynchronize(ctx->stream);
-        hipFree(d_bgr); hipFree(d_g); // on every path
+        const hipError_t es = hipStreamSynchronize(ctx->stream); sc.drained = true;
         if (e == hipSuccess) e = es;
         if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
     }

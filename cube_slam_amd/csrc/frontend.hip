@@ -323,7 +323,7 @@ static void ring_free(FrameRing *R) {
     if (R->copy_out) { hipStreamSynchronize(R->copy_out); hipStreamDestroy(R->copy_out); }
     for (hipEvent_t e : {R->step_done, R->cub_done, R->results_out}) if (e) hipEventDestroy(e);
     if (R->h_status) hipHostFree(R->h_status);
-    for (uint8_t *p : R->d) if (p) hipFree(p);
+    for (uint8_t *p : R->d) if (p) hipFree(p); // (not cs_dalloc / cs_dfree: a slot is made and dropped with its events, in the ring's own order, with no context at hand)
     for (auto *v : {&R->uploaded, &R->used_main, &R->used_line}) for (hipEvent_t e : *v) if (e) hipEventDestroy(e);
     delete R;
 }

@@ -327,12 +327,9 @@ int cs_lbd_batch_desc(cs_ctx *ctx, const cs_keyline *d_kl, const int *d_line_fra
 
 namespace {
 struct Bufs { uint8_t *gray = nullptr, *blur = nullptr; uint32_t *dxy = nullptr; };
-static void free_bufs(Bufs &b) { if (b.gray) hipFree(b.gray); if (b.blur) hipFree(b.blur); if (b.dxy) hipFree(b.dxy); b = Bufs(); }
-static int run_maps(cs_ctx *ctx, const uint8_t *gray, int W, int H, int stride, Bufs &b) {
+static int run_maps(cs_ctx *ctx, cs_scratch &sc, const uint8_t *gray, int W, int H, int stride, Bufs &b) { // the maps of one image in blocks of the call's scratch
     const size_t N = (size_t)W * H;
-    int r = cs_dalloc(ctx, &b.gray, N); if (r) return r;
-    r = cs_dalloc(ctx, &b.blur, N); if (r) return r;
-    r = cs_dalloc(ctx, &b.dxy, N); if (r) return r;
+    CS_TRY(sc.alloc(ctx, &b.gray, N)); CS_TRY(sc.alloc(ctx, &b.blur, N)); CS_TRY(sc.alloc(ctx, &b.dxy, N));
     CS_HIP(ctx, hipMemcpy2DAsync(b.gray, (size_t)W, gray, (size_t)stride, (size_t)W, (size_t)H, hipMemcpyHostToDevice, ctx->stream));
     return cs_lbd_batch_maps(ctx, b.gray, W, H, 1, b.blur, b.dxy);
 }
@@ -343,8 +340,9 @@ extern "C" {
 int cs_lbd_maps(cs_ctx *ctx, const uint8_t *gray, int width, int height, int stride, uint8_t *blur, int16_t *dx, int16_t *dy) {
     if (!ctx || !gray || width < 8 || height < 8 || stride < width) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
+    cs_scratch sc(ctx); // (it waits for the stream on the way out, then releases the maps)
     Bufs b;
-    int r = run_maps(ctx, gray, width, height, stride, b);
+    int r = run_maps(ctx, sc, gray, width, height, stride, b);
     const size_t N = (size_t)width * height;
     if (!r && blur) r = cs_d2h(ctx, blur, b.blur, N);
     if (!r && (dx || dy)) {
@@ -353,8 +351,6 @@ int cs_lbd_maps(cs_ctx *ctx, const uint8_t *gray, int width, int height, int str
         hipStreamSynchronize(ctx->stream);
         if (!r) for (size_t i = 0; i < N; i++) { if (dx) dx[i] = (int16_t)(xy[i] & 0xffff); if (dy) dy[i] = (int16_t)(xy[i] >> 16); }
     }
-    hipStreamSynchronize(ctx->stream);
-    free_bufs(b);
     return r;
 }
 
@@ -363,23 +359,20 @@ int cs_lbd_compute(cs_ctx *ctx, const uint8_t *gray, int width, int height, int 
     if (n == 0) return CS_OK; // the reference prints "keypoint list is empty" and returns (:619-623)
     for (int i = 0; i < n; i++) if (keylines[i].numOfPixels < 0 || keylines[i].numOfPixels > 32767) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
+    cs_scratch sc(ctx);
     Bufs b;
-    int r = run_maps(ctx, gray, width, height, stride, b);
+    CS_TRY(run_maps(ctx, sc, gray, width, height, stride, b));
     cs_keyline *d_kl = nullptr; float *d_f = nullptr; uint8_t *d_desc = nullptr;
-    if (!r) r = cs_dalloc(ctx, &d_kl, (size_t)n);
-    if (!r) r = cs_dalloc(ctx, &d_desc, (size_t)n * 32);
-    if (!r && float_desc) r = cs_dalloc(ctx, &d_f, (size_t)n * 72);
-    if (!r) r = cs_h2d(ctx, d_kl, keylines, (size_t)n);
-    if (!r) {
-        r = cs_lbd_batch_desc(ctx, d_kl, nullptr, n, b.dxy, width, height, d_desc, d_f);
-        if (!r) r = cs_d2h(ctx, desc, d_desc, (size_t)n * 32);
-        if (!r && float_desc) r = cs_d2h(ctx, float_desc, d_f, (size_t)n * 72);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    free_bufs(b);
-    if (d_kl) hipFree(d_kl); if (d_desc) hipFree(d_desc); if (d_f) hipFree(d_f);
-    return r;
+    CS_TRY(sc.alloc(ctx, &d_kl, (size_t)n));
+    CS_TRY(sc.alloc(ctx, &d_desc, (size_t)n * 32));
+    if (float_desc) CS_TRY(sc.alloc(ctx, &d_f, (size_t)n * 72));
+    CS_TRY(cs_h2d(ctx, d_kl, keylines, (size_t)n));
+    CS_TRY(cs_lbd_batch_desc(ctx, d_kl, nullptr, n, b.dxy, width, height, d_desc, d_f));
+    CS_TRY(cs_d2h(ctx, desc, d_desc, (size_t)n * 32));
+    if (float_desc) CS_TRY(cs_d2h(ctx, float_desc, d_f, (size_t)n * 72));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 int cs_lbd_match(cs_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, float dist_thres, int *query_idx, int *train_idx, int *distance, int *n_matches) {

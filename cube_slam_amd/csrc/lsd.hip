@@ -650,9 +650,9 @@ struct cs_lsd {
 int cs_lbd_batch_maps(cs_ctx *ctx, const uint8_t *d_gray, int W, int H, int F, uint8_t *d_blur, uint32_t *d_dxy);
 int cs_lbd_batch_desc(cs_ctx *ctx, const cs_keyline *d_kl, const int *d_line_frame, int n, const uint32_t *d_dxy, int W, int H, uint8_t *d_desc, float *d_f);
 
-static void lsd_free_lines(cs_lsd *l) {
+static void lsd_free_lines(cs_ctx *ctx, cs_lsd *l) {
     void *ptrs[] = {l->d_kl, l->d_line_frame, l->d_desc};
-    for (void *p : ptrs) if (p) hipFree(p);
+    for (void *p : ptrs) cs_dfree(ctx, p);
     l->d_kl = nullptr; l->d_line_frame = nullptr; l->d_desc = nullptr; l->line_cap = 0;
 }
 
@@ -700,7 +700,7 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
     int r;
     if (total > l->ccap) {
         void *old[] = {l->d_caddr, l->d_cdeg, l->d_ccs, l->d_cmod};
-        for (void *q : old) if (q) hipFree(q);
+        for (void *q : old) cs_dfree(ctx, q);
         l->d_caddr = nullptr; l->d_cdeg = nullptr; l->d_ccs = nullptr; l->d_cmod = nullptr; l->ccap = 0;
         const size_t cap = total + total / 16 + 4096; // (16 B per defined pixel, 75 M of them in a 1 024-frame batch: a sixteenth of headroom, a larger batch reallocates)
         r = cs_dalloc(ctx, &l->d_caddr, cap); if (r) return r;
@@ -814,7 +814,7 @@ static int lsd_run(cs_ctx *ctx, cs_lsd *l, int with_lbd) {
         const int nl = l->line_off[F];
         if (nl > 0) {
             if ((size_t)nl > l->line_cap) {
-                lsd_free_lines(l);
+                lsd_free_lines(ctx, l);
                 const size_t cap = (size_t)nl + nl / 4 + 256;
                 r = cs_dalloc(ctx, &l->d_kl, cap); if (r) return r;
                 r = cs_dalloc(ctx, &l->d_line_frame, cap); if (r) return r;
@@ -847,11 +847,11 @@ void cs_lsd_destroy(cs_ctx *ctx, cs_lsd *l) {
     if (!l) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
     void *ptrs[] = {l->d_gray, l->d_tmp, l->d_mod, l->d_ang, l->d_xofs, l->d_yofs, l->d_ax, l->d_ay, l->d_lblur, l->d_dxy};
-    for (void *p : ptrs) if (p) hipFree(p);
-    lsd_free_lines(l);
-    lsd_seq_destroy(l->seq);
+    for (void *p : ptrs) cs_dfree(ctx, p);
+    lsd_free_lines(ctx, l);
+    lsd_seq_destroy(ctx, l->seq);
     void *more[] = {l->d_seg_cnt, l->d_seg_base, l->d_blk_tot, l->d_caddr, l->d_cdeg, l->d_ccs, l->d_cmod};
-    for (void *p : more) if (p) hipFree(p);
+    for (void *p : more) cs_dfree(ctx, p);
     if (l->h_caddr) hipHostFree(l->h_caddr);
     if (l->h_cdeg) hipHostFree(l->h_cdeg);
     if (l->h_ccs) hipHostFree(l->h_ccs);

@@ -419,10 +419,10 @@ struct LsdSeq {
     float4 *d_line = nullptr;
     cs_pinned<int> h_base, h_status; cs_pinned<uint8_t> h_has; cs_pinned<float4> h_line; // the hand-overs to the host, pinned (lsd_seq_destroy frees them)
 };
-void lsd_seq_destroy(LsdSeq *r) {
+void lsd_seq_destroy(cs_ctx *ctx, LsdSeq *r) {
     if (!r) return;
     void *ptrs[] = {r->d_elist, r->d_ang32, r->d_order, r->pix_borrowed ? nullptr : r->d_pix, r->d_glist, r->d_cand_cnt, r->d_cand_base, r->d_status, r->d_frame_base, r->d_rect, r->d_lgt, r->d_has, r->d_line};
-    for (void *p : ptrs) if (p) hipFree(p);
+    for (void *p : ptrs) cs_dfree(ctx, p);
     r->h_base.release(); r->h_status.release(); r->h_has.release(); r->h_line.release();
     delete r;
 }
@@ -445,7 +445,7 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     int rc;
 #define RA_(call) do { rc = (call); if (rc != CS_OK) return rc; } while (0)
     if (!r || r->F < F || r->w != w || r->h != h) {
-        lsd_seq_destroy(r);
+        lsd_seq_destroy(ctx, r);
         r = new LsdSeq();
         *handle = r;
         r->F = F; r->w = w; r->h = h; r->cand_cap = 4096;
@@ -545,7 +545,7 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     lines.assign((size_t)F, {});
     if (n_cand == 0) return CS_OK;
     if ((size_t)n_cand > r->cap_lines) {
-        if (r->d_line) hipFree(r->d_line); if (r->d_has) hipFree(r->d_has);
+        cs_dfree(ctx, r->d_line); cs_dfree(ctx, r->d_has);
         r->d_line = nullptr; r->d_has = nullptr; r->cap_lines = 0;
         const size_t cap = (size_t)n_cand + n_cand / 4 + 1024;
         RA_(cs_dalloc(ctx, &r->d_line, cap)); RA_(cs_dalloc(ctx, &r->d_has, cap));

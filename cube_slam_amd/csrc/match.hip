@@ -693,40 +693,6 @@ struct NodeLists {
     }
 };
 
-#define MT_TRY(call) do { const int r__ = (call); if (r__ != CS_OK) return r__; } while (0)
-
-// The device blocks of a handle or of one call.  Every block is allocated through alloc() and released by free_all(): there is no second list to keep.  The stream that
-// may still use a block must have drained before free_all() -- the destroy functions synchronise first, a call's scratch goes through MtScratch.
-struct MtOwner {
-    std::vector<void *> blocks;
-    template <class T> int alloc(cs_ctx *ctx, T **p, size_t n) {
-        MT_TRY(cs_dalloc(ctx, p, n));
-        blocks.push_back(*p);
-        return CS_OK;
-    }
-    void free_one(cs_ctx *ctx, void *p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); cs_dfree(ctx, p); }
-    void free_all(cs_ctx *ctx) { for (void *p : blocks) cs_dfree(ctx, p); blocks.clear(); }
-};
-// the scratch of one call: released on every way out of the call, after the stream has drained (drain() is the call's own wait for its results)
-struct MtScratch : MtOwner {
-    cs_ctx *ctx; bool drained = false;
-    explicit MtScratch(cs_ctx *c) : ctx(c) {}
-    int drain() { drained = true; CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); return CS_OK; }
-    ~MtScratch() { if (!drained) hipStreamSynchronize(ctx->stream); free_all(ctx); }
-};
-// a device array that grows to what a call needs (each array has its OWN capacity: ADVICE r5 -- one cap shared by arrays of different needs let the smaller one overflow)
-template <class T> struct DBuf {
-    T *p = nullptr; size_t cap = 0;
-    int grow(cs_ctx *ctx, MtOwner &own, size_t need) {
-        if (p && need <= cap) return CS_OK;
-        if (p) { own.free_one(ctx, p); p = nullptr; cap = 0; }
-        const size_t c = need + need / 4 + 64;
-        MT_TRY(own.alloc(ctx, &p, c));
-        cap = c;
-        return CS_OK;
-    }
-};
-
 static FrameP make_frame(int N, float minX, float maxX, float minY, float maxY) {
     FrameP F; F.N = N; F.minX = minX; F.maxX = maxX; F.minY = minY; F.maxY = maxY;
     F.wInv = static_cast<float>(GRID_COLS) / static_cast<float>(maxX - minX); // Frame.cc:285-286
@@ -736,7 +702,7 @@ static FrameP make_frame(int N, float minX, float maxX, float minY, float maxY) 
 // What a search left in the two cursor words ([0] what the candidate arena should have held, [1] an error flag in its low word), after a wait for everything queued before.
 static int mt_cursor(cs_ctx *ctx, const unsigned long long *d_cursor, long cap, long *last_c) {
     unsigned long long cur[2] = {0, 0};
-    MT_TRY(cs_d2h(ctx, cur, d_cursor, 2));
+    CS_TRY(cs_d2h(ctx, cur, d_cursor, 2));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *last_c = (long)cur[0];
     if ((long)cur[0] > cap) { ctx->err = "matcher candidate capacity exceeded"; return CS_ERR_CAPACITY; }
@@ -747,7 +713,7 @@ static int mt_cursor(cs_ctx *ctx, const unsigned long long *d_cursor, long cap, 
 struct cs_matcher {
     int max_kp = 0, max_q = 0; long max_cand = 0;
     FrameP F{};
-    MtOwner own;
+    cs_owner own;
     std::vector<cs_keypoint> keys; // host copy of mvKeysUn (what set_frame_from_orb hands back; the vbPrevMatched update of SearchForInitialization)
     // the frame: per key point (max_kp) and its grid
     cs_keypoint *d_keys = nullptr; unsigned long long *d_desc = nullptr; float *d_ur = nullptr; uint8_t *d_tb = nullptr;
@@ -781,32 +747,32 @@ template <int V> static int mt_resolve(cs_ctx *ctx, const ResolveP &P, int n_pro
 // results (n_res ints and the match count behind them) + the cursor, one wait
 static int mt_finish(cs_ctx *ctx, cs_matcher *m, const int *d_res, int n_res, int *out, int *nmatches) {
     m->h_res.resize((size_t)n_res + 1);
-    MT_TRY(cs_d2h(ctx, m->h_res.data(), d_res, (size_t)n_res + 1));
-    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
+    CS_TRY(cs_d2h(ctx, m->h_res.data(), d_res, (size_t)n_res + 1));
+    CS_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
     if (n_res) memcpy(out, m->h_res.data(), sizeof(int) * (size_t)n_res);
     *nmatches = m->h_res[(size_t)n_res];
     return CS_OK;
 }
 static int mt_alloc(cs_ctx *ctx, cs_matcher *m) {
     const size_t nk = (size_t)m->max_kp, nq = (size_t)m->max_q;
-    MtOwner &o = m->own;
-    MT_TRY(o.alloc(ctx, &m->d_keys, nk)); MT_TRY(o.alloc(ctx, &m->d_desc, nk * 4)); MT_TRY(o.alloc(ctx, &m->d_ur, nk)); MT_TRY(o.alloc(ctx, &m->d_tb, nk));
-    MT_TRY(o.alloc(ctx, &m->d_cell_start, (size_t)NCELL + 1)); MT_TRY(o.alloc(ctx, &m->d_cell_items, nk)); MT_TRY(o.alloc(ctx, &m->d_kp_cell, nk)); MT_TRY(o.alloc(ctx, &m->d_tm, nk + 1));
-    MT_TRY(o.alloc(ctx, &m->d_cell_recs, nk));
-    MT_TRY(o.alloc(ctx, &m->d_q, nq)); MT_TRY(o.alloc(ctx, &m->d_qdesc, nq * 4)); MT_TRY(o.alloc(ctx, &m->d_cstart, nq));
-    MT_TRY(o.alloc(ctx, &m->d_ccount, nq)); MT_TRY(o.alloc(ctx, &m->d_qrec, nq + 1)); MT_TRY(o.alloc(ctx, &m->d_qm, nq + 1)); MT_TRY(o.alloc(ctx, &m->d_level, nq));
-    MT_TRY(o.alloc(ctx, &m->d_wp, nq * 3)); MT_TRY(o.alloc(ctx, &m->d_uv, nq * 2)); MT_TRY(o.alloc(ctx, &m->d_qur, nq)); MT_TRY(o.alloc(ctx, &m->d_ang, nq));
-    MT_TRY(o.alloc(ctx, &m->d_valid, nq)); MT_TRY(o.alloc(ctx, &m->d_blocks, nq));
-    MT_TRY(o.alloc(ctx, &m->d_T, (size_t)12)); MT_TRY(o.alloc(ctx, &m->d_sf, (size_t)32)); MT_TRY(o.alloc(ctx, &m->d_inv, (size_t)32));
-    MT_TRY(o.alloc(ctx, &m->d_nrm, nq * 3)); MT_TRY(o.alloc(ctx, &m->d_mind, nq)); MT_TRY(o.alloc(ctx, &m->d_maxd, nq)); MT_TRY(o.alloc(ctx, &m->d_nout, (size_t)2));
-    MT_TRY(o.alloc(ctx, &m->d_cands, (size_t)m->max_cand)); MT_TRY(o.alloc(ctx, &m->d_cursor, (size_t)2));
+    cs_owner &o = m->own;
+    CS_TRY(o.alloc(ctx, &m->d_keys, nk)); CS_TRY(o.alloc(ctx, &m->d_desc, nk * 4)); CS_TRY(o.alloc(ctx, &m->d_ur, nk)); CS_TRY(o.alloc(ctx, &m->d_tb, nk));
+    CS_TRY(o.alloc(ctx, &m->d_cell_start, (size_t)NCELL + 1)); CS_TRY(o.alloc(ctx, &m->d_cell_items, nk)); CS_TRY(o.alloc(ctx, &m->d_kp_cell, nk)); CS_TRY(o.alloc(ctx, &m->d_tm, nk + 1));
+    CS_TRY(o.alloc(ctx, &m->d_cell_recs, nk));
+    CS_TRY(o.alloc(ctx, &m->d_q, nq)); CS_TRY(o.alloc(ctx, &m->d_qdesc, nq * 4)); CS_TRY(o.alloc(ctx, &m->d_cstart, nq));
+    CS_TRY(o.alloc(ctx, &m->d_ccount, nq)); CS_TRY(o.alloc(ctx, &m->d_qrec, nq + 1)); CS_TRY(o.alloc(ctx, &m->d_qm, nq + 1)); CS_TRY(o.alloc(ctx, &m->d_level, nq));
+    CS_TRY(o.alloc(ctx, &m->d_wp, nq * 3)); CS_TRY(o.alloc(ctx, &m->d_uv, nq * 2)); CS_TRY(o.alloc(ctx, &m->d_qur, nq)); CS_TRY(o.alloc(ctx, &m->d_ang, nq));
+    CS_TRY(o.alloc(ctx, &m->d_valid, nq)); CS_TRY(o.alloc(ctx, &m->d_blocks, nq));
+    CS_TRY(o.alloc(ctx, &m->d_T, (size_t)12)); CS_TRY(o.alloc(ctx, &m->d_sf, (size_t)32)); CS_TRY(o.alloc(ctx, &m->d_inv, (size_t)32));
+    CS_TRY(o.alloc(ctx, &m->d_nrm, nq * 3)); CS_TRY(o.alloc(ctx, &m->d_mind, nq)); CS_TRY(o.alloc(ctx, &m->d_maxd, nq)); CS_TRY(o.alloc(ctx, &m->d_nout, (size_t)2));
+    CS_TRY(o.alloc(ctx, &m->d_cands, (size_t)m->max_cand)); CS_TRY(o.alloc(ctx, &m->d_cursor, (size_t)2));
     return CS_OK;
 }
 
 struct cs_match_stream {
-    MtOwner own;
-    DBuf<cs_keypoint> keys; DBuf<int> cell_start, cell_items, kp_cell, kfirst, qfirst, ccount, qrec, tm, nm; DBuf<CellRec> cell_recs; DBuf<long> cstart; DBuf<QueryS> q; DBuf<int2> cands;
-    DBuf<float> wp, T; DBuf<uint8_t> valid, blocks; DBuf<unsigned long long> qdesc;
+    cs_owner own;
+    cs_dbuf<cs_keypoint> keys; cs_dbuf<int> cell_start, cell_items, kp_cell, kfirst, qfirst, ccount, qrec, tm, nm; cs_dbuf<CellRec> cell_recs; cs_dbuf<long> cstart; cs_dbuf<QueryS> q; cs_dbuf<int2> cands;
+    cs_dbuf<float> wp, T; cs_dbuf<uint8_t> valid, blocks; cs_dbuf<unsigned long long> qdesc;
     float *d_sf = nullptr; unsigned long long *d_cursor = nullptr;
     std::vector<int> h_tm;
     long last_q = 0, last_c = 0;
@@ -846,8 +812,8 @@ int cs_matcher_set_frame(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *keysUn, 
     CS_HIP(ctx, hipSetDevice(ctx->device));
     m->F = make_frame(N, minX, maxX, minY, maxY);
     m->keys.assign(keysUn, keysUn + N);
-    MT_TRY(cs_h2d(ctx, m->d_keys, keysUn, (size_t)N));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_desc, desc, (size_t)N * 32));
+    CS_TRY(cs_h2d(ctx, m->d_keys, keysUn, (size_t)N));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_desc, desc, (size_t)N * 32));
     CS_LAUNCH(ctx, "match_grid", match_grid, dim3(1), dim3(1024), 0, m->F, m->d_keys, (const int *)nullptr, m->d_cell_start, m->d_cell_items, m->d_kp_cell, m->d_cell_recs);
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
@@ -873,7 +839,7 @@ int cs_matcher_set_frame_from_orb(cs_ctx *ctx, cs_matcher *m, const cs_orb *orb,
                                   float maxY, cs_keypoint *keysUn_out, int *n_out) {
     if (!ctx || !m || !orb || !K4 || !(maxX > minX) || !(maxY > minY)) return CS_ERR_BAD_ARG;
     const cs_keypoint *d_k = nullptr; const unsigned long long *d_d = nullptr; int N = 0;
-    MT_TRY(cs_orb_device_frame(orb, frame, &d_k, &d_d, &N));
+    CS_TRY(cs_orb_device_frame(orb, frame, &d_k, &d_d, &N));
     if (N > m->max_kp) return CS_ERR_CAPACITY;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     m->F = make_frame(N, minX, maxX, minY, maxY);
@@ -887,7 +853,7 @@ int cs_matcher_set_frame_from_orb(cs_ctx *ctx, cs_matcher *m, const cs_orb *orb,
     // every search takes what it needs of a train key point from the device copy
     if (keysUn_out) {
         m->keys.resize((size_t)N);
-        MT_TRY(cs_d2h(ctx, m->keys.data(), m->d_keys, (size_t)N));
+        CS_TRY(cs_d2h(ctx, m->keys.data(), m->d_keys, (size_t)N));
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(keysUn_out, m->keys.data(), sizeof(cs_keypoint) * (size_t)N);
     } else m->keys.clear();
@@ -899,16 +865,16 @@ int cs_matcher_features_in_area(cs_ctx *ctx, cs_matcher *m, float x, float y, fl
     if (!ctx || !m || !n) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     QueryS Q{x, y, r, minLevel, maxLevel, 1, 0};
-    MT_TRY(cs_h2d(ctx, m->d_q, &Q, 1));
-    MT_TRY(mt_candidates(ctx, m, 1, false));
+    CS_TRY(cs_h2d(ctx, m->d_q, &Q, 1));
+    CS_TRY(mt_candidates(ctx, m, 1, false));
     long start = 0; int cnt = 0;
-    MT_TRY(cs_d2h(ctx, &start, m->d_cstart, 1));
-    MT_TRY(cs_d2h(ctx, &cnt, m->d_ccount, 1));
-    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
+    CS_TRY(cs_d2h(ctx, &start, m->d_cstart, 1));
+    CS_TRY(cs_d2h(ctx, &cnt, m->d_ccount, 1));
+    CS_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
     *n = cnt;
     if (out && cnt > 0 && cap > 0) {
         std::vector<int2> c((size_t)cnt);
-        MT_TRY(cs_d2h(ctx, c.data(), m->d_cands + start, (size_t)cnt));
+        CS_TRY(cs_d2h(ctx, c.data(), m->d_cands + start, (size_t)cnt));
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < cnt && i < cap; i++) out[i] = c[i].x & 0xffffff;
     }
@@ -926,24 +892,24 @@ int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const f
     const int N = m->F.N;
     *nmatches = 0;
     if (n_last == 0) { for (int i = 0; i < N; i++) train_match[i] = -1; return CS_OK; }
-    MT_TRY(cs_h2d(ctx, m->d_wp, world_pos, (size_t)n_last * 3));
-    MT_TRY(cs_h2d(ctx, m->d_T, Tcw, 12));
-    MT_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
-    MT_TRY(cs_h2d(ctx, m->d_valid, valid, (size_t)n_last));
-    MT_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_last));
-    MT_TRY(cs_h2d(ctx, m->d_level, last_octave, (size_t)n_last));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_last * 32));
-    if (check_orientation) MT_TRY(cs_h2d(ctx, m->d_ang, last_angle, (size_t)n_last));
-    if (train_blocked) MT_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N)); // map point from before the call / KeysStatic[i2] == false, :1451-1457
+    CS_TRY(cs_h2d(ctx, m->d_wp, world_pos, (size_t)n_last * 3));
+    CS_TRY(cs_h2d(ctx, m->d_T, Tcw, 12));
+    CS_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
+    CS_TRY(cs_h2d(ctx, m->d_valid, valid, (size_t)n_last));
+    CS_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_last));
+    CS_TRY(cs_h2d(ctx, m->d_level, last_octave, (size_t)n_last));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_last * 32));
+    if (check_orientation) CS_TRY(cs_h2d(ctx, m->d_ang, last_angle, (size_t)n_last));
+    if (train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N)); // map point from before the call / KeysStatic[i2] == false, :1451-1457
     // (the levels were checked above, before anything was queued; the kernel's own check only keeps its read of the scale table in range)
     CS_LAUNCH(ctx, "match_project", match_project, dim3((n_last + 255) / 256), dim3(256), 0, n_last, 1, (const int *)nullptr, m->d_wp, m->d_valid, m->d_level, (const cs_keypoint *)nullptr,
               m->d_T, fx, fy, cx, cy, m->d_sf, n_levels, th, m->F, m->d_q, reinterpret_cast<int *>(m->d_cursor + 1));
-    MT_TRY(mt_candidates(ctx, m, n_last, true));
+    CS_TRY(mt_candidates(ctx, m, n_last, true));
     // the greedy pass (:1397-1494) and the rotation cut (:1496-1517), on the device
     ResolveP P{};
     P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_last; P.n_train = N; P.tkeys = m->d_keys; P.qangle = m->d_ang; P.blocks = m->d_blocks;
     P.tblocked = train_blocked ? m->d_tb : nullptr; P.check_orientation = check_orientation; P.train_match = m->d_tm; P.q_rec = m->d_qrec; P.nmatches = m->d_tm + N;
-    MT_TRY(mt_resolve<RV_PROJ>(ctx, P, 1, N));
+    CS_TRY(mt_resolve<RV_PROJ>(ctx, P, 1, N));
     return mt_finish(ctx, m, m->d_tm, N, train_match, nmatches);
 }
 
@@ -975,10 +941,10 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
     // the frames f0 .. f0 + n_pairs lie one behind the other in the extractor's buffers
     std::vector<int> first((size_t)n_pairs + 2);
     const cs_keypoint *d_k0 = nullptr; const unsigned long long *d_d0 = nullptr;
-    { int n0 = 0; MT_TRY(cs_orb_device_frame(orb, f0, &d_k0, &d_d0, &n0)); first[0] = 0; first[1] = n0; }
+    { int n0 = 0; CS_TRY(cs_orb_device_frame(orb, f0, &d_k0, &d_d0, &n0)); first[0] = 0; first[1] = n0; }
     for (int p = 1; p <= n_pairs; p++) {
         const cs_keypoint *dk; const unsigned long long *dd; int n = 0;
-        MT_TRY(cs_orb_device_frame(orb, f0 + p, &dk, &dd, &n));
+        CS_TRY(cs_orb_device_frame(orb, f0 + p, &dk, &dd, &n));
         if (dk != d_k0 + first[p]) { ctx->err = "cs_match_by_projection_stream: the extractor's frames are not contiguous"; return CS_ERR_BAD_ARG; }
         first[p + 1] = first[p] + n;
     }
@@ -992,26 +958,26 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
     if (nq == 0 || nk == 0) return CS_OK;
     if (nk_all >= (1 << 24)) { int nmax = 0; for (int p = 1; p <= n_pairs; p++) nmax = std::max(nmax, first[p + 1] - first[p]); if (nmax >= (1 << 24)) return CS_ERR_CAPACITY; }
     const FrameP F = make_frame(0, minX, maxX, minY, maxY);
-    MT_TRY(m->keys.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->cell_items.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->cell_recs.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->kp_cell.grow(ctx, m->own, (size_t)nk_all)); MT_TRY(m->tm.grow(ctx, m->own, (size_t)nk));
-    MT_TRY(m->cell_start.grow(ctx, m->own, (size_t)n_pairs * (NCELL + 1))); MT_TRY(m->kfirst.grow(ctx, m->own, (size_t)n_pairs + 2)); MT_TRY(m->qfirst.grow(ctx, m->own, (size_t)n_pairs + 2)); MT_TRY(m->T.grow(ctx, m->own, (size_t)n_pairs * 12)); MT_TRY(m->nm.grow(ctx, m->own, (size_t)n_pairs));
-    MT_TRY(m->ccount.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->cstart.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->qrec.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->q.grow(ctx, m->own, (size_t)nq)); MT_TRY(m->wp.grow(ctx, m->own, (size_t)nq * 3)); MT_TRY(m->valid.grow(ctx, m->own, (size_t)nq));
-    MT_TRY(m->blocks.grow(ctx, m->own, (size_t)nq)); if (mp_desc) MT_TRY(m->qdesc.grow(ctx, m->own, (size_t)nq * 4));
-    if (!m->d_sf) MT_TRY(m->own.alloc(ctx, &m->d_sf, (size_t)32));
-    if (!m->d_cursor) MT_TRY(m->own.alloc(ctx, &m->d_cursor, (size_t)2));
-    if (!m->cands.p) MT_TRY(m->cands.grow(ctx, m->own, std::max((size_t)nq * 12, (size_t)1 << 16))); // (5.6 candidates per query at th 15 on the bench stream; the cursor says what a window really needs)
+    CS_TRY(m->keys.grow(ctx, m->own, (size_t)nk_all)); CS_TRY(m->cell_items.grow(ctx, m->own, (size_t)nk_all)); CS_TRY(m->cell_recs.grow(ctx, m->own, (size_t)nk_all)); CS_TRY(m->kp_cell.grow(ctx, m->own, (size_t)nk_all)); CS_TRY(m->tm.grow(ctx, m->own, (size_t)nk));
+    CS_TRY(m->cell_start.grow(ctx, m->own, (size_t)n_pairs * (NCELL + 1))); CS_TRY(m->kfirst.grow(ctx, m->own, (size_t)n_pairs + 2)); CS_TRY(m->qfirst.grow(ctx, m->own, (size_t)n_pairs + 2)); CS_TRY(m->T.grow(ctx, m->own, (size_t)n_pairs * 12)); CS_TRY(m->nm.grow(ctx, m->own, (size_t)n_pairs));
+    CS_TRY(m->ccount.grow(ctx, m->own, (size_t)nq)); CS_TRY(m->cstart.grow(ctx, m->own, (size_t)nq)); CS_TRY(m->qrec.grow(ctx, m->own, (size_t)nq)); CS_TRY(m->q.grow(ctx, m->own, (size_t)nq)); CS_TRY(m->wp.grow(ctx, m->own, (size_t)nq * 3)); CS_TRY(m->valid.grow(ctx, m->own, (size_t)nq));
+    CS_TRY(m->blocks.grow(ctx, m->own, (size_t)nq)); if (mp_desc) CS_TRY(m->qdesc.grow(ctx, m->own, (size_t)nq * 4));
+    if (!m->d_sf) CS_TRY(m->own.alloc(ctx, &m->d_sf, (size_t)32));
+    if (!m->d_cursor) CS_TRY(m->own.alloc(ctx, &m->d_cursor, (size_t)2));
+    if (!m->cands.p) CS_TRY(m->cands.grow(ctx, m->own, std::max((size_t)nq * 12, (size_t)1 << 16))); // (5.6 candidates per query at th 15 on the bench stream; the cursor says what a window really needs)
     // UndistortKeyPoints of every frame of the window (device to device), AssignFeaturesToGrid of the current frames
     CS_LAUNCH(ctx, "match_undistort", match_undistort, dim3((nk_all + 255) / 256), dim3(256), 0, nk_all, d_k0, make_undp(K4, dist5), m->keys.p);
     std::vector<int> kfirst((size_t)n_pairs + 1);
     int n2max = 0;
     for (int p = 0; p <= n_pairs; p++) { kfirst[p] = first[p + 1]; if (p < n_pairs) n2max = std::max(n2max, first[p + 2] - first[p + 1]); } // train frame of pair p: key points kfirst[p] .. kfirst[p + 1] of the window's list
-    MT_TRY(cs_h2d(ctx, m->kfirst.p, kfirst.data(), (size_t)n_pairs + 1));
-    MT_TRY(cs_h2d(ctx, m->qfirst.p, first.data(), (size_t)n_pairs + 1));
-    MT_TRY(cs_h2d(ctx, m->T.p, Tcw, (size_t)n_pairs * 12));
-    MT_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
-    MT_TRY(cs_h2d(ctx, m->wp.p, world_pos, (size_t)nq * 3));
-    MT_TRY(cs_h2d(ctx, m->valid.p, valid, (size_t)nq));
-    MT_TRY(cs_h2d(ctx, m->blocks.p, blocks, (size_t)nq));
-    if (mp_desc) MT_TRY(cs_h2d(ctx, (uint8_t *)m->qdesc.p, mp_desc, (size_t)nq * 32));
+    CS_TRY(cs_h2d(ctx, m->kfirst.p, kfirst.data(), (size_t)n_pairs + 1));
+    CS_TRY(cs_h2d(ctx, m->qfirst.p, first.data(), (size_t)n_pairs + 1));
+    CS_TRY(cs_h2d(ctx, m->T.p, Tcw, (size_t)n_pairs * 12));
+    CS_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)n_levels));
+    CS_TRY(cs_h2d(ctx, m->wp.p, world_pos, (size_t)nq * 3));
+    CS_TRY(cs_h2d(ctx, m->valid.p, valid, (size_t)nq));
+    CS_TRY(cs_h2d(ctx, m->blocks.p, blocks, (size_t)nq));
+    if (mp_desc) CS_TRY(cs_h2d(ctx, (uint8_t *)m->qdesc.p, mp_desc, (size_t)nq * 32));
     const unsigned long long *d_qdesc = mp_desc ? m->qdesc.p : d_d0; // NULL: a last frame's key point is matched with its own descriptor
     int *d_err = reinterpret_cast<int *>(m->d_cursor + 1);
     CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 16, ctx->stream));
@@ -1025,16 +991,16 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
         ResolveP P{};
         P.cstart = m->cstart.p; P.ccount = m->ccount.p; P.cands = m->cands.p; P.pfirst = m->qfirst.p; P.kfirst = m->kfirst.p; P.tkeys = m->keys.p; P.qkeys = m->keys.p; P.blocks = m->blocks.p;
         P.check_orientation = check_orientation; P.train_match = m->tm.p; P.q_rec = m->qrec.p; P.nmatches = m->nm.p;
-        MT_TRY(mt_resolve<RV_PROJ>(ctx, P, n_pairs, n2max));
+        CS_TRY(mt_resolve<RV_PROJ>(ctx, P, n_pairs, n2max));
         const int r = mt_cursor(ctx, m->d_cursor, (long)m->cands.cap, &m->last_c); // (BAD_ARG: a valid query whose key point's level is outside the scale table)
         if (r == CS_OK) break;
         if (r != CS_ERR_CAPACITY) return r;
         if (attempt) { ctx->err = "cs_match_by_projection_stream: candidate arena"; return CS_ERR_CAPACITY; }
-        MT_TRY(m->cands.grow(ctx, m->own, (size_t)m->last_c));
+        CS_TRY(m->cands.grow(ctx, m->own, (size_t)m->last_c));
         CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 8, ctx->stream)); // (the cursor; match_project's error flag behind it stays)
     }
-    MT_TRY(cs_d2h(ctx, train_match, m->tm.p, (size_t)nk));
-    MT_TRY(cs_d2h(ctx, nmatches, m->nm.p, (size_t)n_pairs));
+    CS_TRY(cs_d2h(ctx, train_match, m->tm.p, (size_t)nk));
+    CS_TRY(cs_d2h(ctx, nmatches, m->nm.p, (size_t)n_pairs));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
@@ -1062,15 +1028,15 @@ int cs_match_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_x
         }
         q[i] = Q;
     }
-    MT_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
-    MT_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_mp));
-    if (train_blocked) MT_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N));
-    MT_TRY(mt_candidates(ctx, m, n_mp, true));
+    CS_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
+    CS_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_mp));
+    if (train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N));
+    CS_TRY(mt_candidates(ctx, m, n_mp, true));
     ResolveP P{}; // :86-140: best / second with their levels, the ratio rule, claims
     P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_mp; P.n_train = N; P.tkeys = m->d_keys; P.blocks = m->d_blocks;
     P.tblocked = train_blocked ? m->d_tb : nullptr; P.nnratio = nnratio; P.check_orientation = 0; P.train_match = m->d_tm; P.q_rec = m->d_qrec; P.nmatches = m->d_tm + N;
-    MT_TRY(mt_resolve<RV_LOCAL>(ctx, P, 1, N));
+    CS_TRY(mt_resolve<RV_LOCAL>(ctx, P, 1, N));
     return mt_finish(ctx, m, m->d_tm, N, train_match, nmatches);
 }
 
@@ -1088,15 +1054,15 @@ int cs_match_for_initialization(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *k
         if (!(keys1[i].octave > 0)) { Q.x = prev[i * 2]; Q.y = prev[i * 2 + 1]; Q.r = (float)window_size; Q.minLevel = keys1[i].octave; Q.maxLevel = keys1[i].octave; Q.valid = 1; }
         q[i] = Q; ang[i] = keys1[i].angle;
     }
-    MT_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)N1));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, desc1, (size_t)N1 * 32));
-    MT_TRY(cs_h2d(ctx, m->d_ang, ang.data(), (size_t)N1));
-    MT_TRY(mt_candidates(ctx, m, N1, true));
+    CS_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)N1));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, desc1, (size_t)N1 * 32));
+    CS_TRY(cs_h2d(ctx, m->d_ang, ang.data(), (size_t)N1));
+    CS_TRY(mt_candidates(ctx, m, N1, true));
     ResolveP P{}; // :451-504 (vMatchedDistance, vnMatches21 and the displacement of an earlier match) and :506-527
     P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = N1; P.n_train = m->F.N; P.tkeys = m->d_keys; P.qangle = m->d_ang;
     P.nnratio = nnratio; P.check_orientation = check_orientation; P.q_match = m->d_qm; P.q_rec = m->d_qrec; P.nmatches = m->d_qm + N1;
-    MT_TRY(mt_resolve<RV_INIT>(ctx, P, 1, m->F.N));
-    MT_TRY(mt_finish(ctx, m, m->d_qm, N1, vnMatches12, nmatches));
+    CS_TRY(mt_resolve<RV_INIT>(ctx, P, 1, m->F.N));
+    CS_TRY(mt_finish(ctx, m, m->d_qm, N1, vnMatches12, nmatches));
     for (int i1 = 0; i1 < N1; i1++) // :529-532
         if (vnMatches12[i1] >= 0) { prev[i1 * 2] = m->keys[vnMatches12[i1]].x; prev[i1 * 2 + 1] = m->keys[vnMatches12[i1]].y; }
     return CS_OK;
@@ -1121,22 +1087,22 @@ int cs_match_fuse(cs_ctx *ctx, cs_matcher *m, const float *u_right, const float 
         }
         q[i] = Q;
     }
-    MT_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
-    MT_TRY(cs_h2d(ctx, m->d_uv, uv, (size_t)n_mp * 2));
-    MT_TRY(cs_h2d(ctx, m->d_qur, ur, (size_t)n_mp));
-    MT_TRY(cs_h2d(ctx, m->d_inv, inv_level_sigma2, (size_t)n_levels));
-    MT_TRY(cs_h2d(ctx, m->d_level, pred_level, (size_t)n_mp));
-    MT_TRY(cs_h2d(ctx, m->d_valid, valid, (size_t)n_mp));
-    MT_TRY(cs_h2d(ctx, m->d_ur, u_right, (size_t)N));
-    if (keys_static) MT_TRY(cs_h2d(ctx, m->d_tb, keys_static, (size_t)N));
-    MT_TRY(mt_candidates(ctx, m, n_mp, true));
+    CS_TRY(cs_h2d(ctx, m->d_q, q.data(), (size_t)n_mp));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
+    CS_TRY(cs_h2d(ctx, m->d_uv, uv, (size_t)n_mp * 2));
+    CS_TRY(cs_h2d(ctx, m->d_qur, ur, (size_t)n_mp));
+    CS_TRY(cs_h2d(ctx, m->d_inv, inv_level_sigma2, (size_t)n_levels));
+    CS_TRY(cs_h2d(ctx, m->d_level, pred_level, (size_t)n_mp));
+    CS_TRY(cs_h2d(ctx, m->d_valid, valid, (size_t)n_mp));
+    CS_TRY(cs_h2d(ctx, m->d_ur, u_right, (size_t)N));
+    if (keys_static) CS_TRY(cs_h2d(ctx, m->d_tb, keys_static, (size_t)N));
+    CS_TRY(mt_candidates(ctx, m, n_mp, true));
     // :934-981: the tests that need per-keypoint data of the key frame, first minimum wins
     CS_LAUNCH(ctx, "match_fuse_best", match_fuse_best, dim3((n_mp + 255) / 256), dim3(256), 0, n_mp, m->d_cstart, m->d_ccount, m->d_cands, m->d_keys, m->d_ur, m->d_inv, n_levels,
               keys_static ? m->d_tb : (const uint8_t *)nullptr, m->d_uv, m->d_qur, m->d_level, m->d_valid, m->d_qm, m->d_qrec, reinterpret_cast<int *>(m->d_cursor + 1));
-    MT_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
-    MT_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
-    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c)); // (BAD_ARG: a candidate's level outside the sigma table)
+    CS_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
+    CS_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
+    CS_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c)); // (BAD_ARG: a candidate's level outside the sigma table)
     int nf = 0;
     for (int i = 0; i < n_mp; i++) if (best_dist[i] <= TH_LOW) nf++;
     *n_fused = nf;
@@ -1158,25 +1124,25 @@ int cs_match_for_triangulation(cs_ctx *ctx, const cs_keypoint *keys1Un, const ui
     const NodeLists L(node2, N2);
     std::vector<int> n1c((size_t)N1), res((size_t)N1 + 1);
     for (int i = 0; i < N1; i++) n1c[i] = L.compact(node1[i]);
-    MtScratch sc(ctx); // (after the host arrays: it waits for the copies out of and into them before they go)
+    cs_scratch sc(ctx); // (after the host arrays: it waits for the copies out of and into them before they go)
     cs_keypoint *d_k1 = nullptr, *d_k2 = nullptr; unsigned long long *d_d1 = nullptr, *d_d2 = nullptr; int *d_n1 = nullptr, *d_st = nullptr, *d_it = nullptr, *d_m = nullptr;
     uint8_t *d_s1 = nullptr, *d_s2 = nullptr; float *d_u1 = nullptr, *d_u2 = nullptr, *d_sc = nullptr, *d_sg = nullptr;
-    MT_TRY(sc.alloc(ctx, &d_k1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_k2, (size_t)N2)); MT_TRY(sc.alloc(ctx, &d_d1, (size_t)N1 * 4)); MT_TRY(sc.alloc(ctx, &d_d2, (size_t)N2 * 4));
-    MT_TRY(sc.alloc(ctx, &d_n1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_st, L.start.size())); MT_TRY(sc.alloc(ctx, &d_it, L.items.size())); MT_TRY(sc.alloc(ctx, &d_m, (size_t)N1 + 1));
-    MT_TRY(sc.alloc(ctx, &d_s1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_s2, (size_t)N2)); MT_TRY(sc.alloc(ctx, &d_u1, (size_t)N1)); MT_TRY(sc.alloc(ctx, &d_u2, (size_t)N2));
-    MT_TRY(sc.alloc(ctx, &d_sc, (size_t)n_levels)); MT_TRY(sc.alloc(ctx, &d_sg, (size_t)n_levels));
-    MT_TRY(cs_h2d(ctx, d_k1, keys1Un, (size_t)N1)); MT_TRY(cs_h2d(ctx, d_k2, keys2Un, (size_t)N2));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)d_d1, desc1, (size_t)N1 * 32)); MT_TRY(cs_h2d(ctx, (uint8_t *)d_d2, desc2, (size_t)N2 * 32));
-    MT_TRY(cs_h2d(ctx, d_n1, n1c.data(), (size_t)N1)); MT_TRY(cs_h2d(ctx, d_st, L.start.data(), L.start.size())); MT_TRY(cs_h2d(ctx, d_it, L.items.data(), L.items.size()));
-    MT_TRY(cs_h2d(ctx, d_s1, skip1, (size_t)N1)); MT_TRY(cs_h2d(ctx, d_s2, skip2, (size_t)N2)); MT_TRY(cs_h2d(ctx, d_u1, u_right1, (size_t)N1)); MT_TRY(cs_h2d(ctx, d_u2, u_right2, (size_t)N2));
-    MT_TRY(cs_h2d(ctx, d_sc, scale_factors2, (size_t)n_levels)); MT_TRY(cs_h2d(ctx, d_sg, level_sigma2_2, (size_t)n_levels));
+    CS_TRY(sc.alloc(ctx, &d_k1, (size_t)N1)); CS_TRY(sc.alloc(ctx, &d_k2, (size_t)N2)); CS_TRY(sc.alloc(ctx, &d_d1, (size_t)N1 * 4)); CS_TRY(sc.alloc(ctx, &d_d2, (size_t)N2 * 4));
+    CS_TRY(sc.alloc(ctx, &d_n1, (size_t)N1)); CS_TRY(sc.alloc(ctx, &d_st, L.start.size())); CS_TRY(sc.alloc(ctx, &d_it, L.items.size())); CS_TRY(sc.alloc(ctx, &d_m, (size_t)N1 + 1));
+    CS_TRY(sc.alloc(ctx, &d_s1, (size_t)N1)); CS_TRY(sc.alloc(ctx, &d_s2, (size_t)N2)); CS_TRY(sc.alloc(ctx, &d_u1, (size_t)N1)); CS_TRY(sc.alloc(ctx, &d_u2, (size_t)N2));
+    CS_TRY(sc.alloc(ctx, &d_sc, (size_t)n_levels)); CS_TRY(sc.alloc(ctx, &d_sg, (size_t)n_levels));
+    CS_TRY(cs_h2d(ctx, d_k1, keys1Un, (size_t)N1)); CS_TRY(cs_h2d(ctx, d_k2, keys2Un, (size_t)N2));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)d_d1, desc1, (size_t)N1 * 32)); CS_TRY(cs_h2d(ctx, (uint8_t *)d_d2, desc2, (size_t)N2 * 32));
+    CS_TRY(cs_h2d(ctx, d_n1, n1c.data(), (size_t)N1)); CS_TRY(cs_h2d(ctx, d_st, L.start.data(), L.start.size())); CS_TRY(cs_h2d(ctx, d_it, L.items.data(), L.items.size()));
+    CS_TRY(cs_h2d(ctx, d_s1, skip1, (size_t)N1)); CS_TRY(cs_h2d(ctx, d_s2, skip2, (size_t)N2)); CS_TRY(cs_h2d(ctx, d_u1, u_right1, (size_t)N1)); CS_TRY(cs_h2d(ctx, d_u2, u_right2, (size_t)N2));
+    CS_TRY(cs_h2d(ctx, d_sc, scale_factors2, (size_t)n_levels)); CS_TRY(cs_h2d(ctx, d_sg, level_sigma2_2, (size_t)n_levels));
     TriP P; for (int k = 0; k < 9; k++) P.F12[k] = F12[k];
     P.ex = ex; P.ey = ey; P.only_stereo = only_stereo;
     CS_LAUNCH(ctx, "match_triangulation", match_triangulation, dim3((N1 + 3) / 4), dim3(256), 0, N1, d_k1, d_d1, d_n1, d_s1, d_u1, d_k2, d_d2, d_s2, d_u2, d_st, d_it, L.n_nodes, P,
               d_sc, d_sg, d_m);
     CS_LAUNCH(ctx, "match_orient_cut", match_orient_cut, dim3(1), dim3(1024), 0, N1, d_k1, d_k2, d_m, check_orientation, d_m + N1); // :801-830
-    MT_TRY(cs_d2h(ctx, res.data(), d_m, (size_t)N1 + 1));
-    MT_TRY(sc.drain());
+    CS_TRY(cs_d2h(ctx, res.data(), d_m, (size_t)N1 + 1));
+    CS_TRY(sc.drain());
     memcpy(matches12, res.data(), sizeof(int) * (size_t)N1);
     *nmatches = res[(size_t)N1];
     return CS_OK;
@@ -1196,14 +1162,14 @@ static MapP make_mapp(const float *R, const float *t, const float *Ow, const flo
 // uploads the map points, runs the preamble into m's query arrays (points outside the scale table add to *d_nout) and enumerates the windows in m's frame; nothing waits
 template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, int *d_nout) {
     const int n = I.n, N = m->F.N;
-    MT_TRY(cs_h2d(ctx, m->d_wp, I.world_pos, (size_t)n * 3));
-    if (MODE == PM_SIM3) MT_TRY(cs_h2d(ctx, m->d_nrm, I.normal, (size_t)n * 3));
-    MT_TRY(cs_h2d(ctx, m->d_mind, I.min_distance, (size_t)n));
-    MT_TRY(cs_h2d(ctx, m->d_maxd, I.max_distance, (size_t)n));
-    MT_TRY(cs_h2d(ctx, m->d_valid, I.skip, (size_t)n));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, I.mp_desc, (size_t)n * 32));
-    MT_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)P.n_levels));
-    if (I.train_blocked) MT_TRY(cs_h2d(ctx, m->d_tb, I.train_blocked, (size_t)N));
+    CS_TRY(cs_h2d(ctx, m->d_wp, I.world_pos, (size_t)n * 3));
+    if (MODE == PM_SIM3) CS_TRY(cs_h2d(ctx, m->d_nrm, I.normal, (size_t)n * 3));
+    CS_TRY(cs_h2d(ctx, m->d_mind, I.min_distance, (size_t)n));
+    CS_TRY(cs_h2d(ctx, m->d_maxd, I.max_distance, (size_t)n));
+    CS_TRY(cs_h2d(ctx, m->d_valid, I.skip, (size_t)n));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, I.mp_desc, (size_t)n * 32));
+    CS_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)P.n_levels));
+    if (I.train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, I.train_blocked, (size_t)N));
     CS_LAUNCH(ctx, "match_project_map", match_project_map<MODE>, dim3((n + 255) / 256), dim3(256), 0, n, m->d_wp, m->d_nrm, m->d_mind, m->d_maxd, m->d_valid, P, m->d_sf, m->F, m->d_q, m->d_level, d_nout);
     return mt_candidates(ctx, m, n, true);
 }
@@ -1219,15 +1185,15 @@ template <int MODE> static int mt_map_claim(cs_ctx *ctx, cs_matcher *m, const Ma
     if (n_level_outside) *n_level_outside = 0;
     if (I.n == 0) { for (int i = 0; i < N; i++) train_match[i] = -1; return CS_OK; }
     CS_HIP(ctx, hipMemsetAsync(m->d_nout, 0, 2 * sizeof(int), ctx->stream));
-    if (check_orientation) MT_TRY(cs_h2d(ctx, m->d_ang, kf_angle, (size_t)I.n));
-    MT_TRY(mt_map_queries<MODE>(ctx, m, I, P, scale_factors, m->d_nout));
+    if (check_orientation) CS_TRY(cs_h2d(ctx, m->d_ang, kf_angle, (size_t)I.n));
+    CS_TRY(mt_map_queries<MODE>(ctx, m, I, P, scale_factors, m->d_nout));
     ResolveP R{};
     R.cstart = m->d_cstart; R.ccount = m->d_ccount; R.cands = m->d_cands; R.n_steps = I.n; R.n_train = N; R.tkeys = m->d_keys; R.qangle = m->d_ang;
     R.tblocked = I.train_blocked ? m->d_tb : nullptr; R.check_orientation = check_orientation; R.train_match = m->d_tm; R.q_rec = m->d_qrec; R.nmatches = m->d_tm + N; R.accept_dist = accept_dist;
-    MT_TRY(mt_resolve<RV_CLAIM>(ctx, R, 1, N));
+    CS_TRY(mt_resolve<RV_CLAIM>(ctx, R, 1, N));
     int *nout = m->h_nout;
-    MT_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
-    MT_TRY(mt_finish(ctx, m, m->d_tm, N, train_match, nmatches));
+    CS_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
+    CS_TRY(mt_finish(ctx, m, m->d_tm, N, train_match, nmatches));
     if (n_level_outside) *n_level_outside = nout[0];
     return CS_OK;
 }
@@ -1266,13 +1232,13 @@ int cs_match_fuse_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float
     if (n_level_outside) *n_level_outside = 0;
     if (n_mp == 0) return CS_OK;
     CS_HIP(ctx, hipMemsetAsync(m->d_nout, 0, 2 * sizeof(int), ctx->stream));
-    MT_TRY(mt_map_queries<PM_SIM3>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m->d_nout));
+    CS_TRY(mt_map_queries<PM_SIM3>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m->d_nout));
     CS_LAUNCH(ctx, "match_map_best", match_map_best, dim3((n_mp + 255) / 256), dim3(256), 0, n_mp, m->d_cstart, m->d_ccount, m->d_cands, train_blocked ? m->d_tb : (const uint8_t *)nullptr, -1, m->d_qm, m->d_qrec);
     int *nout = m->h_nout;
-    MT_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
-    MT_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
-    MT_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
-    MT_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
+    CS_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
+    CS_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
+    CS_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
+    CS_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
     int nf = 0;
     for (int i = 0; i < n_mp; i++) if (best_dist[i] <= TH_LOW) nf++; // :1121
     *n_fused = nf;
@@ -1297,16 +1263,16 @@ int cs_match_by_sim3(cs_ctx *ctx, cs_matcher *m1, cs_matcher *m2, const float *R
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 == 0 || n2 == 0) return CS_OK; // (no agreement without both directions)
     CS_HIP(ctx, hipMemsetAsync(m2->d_nout, 0, 2 * sizeof(int), ctx->stream));
-    MT_TRY(mt_map_queries<PM_PAIR>(ctx, m2, I1, make_mapp(R1w, t1w, nullptr, sR21, t21, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m2->d_nout)); // :1187-1267
+    CS_TRY(mt_map_queries<PM_PAIR>(ctx, m2, I1, make_mapp(R1w, t1w, nullptr, sR21, t21, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m2->d_nout)); // :1187-1267
     CS_LAUNCH(ctx, "match_map_best", match_map_best, dim3((n1 + 255) / 256), dim3(256), 0, n1, m2->d_cstart, m2->d_ccount, m2->d_cands, train_blocked2 ? m2->d_tb : (const uint8_t *)nullptr, TH_HIGH, m2->d_qm,
               (int *)nullptr);
-    MT_TRY(mt_map_queries<PM_PAIR>(ctx, m1, I2, make_mapp(R2w, t2w, nullptr, sR12, t12, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m2->d_nout)); // :1270-1350
+    CS_TRY(mt_map_queries<PM_PAIR>(ctx, m1, I2, make_mapp(R2w, t2w, nullptr, sR12, t12, fx, fy, cx, cy, log_scale_factor, th, n_levels), scale_factors, m2->d_nout)); // :1270-1350
     CS_LAUNCH(ctx, "match_map_best", match_map_best, dim3((n2 + 255) / 256), dim3(256), 0, n2, m1->d_cstart, m1->d_ccount, m1->d_cands, train_blocked1 ? m1->d_tb : (const uint8_t *)nullptr, TH_HIGH, m1->d_qm,
               (int *)nullptr);
     CS_LAUNCH(ctx, "match_sim3_agree", match_sim3_agree, dim3((n1 + 255) / 256), dim3(256), 0, n1, m2->d_qm, n2, m1->d_qm, m2->d_qrec, m2->d_nout + 1); // :1353-1368
     int *nout = m2->h_nout;
-    MT_TRY(cs_d2h(ctx, nout, m2->d_nout, 2));
-    MT_TRY(cs_d2h(ctx, matches12, m2->d_qrec, (size_t)n1));
+    CS_TRY(cs_d2h(ctx, nout, m2->d_nout, 2));
+    CS_TRY(cs_d2h(ctx, matches12, m2->d_qrec, (size_t)n1));
     const int r2 = mt_cursor(ctx, m2->d_cursor, m2->max_cand, &m2->last_c), r1 = mt_cursor(ctx, m1->d_cursor, m1->max_cand, &m1->last_c); // (the first one waits; both arenas are checked)
     if (r2 != CS_OK || r1 != CS_OK) { for (int i = 0; i < n1; i++) matches12[i] = -1; return r2 != CS_OK ? r2 : r1; }
     *n_found = nout[1];
@@ -1339,24 +1305,24 @@ template <int V> static int bow_search(cs_ctx *ctx, const cs_keypoint *keysK, co
     std::vector<int> qlist((size_t)n_steps);
     for (int s = 0; s < n_steps; s++) qlist[s] = order[s].second;
     std::vector<int> res((size_t)n_out + 1, -1);
-    MtScratch sc(ctx); // (after the host arrays: it waits for the copies out of and into them before they go)
+    cs_scratch sc(ctx); // (after the host arrays: it waits for the copies out of and into them before they go)
     cs_keypoint *d_kk = nullptr, *d_kf = nullptr; unsigned long long *d_dk = nullptr, *d_df = nullptr; int *d_nk = nullptr, *d_st = nullptr, *d_it = nullptr, *d_cnt = nullptr, *d_ql = nullptr, *d_rec = nullptr, *d_out = nullptr;
     long *d_off = nullptr; int2 *d_ca = nullptr; uint8_t *d_sf = nullptr;
-    MT_TRY(sc.alloc(ctx, &d_dk, (size_t)NK * 4)); MT_TRY(sc.alloc(ctx, &d_df, (size_t)NF * 4)); MT_TRY(sc.alloc(ctx, &d_nk, (size_t)NK)); MT_TRY(sc.alloc(ctx, &d_st, L.start.size())); MT_TRY(sc.alloc(ctx, &d_it, L.items.size()));
-    MT_TRY(sc.alloc(ctx, &d_off, off.size())); MT_TRY(sc.alloc(ctx, &d_ca, (size_t)total)); MT_TRY(sc.alloc(ctx, &d_cnt, (size_t)NK)); MT_TRY(sc.alloc(ctx, &d_ql, (size_t)n_steps)); MT_TRY(sc.alloc(ctx, &d_rec, (size_t)NK));
-    MT_TRY(sc.alloc(ctx, &d_out, (size_t)n_out + 1)); MT_TRY(sc.alloc(ctx, &d_kk, (size_t)NK)); MT_TRY(sc.alloc(ctx, &d_kf, (size_t)NF)); if (skipF) MT_TRY(sc.alloc(ctx, &d_sf, (size_t)NF));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)d_dk, descK, (size_t)NK * 32)); MT_TRY(cs_h2d(ctx, (uint8_t *)d_df, descF, (size_t)NF * 32)); MT_TRY(cs_h2d(ctx, d_nk, nkc.data(), (size_t)NK));
-    MT_TRY(cs_h2d(ctx, d_st, L.start.data(), L.start.size())); MT_TRY(cs_h2d(ctx, d_it, L.items.data(), L.items.size())); MT_TRY(cs_h2d(ctx, d_off, off.data(), off.size()));
-    MT_TRY(cs_h2d(ctx, d_cnt, cnt.data(), (size_t)NK)); MT_TRY(cs_h2d(ctx, d_ql, qlist.data(), (size_t)n_steps)); MT_TRY(cs_h2d(ctx, d_kk, keysK, (size_t)NK)); MT_TRY(cs_h2d(ctx, d_kf, keysF, (size_t)NF));
-    if (skipF) MT_TRY(cs_h2d(ctx, d_sf, skipF, (size_t)NF));
+    CS_TRY(sc.alloc(ctx, &d_dk, (size_t)NK * 4)); CS_TRY(sc.alloc(ctx, &d_df, (size_t)NF * 4)); CS_TRY(sc.alloc(ctx, &d_nk, (size_t)NK)); CS_TRY(sc.alloc(ctx, &d_st, L.start.size())); CS_TRY(sc.alloc(ctx, &d_it, L.items.size()));
+    CS_TRY(sc.alloc(ctx, &d_off, off.size())); CS_TRY(sc.alloc(ctx, &d_ca, (size_t)total)); CS_TRY(sc.alloc(ctx, &d_cnt, (size_t)NK)); CS_TRY(sc.alloc(ctx, &d_ql, (size_t)n_steps)); CS_TRY(sc.alloc(ctx, &d_rec, (size_t)NK));
+    CS_TRY(sc.alloc(ctx, &d_out, (size_t)n_out + 1)); CS_TRY(sc.alloc(ctx, &d_kk, (size_t)NK)); CS_TRY(sc.alloc(ctx, &d_kf, (size_t)NF)); if (skipF) CS_TRY(sc.alloc(ctx, &d_sf, (size_t)NF));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)d_dk, descK, (size_t)NK * 32)); CS_TRY(cs_h2d(ctx, (uint8_t *)d_df, descF, (size_t)NF * 32)); CS_TRY(cs_h2d(ctx, d_nk, nkc.data(), (size_t)NK));
+    CS_TRY(cs_h2d(ctx, d_st, L.start.data(), L.start.size())); CS_TRY(cs_h2d(ctx, d_it, L.items.data(), L.items.size())); CS_TRY(cs_h2d(ctx, d_off, off.data(), off.size()));
+    CS_TRY(cs_h2d(ctx, d_cnt, cnt.data(), (size_t)NK)); CS_TRY(cs_h2d(ctx, d_ql, qlist.data(), (size_t)n_steps)); CS_TRY(cs_h2d(ctx, d_kk, keysK, (size_t)NK)); CS_TRY(cs_h2d(ctx, d_kf, keysF, (size_t)NF));
+    if (skipF) CS_TRY(cs_h2d(ctx, d_sf, skipF, (size_t)NF));
     if (V == RV_BOWKF) CS_HIP(ctx, hipMemsetAsync(d_out, 0xff, sizeof(int) * (size_t)NK, ctx->stream)); // K features outside the visiting order have no match
     CS_LAUNCH(ctx, "match_bow_dists", match_bow_dists, dim3((NK + 3) / 4), dim3(256), 0, NK, d_dk, d_nk, d_df, d_st, d_it, d_off, d_ca);
     ResolveP P{};
     P.cstart = d_off; P.ccount = d_cnt; P.cands = d_ca; P.qlist = d_ql; P.n_steps = n_steps; P.n_train = NF; P.tkeys = d_kf; P.qkeys = d_kk; P.tblocked = d_sf; P.nnratio = nnratio;
     P.check_orientation = check_orientation; P.train_match = d_out; P.q_match = d_out; P.q_rec = d_rec; P.nmatches = d_out + n_out;
-    MT_TRY(mt_resolve<V>(ctx, P, 1, NF));
-    MT_TRY(cs_d2h(ctx, res.data(), d_out, (size_t)n_out + 1));
-    MT_TRY(sc.drain());
+    CS_TRY(mt_resolve<V>(ctx, P, 1, NF));
+    CS_TRY(cs_d2h(ctx, res.data(), d_out, (size_t)n_out + 1));
+    CS_TRY(sc.drain());
     memcpy(out, res.data(), sizeof(int) * (size_t)n_out);
     *nmatches = res[(size_t)n_out];
     return CS_OK;
@@ -1386,15 +1352,15 @@ int cs_hamming_knn2(cs_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int
     if (!ctx || !q || !t || nq < 0 || nt < 0 || !best_idx || !best_dist || !second_dist) return CS_ERR_BAD_ARG;
     if (nq == 0) return CS_OK;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    MtScratch sc(ctx);
+    cs_scratch sc(ctx);
     unsigned long long *dq = nullptr, *dt = nullptr; int *dres = nullptr;
-    MT_TRY(sc.alloc(ctx, &dq, (size_t)nq * 4)); MT_TRY(sc.alloc(ctx, &dt, (size_t)std::max(nt, 1) * 4)); MT_TRY(sc.alloc(ctx, &dres, (size_t)nq * 3));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)dq, q, (size_t)nq * 32));
-    MT_TRY(cs_h2d(ctx, (uint8_t *)dt, t, (size_t)nt * 32));
+    CS_TRY(sc.alloc(ctx, &dq, (size_t)nq * 4)); CS_TRY(sc.alloc(ctx, &dt, (size_t)std::max(nt, 1) * 4)); CS_TRY(sc.alloc(ctx, &dres, (size_t)nq * 3));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)dq, q, (size_t)nq * 32));
+    CS_TRY(cs_h2d(ctx, (uint8_t *)dt, t, (size_t)nt * 32));
     CS_LAUNCH(ctx, "match_knn2", match_knn2, dim3((nq + 255) / 256), dim3(256), 0, dq, nq, dt, nt, dres, dres + nq, dres + 2 * nq);
-    MT_TRY(cs_d2h(ctx, best_idx, dres, (size_t)nq));
-    MT_TRY(cs_d2h(ctx, best_dist, dres + nq, (size_t)nq));
-    MT_TRY(cs_d2h(ctx, second_dist, dres + 2 * nq, (size_t)nq));
+    CS_TRY(cs_d2h(ctx, best_idx, dres, (size_t)nq));
+    CS_TRY(cs_d2h(ctx, best_dist, dres + nq, (size_t)nq));
+    CS_TRY(cs_d2h(ctx, second_dist, dres + 2 * nq, (size_t)nq));
     return sc.drain();
 }
 

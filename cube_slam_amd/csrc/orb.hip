@@ -1010,7 +1010,7 @@ void cs_orb_destroy(cs_ctx *ctx, cs_orb *e) {
     void *ptrs[] = {e->d_cell_mask, e->d_pyr, e->d_smap, e->d_blur, e->d_xofs, e->d_yofs, e->d_cell_count, e->d_cell_base, e->d_level_total, e->d_level_base,
                     e->d_ialpha, e->d_ibeta, e->d_cand, e->d_angle, e->d_sel, e->d_kps, e->d_desc, e->d_qperm, e->d_qtmp, e->d_slot_cnt, e->d_sel_base, e->d_qstatus,
                     e->d_qnodes, e->d_slots};
-    for (void *p : ptrs) if (p) hipFree(p);
+    for (void *p : ptrs) cs_dfree(ctx, p);
     delete e;
 }
 
@@ -1214,7 +1214,7 @@ int cs_orb_run(cs_ctx *ctx, cs_orb *e) {
     if (total > e->cand_cap) { ctx->err = "ORB candidate capacity exceeded"; return CS_ERR_CAPACITY; }
     if (total > e->cand_alloc) { // the second pass of orb_cells writes `total` candidates: room for them and a quarter more
         void *old[] = {e->d_cand, e->d_qperm, e->d_qtmp};
-        for (void *q : old) if (q) hipFree(q);
+        for (void *q : old) cs_dfree(ctx, q);
         e->d_cand = nullptr; e->d_qperm = nullptr; e->d_qtmp = nullptr; e->cand_alloc = 0;
         const long cap = std::min<long>(e->cand_cap, total + total / 4 + 4096);
         r = cs_dalloc(ctx, &e->d_cand, (size_t)cap * 3); if (r) return r;

@@ -291,16 +291,11 @@ __global__ void __launch_bounds__(EG_THREADS) sim3_log_kernel(int n, const doubl
     for (int k = 0; k < 7; k++) out[(long)v * 7 + k] = r[k];
 }
 
-template <class T> int eg_upload(cs_ctx *ctx, T **d, const std::vector<T> &h) {
-    int r = cs_dalloc(ctx, d, h.size());
-    if (!r) r = cs_h2d(ctx, *d, h.data(), h.size());
-    return r;
-}
-
 } // namespace
 
 struct cs_essential_graph {
     cs_ctx *ctx = nullptr;
+    cs_owner own;
     int n = 0, m = 0, fixed = 0, fix_scale = 0, nf = 0, nslots = 0, nLb = 0, nHb = 0, nlev = 0;
     struct Launch { int first, count, seq; };
     std::vector<Launch> launches; // over lev_cols, levels ascending
@@ -309,11 +304,6 @@ struct cs_essential_graph {
     uint8_t *d_kind = nullptr, *d_has = nullptr;
     double *d_H = nullptr, *d_L = nullptr, *d_b = nullptr, *d_y = nullptr, *d_x = nullptr, *d_X = nullptr, *d_Xt = nullptr, *d_C = nullptr, *d_e = nullptr, *d_chi = nullptr, *d_J = nullptr,
            *d_rec = nullptr, *d_Scw = nullptr, *d_Snc = nullptr;
-    void free_all() {
-        void *ptrs[] = {d_ei, d_ej, d_pos, d_inc_off, d_inc, d_slot_off, d_slot_edge, d_slot_blk, d_col_start, d_row_idx, d_upd_off, d_upd_a, d_upd_b, d_row_off, d_row_blk, d_row_col, d_lev_cols,
-                        d_status, d_kind, d_has, d_H, d_L, d_b, d_y, d_x, d_X, d_Xt, d_C, d_e, d_chi, d_J, d_rec, d_Scw, d_Snc};
-        for (void *q : ptrs) cs_dfree(ctx, q);
-    }
 };
 
 extern "C" {
@@ -420,35 +410,36 @@ int cs_essential_graph_create(cs_ctx *ctx, int n_vertices, int n_edges, const in
     if ((int)slot_blk.size() != nslots) { delete g; return CS_ERR_CAPACITY; }
     std::vector<int> vi(edge_i, edge_i + m), vj(edge_j, edge_j + m);
     std::vector<uint8_t> vk(edge_kind, edge_kind + m);
-    int r = eg_upload(ctx, &g->d_ei, vi);
-    if (!r) r = eg_upload(ctx, &g->d_ej, vj); if (!r) r = eg_upload(ctx, &g->d_kind, vk); if (!r) r = eg_upload(ctx, &g->d_pos, pos);
-    if (!r) r = eg_upload(ctx, &g->d_inc_off, inc_off); if (!r) r = eg_upload(ctx, &g->d_inc, inc);
-    if (!r) r = eg_upload(ctx, &g->d_slot_off, slot_off); if (!r) r = eg_upload(ctx, &g->d_slot_edge, slot_edge); if (!r) r = eg_upload(ctx, &g->d_slot_blk, slot_blk);
-    if (!r) r = eg_upload(ctx, &g->d_col_start, col_start); if (!r) r = eg_upload(ctx, &g->d_row_idx, row_idx);
-    if (!r) r = eg_upload(ctx, &g->d_upd_off, upd_off); if (!r) r = eg_upload(ctx, &g->d_upd_a, upd_a); if (!r) r = eg_upload(ctx, &g->d_upd_b, upd_b);
-    if (!r) r = eg_upload(ctx, &g->d_row_off, row_off); if (!r) r = eg_upload(ctx, &g->d_row_blk, row_blk); if (!r) r = eg_upload(ctx, &g->d_row_col, row_col);
-    if (!r) r = eg_upload(ctx, &g->d_lev_cols, lev_cols);
+    cs_owner &o = g->own;
+    int r = o.upload(ctx, &g->d_ei, vi.data(), vi.size());
+    if (!r) r = o.upload(ctx, &g->d_ej, vj.data(), vj.size()); if (!r) r = o.upload(ctx, &g->d_kind, vk.data(), vk.size()); if (!r) r = o.upload(ctx, &g->d_pos, pos.data(), pos.size());
+    if (!r) r = o.upload(ctx, &g->d_inc_off, inc_off.data(), inc_off.size()); if (!r) r = o.upload(ctx, &g->d_inc, inc.data(), inc.size());
+    if (!r) r = o.upload(ctx, &g->d_slot_off, slot_off.data(), slot_off.size()); if (!r) r = o.upload(ctx, &g->d_slot_edge, slot_edge.data(), slot_edge.size()); if (!r) r = o.upload(ctx, &g->d_slot_blk, slot_blk.data(), slot_blk.size());
+    if (!r) r = o.upload(ctx, &g->d_col_start, col_start.data(), col_start.size()); if (!r) r = o.upload(ctx, &g->d_row_idx, row_idx.data(), row_idx.size());
+    if (!r) r = o.upload(ctx, &g->d_upd_off, upd_off.data(), upd_off.size()); if (!r) r = o.upload(ctx, &g->d_upd_a, upd_a.data(), upd_a.size()); if (!r) r = o.upload(ctx, &g->d_upd_b, upd_b.data(), upd_b.size());
+    if (!r) r = o.upload(ctx, &g->d_row_off, row_off.data(), row_off.size()); if (!r) r = o.upload(ctx, &g->d_row_blk, row_blk.data(), row_blk.size()); if (!r) r = o.upload(ctx, &g->d_row_col, row_col.data(), row_col.size());
+    if (!r) r = o.upload(ctx, &g->d_lev_cols, lev_cols.data(), lev_cols.size());
     const size_t N = (size_t)n, M = (size_t)m, NF = (size_t)nf, LB = (size_t)nLb;
-    if (!r) r = cs_dalloc(ctx, &g->d_status, 1); if (!r) r = cs_dalloc(ctx, &g->d_has, N);
-    if (!r) r = cs_dalloc(ctx, &g->d_H, LB * 49); if (!r) r = cs_dalloc(ctx, &g->d_L, LB * 49);
-    if (!r) r = cs_dalloc(ctx, &g->d_b, NF * 7); if (!r) r = cs_dalloc(ctx, &g->d_y, NF * 7); if (!r) r = cs_dalloc(ctx, &g->d_x, NF * 7);
-    if (!r) r = cs_dalloc(ctx, &g->d_X, N * 8); if (!r) r = cs_dalloc(ctx, &g->d_Xt, N * 8); if (!r) r = cs_dalloc(ctx, &g->d_Scw, N * 8); if (!r) r = cs_dalloc(ctx, &g->d_Snc, N * 8);
-    if (!r) r = cs_dalloc(ctx, &g->d_C, M * 8); if (!r) r = cs_dalloc(ctx, &g->d_e, M * 7); if (!r) r = cs_dalloc(ctx, &g->d_chi, M); if (!r) r = cs_dalloc(ctx, &g->d_J, M * 98);
-    if (!r) r = cs_dalloc(ctx, &g->d_rec, 4);
+    if (!r) r = o.alloc(ctx, &g->d_status, 1); if (!r) r = o.alloc(ctx, &g->d_has, N);
+    if (!r) r = o.alloc(ctx, &g->d_H, LB * 49); if (!r) r = o.alloc(ctx, &g->d_L, LB * 49);
+    if (!r) r = o.alloc(ctx, &g->d_b, NF * 7); if (!r) r = o.alloc(ctx, &g->d_y, NF * 7); if (!r) r = o.alloc(ctx, &g->d_x, NF * 7);
+    if (!r) r = o.alloc(ctx, &g->d_X, N * 8); if (!r) r = o.alloc(ctx, &g->d_Xt, N * 8); if (!r) r = o.alloc(ctx, &g->d_Scw, N * 8); if (!r) r = o.alloc(ctx, &g->d_Snc, N * 8);
+    if (!r) r = o.alloc(ctx, &g->d_C, M * 8); if (!r) r = o.alloc(ctx, &g->d_e, M * 7); if (!r) r = o.alloc(ctx, &g->d_chi, M); if (!r) r = o.alloc(ctx, &g->d_J, M * 98);
+    if (!r) r = o.alloc(ctx, &g->d_rec, 4);
     if (!r) { // the fill-in blocks of H stay zero: eg_assemble writes the others
         const hipError_t e = hipMemsetAsync(g->d_H, 0, LB * 49 * sizeof(double), ctx->stream);
         if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
     }
     const hipError_t e = hipStreamSynchronize(ctx->stream); // the host vectors above go out of scope
     if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    if (r) { g->free_all(); delete g; return r; }
+    if (r) { g->own.free_all(ctx); delete g; return r; }
     *out = g;
     return CS_OK;
 }
 
 void cs_essential_graph_destroy(cs_essential_graph *eg) {
     if (!eg) return;
-    eg->free_all();
+    eg->own.free_all(eg->ctx);
     delete eg;
 }
 
@@ -546,38 +537,31 @@ int cs_sim3_correct_points(cs_ctx *ctx, int n_points, const double *P, const int
     if (n_points == 0) return CS_OK;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)n_vertices, NP = (size_t)n_points;
+    cs_scratch sc(ctx);
     double *d_S = nullptr, *d_C = nullptr, *d_Ci = nullptr, *d_P = nullptr; int *d_ref = nullptr; float *d_out = nullptr;
-    int r = cs_dalloc(ctx, &d_S, N * 8);
-    if (!r) r = cs_dalloc(ctx, &d_C, N * 8); if (!r) r = cs_dalloc(ctx, &d_Ci, N * 8); if (!r) r = cs_dalloc(ctx, &d_P, NP * 3); if (!r) r = cs_dalloc(ctx, &d_ref, NP); if (!r) r = cs_dalloc(ctx, &d_out, NP * 3);
-    if (!r) r = cs_h2d(ctx, d_S, Scw, N * 8); if (!r) r = cs_h2d(ctx, d_C, sim3_out, N * 8); if (!r) r = cs_h2d(ctx, d_P, P, NP * 3); if (!r) r = cs_h2d(ctx, d_ref, ref_vertex, NP);
-    if (!r) {
-        CS_LAUNCH(ctx, "sim3_inverse_kernel", sim3_inverse_kernel, dim3((n_vertices + EG_THREADS - 1) / EG_THREADS), dim3(EG_THREADS), 0, n_vertices, d_C, d_Ci);
-        CS_LAUNCH(ctx, "sim3_correct_points_kernel", sim3_correct_points_kernel, dim3((n_points + EG_THREADS - 1) / EG_THREADS), dim3(EG_THREADS), 0, n_points, d_P, d_ref, d_S, d_Ci, d_out);
-        r = cs_d2h(ctx, P_out, d_out, NP * 3);
-    }
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_S, d_C, d_Ci, d_P, d_ref, d_out};
-    for (void *q : ptrs) cs_dfree(ctx, q);
-    return r;
+    CS_TRY(sc.alloc(ctx, &d_S, N * 8)); CS_TRY(sc.alloc(ctx, &d_C, N * 8)); CS_TRY(sc.alloc(ctx, &d_Ci, N * 8)); CS_TRY(sc.alloc(ctx, &d_P, NP * 3)); CS_TRY(sc.alloc(ctx, &d_ref, NP)); CS_TRY(sc.alloc(ctx, &d_out, NP * 3));
+    CS_TRY(cs_h2d(ctx, d_S, Scw, N * 8)); CS_TRY(cs_h2d(ctx, d_C, sim3_out, N * 8)); CS_TRY(cs_h2d(ctx, d_P, P, NP * 3)); CS_TRY(cs_h2d(ctx, d_ref, ref_vertex, NP));
+    CS_LAUNCH(ctx, "sim3_inverse_kernel", sim3_inverse_kernel, dim3((n_vertices + EG_THREADS - 1) / EG_THREADS), dim3(EG_THREADS), 0, n_vertices, d_C, d_Ci);
+    CS_LAUNCH(ctx, "sim3_correct_points_kernel", sim3_correct_points_kernel, dim3((n_points + EG_THREADS - 1) / EG_THREADS), dim3(EG_THREADS), 0, n_points, d_P, d_ref, d_S, d_Ci, d_out);
+    CS_TRY(cs_d2h(ctx, P_out, d_out, NP * 3));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 int cs_sim3_log(cs_ctx *ctx, int n, const double *sim3, double *log_out) {
     if (!ctx || n < 0 || (n && (!sim3 || !log_out))) return CS_ERR_BAD_ARG;
     if (n == 0) return CS_OK;
     CS_HIP(ctx, hipSetDevice(ctx->device));
+    cs_scratch sc(ctx);
     double *d_S = nullptr, *d_o = nullptr;
-    int r = cs_dalloc(ctx, &d_S, (size_t)n * 8);
-    if (!r) r = cs_dalloc(ctx, &d_o, (size_t)n * 7);
-    if (!r) r = cs_h2d(ctx, d_S, sim3, (size_t)n * 8);
-    if (!r) {
-        CS_LAUNCH(ctx, "sim3_log_kernel", sim3_log_kernel, dim3((n + EG_THREADS - 1) / EG_THREADS), dim3(EG_THREADS), 0, n, d_S, d_o);
-        r = cs_d2h(ctx, log_out, d_o, (size_t)n * 7);
-    }
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    cs_dfree(ctx, d_S); cs_dfree(ctx, d_o);
-    return r;
+    CS_TRY(sc.alloc(ctx, &d_S, (size_t)n * 8)); CS_TRY(sc.alloc(ctx, &d_o, (size_t)n * 7));
+    CS_TRY(cs_h2d(ctx, d_S, sim3, (size_t)n * 8));
+    CS_LAUNCH(ctx, "sim3_log_kernel", sim3_log_kernel, dim3((n + EG_THREADS - 1) / EG_THREADS), dim3(EG_THREADS), 0, n, d_S, d_o);
+    CS_TRY(cs_d2h(ctx, log_out, d_o, (size_t)n * 7));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 } // extern "C"

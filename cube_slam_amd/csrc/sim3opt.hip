@@ -260,25 +260,22 @@ int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const
     Sim3Problem *d_pr = nullptr; double *d_p1 = nullptr, *d_p2 = nullptr, *d_o1 = nullptr, *d_o2 = nullptr, *d_w1 = nullptr, *d_w2 = nullptr, *d_in = nullptr, *d_out = nullptr, *d_err = nullptr;
     uint8_t *d_rem = nullptr; int *d_ni = nullptr;
     const size_t ne1 = (size_t)std::max(ne, 1), np = (size_t)n_problems, nz = (size_t)ne;
-    int r = cs_dalloc(ctx, &d_pr, np);
-    if (!r) r = cs_dalloc(ctx, &d_p1, ne1 * 3); if (!r) r = cs_dalloc(ctx, &d_p2, ne1 * 3); if (!r) r = cs_dalloc(ctx, &d_o1, ne1 * 2); if (!r) r = cs_dalloc(ctx, &d_o2, ne1 * 2);
-    if (!r) r = cs_dalloc(ctx, &d_w1, ne1); if (!r) r = cs_dalloc(ctx, &d_w2, ne1); if (!r) r = cs_dalloc(ctx, &d_err, ne1 * 4); if (!r) r = cs_dalloc(ctx, &d_rem, ne1);
-    if (!r) r = cs_dalloc(ctx, &d_in, np * 8); if (!r) r = cs_dalloc(ctx, &d_out, np * 8); if (!r) r = cs_dalloc(ctx, &d_ni, np);
-    if (!r) r = cs_h2d(ctx, d_pr, pr.data(), np);
-    if (!r) r = cs_h2d(ctx, d_p1, P1c, nz * 3); if (!r) r = cs_h2d(ctx, d_p2, P2c, nz * 3); if (!r) r = cs_h2d(ctx, d_o1, obs1, nz * 2); if (!r) r = cs_h2d(ctx, d_o2, obs2, nz * 2);
-    if (!r) r = cs_h2d(ctx, d_w1, inv_sigma2_1, nz); if (!r) r = cs_h2d(ctx, d_w2, inv_sigma2_2, nz);
-    if (!r) r = cs_h2d(ctx, d_in, sim3_in, np * 8);
-    if (!r) {
-        CS_LAUNCH(ctx, "sim3_opt_kernel", sim3_opt_kernel, dim3(n_problems), dim3(SIM3_THREADS), 0, d_pr, d_p1, d_p2, d_o1, d_o2, d_w1, d_w2, d_in, d_out, d_rem, d_ni, d_err);
-        r = cs_d2h(ctx, sim3_out, d_out, np * 8);
-        if (!r) r = cs_d2h(ctx, removed, d_rem, nz);
-        if (!r) r = cs_d2h(ctx, n_inliers, d_ni, np);
-    }
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
-    void *ptrs[] = {d_pr, d_p1, d_p2, d_o1, d_o2, d_w1, d_w2, d_in, d_out, d_err, d_rem, d_ni};
-    for (void *q : ptrs) cs_dfree(ctx, q);
-    return r;
+    cs_scratch sc(ctx); // (after the host array: it waits for the copy out of it before it goes)
+    CS_TRY(sc.alloc(ctx, &d_pr, np));
+    CS_TRY(sc.alloc(ctx, &d_p1, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_p2, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_o1, ne1 * 2)); CS_TRY(sc.alloc(ctx, &d_o2, ne1 * 2));
+    CS_TRY(sc.alloc(ctx, &d_w1, ne1)); CS_TRY(sc.alloc(ctx, &d_w2, ne1)); CS_TRY(sc.alloc(ctx, &d_err, ne1 * 4)); CS_TRY(sc.alloc(ctx, &d_rem, ne1));
+    CS_TRY(sc.alloc(ctx, &d_in, np * 8)); CS_TRY(sc.alloc(ctx, &d_out, np * 8)); CS_TRY(sc.alloc(ctx, &d_ni, np));
+    CS_TRY(cs_h2d(ctx, d_pr, pr.data(), np));
+    CS_TRY(cs_h2d(ctx, d_p1, P1c, nz * 3)); CS_TRY(cs_h2d(ctx, d_p2, P2c, nz * 3)); CS_TRY(cs_h2d(ctx, d_o1, obs1, nz * 2)); CS_TRY(cs_h2d(ctx, d_o2, obs2, nz * 2));
+    CS_TRY(cs_h2d(ctx, d_w1, inv_sigma2_1, nz)); CS_TRY(cs_h2d(ctx, d_w2, inv_sigma2_2, nz));
+    CS_TRY(cs_h2d(ctx, d_in, sim3_in, np * 8));
+    CS_LAUNCH(ctx, "sim3_opt_kernel", sim3_opt_kernel, dim3(n_problems), dim3(SIM3_THREADS), 0, d_pr, d_p1, d_p2, d_o1, d_o2, d_w1, d_w2, d_in, d_out, d_rem, d_ni, d_err);
+    CS_TRY(cs_d2h(ctx, sim3_out, d_out, np * 8));
+    CS_TRY(cs_d2h(ctx, removed, d_rem, nz));
+    CS_TRY(cs_d2h(ctx, n_inliers, d_ni, np));
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
 }
 
 } // extern "C"

@@ -229,6 +229,7 @@ __global__ void __launch_bounds__(256) stereo_cut(const PairRec *__restrict__ pa
 
 struct cs_stereo {
     int cap = 0, max_pairs = 0;
+    cs_owner own;
     // device
     float *d_u_right = nullptr, *d_depth = nullptr;
     int *d_sad = nullptr, *d_best = nullptr, *d_n_matched = nullptr, *d_lvl = nullptr;
@@ -244,8 +245,7 @@ extern "C" {
 void cs_stereo_destroy(cs_ctx *ctx, cs_stereo *s) {
     if (!s) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    void *ptrs[] = {s->d_u_right, s->d_depth, s->d_sad, s->d_best, s->d_n_matched, s->d_rec, s->d_pairs, s->d_lvl};
-    for (void *p : ptrs) if (p) hipFree(p);
+    s->own.free_all(ctx);
     delete s;
 }
 
@@ -258,11 +258,10 @@ int cs_stereo_create(cs_ctx *ctx, int max_keypoints_per_frame, int max_pairs, cs
     s->cap = max_keypoints_per_frame; s->max_pairs = max_pairs;
     const size_t n = (size_t)max_keypoints_per_frame * max_pairs;
     int r = CS_OK;
-    if (hipMalloc((void **)&s->d_u_right, n * sizeof(float)) != hipSuccess || hipMalloc((void **)&s->d_depth, n * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&s->d_sad, n * sizeof(int)) != hipSuccess || hipMalloc((void **)&s->d_best, n * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&s->d_rec, n * sizeof(RightRec)) != hipSuccess || hipMalloc((void **)&s->d_n_matched, (size_t)max_pairs * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&s->d_pairs, (size_t)max_pairs * sizeof(PairRec)) != hipSuccess ||
-        hipMalloc((void **)&s->d_lvl, (size_t)max_pairs * (CS_ORB_MAX_LEVELS + 1) * sizeof(int)) != hipSuccess) {
+    cs_owner &o = s->own;
+    if (o.alloc(ctx, &s->d_u_right, n) != CS_OK || o.alloc(ctx, &s->d_depth, n) != CS_OK || o.alloc(ctx, &s->d_sad, n) != CS_OK || o.alloc(ctx, &s->d_best, n) != CS_OK ||
+        o.alloc(ctx, &s->d_rec, n) != CS_OK || o.alloc(ctx, &s->d_n_matched, (size_t)max_pairs) != CS_OK || o.alloc(ctx, &s->d_pairs, (size_t)max_pairs) != CS_OK ||
+        o.alloc(ctx, &s->d_lvl, (size_t)max_pairs * (CS_ORB_MAX_LEVELS + 1)) != CS_OK) { // this call reports a failed allocation as CS_ERR_NOMEM with its own message
         (void)hipGetLastError();
         ctx->err = "cs_stereo_create: out of device memory";
         r = CS_ERR_NOMEM;

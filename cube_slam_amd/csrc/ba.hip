@@ -22,6 +22,7 @@
 //   ba_update         oplus per vertex (cameras: exp(dx) * T; cuboids: T * exp(dx) with the fix-roll-pitch / height / scale flags)
 #include "common.h"
 #include "ba_cr.h"
+#include "lm_schedule.h"
 #include "se3_math.h"
 
 #include <algorithm>
@@ -78,16 +79,6 @@ __device__ inline void err_pc_eval(const Params &G, int o, const Cuboid &c, doub
     if (b1 > b0) for (int k = 0; k < 3; k++) acc[k] = acc[k] / (double)(b1 - b0);
     for (int k = 0; k < 3; k++) e[k] = 1.0 * (acc[k] / c.scale[k]);
 }
-
-// block partial sums, then a fixed-order final sum on the host side of the tiny partial array
-__device__ inline void block_sum_store(double v, double *partials, int bid) {
-    __shared__ double s[4];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[bid] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-__device__ inline void block_sum_store(double v, double *partials) { block_sum_store(v, partials, (int)blockIdx.x); }
 
 __device__ inline bool obs_stereo(const Params &G, int o) { return G.o_ur && G.o_ur[o] >= 0; }
 __device__ __forceinline__ void ba_err_obs_body(const Params &G, double *partials, const int bid) {
@@ -1224,177 +1215,6 @@ __global__ void __launch_bounds__(64) cub9_edge_kernel(int n, int with_jac, cons
     }
 }
 
-// ------------------------------------------------------------------------------------------------ Optimizer::PoseOptimization
-// One workgroup per frame runs the whole routine (Optimizer.cc:253-472): 4 rounds x up to 10 Levenberg-Marquardt iterations of a
-// single 6-dof pose over the frame's map-point matches, inlier / outlier re-classification after every round.  Edges are strided
-// over the 256 threads; the 6x6 normal equations and chi2 are reduced in a fixed order (thread partials in edge order, then a
-// shuffle tree, then the four wave results); thread 0 solves the damped system and every LM decision is broadcast through LDS.
-struct PoseFrame { int e0, e1; double fx, fy, cx, cy, bf; };
-__device__ __forceinline__ void pose_edge_eval(const SE3 &T, const double *Xw, const double *ob, const PoseFrame &F, double *e) {
-    double pc[3];
-    se3_map(T, Xw, pc);
-    if (ob[2] >= 0) { // EdgeStereoSE3ProjectXYZOnlyPose::cam_project (types_six_dof_expmap.cpp:331-338): invz is a float there
-        const float invz = (float)(1.0 / pc[2]);
-        const double u = pc[0] * invz * F.fx + F.cx;
-        e[0] = ob[0] - u;
-        e[1] = ob[1] - (pc[1] * invz * F.fy + F.cy);
-        e[2] = ob[2] - (u - F.bf * invz);
-    } else { // EdgeSE3ProjectXYZOnlyPose::cam_project over project2d (:37-42, 322-328): a division per coordinate
-        e[0] = ob[0] - (pc[0] / pc[2] * F.fx + F.cx);
-        e[1] = ob[1] - (pc[1] / pc[2] * F.fy + F.cy);
-        e[2] = 0.0;
-    }
-}
-__device__ __forceinline__ double pose_edge_chi2(const double *e, double w, bool stereo) {
-    return stereo ? ((e[0] * w * e[0] + e[1] * w * e[1]) + e[2] * w * e[2]) : (e[0] * w * e[0] + e[1] * w * e[1]);
-}
-template <int N> __device__ __forceinline__ void pose_block_reduce(double (&v)[N], double *s_red /* 4 x N */, double *s_out /* N */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-    if (lane == 0) for (int k = 0; k < N; k++) s_red[wave * N + k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < N) s_out[threadIdx.x] = (s_red[threadIdx.x] + s_red[N + threadIdx.x]) + (s_red[2 * N + threadIdx.x] + s_red[3 * N + threadIdx.x]);
-    __syncthreads();
-}
-__global__ void __launch_bounds__(256) pose_opt_kernel(const PoseFrame *frames, const double *Xw, const double *obs, const double *wgt, const double *pose_in, double *pose_out,
-                                                       uint8_t *outlier, int *n_inliers, double *err /* per edge x 3 */) {
-    __shared__ double s_red[4 * 28], s_sys[28]; // 21 upper-triangle entries of H, 6 of b, 1 chi2
-    __shared__ double s_x[6], s_T[7];
-    __shared__ int s_flag;
-    const PoseFrame F = frames[blockIdx.x];
-    const int n = F.e1 - F.e0, tid = threadIdx.x;
-    const double *X = Xw + (long)F.e0 * 3, *O = obs + (long)F.e0 * 3, *W = wgt + F.e0;
-    double *E = err + (long)F.e0 * 3;
-    uint8_t *out = outlier + F.e0;
-    for (int i = tid; i < n; i += 256) out[i] = 0;
-    SE3 T0 = se3_load(pose_in + (long)blockIdx.x * 7);
-    normalize_rotation(T0);
-    if (n < 3) { if (tid == 0) { se3_store(T0, pose_out + (long)blockIdx.x * 7); n_inliers[blockIdx.x] = 0; } return; }
-    const double dMono = (double)(float)sqrt(5.991), dStereo = (double)(float)sqrt(7.815);
-    bool robust = true;
-    SE3 T = T0;
-    int nBadEdges = 0;
-    __syncthreads();
-    auto chi2_sum = [&](const SE3 &Tc) -> double { // computeActiveErrors + activeRobustChi2
-        double v[1] = {0};
-        for (int i = tid; i < n; i += 256) {
-            if (out[i]) continue;
-            double e[3];
-            pose_edge_eval(Tc, X + (long)i * 3, O + (long)i * 3, F, e);
-            E[(long)i * 3] = e[0]; E[(long)i * 3 + 1] = e[1]; E[(long)i * 3 + 2] = e[2];
-            const bool st = O[(long)i * 3 + 2] >= 0;
-            double c = pose_edge_chi2(e, W[i], st);
-            if (robust) { const double d = st ? dStereo : dMono, dsqr = d * d; if (c > dsqr) c = 2 * sqrt(c) * d - dsqr; }
-            v[0] += c;
-        }
-        pose_block_reduce<1>(v, s_red, s_sys + 27);
-        return s_sys[27];
-    };
-    for (int round = 0; round < 4; round++) {
-        T = T0;
-        double lambda = 0, ni = 2;
-        int nBad = 0;
-        for (int it = 0; it < 10; it++) { // OptimizationAlgorithmLevenberg::solve
-            double currentChi = chi2_sum(T);
-            const double iniChi = currentChi;
-            double acc[27];
-#pragma unroll
-            for (int k = 0; k < 27; k++) acc[k] = 0;
-            for (int i = tid; i < n; i += 256) { // linearizeOplus + constructQuadraticForm
-                if (out[i]) continue;
-                double pc[3], J[18];
-                se3_map(T, X + (long)i * 3, pc);
-                const double x = pc[0], y = pc[1], invz = 1.0 / pc[2], invz_2 = invz * invz;
-                J[0] = x * y * invz_2 * F.fx; J[1] = -(1 + (x * x * invz_2)) * F.fx; J[2] = y * invz * F.fx; J[3] = -invz * F.fx; J[4] = 0; J[5] = x * invz_2 * F.fx;
-                J[6] = (1 + y * y * invz_2) * F.fy; J[7] = -x * y * invz_2 * F.fy; J[8] = -x * invz * F.fy; J[9] = 0; J[10] = -invz * F.fy; J[11] = y * invz_2 * F.fy;
-                const bool st = O[(long)i * 3 + 2] >= 0;
-                if (st) { J[12] = J[0] - F.bf * y * invz_2; J[13] = J[1] + F.bf * x * invz_2; J[14] = J[2]; J[15] = J[3]; J[16] = 0; J[17] = J[5] - F.bf * invz_2; }
-                else { for (int k = 12; k < 18; k++) J[k] = 0; }
-                const double e[3] = {E[(long)i * 3], E[(long)i * 3 + 1], E[(long)i * 3 + 2]}, w = W[i];
-                double rw = 1.0;
-                if (robust) { const double c = pose_edge_chi2(e, w, st), d = st ? dStereo : dMono; if (c > d * d) rw = d / sqrt(c); }
-                int k = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int c2 = a; c2 < 6; c2++) { acc[k] += (J[a] * (rw * w) * J[c2] + J[6 + a] * (rw * w) * J[6 + c2]) + J[12 + a] * (rw * w) * J[12 + c2]; k++; }
-                }
-#pragma unroll
-                for (int a = 0; a < 6; a++) acc[21 + a] += rw * ((J[a] * (-(w * e[0])) + J[6 + a] * (-(w * e[1]))) + J[12 + a] * (-(w * e[2])));
-            }
-            pose_block_reduce<27>(acc, s_red, s_sys);
-            if (it == 0) { double mx = 0; int k = 0; for (int a = 0; a < 6; a++) { mx = fmax(fabs(s_sys[k]), mx); k += 6 - a; } lambda = 1e-5 * mx; ni = 2; nBad = 0; }
-            double rho = 0;
-            int qmax = 0;
-            do {
-                const SE3 backup = T;
-                if (tid == 0) { // (H + lambda I) x = b, Cholesky
-                    double L[36], y6[6], x6[6] = {0, 0, 0, 0, 0, 0};
-                    int k = 0;
-                    for (int a = 0; a < 6; a++) for (int c2 = a; c2 < 6; c2++) { L[c2 * 6 + a] = s_sys[k]; L[a * 6 + c2] = s_sys[k]; k++; }
-                    for (int a = 0; a < 6; a++) L[a * 6 + a] += lambda;
-                    bool ok = true;
-                    for (int c2 = 0; c2 < 6 && ok; c2++) {
-                        double d = L[c2 * 6 + c2];
-                        for (int t = 0; t < c2; t++) d -= L[c2 * 6 + t] * L[c2 * 6 + t];
-                        if (!(d > 0)) { ok = false; break; }
-                        d = sqrt(d); L[c2 * 6 + c2] = d;
-                        for (int r = c2 + 1; r < 6; r++) { double v = L[r * 6 + c2]; for (int t = 0; t < c2; t++) v -= L[r * 6 + t] * L[c2 * 6 + t]; L[r * 6 + c2] = v / d; }
-                    }
-                    if (ok) {
-                        for (int r = 0; r < 6; r++) { double v = s_sys[21 + r]; for (int t = 0; t < r; t++) v -= L[r * 6 + t] * y6[t]; y6[r] = v / L[r * 6 + r]; }
-                        for (int r = 5; r >= 0; r--) { double v = y6[r]; for (int t = r + 1; t < 6; t++) v -= L[t * 6 + r] * x6[t]; x6[r] = v / L[r * 6 + r]; }
-                    }
-                    for (int r = 0; r < 6; r++) s_x[r] = x6[r];
-                    s_flag = ok ? 1 : 0;
-                    const SE3 Tn = ok ? se3_mul(se3_exp(x6), T) : T; // VertexSE3Expmap::oplusImpl
-                    se3_store(Tn, s_T);
-                }
-                __syncthreads();
-                const bool ok2 = s_flag != 0;
-                T = se3_load(s_T);
-                double tempChi = chi2_sum(T);
-                if (!ok2) tempChi = DBL_MAX;
-                rho = currentChi - tempChi;
-                double scale = 0;
-                for (int j = 0; j < 6; j++) scale += s_x[j] * (lambda * s_x[j] + s_sys[21 + j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow((2 * rho - 1), 3);
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2; currentChi = tempChi;
-                } else { lambda *= ni; ni *= 2; T = backup; }
-                qmax++;
-                __syncthreads(); // s_x / s_sys[21..] are rewritten by the next trial
-            } while (rho < 0 && qmax < 10);
-            if (qmax == 10 || rho == 0) break;
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-            if (nBad >= 3) break;
-        }
-        // classification (Optimizer.cc:401-431): outliers are re-evaluated at the final estimate, inliers keep the error of the last trial
-        double cnt[1] = {0};
-        for (int i = tid; i < n; i += 256) {
-            double e[3];
-            if (out[i]) { pose_edge_eval(T, X + (long)i * 3, O + (long)i * 3, F, e); E[(long)i * 3] = e[0]; E[(long)i * 3 + 1] = e[1]; E[(long)i * 3 + 2] = e[2]; }
-            else { e[0] = E[(long)i * 3]; e[1] = E[(long)i * 3 + 1]; e[2] = E[(long)i * 3 + 2]; }
-            const bool st = O[(long)i * 3 + 2] >= 0;
-            const float chi2 = (float)pose_edge_chi2(e, W[i], st);
-            const bool bad = chi2 > (st ? 7.815f : 5.991f);
-            out[i] = bad ? 1 : 0;
-            cnt[0] += bad ? 1.0 : 0.0;
-        }
-        pose_block_reduce<1>(cnt, s_red, s_sys + 27);
-        nBadEdges = (int)s_sys[27];
-        __syncthreads();
-        if (round == 2) robust = false;
-        if (n < 10) break;
-    }
-    if (tid == 0) { se3_store(T, pose_out + (long)blockIdx.x * 7); n_inliers[blockIdx.x] = n - nBadEdges; }
-}
-
 struct cs_ba {
     Params G{};
     int rank = 0, world = 1, n_slots = 0, max_col = 0, max_part = 0;
@@ -1966,8 +1786,9 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
     const Params &G = b->G;
     cs_ba_stats S;
     memset(&S, 0, sizeof(S));
-    double lambda = 0, ni = 2, currentChi = 0;
-    int nBad = 0, r;
+    double currentChi = 0;
+    int r;
+    LmSchedule lm;
     const int nl = G.lm_e - G.lm_b;
     auto terminate = [&]() { return (stop_flag && *stop_flag) || (b->stop8 && *b->stop8); }; // sparse_optimizer.cpp:376, optimization_algorithm_levenberg.cpp:149
     // A trial is accepted nearly always, and the next iteration then starts by linearising at the state the trial left.  So that system is BUILT AHEAD: enqueued behind the
@@ -2002,10 +1823,9 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
                 for (double d : buf) mx = std::max(mx, std::fabs(d));
             } else
                 for (int i = 0; i < G.P; i++) for (int k = 0; k < 6; k++) mx = std::max(mx, std::fabs(hpp[(size_t)i * 36 + k * 7]));
-            lambda = 1e-5 * mx; ni = 2; nBad = 0;
+            lm.start(1e-5 * mx);
         }
-        double rho = 0;
-        int qmax = 0;
+        lm.begin_iteration();
         do {
             // push(): back up the estimates
             CS_HIP(ctx, hipMemcpyAsync(b->d_bak_cam, G.cam, sizeof(double) * (size_t)G.n_cams * 7, hipMemcpyDeviceToDevice, ctx->stream));
@@ -2015,9 +1835,9 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
             const int nbs = (int)(((long)G.P * 6 + (long)nl * 3 + 255) / 256);
             double scale;
             if (b->world == 1) { // one host round trip per trial: solve, scale, update and the new residuals are enqueued back to back
-                r = ba_solve(ctx, b, lambda, &ok2, true); if (r) return r;
+                r = ba_solve(ctx, b, lm.lambda, &ok2, true); if (r) return r;
                 const int nb1 = (G.o_e - G.o_b + 255) / 256, nb2 = (G.pose_edges && G.n_cobs + G.n_pc > 0) ? (G.n_cobs + G.n_pc + 255) / 256 : 0, mp = b->max_part;
-                CS_LAUNCH(ctx, "ba_update", ba_scale_update, dim3(nbs + (G.n_cams + G.n_cub + nl * 3 + 255) / 256), dim3(256), 0, G, lambda, b->d_partials, nbs);
+                CS_LAUNCH(ctx, "ba_update", ba_scale_update, dim3(nbs + (G.n_cams + G.n_cub + nl * 3 + 255) / 256), dim3(256), 0, G, lm.lambda, b->d_partials, nbs);
                 if (nb1 > 0) CS_LAUNCH(ctx, "ba_err_obs", ba_err_obs, dim3(nb1), dim3(256), 0, G, b->d_partials + mp);
                 if (nb2 > 0) CS_LAUNCH(ctx, "ba_err_pose_edges", ba_err_pose_edges, dim3(nb2), dim3(256), 0, G, b->d_partials + 2 * mp); // (one grid for both measured no faster: 36 us against 14 + 20, the cuboid edges' registers halve the reprojection edges' occupancy)
                 const size_t need = (size_t)mp * 3 + 1;
@@ -2046,27 +1866,14 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
                 if (nb2 > 0) chi += c2;
                 tempChi = chi;
             } else {
-                r = ba_solve(ctx, b, lambda, &ok2); if (r) return r;
-                CS_LAUNCH(ctx, "ba_scale", ba_scale, dim3(nbs), dim3(256), 0, G, lambda, b->d_partials);
+                r = ba_solve(ctx, b, lm.lambda, &ok2); if (r) return r;
+                CS_LAUNCH(ctx, "ba_scale", ba_scale, dim3(nbs), dim3(256), 0, G, lm.lambda, b->d_partials);
                 scale = sum_partials(ctx, b, nbs);
                 r = allreduce_scalars(ctx, b, &scale, 1); if (r) return r;
                 CS_LAUNCH(ctx, "ba_update", ba_update, dim3((G.n_cams + G.n_cub + nl * 3 + 255) / 256), dim3(256), 0, G);
                 r = ba_compute_errors(ctx, b, &tempChi); if (r) return r;
             }
-            if (!ok2) tempChi = std::numeric_limits<double>::max();
-            rho = (currentChi - tempChi);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = (std::min)(alpha, 2. / 3.);
-                const double scaleFactor = (std::max)(1. / 3., alpha);
-                lambda *= scaleFactor;
-                ni = 2;
-                currentChi = tempChi; // discardTop
-            } else {
-                lambda *= ni;
-                ni *= 2; // pop(): restore
+            if (!lm.trial(currentChi, tempChi, ok2, scale)) { // pop(): restore (an accepted trial's state stands: discardTop)
                 CS_HIP(ctx, hipMemcpyAsync(G.cam, b->d_bak_cam, sizeof(double) * (size_t)G.n_cams * 7, hipMemcpyDeviceToDevice, ctx->stream));
                 if (G.L) CS_HIP(ctx, hipMemcpyAsync(G.pts, b->d_bak_pts, sizeof(double) * (size_t)G.L * 3, hipMemcpyDeviceToDevice, ctx->stream));
                 if (G.n_cub) CS_HIP(ctx, hipMemcpyAsync(G.cub, b->d_bak_cub, sizeof(double) * (size_t)G.n_cub * 7, hipMemcpyDeviceToDevice, ctx->stream));
@@ -2076,49 +1883,16 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
                     built_ahead = false;
                 }
             }
-            qmax++;
             S.lm_trials++;
-        } while (rho < 0 && qmax < 10 && !terminate());
+        } while (lm.retry() && !terminate());
         S.iterations = it + 1;
         if (it < 64) S.chi2_trace[it] = currentChi;
         S.chi2_final = currentChi;
-        if (qmax == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; // stop criterion :155-161
-        if (nBad >= 3) break;
+        if (lm.stop(iniChi, currentChi)) break; // :151-161
     }
-    S.lambda_final = lambda;
+    S.lambda_final = lm.lambda;
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (st) *st = S;
-    return CS_OK;
-}
-
-int cs_pose_optimization(cs_ctx *ctx, int n_frames, const int *edge_off, const double *Xw, const double *obs, const double *inv_sigma2, const double *intrinsics,
-                         const double *pose_in, double *pose_out, uint8_t *outlier, int *n_inliers) {
-    if (!ctx || n_frames < 0 || !edge_off || (n_frames && (!intrinsics || !pose_in || !pose_out || !n_inliers))) return CS_ERR_BAD_ARG;
-    if (n_frames == 0) return CS_OK;
-    CS_HIP(ctx, hipSetDevice(ctx->device));
-    const int ne = edge_off[n_frames];
-    for (int f = 0; f < n_frames; f++) if (edge_off[f + 1] < edge_off[f]) return CS_ERR_BAD_ARG;
-    if (ne > 0 && (!Xw || !obs || !inv_sigma2 || !outlier)) return CS_ERR_BAD_ARG;
-    std::vector<PoseFrame> fr((size_t)n_frames);
-    for (int f = 0; f < n_frames; f++) { fr[f].e0 = edge_off[f]; fr[f].e1 = edge_off[f + 1]; fr[f].fx = intrinsics[f * 5]; fr[f].fy = intrinsics[f * 5 + 1]; fr[f].cx = intrinsics[f * 5 + 2]; fr[f].cy = intrinsics[f * 5 + 3]; fr[f].bf = intrinsics[f * 5 + 4]; }
-    PoseFrame *d_fr = nullptr; double *d_X = nullptr, *d_o = nullptr, *d_w = nullptr, *d_pi = nullptr, *d_po = nullptr, *d_err = nullptr; uint8_t *d_out = nullptr; int *d_ni = nullptr;
-    const size_t ne1 = (size_t)std::max(ne, 1);
-    cs_scratch sc(ctx); // (after the host array: it waits for the copy out of it before it goes)
-    CS_TRY(sc.alloc(ctx, &d_fr, (size_t)n_frames));
-    CS_TRY(sc.alloc(ctx, &d_X, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_o, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_w, ne1)); CS_TRY(sc.alloc(ctx, &d_err, ne1 * 3));
-    CS_TRY(sc.alloc(ctx, &d_pi, (size_t)n_frames * 7)); CS_TRY(sc.alloc(ctx, &d_po, (size_t)n_frames * 7)); CS_TRY(sc.alloc(ctx, &d_out, ne1)); CS_TRY(sc.alloc(ctx, &d_ni, (size_t)n_frames));
-    CS_TRY(cs_h2d(ctx, d_fr, fr.data(), fr.size()));
-    if (ne) { CS_TRY(cs_h2d(ctx, d_X, Xw, (size_t)ne * 3)); CS_TRY(cs_h2d(ctx, d_o, obs, (size_t)ne * 3)); CS_TRY(cs_h2d(ctx, d_w, inv_sigma2, (size_t)ne)); }
-    CS_TRY(cs_h2d(ctx, d_pi, pose_in, (size_t)n_frames * 7));
-    ctx->begin("pose_opt_kernel");
-    hipLaunchKernelGGL(pose_opt_kernel, dim3(n_frames), dim3(256), 0, ctx->stream, d_fr, d_X, d_o, d_w, d_pi, d_po, d_out, d_ni, d_err);
-    ctx->end();
-    CS_TRY(cs_d2h(ctx, pose_out, d_po, (size_t)n_frames * 7));
-    if (ne) CS_TRY(cs_d2h(ctx, outlier, d_out, (size_t)ne));
-    CS_TRY(cs_d2h(ctx, n_inliers, d_ni, (size_t)n_frames));
-    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
-    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
     return CS_OK;
 }
 

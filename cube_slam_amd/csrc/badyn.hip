@@ -21,6 +21,7 @@
 #include "common.h"
 #include "badyn_math.h"
 #include "badyn_lists.h"
+#include "lm_schedule.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,16 +36,9 @@ namespace {
 // 40 KB at this bound, within the default 64 KB per workgroup
 constexpr int DYN_MAX_NP = 4000;
 
-__device__ inline void dyn_block_sum_store(double v, double *partials) {
-    __shared__ double s[4];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-}
 __global__ void __launch_bounds__(256) badyn_errors(DynG G, int n_edges, double *partials) {
     const int e = blockIdx.x * 256 + threadIdx.x;
-    dyn_block_sum_store(e < n_edges ? dyn_error_item(G, e) : 0.0, partials);
+    block_sum_store(e < n_edges ? dyn_error_item(G, e) : 0.0, partials, (int)blockIdx.x);
 }
 template <int ONLY> __global__ void __launch_bounds__(64) badyn_linearize(DynG G, int e0, int n) { // edges [e0, e0 + n) of the concatenated list
     const int e = blockIdx.x * 64 + threadIdx.x;
@@ -480,8 +474,9 @@ int cs_ba_dyn_optimize(cs_ctx *ctx, cs_ba_dyn *b, int iterations, const volatile
     const DynG &G = b->G;
     cs_ba_stats S;
     memset(&S, 0, sizeof(S));
-    double lambda = 0, ni = 2, currentChi = 0;
-    int nBad = 0, r;
+    double currentChi = 0;
+    int r;
+    LmSchedule lm;
     bool accepted = false;
     const size_t nx = (size_t)G.NP + 3 * (size_t)G.L;
     auto terminate = [&]() { return (stop_flag && *stop_flag) || (b->stop8 && *b->stop8); };
@@ -503,13 +498,12 @@ int cs_ba_dyn_optimize(cs_ctx *ctx, cs_ba_dyn *b, int iterations, const volatile
             CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
             double mx = 0;
             for (size_t i = 0; i < nx; i++) mx = std::max(mx, std::fabs(diag[i]));
-            lambda = 1e-5 * mx; ni = 2; nBad = 0;
+            lm.start(1e-5 * mx);
         }
-        double rho = 0;
-        int qmax = 0;
+        lm.begin_iteration();
         do {
             CS_HIP(ctx, hipMemcpyAsync(b->d_bak, b->d_state, sizeof(double) * std::max<size_t>(b->state_doubles, 1), hipMemcpyDeviceToDevice, ctx->stream)); // push()
-            r = dyn_solve(ctx, b, lambda); if (r) return r;
+            r = dyn_solve(ctx, b, lm.lambda); if (r) return r;
             CS_LAUNCH(ctx, "badyn_update", badyn_update, dim3((b->n_vertices + 63) / 64), dim3(64), 0, G, b->n_vertices);
             int status = 0;
             b->h_x.resize(std::max<size_t>(nx, 1));
@@ -517,37 +511,18 @@ int cs_ba_dyn_optimize(cs_ctx *ctx, cs_ba_dyn *b, int iterations, const volatile
             if (G.NP) { r = cs_d2h(ctx, b->h_x.data(), G.xp, (size_t)G.NP); if (r) return r; }
             if (G.L) { r = cs_d2h(ctx, b->h_x.data() + G.NP, G.xl, (size_t)G.L * 3); if (r) return r; }
             r = dyn_errors(ctx, b, &tempChi); if (r) return r; // synchronises
-            if (status != 0) tempChi = std::numeric_limits<double>::max();
-            rho = (currentChi - tempChi);
             double scale = 0; // computeScale :182-190
-            if (status == 0) for (size_t j = 0; j < nx; j++) scale += b->h_x[j] * (lambda * b->h_x[j] + b->h_b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = (std::min)(alpha, 2. / 3.);
-                const double scaleFactor = (std::max)(1. / 3., alpha);
-                lambda *= scaleFactor;
-                ni = 2;
-                currentChi = tempChi;
-                accepted = true;
-            } else {
-                accepted = false;
-                lambda *= ni;
-                ni *= 2;
-                CS_HIP(ctx, hipMemcpyAsync(b->d_state, b->d_bak, sizeof(double) * std::max<size_t>(b->state_doubles, 1), hipMemcpyDeviceToDevice, ctx->stream)); // pop()
-            }
-            qmax++;
+            if (status == 0) for (size_t j = 0; j < nx; j++) scale += b->h_x[j] * (lm.lambda * b->h_x[j] + b->h_b[j]);
+            accepted = lm.trial(currentChi, tempChi, status == 0, scale);
+            if (!accepted) CS_HIP(ctx, hipMemcpyAsync(b->d_state, b->d_bak, sizeof(double) * std::max<size_t>(b->state_doubles, 1), hipMemcpyDeviceToDevice, ctx->stream)); // pop()
             S.lm_trials++;
-        } while (rho < 0 && qmax < 10 && !terminate());
+        } while (lm.retry() && !terminate());
         S.iterations = it + 1;
         if (it < 64) S.chi2_trace[it] = currentChi;
         S.chi2_final = currentChi;
-        if (qmax == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        if (nBad >= 3) break;
+        if (lm.stop(iniChi, currentChi)) break;
     }
-    S.lambda_final = lambda;
+    S.lambda_final = lm.lambda;
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (st) *st = S;
     return CS_OK;

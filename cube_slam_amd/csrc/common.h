@@ -242,6 +242,30 @@ __device__ __forceinline__ int wave_incl_min_scan(int x) {
 }
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
+// The sums of a 256-thread workgroup, in one fixed order of additions (the optimisers' results depend on it): the lanes of a wave by a shuffle tree 32 .. 1,
+// then the four wave results as (w0 + w1) + (w2 + w3).  s_red holds 4 x N doubles.
+template <int N> __device__ __forceinline__ void block_reduce_waves(double (&v)[N], double *s_red) { // -> s_red[wave * N + k], readable behind the call
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; k++) for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
+    if (lane == 0) for (int k = 0; k < N; k++) s_red[wave * N + k] = v[k];
+    __syncthreads();
+}
+template <int N> __device__ __forceinline__ double block_reduce_sum(const double *s_red, int k) { return (s_red[k] + s_red[N + k]) + (s_red[2 * N + k] + s_red[3 * N + k]); }
+// N values per thread -> s_out[0 .. N), which every thread may read behind the call
+template <int N> __device__ __forceinline__ void block_reduce(double (&v)[N], double *s_red, double *s_out) {
+    block_reduce_waves(v, s_red);
+    if (threadIdx.x < N) s_out[threadIdx.x] = block_reduce_sum<N>(s_red, threadIdx.x);
+    __syncthreads();
+}
+// one value per thread -> partials[bid]: the workgroup's share of a sum the host (or a later kernel) finishes over the small partial array
+__device__ inline void block_sum_store(double v, double *partials, int bid) {
+    __shared__ double s[4];
+    double w[1] = {v};
+    block_reduce_waves(w, s);
+    if (threadIdx.x == 0) partials[bid] = block_reduce_sum<1>(s, 0);
+}
+
 // Four neighbouring pixels of a u8 row with one load.  gfx950 runs global memory in unaligned-access mode (a dword load may start at
 // any byte; tools/ubench/unaligned_load.hip checks it on the device), and one dword gather costs the texture-address unit a quarter
 // of four byte gathers.

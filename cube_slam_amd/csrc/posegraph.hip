@@ -21,6 +21,7 @@
 // The host runs optimization_algorithm_levenberg.cpp's schedule and reads one record of four doubles per trial.  Where the solve fails the step is taken as zero (g2o
 // applies whatever its x held before); the trial is undone either way.
 #include "common.h"
+#include "lm_schedule.h"
 #include "sim3_math.h"
 
 #include <algorithm>
@@ -254,17 +255,14 @@ __global__ void __launch_bounds__(EG_THREADS) eg_update(int n, const int *pos, i
 // rec[slot] = sum chi; rec[2] = sum x (lambda x + b) where nx > 0; rec[3] = status.  One workgroup, a fixed order.
 __global__ void __launch_bounds__(EG_THREADS) eg_reduce(int m, const double *chi, int slot, int nx, const double *x, const double *b, double lambda, const int *status, double *rec) {
     __shared__ double s_red[8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     double v[2] = {0, 0};
     for (int i = tid; i < m; i += EG_THREADS) v[0] += chi[i];
     for (int i = tid; i < nx; i += EG_THREADS) v[1] += x[i] * (lambda * x[i] + b[i]);
-#pragma unroll
-    for (int k = 0; k < 2; k++) for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-    if (lane == 0) { s_red[wave * 2] = v[0]; s_red[wave * 2 + 1] = v[1]; }
-    __syncthreads();
+    block_reduce_waves(v, s_red);
     if (tid == 0) {
-        rec[slot] = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]);
-        if (nx > 0) { rec[2] = (s_red[1] + s_red[3]) + (s_red[5] + s_red[7]); rec[3] = (double)*status; }
+        rec[slot] = block_reduce_sum<2>(s_red, 0);
+        if (nx > 0) { rec[2] = block_reduce_sum<2>(s_red, 1); rec[3] = (double)*status; }
     }
 }
 
@@ -461,59 +459,46 @@ int cs_essential_graph_optimize(cs_ctx *ctx, cs_essential_graph *g, const double
     st.levels = g->nlev; st.l_blocks = g->nLb; st.h_blocks = g->nHb;
     st.launches_per_trial = 2 * (int)g->launches.size() + 3;
     double *X = g->d_X, *Xt = g->d_Xt;
-    double lambda = 0, ni = 2, rec[4] = {0, 0, 0, 0};
-    int nBad = 0;
+    double rec[4] = {0, 0, 0, 0};
+    LmSchedule lm;
     for (int it = 0; it < iterations; it++) { // OptimizationAlgorithmLevenberg::solve
         CS_LAUNCH(ctx, "eg_error", eg_error, ge, tb, 0, m, g->d_ei, g->d_ej, g->d_C, X, g->d_e, g->d_chi);
         CS_LAUNCH(ctx, "eg_reduce", eg_reduce, dim3(1), tb, 0, m, g->d_chi, 0, 0, g->d_x, g->d_b, 0.0, g->d_status, g->d_rec);
         CS_LAUNCH(ctx, "eg_linearize", eg_linearize, gl, tb, 0, m, g->d_ei, g->d_ej, g->d_C, X, g->fixed, g->fix_scale, g->d_J);
         CS_LAUNCH(ctx, "eg_assemble", eg_assemble, dim3(nf + g->nslots), dim3(64), 0, nf, g->d_inc_off, g->d_inc, g->d_slot_off, g->d_slot_edge, g->d_slot_blk, g->d_col_start, g->d_J, g->d_e, g->d_H,
                   g->d_b);
-        if (it == 0) { lambda = 1e-16; ni = 2; nBad = 0; } // computeLambdaInit: _userLambdaInit > 0
-        double rho = 0, currentChi = 0, iniChi = 0;
-        int qmax = 0;
+        if (it == 0) lm.start(1e-16); // computeLambdaInit: _userLambdaInit > 0
+        lm.begin_iteration();
+        double currentChi = 0, iniChi = 0;
         st.iterations++;
         do {
             CS_HIP(ctx, hipMemsetAsync(g->d_status, 0, sizeof(int), ctx->stream));
             for (const auto &l : g->launches)
                 CS_LAUNCH(ctx, "eg_factor", eg_factor, dim3(l.seq ? 1 : l.count), tb, 0, g->d_lev_cols + l.first, l.count, l.seq, g->d_col_start, g->d_upd_off, g->d_upd_a, g->d_upd_b, g->d_row_off,
-                          g->d_row_blk, g->d_row_col, g->d_H, g->d_b, lambda, g->d_L, g->d_y, g->d_status);
+                          g->d_row_blk, g->d_row_col, g->d_H, g->d_b, lm.lambda, g->d_L, g->d_y, g->d_status);
             for (size_t k = g->launches.size(); k-- > 0;) {
                 const auto &l = g->launches[k];
                 CS_LAUNCH(ctx, "eg_back", eg_back, dim3(l.seq ? 1 : l.count), dim3(64), 0, g->d_lev_cols + l.first, l.count, l.seq, g->d_col_start, g->d_row_idx, g->d_L, g->d_y, g->d_x);
             }
             CS_LAUNCH(ctx, "eg_update", eg_update, gv, tb, 0, n, g->d_pos, g->fix_scale, 1, g->d_status, g->d_x, X, Xt);
             CS_LAUNCH(ctx, "eg_error", eg_error, ge, tb, 0, m, g->d_ei, g->d_ej, g->d_C, Xt, (double *)nullptr, g->d_chi);
-            CS_LAUNCH(ctx, "eg_reduce", eg_reduce, dim3(1), tb, 0, m, g->d_chi, 1, nf * 7, g->d_x, g->d_b, lambda, g->d_status, g->d_rec);
+            CS_LAUNCH(ctx, "eg_reduce", eg_reduce, dim3(1), tb, 0, m, g->d_chi, 1, nf * 7, g->d_x, g->d_b, lm.lambda, g->d_status, g->d_rec);
             r = cs_d2h(ctx, rec, g->d_rec, 4);
             if (r) return r;
             CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (qmax == 0) { currentChi = iniChi = rec[0]; if (it == 0) st.chi2_first = rec[0]; }
-            const bool ok2 = rec[3] == 0.0;
-            double tempChi = rec[1];
-            if (!ok2) tempChi = DBL_MAX;
-            rho = currentChi - tempChi;
-            const double scale = rec[2] + 1e-3;
-            rho /= scale;
-            const bool accepted = rho > 0 && std::isfinite(tempChi);
+            if (lm.qmax == 0) { currentChi = iniChi = rec[0]; if (it == 0) st.chi2_first = rec[0]; }
+            const bool accepted = lm.trial(currentChi, rec[1], rec[3] == 0.0, rec[2]);
             if (accepted) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha);
-                ni = 2; currentChi = tempChi;
                 std::swap(X, Xt); // the trial's estimates stand; a rejected trial's are simply not taken
                 st.accepted++;
-            } else { lambda *= ni; ni *= 2; st.rejected++; }
+            } else st.rejected++;
             if (st.trials < CS_EG_MAX_TRIALS) st.trial_accepted[st.trials] = accepted ? 1 : 0;
             st.trials++;
-            qmax++;
-        } while (rho < 0 && qmax < 10);
+        } while (lm.retry());
         st.chi2_last = currentChi;
-        if (qmax == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        if (nBad >= 3) break;
+        if (lm.stop(iniChi, currentChi)) break;
     }
-    st.lambda_last = lambda;
+    st.lambda_last = lm.lambda;
     r = cs_d2h(ctx, sim3_out, X, N * 8);
     if (r) return r;
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -1,14 +1,11 @@
-// SE3Quat / cuboid / robust-kernel helpers shared by the bundle-adjustment kernels (ba.hip, badyn.hip): the vendored g2o types/se3quat.h,
+// SE3Quat / cuboid / robust-kernel helpers shared by the optimisers' kernels (ba.hip, badyn.hip, poseopt.hip): the vendored g2o types/se3quat.h,
 // orb_object_slam/{include/g2o_Object.h, src/g2o_Object.cpp} and core/robust_kernel_impl.cpp spelled out in Eigen's evaluation order.
 // HD functions are plain C++ as well: tests/cpp/badyn_items.cpp compiles the per-item bodies of badyn_math.h with g++ to check them against
 // the oracle without a GPU (test infrastructure; the product only ever runs them inside kernels).
 #pragma once
 #include <cmath>
-#if defined(__HIPCC__)
-#define HD __host__ __device__ inline
-#else
-#define HD inline
-#endif
+
+#include "hd.h"
 
 namespace {
 

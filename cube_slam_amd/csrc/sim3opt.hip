@@ -3,7 +3,7 @@
 // Replaces Optimizer::OptimizeSim3 (reference orb_object_slam/include/Optimizer.h, src/Optimizer.cc:2838-3033): the 7-dof refinement of the Sim3 between two key frames
 // that LoopClosing::ComputeSim3 runs between SearchBySim3 and SearchByProjection(pKF, Scw, ...).  One free VertexSim3Expmap, two unary edges per correspondence (both
 // point vertices are fixed), g2o's Levenberg-Marquardt in two stages with an outlier cut between them.  One workgroup of 256 threads runs the whole routine for one
-// problem in one launch; the model is pose_opt_kernel (ba.hip).
+// problem in one launch, as pose_opt_kernel (poseopt.hip) does for a frame.
 //
 //   * correspondences are strided over the threads; EdgeSim3ProjectXYZ is obs1 - cam_map1(project(S.map(P2c))), EdgeInverseSim3ProjectXYZ is
 //     obs2 - cam_map2(project(S.inverse().map(P1c))) (types_seven_dof_expmap.h:130-171), information invSigma2 * I, Huber with delta = (float)sqrt(th2)
@@ -13,16 +13,16 @@
 //   * under fix_scale oplusImpl zeroes update[6]: column 6 of every Jacobian is exactly zero, H(6,6) is lambda alone and the step's seventh component is dropped.  The
 //     system stays 7 x 7
 //   * the 28 lower-triangle entries of H (LinearSolverDense's L D L^T reads that triangle), the 7 of b and chi2 are reduced in a fixed order: thread partials in
-//     correspondence order (e12 before e21), a shuffle tree, the four wave results.  Thread 0 solves the damped system; every LM decision is taken by all threads
-//     from the same LDS values
+//     correspondence order (e12 before e21), a shuffle tree, the four wave results (block_reduce, common.h).  Thread 0 solves the damped system; every LM decision
+//     (lm_schedule.h) is taken by all threads from the same LDS values
 //   * optimize(5); chi2 > th2 on either edge, on the _error the last trial left, removes the pair; fewer than 10 left: return 0 with the Sim3 as it came; otherwise
 //     optimize(nBad > 0 ? 10 : 5) from the first stage's estimate and a second cut that only flags
 // Every loop is bounded by those constants; no atomics, no waiting on other workgroups.
 #include "common.h"
+#include "lm_schedule.h"
 #include "sim3_math.h"
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <vector>
 
@@ -32,15 +32,6 @@ struct Sim3Problem { int e0, e1, fix_scale; double K[8]; double delta, dsqr, th2
 
 constexpr int SIM3_THREADS = 256, SIM3_NSYS = 36; // 28 of H + 7 of b + 1 scalar (chi2 or a count)
 
-template <int N> __device__ __forceinline__ void sim3_block_reduce(double (&v)[N], double *s_red /* 4 x N */, double *s_out /* N */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-    if (lane == 0) for (int k = 0; k < N; k++) s_red[wave * N + k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < N) s_out[threadIdx.x] = (s_red[threadIdx.x] + s_red[N + threadIdx.x]) + (s_red[2 * N + threadIdx.x] + s_red[3 * N + threadIdx.x]);
-    __syncthreads();
-}
 // obs - cam_map(project(S.map(p))) (se3_ops.hpp:49-55: a division per coordinate)
 __device__ __forceinline__ void sim3_edge_error(const Sim3 &S, const double *p, const double *ob, const double *K, double *e) {
     double q[3];
@@ -86,14 +77,13 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
             if (!(c <= F.dsqr)) c = 2 * sqrt(c) * F.delta - F.dsqr;
             v[0] += c;
         }
-        sim3_block_reduce<1>(v, s_red, s_sys + 35);
+        block_reduce<1>(v, s_red, s_sys + 35);
         return s_sys[35];
     };
     int nBad = 0, nIn = 0;
     for (int stage = 0; stage < 2; stage++) {
         const int iterations = stage == 0 ? 5 : (nBad > 0 ? 10 : 5);
-        double lambda = 0, ni = 2;
-        int nBadSteps = 0;
+        LmSchedule lm;
         for (int it = 0; it < iterations; it++) { // OptimizationAlgorithmLevenberg::solve
             double currentChi = chi2_sum(S);
             const double iniChi = currentChi;
@@ -141,10 +131,9 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
                     for (int a = 0; a < 7; a++) acc[28 + a] += J0[a] * r0 + J1[a] * r1;
                 }
             }
-            sim3_block_reduce<35>(acc, s_red, s_sys);
-            if (it == 0) { double mx = 0; for (int a = 0; a < 7; a++) mx = fmax(fabs(s_sys[a * (a + 1) / 2 + a]), mx); lambda = 1e-5 * mx; ni = 2; nBadSteps = 0; }
-            double rho = 0;
-            int qmax = 0;
+            block_reduce<35>(acc, s_red, s_sys);
+            if (it == 0) { double mx = 0; for (int a = 0; a < 7; a++) mx = fmax(fabs(s_sys[a * (a + 1) / 2 + a]), mx); lm.start(1e-5 * mx); }
+            lm.begin_iteration();
             do {
                 const Sim3 backup = S;
                 if (tid == 0) { // (H + lambda I) x = b: LinearSolverDense, L D L^T from the lower triangle, solved where every D is positive
@@ -152,7 +141,7 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
                     bool positive = true;
 #pragma unroll
                     for (int j = 0; j < 7; j++) {
-                        double d = s_sys[j * (j + 1) / 2 + j] + lambda;
+                        double d = s_sys[j * (j + 1) / 2 + j] + lm.lambda;
 #pragma unroll
                         for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * D[k];
                         D[j] = d;
@@ -192,24 +181,12 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
                 const bool ok2 = s_flag != 0;
                 S = sim3_load(s_S);
                 double tempChi = chi2_sum(S);
-                if (!ok2) tempChi = DBL_MAX;
-                rho = currentChi - tempChi;
-                double scale = 0;
-                for (int j = 0; j < 7; j++) scale += s_x[j] * (lambda * s_x[j] + s_sys[28 + j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow((2 * rho - 1), 3);
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2; currentChi = tempChi;
-                } else { lambda *= ni; ni *= 2; S = backup; }
-                qmax++;
+                double scale = 0; // computeScale
+                for (int j = 0; j < 7; j++) scale += s_x[j] * (lm.lambda * s_x[j] + s_sys[28 + j]);
+                if (!lm.trial(currentChi, tempChi, ok2, scale)) S = backup;
                 __syncthreads(); // s_x / s_S are rewritten by the next trial
-            } while (rho < 0 && qmax < 10);
-            if (qmax == 10 || rho == 0) break;
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBadSteps++; else nBadSteps = 0;
-            if (nBadSteps >= 3) break;
+            } while (lm.retry());
+            if (lm.stop(iniChi, currentChi)) break;
         }
         // the cut (Optimizer.cc:2976-2995, 3011-3026): on the _error the last trial left, accepted or not
         double cnt[1] = {0};
@@ -218,7 +195,7 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
             const double e[4] = {E[(long)i * 4], E[(long)i * 4 + 1], E[(long)i * 4 + 2], E[(long)i * 4 + 3]};
             if (sim3_edge_chi2(e, W1[i]) > F.th2 || sim3_edge_chi2(e + 2, W2[i]) > F.th2) { rem[i] = 1; cnt[0] += 1.0; }
         }
-        sim3_block_reduce<1>(cnt, s_red, s_sys + 35);
+        block_reduce<1>(cnt, s_red, s_sys + 35);
         const int flagged = (int)s_sys[35];
         __syncthreads();
         if (stage == 0) {

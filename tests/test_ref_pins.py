@@ -316,6 +316,19 @@ def test_detect_cuboid_equals_reference(ref, oracle, mode):
     assert total >= (9 if mode != "top3" else 20), total
 
 
+# (seed, synth.ba_problem arguments, iterations): shared with tests/test_lm_schedule.py
+LEVENBERG_BA_PROBLEMS = ((1, dict(n_kf=6, n_points=60, n_cuboids=2), 10), (2, dict(n_kf=8, n_points=90, n_cuboids=3, noise_pose=0.15), 15),
+                         (3, dict(n_kf=5, n_points=40, n_cuboids=0), 8), (4, dict(n_kf=7, n_points=70, n_cuboids=2, noise_pose=0.4, noise_point=0.5), 20),
+                         (5, dict(n_kf=6, n_points=50, n_cuboids=2, noise_pose=1.0, noise_point=1.5), 20))
+
+
+def levenberg_ba_problem(seed, kw):
+    try:
+        return synth.ba_problem(seed, **kw)
+    except TypeError:
+        return synth.ba_problem(seed, **{k: v for k, v in kw.items() if not k.startswith("noise")})
+
+
 def test_levenberg_schedule_equals_reference(ref, oracle):
     """g2o's Levenberg-Marquardt as the reference vendors it: OptimizationAlgorithmLevenberg::solve / computeLambdaInit / computeScale and its
     constructor's constants (Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:43-56, 61-189) and SparseOptimizer::optimize
@@ -325,13 +338,8 @@ def test_levenberg_schedule_equals_reference(ref, oracle):
     import oracle.pyoracle as po
     ref.ref_ba_levenberg.restype = C.c_int
     n_rejected = 0
-    for seed, kw, iters in ((1, dict(n_kf=6, n_points=60, n_cuboids=2), 10), (2, dict(n_kf=8, n_points=90, n_cuboids=3, noise_pose=0.15), 15),
-                            (3, dict(n_kf=5, n_points=40, n_cuboids=0), 8), (4, dict(n_kf=7, n_points=70, n_cuboids=2, noise_pose=0.4, noise_point=0.5), 20),
-                            (5, dict(n_kf=6, n_points=50, n_cuboids=2, noise_pose=1.0, noise_point=1.5), 20)):
-        try:
-            d = synth.ba_problem(seed, **kw)
-        except TypeError:
-            d = synth.ba_problem(seed, **{k: v for k, v in kw.items() if not k.startswith("noise")})
+    for seed, kw, iters in LEVENBERG_BA_PROBLEMS:
+        d = levenberg_ba_problem(seed, kw)
         p = po.ba_struct(d)
         cam = np.zeros((p.n_cams, 7)); pts = np.zeros((p.n_points, 3)); cub = np.zeros((max(p.n_cuboids, 1), 7))
         trials, lam, chi = C.c_int(), C.c_double(), C.c_double()
@@ -756,6 +764,23 @@ def test_fuse_equals_reference(ref, oracle):
     assert total > 1500
 
 
+# (seed, synth.ba_dyn_problem arguments, iterations): shared with tests/test_lm_schedule.py
+LEVENBERG_BADYN_PROBLEMS = ((31, dict(n_kf=8, n_points=150, n_objects=2, pts_per_obj=20), 6), (32, dict(n_kf=6, n_points=80, n_objects=3, pts_per_obj=12, stereo_frac=0.6), 10),
+                            (33, dict(n_kf=7, n_points=100, n_objects=2, pts_per_obj=16, fix_points=True), 8), (34, dict(n_kf=6, n_points=80, n_objects=2, pts_per_obj=12), 15),
+                            (37, dict(n_kf=6, n_points=80, n_objects=2, pts_per_obj=12), 15))
+
+
+def levenberg_badyn_problem(seed, kw):
+    d = dict(synth.ba_dyn_problem(seed, **kw))
+    if seed == 32:
+        d["obs_uv"] = d["obs_uv"].copy(); d["obs_uv"][::23] += 35.0  # gross outliers
+    if seed in (34, 37):  # a start far enough off for rejected trials (lambda grows, the state is restored) and, for 37, an early stop
+        rng = np.random.default_rng(seed)
+        d["obj_pose"] = d["obj_pose"].copy(); d["obj_pose"][:, :3] += rng.normal(0, 1.5, d["obj_pose"][:, :3].shape)
+        d["cam_pose"] = d["cam_pose"].copy(); d["cam_pose"][1:, :3] += rng.normal(0, 0.5, d["cam_pose"][1:, :3].shape)
+    return d
+
+
 def test_dynamic_ba_schedule_equals_reference(ref, oracle):
     """The dynamic-object BA oracle's LM loop against g2o's own OptimizationAlgorithmLevenberg::solve / SparseOptimizer::optimize text (as
     test_levenberg_schedule_equals_reference does for the static BA) driven over the same oracle's pieces: iterations, trials, lambda, chi2 and every estimate
@@ -763,16 +788,8 @@ def test_dynamic_ba_schedule_equals_reference(ref, oracle):
     import oracle.pyoracle as po
     ref.ref_badyn_levenberg.restype = C.c_int
     rejected = 0
-    for seed, kw, iters in ((31, dict(n_kf=8, n_points=150, n_objects=2, pts_per_obj=20), 6), (32, dict(n_kf=6, n_points=80, n_objects=3, pts_per_obj=12, stereo_frac=0.6), 10),
-                            (33, dict(n_kf=7, n_points=100, n_objects=2, pts_per_obj=16, fix_points=True), 8), (34, dict(n_kf=6, n_points=80, n_objects=2, pts_per_obj=12), 15),
-                            (37, dict(n_kf=6, n_points=80, n_objects=2, pts_per_obj=12), 15)):
-        d = dict(synth.ba_dyn_problem(seed, **kw))
-        if seed == 32:
-            d["obs_uv"] = d["obs_uv"].copy(); d["obs_uv"][::23] += 35.0  # gross outliers
-        if seed in (34, 37):  # a start far enough off for rejected trials (lambda grows, the state is restored) and, for 37, an early stop
-            rng = np.random.default_rng(seed)
-            d["obj_pose"] = d["obj_pose"].copy(); d["obj_pose"][:, :3] += rng.normal(0, 1.5, d["obj_pose"][:, :3].shape)
-            d["cam_pose"] = d["cam_pose"].copy(); d["cam_pose"][1:, :3] += rng.normal(0, 0.5, d["cam_pose"][1:, :3].shape)
+    for seed, kw, iters in LEVENBERG_BADYN_PROBLEMS:
+        d = levenberg_badyn_problem(seed, kw)
         p = po.badyn_struct(d)
         out = [np.zeros((max(n, 1), k)) for n, k in ((p.n_cams, 7), (p.n_objs, 7), (p.n_vels, 2), (p.n_points, 3), (p.n_dpoints, 3))]
         trials, lam, chi = C.c_int(), C.c_double(), C.c_double()

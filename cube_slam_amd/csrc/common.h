@@ -101,7 +101,18 @@ struct cs_ctx {
     // A second, lowest-priority stream of this context for ONE kind of launch: a kernel that holds its wave slots for ~100 ms and paces itself (the LSD region
     // walk).  Everything else of the context then runs at the context's own priority beside it, ordered against it by two events.
     hipStream_t bg_stream = nullptr; hipEvent_t bg_in = nullptr, bg_out = nullptr;
-    hipStream_t aux_stream = nullptr; // a second stream at the context's priority for a branch of a launch chain that reads nothing of the other branch (cs_cuboid_batch_run); created on first use
+    // a second stream, at DEFAULT priority, for a branch of a launch chain that reads nothing of the other branch (cs_cuboid_batch_run); created on first use.  At the
+    // context's own priority (hipStreamGetPriority of `stream`) config 4's batch measured 64.5 k frames/s against 65.3 k, three alternating runs each, so it stays as it is.
+    hipStream_t aux_stream = nullptr;
+    hipError_t aux_get(hipStream_t *s) {
+        const hipError_t e = aux_stream ? hipSuccess : hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking);
+        *s = aux_stream;
+        return e;
+    }
+    hipError_t drain() { // every stream that work on a handle's blocks may run on (bg_stream's launches are joined into `stream` by bg_end)
+        const hipError_t e = hipStreamSynchronize(stream);
+        return e == hipSuccess && aux_stream ? hipStreamSynchronize(aux_stream) : e;
+    }
     hipError_t bg_begin() { // work queued on `stream` so far precedes what is queued on bg_stream from here on
         hipError_t e = hipSuccess;
         if (!bg_stream) {
@@ -142,13 +153,14 @@ struct cs_ctx {
         }                                                                                         \
     } while (0)
 
-// Launch helper: named, timed when ctx->timing is on.
-#define CS_LAUNCH(ctx, name, kernel, grid, block, shmem, ...)                         \
+// Launch helper: named, timed when ctx->timing is on.  The events of a timed launch are recorded on ctx->stream: CS_LAUNCH_ON with another stream only while timing is off.
+#define CS_LAUNCH_ON(ctx, on_stream, name, kernel, grid, block, shmem, ...)           \
     do {                                                                              \
         (ctx)->begin(name);                                                           \
-        hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->stream, __VA_ARGS__);   \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, on_stream, __VA_ARGS__);       \
         (ctx)->end();                                                                 \
     } while (0)
+#define CS_LAUNCH(ctx, name, kernel, grid, block, shmem, ...) CS_LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, shmem, __VA_ARGS__)
 
 // The rule for device blocks: a block is obtained only through cs_dalloc (or a cs_owner, which calls it) and returned only through cs_dfree (or the owner).
 // cs_dalloc may hand out a block of the context's pool, which only cs_dfree knows how to give back; no file but this one and ctx.hip calls hipMalloc / hipFree
@@ -171,6 +183,12 @@ template <class T> static inline int cs_d2h(cs_ctx *ctx, T *h, const T *d, size_
     return CS_OK;
 }
 #define CS_TRY(call) do { const int r__ = (call); if (r__ != CS_OK) return r__; } while (0)
+// CSR offsets of n ranges as the entry points take them: they start at 0 and do not decrease; rows may be NULL only when there is no row
+static inline bool cs_offsets_ok(const int *off, int n, const void *rows) {
+    if (!off || off[0] != 0) return false;
+    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) return false;
+    return off[n] == 0 || rows;
+}
 
 // The device blocks of a handle or of one call.  Every block is allocated through alloc() and released by free_all(): there is no second list to keep.  The stream that
 // may still use a block must have drained before free_all() -- the destroy functions synchronise first, a call's scratch goes through cs_scratch.
@@ -187,6 +205,7 @@ struct cs_owner {
     }
     void free_one(cs_ctx *ctx, void *p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); cs_dfree(ctx, p); }
     void free_all(cs_ctx *ctx) { for (void *p : blocks) cs_dfree(ctx, p); blocks.clear(); }
+    void adopt(cs_owner &o) { blocks.insert(blocks.end(), o.blocks.begin(), o.blocks.end()); o.blocks.clear(); } // o's blocks are this owner's from here on
 };
 // the scratch of one call: released on every way out of the call, after the stream has drained (drain() is the call's own wait for its results;
 // a call that keeps a wait of its own, for the error text it reports, sets `drained` behind it)

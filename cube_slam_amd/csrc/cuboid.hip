@@ -23,6 +23,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <array>
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -1237,19 +1238,11 @@ template <int CFG, bool HYB, bool LEAN> __device__ __forceinline__ void sc_score
     double ang[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) ang[k] = E.ang[k];
-#ifdef NO_ANGLE
-    const double ae = ang[0];
-#else
     const double ae = edge_angle_error_reg<CFG>(ang, cx, cy);
-#endif
     const double rx = (double)U.roi_x, ry = (double)U.roi_y;
 #pragma unroll
     for (int k = 0; k < 8; k++) { cx[k] = cx[k] - rx; cy[k] = cy[k] - ry; } // :423-425
-#ifdef NO_SUM
-    const float sum_dist = (float)(cx[0] + cy[1] + cx[2] + cy[3] + cx[4] + cy[5] + cx[6] + cy[7]);
-#else
     const float sum_dist = edge_sum_dists_code<CFG, HYB, LEAN>(cx, cy, U.roi_w, lmap, gdist, n_res, U.roi_w * U.roi_h - 1);
-#endif
     if (live) {
         derr[g] = double(sum_dist) / U.diag; // :451
         aerr[g] = ae;
@@ -1331,11 +1324,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
         if (work) {
             if (tid == 0 && slice == 0) uflag[u] = escape ? 1 : 0;
             if (escape) n_res = 0;
-#ifdef NO_HYB
-            const bool hyb = false;
-#else
             const bool hyb = escape || !fits;
-#endif
             for (;;) { // waves pull tasks of 64 proposals of one configuration
                 int t = 0;
                 if (lane == 0) t = atomicAdd(&ctrl[0], n_slices);
@@ -1785,60 +1774,26 @@ static void host_euler_from_T(const double *T, double *euler) { // set_cam_pose 
 
 } // namespace
 
-struct cs_cuboid_batch {
-    int n_frames = 0, W = 0, H = 0, n_boxes = 0, n_units = 0;
-    Opts o{};
-    Calib cal{};
-    std::vector<Unit> units;
-    std::vector<FrameInfo> fi;   // host copy (cs_cuboid_batch_set_lines rewrites the line ranges)
-    long cap_lines_in = 0, cap_line_rows = 0;
-    // capacities of the plan-sized device arrays (cs_cuboid_batch_set_scene grows them when another set of boxes needs more) and the pinned staging of its uploads
-    long cap_pix = 0, cap_hyp = 0, cap_vp = 0, cap_dttmp = 0; int cap_units = 0, cap_boxes = 0, sample_bbox_height = 0;
-    uint8_t *h_stage[2] = {nullptr, nullptr}; size_t stage_cap[2] = {0, 0}; hipEvent_t stage_ev[2] = {nullptr, nullptr}; int stage_k = 0;
-    std::vector<int> box_first_unit;
-    long pix_total = 0, hyp_total = 0, vp_total = 0, line_rows = 0;
-    int max_tiles = 0, max_cc_blocks = 0, max_vp_blocks = 0, blocks_per_unit = 0, max_roi_w = 0;
-    int n_nms = 0, n_cc = 0, n_hb = 0, cap_wgmap = 0; // workgroups of the compact grids; d_wgmap = [unit of every NMS tile | of every 4 096-pixel band | of every hypothesis block]
-    int *d_wgmap = nullptr;
-    // the two branches of a run that read nothing of each other -- poses / edge lists / vanishing points, and the image: Canny, components, distance transform -- on two
-    // streams, joined before the sweep (cs_cuboid_batch_run): a small batch (one frame of a drop-in call, config 4's 512 units) does not fill the chip and its kernels are
-    // per-unit latency chains, so the branches cost their sum when queued behind each other
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr; // (the second stream is the context's: cs_ctx::aux_stream)
-    // device
-    uint8_t *d_gray = nullptr, *d_emap = nullptr, *d_flag = nullptr;
-    int *d_lab = nullptr; // aliases d_dist
-    float *d_dist = nullptr;
-    int *d_dttmp = nullptr; long *d_dttmp_off = nullptr;
-    int *d_order = nullptr, *d_cursor = nullptr; // cuboid_sweep_score: units by falling cost estimate, the work cursor
-    int *d_uflag = nullptr;                      // per unit: 1 = a pixel without a 16-bit code (scored from the float map)
-    int score_G = 256;      // workgroups of cuboid_sweep_score (one per CU)
-    int score_T = 512;      // threads per workgroup (CUBESLAM_SCORE_THREADS = 256 | 512 | 768 | 1024: 1 / 2 / 3 / 4 waves per SIMD with 128 / 256 / 168 / 128 registers)
-    bool score_T_forced = false; // set by the environment: cs_cuboid_batch_set_shared_gpu leaves it alone
-    int score_slices = 1;   // items per unit (more than one when there are fewer units than CUs)
-    int dt_C = 0; // wave-per-ROI distance transform: int map between the passes, lane-major
-    FrameInfo *d_fi = nullptr; FrameDyn *d_fd = nullptr; CamRP *d_cam = nullptr;
-    double *d_yaw = nullptr, *d_lines_in = nullptr, *d_lines_al = nullptr, *d_mlines = nullptr, *d_mangle = nullptr, *d_mmid = nullptr;
-    Unit *d_units = nullptr; UnitDyn *d_ud = nullptr; int *d_box_first = nullptr, *d_status = nullptr, *d_counts = nullptr, *d_carry = nullptr;
-    bool want_carry = false; // cs_cuboid_detect's box-to-box chain asks cuboid_select which roll / pitch sample the last kept proposal carries
-    VPEntry *d_vp = nullptr;
-    int *d_vcount = nullptr, *d_vlist = nullptr; // per unit: number of surviving proposals and their hypothesis indices
-    double *d_derr = nullptr, *d_aerr = nullptr, *d_score = nullptr, *d_nscore = nullptr;
-    unsigned long long *d_ckd = nullptr, *d_cka = nullptr; int *d_cidx = nullptr;
-    cs_cuboid *d_out = nullptr;
-};
-
-
 // The plan of a batch: one Unit per (frame, box, height sample) with its ROI, top samples and its slices of the pixel / hypothesis / vanishing-point / merged-line arenas
-// (box_proposal_detail.cpp:107-161), and the per-frame pose record.  Built on the host from the boxes and poses alone (3 072 units: ~0.2 ms), by cs_cuboid_batch_create and
-// again by cs_cuboid_batch_set_scene when a step brings other boxes.  keep_lines: the frames' line ranges when the edge lists stay (line_offsets NULL).
+// (box_proposal_detail.cpp:107-161), the per-frame pose record, and what follows from them alone (plan_derived).  Built on the host from the boxes and poses (3 072 units:
+// ~0.2 ms), by cs_cuboid_batch_create and again by cs_cuboid_batch_set_scene when a step brings other boxes.  keep_lines: the frames' line ranges when the edge lists stay
+// (line_offsets NULL).
 struct Plan {
-    std::vector<Unit> units; std::vector<FrameInfo> fi; std::vector<int> box_first_unit;
+    std::vector<Unit> units; std::vector<FrameInfo> fi; std::vector<int> box_first_unit; // (fi: cs_cuboid_batch_set_lines rewrites the line ranges)
     long pix_total = 0, hyp_total = 0, vp_total = 0, line_rows = 0;
-    int max_tiles = 0, max_cc_blocks = 0, max_vp_blocks = 0, blocks_per_unit = 0, max_roi_w = 0, n_boxes = 0;
-    int n_nms = 0, n_cc = 0, n_hb = 0; // workgroups of the compact grids
+    int max_cc_blocks = 0, max_vp_blocks = 0, max_roi_w = 0, n_boxes = 0, n_units = 0;
+    int n_nms = 0, n_cc = 0, n_hb = 0; // workgroups of the compact grids; wgmap = [unit of every NMS tile | of every 4 096-pixel band | of every hypothesis block]
+    // plan_derived:
+    int dt_C = 0;         // wave-per-ROI distance transform: int map between the passes, lane-major (0: the workgroup-per-ROI or the serial kernel)
+    int score_slices = 1; // items per unit of cuboid_sweep_score (more than one when there are fewer units than CUs)
+    std::vector<long> dt_off; std::vector<int> order, wgmap; // the distance transform's scratch offsets, the units by falling cost estimate, the workgroup map
 };
-static int plan_build(const Opts &o, int sample_bbox_height, int n_frames, int width, int height, const double *Twc, const int *box_offsets, const double *boxes, const int *line_offsets,
-                      const std::vector<FrameInfo> *keep_lines, Plan &P) {
+static int plan_build(cs_ctx *ctx, const Opts &o, int sample_bbox_height, int n_frames, int width, int height, const double *Twc, const int *box_offsets, const double *boxes, const int *line_offsets,
+                      const double *lines, const std::vector<FrameInfo> *keep_lines, Plan &P) {
+    if (!cs_offsets_ok(box_offsets, n_frames, boxes) || (line_offsets && !cs_offsets_ok(line_offsets, n_frames, lines))) {
+        ctx->err = "box / line offsets must start at 0 and not decrease, and their rows may be NULL only when there are none";
+        return CS_ERR_BAD_ARG;
+    }
     P.n_boxes = box_offsets[n_frames];
     std::vector<FrameInfo> &fi = P.fi;
     fi.resize(n_frames);
@@ -1890,7 +1845,7 @@ static int plan_build(const Opts &o, int sample_bbox_height, int n_frames, int w
                 U.roi_y = std::max(0, top_y_raw - ew);
                 U.roi_b = std::min(height - 1, U.down_y_expan + ew);
                 U.roi_w = U.roi_r - U.roi_x; U.roi_h = U.roi_b - U.roi_y;
-                if (U.roi_w <= 0 || U.roi_h <= 0 || U.roi_x + U.roi_w > width || U.roi_y + U.roi_h > height) return CS_ERR_BAD_ARG;
+                if (U.roi_w <= 0 || U.roi_h <= 0 || U.roi_x + U.roi_w > width || U.roi_y + U.roi_h > height) { ctx->err = "box ROI outside the image"; return CS_ERR_BAD_ARG; }
                 U.pix_off = P.pix_total; P.pix_total += ((long)U.roi_w * U.roi_h + 63) / 64 * 64;
                 U.hyp_cap = rp_cap * o.yaw_cap * U.n_tops * 2;
                 U.hyp_off = P.hyp_total; P.hyp_total += ((long)U.hyp_cap + 63) / 64 * 64;
@@ -1900,50 +1855,158 @@ static int plan_build(const Opts &o, int sample_bbox_height, int n_frames, int w
                 U.cc_off = P.n_cc; P.n_cc += (int)(((long)U.roi_w * U.roi_h + 4095) / 4096);
                 U.hb_off = P.n_hb; P.n_hb += (U.hyp_cap + SWEEP_HB - 1) / SWEEP_HB;
                 P.max_roi_w = std::max(P.max_roi_w, U.roi_w);
-                P.max_tiles = std::max(P.max_tiles, ((U.roi_w + NMS_TW - 1) / NMS_TW) * ((U.roi_h + NMS_TH - 1) / NMS_TH));
                 P.max_cc_blocks = std::max(P.max_cc_blocks, (int)(((long)U.roi_w * U.roi_h + 4095) / 4096));
-                P.blocks_per_unit = std::max(P.blocks_per_unit, (U.hyp_cap + SWEEP_HB - 1) / SWEEP_HB);
                 P.units.push_back(U);
             }
         }
     P.max_vp_blocks = (rp_cap * o.yaw_cap + 255) / 256;
+    P.n_units = (int)P.units.size();
     if (P.vp_total > INT_MAX || P.line_rows > INT_MAX) return CS_ERR_CAPACITY;
     return CS_OK;
 }
-static void plan_commit(cs_cuboid_batch *b, Plan &P) {
-    b->units.swap(P.units); b->fi.swap(P.fi); b->box_first_unit.swap(P.box_first_unit);
-    b->n_boxes = P.n_boxes; b->n_units = (int)b->units.size();
-    b->pix_total = P.pix_total; b->hyp_total = P.hyp_total; b->vp_total = P.vp_total; b->line_rows = P.line_rows;
-    b->n_nms = P.n_nms; b->n_cc = P.n_cc; b->n_hb = P.n_hb;
-    b->max_tiles = P.max_tiles; b->max_cc_blocks = P.max_cc_blocks; b->max_vp_blocks = P.max_vp_blocks; b->blocks_per_unit = P.blocks_per_unit; b->max_roi_w = P.max_roi_w;
-}
-// the distance transform's column count per lane, its scratch offsets, the score kernel's item split and the units by falling cost estimate: functions of the plan
-static void plan_derived(cs_cuboid_batch *b, std::vector<long> &dt_off, std::vector<int> &order, std::vector<int> &wgmap) {
-    wgmap.resize((size_t)b->n_nms + b->n_cc + b->n_hb);
-    for (size_t u = 0; u < b->units.size(); u++) {
-        const Unit &U = b->units[u];
-        const int e_nms = u + 1 < b->units.size() ? b->units[u + 1].nms_off : b->n_nms, e_cc = u + 1 < b->units.size() ? b->units[u + 1].cc_off : b->n_cc, e_hb = u + 1 < b->units.size() ? b->units[u + 1].hb_off : b->n_hb;
-        for (int k = U.nms_off; k < e_nms; k++) wgmap[(size_t)k] = (int)u;
-        for (int k = U.cc_off; k < e_cc; k++) wgmap[(size_t)b->n_nms + k] = (int)u;
-        for (int k = U.hb_off; k < e_hb; k++) wgmap[(size_t)b->n_nms + b->n_cc + k] = (int)u;
+// the distance transform's column count per lane, its scratch offsets, the score kernel's item split (score_G: its workgroups) and the units by falling cost estimate
+static void plan_derived(Plan &P, int score_G) {
+    const size_t n = P.units.size();
+    P.wgmap.resize((size_t)P.n_nms + P.n_cc + P.n_hb);
+    for (size_t u = 0; u < n; u++) {
+        const Unit &U = P.units[u];
+        const int e_nms = u + 1 < n ? P.units[u + 1].nms_off : P.n_nms, e_cc = u + 1 < n ? P.units[u + 1].cc_off : P.n_cc, e_hb = u + 1 < n ? P.units[u + 1].hb_off : P.n_hb;
+        for (int k = U.nms_off; k < e_nms; k++) P.wgmap[(size_t)k] = (int)u;
+        for (int k = U.cc_off; k < e_cc; k++) P.wgmap[(size_t)P.n_nms + k] = (int)u;
+        for (int k = U.hb_off; k < e_hb; k++) P.wgmap[(size_t)P.n_nms + P.n_cc + k] = (int)u;
     }
     static const int CS_[] = {4, 5, 6, 8, 10, 12, 16, 20};
-    const int need = (b->max_roi_w + 63) / 64;
-    b->dt_C = 0;
-    for (int c : CS_) if (c >= need) { b->dt_C = c; break; }
+    const int need = (P.max_roi_w + 63) / 64;
+    P.dt_C = 0;
+    for (int c : CS_) if (c >= need) { P.dt_C = c; break; }
     const char *dte = getenv("CUBESLAM_DT"); // "block": the workgroup-per-ROI variant
-    if (dte && !strcmp(dte, "block")) b->dt_C = 0;
-    dt_off.assign(b->units.size() + 1, 0);
-    if (b->dt_C) for (size_t u = 0; u < b->units.size(); u++) dt_off[u + 1] = dt_off[u] + (long)b->units[u].roi_h * b->dt_C * 64;
-    b->score_slices = b->n_units >= 2 * b->score_G ? 1 : std::min(16, (2 * b->score_G + b->n_units - 1) / std::max(1, b->n_units));
+    if (dte && !strcmp(dte, "block")) P.dt_C = 0;
+    P.dt_off.assign(n + 1, 0);
+    if (P.dt_C) for (size_t u = 0; u < n; u++) P.dt_off[u + 1] = P.dt_off[u] + (long)P.units[u].roi_h * P.dt_C * 64;
+    P.score_slices = P.n_units >= 2 * score_G ? 1 : std::min(16, (2 * score_G + P.n_units - 1) / std::max(1, P.n_units));
     const char *se = getenv("CUBESLAM_SCORE_SLICES"); // tuning knob / tests: items per unit
-    if (se && atoi(se) > 0) b->score_slices = std::min(64, atoi(se));
+    if (se && atoi(se) > 0) P.score_slices = std::min(64, atoi(se));
     // units by falling cost estimate (map copy ~ pixels, scoring ~ hypotheses): the persistent workgroups take the big ones first
-    order.resize(b->units.size());
-    for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
-    auto cost = [&](int u) { const Unit &U = b->units[u]; return 0.19 * (double)U.roi_w * U.roi_h + 10.8 * (double)U.hyp_cap; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return cost(a) > cost(c); });
+    P.order.resize(n);
+    for (size_t i = 0; i < n; i++) P.order[i] = (int)i;
+    auto cost = [&](int u) { const Unit &U = P.units[u]; return 0.19 * (double)U.roi_w * U.roi_h + 10.8 * (double)U.hyp_cap; };
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int a, int c) { return cost(a) > cost(c); });
 }
+
+// The size classes of the plan-sized device arrays.  A class has ONE capacity, in its own unit (ROI pixels, hypotheses, ...), and every array of the class is sized by it.
+enum { K_PIX, K_HYP, K_VP, K_UNITS, K_BOXES, K_LINES_IN, K_LINE_ROWS, K_WGMAP, K_DTTMP, K_N };
+typedef std::array<long, K_N> Needs; // per class: what a plan needs (a negative entry: the class is not asked about)
+static Needs plan_needs(const Plan &P, long n_lines_in) {
+    Needs n;
+    n[K_PIX] = P.pix_total; n[K_HYP] = P.hyp_total; n[K_VP] = P.vp_total; n[K_UNITS] = P.n_units; n[K_BOXES] = P.n_boxes; n[K_LINES_IN] = n_lines_in; n[K_LINE_ROWS] = P.line_rows;
+    n[K_WGMAP] = (long)P.wgmap.size(); n[K_DTTMP] = P.dt_off.back();
+    return n;
+}
+
+struct cs_cuboid_batch : Plan { // (the plan in force: plan_commit)
+    int n_frames = 0, W = 0, H = 0, sample_bbox_height = 0;
+    Opts o{};
+    Calib cal{};
+    cs_owner own; // every device block below
+    Needs cap;    // capacity of every size class (batch_reserve)
+    cs_pinned<uint8_t> stage[2]; hipEvent_t stage_ev[2] = {nullptr, nullptr}; int stage_k = 0; // pinned staging of cs_cuboid_batch_set_scene's uploads
+    // the two branches of a run that read nothing of each other -- poses / edge lists / vanishing points, and the image: Canny, components, distance transform -- on two
+    // streams, joined before the sweep (cs_cuboid_batch_run): a small batch (one frame of a drop-in call, config 4's 512 units) does not fill the chip and its kernels are
+    // per-unit latency chains, so the branches cost their sum when queued behind each other
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr; // (the second stream is the context's: cs_ctx::aux_stream)
+    int score_G = 256;      // workgroups of cuboid_sweep_score (one per CU)
+    int score_T = 512;      // threads per workgroup (CUBESLAM_SCORE_THREADS = 256 | 512 | 768 | 1024: 1 / 2 / 3 / 4 waves per SIMD with 128 / 256 / 168 / 128 registers)
+    bool score_T_forced = false; // set by the environment: cs_cuboid_batch_set_shared_gpu leaves it alone
+    bool want_carry = false; // cs_cuboid_detect's box-to-box chain asks cuboid_select which roll / pitch sample the last kept proposal carries
+    // device, sized once (cs_cuboid_batch_create)
+    uint8_t *d_gray = nullptr;
+    FrameInfo *d_fi = nullptr; FrameDyn *d_fd = nullptr; CamRP *d_cam = nullptr;
+    double *d_yaw = nullptr;
+    int *d_status = nullptr, *d_cursor = nullptr; // (d_cursor: the work cursor of cuboid_sweep_score)
+    // device, sized by the plan (batch_arrays)
+    uint8_t *d_emap = nullptr, *d_flag = nullptr;
+    float *d_dist = nullptr;
+    int *d_lab = nullptr; // aliases d_dist
+    int *d_dttmp = nullptr; long *d_dttmp_off = nullptr;
+    int *d_wgmap = nullptr;
+    int *d_order = nullptr; // cuboid_sweep_score: units by falling cost estimate
+    int *d_uflag = nullptr; // per unit: 1 = a pixel without a 16-bit code (scored from the float map)
+    double *d_lines_in = nullptr, *d_lines_al = nullptr, *d_mlines = nullptr, *d_mangle = nullptr, *d_mmid = nullptr;
+    Unit *d_units = nullptr; UnitDyn *d_ud = nullptr; int *d_box_first = nullptr, *d_counts = nullptr, *d_carry = nullptr;
+    VPEntry *d_vp = nullptr;
+    int *d_vcount = nullptr, *d_vlist = nullptr; // per unit: number of surviving proposals and their hypothesis indices
+    double *d_derr = nullptr, *d_aerr = nullptr, *d_score = nullptr, *d_nscore = nullptr;
+    unsigned long long *d_ckd = nullptr, *d_cka = nullptr; int *d_cidx = nullptr;
+    cs_cuboid *d_out = nullptr;
+    cs_cuboid_batch() { cap.fill(-1); }
+};
+static void plan_commit(cs_cuboid_batch *b, Plan &P) { static_cast<Plan &>(*b) = std::move(P); }
+
+// The plan-sized arrays, each stated once: it holds cap[cls] * mul + add elements.
+struct BatchArray { void **slot; int cls; size_t elem, mul, add; };
+template <class T> static BatchArray array_of(T *&p, int cls, size_t mul = 1, size_t add = 0) { return {reinterpret_cast<void **>(&p), cls, sizeof(T), mul, add}; }
+constexpr size_t N_BATCH_ARRAYS = 29;
+static std::array<BatchArray, N_BATCH_ARRAYS> batch_arrays(cs_cuboid_batch *b) {
+    return {{array_of(b->d_emap, K_PIX, 1, 256), // slack: the wave distance transform reads whole dwords at the row ends
+             array_of(b->d_dist, K_PIX),
+             array_of(b->d_flag, K_HYP), array_of(b->d_vlist, K_HYP), array_of(b->d_derr, K_HYP), array_of(b->d_aerr, K_HYP), array_of(b->d_score, K_HYP), array_of(b->d_nscore, K_HYP),
+             array_of(b->d_ckd, K_HYP), array_of(b->d_cka, K_HYP), array_of(b->d_cidx, K_HYP),
+             array_of(b->d_vp, K_VP),
+             array_of(b->d_units, K_UNITS), array_of(b->d_ud, K_UNITS), array_of(b->d_order, K_UNITS), array_of(b->d_uflag, K_UNITS), array_of(b->d_vcount, K_UNITS, 2),
+             array_of(b->d_dttmp_off, K_UNITS, 1, 1),
+             array_of(b->d_box_first, K_BOXES), array_of(b->d_counts, K_BOXES), array_of(b->d_carry, K_BOXES), array_of(b->d_out, K_BOXES, (size_t)b->o.max_cuboid_num),
+             array_of(b->d_lines_in, K_LINES_IN, 4), array_of(b->d_lines_al, K_LINES_IN, 4),
+             array_of(b->d_mlines, K_LINE_ROWS, 4), array_of(b->d_mangle, K_LINE_ROWS), array_of(b->d_mmid, K_LINE_ROWS, 2),
+             array_of(b->d_wgmap, K_WGMAP),
+             array_of(b->d_dttmp, K_DTTMP)}};
+}
+// Room for `need` units of every class; exact: no headroom (create), else a quarter of it (a stream's box sizes wander) and 64 more for the two line classes.  Every array of
+// every class that has to grow is allocated BEFORE the batch is touched: if one fails, the new blocks go back and the batch is bit for bit what it was.  Then the streams that
+// may still use the old blocks are drained, once, and blocks and capacities change hands.  Nothing waits when nothing grows.
+static int batch_reserve(cs_ctx *ctx, cs_cuboid_batch *b, const Needs &need, bool exact) {
+    Needs cap = b->cap;
+    for (int c = 0; c < K_N; c++)
+        if (need[c] > cap[c]) cap[c] = exact ? need[c] : need[c] + need[c] / 4 + (c == K_LINES_IN || c == K_LINE_ROWS ? 64 : 0);
+    if (cap == b->cap) return CS_OK;
+    const auto arrays = batch_arrays(b);
+    cs_owner fresh;
+    std::array<uint8_t *, N_BATCH_ARRAYS> blk{};
+    for (size_t i = 0; i < arrays.size(); i++) {
+        const BatchArray &A = arrays[i];
+        if (cap[A.cls] == b->cap[A.cls]) continue;
+        const int r = fresh.alloc(ctx, &blk[i], std::max<size_t>(1, (size_t)cap[A.cls] * A.mul + A.add) * A.elem);
+        if (r != CS_OK) { fresh.free_all(ctx); return r; }
+    }
+    bool replaces = false; // (a batch that is being created has no block anything could still use: nothing to wait for)
+    for (size_t i = 0; i < arrays.size(); i++) replaces |= blk[i] && *arrays[i].slot;
+    const hipError_t e = replaces ? ctx->drain() : hipSuccess;
+    if (e != hipSuccess) { fresh.free_all(ctx); ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    for (size_t i = 0; i < arrays.size(); i++)
+        if (blk[i]) { if (*arrays[i].slot) b->own.free_one(ctx, *arrays[i].slot); *arrays[i].slot = blk[i]; }
+    b->own.adopt(fresh);
+    b->cap = cap;
+    b->d_lab = (int *)b->d_dist;
+    return CS_OK;
+}
+// The plan in force to the device: units, frame records, first unit of every box, order, scratch offsets, workgroup map and n_lines edge rows (0: the lists stay), as copies on
+// the context's stream.  The sources are the caller's: they stay untouched until the stream has passed the copies.
+struct PlanSrc { const Unit *units; const FrameInfo *fi; const int *box_first, *order; const long *dt_off; const int *wgmap; const double *lines; };
+static int plan_upload(cs_ctx *ctx, cs_cuboid_batch *b, const PlanSrc &S, size_t n_lines) {
+    CS_TRY(cs_h2d(ctx, b->d_units, S.units, (size_t)b->n_units));
+    CS_TRY(cs_h2d(ctx, b->d_fi, S.fi, (size_t)b->n_frames));
+    CS_TRY(cs_h2d(ctx, b->d_box_first, S.box_first, (size_t)b->n_boxes));
+    CS_TRY(cs_h2d(ctx, b->d_order, S.order, (size_t)b->n_units));
+    CS_TRY(cs_h2d(ctx, b->d_dttmp_off, S.dt_off, (size_t)b->n_units + 1));
+    CS_TRY(cs_h2d(ctx, b->d_wgmap, S.wgmap, (size_t)b->n_nms + b->n_cc + b->n_hb));
+    return cs_h2d(ctx, b->d_lines_in, S.lines, n_lines * 4);
+}
+// The side branch of a run between its fork and the main stream's wait for it.  Until ev_join is recorded on the side stream, every way out of the run waits for that stream
+// itself; from then on every way out makes the context's stream wait for the event, as the run's own join does.
+struct SideBranch {
+    cs_ctx *ctx; hipStream_t side = nullptr; hipEvent_t joined = nullptr;
+    hipError_t join() { const hipEvent_t e = joined; side = nullptr; joined = nullptr; return e ? hipStreamWaitEvent(ctx->stream, e, 0) : hipSuccess; }
+    ~SideBranch() { if (joined) hipStreamWaitEvent(ctx->stream, joined, 0); else if (side) hipStreamSynchronize(side); }
+};
 
 extern "C" {
 
@@ -1957,12 +2020,9 @@ void cs_cuboid_default_opts(cs_cuboid_opts *o) {
 
 void cs_cuboid_batch_destroy(cs_ctx *ctx, cs_cuboid_batch *b) {
     if (!b) return;
-    if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    void *ptrs[] = {b->d_gray, b->d_emap, b->d_flag, b->d_dist, b->d_dttmp, b->d_dttmp_off, b->d_fi, b->d_fd, b->d_cam, b->d_yaw, b->d_lines_in, b->d_lines_al,
-                    b->d_mlines, b->d_mangle, b->d_mmid, b->d_units, b->d_ud, b->d_box_first, b->d_status, b->d_counts, b->d_carry, b->d_vp,
-                    b->d_derr, b->d_aerr, b->d_score, b->d_nscore, b->d_ckd, b->d_cka, b->d_cidx, b->d_out, b->d_vcount, b->d_vlist, b->d_order, b->d_cursor, b->d_uflag, b->d_wgmap};
-    for (void *p : ptrs) cs_dfree(ctx, p);
-    for (int k = 0; k < 2; k++) { if (b->h_stage[k]) hipHostFree(b->h_stage[k]); if (b->stage_ev[k]) hipEventDestroy(b->stage_ev[k]); }
+    if (ctx) { hipSetDevice(ctx->device); ctx->drain(); }
+    b->own.free_all(ctx);
+    for (int k = 0; k < 2; k++) { b->stage[k].release(); if (b->stage_ev[k]) hipEventDestroy(b->stage_ev[k]); }
     if (b->ev_fork) hipEventDestroy(b->ev_fork);
     if (b->ev_join) hipEventDestroy(b->ev_join);
     delete b;
@@ -1993,97 +2053,50 @@ int cs_cuboid_batch_create(cs_ctx *ctx, int n_frames, int width, int height, con
     if ((int)std::lrint((double)(0.955f * 65536)) != DT_HV || (int)std::lrint((double)(1.3693f * 65536)) != DT_DIAG) {
         ctx->err = "chamfer constants mismatch"; delete b; return CS_ERR_BAD_ARG;
     }
-    const int n_boxes = box_offsets[n_frames], n_lines = line_offsets[n_frames];
     b->sample_bbox_height = opts->whether_sample_bbox_height;
+    for (const void *fn : {reinterpret_cast<const void *>(cuboid_sweep_score<256>), reinterpret_cast<const void *>(cuboid_sweep_score<512>), reinterpret_cast<const void *>(cuboid_sweep_score<768>),
+                           reinterpret_cast<const void *>(cuboid_sweep_score<1024>)}) { // (per call: the attribute is per device)
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_BYTES);
+        if (e != hipSuccess) { ctx->err = hipGetErrorString(e); delete b; return CS_ERR_HIP; }
+    }
     {
-        Plan P;
-        const int status = plan_build(o, b->sample_bbox_height, n_frames, width, height, Twc, box_offsets, boxes, line_offsets, nullptr, P);
-        if (status == CS_ERR_CAPACITY) { delete b; return status; }
-        if (status != CS_OK) { ctx->err = "box ROI outside the image"; delete b; return status; }
+        static int cu_of_device[64]; // (hipGetDeviceProperties is slow enough to show in the per-frame call: asked once per device)
+        const int dv = ctx->device & 63;
+        int cus = __atomic_load_n(&cu_of_device[dv], __ATOMIC_RELAXED);
+        if (cus == 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0) __atomic_store_n(&cu_of_device[dv], cus, __ATOMIC_RELAXED);
+        if (cus > 0) b->score_G = cus;
+    }
+    const char *ge = getenv("CUBESLAM_SCORE_SEGMENTS"); // tuning knob: workgroups of cuboid_sweep_score
+    if (ge && atoi(ge) > 0) b->score_G = atoi(ge);
+    const char *te = getenv("CUBESLAM_SCORE_THREADS"); // tuning knob: 512 (2 waves per SIMD, 256 registers) or 1024 (4 waves per SIMD, 128 registers)
+    if (te && (atoi(te) == 256 || atoi(te) == 512 || atoi(te) == 768 || atoi(te) == 1024)) { b->score_T = atoi(te); b->score_T_forced = true; }
+    Plan P;
+    int r = plan_build(ctx, o, b->sample_bbox_height, n_frames, width, height, Twc, box_offsets, boxes, line_offsets, lines, nullptr, P);
+    if (r != CS_OK) { delete b; return r; }
+    plan_derived(P, b->score_G);
+    const size_t npx = (size_t)n_frames * width * height, n_lines = (size_t)line_offsets[n_frames];
+    r = batch_reserve(ctx, b, plan_needs(P, (long)n_lines), true); // exact sizes: nothing here knows whether another scene will come
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_gray, npx);
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_fi, (size_t)n_frames);
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_fd, (size_t)n_frames);
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_cam, (size_t)n_frames * RP_CAP);
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_yaw, (size_t)n_frames * o.yaw_cap);
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_status, (size_t)1);
+    if (r == CS_OK) r = b->own.alloc(ctx, &b->d_cursor, (size_t)1);
+    if (r == CS_OK) {
         plan_commit(b, P);
+        // the slices' padding (to 64 pixels) stays zero: cuboid_sweep_score encodes whole groups of 8
+        const hipError_t e = hipMemsetAsync(b->d_dist, 0, sizeof(float) * (size_t)b->pix_total, ctx->stream);
+        if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
     }
-    b->cap_pix = b->pix_total; b->cap_hyp = b->hyp_total; b->cap_vp = b->vp_total; b->cap_units = b->n_units; b->cap_boxes = n_boxes;
-
-#define A_(call) do { int r__ = (call); if (r__ != CS_OK) { cs_cuboid_batch_destroy(ctx, b); return r__; } } while (0)
-    const size_t npx = (size_t)n_frames * width * height;
-    A_(cs_dalloc(ctx, &b->d_gray, npx));
-    A_(cs_dalloc(ctx, &b->d_emap, (size_t)b->pix_total + 256)); // slack: the wave distance transform reads whole dwords at the row ends
-    {
-        for (const void *fn : {reinterpret_cast<const void *>(cuboid_sweep_score<256>), reinterpret_cast<const void *>(cuboid_sweep_score<512>), reinterpret_cast<const void *>(cuboid_sweep_score<768>),
-                               reinterpret_cast<const void *>(cuboid_sweep_score<1024>)}) { // (per call: the attribute is per device)
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_BYTES);
-            if (e != hipSuccess) { ctx->err = hipGetErrorString(e); cs_cuboid_batch_destroy(ctx, b); return CS_ERR_HIP; }
-        }
-        {
-            static int cu_of_device[64]; // (hipGetDeviceProperties is slow enough to show in the per-frame call: asked once per device)
-            const int dv = ctx->device & 63;
-            int cus = __atomic_load_n(&cu_of_device[dv], __ATOMIC_RELAXED);
-            if (cus == 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0) __atomic_store_n(&cu_of_device[dv], cus, __ATOMIC_RELAXED);
-            if (cus > 0) b->score_G = cus;
-        }
-        const char *ge = getenv("CUBESLAM_SCORE_SEGMENTS"); // tuning knob: workgroups of cuboid_sweep_score
-        if (ge && atoi(ge) > 0) b->score_G = atoi(ge);
-        const char *te = getenv("CUBESLAM_SCORE_THREADS"); // tuning knob: 512 (2 waves per SIMD, 256 registers) or 1024 (4 waves per SIMD, 128 registers)
-        if (te && (atoi(te) == 256 || atoi(te) == 512 || atoi(te) == 768 || atoi(te) == 1024)) { b->score_T = atoi(te); b->score_T_forced = true; }
-        std::vector<long> dt_off; std::vector<int> order, wgmap;
-        plan_derived(b, dt_off, order, wgmap);
-        b->cap_wgmap = (int)std::max<size_t>(wgmap.size(), 1);
-        A_(cs_dalloc(ctx, &b->d_wgmap, (size_t)b->cap_wgmap));
-        A_(cs_h2d(ctx, b->d_wgmap, wgmap.data(), wgmap.size()));
-        b->cap_dttmp = std::max<long>(dt_off.back(), 1);
-        A_(cs_dalloc(ctx, &b->d_dttmp, (size_t)b->cap_dttmp));
-        A_(cs_dalloc(ctx, &b->d_dttmp_off, dt_off.size()));
-        A_(cs_h2d(ctx, b->d_dttmp_off, dt_off.data(), dt_off.size()));
-        A_(cs_dalloc(ctx, &b->d_order, std::max<size_t>(1, order.size())));
-        A_(cs_h2d(ctx, b->d_order, order.data(), order.size()));
-        CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the two vectors are locals)
-        A_(cs_dalloc(ctx, &b->d_cursor, (size_t)1));
-        A_(cs_dalloc(ctx, &b->d_uflag, (size_t)std::max(1, b->n_units)));
-    }
-    A_(cs_dalloc(ctx, &b->d_dist, (size_t)b->pix_total));
-    CS_HIP(ctx, hipMemsetAsync(b->d_dist, 0, sizeof(float) * (size_t)b->pix_total, ctx->stream)); // the slices' padding (to 64 pixels) stays zero: cuboid_sweep_score encodes whole groups of 8
-    b->d_lab = (int *)b->d_dist;
-    A_(cs_dalloc(ctx, &b->d_fi, (size_t)n_frames));
-    A_(cs_dalloc(ctx, &b->d_fd, (size_t)n_frames));
-    A_(cs_dalloc(ctx, &b->d_cam, (size_t)n_frames * RP_CAP));
-    A_(cs_dalloc(ctx, &b->d_yaw, (size_t)n_frames * o.yaw_cap));
-    A_(cs_dalloc(ctx, &b->d_lines_in, (size_t)n_lines * 4));
-    A_(cs_dalloc(ctx, &b->d_lines_al, (size_t)n_lines * 4));
-    A_(cs_dalloc(ctx, &b->d_mlines, (size_t)b->line_rows * 4));
-    A_(cs_dalloc(ctx, &b->d_mangle, (size_t)b->line_rows));
-    A_(cs_dalloc(ctx, &b->d_mmid, (size_t)b->line_rows * 2));
-    b->cap_lines_in = n_lines; b->cap_line_rows = b->line_rows;
-    A_(cs_dalloc(ctx, &b->d_units, (size_t)b->n_units));
-    A_(cs_dalloc(ctx, &b->d_ud, (size_t)b->n_units));
-    A_(cs_dalloc(ctx, &b->d_box_first, (size_t)n_boxes));
-    A_(cs_dalloc(ctx, &b->d_status, (size_t)1));
-    A_(cs_dalloc(ctx, &b->d_counts, (size_t)n_boxes));
-    A_(cs_dalloc(ctx, &b->d_carry, (size_t)n_boxes));
-    A_(cs_dalloc(ctx, &b->d_vp, (size_t)b->vp_total));
-    A_(cs_dalloc(ctx, &b->d_flag, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_vcount, (size_t)std::max<size_t>(1, 2 * b->units.size())));
-    A_(cs_dalloc(ctx, &b->d_vlist, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_derr, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_aerr, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_score, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_nscore, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_ckd, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_cka, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_cidx, (size_t)b->hyp_total));
-    A_(cs_dalloc(ctx, &b->d_out, (size_t)n_boxes * o.max_cuboid_num));
-    A_(cs_h2d(ctx, b->d_gray, gray, npx));
-    A_(cs_h2d(ctx, b->d_fi, b->fi.data(), (size_t)n_frames));
-    A_(cs_h2d(ctx, b->d_lines_in, lines, (size_t)n_lines * 4));
-    A_(cs_h2d(ctx, b->d_units, b->units.data(), (size_t)b->n_units));
-    A_(cs_h2d(ctx, b->d_box_first, b->box_first_unit.data(), (size_t)n_boxes));
-    { hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) { ctx->err = hipGetErrorString(e); cs_cuboid_batch_destroy(ctx, b); return CS_ERR_HIP; } }
-#undef A_
+    if (r == CS_OK) r = cs_h2d(ctx, b->d_gray, gray, npx);
+    if (r == CS_OK) r = plan_upload(ctx, b, {b->units.data(), b->fi.data(), b->box_first_unit.data(), b->order.data(), b->dt_off.data(), b->wgmap.data(), lines}, n_lines);
+    if (r == CS_OK) { const hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; } } // (the sources are the caller's and the plan's)
+    if (r != CS_OK) { cs_cuboid_batch_destroy(ctx, b); return r; }
     *out = b;
     return CS_OK;
 }
 
-// New edge lists for the frames of an existing batch (same frames, boxes and options): what a step of the chain detect_filter_lines ->
-// detect_cuboid (main_obj.cpp:428-449) hands over when the frames stay resident.  Only the line ranges of the plan change.
 int cs_cuboid_batch_n_frames(const cs_cuboid_batch *b) { return b ? b->n_frames : -1; }
 int cs_cuboid_batch_n_boxes(const cs_cuboid_batch *b) { return b ? b->n_boxes : -1; }
 int cs_cuboid_batch_geometry(const cs_cuboid_batch *b, int *width, int *height, int *n_frames) { // (library-internal, see cs_orb_geometry)
@@ -2098,12 +2111,13 @@ int cs_cuboid_batch_set_gray_device(cs_ctx *ctx, cs_cuboid_batch *b, const uint8
     CS_HIP(ctx, hipMemcpyAsync(b->d_gray, d_gray, (size_t)b->n_frames * b->W * b->H, hipMemcpyDeviceToDevice, ctx->stream));
     return CS_OK;
 }
+// New edge lists for the frames of an existing batch (same frames, boxes and options): what a step of the chain detect_filter_lines ->
+// detect_cuboid (main_obj.cpp:428-449) hands over when the frames stay resident.  Only the line ranges of the plan change.
 int cs_cuboid_batch_set_lines(cs_ctx *ctx, cs_cuboid_batch *b, const int *line_offsets, const double *lines) {
-    if (!ctx || !b || !line_offsets || (line_offsets[b->n_frames] > 0 && !lines)) return CS_ERR_BAD_ARG;
+    if (!ctx || !b || !cs_offsets_ok(line_offsets, b->n_frames, lines)) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (a run still reading the old lists)
     const int n_lines = line_offsets[b->n_frames];
-    // the new plan is worked out beside the old one and committed only when every check and allocation has succeeded: a failure leaves the batch as it was
+    // the new ranges are worked out beside the old ones and written only when every check and allocation has succeeded: a failure leaves the batch as it was
     std::vector<int> unit_off(b->units.size());
     long rows = 0;
     for (size_t u = 0; u < b->units.size(); u++) {
@@ -2111,106 +2125,52 @@ int cs_cuboid_batch_set_lines(cs_ctx *ctx, cs_cuboid_batch *b, const int *line_o
         unit_off[u] = (int)rows; rows += std::min(line_offsets[f + 1] - line_offsets[f], CS_MAX_ROI_LINES);
         if (rows > INT_MAX) return CS_ERR_CAPACITY;
     }
-    int r;
-    if (n_lines > b->cap_lines_in) {
-        const size_t cap = (size_t)n_lines + n_lines / 4 + 64;
-        double *a = nullptr, *c = nullptr;
-        r = cs_dalloc(ctx, &a, cap * 4); if (r) return r;
-        r = cs_dalloc(ctx, &c, cap * 4); if (r) { cs_dfree(ctx, a); return r; }
-        cs_dfree(ctx, b->d_lines_in); cs_dfree(ctx, b->d_lines_al);
-        b->d_lines_in = a; b->d_lines_al = c; b->cap_lines_in = (long)cap;
-    }
-    if (rows > b->cap_line_rows) {
-        const size_t cap = (size_t)rows + rows / 4 + 64;
-        decltype(b->d_mlines) m1 = nullptr; decltype(b->d_mangle) m2 = nullptr; decltype(b->d_mmid) m3 = nullptr;
-        r = cs_dalloc(ctx, &m1, cap * 4); if (r) return r;
-        r = cs_dalloc(ctx, &m2, cap); if (r) { cs_dfree(ctx, m1); return r; }
-        r = cs_dalloc(ctx, &m3, cap * 2); if (r) { cs_dfree(ctx, m1); cs_dfree(ctx, m2); return r; }
-        cs_dfree(ctx, b->d_mlines); cs_dfree(ctx, b->d_mangle); cs_dfree(ctx, b->d_mmid);
-        b->d_mlines = m1; b->d_mangle = m2; b->d_mmid = m3; b->cap_line_rows = (long)cap;
-    }
+    Needs need; need.fill(-1);
+    need[K_LINES_IN] = n_lines; need[K_LINE_ROWS] = rows;
+    CS_TRY(batch_reserve(ctx, b, need, false));
     for (int f = 0; f < b->n_frames; f++) { b->fi[f].line_off = line_offsets[f]; b->fi[f].n_lines = line_offsets[f + 1] - line_offsets[f]; }
     for (size_t u = 0; u < b->units.size(); u++) b->units[u].line_off = unit_off[u];
     b->line_rows = rows;
-    if (n_lines > 0) { r = cs_h2d(ctx, b->d_lines_in, lines, (size_t)n_lines * 4); if (r) return r; }
-    r = cs_h2d(ctx, b->d_fi, b->fi.data(), (size_t)b->n_frames); if (r) return r;
-    r = cs_h2d(ctx, b->d_units, b->units.data(), (size_t)b->n_units); if (r) return r;
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CS_TRY(cs_h2d(ctx, b->d_lines_in, lines, (size_t)n_lines * 4));
+    CS_TRY(cs_h2d(ctx, b->d_fi, b->fi.data(), (size_t)b->n_frames));
+    CS_TRY(cs_h2d(ctx, b->d_units, b->units.data(), (size_t)b->n_units));
+    CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the sources are the caller's and the batch's own records)
     return CS_OK;
 }
 
 // Other 2-D boxes, camera poses and (optionally) edge lists for the frames of an existing batch -- what every call of detect_cuboid brings with its pixels
 // (detect_3d_cuboid.h:62-63, main_obj.cpp:420-449).  The plan (ROIs, top samples, arena slices: box_proposal_detail.cpp:107-161) is rebuilt on the host -- it is a function
 // of the boxes and poses alone, ~0.2 ms for 3 072 units -- and goes to the device from pinned staging as copies on the context's stream behind whatever run still reads the
-// old plan: nothing waits unless an arena has to grow.  line_offsets NULL: the edge lists stay.  The frame count, the
-// image size and the options are the batch's.
+// old plan: nothing waits unless an arena has to grow.  line_offsets NULL: the edge lists stay.  The frame count, the image size and the options are the batch's.
+// The order: (1) the new plan and what follows from it, beside the old one; (2) the pinned staging block, waited for, grown and filled; (3) batch_reserve; (4) plan_commit;
+// (5) the uploads; (6) cuboid_clear_pad.  Whatever fails before (4) leaves the batch as it was, and nothing that can fail stands between (3) and (4).
 int cs_cuboid_batch_set_scene(cs_ctx *ctx, cs_cuboid_batch *b, const double *Twc, const int *box_offsets, const double *boxes, const int *line_offsets, const double *lines) {
-    if (!ctx || !b || !Twc || !box_offsets || (box_offsets[b->n_frames] > 0 && !boxes) || (line_offsets && line_offsets[b->n_frames] > 0 && !lines)) return CS_ERR_BAD_ARG;
+    if (!ctx || !b || !Twc || !box_offsets) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     Plan P;
-    int r = plan_build(b->o, b->sample_bbox_height, b->n_frames, b->W, b->H, Twc, box_offsets, boxes, line_offsets, &b->fi, P);
-    if (r == CS_ERR_BAD_ARG) ctx->err = "box ROI outside the image";
-    if (r != CS_OK) return r; // (the batch is as it was)
-    const int n_lines = line_offsets ? line_offsets[b->n_frames] : 0, n_units = (int)P.units.size(), n_boxes = P.n_boxes;
-    // arenas that are too small for this plan: wait for the runs that read them, then grow (a quarter of headroom: a stream's box sizes wander)
-    bool synced = false;
-    auto grow = [&](auto **p, size_t n) -> int { if (!synced) { CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); synced = true; } cs_dfree(ctx, *p); *p = nullptr; return cs_dalloc(ctx, p, n); };
-#define G_(call) do { r = (call); if (r != CS_OK) return r; } while (0)
-    if (P.pix_total > b->cap_pix) {
-        const long c = P.pix_total + P.pix_total / 4;
-        G_(grow(&b->d_emap, (size_t)c + 256)); G_(grow(&b->d_dist, (size_t)c)); b->d_lab = (int *)b->d_dist; b->cap_pix = c;
-    }
-    if (P.hyp_total > b->cap_hyp) {
-        const long c = P.hyp_total + P.hyp_total / 4;
-        G_(grow(&b->d_flag, (size_t)c)); G_(grow(&b->d_vlist, (size_t)c)); G_(grow(&b->d_derr, (size_t)c)); G_(grow(&b->d_aerr, (size_t)c)); G_(grow(&b->d_score, (size_t)c)); G_(grow(&b->d_nscore, (size_t)c));
-        G_(grow(&b->d_ckd, (size_t)c)); G_(grow(&b->d_cka, (size_t)c)); G_(grow(&b->d_cidx, (size_t)c)); b->cap_hyp = c;
-    }
-    if (P.vp_total > b->cap_vp) { const long c = P.vp_total + P.vp_total / 4; G_(grow(&b->d_vp, (size_t)c)); b->cap_vp = c; }
-    if (n_units > b->cap_units) {
-        const int c = n_units + n_units / 4;
-        G_(grow(&b->d_units, (size_t)c)); G_(grow(&b->d_ud, (size_t)c)); G_(grow(&b->d_order, (size_t)c)); G_(grow(&b->d_uflag, (size_t)c)); G_(grow(&b->d_vcount, (size_t)2 * c)); G_(grow(&b->d_dttmp_off, (size_t)c + 1));
-        b->cap_units = c;
-    }
-    if (n_boxes > b->cap_boxes) {
-        const int c = n_boxes + n_boxes / 4;
-        G_(grow(&b->d_box_first, (size_t)c)); G_(grow(&b->d_counts, (size_t)c)); G_(grow(&b->d_carry, (size_t)c)); G_(grow(&b->d_out, (size_t)c * b->o.max_cuboid_num)); b->cap_boxes = c;
-    }
-    if (line_offsets && n_lines > b->cap_lines_in) { const long c = (long)n_lines + n_lines / 4 + 64; G_(grow(&b->d_lines_in, (size_t)c * 4)); G_(grow(&b->d_lines_al, (size_t)c * 4)); b->cap_lines_in = c; }
-    if (P.line_rows > b->cap_line_rows) { const long c = P.line_rows + P.line_rows / 4 + 64; G_(grow(&b->d_mlines, (size_t)c * 4)); G_(grow(&b->d_mangle, (size_t)c)); G_(grow(&b->d_mmid, (size_t)c * 2)); b->cap_line_rows = c; }
-    plan_commit(b, P);
-    std::vector<long> dt_off; std::vector<int> order, wgmap;
-    plan_derived(b, dt_off, order, wgmap);
-    if ((int)wgmap.size() > b->cap_wgmap) { const int c = (int)(wgmap.size() + wgmap.size() / 4); G_(grow(&b->d_wgmap, (size_t)c)); b->cap_wgmap = c; }
-    if (std::max<long>(dt_off.back(), 1) > b->cap_dttmp) { const long c = dt_off.back() + dt_off.back() / 4; G_(grow(&b->d_dttmp, (size_t)c)); b->cap_dttmp = c; }
-    // one pinned block: units | frame records | first unit of every box | order | scratch offsets | edge lists; two blocks alternate, a block is reused once its copies are through
-    const int k = b->stage_k; b->stage_k ^= 1;
-    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    const size_t o_units = 0, o_fi = al(o_units + sizeof(Unit) * (size_t)n_units), o_bf = al(o_fi + sizeof(FrameInfo) * (size_t)b->n_frames), o_ord = al(o_bf + sizeof(int) * (size_t)n_boxes),
-                 o_dt = al(o_ord + sizeof(int) * (size_t)n_units), o_wg = al(o_dt + sizeof(long) * ((size_t)n_units + 1)), o_ln = al(o_wg + sizeof(int) * wgmap.size()), total = al(o_ln + sizeof(double) * 4 * (size_t)n_lines);
+    CS_TRY(plan_build(ctx, b->o, b->sample_bbox_height, b->n_frames, b->W, b->H, Twc, box_offsets, boxes, line_offsets, lines, &b->fi, P));
+    plan_derived(P, b->score_G);
+    const size_t n_lines = line_offsets ? (size_t)line_offsets[b->n_frames] : 0, n_units = (size_t)P.n_units;
+    // one pinned block holds every source of plan_upload, 64-byte aligned; two blocks alternate, a block is reused once its copies are through
+    const int k = b->stage_k;
     if (!b->stage_ev[k]) CS_HIP(ctx, hipEventCreateWithFlags(&b->stage_ev[k], hipEventDisableTiming));
     else CS_HIP(ctx, hipEventSynchronize(b->stage_ev[k]));
-    if (total > b->stage_cap[k]) {
-        if (b->h_stage[k]) hipHostFree(b->h_stage[k]);
-        b->h_stage[k] = nullptr; b->stage_cap[k] = 0;
-        CS_HIP(ctx, hipHostMalloc((void **)&b->h_stage[k], total + total / 4, hipHostMallocDefault));
-        b->stage_cap[k] = total + total / 4;
-    }
-    uint8_t *h = b->h_stage[k];
-    memcpy(h + o_units, b->units.data(), sizeof(Unit) * (size_t)n_units); memcpy(h + o_fi, b->fi.data(), sizeof(FrameInfo) * (size_t)b->n_frames);
-    memcpy(h + o_bf, b->box_first_unit.data(), sizeof(int) * (size_t)n_boxes); memcpy(h + o_ord, order.data(), sizeof(int) * (size_t)n_units);
-    memcpy(h + o_dt, dt_off.data(), sizeof(long) * ((size_t)n_units + 1));
-    memcpy(h + o_wg, wgmap.data(), sizeof(int) * wgmap.size());
-    if (n_lines) memcpy(h + o_ln, lines, sizeof(double) * 4 * (size_t)n_lines);
-    G_(cs_h2d(ctx, b->d_units, reinterpret_cast<const Unit *>(h + o_units), (size_t)n_units));
-    G_(cs_h2d(ctx, b->d_fi, reinterpret_cast<const FrameInfo *>(h + o_fi), (size_t)b->n_frames));
-    G_(cs_h2d(ctx, b->d_box_first, reinterpret_cast<const int *>(h + o_bf), (size_t)n_boxes));
-    G_(cs_h2d(ctx, b->d_order, reinterpret_cast<const int *>(h + o_ord), (size_t)n_units));
-    G_(cs_h2d(ctx, b->d_dttmp_off, reinterpret_cast<const long *>(h + o_dt), (size_t)n_units + 1));
-    G_(cs_h2d(ctx, b->d_wgmap, reinterpret_cast<const int *>(h + o_wg), wgmap.size()));
-    if (n_lines) G_(cs_h2d(ctx, b->d_lines_in, reinterpret_cast<const double *>(h + o_ln), (size_t)n_lines * 4));
+    const void *src[7] = {P.units.data(), P.fi.data(), P.box_first_unit.data(), P.order.data(), P.dt_off.data(), P.wgmap.data(), lines};
+    const size_t bytes[7] = {sizeof(Unit) * n_units, sizeof(FrameInfo) * (size_t)b->n_frames, sizeof(int) * (size_t)P.n_boxes, sizeof(int) * n_units, sizeof(long) * (n_units + 1),
+                             sizeof(int) * P.wgmap.size(), sizeof(double) * 4 * n_lines};
+    size_t at[8] = {0};
+    for (int i = 0; i < 7; i++) at[i + 1] = (at[i] + bytes[i] + 63) & ~(size_t)63;
+    CS_TRY(b->stage[k].reserve(ctx, at[7]));
+    uint8_t *h = b->stage[k].p;
+    for (int i = 0; i < 7; i++) if (bytes[i]) memcpy(h + at[i], src[i], bytes[i]);
+    // last of what can fail: blocks that grow come back uninitialised, so nothing may stand between this and the commit with its uploads
+    CS_TRY(batch_reserve(ctx, b, plan_needs(P, line_offsets ? (long)n_lines : -1), false));
+    b->stage_k ^= 1;
+    plan_commit(b, P);
+    CS_TRY(plan_upload(ctx, b, {reinterpret_cast<const Unit *>(h + at[0]), reinterpret_cast<const FrameInfo *>(h + at[1]), reinterpret_cast<const int *>(h + at[2]), reinterpret_cast<const int *>(h + at[3]),
+                                reinterpret_cast<const long *>(h + at[4]), reinterpret_cast<const int *>(h + at[5]), reinterpret_cast<const double *>(h + at[6])}, n_lines));
     CS_HIP(ctx, hipEventRecord(b->stage_ev[k], ctx->stream));
-    if (n_units) CS_LAUNCH(ctx, "cuboid_clear_pad", cuboid_clear_pad, dim3((n_units + 3) / 4), dim3(256), 0, b->d_units, n_units, b->d_dist);
-#undef G_
+    if (b->n_units) CS_LAUNCH(ctx, "cuboid_clear_pad", cuboid_clear_pad, dim3((b->n_units + 3) / 4), dim3(256), 0, b->d_units, b->n_units, b->d_dist);
     return CS_OK;
 }
 
@@ -2237,27 +2197,24 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
     }
     int ul_cap = 1;
     for (const FrameInfo &fi_ : b->fi) ul_cap = std::max(ul_cap, std::min(fi_.n_lines, CS_MAX_ROI_LINES));
-    // (per-kernel event timing reads one stream: a timed run keeps everything on it)
+    // poses, edge lists and vanishing points read nothing of the image branch: on the side stream, or (per-kernel event timing reads one stream) in front of it on this one
     const bool fork = !ctx->timing;
+    hipStream_t side = ctx->stream;
+    SideBranch branch{ctx};
     if (fork) {
-        if (!ctx->aux_stream) CS_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        hipStream_t side = ctx->aux_stream;
-        if (!b->ev_fork) {
-            CS_HIP(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-            CS_HIP(ctx, hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
-        }
+        CS_HIP(ctx, ctx->aux_get(&side));
+        if (!b->ev_fork) CS_HIP(ctx, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
+        if (!b->ev_join) CS_HIP(ctx, hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
         CS_HIP(ctx, hipEventRecord(b->ev_fork, ctx->stream)); // behind the two memsets above, the batch's uploads and the last run's readers
+        branch.side = side;
         CS_HIP(ctx, hipStreamWaitEvent(side, b->ev_fork, 0));
-        hipLaunchKernelGGL(cuboid_frame_prep, dim3(b->n_frames), dim3(64), 0, side, b->d_fi, b->d_fd, b->d_cam, b->d_yaw, b->cal, b->o, b->d_lines_in, b->d_lines_al);
-        hipLaunchKernelGGL(cuboid_unit_lines, dim3(U), dim3(64), sizeof(double) * 5 * (size_t)ul_cap, side, b->d_units, b->d_ud, b->d_fi, b->d_lines_al, b->d_mlines, b->d_mangle, b->d_mmid, b->d_status, ul_cap);
-        hipLaunchKernelGGL(cuboid_vp, dim3(b->max_vp_blocks, U), dim3(256), 0, side, b->d_units, b->d_ud, b->d_fd, b->d_cam, b->d_yaw, b->o, b->d_mangle, b->d_mmid, b->d_vp);
-        CS_HIP(ctx, hipEventRecord(b->ev_join, side));
-    } else {
-        CS_LAUNCH(ctx, "cuboid_frame_prep", cuboid_frame_prep, dim3(b->n_frames), dim3(64), 0, b->d_fi, b->d_fd, b->d_cam, b->d_yaw, b->cal, b->o,
-                  b->d_lines_in, b->d_lines_al);
-        CS_LAUNCH(ctx, "cuboid_unit_lines", cuboid_unit_lines, dim3(U), dim3(64), sizeof(double) * 5 * (size_t)ul_cap, b->d_units, b->d_ud, b->d_fi, b->d_lines_al, b->d_mlines,
-                  b->d_mangle, b->d_mmid, b->d_status, ul_cap);
     }
+    CS_LAUNCH_ON(ctx, side, "cuboid_frame_prep", cuboid_frame_prep, dim3(b->n_frames), dim3(64), 0, b->d_fi, b->d_fd, b->d_cam, b->d_yaw, b->cal, b->o, b->d_lines_in, b->d_lines_al);
+    CS_LAUNCH_ON(ctx, side, "cuboid_unit_lines", cuboid_unit_lines, dim3(U), dim3(64), sizeof(double) * 5 * (size_t)ul_cap, b->d_units, b->d_ud, b->d_fi, b->d_lines_al, b->d_mlines,
+                 b->d_mangle, b->d_mmid, b->d_status, ul_cap);
+    CS_LAUNCH_ON(ctx, side, "cuboid_vp", cuboid_vp, dim3(b->max_vp_blocks, U), dim3(256), 0, b->d_units, b->d_ud, b->d_fd, b->d_cam, b->d_yaw, b->o, b->d_mangle, b->d_mmid, b->d_vp);
+    CS_HIP(ctx, hipGetLastError());
+    if (fork) { CS_HIP(ctx, hipEventRecord(b->ev_join, side)); branch.joined = b->ev_join; }
     CS_HIP(ctx, hipMemsetAsync(b->d_emap, 0, (size_t)b->pix_total, ctx->stream));
     CS_LAUNCH(ctx, "cuboid_canny_nms", cuboid_canny_nms, dim3(b->n_nms), dim3(256), 0, b->d_units, b->d_wgmap, b->d_gray, b->W, b->H, b->d_emap,
               b->d_lab, b->o.canny_low, b->o.canny_high);
@@ -2278,10 +2235,7 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
         const int wbuf = b->max_roi_w + 2;
         CS_LAUNCH(ctx, "cuboid_dt", cuboid_dt, dim3((U + 3) / 4), dim3(256), (size_t)wbuf * DT_SERIAL_ROW_BYTES, b->d_units, U, b->d_emap, b->d_dist, wbuf);
     }
-    if (fork) CS_HIP(ctx, hipStreamWaitEvent(ctx->stream, b->ev_join, 0));
-    else
-        CS_LAUNCH(ctx, "cuboid_vp", cuboid_vp, dim3(b->max_vp_blocks, U), dim3(256), 0, b->d_units, b->d_ud, b->d_fd, b->d_cam, b->d_yaw, b->o,
-                  b->d_mangle, b->d_mmid, b->d_vp);
+    CS_HIP(ctx, branch.join());
     CS_HIP(ctx, hipMemsetAsync(b->d_vcount, 0, sizeof(int) * 2 * (size_t)U, ctx->stream));
     CS_LAUNCH(ctx, "cuboid_sweep_filter", cuboid_sweep_filter, dim3(b->n_hb), dim3(256), 0, b->d_units, b->d_wgmap + b->n_nms + b->n_cc, b->d_fd, b->o, b->d_vp,
               b->d_flag, b->d_vcount, b->d_vlist);
@@ -2289,18 +2243,12 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
     CS_HIP(ctx, hipMemsetAsync(b->d_uflag, 0, sizeof(int) * (size_t)U, ctx->stream));
     {
         const int items = U * b->score_slices, grid = std::min(b->score_G, items);
-        if (b->score_T == 256)
-            CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<256>, dim3(grid), dim3(256), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
-        else if (b->score_T == 512)
-            CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<512>, dim3(grid), dim3(512), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
-        else if (b->score_T == 768)
-            CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<768>, dim3(grid), dim3(768), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
-        else
-            CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<1024>, dim3(grid), dim3(1024), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp,
-                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr);
+        switch (b->score_T) {
+#define SCORE_(nt) case nt: CS_LAUNCH(ctx, "cuboid_sweep_score", cuboid_sweep_score<nt>, dim3(grid), dim3(nt), SC_LDS_BYTES, b->d_units, b->d_order, items, b->score_slices, b->d_cursor, b->d_vp, \
+                                      b->d_dist, b->d_vcount, b->d_vlist, b->d_uflag, b->d_derr, b->d_aerr); break;
+            SCORE_(256) SCORE_(512) SCORE_(768) SCORE_(1024)
+#undef SCORE_
+        }
     }
     CS_LAUNCH(ctx, "cuboid_select", cuboid_select, dim3(b->n_boxes), dim3(256), 0, b->d_units, b->d_ud, b->d_box_first, b->d_fd, b->d_fi,
               b->d_cam, b->d_yaw, b->cal, b->o, b->d_flag, b->d_derr, b->d_aerr, b->d_vp, b->d_score, b->d_nscore,

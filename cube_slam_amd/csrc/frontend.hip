@@ -367,7 +367,9 @@ int cs_frontend_stream_push(cs_frontend *fe, const uint8_t *gray) { return strea
 // rows of 5) and their edge lists (line_offsets NULL: the batch's lists stay).  The step that takes the
 // slot rebuilds the cuboid batch's plan for them (cs_cuboid_batch_set_scene).
 int cs_frontend_stream_push_scene(cs_frontend *fe, const uint8_t *gray, const double *Twc, const int *box_offsets, const double *boxes, const int *line_offsets, const double *lines) {
-    if (!fe || !fe->batch || !Twc || !box_offsets) return CS_ERR_BAD_ARG;
+    if (!fe || !fe->batch || !fe->ring || !Twc) return CS_ERR_BAD_ARG;
+    const int F = fe->ring->n_frames; // (the slot's copy of the scene reads boxes and lines by these offsets)
+    if (!cs_offsets_ok(box_offsets, F, boxes) || (line_offsets && !cs_offsets_ok(line_offsets, F, lines))) return CS_ERR_BAD_ARG;
     return stream_push(fe, gray, Twc, box_offsets, boxes, line_offsets, lines);
 }
 static int stream_push(cs_frontend *fe, const uint8_t *gray, const double *Twc, const int *box_offsets, const double *boxes, const int *line_offsets, const double *lines) {

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define CS_VERSION 108 /* 108: cs_stereo_* (Frame::ComputeStereoMatches on the extractor's resident buffers); 107: cs_match_by_projection_stream takes n_queries / n_train, cs_cuboid_batch_set_boxes, the matchers' claim passes run on the device; 106: cs_cuboid_batch_n_frames, cs_frontend_queues, cs_match_by_projection_stream, cs_frontend_stream_*, cs_*_set_frames_device, cs_orb_read_packed; 105: cs_frontend_set_backlog; 104: cs_frontend_set_cuboid_ctx; 103: cs_lsd_read_filter_lines takes the caller's frame count, cs_frontend_set_chain; 102: cs_cuboid_batch_set_lines, cs_cuboid_batch_set_shared_gpu, cs_lsd_read_filter_lines; 101: cs_ba_set_stop_flag_bool / cs_ba_dyn_set_stop_flag_bool; cs_match_by_projection_frame takes train_blocked */
+#define CS_VERSION 108 /* 108: cs_stereo_* (Frame::ComputeStereoMatches on the extractor's resident buffers); 107: cs_match_by_projection_stream takes n_queries / n_train, cs_cuboid_batch_set_scene, the matchers' claim passes run on the device; 106: cs_cuboid_batch_n_frames, cs_frontend_queues, cs_match_by_projection_stream, cs_frontend_stream_*, cs_*_set_frames_device, cs_orb_read_packed; 105: cs_frontend_set_backlog; 104: cs_frontend_set_cuboid_ctx; 103: cs_lsd_read_filter_lines takes the caller's frame count, cs_frontend_set_chain; 102: cs_cuboid_batch_set_lines, cs_cuboid_batch_set_shared_gpu, cs_lsd_read_filter_lines; 101: cs_ba_set_stop_flag_bool / cs_ba_dyn_set_stop_flag_bool; cs_match_by_projection_frame takes train_blocked */
 
 typedef enum cs_status {
     CS_OK = 0,
@@ -144,7 +144,8 @@ int cs_cuboid_batch_n_frames(const cs_cuboid_batch *b);
 /* Other 2-D boxes, camera poses and (line_offsets non-NULL) edge lists for the frames of an existing batch -- the arguments every call of detect_cuboid brings with its
  * pixels (detect_3d_cuboid.h:62-63).  Same frame count, image size and options; layouts as in cs_cuboid_batch_create.  The plan of the sweep (ROIs, top samples, arena
  * slices: box_proposal_detail.cpp:107-161) is rebuilt for them on the host (a function of boxes and poses alone) and uploaded from pinned staging on the context's stream
- * behind the run that still reads the old one; the call waits only when an arena has to grow.  A box whose ROI leaves the image: CS_ERR_BAD_ARG, the batch stays as it was.
+ * behind the run that still reads the old one; the call waits only when an arena has to grow.  A box whose ROI leaves the image, offsets that do not start at 0 or
+ * that decrease, rows that are NULL where the offsets count some: CS_ERR_BAD_ARG; after that or a failed allocation the batch stays as it was.
  * Results (cs_cuboid_batch_read) then hold box_offsets[n_frames] boxes. */
 int cs_cuboid_batch_set_scene(cs_ctx *ctx, cs_cuboid_batch *b, const double *Twc, const int *box_offsets, const double *boxes, const int *line_offsets, const double *lines);
 int cs_cuboid_batch_n_boxes(const cs_cuboid_batch *b);

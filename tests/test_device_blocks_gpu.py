@@ -12,7 +12,12 @@ The granule: the runtime carves small blocks out of 2 MiB chunks, 4 KiB apiece. 
 one after the other, 4-byte blocks moved it by 2 097 152 bytes at the 257th and again at every 512th after it (twice the same), and by nothing in between.  So 2 MiB is
 the only step there is, and a pass that merely tips into the next chunk is not a leak.
 REPEATS: a block leaked once per call must cost at least four times ALLOWED_DROP.  200 held 4-byte blocks cost 0 bytes and 1000 cost 4 MiB, which is too few; 2560 cost
-10 485 760 bytes = 5 x ALLOWED_DROP (measured in the same session), so every loop runs 2560 times.  A part takes 0.1 to 0.4 s at that count."""
+10 485 760 bytes = 5 x ALLOWED_DROP (measured in the same session), so every loop runs 2560 times.  A part takes 0.1 to 0.4 s at that count.
+
+cs_cuboid_batch is the one handle that is re-planned while it lives: its parts (cuboid_batch_parts) take it through create / destroy, through every growth path of batch_reserve
+and down its refusals.  The same loops against the commit before batch_reserve, 2560 repeats each, on an MI355X: drop of free memory 0 bytes in every part (so PARENT_DROP
+stays 0); seconds per part: create_destroy 0.31, create_set_scene_destroy 0.97, alternate_set_scene 0.18, alternate_set_lines 0.13, refuse_create 0.05, refuse_set_scene 0.56.
+refuse_offsets could not run there: that commit read boxes and lines by whatever offsets it was handed."""
 import ctypes as C
 
 import numpy as np
@@ -21,7 +26,7 @@ import pytest
 from cube_slam_amd import synth
 from cube_slam_amd._lib import CubeSlamError, lib
 from cube_slam_amd.bow import KeyFrameDatabase, ORBVocabulary
-from cube_slam_amd.cuboid import detect_3d_cuboid
+from cube_slam_amd.cuboid import CuboidBatch, detect_3d_cuboid
 from cube_slam_amd.matcher import ORBmatcher
 from cube_slam_amd.optimizer import EssentialGraph, OptimizeSim3, correct_points, sim3_log
 from cube_slam_amd.stereo import StereoMatcher
@@ -147,6 +152,65 @@ def _sim3_refusal(ctx):  # correspondence offsets that decrease
                                        _p(np.zeros(1, np.uint8), C.c_uint8), _p(z, C.c_double), None, _p(np.zeros(1, np.int32), C.c_int)), CS_ERR_BAD_ARG)
 
 
+# ---- cs_cuboid_batch: the handle whose arrays are re-planned while it lives -----------------------------------------------------------------------
+# One 128 x 96 frame of zeros (content does not matter for ownership) and the box (30, 20, 60, 50): ew = 10, the ROI (20, 10) .. (100, 80) lies inside the image, nine top samples.
+CB_GRAY = np.zeros((1, 96, 128), np.uint8)
+CB_T = synth.camera_pose(height=1.1, pitch_deg=25.0, yaw_deg=0.0)[None]
+CB_LINES = np.array([[22.0 + 3 * i, 12.0, 24.0 + 3 * i, 78.0] for i in range(24)])
+CB_SMALL = ([np.array([[30.0, 20.0, 60.0, 50.0, 0.9]])], [CB_LINES[:4]])  # (boxes of every frame, lines of every frame)
+CB_LARGE = ([np.array([[30.0, 20.0, 60.0, 50.0, 0.9], [10.0, 10.0, 40.0, 40.0, 0.9], [60.0, 30.0, 50.0, 50.0, 0.9]])], [CB_LINES])  # three units, six times the lines: every size class grows
+CB_OUTSIDE = ([np.array([[200.0, 20.0, 60.0, 50.0, 0.9]])], [CB_LINES[:4]])  # roi_x = 190 lies right of the last column
+
+
+def cb_create(ctx, scene):
+    return CuboidBatch(ctx, CB_GRAY, synth.K_TUM, CB_T, scene[0], scene[1], detect_3d_cuboid(ctx).opts())
+
+
+def cb_refused(fn):
+    with pytest.raises(CubeSlamError, match="CS_ERR_BAD_ARG"):
+        fn()
+
+
+def cb_runs_and_reads(b):
+    b.run()
+    assert len(b.read()) == b.n_boxes
+
+
+def cuboid_batch_parts(ctx, small, lines):
+    """small: a batch created on CB_SMALL that the alternating set_scene part grows once; lines: another one for the alternating set_lines part"""
+    def create_destroy():
+        cb_create(ctx, CB_SMALL).close()
+
+    def create_grow_destroy():
+        b = cb_create(ctx, CB_SMALL)
+        b.set_scene(CB_T, *CB_LARGE)
+        b.close()
+
+    def alternate_scenes():
+        small.set_scene(CB_T, *CB_LARGE)
+        small.set_scene(CB_T, *CB_SMALL)
+
+    def alternate_lines():
+        lines.set_lines(CB_LARGE[1])
+        lines.set_lines(CB_SMALL[1])
+
+    def refuse_create():
+        cb_refused(lambda: cb_create(ctx, CB_OUTSIDE))
+
+    def refuse_scene():
+        cb_refused(lambda: small.set_scene(CB_T, *CB_OUTSIDE))
+        cb_runs_and_reads(small)
+
+    def refuse_offsets():  # what cs_frontend_stream_push_scene hands on: box offsets that decrease, line offsets that do not start at 0
+        T, bo, boxes, lo, ln = CuboidBatch.pack_scene(CB_T, *CB_SMALL)
+        cb_refused(lambda: small.set_scene(None, None, packed=(T, np.array([0, -1], np.int32), boxes, lo, ln)))
+        cb_refused(lambda: small.set_scene(None, None, packed=(T, bo, boxes, np.array([1, 4], np.int32), ln)))
+        cb_runs_and_reads(small)
+
+    return {"create_destroy": create_destroy, "create_set_scene_destroy": create_grow_destroy, "alternate_set_scene": alternate_scenes, "alternate_set_lines": alternate_lines,
+            "refuse_create": refuse_create, "refuse_set_scene": refuse_scene, "refuse_offsets": refuse_offsets}
+
+
 @pytest.fixture(scope="module")
 def resident(ctx):
     """a vocabulary and a database of two key frames for the one-shot calls"""
@@ -177,6 +241,20 @@ def test_one_shot_calls_return_their_scratch(ctx, resident, name):
     base = free_bytes()
     fn()
     check_drop(name + " refused", base - free_bytes())
+
+
+@gpu
+@pytest.mark.parametrize("name", ["create_destroy", "create_set_scene_destroy", "alternate_set_scene", "alternate_set_lines", "refuse_create", "refuse_set_scene", "refuse_offsets"])
+def test_cuboid_batch_returns_every_block(ctx, name):
+    """cs_cuboid_batch through create, reserve (set_scene, set_lines) and destroy, and down each refusal; every part has batches of its own, so none hides another's leak"""
+    small, lines = cb_create(ctx, CB_SMALL), cb_create(ctx, CB_SMALL)
+    try:
+        check_drop("cs_cuboid_batch " + name, drop_after(cuboid_batch_parts(ctx, small, lines)[name], REPEATS))
+        cb_runs_and_reads(small)
+        cb_runs_and_reads(lines)
+    finally:
+        small.close()
+        lines.close()
 
 
 @gpu

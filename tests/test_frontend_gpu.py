@@ -341,6 +341,42 @@ def test_streaming_source_carries_boxes_poses_and_lines(ctx, oracle):
     fe.close(); batch.close()
 
 
+def test_push_scene_refuses_bad_offsets_and_missing_rows(ctx):
+    """cs_frontend_stream_push_scene copies a slot's scene by the offsets it is handed, so it checks them itself: offsets that decrease or do not start at 0, and rows that
+    are NULL where the offsets count some, return CS_ERR_BAD_ARG before anything is read or the slot is taken; the scene pushed after them runs as if they had not been."""
+    import ctypes as C
+    F = 2
+    first, second = ([synth.cuboid_scene(940 + 10 * k + i, n_boxes=2) for i in range(F)] for k in range(2))
+    K = first[0]["K"]
+    opts = detect_3d_cuboid(ctx).opts()
+    mk = lambda sc: CuboidBatch(ctx, np.ascontiguousarray(np.stack([s["gray"] for s in sc])), K, np.stack([s["Twc"] for s in sc]), [s["boxes"] for s in sc], [s["lines"] for s in sc], opts)  # noqa: E731
+    batch = mk(first)
+    fe = Frontend(ctx, orb=None, batch=batch, line_detectors=[])
+    fe.stream_begin(F, 640, 480, n_slots=2)
+    gray = np.ascontiguousarray(np.stack([s["gray"] for s in second]))
+    packed = CuboidBatch.pack_scene(np.stack([s["Twc"] for s in second]), [s["boxes"] for s in second], [s["lines"] for s in second])
+    T, bo, boxes, lo, lines = packed
+    assert bo.tolist() == [0, 2, 4] and lo[F] > 0
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    ip = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).ctypes.data_as(C.POINTER(C.c_int))  # noqa: E731
+    push = lambda bo_, boxes_, lo_, lines_: _lib.lib().cs_frontend_stream_push_scene(fe._fe, gray.ctypes.data_as(C.POINTER(C.c_uint8)), dp(T), ip(bo_), dp(boxes_), ip(lo_), dp(lines_))  # noqa: E731
+    CS_ERR_BAD_ARG = -2
+    assert push(np.array([0, 4, 2]), boxes, lo, lines) == CS_ERR_BAD_ARG  # box offsets that decrease
+    assert push(bo + 1, boxes, lo, lines) == CS_ERR_BAD_ARG  # ... that do not start at 0
+    assert push(bo, None, lo, lines) == CS_ERR_BAD_ARG  # four boxes counted, no rows
+    assert push(bo, boxes, np.array([0, int(lo[F]), int(lo[1])]), lines) == CS_ERR_BAD_ARG  # line offsets that decrease
+    assert push(bo, boxes, lo, None) == CS_ERR_BAD_ARG  # lines counted, no rows
+    fe.stream_push_scene(gray, packed)  # no slot was taken: this is the first step's scene
+    fe.step()
+    ctx.sync()
+    got = batch.read()
+    fe.stream_end()
+    want_b = mk(second); want_b.run(); want = want_b.read(); want_b.close()
+    assert len(got) == len(want) == 4 and sum(len(c) for c in want) >= 1
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(got, want))
+    fe.close(); batch.close()
+
+
 def test_phased_passes_with_the_chain(ctx, oracle, monkeypatch):
     """Phased runner + chained hand-over together (a phased worker still runs rectangles / LBD of pass k - W when step k hands it the next pass; its packet must be
     filed under ITS number): ten steps complete, and the cuboids from the chained lines equal a batch that was given detect_filter_lines' lists directly."""

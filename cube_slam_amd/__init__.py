@@ -6,3 +6,4 @@ package is the thin host-side mirror of the reference interfaces used by tests a
 from . import _lib  # noqa: F401
 from .stereo import ComputeStereoMatches, StereoMatcher  # noqa: F401
 from .bow import KeyFrameDatabase, ORBVocabulary  # noqa: F401
+from .local_mapping import ComputeDistinctiveDescriptors, KeyFrameView, LocalMapping, UpdateNormalAndDepth  # noqa: F401

@@ -23,6 +23,7 @@
 //   match_bow_dists      SearchByBoW: the distances of a feature to its node's features, as candidate lists for match_resolve
 //   match_knn2           all-pairs best / second best, train descriptors staged through LDS
 #include "common.h"
+#include "cv_math.h"
 #include "glibc_logf.h"
 
 #include <algorithm>
@@ -166,14 +167,7 @@ __global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const 
 // (and one whose ratio is not a positive normal float) is an invalid query and is counted in *n_outside; the call goes on.
 enum { PM_SIM3 = 0, PM_PAIR = 1, PM_RELOC = 2 };
 struct MapP { float R[9], t[3], Ow[3], R2[9], t2[3]; float fx, fy, cx, cy, log_sf, th; int n_levels; };
-__device__ __forceinline__ void gemm3(const float *R, const float *p, const float *t, float *o) {
-    for (int r = 0; r < 3; r++) {
-        double sacc = 0;
-        for (int k = 0; k < 3; k++) sacc += (double)R[r * 3 + k] * (double)p[k];
-        o[r] = (float)(sacc * 1.0 + (double)t[r] * 1.0);
-    }
-}
-__device__ __forceinline__ float norm3(const float *v) { double s = 0; for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k]; return (float)sqrt(s); }
+// gemm3 / norm3: cv_math.h
 template <int MODE> __global__ void __launch_bounds__(256) match_project_map(int n, const float *world_pos, const float *normal, const float *min_distance, const float *max_distance, const uint8_t *skip,
                                                                              MapP P, const float *scale_factors, FrameP F, QueryS *q, int *level, int *n_outside) {
     const int i = blockIdx.x * 256 + threadIdx.x;

@@ -737,6 +737,49 @@ int cs_bow_db_query(cs_ctx *ctx, cs_bow_db *db, int n_query, const int *q_off, c
                     long *out_order, int *out_common, int *out_minword, double *out_score);
 void cs_bow_db_destroy(cs_bow_db *db);
 
+/* ===================================================================== local mapping
+ * The triangulation loop of ORB_SLAM2::LocalMapping::CreateNewMapPoints (orb_object_slam/src/LocalMapping.cc:319-570) and the per-point upkeep
+ * MapPoint::ComputeDistinctiveDescriptors / MapPoint::UpdateNormalAndDepth (MapPoint.cc:381-446, :469-510).
+ *
+ * CreateNewMapPoints builds its matcher as ORBmatcher(0.6, false): SearchForTriangulation then neither cuts by rotation nor claims key points of the neighbour, so the match of
+ * a key point idx1 in a neighbour depends on idx1 and that neighbour alone, and the only coupling between neighbours is pKF1->GetMapPoint(idx1) (ORBmatcher.cc:721-725), non-NULL
+ * exactly where an earlier neighbour's triangulation succeeded.  The loop therefore equals: search every neighbour with the INITIAL skip1, triangulate all pairs of all
+ * neighbours independently, and per idx1 keep the first neighbour in order whose pair was accepted.  The test :402-407 can never fire: the search has already skipped key points
+ * that are not static (skip1 / skip2 of cs_match_for_triangulation), so there is no argument for it. */
+typedef struct cs_lm_frame {             /* what :329-344, :381-393 and the loop read of a KeyFrame */
+    const cs_keypoint *keysUn;           /* mvKeysUn */
+    const float *keys_xy;                /* mvKeys[i].pt as x, y (KeyFrame::UnprojectStereo, KeyFrame.cc:675-691, reads the distorted key point) */
+    const float *u_right, *depth;        /* mvuRight, mvDepth */
+    int N;
+    float Rcw[9], tcw[3], Ow[3];         /* GetRotation(), GetTranslation(), GetCameraCenter() as stored; the library forms Rwc = Rcw.t() and Tcw = [Rcw | tcw], both copies */
+    float fx, fy, cx, cy, invfx, invfy, mbf, mb;
+    const float *scale_factors, *level_sigma2; /* mvScaleFactors, mvLevelSigma2 */
+    int n_levels;
+    float scale_factor;                  /* mfScaleFactor (read of the current key frame only: ratioFactor = 1.5f * mfScaleFactor) */
+} cs_lm_frame;
+/* matches12[n_neigh * N1]: per neighbour the matches12 of cs_match_for_triangulation run with the initial skip1.  The pairs are the entries >= 0, in neighbour order and then
+ * idx1 ascending (the order of vMatchedPairs): pair_off[n_neigh + 1] and, per pair, idx1, idx2, x3D[3] and a status byte -- 0 a point is created, else the first test that
+ * failed: 1 parallax :467, 2 w == 0 :452, 3 z1 :473, 4 z2 :477, 5 reprojection in the current key frame :492 / :503, 6 in the neighbour :518 / :529, 7 zero distance :540,
+ * 8 scale :548, 9 an earlier neighbour created the point of idx1, 10 a stereo key point (u_right >= 0) with depth <= 0 where the reference reads the empty Mat of UnprojectStereo.
+ * x3D is 0 0 0 for 1, 2 and 10.  new_pair_of_idx1[N1] = the pair that creates the point of idx1, -1 none; *nnew their number.  The reference creates the points in pair order.
+ * cv::SVD and cos(2 * atan2(mb / 2, depth)) are the library's stated definitions (csrc/triangulate_math.h).
+ * CS_ERR_BAD_ARG (nothing written, nothing launched): NULL arguments, n_neigh outside 0..32, a matches12 entry >= N2 or < -1, an octave outside 0..n_levels - 1;
+ * CS_ERR_CAPACITY (nothing written but pair_off) when there are more than pair_cap pairs. */
+#define CS_LM_MAX_NEIGHBOURS 32
+int cs_create_new_map_points(cs_ctx *ctx, const cs_lm_frame *kf, const cs_lm_frame *neighbours, int n_neigh, const int *matches12, int pair_cap, int *pair_off, int *pair_idx1,
+                             int *pair_idx2, float *x3D, uint8_t *status, int *new_pair_of_idx1, int *nnew);
+/* MapPoint::ComputeDistinctiveDescriptors for n_points points: the observations of point p are desc[32 * obs_off[p]] .. desc[32 * obs_off[p + 1]), in the iteration order of
+ * mObservations with bad key frames left out (:400-406).  best[p] = index within the run of the first row whose sorted distances have the smallest vDists[int(0.5 * (N - 1))],
+ * -1 for an empty run (the reference returns and keeps mDescriptor). */
+int cs_mappoint_distinctive_descriptors(cs_ctx *ctx, int n_points, const int *obs_off, const uint8_t *desc, int *best);
+/* MapPoint::UpdateNormalAndDepth for n_points points: obs_kf[obs_off[p]] .. = index into kf_Ow[3 * n_kf] (GetCameraCenter) of every observing key frame in the order of
+ * mObservations; ref_kf[p] / ref_octave[p] = mpRefKF and the octave of its key point; scale_factors[n_levels] = mvScaleFactors.  normal[3 n] = mNormalVector, min_distance /
+ * max_distance = mfMinDistance / mfMaxDistance; updated[p] = 1, or 0 for an empty run, whose three outputs are left untouched.  normali / cv::norm(normali) and normal / n are
+ * float(v_k * (1.0 / s)) (the stated definition of the cv::MatExpr scale).  CS_ERR_BAD_ARG: an index outside its table. */
+int cs_mappoint_update_normal_and_depth(cs_ctx *ctx, int n_points, const float *world_pos, const int *obs_off, const int *obs_kf, int n_kf, const float *kf_Ow,
+                                        const int *ref_kf, const int *ref_octave, const float *scale_factors, int n_levels, float *normal, float *min_distance,
+                                        float *max_distance, uint8_t *updated);
+
 #ifdef __cplusplus
 }
 #endif

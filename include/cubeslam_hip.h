@@ -780,6 +780,31 @@ int cs_mappoint_update_normal_and_depth(cs_ctx *ctx, int n_points, const float *
                                         const int *ref_kf, const int *ref_octave, const float *scale_factors, int n_levels, float *normal, float *min_distance,
                                         float *max_distance, uint8_t *updated);
 
+/* ---- Sim3Solver (orb_object_slam/src/Sim3Solver.cc), the RANSAC of LoopClosing::ComputeSim3 (LoopClosing.cc:231-342): every hypothesis of every loop candidate in one call.
+ * Problem p (one Sim3Solver) has the correspondences corr_off[p] .. corr_off[p + 1] -- X3Dc1 / X3Dc2 the floats of mvX3Dc1 / mvX3Dc2 (:92-96), max_err1 / max_err2 =
+ * mvnMaxError1 / 2 (:85-86; std::vector<size_t> in this reference, so the caller passes (float)(size_t)(9.210 * sigma2)) -- K8[8 p ..] = fx fy cx cy of mK1, then of mK2, fix_scale[p] = mbFixScale, and the hypotheses hyp_off[p] .. hyp_off[p + 1]; triples[3 h ..] are
+ * the three indices (into the problem's correspondences) that iteration draws at :161-175.  Per hypothesis: ComputeSim3 (:224-334) on the triple and CheckInliers (:336-360)
+ * on all N correspondences -> n_inliers[h] = mnInliersi, sRt[13 h ..] = ms12i, mR12i row-major, mt12i, and the mask of mvbInliersi: hypothesis h of problem p owns the
+ * W_p = (N_p + 31) / 32 words from  sum over q < p of (hyp_off[q + 1] - hyp_off[q]) * W_q  +  (h - hyp_off[p]) * W_p,  bit (i & 31) of word (i >> 5) = mvbInliersi[i], the bits
+ * from N_p up 0 (cs_sim3_solver_mask_words gives the total).  cv::eigen and atan2 + cv::Rodrigues are the library's stated definitions (csrc/horn_math.h, INTEGRATION.md
+ * 8b'); where the reference's values turn NaN or inf (a coincident triple, a zero imaginary part, den == 0, a point with z == 0) they do here, and nothing is an inlier of a
+ * NaN test.  One launch (one wave per hypothesis) and one read-back.
+ * ctx == NULL evaluates the same text (csrc/horn_math.h) on the host, one thread, with the same checks and byte-equal results: the comparison side of tests and bench, asked
+ * for explicitly -- a call with a context never runs it.
+ * CS_ERR_BAD_ARG (nothing written, nothing launched): NULL arrays, offsets that do not start at 0 or decrease, a triple index outside 0..N_p - 1, two equal indices in a
+ * triple, a problem with hypotheses and N_p < 3.  n_problems == 0 or a problem without hypotheses: success, nothing launched for it. */
+int cs_sim3_solver_hypotheses(cs_ctx *ctx, int n_problems, const int *corr_off, const float *X3Dc1, const float *X3Dc2, const float *max_err1, const float *max_err2,
+                              const float *K8, const uint8_t *fix_scale, const int *hyp_off, const int *triples, int *n_inliers, float *sRt, uint32_t *inlier_mask);
+long cs_sim3_solver_mask_words(int n_problems, const int *corr_off, const int *hyp_off); /* -1 for NULL or decreasing offsets */
+/* Sim3Solver::SetRansacParameters :118-133 -> mRansacMaxIts, with the float epsilon and the double log / pow as written; 0 for N < min_inliers, where iterate returns at :144
+ * and the value is never read.  Where ceil(log / log) does not fit an int (N in the thousands at a small min_inliers) the reference's conversion is
+ * undefined -- x86 yields one iteration --; the library takes max_iterations.  Host only. */
+int cs_sim3_solver_max_iterations(double probability, int min_inliers, int max_iterations, int N);
+/* The loop :156-199 and the test :201 of Sim3Solver::iterate(nIterations, bNoMore, ...) over the table n_inliers[ransac_max_its] of the solver's hypotheses in drawing order
+ * (N >= min_inliers: :144 is the caller's, with cs_sim3_solver_max_iterations == 0).  *mnIterations and *mnBestInliers live across calls (both start at 0);
+ * *best_hypothesis is the hypothesis of mBestT12 and friends (-1 until there is one).  Returns the hypothesis whose mBestT12 iterate returns, or -1 (cv::Mat()).  Host only. */
+int cs_sim3_solver_walk(const int *n_inliers, int ransac_max_its, int min_inliers, int *mnIterations, int *mnBestInliers, int *best_hypothesis, int nIterations, int *bNoMore);
+
 #ifdef __cplusplus
 }
 #endif

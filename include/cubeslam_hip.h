@@ -805,6 +805,43 @@ int cs_sim3_solver_max_iterations(double probability, int min_inliers, int max_i
  * *best_hypothesis is the hypothesis of mBestT12 and friends (-1 until there is one).  Returns the hypothesis whose mBestT12 iterate returns, or -1 (cv::Mat()).  Host only. */
 int cs_sim3_solver_walk(const int *n_inliers, int ransac_max_its, int min_inliers, int *mnIterations, int *mnBestInliers, int *best_hypothesis, int nIterations, int *bNoMore);
 
+/* ---- PnPsolver (orb_object_slam/src/PnPsolver.cc), the RANSAC over EPnP of Tracking::Relocalization (Tracking.cc:2876-3030): every hypothesis of every relocalisation
+ * candidate, and every distinct Refine(), in one call.  Problem p (one PnPsolver) has the correspondences corr_off[p] .. corr_off[p + 1] -- P3Dw / P2D the floats of mvP3Dw /
+ * mvP2D (:89-93), max_err = mvMaxError (:155) --, K4[4 p ..] = fu fv uc vc (:104-107), min_inliers[p] = mRansacMinInliers as SetRansacParameters adjusted it (:133-138),
+ * best_in[p] = mnBestInliers carried into this table (0 for a solver's first table) and the hypotheses hyp_off[p] .. hyp_off[p + 1]; quads[4 h ..] are the four indices (into
+ * the problem's correspondences) that iteration draws at :187-200.  Per hypothesis: compute_pose (:482-532) on the quad and CheckInliers (:305-336) on all N correspondences ->
+ * n_inliers[h] = mnInliersi, Rt[12 h ..] = mRi row-major, mti, and the mask of mvbInliersi in the word layout of cs_sim3_solver_hypotheses (cs_sim3_solver_mask_words gives
+ * the total).  A hypothesis is a record where n_inliers[h] >= min_inliers[p] and n_inliers[h] > every earlier count of the problem and best_in[p] (:208-211); records are found
+ * on the device.  Refine() (:258-303) always runs on mvbBestInliers, the mask of the latest record, so its distinct results are one per record: refined_n[h] =
+ * mnRefinedInliers, refined_Rt[12 h ..], refined_mask (same layout) = mvbRefinedInliers; refined_n[h] = -1 and zeros where h is no record.
+ * status[h]: bit 0 -- qr_solve met a zero column (:916-921) in the hypothesis, bit 1 -- in its refinement; there the reference leaves X unwritten, and the library adds the
+ * previous iteration's increment (zeros before the first solve).  Bit 2: h is a record.  cvSVD, cvInvert, cvSolve and cvMulTransposed are the library's stated definitions
+ * (csrc/cv_svd_math.h, INTEGRATION.md 8b''); inf and NaN arise where the reference's statements make them (betas[0] == 0 -- two pairs of coincident points in a quad, for
+ * one --, Zc == 0) and nothing is an inlier of an inf or NaN test; a coplanar or collinear quad and a single pair of coincident points give finite poses, because the SVD forms of
+ * cvInvert and cvSolve leave out the vanishing singular values.  Three launches back to back and one read-back; the per-point arrays of a refinement live in the call's scratch, there is no cap on N_p: the scratch
+ * is reserved for every hypothesis, 104 N_p bytes each (which hypotheses are records is found on the device, and the bound the counts give -- N_p - min_inliers + 1 records -- is
+ * no smaller than n_hyp_p at the parameters of Relocalization), so a call needs 104 * sum over p of n_hyp_p * N_p bytes of device memory: 23 MB at 16 x 35 x 400, 156 MB at
+ * 300 hypotheses on 5 000 correspondences; CS_ERR_HIP where the device cannot give them.
+ * ctx == NULL evaluates the same text (csrc/epnp_math.h) on the host, one thread, with the same checks and byte-equal results: the comparison side of tests and bench, asked
+ * for explicitly -- a call with a context never runs it.
+ * CS_ERR_BAD_ARG (nothing written, nothing launched): NULL arrays, offsets that do not start at 0 or decrease, a quad index outside 0..N_p - 1 or repeated within its quad, a
+ * problem with hypotheses and N_p < 4 or min_inliers[p] < 4 (:136-137 make it at least minSet).  n_problems == 0 or a problem without hypotheses: success. */
+int cs_pnp_solver_evaluate(cs_ctx *ctx, int n_problems, const int *corr_off, const float *P3Dw, const float *P2D, const float *max_err, const float *K4, const int *min_inliers,
+                           const int *best_in, const int *hyp_off, const int *quads, int *n_inliers, double *Rt, uint32_t *status, uint32_t *inlier_mask, int *refined_n,
+                           double *refined_Rt, uint32_t *refined_mask);
+/* PnPsolver::SetRansacParameters :120-151 for N correspondences -> the adjusted mRansacMinInliers, mRansacMaxIts and mRansacEpsilon, with the float epsilon and the double
+ * log / pow as written (pow(epsilon, 3), :149).  Where ceil(log / log) does not fit an int the library takes maxIterations, as cs_sim3_solver_max_iterations does.  Host only. */
+int cs_pnp_solver_ransac_parameters(double probability, int minInliers, int maxIterations, int minSet, float epsilon, int N, int *mRansacMinInliers, int *mRansacMaxIts,
+                                    float *mRansacEpsilon);
+/* The loop :181-237 and the tail :239-255 of PnPsolver::iterate(nIterations, bNoMore, ...) over the tables n_inliers[n_hyp], refined_n[n_hyp] of the solver's hypotheses in
+ * drawing order (N >= min_inliers: :172 is the caller's).  *mnIterations, *mnBestInliers (both start at 0) and *best_hypothesis (the hypothesis of mBestTcw and
+ * mvbBestInliers, -1 until there is one) live across calls.  Returns the hypothesis whose pose iterate returns -- *refined = 1: mRefinedTcw of its refinement (:234),
+ * *refined = 0: its own mBestTcw at exhaustion (:251) --, -1 for cv::Mat(), or -2 where the loop would read hypothesis n_hyp: it stops before consuming it, and the caller
+ * resumes with a longer table and nIterations less the hypotheses this call consumed.  Note :181: a call made at mnIterations >= mRansacMaxIts still runs nIterations
+ * hypotheses, and bNoMore is set only at :239-241.  Host only. */
+int cs_pnp_solver_walk(const int *n_inliers, const int *refined_n, int n_hyp, int ransac_max_its, int min_inliers, int *mnIterations, int *mnBestInliers, int *best_hypothesis,
+                       int nIterations, int *bNoMore, int *refined);
+
 #ifdef __cplusplus
 }
 #endif

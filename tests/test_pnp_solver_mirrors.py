@@ -1,0 +1,263 @@
+"""The two mirrors of ORB_SLAM2::PnPsolver -- cube_slam_amd.pnp_solver.PnPsolver over the library's host path and cubeslam::PnPsolver (cube_slam_amd/host/pnp_solver.hpp) built by
+g++ over csrc/epnp_math.h and csrc/cv_svd_math.h with nothing of the library -- give the same tables bit for bit on every pattern and walk the scripted Relocalization
+round-robin alike, with fixed tables and with quads drawn past the table (-2 from the walk, then resumed).  The C++ program is built a second time with
+-fsanitize=address,undefined and run as a child process over all patterns.  The walk on hand-made tables, best_in carry-over, the C-ABI's symbols and its refusals."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import pnp_solver_patterns as P
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KEYS = ("n_inliers", "Rt", "status", "mask", "refined_n", "refined_Rt", "refined_mask")
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(na, nb) and a[~na].tobytes() == b[~nb].tobytes()
+
+
+def test_symbols_and_declarations():
+    from cube_slam_amd import PnPsolver, _lib  # noqa: F401
+    header = open(os.path.join(ROOT, "include", "cubeslam_hip.h")).read()
+    for sym in ("cs_pnp_solver_evaluate", "cs_pnp_solver_ransac_parameters", "cs_pnp_solver_walk"):
+        assert hasattr(_lib.lib(), sym) and ("int %s(" % sym) in header, sym
+
+
+# ---- the walk
+def _walk_reference(counts, refined_n, max_its, min_inl, script):
+    """iterate() :181-255 written out over the tables; script = the nIterations of successive calls -> the outcome of each."""
+    it, best, bh, out = 0, 0, -1, []
+    for n in script:
+        cur, res = 0, None
+        while it < max_its or cur < n:
+            if it >= len(counts):
+                res = (-2, False, False)
+                break
+            cur += 1; h = it; it += 1
+            if counts[h] >= min_inl:
+                if counts[h] > best:
+                    best, bh = counts[h], h
+                if refined_n[bh] > min_inl:
+                    res = (bh, True, False)
+                    break
+        if res is None:
+            res = ((bh if best >= min_inl else -1), False, True) if it >= max_its else (-1, False, False)
+        out.append(res + (it, best, bh))
+        if res[0] == -2:
+            break
+    return out
+
+
+def _walk_library(counts, refined_n, max_its, min_inl, script):
+    from cube_slam_amd.pnp_solver import walk
+    it, best, bh, out = 0, 0, -1, []
+    for n in script:
+        t, refined, nomore, it, best, bh = walk(counts, refined_n, max_its, min_inl, it, best, bh, n)
+        out.append((t, refined, nomore, it, best, bh))
+        if t == -2:
+            break
+    return out
+
+
+def test_walk_random_tables():
+    rng = np.random.RandomState(7)
+    for _ in range(300):
+        H, max_its, min_inl = rng.randint(1, 60), rng.randint(1, 40), rng.randint(4, 12)
+        counts = rng.randint(0, 20, H).astype(np.int32)
+        refined = np.full(H, -1, np.int32)
+        for h in P.records(counts, min_inl):
+            refined[h] = rng.randint(0, 20)
+        script = list(rng.randint(1, 8, 30))
+        assert _walk_library(counts, refined, max_its, min_inl, script) == _walk_reference(counts, refined, max_its, min_inl, script)
+
+
+def test_walk_named_tables():
+    from cube_slam_amd.pnp_solver import walk
+    m = 10
+    # the first iterate(5) runs to mRansacMaxIts where no refinement succeeds; exhaustion with a best returns it unrefined (:242)
+    counts, refined = np.array([3, 10, 0, 12, 9, 0], np.int32), np.array([-1, 10, -1, 9, -1, -1], np.int32)
+    assert walk(counts, refined, 6, m, 0, 0, -1, 5) == (3, False, True, 6, 12, 3)
+    # nothing qualifies: cv::Mat() and bNoMore; with nIterations = 5 the same call reads hypotheses 3 and 4 (the || of :181)
+    assert walk(np.array([3, 9, 0], np.int32), np.full(3, -1, np.int32), 3, m, 0, 0, -1, 5)[0] == -2
+    assert walk(np.array([3, 9, 0], np.int32), np.full(3, -1, np.int32), 3, m, 0, 0, -1, 3) == (-1, False, True, 3, 0, -1)
+    # a success is repeated by the next qualifying hypothesis although it is no record (Refine() over the unchanged best mask), and a call made at mRansacMaxIts still runs
+    counts, refined = np.array([12, 0, 11, 0, 0, 0, 11, 0], np.int32), np.array([13, -1, -1, -1, -1, -1, -1, -1], np.int32)
+    assert walk(counts, refined, 3, m, 0, 0, -1, 5) == (0, True, False, 1, 12, 0)
+    assert walk(counts, refined, 3, m, 1, 12, 0, 5) == (0, True, False, 3, 12, 0)
+    assert walk(counts, refined, 3, m, 3, 12, 0, 5) == (0, True, False, 7, 12, 0)  # (past mRansacMaxIts = 3: :181)
+    # the next hypothesis lies beyond the table: -2 before consuming it, and the longer table resumes
+    assert walk(counts, refined, 3, m, 7, 12, 0, 5) == (-2, False, False, 8, 12, 0)
+    longer = np.concatenate([counts, np.zeros(6, np.int32)]), np.concatenate([refined, np.full(6, -1, np.int32)])
+    assert walk(longer[0], longer[1], 3, m, 8, 12, 0, 4) == (0, False, True, 12, 12, 0)  # (5 less the one consumed: exhaustion, the unrefined best)
+    # refined_n == mRansacMinInliers is no success (:290 is strict)
+    assert walk(np.array([10, 0], np.int32), np.array([10, -1], np.int32), 2, m, 0, 0, -1, 2) == (0, False, True, 2, 10, 0)
+
+
+def test_ransac_parameters():
+    from cube_slam_amd.pnp_solver import ransac_parameters
+    assert ransac_parameters(*P.RELOC[:5], 20)[:2] == (10, 35) and ransac_parameters(*P.RELOC[:5], 15)[:2] == (10, 14) and ransac_parameters(*P.RELOC[:5], 400)[:2] == (200, 35)
+    assert ransac_parameters(0.99, 4, 300, 4, 0.5, 4)[:2] == (4, 1)
+    for N in list(range(4, 130)) + [400, 5000]:
+        for args in (P.RELOC, (0.99, 8, 300, 4, 0.4, 5.991), (0.99, 50, 300, 4, 0.01, 5.991)):
+            mi, its, eps = ransac_parameters(*args[:5], N)
+            assert (mi, its) == P.parameters(args, N)[:2] and eps == P.parameters(args, N)[2], (N, args)
+
+
+def test_draw_quads():
+    c = P.case("n33")
+    rng = np.random.RandomState(3)
+    s = P.solver("n33")
+    q = s.draw_quads(lambda lo, hi: int(rng.randint(lo, hi + 1)), extra=5)
+    assert q.shape == (c["max_its"] + 5, 4) and np.array_equal(q, P.draw(33, c["max_its"] + 5, 3))
+    from cube_slam_amd._lib import CubeSlamError
+    with pytest.raises(CubeSlamError):  # only minSet == 4 is built
+        s.SetRansacParameters(0.99, 10, 300, 3, 0.5, 5.991)
+    s.SetRansacParameters(*P.RELOC)
+    with pytest.raises(CubeSlamError):  # a live solver without quads
+        s.iterate(5)
+
+
+# ---- tables: best_in carry-over
+@pytest.mark.parametrize("name,cut", [("planted", 20), ("planted", 30), ("n63", 7), ("coincident", 3)])
+def test_split_table_equals_one_piece(name, cut):
+    c, whole = P.case(name), P.judged(name)
+    a = P.evaluate([c], quads=[c["quads"][:cut]])
+    best = max([0] + [int(n) for n in a["n_inliers"] if n >= c["min_inliers"]])
+    b = P.evaluate([c], quads=[c["quads"][cut:]], best_in=[best])
+    for k in KEYS:
+        assert _same(np.concatenate([a[k].reshape((-1, 12) if k.endswith("Rt") else -1), b[k].reshape((-1, 12) if k.endswith("Rt") else -1)]), whole[k]), k
+
+
+# ---- the Python mirror: fixed tables against quads drawn past the table
+def _script(solvers):
+    def iterate(k, n):
+        s = solvers[k]
+        T, nomore, vb, ni = s.iterate(n)
+        return T, nomore, vb, ni, s.mnIterations, s.mnBestInliers
+    return P.run_script(iterate)
+
+
+class _Replay:
+    """RandomInt replaying wanted indices: the position of each in the Fisher-Yates' vAvailableIndices."""
+
+    def __init__(self, N, want):
+        self.N, self.want, self.pos, self.avail = N, [int(v) for v in np.asarray(want).reshape(-1)], 0, []
+
+    def __call__(self, lo, hi):
+        if self.pos % 4 == 0:
+            self.avail = list(range(self.N))
+        at = self.avail.index(self.want[self.pos]); self.pos += 1
+        assert lo == 0 and hi == len(self.avail) - 1
+        self.avail[at] = self.avail[-1]; self.avail.pop()
+        return at
+
+
+def _same_calls(a, b):
+    assert len(a) == len(b)
+    for (ka, x), (kb, y) in zip(a, b):
+        assert ka == kb and (x[0] is None) == (y[0] is None) and x[1] == y[1] and x[3:] == y[3:] and np.array_equal(x[2], y[2]), P.SCRIPT_NAMES[ka]
+        assert x[0] is None or x[0].tobytes() == y[0].tobytes()
+
+
+@pytest.fixture(scope="module")
+def fixed_calls():
+    return _script([P.solver(n) for n in P.SCRIPT_NAMES])
+
+
+def test_python_mirror_resumes_past_the_table(fixed_calls):
+    from cube_slam_amd._lib import CubeSlamError
+    solvers = []
+    for n in P.SCRIPT_NAMES:
+        c = P.case(n)
+        s = P.solver(n)
+        if len(c["quads"]):
+            s.draw_quads(_Replay(len(c["P3Dw"]), c["quads"]), extra=0)  # mRansacMaxIts quads now, five more whenever the walk returns -2
+        solvers.append(s)
+    _same_calls(_script(solvers), fixed_calls)
+    assert any(len(s.quads) > P.case(n)["max_its"] for s, n in zip(solvers, P.SCRIPT_NAMES) if len(P.case(n)["quads"]))
+    short = P.solver("planted")
+    short.set_quads(P.case("planted")["quads"][:P.case("planted")["max_its"]])
+    with pytest.raises(CubeSlamError):  # a fixed table that iterate() runs past
+        for _ in range(12):
+            short.iterate(5)
+
+
+# ---- the C++ mirror, plain and sanitised
+@pytest.fixture(scope="module")
+def exes(tmp_path_factory):
+    d = tmp_path_factory.mktemp("pnp_solver_mirror")
+    src = os.path.join(ROOT, "tests", "cpp", "pnp_solver_mirror.cpp")
+    base = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-DCUBESLAM_PNP_HOST_ONLY", "-I", ROOT, src]
+    subprocess.check_call(base + ["-O2", "-o", str(d / "mirror")])
+    subprocess.check_call(base + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(d / "mirror_san")])
+    return d
+
+
+@pytest.mark.parametrize("exe,mode", [("mirror", "table"), ("mirror", "draw"), ("mirror_san", "table"), ("mirror_san", "draw")])
+def test_cpp_mirror_equals_python_mirror(exes, exe, mode, fixed_calls, tmp_path):
+    ks = [k for k, _ in fixed_calls]
+    (tmp_path / "in.bin").write_bytes(P.driver_input(P.SCRIPT_NAMES, ks))
+    r = subprocess.run([str(exes / exe), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["draw"] if mode == "draw" else []), capture_output=True, timeout=120)
+    assert r.returncode == 0 and r.stderr == b"", r.stderr.decode()
+    out = P.driver_output((tmp_path / "out.bin").read_bytes(), P.SCRIPT_NAMES, ks)
+    for name in P.SCRIPT_NAMES:
+        if not len(P.case(name)["quads"]):
+            continue
+        t, j = out["tables"][name], P.judged(name)
+        H = len(t["n_inliers"])
+        W = (len(P.case(name)["P3Dw"]) + 31) // 32
+        assert H == len(j["n_inliers"]) if mode == "table" else P.case(name)["max_its"] <= H <= len(j["n_inliers"])
+        for k in KEYS:
+            want = j[k].reshape(len(j["n_inliers"]), -1)[:H] if k.endswith("mask") else j[k][:H]
+            assert _same(t[k].reshape(want.shape), want), (name, k)
+        assert W * H == len(t["mask"])
+    _same_calls([(k, o) for k, o in zip(ks, out["script"])], fixed_calls)
+
+
+# ---- the refusals write nothing
+def test_bad_arguments_write_nothing():
+    from cube_slam_amd._lib import CubeSlamError
+    from cube_slam_amd.pnp_solver import solver_evaluate
+    c = P.case("n15")
+    N = len(c["P3Dw"])
+    q = c["quads"][:3].copy()
+    ok = dict(corr_off=[0, N], P3Dw=c["P3Dw"], P2D=c["P2D"], max_err=c["max_err"], K4=c["K"], min_inliers=[10], best_in=[0], hyp_off=[0, 3], quads=q)
+    solver_evaluate(None, **ok)
+    bad = []
+    for i, v in ((0, -1), (1, N), (2, int(q[2, 0]))):  # an index below 0, one at N, one repeated within its quad
+        b = q.copy(); b[2, 1 if i == 2 else 0] = v
+        bad.append(dict(ok, quads=b))
+    bad.append(dict(ok, corr_off=[1, N + 1]))
+    bad.append(dict(ok, hyp_off=[1, 4], quads=np.concatenate([q, q[:1]])))
+    bad.append(dict(ok, corr_off=[0, N, N - 1], hyp_off=[0, 3, 3], K4=np.tile(c["K"], 2), min_inliers=[10, 10], best_in=[0, 0]))                       # decreasing offsets
+    bad.append(dict(ok, corr_off=[0, 3], P3Dw=c["P3Dw"][:3], P2D=c["P2D"][:3], max_err=c["max_err"][:3], quads=np.array([[0, 1, 2, 0]] * 3, np.int32)))  # N_p < 4
+    import cube_slam_amd.pnp_solver as M
+    for kw in bad:
+        with pytest.raises((CubeSlamError, ValueError)):
+            solver_evaluate(None, **kw)
+    # NULL arrays, straight at the C-ABI with sentinel-filled outputs
+    f = M.lib().cs_pnp_solver_evaluate
+    co, ho = np.array([0, N], np.int32), np.array([0, 3], np.int32)
+    ni = np.full(3, -77, np.int32); Rt = np.full(36, -5.5); st = np.full(3, 7, np.uint32); mk = np.full(3, 0xA5A5A5A5, np.uint32)
+    rn = ni.copy(); rRt = Rt.copy(); rmk = mk.copy()
+    p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    mi, bi = np.array([10], np.int32), np.array([0], np.int32)
+    X, U, E, K = (np.ascontiguousarray(c[k], np.float32) for k in ("P3Dw", "P2D", "max_err", "K"))
+    args = [None, 1, p(co, C.c_int), p(X, C.c_float), p(U, C.c_float), p(E, C.c_float), p(K, C.c_float), p(mi, C.c_int), p(bi, C.c_int), p(ho, C.c_int), p(q, C.c_int), p(ni, C.c_int),
+            p(Rt, C.c_double), p(st, C.c_uint32), p(mk, C.c_uint32), p(rn, C.c_int), p(rRt, C.c_double), p(rmk, C.c_uint32)]
+    CS_ERR_BAD_ARG = f(*(args[:3] + [None] + args[4:]))
+    assert CS_ERR_BAD_ARG != 0
+    for i in (2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17):
+        assert f(*(args[:i] + [None] + args[i + 1:])) == CS_ERR_BAD_ARG, i
+    for bq in (np.array([[0, 1, 2, -1]] * 3, np.int32), np.array([[0, 1, 2, N]] * 3, np.int32), np.array([[0, 1, 2, 1]] * 3, np.int32)):
+        assert f(*(args[:10] + [p(bq, C.c_int)] + args[11:])) == CS_ERR_BAD_ARG
+    for a, s in ((ni, -77), (rn, -77), (st, 7), (mk, 0xA5A5A5A5), (rmk, 0xA5A5A5A5)):
+        assert (a == s).all()
+    assert (Rt == -5.5).all() and (rRt == -5.5).all()
+    assert f(*args) == 0 and (ni >= 0).all()  # (and the good call writes)
+    assert f(None, 0, *([None] * 16)) == 0      # n_problems == 0

@@ -1,0 +1,47 @@
+// The comparison side of tools/pnp_solver_bench.py: cubeslam::PnPsolver::evaluate_many without a context -- csrc/epnp_math.h and csrc/cv_svd_math.h on one CPU thread -- on the
+// tool's inputs.
+//   pnp_solver_bench_host <in> <out> <reps> <warmup>      (g++ -O2 -ffp-contract=off -DCUBESLAM_PNP_HOST_ONLY)
+// <in>: int32 n_solvers; per solver int32 N, n_quads, float K[4], P3Dw[3 N], P2D[2 N], sigma2[N], int32 quads[4 n_quads] (SetRansacParameters as Tracking.cc:2921).
+// <out>: per solver n_inliers, refined_n, status, Rt, refined_Rt, mask, refined_mask as the library lays them out.  Prints the milliseconds of every repetition, one line.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <vector>
+
+#include "cube_slam_amd/host/pnp_solver.hpp"
+
+static FILE *in, *out;
+template <class T> static std::vector<T> rd(size_t n) { std::vector<T> v(n); if (n && fread(v.data(), sizeof(T), n, in) != n) { fprintf(stderr, "short input\n"); exit(2); } return v; }
+template <class T> static void wr(const std::vector<T> &v) { if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), out); }
+
+int main(int argc, char **argv) {
+    if (argc < 5 || !(in = fopen(argv[1], "rb")) || !(out = fopen(argv[2], "wb"))) return 2;
+    const int reps = atoi(argv[3]), warmup = atoi(argv[4]);
+    const int n = rd<int>(1)[0];
+    std::vector<std::unique_ptr<cubeslam::PnPsolver>> solvers;
+    std::vector<std::vector<int>> quads;
+    for (int s = 0; s < n; s++) {
+        const std::vector<int> h = rd<int>(2);
+        const std::vector<float> K = rd<float>(4);
+        std::vector<float> X = rd<float>(3 * (size_t)h[0]), U = rd<float>(2 * (size_t)h[0]), S = rd<float>((size_t)h[0]);
+        quads.push_back(rd<int>(4 * (size_t)h[1]));
+        std::vector<int> idx((size_t)h[0]);
+        for (int i = 0; i < h[0]; i++) idx[i] = i;
+        solvers.emplace_back(new cubeslam::PnPsolver(X, U, S, K.data(), idx, h[0], nullptr));
+        solvers.back()->SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991);
+    }
+    std::vector<cubeslam::PnPsolver *> all;
+    for (auto &s : solvers) all.push_back(s.get());
+    for (int r = 0; r < warmup + reps; r++) {
+        for (int s = 0; s < n; s++) solvers[s]->set_quads(quads[s]); // (drops the tables)
+        const auto t0 = std::chrono::steady_clock::now();
+        cubeslam::PnPsolver::evaluate_many(all, nullptr);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (r >= warmup) printf("%s%.6f", r > warmup ? " " : "", ms);
+    }
+    printf("\n");
+    for (auto &s : solvers) { wr(s->n_inliers); wr(s->refined_n); wr(s->status); wr(s->Rt); wr(s->refined_Rt); wr(s->inlier_mask); wr(s->refined_mask); }
+    fclose(out);
+    return 0;
+}

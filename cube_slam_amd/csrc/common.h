@@ -88,19 +88,25 @@ struct cs_ctx {
         if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
         hipEvent_t e; hipEventCreate(&e); return e;
     }
-    void begin(const char *name) {
+    void begin(const char *name) { begin_on(name, stream); }
+    void end() { end_on(stream); }
+    // the same pair around a launch on another stream of this context: both events belong to the stream the launch is on (bg_launch)
+    void begin_on(const char *name, hipStream_t s) {
         if (!timing) return;
         pending_ev p; p.name = name; p.a = get_event(); p.b = get_event();
-        hipEventRecord(p.a, stream);
+        hipEventRecord(p.a, s);
         pending.push_back(p);
     }
-    void end() {
+    void end_on(hipStream_t s) {
         if (!timing) return;
-        hipEventRecord(pending.back().b, stream);
+        hipEventRecord(pending.back().b, s);
     }
     // A second, lowest-priority stream of this context for ONE kind of launch: a kernel that holds its wave slots for ~100 ms and paces itself (the LSD region
-    // walk).  Everything else of the context then runs at the context's own priority beside it, ordered against it by two events.
-    hipStream_t bg_stream = nullptr; hipEvent_t bg_in = nullptr, bg_out = nullptr;
+    // walk), with the few small launches and copies that hand its counts to the host queued behind it.  Everything else of the context runs at the context's own
+    // priority beside it.  bg_begin orders it behind `stream` with an event (a wait of the few short kernels in front of the walk, in the background stream's own
+    // queue); the way back is a wait of the HOST, bg_end: a device-side wait for the walk would sit at the head of `stream`'s hardware queue for the walk's ~100 ms,
+    // and where the runtime has put a second stream onto that queue (more streams of a priority than GPU_MAX_HW_QUEUES) it would hold up that stream's kernels too.
+    hipStream_t bg_stream = nullptr; hipEvent_t bg_in = nullptr;
     // a second stream, at DEFAULT priority, for a branch of a launch chain that reads nothing of the other branch (cs_cuboid_batch_run); created on first use.  At the
     // context's own priority (hipStreamGetPriority of `stream`) config 4's batch measured 64.5 k frames/s against 65.3 k, three alternating runs each, so it stays as it is.
     hipStream_t aux_stream = nullptr;
@@ -109,9 +115,10 @@ struct cs_ctx {
         *s = aux_stream;
         return e;
     }
-    hipError_t drain() { // every stream that work on a handle's blocks may run on (bg_stream's launches are joined into `stream` by bg_end)
-        const hipError_t e = hipStreamSynchronize(stream);
-        return e == hipSuccess && aux_stream ? hipStreamSynchronize(aux_stream) : e;
+    hipError_t drain() { // every stream that work on a handle's blocks may run on (bg_stream: nothing joins it into `stream` on the device, and a call that failed between bg_begin and bg_end has left it running)
+        hipError_t e = hipStreamSynchronize(stream);
+        if (e == hipSuccess && aux_stream) e = hipStreamSynchronize(aux_stream);
+        return e == hipSuccess && bg_stream ? hipStreamSynchronize(bg_stream) : e;
     }
     hipError_t bg_begin() { // work queued on `stream` so far precedes what is queued on bg_stream from here on
         hipError_t e = hipSuccess;
@@ -120,19 +127,17 @@ struct cs_ctx {
             if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) e = hipStreamCreateWithPriority(&bg_stream, hipStreamNonBlocking, lo);
             else e = hipStreamCreateWithFlags(&bg_stream, hipStreamNonBlocking);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&bg_in, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&bg_out, hipEventDisableTiming);
             if (e != hipSuccess) return e;
         }
         e = hipEventRecord(bg_in, stream);
         return e == hipSuccess ? hipStreamWaitEvent(bg_stream, bg_in, 0) : e;
     }
-    hipError_t bg_end() { // ... and `stream` goes on behind it
-        const hipError_t e = hipEventRecord(bg_out, bg_stream);
-        return e == hipSuccess ? hipStreamWaitEvent(stream, bg_out, 0) : e;
-    }
+    // ... and the calling thread waits until bg_stream has run everything queued on it.  Only then may the caller launch, on any stream, what reads the results of
+    // the background launches or reuses their memory: nothing on the device orders `stream` behind bg_stream.
+    hipError_t bg_end() { return hipStreamSynchronize(bg_stream); }
     void flush() {
         if (pending.empty()) return;
-        hipStreamSynchronize(stream);
+        drain(); // (the events of a background launch are bg_stream's)
         for (auto &p : pending) {
             float ms = 0;
             if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { auto &r = timings[p.name]; r.total_ms += ms; r.count++; }
@@ -161,6 +166,13 @@ struct cs_ctx {
         (ctx)->end();                                                                 \
     } while (0)
 #define CS_LAUNCH(ctx, name, kernel, grid, block, shmem, ...) CS_LAUNCH_ON(ctx, (ctx)->stream, name, kernel, grid, block, shmem, __VA_ARGS__)
+// ... and on the context's background stream, between bg_begin and bg_end: timed or not, with its events on that stream
+#define CS_LAUNCH_BG(ctx, name, kernel, grid, block, shmem, ...)                            \
+    do {                                                                                    \
+        (ctx)->begin_on(name, (ctx)->bg_stream);                                            \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->bg_stream, __VA_ARGS__);      \
+        (ctx)->end_on((ctx)->bg_stream);                                                    \
+    } while (0)
 
 // The rule for device blocks: a block is obtained only through cs_dalloc (or a cs_owner, which calls it) and returned only through cs_dfree (or the owner).
 // cs_dalloc may hand out a block of the context's pool, which only cs_dfree knows how to give back; no file but this one and ctx.hip calls hipMalloc / hipFree

@@ -142,7 +142,7 @@ void cs_destroy(cs_ctx *ctx) {
     cs_comm_destroy(ctx);
     for (auto e : ctx->pool) hipEventDestroy(e);
     ctx->pool_drop();
-    if (ctx->bg_stream) { hipStreamSynchronize(ctx->bg_stream); hipStreamDestroy(ctx->bg_stream); hipEventDestroy(ctx->bg_in); hipEventDestroy(ctx->bg_out); }
+    if (ctx->bg_stream) { hipStreamSynchronize(ctx->bg_stream); hipStreamDestroy(ctx->bg_stream); hipEventDestroy(ctx->bg_in); }
     if (ctx->aux_stream) { hipStreamSynchronize(ctx->aux_stream); hipStreamDestroy(ctx->aux_stream); }
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -152,7 +152,7 @@ const char *cs_last_error(const cs_ctx *ctx) { return ctx ? ctx->err.c_str() : "
 
 int cs_sync(cs_ctx *ctx) {
     if (!ctx) return CS_ERR_BAD_ARG;
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CS_HIP(ctx, ctx->drain());
     return CS_OK;
 }
 

@@ -216,13 +216,15 @@ int cs_frontend_create(cs_ctx *ctx, cs_orb *orb, cs_cuboid_batch *batch, int n_l
         fe->workers.push_back(w);
     }
     // the runner keeps 1 + 2 W streams busy (the caller's, every worker's and its background stream for the region walk); the HIP runtime maps streams onto
-    // GPU_MAX_HW_QUEUES hardware queues (4 unless the variable was set before the runtime started) and serialises the streams that share one: say so once, loudly
+    // GPU_MAX_HW_QUEUES hardware queues (4 unless the variable was set before the runtime started), per stream priority, and runs the streams that share one in the
+    // order of their launches: say so once.  What a shared queue costs is the overlap of its streams' short kernels: no stream of the runner waits on the device
+    // for a region walk (the worker's thread does, cs_ctx::bg_end), so no 100 ms barrier sits in front of a neighbour's kernels
     fe->streams = 1 + 2 * n_line_workers;
     { const char *q = getenv("GPU_MAX_HW_QUEUES"); fe->hw_queues = q && atoi(q) > 0 ? atoi(q) : 4; }
     if (fe->hw_queues < fe->streams) {
         static bool said = false;
-        if (!said) { said = true; fprintf(stderr, "[cubeslam-hip] cs_frontend_create: %d streams on %d hardware queues (GPU_MAX_HW_QUEUES%s): streams that share a queue run one after the other -- a 100 ms region walk then "
-                                          "stalls another stream's kernels (up to -25 %% measured).  Export GPU_MAX_HW_QUEUES=16 before the HIP runtime starts (INTEGRATION.md).\n", fe->streams, fe->hw_queues, getenv("GPU_MAX_HW_QUEUES") ? "" : " unset: the runtime's default"); }
+        if (!said) { said = true; fprintf(stderr, "[cubeslam-hip] cs_frontend_create: %d streams on %d hardware queues (GPU_MAX_HW_QUEUES%s): streams that share a queue run their short kernels one after the other.  "
+                                          "No stream waits there for a 100 ms region walk (the line workers' host threads do).  GPU_MAX_HW_QUEUES=16, exported before the HIP runtime starts, gives every stream a queue of its own (INTEGRATION.md).\n", fe->streams, fe->hw_queues, getenv("GPU_MAX_HW_QUEUES") ? "" : " unset: the runtime's default"); }
     }
     if (fe->batch) cs_cuboid_batch_set_shared_gpu(fe->batch, n_line_workers > 0); // alternating runner: the detectors' region walks hold most CUs all the time
     for (LineWorker *w : fe->workers) cs_lsd_set_shared_gpu(w->lsd, n_line_workers > 1);

@@ -845,7 +845,7 @@ extern "C" {
 
 void cs_lsd_destroy(cs_ctx *ctx, cs_lsd *l) {
     if (!l) return;
-    if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
+    if (ctx) { hipSetDevice(ctx->device); ctx->drain(); } // (the background stream too: a region walk of a run that failed behind its launch may still be on it)
     void *ptrs[] = {l->d_gray, l->d_tmp, l->d_mod, l->d_ang, l->d_xofs, l->d_yofs, l->d_ax, l->d_ay, l->d_lblur, l->d_dxy};
     for (void *p : ptrs) cs_dfree(ctx, p);
     lsd_free_lines(ctx, l);

@@ -437,7 +437,8 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
                 void *scratch, size_t scratch_bytes /* memory the caller has no use for while the stage runs: lsd_rg_seq's pixel records go there when it is large enough */,
                 bool pix_ready /* lsd_emit<true> already left the pixel records at the head of `scratch` and the seeds' cos / sin in d_ccs: no fill, no scatter */,
                 bool walk_bg /* lsd_rg_seq on the context's lowest-priority background stream (cs_ctx::bg_begin): the walk paces itself (it takes its ~100 ms whatever runs beside it),
-                                so the context's own stream can have the priority of the short kernels in front of it and behind it */) {
+                                so the context's own stream can have the priority of the short kernels in front of it and behind it.  The calling thread waits for the walk
+                                (cs_ctx::bg_end); the context's stream holds no wait for it */) {
     LsdSeq *r = *handle;
     if (w > 0xffff || h > 0x7fff) return CS_ERR_CAPACITY; // (the region list packs x | y << 16)
     int max_ne = 0;
@@ -487,6 +488,7 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     }
     if (!pix_ready) CS_LAUNCH(ctx, "lsd_rg_scatter", lsd_rg_scatter, dim3((max_ne + 255) / 256, F), dim3(256), 0, S);
     int wpb = std::max(1, std::min(16, waves_per_workgroup)); // waves (= frames) per workgroup
+    RA_(r->h_base.reserve(ctx, (size_t)F + 1)); RA_(r->h_status.reserve(ctx, (size_t)F * 4)); // (in front of the walk: nothing that allocates stands between its launch and the wait for it)
     if (before_seq) before_seq(gate_arg);
     if (grp) {
         const size_t npx = (size_t)w * h, head = (size_t)((w + 8 + 3) & ~3);
@@ -522,19 +524,23 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
 #undef WLK_
         }
     } else if (walk_bg) {
+        // The walk, the scan of its counts and their two copies to the host go to the background stream, and this thread waits for THAT stream: the context's own
+        // stream never waits for the walk on the device (cs_ctx::bg_end says why).  Everything below that reads what the walk wrote -- rectangles, counts, status --
+        // or reuses its map (the LBD blur, lsd.hip) is launched behind this wait.
         CS_HIP(ctx, ctx->bg_begin());
-        cs_ctx::pending_ev pe;
-        if (ctx->timing) { pe.name = "lsd_rg_seq"; pe.a = ctx->get_event(); pe.b = ctx->get_event(); hipEventRecord(pe.a, ctx->bg_stream); }
-        hipLaunchKernelGGL(lsd_rg_seq, dim3((F + wpb - 1) / wpb), dim3(64 * wpb), 0, ctx->bg_stream, S);
-        if (ctx->timing) { hipEventRecord(pe.b, ctx->bg_stream); ctx->pending.push_back(pe); }
+        CS_LAUNCH_BG(ctx, "lsd_rg_seq", lsd_rg_seq, dim3((F + wpb - 1) / wpb), dim3(64 * wpb), 0, S);
+        CS_LAUNCH_BG(ctx, "lsd_rg_cand_scan", lsd_rg_cand_scan, dim3(1), dim3(1024), 0, r->d_cand_cnt, F, r->d_cand_base);
+        CS_HIP(ctx, hipMemcpyAsync(r->h_base.p, r->d_cand_base, ((size_t)F + 1) * sizeof(int), hipMemcpyDeviceToHost, ctx->bg_stream));
+        CS_HIP(ctx, hipMemcpyAsync(r->h_status.p, r->d_status, (size_t)F * 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->bg_stream));
         CS_HIP(ctx, ctx->bg_end());
     } else
     CS_LAUNCH(ctx, "lsd_rg_seq", lsd_rg_seq, dim3((F + wpb - 1) / wpb), dim3(64 * wpb), 0, S);
-    CS_LAUNCH(ctx, "lsd_rg_cand_scan", lsd_rg_cand_scan, dim3(1), dim3(1024), 0, r->d_cand_cnt, F, r->d_cand_base);
-    RA_(r->h_base.reserve(ctx, (size_t)F + 1)); RA_(r->h_status.reserve(ctx, (size_t)F * 4));
-    RA_(cs_d2h(ctx, r->h_base.p, r->d_cand_base, (size_t)F + 1));
-    RA_(cs_d2h(ctx, r->h_status.p, r->d_status, (size_t)F * 4));
-    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (grp || !walk_bg) {
+        CS_LAUNCH(ctx, "lsd_rg_cand_scan", lsd_rg_cand_scan, dim3(1), dim3(1024), 0, r->d_cand_cnt, F, r->d_cand_base);
+        RA_(cs_d2h(ctx, r->h_base.p, r->d_cand_base, (size_t)F + 1));
+        RA_(cs_d2h(ctx, r->h_status.p, r->d_status, (size_t)F * 4));
+        CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     if (after_seq) after_seq(gate_arg);
     long grows = 0, fetches = 0, nreg = 0;
     bool bad = false;

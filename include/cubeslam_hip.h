@@ -611,13 +611,15 @@ int cs_sim3_log(cs_ctx *ctx, int n, const double *sim3, double *log_out);
  * detectors (both holding the same frames) consecutive passes alternate between them, so the host stage of LSD overlaps GPU work.
  * cs_frontend_step returns when ORB and the cuboid batch of this pass are done; cs_frontend_drain waits for the line passes.
  * Streams: the caller's, one per line detector and, for batches whose region stage runs on the device, one lowest-priority background stream per detector for
- * that stage's one long kernel.  The HIP runtime serialises streams that share a hardware queue and creates four by default: export GPU_MAX_HW_QUEUES=16 (or
- * more) before the runtime starts in a process that uses the runner. */
+ * that stage's one long kernel, which the detector's worker thread waits for on the host: no stream waits for it on the device.  The HIP runtime creates four
+ * hardware queues per stream priority by default and runs the streams that share one in launch order, so their short kernels do not overlap: export
+ * GPU_MAX_HW_QUEUES=16 (or more) before the runtime starts in a process that uses the runner. */
 typedef struct cs_frontend cs_frontend;
 int cs_frontend_create(cs_ctx *ctx, cs_orb *orb /* nullable */, cs_cuboid_batch *batch /* nullable */, int n_line_workers, cs_ctx *const *line_ctx,
                        cs_lsd *const *lsd, cs_frontend **out);
 /* 1: the process offers at least as many hardware queues (GPU_MAX_HW_QUEUES as the process saw it at cs_frontend_create, 4 when unset) as the runner keeps streams
- * busy (1 + 2 per line worker); 0: it does not -- cs_frontend_create has said so on stderr -- and streams that share a queue serialise; < 0: error. */
+ * busy (1 + 2 per line worker); 0: it does not -- cs_frontend_create has said so on stderr -- and streams that share a queue run their short kernels one after
+ * the other (none of them is held up for the length of a region walk: the wait for a walk is the worker thread's, not a stream's); < 0: error. */
 int cs_frontend_queues(const cs_frontend *fe, int *streams, int *hw_queues);
 int cs_frontend_step(cs_frontend *fe);
 int cs_frontend_drain(cs_frontend *fe);

@@ -1,29 +1,20 @@
 // pnp_walk.h -- the host-only rules of PnPsolver (orb_object_slam/src/PnPsolver.cc) that need no arithmetic of a hypothesis: SetRansacParameters (:120-151) and the loop and
 // tail of iterate() (:181-255) over the two tables of counts.  One place for cs_pnp_solver_ransac_parameters / cs_pnp_solver_walk (pnpsolver.hip) and for
-// cubeslam::PnPsolver built without the library (host/pnp_solver.hpp).
+// cubeslam::PnPsolver with or without the library (host/pnp_solver.hpp).  The iteration count is ransac_iterations (ransac_batch.h), Sim3Solver's too.
 #pragma once
-#include <math.h>
-
-#include <algorithm>
+#include "ransac_batch.h"
 
 inline void pnp_ransac_parameters(double probability, int minInliers, int maxIterations, int minSet, float epsilon, int N, int *mRansacMinInliers_out, int *mRansacMaxIts_out,
                                   float *mRansacEpsilon_out) {
-    int mRansacMinInliers = minInliers, mRansacMaxIts = maxIterations;
+    int mRansacMinInliers = minInliers;
     float mRansacEpsilon = epsilon;
     int nMinInliers = (int)((float)N * mRansacEpsilon); // int * float: a float product, truncated
     if (nMinInliers < mRansacMinInliers) nMinInliers = mRansacMinInliers;
     if (nMinInliers < minSet) nMinInliers = minSet;
     mRansacMinInliers = nMinInliers;
     if (N > 0 && mRansacEpsilon < (float)mRansacMinInliers / N) mRansacEpsilon = (float)mRansacMinInliers / N; // (N == 0: iterate returns at :172 and nothing reads the values)
-    int nIterations;
-    if (mRansacMinInliers == N) nIterations = 1;
-    else {
-        // (pow(float, int) is the double pow.)  Where the quotient does not fit an int, or is a NaN (epsilon > 1: N < mRansacMinInliers, where :172 returns before the value is
-        // read), the reference's conversion is undefined; the library takes maxIterations, the rule of cs_sim3_solver_max_iterations
-        const double q = ceil(log(1 - probability) / log(1 - pow((double)mRansacEpsilon, 3.0)));
-        nIterations = (q > -2147483648.0 && q < 2147483648.0) ? (int)q : maxIterations;
-    }
-    mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+    // (epsilon > 1 where N < mRansacMinInliers: :172 returns before the value is read)
+    const int mRansacMaxIts = mRansacMinInliers == N ? 1 : ransac_iterations(probability, mRansacEpsilon, maxIterations);
     *mRansacMinInliers_out = mRansacMinInliers; *mRansacMaxIts_out = mRansacMaxIts; *mRansacEpsilon_out = mRansacEpsilon;
 }
 

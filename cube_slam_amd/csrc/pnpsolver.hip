@@ -6,7 +6,8 @@
 //
 //   pnp_hypotheses   one wave (one workgroup) per hypothesis: EPnP on the quad (epnp_compute_pose, epnp_math.h) with its state in LDS -- the 12 x 12 Jacobi spreads a
 //                    rotation's 24 element updates over the lanes, every dot product is summed by each lane over ascending k, the serial statements are lane 0's --, then the
-//                    problem's N correspondences strided over the lanes (epnp_is_inlier): the mask words are the halves of __ballot, the count its popcount
+//                    problem's N correspondences strided over the lanes (epnp_is_inlier): the mask words are the halves of __ballot, the count its popcount (ransac_wave_inliers,
+//                    ransac_batch.h)
 //   pnp_records      one wave per problem: the strict prefix maximum over the counts from best_in[p], by a max-scan over lane shuffles; integers only
 //   pnp_refine       launched over all hypotheses, a non-record leaves at once: the record's inliers are gathered in ascending order (ballot ranks) into its slice of the
 //                    call's scratch, EPnP on them -- the 3 + 6 + 78 + 6 + 9 sums over correspondences one lane per entry over ascending i, alphas, pcs and the
@@ -31,23 +32,7 @@ __device__ int pnp_check_inliers(const PnpProblem &P, const PnpCorr *C, const do
     for (int k = 0; k < 9; k++) R[k] = Rt_lds[k];
 #pragma unroll
     for (int k = 0; k < 3; k++) t[k] = Rt_lds[9 + k];
-    const int N = P.N, W = (N + 31) >> 5;
-    int count = 0;
-    for (int base = 0; base < N; base += 64) { // (wave-uniform trip count: every lane reaches the ballot)
-        const int i = base + lane;
-        bool in = false;
-        if (i < N) {
-            const PnpCorr x = C[i];
-            in = epnp_is_inlier(R, t, P.K, x.X, x.u, x.e);
-        }
-        const unsigned long long bal = __ballot(in);
-        count += __popcll(bal);
-        if (lane == 0) {
-            m[base >> 5] = (uint32_t)bal;
-            if ((base >> 5) + 1 < W) m[(base >> 5) + 1] = (uint32_t)(bal >> 32);
-        }
-    }
-    return count;
+    return ransac_wave_inliers(P.N, lane, [&](int i) { const PnpCorr x = C[i]; return epnp_is_inlier(R, t, P.K, x.X, x.u, x.e); }, m);
 }
 
 __global__ void __launch_bounds__(64) pnp_hypotheses(const int *hyp_problem, const PnpProblem *problems, const PnpCorr *corr, const int *quads, int *n_inliers, double *Rt,
@@ -69,7 +54,7 @@ __global__ void __launch_bounds__(64) pnp_hypotheses(const int *hyp_problem, con
     }
     x.sync();
     epnp_compute_pose(x, &w, pose, pose + 9);
-    const int count = pnp_check_inliers(P, C, pose, lane, mask + P.w0 + (size_t)(h - P.h0) * ((P.N + 31) >> 5));
+    const int count = pnp_check_inliers(P, C, pose, lane, mask + P.w0 + (size_t)(h - P.h0) * ransac_words(P.N));
     if (lane < 12) Rt[12 * (size_t)h + lane] = pose[lane];
     if (lane == 0) { n_inliers[h] = count; status[h] = w.status; }
 }
@@ -105,7 +90,7 @@ __global__ void __launch_bounds__(64) pnp_refine(const int *hyp_problem, const P
     }
     const PnpProblem &P = problems[hyp_problem[h]];
     const PnpCorr *C = corr + P.c0;
-    const int N = P.N, W = (N + 31) >> 5, n = n_inliers[h];
+    const int N = P.N, W = ransac_words(N), n = n_inliers[h];
     const uint32_t *m = mask + P.w0 + (size_t)(h - P.h0) * W;
     double *points = scratch + P.s0 + (size_t)(h - P.h0) * N * PNP_POINT_DOUBLES; // n <= N of them are used
     const PnpWave x{lane};
@@ -114,7 +99,7 @@ __global__ void __launch_bounds__(64) pnp_refine(const int *hyp_problem, const P
     int rank = 0; // Refine :263-279: the inliers in ascending order
     for (int base = 0; base < N; base += 64) {
         const int i = base + lane;
-        const bool in = i < N && ((m[i >> 5] >> (i & 31)) & 1u);
+        const bool in = i < N && ransac_mask_bit(m, i);
         const unsigned long long bal = __ballot(in);
         if (in) {
             const int k = rank + __popcll(bal & ((1ull << lane) - 1ull));
@@ -134,16 +119,6 @@ __global__ void __launch_bounds__(64) pnp_refine(const int *hyp_problem, const P
     }
 }
 
-static int pnp_bad(cs_ctx *ctx, const char *what, long a, long b) {
-    if (!ctx) return CS_ERR_BAD_ARG;
-    char buf[256];
-    if (a >= 0 && b >= 0) snprintf(buf, sizeof buf, "cs_pnp_solver_evaluate: %s (%ld, %ld)", what, a, b);
-    else if (a >= 0) snprintf(buf, sizeof buf, "cs_pnp_solver_evaluate: %s (%ld)", what, a);
-    else snprintf(buf, sizeof buf, "cs_pnp_solver_evaluate: %s", what);
-    ctx->err = buf;
-    return CS_ERR_BAD_ARG;
-}
-
 extern "C" {
 
 int cs_pnp_solver_evaluate(cs_ctx *ctx, int n_problems, const int *corr_off, const float *P3Dw, const float *P2D, const float *max_err, const float *K4, const int *min_inliers,
@@ -155,7 +130,7 @@ int cs_pnp_solver_evaluate(cs_ctx *ctx, int n_problems, const int *corr_off, con
     long words = 0, sdoubles = 0, at[2] = {-1, -1};
     if (const char *what = pnp_build(n_problems, corr_off, P3Dw, P2D, max_err, K4, min_inliers, best_in, hyp_off, quads,
                                      n_inliers && Rt && status && inlier_mask && refined_n && refined_Rt && refined_mask, problems, corr, hyp_problem, &words, &sdoubles, at))
-        return pnp_bad(ctx, what, at[0], at[1]);
+        return ransac_bad(ctx, "cs_pnp_solver_evaluate", what, at[0], at[1]);
     if (n_problems == 0) return CS_OK;
     const int H = hyp_off[n_problems];
     if (H == 0) return CS_OK;

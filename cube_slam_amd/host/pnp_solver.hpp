@@ -7,7 +7,7 @@
 //                                         table (:181 runs past mRansacMaxIts after a success); or set_quads with a table
 // The constructor's filter (:79-101) stays the caller's: the solver is built over its results (INTEGRATION.md 8b'').  Without a context (ctx == nullptr) the tables are
 // evaluated on the host over the text the kernels run (csrc/epnp_math.h, csrc/cv_svd_math.h; compile with -ffp-contract=off), byte-equal to the device: the comparison side of
-// tests and bench.  With CUBESLAM_PNP_HOST_ONLY defined the header needs neither the library nor a context type.
+// tests and bench.  With CUBESLAM_HOST_ONLY defined the header needs neither the library nor a context type.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -17,7 +17,7 @@
 
 #include "../csrc/pnp_host.h"
 #include "../csrc/pnp_walk.h"
-#ifndef CUBESLAM_PNP_HOST_ONLY
+#ifndef CUBESLAM_HOST_ONLY
 #include "../../include/cubeslam_hip.h"
 #include "detect_3d_cuboid.hpp" // cubeslam::Context
 #else
@@ -58,7 +58,7 @@ class PnPsolver {
     void draw_quads(std::function<int(int, int)> RandomInt, int extra = 5) {
         random_int_ = std::move(RandomInt);
         std::vector<int> q;
-        if (live()) draw(mRansacMaxIts + extra, q);
+        if (live()) ransac_draw<4>(N, mRansacMaxIts + extra, random_int_, q);
         set_quads(std::move(q));
     }
 
@@ -90,7 +90,7 @@ class PnPsolver {
         std::vector<double> Rt(12 * (size_t)H), rRt(12 * (size_t)H, 0.0);
         std::vector<uint32_t> st((size_t)H), mask((size_t)words), rmask((size_t)words, 0u);
         if (ctx) {
-#ifndef CUBESLAM_PNP_HOST_ONLY
+#ifndef CUBESLAM_HOST_ONLY
             const int r = cs_pnp_solver_evaluate(ctx->ctx, (int)solvers.size(), corr_off.data(), X.data(), U.data(), E.data(), K.data(), mi.data(), bi.data(), hyp_off.data(), q.data(),
                                                  ni.data(), Rt.data(), st.data(), mask.data(), rn.data(), rRt.data(), rmask.data());
             if (r != CS_OK) throw std::runtime_error("cs_pnp_solver_evaluate failed (" + std::to_string(r) + "): " + cs_last_error(ctx->ctx));
@@ -101,7 +101,7 @@ class PnPsolver {
             pnp_host_evaluate(problems, corr, q.data(), ni.data(), Rt.data(), st.data(), mask.data(), rn.data(), rRt.data(), rmask.data());
         for (size_t p = 0; p < solvers.size(); p++) {
             PnPsolver *s = solvers[p];
-            const long W = (s->N + 31) / 32, w0 = problems[p].w0, nh = hyp_off[p + 1] - hyp_off[p];
+            const long W = ransac_words(s->N), w0 = problems[p].w0, nh = hyp_off[p + 1] - hyp_off[p];
             s->n_inliers.insert(s->n_inliers.end(), ni.begin() + hyp_off[p], ni.begin() + hyp_off[p + 1]);
             s->refined_n.insert(s->refined_n.end(), rn.begin() + hyp_off[p], rn.begin() + hyp_off[p + 1]);
             s->status.insert(s->status.end(), st.begin() + hyp_off[p], st.begin() + hyp_off[p + 1]);
@@ -124,16 +124,15 @@ class PnPsolver {
             if (t != -2) break;
             if (!random_int_) throw std::runtime_error("PnPsolver: iterate() reads past the table of quads (:181 runs past mRansacMaxIts after a success)");
             left -= mnIterations - before;
-            draw(5, quads);
+            ransac_draw<4>(N, 5, random_int_, quads);
         }
         r.bNoMore = nomore != 0;
         if (t < 0) return r;
         r.found = true;
-        const int W = (N + 31) / 32;
-        const uint32_t *m = (refined ? refined_mask.data() : inlier_mask.data()) + (size_t)t * W;
+        const uint32_t *m = (refined ? refined_mask.data() : inlier_mask.data()) + (size_t)t * ransac_words(N);
         const double *p = (refined ? refined_Rt.data() : Rt.data()) + 12 * (size_t)t;
         r.nInliers = refined ? refined_n[t] : n_inliers[t];
-        for (int i = 0; i < N; i++) if (m[i >> 5] >> (i & 31) & 1u) r.vbInliers[mvKeyPointIndices[i]] = true;
+        for (int i = 0; i < N; i++) if (ransac_mask_bit(m, i)) r.vbInliers[mvKeyPointIndices[i]] = true;
         for (int k = 0; k < 16; k++) r.Tcw[k] = (k % 5 == 0) ? 1.f : 0.f; // :216-222 / :292-298
         for (int a = 0; a < 3; a++) {
             for (int b = 0; b < 3; b++) r.Tcw[4 * a + b] = (float)p[3 * a + b];
@@ -161,18 +160,6 @@ class PnPsolver {
     int best_ = -1;
     std::function<int(int, int)> random_int_;
     void clear_tables() { n_inliers.clear(); refined_n.clear(); status.clear(); Rt.clear(); refined_Rt.clear(); inlier_mask.clear(); refined_mask.clear(); }
-    void draw(int count, std::vector<int> &q) { // :187-200
-        for (int it = 0; it < count; it++) {
-            std::vector<int> vAvailableIndices((size_t)N);
-            for (int i = 0; i < N; i++) vAvailableIndices[i] = i;
-            for (short i = 0; i < 4; ++i) {
-                const int randi = random_int_(0, (int)vAvailableIndices.size() - 1);
-                q.push_back(vAvailableIndices[randi]);
-                vAvailableIndices[randi] = vAvailableIndices.back();
-                vAvailableIndices.pop_back();
-            }
-        }
-    }
 };
 
 } // namespace cubeslam

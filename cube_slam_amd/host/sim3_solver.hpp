@@ -1,10 +1,11 @@
 // sim3_solver.hpp -- ORB_SLAM2::Sim3Solver (orb_object_slam/src/Sim3Solver.cc), the RANSAC of LoopClosing::ComputeSim3 (LoopClosing.cc:231-342), with the reference's member
 // names over the C-ABI (include/cubeslam_hip.h) and plain arrays:
 //   cubeslam::Sim3Solver::evaluate_many   the hypotheses of all candidates of one ComputeSim3 in one cs_sim3_solver_hypotheses call
-//   iterate / find                        the reference's sequential rule (:138-205) walked over the table of counts (cs_sim3_solver_walk)
+//   iterate / find                        the reference's sequential rule (:138-205) walked over the table of counts (s3s_walk, what cs_sim3_solver_walk runs)
 //   draw_triples                          the partial Fisher-Yates of :161-175 over a caller's RandomInt(min, max); or set_triples with a table
 // The constructor's filter (:60-101) stays the caller's: the solver is built over its results (INTEGRATION.md 8b').  Without a context (ctx == nullptr) the tables are evaluated
-// on the host over the text the kernel runs (csrc/horn_math.h; compile with -ffp-contract=off), byte-equal to the device: the comparison side of tests and bench.
+// on the host by s3s_host_evaluate (csrc/sim3_host.h, the library's own path without a context; compile with -ffp-contract=off), byte-equal to the device: the comparison side
+// of tests and bench.  With CUBESLAM_HOST_ONLY defined the header needs neither the library nor a context type.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -12,9 +13,13 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/sim3_host.h"
+#ifndef CUBESLAM_HOST_ONLY
 #include "../../include/cubeslam_hip.h"
-#include "../csrc/horn_math.h"
 #include "detect_3d_cuboid.hpp" // cubeslam::Context
+#else
+namespace cubeslam { struct Context; }
+#endif
 
 namespace cubeslam {
 
@@ -37,7 +42,7 @@ class Sim3Solver {
 
     void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
         mRansacProb = probability; mRansacMinInliers = minInliers;
-        mRansacMaxIts = cs_sim3_solver_max_iterations(probability, minInliers, maxIterations, N);
+        mRansacMaxIts = s3s_max_iterations(probability, minInliers, maxIterations, N);
         mnIterations = 0;
         triples.clear(); evaluated_ = false;
     }
@@ -48,16 +53,7 @@ class Sim3Solver {
     }
     void draw_triples(const std::function<int(int, int)> &RandomInt) { // :161-175 for every iteration
         std::vector<int> t;
-        for (int it = 0; it < mRansacMaxIts; it++) {
-            std::vector<int> vAvailableIndices((size_t)N);
-            for (int i = 0; i < N; i++) vAvailableIndices[i] = i;
-            for (short i = 0; i < 3; ++i) {
-                const int randi = RandomInt(0, (int)vAvailableIndices.size() - 1);
-                t.push_back(vAvailableIndices[randi]);
-                vAvailableIndices[randi] = vAvailableIndices.back();
-                vAvailableIndices.pop_back();
-            }
-        }
+        ransac_draw<3>(N, mRansacMaxIts, RandomInt, t);
         set_triples(std::move(t));
     }
 
@@ -66,7 +62,6 @@ class Sim3Solver {
         std::vector<int> corr_off{0}, hyp_off{0}, tri;
         std::vector<float> X1, X2, e1, e2, K;
         std::vector<uint8_t> fix;
-        long words = 0;
         for (const Sim3Solver *s : solvers) {
             if (s->mRansacMaxIts && s->triples.empty()) throw std::runtime_error("Sim3Solver: no triples (set_triples or draw_triples)");
             corr_off.push_back(corr_off.back() + s->N); hyp_off.push_back(hyp_off.back() + s->mRansacMaxIts);
@@ -74,27 +69,35 @@ class Sim3Solver {
             e1.insert(e1.end(), s->mvnMaxError1.begin(), s->mvnMaxError1.end()); e2.insert(e2.end(), s->mvnMaxError2.begin(), s->mvnMaxError2.end());
             K.insert(K.end(), s->K8, s->K8 + 8); fix.push_back(s->mbFixScale);
             tri.insert(tri.end(), s->triples.begin(), s->triples.end());
-            words += (long)s->mRansacMaxIts * ((s->N + 31) / 32);
         }
+        std::vector<S3sProblem> problems;
+        std::vector<S3sCorr> corr;
+        std::vector<int> hyp_problem;
+        long words = 0, at[2];
+        const char *what = s3s_build((int)solvers.size(), corr_off.data(), X1.data(), X2.data(), e1.data(), e2.data(), K.data(), fix.data(), hyp_off.data(), tri.data(), true, problems,
+                                     corr, hyp_problem, &words, at);
+        if (what) throw std::invalid_argument(std::string("Sim3Solver: ") + what);
         const int H = hyp_off.back();
         std::vector<int> ni((size_t)H);
         std::vector<float> sRt(13 * (size_t)H);
         std::vector<uint32_t> mask((size_t)words);
         if (ctx) {
+#ifndef CUBESLAM_HOST_ONLY
             const int r = cs_sim3_solver_hypotheses(ctx->ctx, (int)solvers.size(), corr_off.data(), X1.data(), X2.data(), e1.data(), e2.data(), K.data(), fix.data(), hyp_off.data(),
                                                     tri.data(), ni.data(), sRt.data(), mask.data());
             if (r != CS_OK) throw std::runtime_error("cs_sim3_solver_hypotheses failed (" + std::to_string(r) + "): " + cs_last_error(ctx->ctx));
+#else
+            throw std::runtime_error("Sim3Solver: built without the library");
+#endif
         } else
-            evaluate_host(solvers, ni.data(), sRt.data(), mask.data());
-        long w0 = 0;
+            s3s_host_evaluate(problems, hyp_problem, corr, tri.data(), ni.data(), sRt.data(), mask.data());
         for (size_t p = 0; p < solvers.size(); p++) {
             Sim3Solver *s = solvers[p];
-            const long nw = (long)s->mRansacMaxIts * ((s->N + 31) / 32);
+            const long w0 = problems[p].w0, nw = (long)s->mRansacMaxIts * ransac_words(s->N);
             s->n_inliers.assign(ni.begin() + hyp_off[p], ni.begin() + hyp_off[p + 1]);
             s->sRt.assign(sRt.begin() + 13 * (size_t)hyp_off[p], sRt.begin() + 13 * (size_t)hyp_off[p + 1]);
             s->inlier_mask.assign(mask.begin() + w0, mask.begin() + w0 + nw);
             s->evaluated_ = true;
-            w0 += nw;
         }
     }
 
@@ -104,12 +107,12 @@ class Sim3Solver {
         if (N < mRansacMinInliers) { r.bNoMore = true; return r; } // :144
         if (!evaluated_) evaluate_many({this}, ctx_);
         int nomore = 0;
-        const int t = cs_sim3_solver_walk(n_inliers.data(), mRansacMaxIts, mRansacMinInliers, &mnIterations, &mnBestInliers, &best_, nIterations, &nomore);
+        const int t = s3s_walk(n_inliers.data(), mRansacMaxIts, mRansacMinInliers, &mnIterations, &mnBestInliers, &best_, nIterations, &nomore);
         r.bNoMore = nomore != 0;
         if (t < 0) return r;
         r.found = true; r.nInliers = n_inliers[t];
-        const int W = (N + 31) / 32;
-        for (int i = 0; i < N; i++) if (inlier_mask[(size_t)t * W + (i >> 5)] >> (i & 31) & 1u) r.vbInliers[mvnIndices1[i]] = true;
+        const uint32_t *m = &inlier_mask[(size_t)t * ransac_words(N)];
+        for (int i = 0; i < N; i++) if (ransac_mask_bit(m, i)) r.vbInliers[mvnIndices1[i]] = true;
         const float *h = &sRt[13 * (size_t)t];
         for (int k = 0; k < 16; k++) r.T12[k] = (k % 5 == 0) ? 1.f : 0.f;
         for (int a = 0; a < 3; a++) {
@@ -141,27 +144,6 @@ class Sim3Solver {
     bool evaluated_ = false;
     int best_ = -1;
     int checked_best() const { if (best_ < 0 || !evaluated_) throw std::runtime_error("Sim3Solver: no best hypothesis yet"); return best_; }
-
-    static void evaluate_host(const std::vector<Sim3Solver *> &solvers, int *ni, float *sRt, uint32_t *mask) {
-        for (const Sim3Solver *s : solvers) {
-            const int W = (s->N + 31) / 32;
-            for (int h = 0; h < s->mRansacMaxIts; h++, ni++, sRt += 13, mask += W) {
-                const int *t = &s->triples[3 * (size_t)h];
-                for (int k = 0; k < 3; k++) if (t[k] < 0 || t[k] >= s->N || t[k] == t[(k + 1) % 3]) throw std::invalid_argument("Sim3Solver: a triple outside its solver or with a repeated index");
-                const float *A = s->mvX3Dc1.data(), *B = s->mvX3Dc2.data();
-                HornSim3 H;
-                horn_sim3(A + 3 * t[0], A + 3 * t[1], A + 3 * t[2], B + 3 * t[0], B + 3 * t[1], B + 3 * t[2], s->mbFixScale, &H);
-                for (int w = 0; w < W; w++) mask[w] = 0;
-                int count = 0;
-                for (int i = 0; i < s->N; i++)
-                    if (horn_is_inlier(H, A + 3 * i, B + 3 * i, s->mvnMaxError1[i], s->mvnMaxError2[i], s->K8, nullptr)) { mask[i >> 5] |= 1u << (i & 31); count++; }
-                *ni = count;
-                sRt[0] = H.s;
-                for (int k = 0; k < 9; k++) sRt[1 + k] = H.R[k];
-                for (int k = 0; k < 3; k++) sRt[10 + k] = H.t[k];
-            }
-        }
-    }
 };
 
 } // namespace cubeslam

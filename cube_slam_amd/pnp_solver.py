@@ -8,13 +8,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import CubeSlamError, check, lib
-from .sim3_solver import mask_bits
+from ._ransac import _p, batch, cat, draw, f32, i32, mask_bits, offsets, problem_slices
 
 STATUS_QR_SINGULAR, STATUS_REFINE_QR_SINGULAR, STATUS_RECORD = 1, 2, 4
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 def ransac_parameters(probability, minInliers, maxIterations, minSet, epsilon, N):
@@ -38,20 +34,10 @@ def walk(n_inliers, refined_n, ransac_max_its, min_inliers, mnIterations, mnBest
 def solver_evaluate(ctx, corr_off, P3Dw, P2D, max_err, K4, min_inliers, best_in, hyp_off, quads):
     """cs_pnp_solver_evaluate on flat arrays -> dict of n_inliers[H], Rt[H, 12], status[H], mask (words), refined_n[H], refined_Rt[H, 12], refined_mask (words; layout in
     include/cubeslam_hip.h).  ctx=None: the host evaluation."""
-    co = np.ascontiguousarray(corr_off, np.int32); ho = np.ascontiguousarray(hyp_off, np.int32)
-    n = len(co) - 1
-    if len(ho) != n + 1:
-        raise ValueError("corr_off and hyp_off must have one entry per problem and one more")
-    f32 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1)
-    i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+    co, ho, n, NC, H, words = batch(corr_off, hyp_off)
     x, u, e, k4, mi, bi, q = f32(P3Dw), f32(P2D), f32(max_err), f32(K4), i32(min_inliers), i32(best_in), i32(quads)
-    NC, H = (int(co[-1]), int(ho[-1])) if n else (0, 0)
     if len(x) != 3 * NC or len(u) != 2 * NC or len(e) != NC or len(k4) != 4 * n or len(mi) != n or len(bi) != n or len(q) != 4 * H:
         raise ValueError("array lengths do not fit corr_off / hyp_off")
-    lib().cs_sim3_solver_mask_words.restype = C.c_long
-    words = lib().cs_sim3_solver_mask_words(n, _p(co, C.c_int), _p(ho, C.c_int)) if n else 0
-    if words < 0:
-        words = 0  # (decreasing offsets: the library's to refuse)
     out = {"n_inliers": np.zeros(max(H, 1), np.int32), "Rt": np.zeros((max(H, 1), 12), np.float64), "status": np.zeros(max(H, 1), np.uint32),
            "mask": np.zeros(max(words, 1), np.uint32), "refined_n": np.zeros(max(H, 1), np.int32), "refined_Rt": np.zeros((max(H, 1), 12), np.float64),
            "refined_mask": np.zeros(max(words, 1), np.uint32)}
@@ -112,22 +98,11 @@ class PnPsolver:
             raise ValueError("%d quads for mRansacMaxIts = %d" % (len(q), self.mRansacMaxIts))
         self.quads, self._table = q, None
 
-    def _draw(self, random_int, count):
-        q = np.zeros((count, 4), np.int32)
-        for it in range(count):  # :187-200: the partial Fisher-Yates over DUtils::Random::RandomInt
-            vAvailableIndices = list(range(self.N))
-            for i in range(4):
-                randi = random_int(0, len(vAvailableIndices) - 1)
-                q[it, i] = vAvailableIndices[randi]
-                vAvailableIndices[randi] = vAvailableIndices[-1]
-                vAvailableIndices.pop()
-        return q
-
     def draw_quads(self, random_int, extra=5):
         """mRansacMaxIts + extra quads from random_int, which is kept for those a later iterate() needs."""
         self.random_int = random_int
         n = self.mRansacMaxIts + int(extra) if self.N >= max(self.mRansacMinInliers, 4) else 0
-        self.set_quads(self._draw(random_int, n))
+        self.set_quads(draw(self.N, 4, n, random_int))  # :187-200
         return self.quads
 
     # ---- the tables of all hypotheses
@@ -143,20 +118,12 @@ class PnPsolver:
         todo = [s.quads[d:] if s.N >= max(s.mRansacMinInliers, 4) else s.quads[:0] for s, d in zip(solvers, done)]
         if not any(len(t) for t in todo):
             return
-        co = np.concatenate([[0], np.cumsum([s.N for s in solvers])]).astype(np.int32)
-        ho = np.concatenate([[0], np.cumsum([len(t) for t in todo])]).astype(np.int32)
-        cat = lambda parts, dt, w: np.concatenate([np.asarray(p, dt).reshape(-1, w) for p in parts])
+        ho = offsets(len(t) for t in todo)
         best_in = [0 if s._table is None else int(max([0] + [c for c in s._table["n_inliers"] if c >= s.mRansacMinInliers])) for s in solvers]
-        out = solver_evaluate(ctx, co, cat([s.mvP3Dw for s in solvers], np.float32, 3), cat([s.mvP2D for s in solvers], np.float32, 2),
+        out = solver_evaluate(ctx, offsets(s.N for s in solvers), cat([s.mvP3Dw for s in solvers], np.float32, 3), cat([s.mvP2D for s in solvers], np.float32, 2),
                               cat([s.mvMaxError for s in solvers], np.float32, 1), cat([s.K4 for s in solvers], np.float32, 4), [s.mRansacMinInliers for s in solvers], best_in, ho,
                               cat(todo, np.int32, 4))
-        w0 = 0
-        for p, s in enumerate(solvers):
-            W, nh = (s.N + 31) // 32, len(todo[p])
-            new = {k: out[k][ho[p]:ho[p + 1]].copy() for k in ("n_inliers", "Rt", "status", "refined_n", "refined_Rt")}
-            new["mask"] = out["mask"][w0:w0 + nh * W].reshape(nh, W).copy()
-            new["refined_mask"] = out["refined_mask"][w0:w0 + nh * W].reshape(nh, W).copy()
-            w0 += nh * W
+        for s, new in zip(solvers, problem_slices(out, ho, [s.N for s in solvers], masks=("mask", "refined_mask"))):
             s._table = new if s._table is None else {k: np.concatenate([s._table[k], new[k]]) for k in new}
 
     def table(self):
@@ -183,7 +150,7 @@ class PnPsolver:
             if self.random_int is None:
                 raise CubeSlamError("PnPsolver: iterate() reads hypothesis %d and the table has %d quads (:181 runs past mRansacMaxIts after a success)" % (self.mnIterations, len(self.quads)))
             left -= self.mnIterations - before
-            self.quads = np.concatenate([self.quads, self._draw(self.random_int, 5)])
+            self.quads = np.concatenate([self.quads, draw(self.N, 4, 5, self.random_int)])
         if t < 0:
             return None, nomore, vbInliers, 0
         mask, Rt, n = (T["refined_mask"][t], T["refined_Rt"][t], T["refined_n"][t]) if refined else (T["mask"][t], T["Rt"][t], T["n_inliers"][t])

@@ -8,10 +8,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import CubeSlamError, check, lib
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+from ._ransac import _p, batch, cat, draw, f32, mask_bits, offsets, problem_slices
 
 
 def max_iterations(probability, min_inliers, max_its, N):
@@ -22,20 +19,11 @@ def max_iterations(probability, min_inliers, max_its, N):
 
 def solver_hypotheses(ctx, corr_off, X3Dc1, X3Dc2, max_err1, max_err2, K8, fix_scale, hyp_off, triples, n_inliers=None, sRt=None, mask=None):
     """cs_sim3_solver_hypotheses on flat arrays -> n_inliers[H], sRt[H, 13], inlier_mask (words; layout in include/cubeslam_hip.h).  ctx=None: the host evaluation."""
-    co = np.ascontiguousarray(corr_off, np.int32); ho = np.ascontiguousarray(hyp_off, np.int32)
-    n = len(co) - 1
-    if len(ho) != n + 1:
-        raise ValueError("corr_off and hyp_off must have one entry per problem and one more")
-    f32 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1)
+    co, ho, n, NC, H, words = batch(corr_off, hyp_off)
     x1, x2, e1, e2, k8 = f32(X3Dc1), f32(X3Dc2), f32(max_err1), f32(max_err2), f32(K8)
     fs = np.ascontiguousarray(fix_scale, np.uint8).reshape(-1); tr = np.ascontiguousarray(triples, np.int32).reshape(-1)
-    NC, H = (int(co[-1]), int(ho[-1])) if n else (0, 0)
     if len(x1) != 3 * NC or len(x2) != 3 * NC or len(e1) != NC or len(e2) != NC or len(k8) != 8 * n or len(fs) != n or len(tr) != 3 * H:
         raise ValueError("array lengths do not fit corr_off / hyp_off")
-    lib().cs_sim3_solver_mask_words.restype = C.c_long
-    words = lib().cs_sim3_solver_mask_words(n, _p(co, C.c_int), _p(ho, C.c_int)) if n else 0
-    if words < 0:
-        words = 0  # (decreasing offsets: the library's to refuse)
     ni = np.zeros(max(H, 1), np.int32) if n_inliers is None else n_inliers
     st = np.zeros((max(H, 1), 13), np.float32) if sRt is None else sRt
     mk = np.zeros(max(words, 1), np.uint32) if mask is None else mask
@@ -44,11 +32,6 @@ def solver_hypotheses(ctx, corr_off, X3Dc1, X3Dc2, max_err1, max_err2, K8, fix_s
                                           _p(k8, C.c_float), _p(fs, C.c_uint8), _p(ho, C.c_int), _p(tr, C.c_int), _p(ni, C.c_int), _p(st, C.c_float), _p(mk, C.c_uint32)),
           "cs_sim3_solver_hypotheses")
     return ni[:H], st[:H], mk[:words]
-
-
-def mask_bits(words, N):
-    """mvbInliersi of one hypothesis from its ceil(N / 32) mask words."""
-    return np.unpackbits(np.ascontiguousarray(words, "<u4").view(np.uint8), bitorder="little")[:N].astype(bool)
 
 
 class Sim3Solver:
@@ -92,14 +75,7 @@ class Sim3Solver:
 
     def draw_triples(self, random_int):
         """:161-175 for every iteration: the partial Fisher-Yates over random_int(min, max), DUtils::Random::RandomInt."""
-        t = np.zeros((self.mRansacMaxIts, 3), np.int32)
-        for it in range(self.mRansacMaxIts):
-            vAvailableIndices = list(range(self.N))
-            for i in range(3):
-                randi = random_int(0, len(vAvailableIndices) - 1)
-                t[it, i] = vAvailableIndices[randi]
-                vAvailableIndices[randi] = vAvailableIndices[-1]
-                vAvailableIndices.pop()
+        t = draw(self.N, 3, self.mRansacMaxIts, random_int)
         self.set_triples(t)
         return t
 
@@ -114,18 +90,13 @@ class Sim3Solver:
         for s in solvers:
             if s.mRansacMaxIts and s.triples is None:
                 raise CubeSlamError("Sim3Solver: no triples (set_triples or draw_triples)")
-        co = np.concatenate([[0], np.cumsum([s.N for s in solvers])]).astype(np.int32)
-        ho = np.concatenate([[0], np.cumsum([s.mRansacMaxIts for s in solvers])]).astype(np.int32)
-        cat = lambda parts, dt, w: np.concatenate([np.asarray(p, dt).reshape(-1, w) for p in parts]) if parts else np.zeros((0, w), dt)
-        ni, sRt, mk = solver_hypotheses(ctx, co, cat([s.mvX3Dc1 for s in solvers], np.float32, 3), cat([s.mvX3Dc2 for s in solvers], np.float32, 3),
+        ho = offsets(s.mRansacMaxIts for s in solvers)
+        ni, sRt, mk = solver_hypotheses(ctx, offsets(s.N for s in solvers), cat([s.mvX3Dc1 for s in solvers], np.float32, 3), cat([s.mvX3Dc2 for s in solvers], np.float32, 3),
                                         cat([s.mvnMaxError1 for s in solvers], np.float32, 1), cat([s.mvnMaxError2 for s in solvers], np.float32, 1),
                                         cat([s.K8 for s in solvers], np.float32, 8), [s.mbFixScale for s in solvers], ho,
                                         cat([s.triples for s in solvers if s.mRansacMaxIts], np.int32, 3))
-        w0 = 0
-        for p, s in enumerate(solvers):
-            W, nh = (s.N + 31) // 32, s.mRansacMaxIts
-            s._table = (ni[ho[p]:ho[p + 1]].copy(), sRt[ho[p]:ho[p + 1]].copy(), mk[w0:w0 + nh * W].reshape(nh, W).copy())
-            w0 += nh * W
+        for s, t in zip(solvers, problem_slices({"n": ni, "sRt": sRt, "mask": mk}, ho, [s.N for s in solvers], masks=("mask",))):
+            s._table = (t["n"], t["sRt"], t["mask"])
 
     def table(self):
         if self._table is None:

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: driver of cube_slam_amd/host/pnp_solver.hpp for tests/test_pnp_solver_mirrors.py: cubeslam::PnPsolver without a context, the g++ build of
-// csrc/epnp_math.h and csrc/cv_svd_math.h (built with -DCUBESLAM_PNP_HOST_ONLY it links nothing of the library, and a second time with -fsanitize=address,undefined).
+// csrc/epnp_math.h and csrc/cv_svd_math.h (built with -DCUBESLAM_HOST_ONLY it links nothing of the library, and a second time with -fsanitize=address,undefined).
 //   pnp_solver_mirror <in> <out> [draw]
 // <in>, <out>: the formats of tests/pnp_solver_patterns.py (driver_input, driver_output), those of tests/cpp/ref_pnp_solver_standins.cpp.  `draw`: every solver gets only its
 // first mRansacMaxIts quads as a table and a RandomInt that replays the others, so iterate() draws past the table (-2 from the walk, then resumed); the tables written are

@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE: driver of cube_slam_amd/host/sim3_solver.hpp for tests/test_sim3_solver_host_cpp_gpu.py (on the device) and tests/test_sim3_solver_mirrors.py (`host`:
-// no context, the g++ build of csrc/horn_math.h).
+// no context, the g++ build of csrc/sim3_host.h over csrc/horn_math.h; built with -DCUBESLAM_HOST_ONLY it links nothing of the library and runs `host` only, and a second
+// time with -fsanitize=address,undefined).
 //   sim3_solver_mirror <in> <out> [host]
 // <in>: int32 n_solvers; per solver int32 N, mN1, fix_scale, minInliers, maxIterations, double probability, X3Dc1[3N], X3Dc2[3N], max_err1[N], max_err2[N], K1[4], K2[4],
 // mvnIndices1[N], then int32 3 * mRansacMaxIts as the test expects it and that many triple indices; int32 n_reject and n_reject pairs (solver, hypothesis): the successes the
@@ -23,8 +24,13 @@ template <class T> static void wr(const std::vector<T> &v) { if (!v.empty()) fwr
 int main(int argc, char **argv) {
     if (argc < 3 || !(in = fopen(argv[1], "rb")) || !(out = fopen(argv[2], "wb"))) return 2;
     const bool host = argc > 3 && !strcmp(argv[3], "host");
-    std::unique_ptr<cubeslam::Context> ctx;
-    if (!host) ctx.reset(new cubeslam::Context(0));
+    cubeslam::Context *ctx = nullptr;
+#ifndef CUBESLAM_HOST_ONLY
+    std::unique_ptr<cubeslam::Context> device;
+    if (!host) { device.reset(new cubeslam::Context(0)); ctx = device.get(); }
+#else
+    if (!host) { fprintf(stderr, "built without the library: `host` only\n"); return 2; }
+#endif
     const int n = rd_int();
     std::vector<std::unique_ptr<cubeslam::Sim3Solver>> solvers;
     for (int s = 0; s < n; s++) {
@@ -32,7 +38,7 @@ int main(int argc, char **argv) {
         const double prob = rd<double>(1)[0];
         std::vector<float> X1 = rd<float>(3 * (size_t)N), X2 = rd<float>(3 * (size_t)N), e1 = rd<float>(N), e2 = rd<float>(N), K1 = rd<float>(4), K2 = rd<float>(4);
         std::vector<int> idx1 = rd<int>(N);
-        solvers.emplace_back(new cubeslam::Sim3Solver(X1, X2, e1, e2, K1.data(), K2.data(), idx1, mN1, fix != 0, ctx.get()));
+        solvers.emplace_back(new cubeslam::Sim3Solver(X1, X2, e1, e2, K1.data(), K2.data(), idx1, mN1, fix != 0, ctx));
         solvers.back()->SetRansacParameters(prob, minInliers, maxIterations);
         const int nt = rd_int();
         std::vector<int> tri = rd<int>(nt);
@@ -45,7 +51,7 @@ int main(int argc, char **argv) {
 
     std::vector<cubeslam::Sim3Solver *> all;
     for (auto &s : solvers) all.push_back(s.get());
-    cubeslam::Sim3Solver::evaluate_many(all, ctx.get()); // one call for every candidate
+    cubeslam::Sim3Solver::evaluate_many(all, ctx); // one call for every candidate
     for (auto &s : solvers) { wr(std::vector<int>{s->mRansacMaxIts}); wr(s->n_inliers); wr(s->sRt); wr(s->inlier_mask); }
 
     // LoopClosing::ComputeSim3 :283-342 with iterate(5)

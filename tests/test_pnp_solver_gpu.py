@@ -8,6 +8,11 @@ import os
 
 import numpy as np
 import pytest
+import torch
+
+# torch's copy of the HIP runtime must be the first in the process (the ctx fixture of tests/conftest.py), and importing this module loads libcubeslam_hip.so: P.case below
+# evaluates on the host.  In a run of the whole suite another module has imported torch by then; in a run of this file alone none has.
+torch.cuda.is_available()
 
 from tests import pnp_solver_patterns as P
 
@@ -43,6 +48,22 @@ WITH_QUADS = [n for n in P.ALL if len(P.case(n)["quads"])]
 @pytest.mark.parametrize("name", WITH_QUADS)
 def test_single_equals_host(ctx, name):
     _assert_same(P.evaluate([P.case(name)], ctx=ctx), P.judged(name))
+
+
+SEAM_SEED = 70  # at N = 32 hypothesis 4 and at N = 33 hypothesis 0 reach min_inliers = 16: pnp_refine runs at both sizes
+
+
+@pytest.mark.parametrize("N", [32, 33])
+def test_second_mask_word_seam_equals_host(ctx, N):
+    """One mask word with lane 31 the last (N = 32) and the first N with a second word (N = 33), where the upper ballot half starts to be stored: five quads drawn for the size,
+    min_inliers of the relocalisation parameters, best_in 0; the seven outputs of the device against the host path.  Not a pattern of P.ALL: the golden file has no part in it."""
+    c = P.correspondences(N, SEAM_SEED)
+    c["min_inliers"], c["max_its"], _ = P.parameters(P.RELOC, N)
+    c["max_err"] = c["sigma2"] * np.float32(P.RELOC[5])
+    c["quads"] = P.draw(N, 5, 100 + SEAM_SEED)
+    host = P.evaluate([c], best_in=[0])
+    assert c["min_inliers"] == 16 and (host["refined_n"] >= 0).any() and len(host["mask"]) == 5 * (1 if N == 32 else 2)
+    _assert_same(P.evaluate([c], ctx=ctx, best_in=[0]), host)
 
 
 def test_batch_equals_host(ctx):

@@ -192,7 +192,7 @@ def test_python_mirror_resumes_past_the_table(fixed_calls):
 def exes(tmp_path_factory):
     d = tmp_path_factory.mktemp("pnp_solver_mirror")
     src = os.path.join(ROOT, "tests", "cpp", "pnp_solver_mirror.cpp")
-    base = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-DCUBESLAM_PNP_HOST_ONLY", "-I", ROOT, src]
+    base = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-DCUBESLAM_HOST_ONLY", "-I", ROOT, src]
     subprocess.check_call(base + ["-O2", "-o", str(d / "mirror")])
     subprocess.check_call(base + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(d / "mirror_san")])
     return d

@@ -1,7 +1,9 @@
 """Sim3Solver on the device against the restatement (tests/sim3_solver_restatement.py): cs_sim3_solver_hypotheses on the cases of tests/sim3_solver_patterns.py.  No tolerance
 anywhere: counts and mask words equal entry for entry, the 13 floats of every hypothesis equal as bit patterns, a NaN equal to any NaN (the bit class: x86 and the device give
 NaNs of different sign and payload for 0 / 0).  Every output array is prefilled with a sentinel, so equality also shows that every entry is written; the refusals leave the
-sentinels in place.  The shapes are the smallest at which the kernel can go wrong: N = 20 (the one-iteration branch of SetRansacParameters), 21, 63 / 64 / 65 (the wave seam and
+sentinels in place.  The shapes are the smallest at which the kernel can go wrong: N = 20 (the one-iteration branch of SetRansacParameters), 21, 32 / 33 (one mask word with lane 31 the last, and the first N
+with a second word: the condition under which the upper ballot half is stored; with 5 hypotheses no correspondence is an inlier and the words must be written as zeros, with
+300 the last bit -- 31 and 32 -- is set in dozens of them), 63 / 64 / 65 (the wave seam and
 the seam of the second mask word), 129 (a fifth mask word: the upper ballot half of the last pass is not stored), 200 (several passes per lane); 1, 5 and 300 hypotheses (less
 than one workgroup, a partly filled one, many); 1, 3 and 16 problems of different N and hypothesis counts in one call (the offset seams), one of them without hypotheses."""
 import numpy as np
@@ -40,7 +42,7 @@ def _check(got, judged_list):
     assert np.array_equal(mk, np.concatenate([j["mask"].reshape(-1) for j in judged_list]))
 
 
-@pytest.mark.parametrize("N,H", [(20, 5), (21, 5), (63, 5), (64, 5), (65, 5), (129, 5), (200, 5), (65, 1), (64, 300), (129, 300), (200, 300)])
+@pytest.mark.parametrize("N,H", [(20, 5), (21, 5), (32, 5), (33, 5), (63, 5), (64, 5), (65, 5), (129, 5), (200, 5), (65, 1), (32, 300), (33, 300), (64, 300), (129, 300), (200, 300)])
 def test_one_problem(ctx, N, H):
     _check(_call(ctx, [P.raw_case(N, H, N)]), [P.raw_judged(N, H, N)])
 

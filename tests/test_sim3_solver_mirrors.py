@@ -1,7 +1,8 @@
 """CPU: (1) the two host-only rules of the library -- cs_sim3_solver_walk and cs_sim3_solver_max_iterations -- and draw_triples against the literal Python transcription of
 Sim3Solver::iterate / SetRansacParameters (orb_object_slam/src/Sim3Solver.cc:112-205, tests/sim3_solver_restatement.py) over random tables of counts; (2) the HD text the
-kernel runs (cube_slam_amd/csrc/horn_math.h) compiled by g++ into the C++ mirror's host path (tests/cpp/sim3_solver_mirror.cpp `host`), and by the library's host compiler
-into the Python mirror's (ctx=None), give the restatement's tables bit for bit on every pattern, and both mirrors walk the scripted round-robin alike."""
+kernel runs (cube_slam_amd/csrc/horn_math.h) under the one host statement of a hypothesis (csrc/sim3_host.h), compiled by g++ into the C++ mirror's host path
+(tests/cpp/sim3_solver_mirror.cpp `host`, built with nothing of the library, plain and with -fsanitize=address,undefined) and by the library's host compiler into the Python
+mirror's (ctx=None), give the restatement's tables bit for bit on every pattern, and both mirrors walk the scripted round-robin alike."""
 import ctypes as C
 import os
 import re
@@ -125,24 +126,28 @@ def test_python_host_path_equals_restatement():
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    e = str(tmp_path_factory.mktemp("sim3_solver_mirror") / "sim3_solver_mirror")
-    lib_dir = os.path.join(ROOT, "cube_slam_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", ROOT, os.path.join(ROOT, "tests", "cpp", "sim3_solver_mirror.cpp"), "-o", e, "-L", lib_dir,
-                           "-lcubeslam_hip", "-Wl,-rpath," + lib_dir])
-    return e
+def exes(tmp_path_factory):
+    """The mirror built with nothing of the library, plain and a second time with the sanitizers."""
+    d = tmp_path_factory.mktemp("sim3_solver_mirror")
+    base = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-DCUBESLAM_HOST_ONLY", "-I", ROOT, os.path.join(ROOT, "tests", "cpp", "sim3_solver_mirror.cpp")]
+    subprocess.check_call(base + ["-O2", "-o", str(d / "mirror")])
+    subprocess.check_call(base + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(d / "mirror_san")])
+    return d
 
 
-def test_gpp_build_of_header_equals_restatement(exe, tmp_path):
-    """Every pattern through cubeslam::Sim3Solver without a context: g++'s build of horn_math.h.  The output must be, byte for byte, what the restatement's tables, the Python
-    mirror's round-robin over them and the transcription's draw give (no NaN occurs in these patterns, so bytes can be compared)."""
+def test_gpp_build_of_header_equals_restatement(exes, tmp_path):
+    """Every pattern through cubeslam::Sim3Solver without a context and without the library: g++'s build of sim3_host.h over horn_math.h, plain and sanitised, each run as a
+    child process.  The output must be, byte for byte, what the restatement's tables, the Python mirror's round-robin over them and the transcription's draw give (no NaN
+    occurs in these patterns, so bytes can be compared)."""
     names = P.ALL
     reject = {(names.index(nm), P.first_success(nm)) for nm in ("n21", "n63", "n64_fix", "n65")}
     rng = np.random.RandomState(4)
     c0 = P.solver_case(names[0])
     rnd = [int(rng.randint(0, len(c0["X1"]) - i)) for _ in range(c0["max_its"]) for i in range(3)]
     (tmp_path / "in.bin").write_bytes(P.mirror_input(names, reject, rnd))
-    subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "host"], timeout=60)
+    for exe in ("mirror", "mirror_san"):
+        r = subprocess.run([str(exes / exe), str(tmp_path / "in.bin"), str(tmp_path / (exe + ".bin")), "host"], capture_output=True, timeout=120)
+        assert r.returncode == 0 and r.stderr == b"", (exe, r.stderr.decode())
     tables = [None if not P.solver_case(nm)["max_its"] else (P.judged(nm)["n_inliers"], P.judged(nm)["sRt"], P.judged(nm)["mask"]) for nm in names]
     assert not any(np.isnan(t[1]).any() for t in tables if t is not None)
     log = P.round_robin(_python_mirror(names), reject)
@@ -152,4 +157,6 @@ def test_gpp_build_of_header_equals_restatement(exe, tmp_path):
     s0 = Sim3Solver(c0["X1"], c0["X2"], c0["e1"], c0["e2"], P.K1, P.K2, c0["idx1"], c0["mN1"])
     s0.SetRansacParameters(P.PROB, P.MIN_INLIERS, P.MAX_ITS)
     drawn = s0.draw_triples(lambda lo, hi: next(it))
-    assert (tmp_path / "out.bin").read_bytes() == P.mirror_output(names, tables, log, drawn)
+    want = P.mirror_output(names, tables, log, drawn)
+    for exe in ("mirror", "mirror_san"):
+        assert (tmp_path / (exe + ".bin")).read_bytes() == want, exe

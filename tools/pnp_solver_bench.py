@@ -42,7 +42,7 @@ def main():
     try:
         exe = os.path.join(tmp, "pnp_solver_bench_host")
         if not a.no_cpu:
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DCUBESLAM_PNP_HOST_ONLY", "-I", ROOT, os.path.join(ROOT, "tools", "pnp_solver_bench_host.cpp"), "-o", exe])
+            subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-DCUBESLAM_HOST_ONLY", "-I", ROOT, os.path.join(ROOT, "tools", "pnp_solver_bench_host.cpp"), "-o", exe])
         for N in a.correspondences:
             for nc in a.candidates:
                 cases = []

@@ -1,6 +1,6 @@
 // The comparison side of tools/pnp_solver_bench.py: cubeslam::PnPsolver::evaluate_many without a context -- csrc/epnp_math.h and csrc/cv_svd_math.h on one CPU thread -- on the
 // tool's inputs.
-//   pnp_solver_bench_host <in> <out> <reps> <warmup>      (g++ -O2 -ffp-contract=off -DCUBESLAM_PNP_HOST_ONLY)
+//   pnp_solver_bench_host <in> <out> <reps> <warmup>      (g++ -O2 -ffp-contract=off -DCUBESLAM_HOST_ONLY)
 // <in>: int32 n_solvers; per solver int32 N, n_quads, float K[4], P3Dw[3 N], P2D[2 N], sigma2[N], int32 quads[4 n_quads] (SetRansacParameters as Tracking.cc:2921).
 // <out>: per solver n_inliers, refined_n, status, Rt, refined_Rt, mask, refined_mask as the library lays them out.  Prints the milliseconds of every repetition, one line.
 #include <chrono>

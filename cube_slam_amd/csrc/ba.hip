@@ -1482,6 +1482,7 @@ int cs_ba_create(cs_ctx *ctx, const cs_ba_problem *p, int rank, int world, cs_ba
         std::vector<std::vector<std::pair<int, int>>> cub_edges(Q); // (camera, slot), alive edges only
         for (int o = 0; o < p->n_cobs; o++) { const int pi = cam_idx[p->cobs_cam[o]]; if (pi >= 0) cub_edges[p->cobs_cuboid[o]].push_back(std::make_pair(pi, P + o)); }
         for (auto &e : cub_edges) { std::stable_sort(e.begin(), e.end()); if (!e.empty()) Bc = std::max(Bc, e.back().first - e.front().first); }
+        Bc = std::max(Bc, 1); // one free camera, or free cameras that share nothing: band_back's chunks hold (Bc + 1) / 2 columns, none at Bc = 0; the extra block is explicit zeros
         const char *force = getenv("CUBESLAM_BA_SOLVER"); // "sparse" / "band" / "band1" (band, one workgroup): pick the path (tests run all)
         const int BAND_MAX = 20; // (Bc+2)(Bc+1) blocks of 288 B must fit the 160 KB LDS
         if (force && !strcmp(force, "sparse")) okb = false;

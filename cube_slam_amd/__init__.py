@@ -7,5 +7,6 @@ from . import _lib  # noqa: F401
 from .stereo import ComputeStereoMatches, StereoMatcher  # noqa: F401
 from .bow import KeyFrameDatabase, ORBVocabulary  # noqa: F401
 from .local_mapping import ComputeDistinctiveDescriptors, KeyFrameView, LocalMapping, UpdateNormalAndDepth  # noqa: F401
+from .initializer import Initializer  # noqa: F401
 from .pnp_solver import PnPsolver  # noqa: F401
 from .sim3_solver import Sim3Solver  # noqa: F401

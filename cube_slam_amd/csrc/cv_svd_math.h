@@ -20,6 +20,8 @@
 //   cvx_solve_svd     cvSolve(A, b, x, CV_SVD), A m x n, m >= n (:698, :733, :772)
 //   cvx_invert3_svd   cvInvert(A, Ainv, CV_SVD) 3 x 3 (:422): Ainv[r][c] = sum over i of v_i[r] (u_i[c] (1 / W_i)), same threshold
 //   cvx_gram_entry    one entry of cvMulTransposed(A, dst, 1) = At A: the sum over the rows of A ascending
+// cvx_jacobi_rows and cvx_unit_rows are generic over the storage type (CvxType below): double for the above, float for cv::SVDecomp on CV_32F (initializer_math.h,
+// INTEGRATION.md 8b''').
 #pragma once
 #include <math.h>
 
@@ -41,13 +43,20 @@ constexpr double CVX_EPS = 2.2204460492503131e-15;     // 10 DBL_EPSILON
 constexpr double CVX_MINVAL = 2.2250738585072014e-308; // DBL_MIN
 constexpr double CVX_BK_EPS = 4.4408920985006262e-16;  // 2 DBL_EPSILON
 
-template <class X> HD void cvx_jacobi_rows(X x, double *At, int m, int n, double *W, double *Vt) {
+// The storage type T of At and Vt: OpenCV's JacobiSVDImpl_<_Tp> keeps the elements and the rotation's c and s in _Tp and every sum in double.  For double the casts below
+// are no operation; for float (Initializer.cc, initializer_math.h) an element is rounded to float after each rotation, the skip threshold is 2 FLT_EPSILON (as a float,
+// widened) and a row is a zero row where its norm is <= FLT_MIN.
+template <class T> struct CvxType;
+template <> struct CvxType<double> { static constexpr double eps = CVX_EPS, minval = CVX_MINVAL; };
+template <> struct CvxType<float> { static constexpr double eps = 2.384185791015625e-07 /* 2 FLT_EPSILON = 2^-22 */, minval = 1.1754943508222875e-38 /* FLT_MIN */; };
+
+template <class X, class T> HD void cvx_jacobi_rows(X x, T *At, int m, int n, double *W, T *Vt) {
     if (x.lane == 0)
         CVX_NOUNROLL for (int i = 0; i < n; i++) {
             double sd = 0;
-            CVX_NOUNROLL for (int k = 0; k < m; k++) sd += At[i * m + k] * At[i * m + k];
+            CVX_NOUNROLL for (int k = 0; k < m; k++) sd += (double)At[i * m + k] * At[i * m + k];
             W[i] = sd;
-            CVX_NOUNROLL for (int k = 0; k < n; k++) Vt[i * n + k] = (k == i) ? 1.0 : 0.0;
+            CVX_NOUNROLL for (int k = 0; k < n; k++) Vt[i * n + k] = (k == i) ? (T)1 : (T)0;
         }
     x.sync();
     const int max_iter = m > 30 ? m : 30;
@@ -55,30 +64,30 @@ template <class X> HD void cvx_jacobi_rows(X x, double *At, int m, int n, double
         bool changed = false;
         CVX_NOUNROLL for (int i = 0; i < n - 1; i++)
             CVX_NOUNROLL for (int j = i + 1; j < n; j++) {
-                double *Ai = At + i * m, *Aj = At + j * m;
+                T *Ai = At + i * m, *Aj = At + j * m;
                 double a = W[i], b = W[j], p = 0;
-                CVX_NOUNROLL for (int k = 0; k < m; k++) p += Ai[k] * Aj[k];
-                if (fabs(p) <= CVX_EPS * sqrt(a * b)) continue; // (false for a NaN: the pair is rotated, as in the model)
+                CVX_NOUNROLL for (int k = 0; k < m; k++) p += (double)Ai[k] * Aj[k];
+                if (fabs(p) <= CvxType<T>::eps * sqrt(a * b)) continue; // (false for a NaN: the pair is rotated, as in the model)
                 p *= 2;
                 const double beta = a - b, gamma = sqrt(p * p + beta * beta);
-                double c, s;
+                T c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;
-                    s = sqrt(delta / gamma);
-                    c = p / (gamma * s * 2);
+                    s = (T)sqrt(delta / gamma);
+                    c = (T)(p / (gamma * s * 2));
                 } else {
-                    c = sqrt((gamma + beta) / (gamma * 2));
-                    s = p / (gamma * c * 2);
+                    c = (T)sqrt((gamma + beta) / (gamma * 2));
+                    s = (T)(p / (gamma * c * 2));
                 }
                 x.sync(); // (every lane has read the two rows and W)
                 CVX_NOUNROLL for (int k = x.lane; k < m + n; k += x.lanes) {
-                    double *Pi = k < m ? Ai + k : Vt + i * n + (k - m), *Pj = k < m ? Aj + k : Vt + j * n + (k - m);
-                    const double t0 = c * *Pi + s * *Pj, t1 = -s * *Pi + c * *Pj;
+                    T *Pi = k < m ? Ai + k : Vt + i * n + (k - m), *Pj = k < m ? Aj + k : Vt + j * n + (k - m);
+                    const T t0 = c * *Pi + s * *Pj, t1 = -s * *Pi + c * *Pj;
                     *Pi = t0; *Pj = t1;
                 }
                 x.sync();
                 a = b = 0;
-                CVX_NOUNROLL for (int k = 0; k < m; k++) { a += Ai[k] * Ai[k]; b += Aj[k] * Aj[k]; }
+                CVX_NOUNROLL for (int k = 0; k < m; k++) { a += (double)Ai[k] * Ai[k]; b += (double)Aj[k] * Aj[k]; }
                 if (x.lane == 0) { W[i] = a; W[j] = b; }
                 changed = true;
                 x.sync();
@@ -88,7 +97,7 @@ template <class X> HD void cvx_jacobi_rows(X x, double *At, int m, int n, double
     if (x.lane == 0) {
         CVX_NOUNROLL for (int i = 0; i < n; i++) {
             double sd = 0;
-            CVX_NOUNROLL for (int k = 0; k < m; k++) sd += At[i * m + k] * At[i * m + k];
+            CVX_NOUNROLL for (int k = 0; k < m; k++) sd += (double)At[i * m + k] * At[i * m + k];
             W[i] = sqrt(sd);
         }
         CVX_NOUNROLL for (int i = 0; i < n - 1; i++) {
@@ -97,18 +106,19 @@ template <class X> HD void cvx_jacobi_rows(X x, double *At, int m, int n, double
                 if (W[j] < W[k]) j = k;
             if (i != j) {
                 double t = W[i]; W[i] = W[j]; W[j] = t;
-                CVX_NOUNROLL for (int k = 0; k < m; k++) { t = At[i * m + k]; At[i * m + k] = At[j * m + k]; At[j * m + k] = t; }
-                CVX_NOUNROLL for (int k = 0; k < n; k++) { t = Vt[i * n + k]; Vt[i * n + k] = Vt[j * n + k]; Vt[j * n + k] = t; }
+                CVX_NOUNROLL for (int k = 0; k < m; k++) { const T u = At[i * m + k]; At[i * m + k] = At[j * m + k]; At[j * m + k] = u; }
+                CVX_NOUNROLL for (int k = 0; k < n; k++) { const T u = Vt[i * n + k]; Vt[i * n + k] = Vt[j * n + k]; Vt[j * n + k] = u; }
             }
         }
     }
     x.sync();
 }
 
-template <class X> HD void cvx_unit_rows(X x, double *At, int m, int n, const double *W) {
+template <class X, class T> HD void cvx_unit_rows(X x, T *At, int m, int n, const double *W) {
     if (x.lane == 0)
         CVX_NOUNROLL for (int i = 0; i < n; i++) {
-            const double sd = W[i], s = sd > CVX_MINVAL ? 1 / sd : 0.;
+            const double sd = W[i];
+            const T s = (T)(sd > CvxType<T>::minval ? 1 / sd : 0.);
             CVX_NOUNROLL for (int k = 0; k < m; k++) At[i * m + k] *= s;
         }
     x.sync();

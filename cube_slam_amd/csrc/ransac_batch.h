@@ -1,4 +1,5 @@
-// ransac_batch.h -- what the batched RANSACs of the library share (sim3solver.hip over sim3_host.h, pnpsolver.hip over pnp_host.h, and their mirrors under host/): a CSR batch
+// ransac_batch.h -- what the batched RANSACs of the library share (sim3solver.hip over sim3_host.h, pnpsolver.hip over pnp_host.h, initializer.hip over initializer_host.h, and
+// their mirrors under host/): a CSR batch
 // of problems (corr_off, hyp_off) whose minimal sets of K indices are input, one mask of ceil(N / 32) words per hypothesis, and the rules that need no arithmetic of a
 // hypothesis.  Nothing here knows a solver.  Plain C++ for the g++ builds of the mirrors and the tests; the wave's part and the error text of an entry point under hipcc.
 #pragma once
@@ -27,8 +28,9 @@ template <class Pred> inline void ransac_host_inliers(int N, Pred pred, uint32_t
 }
 
 #if defined(__HIPCC__)
-// pred(i) with the N correspondences strided over the 64 lanes of a wave: the mask words are the two halves of __ballot, the count its popcount, returned to every lane
-template <class Pred> __device__ __forceinline__ int ransac_wave_inliers(int N, int lane, Pred pred, uint32_t *m) {
+// pred(i) with the N correspondences strided over the 64 lanes of a wave: the mask words are the two halves of __ballot, the count its popcount, returned to every lane.
+// after_chunk(base), where given, is called by every lane after the 64 correspondences from base: for what a solver accumulates in their order (Initializer's score)
+template <class Pred, class Chunk> __device__ __forceinline__ int ransac_wave_inliers(int N, int lane, Pred pred, uint32_t *m, Chunk after_chunk) {
     const int W = ransac_words(N);
     int count = 0;
     for (int base = 0; base < N; base += 64) { // (wave-uniform trip count: every lane reaches the ballot)
@@ -41,8 +43,12 @@ template <class Pred> __device__ __forceinline__ int ransac_wave_inliers(int N, 
             m[base >> 5] = (uint32_t)bal;
             if ((base >> 5) + 1 < W) m[(base >> 5) + 1] = (uint32_t)(bal >> 32);
         }
+        after_chunk(base);
     }
     return count;
+}
+template <class Pred> __device__ __forceinline__ int ransac_wave_inliers(int N, int lane, Pred pred, uint32_t *m) {
+    return ransac_wave_inliers(N, lane, pred, m, [](int) {});
 }
 #endif
 
@@ -54,7 +60,7 @@ struct RansacSlot { int c0, N, h0, nh; long w0; };
 // and output arrays are all given; the second is asked for only where there are correspondences, the third and sets only where there are hypotheses.
 template <int K> inline const char *ransac_batch_build(int n_problems, const int *corr_off, const int *hyp_off, const int *sets, bool have_problem_arrays, bool have_corr_arrays,
                                                        bool have_outputs, std::vector<RansacSlot> &slots, std::vector<int> &hyp_problem, long *words_out, long at[2]) {
-    static_assert(K == 3 || K == 4, "triples or quads");
+    static_assert(K == 3 || K == 4 || K == 8, "triples, quads or sets of eight");
     at[0] = at[1] = -1;
     slots.clear(); hyp_problem.clear(); *words_out = 0;
     if (n_problems < 0) return "n_problems < 0";
@@ -70,14 +76,19 @@ template <int K> inline const char *ransac_batch_build(int n_problems, const int
     for (int p = 0; p < n_problems; p++) {
         const int N = corr_off[p + 1] - corr_off[p], nh = hyp_off[p + 1] - hyp_off[p];
         at[0] = p;
-        if (nh && N < K) return K == 3 ? "a problem with hypotheses and fewer than 3 correspondences" : "a problem with hypotheses and fewer than 4 correspondences";
+        if (nh && N < K)
+            return K == 3 ? "a problem with hypotheses and fewer than 3 correspondences"
+                 : K == 4 ? "a problem with hypotheses and fewer than 4 correspondences" : "a problem with hypotheses and fewer than 8 correspondences";
         for (int h = hyp_off[p]; h < hyp_off[p + 1]; h++) {
             const int *s = sets + K * (size_t)h;
             at[1] = h;
             for (int k = 0; k < K; k++) {
-                if (s[k] < 0 || s[k] >= N) return K == 3 ? "a triple index outside its problem (problem, hypothesis)" : "a quad index outside its problem (problem, hypothesis)";
+                if (s[k] < 0 || s[k] >= N) return K == 3 ? "a triple index outside its problem (problem, hypothesis)"
+                         : K == 4 ? "a quad index outside its problem (problem, hypothesis)" : "a set index outside its problem (problem, hypothesis)";
                 for (int l = 0; l < k; l++)
-                    if (s[l] == s[k]) return K == 3 ? "two equal indices in a triple (problem, hypothesis)" : "two equal indices in a quad (problem, hypothesis)";
+                    if (s[l] == s[k])
+                        return K == 3 ? "two equal indices in a triple (problem, hypothesis)"
+                             : K == 4 ? "two equal indices in a quad (problem, hypothesis)" : "two equal indices in a set of eight (problem, hypothesis)";
             }
             hyp_problem[h] = p;
         }

@@ -844,6 +844,41 @@ int cs_pnp_solver_ransac_parameters(double probability, int minInliers, int maxI
 int cs_pnp_solver_walk(const int *n_inliers, const int *refined_n, int n_hyp, int ransac_max_its, int min_inliers, int *mnIterations, int *mnBestInliers, int *best_hypothesis,
                        int nIterations, int *bNoMore, int *refined);
 
+/* ---- Initializer (orb_object_slam/src/Initializer.cc), the two-view initialisation of Tracking::MonocularInitialization (Tracking.cc:948-983): FindHomography (:131-179),
+ * FindFundamental (:181-229), the choice of :113-126 and the CheckRT passes of ReconstructF (:474-501) / ReconstructH (:579-724) for every frame pair of a batch in one call.
+ * Problem p (one Initialize call) has the key points key1_off[p] .. key1_off[p + 1] of the reference frame (keys1: x y of mvKeys1, all of them: Normalize :754-800 runs over
+ * every key point) and key2_off[p] .. of the current frame (mvKeys2), the correspondences corr_off[p] .. corr_off[p + 1] -- matches12[2 i ..] = mvMatches12[i].first, .second,
+ * indices into the problem's key points (:55-64) --, K9[9 p ..] = mK row-major, sigma[p] = mSigma, and the hypotheses hyp_off[p] .. hyp_off[p + 1]; sets[8 h ..] are the eight
+ * indices (into the problem's correspondences) of mvSets[it] (:83-98).  H = hyp_off[n_problems], NC = corr_off[n_problems], W_p = (N_p + 31) / 32.
+ * Per hypothesis and model (0 = homography, 1 = fundamental; model m of hypothesis h is entry m * H + h): score = currentScore, matrix[9 ..] = H21i / F21i row-major, and the
+ * mask of vbCurrentInliers in the word layout of cs_sim3_solver_hypotheses, the masks of model 1 following all of model 0 (cs_sim3_solver_mask_words gives the words of one
+ * model).
+ * Per problem: best[2 p + m] = the hypothesis (counted from hyp_off[p]) that :172 / :222 keep -- the first strict maximum of the scores above 0 --, -1 without one;
+ * S[2 p + m] = SH, SF; RH[p] (:113); model[p] = 0 where RH > 0.40 (:117), else 1, or -1 ("no model") where the chosen model has no hypothesis with a score above 0: there RH is
+ * a NaN and the reference goes on with an empty matrix, which OpenCV refuses.  n_inliers[p] = N of :477-480 / :582-585, the set bits of the chosen mask.  cand_Rt[12 (8 p + c) ..]
+ * = R row-major, t of candidate c, n_cand[p] of them: the four of :498-501 in that order, or vR[i], vt[i] of :626-693, or none where ReconstructH returns at :604; zeros behind
+ * them.  Per candidate, CheckRT (:802-911): nGood[8 p + c], cos_parallax[8 p + c] = vCosParallax[min(50, nGood - 1)] after the sort (0 where nGood == 0; the acos of :905 is
+ * the walk's), good_mask = vbGood per correspondence -- candidate c of problem p owns the W_p words from  8 * sum over q < p of W_q  +  c * W_p  -- and points[3 (8 corr_off[p] +
+ * c N_p + i) ..] = vP3D of correspondence i, zeros where :893 is not reached.  The reference indexes vbGood and vP3D by mvMatches12[i].first; the mirrors scatter.
+ * cv::SVDecomp on CV_32F, Mat::inv, cv::determinant and the order of std::sort are the library's stated definitions (csrc/initializer_math.h, INTEGRATION.md 8b'''); inf and
+ * NaN arise where the reference's statements make them, and nothing is an inlier of a NaN test that the reference writes with >.  Four launches back to back and one read-back.
+ * ctx == NULL evaluates the same text on the host, one thread, with the same checks and byte-equal results: the comparison side of tests and bench, asked for explicitly -- a
+ * call with a context never runs it.
+ * CS_ERR_BAD_ARG (nothing written, nothing launched): NULL arrays, offsets that do not start at 0 or decrease, a match outside the key points of its frame, a set index outside
+ * 0..N_p - 1 or repeated within its set, a problem with hypotheses and N_p < 8.  Which arrays may be NULL: with n_problems > 0 every per-problem and per-candidate output
+ * (model .. cos_parallax, good_mask, points) is required, hypotheses or not -- they are written for a problem without hypotheses too --; score, matrix, inlier_mask and sets only
+ * where the call has hypotheses; keys, matches12 only where there are key points, matches.  n_problems == 0: success whatever the arrays.  A problem without hypotheses: no model. */
+int cs_initializer_evaluate(cs_ctx *ctx, int n_problems, const int *key1_off, const float *keys1, const int *key2_off, const float *keys2, const int *corr_off,
+                            const int *matches12, const float *K9, const float *sigma, const int *hyp_off, const int *sets, float *score, float *matrix, uint32_t *inlier_mask,
+                            int *model, int *best, float *S, float *RH, int *n_inliers, int *n_cand, float *cand_Rt, int *nGood, float *cos_parallax, uint32_t *good_mask,
+                            float *points);
+/* The decisions of ReconstructF :503-576 (model 1, n_cand 4) and ReconstructH :695-736 (model 0, n_cand 8; n_cand 0 is the return of :604) over the candidates' nGood[n_cand]
+ * and cos_parallax[n_cand] of cs_initializer_evaluate and N = n_inliers: nsimilar and nMinGood, or best / second best, with the reference's strict comparisons and the first
+ * among equals; parallax = acos(cos) * 180 / CV_PI as :905 writes it (acosf, a float product, a double quotient).  Initialize passes minParallax = 1.0, minTriangulated = 50
+ * (:116-125).  Returns the candidate whose R21, t21, vP3D and vbTriangulated Initialize hands back, or -1 (false; also for model -1); *parallax (optional) = the parallax the
+ * rule compared.  CS_ERR_BAD_ARG for a NULL table.  Host only. */
+int cs_initializer_walk(int model, int n_cand, const int *nGood, const float *cos_parallax, int N, float minParallax, int minTriangulated, float *parallax);
+
 #ifdef __cplusplus
 }
 #endif

@@ -575,10 +575,13 @@ struct PoseOpt {
     std::vector<double> err;      // n x 3, as left by the last evaluation of each edge
     std::vector<uint8_t> level1;  // edge excluded from the optimisation
     bool robust = true;
+    orc_pose_trace *tr = nullptr; // what the run went through (orc_pose_optimization_trace); counted, never read
+    int round = 0;
     bool stereo(int i) const { return obs[(size_t)i * 3 + 2] >= 0; }
     void eval(int i) { // computeError
         double pc[3];
         se3_map(T, Xw + (size_t)i * 3, pc);
+        if (pc[2] <= 0) tr->nonpositive_depth = 1;
         double *e = &err[(size_t)i * 3];
         if (stereo(i)) { // EdgeStereoSE3ProjectXYZOnlyPose::cam_project (types_six_dof_expmap.cpp:331-338): invz is a float there, bf the edge's double
             const float invz = (float)(1.0 / pc[2]);
@@ -607,6 +610,7 @@ struct PoseOpt {
             if (level1[i]) continue;
             double pc[3], J[18];
             se3_map(T, Xw + (size_t)i * 3, pc);
+            if (pc[2] <= 0) tr->nonpositive_depth = 1;
             const double x = pc[0], y = pc[1], invz = 1.0 / pc[2], invz_2 = invz * invz;
             J[0] = x * y * invz_2 * fx; J[1] = -(1 + (x * x * invz_2)) * fx; J[2] = y * invz * fx; J[3] = -invz * fx; J[4] = 0; J[5] = x * invz_2 * fx;
             J[6] = (1 + y * y * invz_2) * fy; J[7] = -x * y * invz_2 * fy; J[8] = -x * invz * fy; J[9] = 0; J[10] = -invz * fy; J[11] = y * invz_2 * fy;
@@ -642,6 +646,7 @@ struct PoseOpt {
     int optimize(int iterations) { // SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve
         double lambda = 0, ni = 2;
         int nBad = 0, done = 0;
+        tr->exit_kind[round] = ORC_POSE_EXIT_ITERATIONS;
         for (int it = 0; it < iterations; it++) {
             compute_active_errors();
             double currentChi = active_robust_chi2(), tempChi = currentChi;
@@ -668,22 +673,27 @@ struct PoseOpt {
                     alpha = (std::min)(alpha, 2. / 3.);
                     lambda *= (std::max)(1. / 3., alpha);
                     ni = 2; currentChi = tempChi;
-                } else { lambda *= ni; ni *= 2; T = backup; }
+                } else { lambda *= ni; ni *= 2; T = backup; tr->rejected[round]++; if (!ok2) tr->failed_solves[round]++; }
                 qmax++;
+                tr->trials[round]++;
             } while (rho < 0 && qmax < 10);
             done = it + 1;
-            if (qmax == 10 || rho == 0) break;
+            tr->iterations[round] = done;
+            if (qmax == 10 || rho == 0) { tr->exit_kind[round] = qmax == 10 ? ORC_POSE_EXIT_QMAX : ORC_POSE_EXIT_RHO0; break; }
             if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-            if (nBad >= 3) break;
+            if (nBad >= 3) { tr->exit_kind[round] = ORC_POSE_EXIT_NBAD; break; }
         }
         return done;
     }
 };
 } // namespace
 
-extern "C" int orc_pose_optimization(int n, const double *Xw, const double *obs, const double *inv_sigma2, double fx, double fy, double cx, double cy, double bf,
-                                     const double *pose_in, double *pose_out, uint8_t *outlier) {
+extern "C" int orc_pose_optimization_trace(int n, const double *Xw, const double *obs, const double *inv_sigma2, double fx, double fy, double cx, double cy, double bf,
+                                           const double *pose_in, double *pose_out, uint8_t *outlier, orc_pose_trace *trace) {
     PoseOpt P;
+    std::memset(trace, 0, sizeof *trace);
+    trace->min_margin = std::numeric_limits<double>::max();
+    P.tr = trace;
     P.n = n; P.Xw = Xw; P.obs = obs; P.w = inv_sigma2; P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.bf = bf;
     P.err.assign((size_t)n * 3, 0.0); P.level1.assign((size_t)n, 0);
     for (int i = 0; i < n; i++) outlier[i] = 0;
@@ -694,19 +704,33 @@ extern "C" int orc_pose_optimization(int n, const double *Xw, const double *obs,
     int nBad = 0;
     for (int it = 0; it < 4; it++) {
         P.T = T0;
+        P.round = it;
+        trace->rounds = it + 1;
+        for (int i = 0; i < n; i++) trace->active[it] += P.level1[i] ? 0 : 1;
         P.optimize(10);
         nBad = 0;
         for (int i = 0; i < n; i++) {
             if (outlier[i]) P.eval(i);
             const float chi2 = (float)P.chi2(i);
+            const double th = P.stereo(i) ? chi2Stereo : chi2Mono;
+            trace->min_margin = std::min(trace->min_margin, std::fabs((double)chi2 - th) / th);
             if (chi2 > (P.stereo(i) ? chi2Stereo : chi2Mono)) { outlier[i] = 1; P.level1[i] = 1; nBad++; }
             else { outlier[i] = 0; P.level1[i] = 0; }
         }
         if (it == 2) P.robust = false;
         if (n < 10) break;
     }
+    for (int it = 0; it < trace->rounds; it++) {
+        trace->total_iterations += trace->iterations[it]; trace->total_trials += trace->trials[it];
+        trace->total_rejected += trace->rejected[it]; trace->total_failed_solves += trace->failed_solves[it];
+    }
     se3_to7(P.T, pose_out);
     return n - nBad;
+}
+extern "C" int orc_pose_optimization(int n, const double *Xw, const double *obs, const double *inv_sigma2, double fx, double fy, double cx, double cy, double bf,
+                                     const double *pose_in, double *pose_out, uint8_t *outlier) {
+    orc_pose_trace trace;
+    return orc_pose_optimization_trace(n, Xw, obs, inv_sigma2, fx, fy, cx, cy, bf, pose_in, pose_out, outlier, &trace);
 }
 
 // Test hook (tests/test_ref_pins.py): one computeActiveErrors + linearisation of PoseOptimization's graph at pose_in, to be held against the reference's own
@@ -717,6 +741,8 @@ extern "C" void orc_pose_linearize(int n, const double *Xw, const double *obs, c
     P.n = n; P.Xw = Xw; P.obs = obs; P.w = inv_sigma2; P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.bf = bf;
     P.err.assign((size_t)n * 3, 0.0); P.level1.assign((size_t)n, 0);
     P.T = se3_from7(pose_in); P.robust = robust != 0;
+    orc_pose_trace trace = {};
+    P.tr = &trace;
     P.compute_active_errors();
     for (int i = 0; i < n; i++) chi2[i] = P.chi2(i);
     P.build(H, b);

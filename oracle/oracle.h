@@ -264,6 +264,22 @@ int orc_lbd_maps(const uint8_t *gray, int W, int H, uint8_t *blur, int16_t *dx, 
  * pose = [t, qx qy qz qw] of Tcw.  outlier: n flags (mvbOutlier).  Returns nInitialCorrespondences - nBad. */
 int orc_pose_optimization(int n, const double *Xw, const double *obs, const double *inv_sigma2, double fx, double fy, double cx, double cy, double bf,
                           const double *pose_in, double *pose_out, uint8_t *outlier);
+/* What a run went through, per round (the reference's `it` 0..3) and in total: for tests that have to show which paths of the routine an input reaches. */
+enum { ORC_POSE_EXIT_NONE = 0, ORC_POSE_EXIT_QMAX = 1 /* qmax == 10 */, ORC_POSE_EXIT_RHO0 = 2 /* rho == 0 */, ORC_POSE_EXIT_NBAD = 3 /* nBad >= 3 */,
+       ORC_POSE_EXIT_ITERATIONS = 4 /* all 10 iterations */ };
+typedef struct orc_pose_trace {
+    int rounds;                                      /* rounds run: 0 (n < 3), 1 (n < 10) or 4 */
+    int active[4];                                   /* edges in the optimisation when the round starts */
+    int iterations[4], trials[4];                    /* LM iterations done, trials (solves) over them */
+    int rejected[4], failed_solves[4];               /* trials undone, and those among them whose 6 x 6 solve failed */
+    int exit_kind[4];                                /* ORC_POSE_EXIT_* that ended the round's optimize() */
+    int total_iterations, total_trials, total_rejected, total_failed_solves;
+    int nonpositive_depth;                           /* 1 where a point with pc[2] <= 0 was projected or linearised */
+    double min_margin;                               /* smallest |chi2 - th| / th over every classification; DBL_MAX where none was made */
+} orc_pose_trace;
+/* orc_pose_optimization is this with the trace thrown away. */
+int orc_pose_optimization_trace(int n, const double *Xw, const double *obs, const double *inv_sigma2, double fx, double fy, double cx, double cy, double bf,
+                                const double *pose_in, double *pose_out, uint8_t *outlier, orc_pose_trace *trace);
 
 /* ------------------------------------------------------------------ 9-dof g2o::cuboid of object_slam (g2o_Object.h:23-252)
  * cuboid = 10 doubles [t, qx qy qz qw, half scale].  oplus: VertexCuboid::oplusImpl (pose * exp(update[0:6]), scale + update[6:9]);

@@ -589,17 +589,49 @@ def lbd_maps(gray):
     return b, dx, dy
 
 
-def pose_optimization(Xw, obs, inv_sigma2, intr, pose):
-    """Optimizer::PoseOptimization for one frame -> (pose_out[7], outlier[n] u8, n_inliers)."""
+class PoseTrace(C.Structure):
+    _fields_ = [("rounds", C.c_int), ("active", C.c_int * 4), ("iterations", C.c_int * 4), ("trials", C.c_int * 4), ("rejected", C.c_int * 4),
+                ("failed_solves", C.c_int * 4), ("exit_kind", C.c_int * 4), ("total_iterations", C.c_int), ("total_trials", C.c_int),
+                ("total_rejected", C.c_int), ("total_failed_solves", C.c_int), ("nonpositive_depth", C.c_int), ("min_margin", C.c_double)]
+
+
+POSE_EXITS = (None, "qmax", "rho0", "nbad", "iterations")  # ORC_POSE_EXIT_*
+
+
+def _pose_optimization(Xw, obs, inv_sigma2, intr, pose, trace):
     Xw = np.ascontiguousarray(Xw, np.float64).reshape(-1, 3); obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 3)
     w = np.ascontiguousarray(inv_sigma2, np.float64); pose = np.ascontiguousarray(pose, np.float64)
     n = len(Xw)
     out = np.zeros(7); flags = np.zeros(max(n, 1), np.uint8)
     fx, fy, cx, cy, bf = [float(v) for v in intr]
-    lib().orc_pose_optimization.restype = C.c_int
-    r = lib().orc_pose_optimization(n, _p(Xw, C.c_double), _p(obs, C.c_double), _p(w, C.c_double), C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(bf),
-                                    _p(pose, C.c_double), _p(out, C.c_double), _p(flags, C.c_uint8))
+    args = (n, _p(Xw, C.c_double), _p(obs, C.c_double), _p(w, C.c_double), C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(bf),
+            _p(pose, C.c_double), _p(out, C.c_double), _p(flags, C.c_uint8))
+    if trace is None:
+        lib().orc_pose_optimization.restype = C.c_int
+        r = lib().orc_pose_optimization(*args)
+    else:
+        lib().orc_pose_optimization_trace.restype = C.c_int
+        r = lib().orc_pose_optimization_trace(*args, C.byref(trace))
     return out, flags[:n], r
+
+
+def pose_optimization(Xw, obs, inv_sigma2, intr, pose):
+    """Optimizer::PoseOptimization for one frame -> (pose_out[7], outlier[n] u8, n_inliers)."""
+    return _pose_optimization(Xw, obs, inv_sigma2, intr, pose, None)
+
+
+def pose_optimization_trace(Xw, obs, inv_sigma2, intr, pose):
+    """pose_optimization plus what the run went through -> (pose_out[7], outlier[n] u8, n_inliers, trace).  trace: rounds; per round run the lists active, iterations,
+    trials, rejected, failed_solves and exits (one of POSE_EXITS[1:]); the totals iterations_total, trials_total, rejected_total, failed_solves_total;
+    nonpositive_depth (bool); min_margin (inf where nothing was classified)."""
+    t = PoseTrace()
+    out, flags, r = _pose_optimization(Xw, obs, inv_sigma2, intr, pose, t)
+    k = t.rounds
+    trace = {"rounds": k, "active": list(t.active)[:k], "iterations": list(t.iterations)[:k], "trials": list(t.trials)[:k], "rejected": list(t.rejected)[:k],
+             "failed_solves": list(t.failed_solves)[:k], "exits": [POSE_EXITS[e] for e in list(t.exit_kind)[:k]], "iterations_total": t.total_iterations,
+             "trials_total": t.total_trials, "rejected_total": t.total_rejected, "failed_solves_total": t.total_failed_solves,
+             "nonpositive_depth": bool(t.nonpositive_depth), "min_margin": float("inf") if k == 0 else t.min_margin}
+    return out, flags, r, trace
 
 
 def cuboid9_oplus(cub, upd):

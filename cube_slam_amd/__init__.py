@@ -10,3 +10,4 @@ from .local_mapping import ComputeDistinctiveDescriptors, KeyFrameView, LocalMap
 from .initializer import Initializer  # noqa: F401
 from .pnp_solver import PnPsolver  # noqa: F401
 from .sim3_solver import Sim3Solver  # noqa: F401
+from .tracking import Tracking  # noqa: F401

@@ -9,7 +9,8 @@
 //   match_undistort      Frame::UndistortKeyPoints: cv::undistortPoints with P = K, a thread per key point
 //   match_project        per last-frame map point: Rcw*x+tcw (cv::gemm: double accumulate, one rounding), pinhole projection,
 //                        window radius th*scale[octave]; one pose or one pose per pair of a window
-//   match_project_map<M> per map point of a Sim3 / relocalisation search (:309-427, :1010-1139, :1141-1371, :1727-1858) the whole preamble: transform, depth, image, distance and
+//   match_project_map<M> per map point of a Sim3 / relocalisation search (:309-427, :1010-1139, :1141-1371, :1727-1858), of Tracking::SearchLocalPoints (Frame::isInFrustum,
+//                        Frame.cc:346-402) or of Fuse(pKF, vpMapPoints, th) (:871-920) the whole preamble: transform, depth, image, distance and
 //                        viewing-angle tests, MapPoint::PredictScale (glibc's logf restated), radius -- the query and its level window, written where match_candidates reads them
 //   match_candidates     MC_G lanes per query: lane = grid cell of the window (ix outer, iy inner = the reference's candidate
 //                        order), level + |dx|<r,|dy|<r filters, ordered compaction by a prefix sum, 256-bit Hamming
@@ -165,32 +166,45 @@ __global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const 
 // then MapPoint::PredictScale (MapPoint.cc:524-533) L = ceil(logf(mfMaxDistance / dist) / logScaleFactor) with glibc's logf, r = th * mvScaleFactors[L].
 // This fork's PredictScale does not clamp and 0.8 min <= dist <= 1.2 max allows L = -1, n_levels, n_levels + 1, where the reference reads past mvScaleFactors: such a point
 // (and one whose ratio is not a positive normal float) is an invalid query and is counted in *n_outside; the call goes on.
-enum { PM_SIM3 = 0, PM_PAIR = 1, PM_RELOC = 2 };
-struct MapP { float R[9], t[3], Ow[3], R2[9], t2[3]; float fx, fy, cx, cy, log_sf, th; int n_levels; };
+//   PM_FUSE     Fuse(pKF, vpMapPoints, th) :871-920   PM_SIM3's statements and ur = u - bf * invz (:900); the window has no level limits (:922), match_fuse_best applies them
+//   PM_FRUSTUM  Frame::isInFrustum (Frame.cc:346-402) + the radius of SearchByProjection(F, vpMapPoints, th) (:54, :72-78)   Pc = Rcw p + tcw, PcZ < 0, invz = 1.0f / PcZ,
+//             u = fx * PcX * invz + cx (PM_RELOC's association), the Frame's bounds (both ends inclusive), dist = |p - Ow|, viewCos = PO.dot(Pn) / dist (a double division
+//             rounded to float) tested as viewCos < viewingCosLimit, uR = u - bf * invz; r = RadiusByViewingCos (viewCos > 0.998 compared in DOUBLE: float(0.998) > 0.998),
+//             times th only when th != 1.0, times mvScaleFactors[L]; levels [L - 1, L].  PcZ == 0 passes the reference's depth test; where it leaves u or v not finite (0 * inf:
+//             every comparison of the bounds test is false and the reference goes on to undefined float -> int casts) the point is rejected here.
+// The last two modes also leave what the reference keeps per map point in O: valid / in view, (u, v, ur), the viewing cosine (PM_FRUSTUM) -- zeros for a rejected point -- and
+// add the number of valid points to n_outside[1].
+enum { PM_SIM3 = 0, PM_PAIR = 1, PM_RELOC = 2, PM_FUSE = 3, PM_FRUSTUM = 4 };
+struct MapP { float R[9], t[3], Ow[3], R2[9], t2[3]; float fx, fy, cx, cy, log_sf, th; int n_levels; float bf, view_cos_limit; };
+struct MapOut { uint8_t *valid; float *proj, *aux; }; // PM_FRUSTUM: proj = (u, v, uR) per point, aux = the viewing cosine; PM_FUSE: proj = (u, v), aux = ur, as match_fuse_best reads them
 // gemm3 / norm3: cv_math.h
 template <int MODE> __global__ void __launch_bounds__(256) match_project_map(int n, const float *world_pos, const float *normal, const float *min_distance, const float *max_distance, const uint8_t *skip,
-                                                                             MapP P, const float *scale_factors, FrameP F, QueryS *q, int *level, int *n_outside) {
+                                                                             MapP P, const float *scale_factors, FrameP F, QueryS *q, int *level, int *n_outside, MapOut O) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     QueryS Q{0, 0, 0, 0, 0, 0, 0};
     int L = -1;
+    float o_u = 0.0f, o_v = 0.0f, o_ur = 0.0f, o_cos = 0.0f;
     do {
         if (skip[i]) break;
         const float p[3] = {world_pos[(size_t)i * 3], world_pos[(size_t)i * 3 + 1], world_pos[(size_t)i * 3 + 2]};
         float pc[3];
         gemm3(P.R, p, P.t, pc);
         if (MODE == PM_PAIR) { float p2[3]; gemm3(P.R2, pc, P.t2, p2); pc[0] = p2[0]; pc[1] = p2[1]; pc[2] = p2[2]; }
-        float u, v;
-        if (MODE == PM_RELOC) {
+        float u, v, invz = 0.0f;
+        if (MODE == PM_RELOC || MODE == PM_FRUSTUM) {
+            if (MODE == PM_FRUSTUM && pc[2] < 0.0f) break; // Frame.cc:360
             const float xc = pc[0], yc = pc[1];
-            const float invzc = (float)(1.0 / (double)pc[2]);
+            const float invzc = (float)(1.0 / (double)pc[2]); // (1.0f / PcZ of Frame.cc:364 is the same float: a quotient of two floats rounds once either way)
             u = P.fx * xc * invzc + P.cx;
             v = P.fy * yc * invzc + P.cy;
+            if (MODE == PM_FRUSTUM && !(isfinite(u) && isfinite(v))) break;
             if (u < F.minX || u > F.maxX) break;
             if (v < F.minY || v > F.maxY) break;
+            invz = invzc;
         } else {
             if (pc[2] < 0.0f) break;
-            const float invz = (float)(1.0 / (double)pc[2]);
+            invz = (float)(1.0 / (double)pc[2]);
             const float x = pc[0] * invz, y = pc[1] * invz;
             u = P.fx * x + P.cx;
             v = P.fy * y + P.cy;
@@ -201,19 +215,38 @@ template <int MODE> __global__ void __launch_bounds__(256) match_project_map(int
         if (MODE != PM_PAIR) for (int k = 0; k < 3; k++) PO[k] = p[k] - P.Ow[k];
         const float dist = norm3(PO);
         if (dist < minDistance || dist > maxDistance) break;
-        if (MODE == PM_SIM3) { // viewing angle below 60 degrees (:374-377, :1076-1079)
+        float viewCos = 0.0f;
+        if (MODE == PM_SIM3 || MODE == PM_FUSE || MODE == PM_FRUSTUM) { // viewing angle below 60 degrees (:374-377, :914, :1076-1079)
             double dot = 0;
             for (int k = 0; k < 3; k++) dot += (double)PO[k] * (double)normal[(size_t)i * 3 + k];
-            if (dot < 0.5 * (double)dist) break;
+            if (MODE == PM_FRUSTUM) { // Frame.cc:385-388
+                viewCos = (float)(dot / (double)dist);
+                if (viewCos < P.view_cos_limit) break;
+            } else if (dot < 0.5 * (double)dist) break;
         }
         const float ratio = max_distance[i] / dist;
         float lf = -1.0f;
         if (glibc_logf::in_domain(ratio)) lf = ceilf(glibc_logf::logf_(ratio) / P.log_sf);
         if (!(lf >= 0.0f && lf < (float)P.n_levels)) { atomicAdd(n_outside, 1); break; }
         L = (int)lf;
-        Q.x = u; Q.y = v; Q.r = P.th * scale_factors[L]; Q.minLevel = L - 1; Q.maxLevel = MODE == PM_RELOC ? L + 1 : L; Q.valid = 1;
+        float r = P.th;
+        if (MODE == PM_FRUSTUM) { // RadiusByViewingCos (:144-150) and bFactor (:54, :74-75)
+            r = (double)viewCos > 0.998 ? 2.5f : 4.0f;
+            if (P.th != 1.0f) r *= P.th;
+        }
+        Q.x = u; Q.y = v; Q.r = r * scale_factors[L]; Q.valid = 1;
+        if (MODE == PM_FUSE) { Q.minLevel = -1; Q.maxLevel = -1; }
+        else { Q.minLevel = L - 1; Q.maxLevel = MODE == PM_RELOC ? L + 1 : L; }
+        o_u = u; o_v = v; o_ur = u - P.bf * invz; o_cos = viewCos;
     } while (0);
     q[i] = Q; level[i] = L;
+    if (MODE == PM_FUSE || MODE == PM_FRUSTUM) {
+        O.valid[i] = (uint8_t)Q.valid;
+        if (MODE == PM_FRUSTUM) { O.proj[(size_t)i * 3] = o_u; O.proj[(size_t)i * 3 + 1] = o_v; O.proj[(size_t)i * 3 + 2] = o_ur; O.aux[i] = o_cos; }
+        else { O.proj[(size_t)i * 2] = o_u; O.proj[(size_t)i * 2 + 1] = o_v; O.aux[i] = o_ur; }
+        const unsigned long long in = __ballot(Q.valid);
+        if (in && lane_id() == __ffsll((long long)__ballot(1)) - 1) atomicAdd(n_outside + 1, __popcll(in)); // one update per wave, by its first live lane
+    }
 }
 
 __device__ __forceinline__ int hamming256(const unsigned long long *a, unsigned long long b0, unsigned long long b1, unsigned long long b2,
@@ -718,6 +751,7 @@ struct cs_matcher {
     float *d_wp = nullptr /* x 3 */, *d_uv = nullptr /* x 2 */, *d_qur = nullptr, *d_ang = nullptr; uint8_t *d_valid = nullptr, *d_blocks = nullptr;
     float *d_T = nullptr /* 12 */, *d_sf = nullptr /* 32 */, *d_inv = nullptr /* 32 */; // a pose and the per-level tables (n_levels <= 32)
     float *d_nrm = nullptr /* x 3 */, *d_mind = nullptr, *d_maxd = nullptr; int *d_nout = nullptr /* 2 */; // the Sim3 / relocalisation preamble: normals, distance ranges; points outside the scale table, nFound
+    float *d_proj = nullptr /* x 3 */; uint8_t *d_inview = nullptr; // what the frustum / Fuse preamble leaves per map point: (u, v, uR), mbTrackInView (the viewing cosine goes to d_ang)
     int2 *d_cands = nullptr; unsigned long long *d_cursor = nullptr; // [0] the arena's cursor, [1] an error flag (its low word)
     std::vector<int> h_res; int h_nout[2] = {0, 0};
     long last_q = 0, last_c = 0;
@@ -759,6 +793,7 @@ static int mt_alloc(cs_ctx *ctx, cs_matcher *m) {
     CS_TRY(o.alloc(ctx, &m->d_valid, nq)); CS_TRY(o.alloc(ctx, &m->d_blocks, nq));
     CS_TRY(o.alloc(ctx, &m->d_T, (size_t)12)); CS_TRY(o.alloc(ctx, &m->d_sf, (size_t)32)); CS_TRY(o.alloc(ctx, &m->d_inv, (size_t)32));
     CS_TRY(o.alloc(ctx, &m->d_nrm, nq * 3)); CS_TRY(o.alloc(ctx, &m->d_mind, nq)); CS_TRY(o.alloc(ctx, &m->d_maxd, nq)); CS_TRY(o.alloc(ctx, &m->d_nout, (size_t)2));
+    CS_TRY(o.alloc(ctx, &m->d_proj, nq * 3)); CS_TRY(o.alloc(ctx, &m->d_inview, nq));
     CS_TRY(o.alloc(ctx, &m->d_cands, (size_t)m->max_cand)); CS_TRY(o.alloc(ctx, &m->d_cursor, (size_t)2));
     return CS_OK;
 }
@@ -1146,25 +1181,27 @@ int cs_match_for_triangulation(cs_ctx *ctx, const cs_keypoint *keys1Un, const ui
 
 // ---- the searches that project map points through a Sim3 or a relocalisation pose: preamble, window enumeration and the loops, all on the device ----------------------------------
 struct MapIn { int n; const float *world_pos, *normal, *min_distance, *max_distance; const uint8_t *skip, *mp_desc, *train_blocked; };
-static MapP make_mapp(const float *R, const float *t, const float *Ow, const float *R2, const float *t2, float fx, float fy, float cx, float cy, float log_sf, float th, int n_levels) {
+static MapP make_mapp(const float *R, const float *t, const float *Ow, const float *R2, const float *t2, float fx, float fy, float cx, float cy, float log_sf, float th, int n_levels,
+                      float bf = 0.0f, float view_cos_limit = 0.0f) {
     MapP P{};
+    P.bf = bf; P.view_cos_limit = view_cos_limit;
     for (int k = 0; k < 9; k++) { P.R[k] = R[k]; if (R2) P.R2[k] = R2[k]; }
     for (int k = 0; k < 3; k++) { P.t[k] = t[k]; if (Ow) P.Ow[k] = Ow[k]; if (t2) P.t2[k] = t2[k]; }
     P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.log_sf = log_sf; P.th = th; P.n_levels = n_levels;
     return P;
 }
 // uploads the map points, runs the preamble into m's query arrays (points outside the scale table add to *d_nout) and enumerates the windows in m's frame; nothing waits
-template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, int *d_nout) {
+template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, int *d_nout, const MapOut &O = MapOut{nullptr, nullptr, nullptr}) {
     const int n = I.n, N = m->F.N;
     CS_TRY(cs_h2d(ctx, m->d_wp, I.world_pos, (size_t)n * 3));
-    if (MODE == PM_SIM3) CS_TRY(cs_h2d(ctx, m->d_nrm, I.normal, (size_t)n * 3));
+    if (MODE == PM_SIM3 || MODE == PM_FUSE || MODE == PM_FRUSTUM) CS_TRY(cs_h2d(ctx, m->d_nrm, I.normal, (size_t)n * 3));
     CS_TRY(cs_h2d(ctx, m->d_mind, I.min_distance, (size_t)n));
     CS_TRY(cs_h2d(ctx, m->d_maxd, I.max_distance, (size_t)n));
     CS_TRY(cs_h2d(ctx, m->d_valid, I.skip, (size_t)n));
     CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, I.mp_desc, (size_t)n * 32));
     CS_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)P.n_levels));
     if (I.train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, I.train_blocked, (size_t)N));
-    CS_LAUNCH(ctx, "match_project_map", match_project_map<MODE>, dim3((n + 255) / 256), dim3(256), 0, n, m->d_wp, m->d_nrm, m->d_mind, m->d_maxd, m->d_valid, P, m->d_sf, m->F, m->d_q, m->d_level, d_nout);
+    CS_LAUNCH(ctx, "match_project_map", match_project_map<MODE>, dim3((n + 255) / 256), dim3(256), 0, n, m->d_wp, m->d_nrm, m->d_mind, m->d_maxd, m->d_valid, P, m->d_sf, m->F, m->d_q, m->d_level, d_nout, O);
     return mt_candidates(ctx, m, n, true);
 }
 static bool map_in_ok(const cs_matcher *m, const MapIn &I, bool need_normal) {
@@ -1235,6 +1272,73 @@ int cs_match_fuse_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float
     CS_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c));
     int nf = 0;
     for (int i = 0; i < n_mp; i++) if (best_dist[i] <= TH_LOW) nf++; // :1121
+    *n_fused = nf;
+    if (n_level_outside) *n_level_outside = nout[0];
+    return CS_OK;
+}
+
+int cs_match_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
+                               const float *max_distance, const uint8_t *skip, const uint8_t *blocks, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx, float cy,
+                               float bf, float log_scale_factor, const float *scale_factors, int n_levels, float viewing_cos_limit, float th, float nnratio, int *train_match, int *nmatches,
+                               int *n_to_match, int *n_level_outside, uint8_t *in_view, float *proj, int *pred_level, float *view_cos) {
+    if (!ctx || !m) return CS_ERR_BAD_ARG;
+    const MapIn I{n_mp, world_pos, normal, min_distance, max_distance, skip, mp_desc, train_blocked};
+    if (!Rcw || !tcw || !Ow || !map_in_ok(m, I, true) || (n_mp && (!blocks || !in_view)) || !scale_factors || n_levels < 1 || n_levels > 32 || !train_match || !nmatches || !n_to_match)
+        return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    const int N = m->F.N;
+    *nmatches = 0; *n_to_match = 0;
+    if (n_level_outside) *n_level_outside = 0;
+    if (n_mp == 0) { for (int i = 0; i < N; i++) train_match[i] = -1; return CS_OK; }
+    CS_HIP(ctx, hipMemsetAsync(m->d_nout, 0, 2 * sizeof(int), ctx->stream));
+    CS_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_mp));
+    // Tracking::SearchLocalPoints :2699-2715 (isInFrustum per point) and the window of ORBmatcher.cc:72-78, written where match_candidates reads it
+    CS_TRY(mt_map_queries<PM_FRUSTUM>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels, bf, viewing_cos_limit), scale_factors, m->d_nout,
+                                      MapOut{m->d_inview, m->d_proj, m->d_ang}));
+    // (:2717: without a point in view the reference does not call the search; here no query is valid then and the search leaves train_match at -1 -- the same result without a
+    //  second wait for the count)
+    ResolveP P{}; // :86-140, as cs_match_local_map
+    P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_mp; P.n_train = N; P.tkeys = m->d_keys; P.blocks = m->d_blocks;
+    P.tblocked = train_blocked ? m->d_tb : nullptr; P.nnratio = nnratio; P.check_orientation = 0; P.train_match = m->d_tm; P.q_rec = m->d_qrec; P.nmatches = m->d_tm + N;
+    CS_TRY(mt_resolve<RV_LOCAL>(ctx, P, 1, N));
+    int *nout = m->h_nout;
+    CS_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
+    CS_TRY(cs_d2h(ctx, in_view, m->d_inview, (size_t)n_mp));
+    if (proj) CS_TRY(cs_d2h(ctx, proj, m->d_proj, (size_t)n_mp * 3));
+    if (pred_level) CS_TRY(cs_d2h(ctx, pred_level, m->d_level, (size_t)n_mp));
+    if (view_cos) CS_TRY(cs_d2h(ctx, view_cos, m->d_ang, (size_t)n_mp));
+    CS_TRY(mt_finish(ctx, m, m->d_tm, N, train_match, nmatches));
+    *n_to_match = nout[1];
+    if (n_level_outside) *n_level_outside = nout[0];
+    return CS_OK;
+}
+
+int cs_match_fuse_map(cs_ctx *ctx, cs_matcher *m, const float *u_right, const float *inv_level_sigma2, int n_levels, const uint8_t *keys_static, const float *Rcw, const float *tcw, const float *Ow,
+                      int n_mp, const float *world_pos, const float *normal, const float *min_distance, const float *max_distance, const uint8_t *skip, const uint8_t *mp_desc, float fx, float fy,
+                      float cx, float cy, float bf, float log_scale_factor, const float *scale_factors, float th, int *best_idx, int *best_dist, int *n_fused, int *n_level_outside) {
+    if (!ctx || !m) return CS_ERR_BAD_ARG;
+    const MapIn I{n_mp, world_pos, normal, min_distance, max_distance, skip, mp_desc, nullptr};
+    if (!Rcw || !tcw || !Ow || !map_in_ok(m, I, true) || !u_right || !inv_level_sigma2 || !scale_factors || n_levels < 1 || n_levels > 32 || !best_idx || !best_dist || !n_fused) return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    *n_fused = 0;
+    if (n_level_outside) *n_level_outside = 0;
+    if (n_mp == 0) return CS_OK;
+    const int N = m->F.N;
+    CS_HIP(ctx, hipMemsetAsync(m->d_nout, 0, 2 * sizeof(int), ctx->stream));
+    CS_TRY(cs_h2d(ctx, m->d_inv, inv_level_sigma2, (size_t)n_levels));
+    CS_TRY(cs_h2d(ctx, m->d_ur, u_right, (size_t)N));
+    if (keys_static) CS_TRY(cs_h2d(ctx, m->d_tb, keys_static, (size_t)N));
+    CS_TRY(mt_map_queries<PM_FUSE>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels, bf), scale_factors, m->d_nout,
+                                   MapOut{m->d_inview, m->d_uv, m->d_qur})); // :871-922
+    CS_LAUNCH(ctx, "match_fuse_best", match_fuse_best, dim3((n_mp + 255) / 256), dim3(256), 0, n_mp, m->d_cstart, m->d_ccount, m->d_cands, m->d_keys, m->d_ur, m->d_inv, n_levels,
+              keys_static ? m->d_tb : (const uint8_t *)nullptr, m->d_uv, m->d_qur, m->d_level, m->d_inview, m->d_qm, m->d_qrec, reinterpret_cast<int *>(m->d_cursor + 1)); // :934-981
+    int *nout = m->h_nout;
+    CS_TRY(cs_d2h(ctx, nout, m->d_nout, 2));
+    CS_TRY(cs_d2h(ctx, best_idx, m->d_qm, (size_t)n_mp));
+    CS_TRY(cs_d2h(ctx, best_dist, m->d_qrec, (size_t)n_mp));
+    CS_TRY(mt_cursor(ctx, m->d_cursor, m->max_cand, &m->last_c)); // (BAD_ARG: a candidate's level outside the sigma table)
+    int nf = 0;
+    for (int i = 0; i < n_mp; i++) if (best_dist[i] <= TH_LOW) nf++;
     *n_fused = nf;
     if (n_level_outside) *n_level_outside = nout[0];
     return CS_OK;

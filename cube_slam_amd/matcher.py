@@ -155,6 +155,42 @@ class ORBmatcher:
                                                      C.c_float(th), _p(bi, C.c_int), _p(bd, C.c_int), C.byref(n), C.byref(no)), "cs_match_fuse_sim3")
         return bi[:len(sk)].copy(), bd[:len(sk)].copy(), n.value, no.value
 
+    def SearchLocalPoints(self, Rcw, tcw, Ow, world_pos, normal, min_distance, max_distance, skip, blocks, mp_desc, fx, fy, cx, cy, bf, log_scale_factor, scale_factors, th,
+                          viewing_cos_limit=0.5, train_blocked=None):
+        """Tracking::SearchLocalPoints (Tracking.cc:2696-2727): Frame::isInFrustum per local map point and ORBmatcher::SearchByProjection(F, vpMapPoints, th) against the current
+        frame given to set_frame, in one call.  Returns a dict: train_match per key point (index of the local point or -1), nmatches, n_to_match, outside (points dropped because
+        their predicted level is outside the scale table) and, per local point, in_view, proj (u, v, uR), pred_level, view_cos."""
+        wp, mn, mx, sk, md, nr = self._map_points(world_pos, min_distance, max_distance, skip, mp_desc, normal)
+        R, t, O = self._f(Rcw, 9), self._f(tcw, 3), self._f(Ow, 3); sf = np.ascontiguousarray(scale_factors, np.float32); bl = np.ascontiguousarray(blocks, np.uint8)
+        tb = None if train_blocked is None else np.ascontiguousarray(train_blocked, np.uint8)
+        n_mp = len(sk); k = max(n_mp, 1)
+        tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int(); nt = C.c_int(); no = C.c_int()
+        iv = np.zeros(k, np.uint8); pj = np.zeros((k, 3), np.float32); pl = np.full(k, -1, np.int32); vc = np.zeros(k, np.float32)
+        check(self.ctx.ptr, lib().cs_match_local_map_frustum(self.ctx.ptr, self._m, _p(R, C.c_float), _p(t, C.c_float), _p(O, C.c_float), n_mp, _p(wp, C.c_float), _p(nr, C.c_float),
+                                                             _p(mn, C.c_float), _p(mx, C.c_float), _p(sk, C.c_uint8), _p(bl, C.c_uint8), _p(md, C.c_uint8),
+                                                             None if tb is None else _p(tb, C.c_uint8), C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.c_float(bf),
+                                                             C.c_float(log_scale_factor), _p(sf, C.c_float), len(sf), C.c_float(viewing_cos_limit), C.c_float(th), C.c_float(self.mfNNratio),
+                                                             _p(tm, C.c_int), C.byref(n), C.byref(nt), C.byref(no), _p(iv, C.c_uint8), _p(pj, C.c_float), _p(pl, C.c_int), _p(vc, C.c_float)),
+              "cs_match_local_map_frustum")
+        return {"train_match": tm[:self.N].copy(), "nmatches": n.value, "n_to_match": nt.value, "outside": no.value, "in_view": iv[:n_mp], "proj": pj[:n_mp], "pred_level": pl[:n_mp],
+                "view_cos": vc[:n_mp]}
+
+    def FuseMap(self, u_right, inv_level_sigma2, Rcw, tcw, Ow, world_pos, normal, min_distance, max_distance, skip, mp_desc, fx, fy, cx, cy, bf, log_scale_factor, scale_factors, th=3.0,
+                keys_static=None):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) with its preamble (ORBmatcher.cc:871-983) against the key frame given to set_frame: (best_idx, best_dist per map point, nFused,
+        points outside the scale table)."""
+        wp, mn, mx, sk, md, nr = self._map_points(world_pos, min_distance, max_distance, skip, mp_desc, normal)
+        R, t, O = self._f(Rcw, 9), self._f(tcw, 3), self._f(Ow, 3); sf = np.ascontiguousarray(scale_factors, np.float32)
+        kr = np.ascontiguousarray(u_right, np.float32); isg = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        assert len(isg) == len(sf)
+        ks = None if keys_static is None else np.ascontiguousarray(keys_static, np.uint8)
+        bi = np.zeros(max(len(sk), 1), np.int32); bd = np.zeros(max(len(sk), 1), np.int32); n = C.c_int(); no = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_fuse_map(self.ctx.ptr, self._m, _p(kr, C.c_float), _p(isg, C.c_float), len(isg), None if ks is None else _p(ks, C.c_uint8), _p(R, C.c_float),
+                                                    _p(t, C.c_float), _p(O, C.c_float), len(sk), _p(wp, C.c_float), _p(nr, C.c_float), _p(mn, C.c_float), _p(mx, C.c_float), _p(sk, C.c_uint8),
+                                                    _p(md, C.c_uint8), C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.c_float(bf), C.c_float(log_scale_factor), _p(sf, C.c_float),
+                                                    C.c_float(th), _p(bi, C.c_int), _p(bd, C.c_int), C.byref(n), C.byref(no)), "cs_match_fuse_map")
+        return bi[:len(sk)].copy(), bd[:len(sk)].copy(), n.value, no.value
+
     def SearchBySim3(self, other, R1w, t1w, R2w, t2w, sR12, t12, sR21, t21, points1, points2, fx, fy, cx, cy, log_scale_factor, scale_factors, th, train_blocked1=None, train_blocked2=None):
         """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:1141-1371); self holds KF1, `other` KF2.  points_k = (world_pos, min_distance,
         max_distance, skip, mp_desc) of KFk's map points, one per key point.  Returns (matches12 per key point of KF1 = key point of KF2 or -1, nFound, points outside the scale table)."""

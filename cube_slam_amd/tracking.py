@@ -1,0 +1,178 @@
+"""Python host-side mirror of ORB_SLAM2::Tracking::TrackLocalMap (reference orb_object_slam/src/Tracking.cc:1356-1416) and what it calls: UpdateLocalMap (:2730-2738) with
+UpdateLocalKeyFrames (:2766-2874) and UpdateLocalPoints (:2740-2764), SearchLocalPoints (:2673-2728), Optimizer::PoseOptimization and the statistics loop (:1372-1397).
+
+The map is a table of points and a table of key frames in flat arrays (`Map` below); a frame is a `TrackedFrame`.  What the reference keeps as pointers are indices into those
+tables, -1 for NULL.  The search, the frustum test, the local point list and the pose run on the device; the walk over the key-frame graph, the loop over the frame's own
+points and the statistics over N flags stay on the host."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+from .matcher import ORBmatcher
+from .optimizer import PoseOptimization
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _u8(a):
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def track_local_points(ctx, kf_off, kf_mp, skip):
+    """Tracking::UpdateLocalPoints (cs_track_local_points): the concatenated map-point lists of the local key frames -> mvpLocalMapPoints."""
+    off, mp, sk = _i32(kf_off), _i32(kf_mp), _u8(skip)
+    out = np.zeros(max(min(int(off[-1]), len(sk)), 1), np.int32); n = C.c_int()
+    check(ctx.ptr, lib().cs_track_local_points(ctx.ptr, len(off) - 1, _p(off, C.c_int), _p(mp, C.c_int), len(sk), _p(sk, C.c_uint8), _p(out, C.c_int), C.byref(n)), "cs_track_local_points")
+    return out[:n.value].copy()
+
+
+def track_local_keyframes(frame_mp, mp_skip, obs_off, obs_kf, kf_bad, cov_off, cov_kf, child_off, child_kf, parent):
+    """Tracking::UpdateLocalKeyFrames (cs_track_local_keyframes, host) -> (mvpLocalKeyFrames or None when no key frame received a vote, pKFmax or -1)."""
+    fm, ms, oo, ok, kb = _i32(frame_mp), _u8(mp_skip), _i32(obs_off), _i32(obs_kf), _u8(kf_bad)
+    co, ck, ho, hk, pa = _i32(cov_off), _i32(cov_kf), _i32(child_off), _i32(child_kf), _i32(parent)
+    out = np.zeros(max(len(kb), 1), np.int32); n = C.c_int(); mx = C.c_int()
+    r = lib().cs_track_local_keyframes(len(fm), _p(fm, C.c_int), len(ms), _p(ms, C.c_uint8), _p(oo, C.c_int), _p(ok, C.c_int), len(kb), _p(kb, C.c_uint8), _p(co, C.c_int), _p(ck, C.c_int),
+                                       _p(ho, C.c_int), _p(hk, C.c_int), _p(pa, C.c_int), _p(out, C.c_int), C.byref(n), C.byref(mx))
+    check(None, r, "cs_track_local_keyframes")
+    return (None if n.value < 0 else out[:n.value].copy()), mx.value
+
+
+class Map:
+    """The point and key-frame tables the tracking thread reads.  Points: world_pos, normal, min_distance (mfMinDistance), max_distance, desc, bad (isBad), dynamic (is_dynamic),
+    n_obs (Observations()), obs_off / obs_kf (the key frames of GetObservations()), last_frame_seen, visible, found.  Key frames: kf_off / kf_mp (GetMapPointMatches()), kf_bad,
+    cov_off / cov_kf (mvpOrderedConnectedKeyFrames), child_off / child_kf, parent."""
+
+    def __init__(self, **arrays):
+        self.__dict__.update(arrays)
+        n = len(self.bad)
+        for name in ("last_frame_seen", "visible", "found"):
+            if not hasattr(self, name):
+                setattr(self, name, np.full(n, -1, np.int64) if name == "last_frame_seen" else np.zeros(n, np.int64))
+        if not hasattr(self, "dynamic"):
+            self.dynamic = np.zeros(n, np.uint8)
+
+
+class TrackedFrame:
+    """mCurrentFrame as TrackLocalMap reads and writes it: mnId, mvKeysUn, mDescriptors, the image bounds, mvpMapPoints (indices, -1), mvbOutlier, the pose (Rcw, tcw, Ow as float32),
+    intr = (fx, fy, cx, cy, mbf), mfLogScaleFactor, mvScaleFactors, mvInvLevelSigma2, mvuRight (optional), KeysStatic (optional)."""
+
+    def __init__(self, mnId, keysUn, desc, bounds, mvpMapPoints, Rcw, tcw, Ow, intr, log_scale_factor, scale_factors, inv_level_sigma2, pose7, u_right=None, keys_static=None):
+        self.mnId, self.keysUn, self.desc, self.bounds = mnId, keysUn, desc, bounds
+        self.mvpMapPoints = np.array(mvpMapPoints, np.int32)
+        self.mvbOutlier = np.zeros(len(keysUn), np.uint8)
+        self.Rcw, self.tcw, self.Ow = Rcw, tcw, Ow
+        self.intr, self.log_scale_factor, self.scale_factors, self.inv_level_sigma2 = intr, log_scale_factor, scale_factors, inv_level_sigma2
+        self.pose7 = np.asarray(pose7, np.float64)
+        self.u_right = np.full(len(keysUn), -1.0, np.float32) if u_right is None else np.asarray(u_right, np.float32)
+        self.keys_static = keys_static
+
+
+class Tracking:
+    STEREO, MONOCULAR, RGBD = 1, 0, 2  # System::eSensor
+
+    def __init__(self, ctx=None, device=0, sensor=0, whether_dynamic_object=False, whether_detect_object=False, mbOnlyTracking=False, mMaxFrames=30, **matcher_kw):
+        self.ctx = ctx or _lib.Context(device)
+        self.mSensor, self.whether_dynamic_object, self.whether_detect_object, self.mbOnlyTracking, self.mMaxFrames = sensor, whether_dynamic_object, whether_detect_object, mbOnlyTracking, mMaxFrames
+        self.matcher = ORBmatcher(0.8, True, ctx=self.ctx, **matcher_kw)  # :2719
+        self.mvpLocalKeyFrames = np.zeros(0, np.int32)
+        self.mvpLocalMapPoints = np.zeros(0, np.int32)
+        self.mpReferenceKF = -1
+        self.mnLastRelocFrameId = -10 ** 9
+        self.mnMatchesInliers = 0
+        self.last_search = None
+
+    def _skip(self, m):
+        return (m.bad != 0) | ((m.dynamic != 0) if self.whether_dynamic_object else False)
+
+    def UpdateLocalKeyFrames(self, F, m):
+        mp = F.mvpMapPoints
+        has = mp >= 0
+        F.mvpMapPoints[has & (m.bad[np.where(has, mp, 0)] != 0)] = -1  # :2783-2786
+        local, kfmax = track_local_keyframes(F.mvpMapPoints, self._skip(m), m.obs_off, m.obs_kf, m.kf_bad, m.cov_off, m.cov_kf, m.child_off, m.child_kf, m.parent)
+        if local is not None:
+            self.mvpLocalKeyFrames = local
+            if kfmax >= 0:
+                self.mpReferenceKF = kfmax
+        return self.mvpLocalKeyFrames
+
+    def UpdateLocalPoints(self, F, m):
+        off = np.zeros(len(self.mvpLocalKeyFrames) + 1, np.int32)
+        lens = (m.kf_off[1:] - m.kf_off[:-1])[self.mvpLocalKeyFrames]
+        off[1:] = np.cumsum(lens)
+        mp = np.concatenate([m.kf_mp[m.kf_off[j]:m.kf_off[j + 1]] for j in self.mvpLocalKeyFrames]) if len(lens) else np.zeros(0, np.int32)
+        self.mvpLocalMapPoints = track_local_points(self.ctx, off, mp, self._skip(m))
+        return self.mvpLocalMapPoints
+
+    def UpdateLocalMap(self, F, m):
+        self.UpdateLocalKeyFrames(F, m)
+        return self.UpdateLocalPoints(F, m)
+
+    def SearchLocalPoints(self, F, m):
+        mp = F.mvpMapPoints
+        has = mp >= 0
+        F.mvpMapPoints[has & (m.bad[np.where(has, mp, 0)] != 0)] = -1  # :2681-2684
+        own = F.mvpMapPoints[(F.mvpMapPoints >= 0)]
+        own = own[m.dynamic[own] == 0]  # :2687
+        np.add.at(m.visible, own, 1)
+        m.last_frame_seen[own] = F.mnId
+        lp = self.mvpLocalMapPoints
+        skip = (m.last_frame_seen[lp] == F.mnId) | (m.bad[lp] != 0) | (m.dynamic[lp] != 0)  # :2702-2707
+        th = 1
+        if self.mSensor == self.RGBD:
+            th = 3
+        if F.mnId < self.mnLastRelocFrameId + 2:
+            th = 5
+        held = F.mvpMapPoints >= 0
+        tb = np.zeros(len(F.keysUn), np.uint8)
+        tb[held] = m.n_obs[F.mvpMapPoints[held]] > 0  # :96-98
+        if F.keys_static is not None:
+            tb |= (np.asarray(F.keys_static) == 0).astype(np.uint8)  # :101
+        self.matcher.set_frame(F.keysUn, F.desc, F.bounds)
+        fx, fy, cx, cy, bf = F.intr
+        r = self.matcher.SearchLocalPoints(F.Rcw, F.tcw, F.Ow, m.world_pos[lp], m.normal[lp], m.min_distance[lp], m.max_distance[lp], skip, m.n_obs[lp] > 0, m.desc[lp], fx, fy, cx, cy, bf,
+                                           F.log_scale_factor, F.scale_factors, float(th), 0.5, tb)
+        np.add.at(m.visible, lp[r["in_view"] != 0], 1)  # :2712
+        got = r["train_match"] >= 0
+        F.mvpMapPoints[got] = lp[r["train_match"][got]]  # :136
+        self.last_search = r
+        return r
+
+    def TrackLocalMap(self, F, m):
+        self.UpdateLocalMap(F, m)
+        self.SearchLocalPoints(F, m)
+        idx = np.nonzero(F.mvpMapPoints >= 0)[0]
+        mp = F.mvpMapPoints[idx]
+        obs = np.stack([F.keysUn["x"][idx], F.keysUn["y"][idx], F.u_right[idx]], axis=1).astype(np.float64) if len(idx) else np.zeros((0, 3))
+        fr = {"Xw": m.world_pos[mp].astype(np.float64), "obs": obs, "inv_sigma2": np.asarray(F.inv_level_sigma2, np.float32)[F.keysUn["octave"][idx]].astype(np.float64),
+              "intr": np.asarray(F.intr, np.float32).astype(np.float64), "pose": F.pose7}  # (the Frame's intrinsics are floats)
+        pose, flags, _ = PoseOptimization([fr], ctx=self.ctx)[0]  # :1366
+        F.pose7 = pose
+        F.mvbOutlier[:] = 0
+        F.mvbOutlier[idx] = flags
+        self.mnMatchesInliers = 0
+        for i, p in zip(idx, mp):  # :1372-1397
+            if not F.mvbOutlier[i]:
+                if self.whether_dynamic_object and m.dynamic[p]:
+                    continue
+                m.found[p] += 1
+                if not self.mbOnlyTracking:
+                    if m.n_obs[p] > 0:
+                        self.mnMatchesInliers += 1
+                else:
+                    self.mnMatchesInliers += 1
+            elif self.mSensor == self.STEREO:
+                F.mvpMapPoints[i] = -1
+        if F.mnId < self.mnLastRelocFrameId + self.mMaxFrames and self.mnMatchesInliers < 50:  # :1402
+            return False
+        return self.mnMatchesInliers >= (20 if self.whether_detect_object else 30)  # :1405-1415
+
+    def close(self):
+        self.matcher.close()

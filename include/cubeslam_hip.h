@@ -354,6 +354,43 @@ int cs_match_by_projection_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, co
 int cs_match_fuse_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
                        const float *max_distance, const uint8_t *skip, const uint8_t *mp_desc, const uint8_t *train_blocked /* nullable */, float fx, float fy, float cx, float cy,
                        float log_scale_factor, const float *scale_factors, int n_levels, float th, int *best_idx, int *best_dist, int *n_fused, int *n_level_outside /* nullable */);
+/* Tracking::SearchLocalPoints (Tracking.cc:2673-2728) in one call: Frame::isInFrustum (Frame.cc:346-402) for every local map point and ORBmatcher::SearchByProjection(F,
+ * vpMapPoints, th) (ORBmatcher.cc:50-142) -- cs_match_local_map with its preamble on the device.  The matcher holds the current frame; Rcw, tcw, Ow = mRcw, mtcw, mOw;
+ * skip[i] = mnLastFrameSeen == mCurrentFrame.mnId || isBad || is_dynamic (:2702-2707; the loop over the frame's own points, :2676-2694, stays with the caller); blocks[i] =
+ * Observations() > 0 (what a later point's candidate loop asks of a key point claimed by point i, :96-98); train_blocked[idx] = (mvpMapPoints[idx] && Observations() > 0) ||
+ * !KeysStatic[idx]; bf = mbf; viewing_cos_limit = 0.5 at :2710; th = the search radius factor (:2720-2725), nnratio = 0.8 (:2719).
+ * train_match[N]: the local point a key point receives, -1 none; *nmatches: what the search returns; *n_to_match = nToMatch.  What isInFrustum leaves on a map point comes back per
+ * point: in_view[n] = mbTrackInView (the caller's IncreaseVisible), proj[3 n] = (mTrackProjX, mTrackProjY, mTrackProjXR), pred_level[n] = mnTrackScaleLevel (-1 when not in view),
+ * view_cos[n] = mTrackViewCos (proj and view_cos 0 when not in view); the last three are nullable.
+ * Deviations: (1) a predicted level outside the scale table drops the point and counts it in *n_level_outside, as above -- it is not in view and not in *n_to_match; (2) PcZ == 0
+ * passes the reference's depth test, and where it leaves u or v not finite (NaN: the bounds comparisons are all false and the reference goes on to undefined float -> int casts) the
+ * point is rejected.  With *n_to_match == 0 the reference does not call the search (:2717); here no query is valid then and train_match is all -1 all the same.  The stereo test on
+ * mvuRight (:104-109) is not applied, as in cs_match_local_map; uR is only returned.  One wait per call; nothing is allocated. */
+int cs_match_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal,
+                               const float *min_distance, const float *max_distance, const uint8_t *skip, const uint8_t *blocks, const uint8_t *mp_desc,
+                               const uint8_t *train_blocked /* nullable */, float fx, float fy, float cx, float cy, float bf, float log_scale_factor, const float *scale_factors, int n_levels,
+                               float viewing_cos_limit, float th, float nnratio, int *train_match, int *nmatches, int *n_to_match, int *n_level_outside /* nullable */, uint8_t *in_view,
+                               float *proj /* nullable */, int *pred_level /* nullable */, float *view_cos /* nullable */);
+/* ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) (ORBmatcher.cc:852-1003) with its preamble (:871-920) on the device: cs_match_fuse without the caller's part.  The
+ * matcher holds pKF; Rcw, tcw, Ow = GetRotation / GetTranslation / GetCameraCenter; skip[i] = !pMP || isBad || IsInKeyFrame(pKF) || is_dynamic; bf = mbf; u_right, inv_level_sigma2,
+ * keys_static, best_idx, best_dist, *n_fused as for cs_match_fuse; *n_level_outside as above. */
+int cs_match_fuse_map(cs_ctx *ctx, cs_matcher *m, const float *u_right, const float *inv_level_sigma2, int n_levels, const uint8_t *keys_static /* nullable */, const float *Rcw,
+                      const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance, const float *max_distance, const uint8_t *skip,
+                      const uint8_t *mp_desc, float fx, float fy, float cx, float cy, float bf, float log_scale_factor, const float *scale_factors, float th, int *best_idx, int *best_dist,
+                      int *n_fused, int *n_level_outside /* nullable */);
+/* Tracking::UpdateLocalPoints (Tracking.cc:2740-2764).  kf_off[n_kf + 1] / kf_mp: the GetMapPointMatches() lists of mvpLocalKeyFrames in order, as indices into the caller's point
+ * table (-1: no map point); skip[n_points] = isBad || (whether_dynamic_object && is_dynamic).  local_points (room for min(kf_off[n_kf], n_points)): mvpLocalMapPoints -- every point
+ * that is not skipped, once, in the order of its first occurrence in the concatenated lists; *n_local its length.  The result does not depend on the order in which the device runs
+ * anything.  CS_ERR_BAD_ARG for an index outside the point table. */
+int cs_track_local_points(cs_ctx *ctx, int n_kf, const int *kf_off, const int *kf_mp, int n_points, const uint8_t *skip, int *local_points, int *n_local);
+/* Tracking::UpdateLocalKeyFrames (Tracking.cc:2766-2874), on the host.  frame_mp[n_frame] = mCurrentFrame.mvpMapPoints as indices into the point table (-1 none); mp_skip[n_points] =
+ * isBad || (whether_dynamic_object && is_dynamic) (clearing a bad point's slot, :2785, stays with the caller); obs_off[n_points + 1] / obs_kf = the key frames of GetObservations();
+ * kf_bad[n_kf] = isBad; cov_off / cov_kf = mvpOrderedConnectedKeyFrames per key frame (its first ten are used); child_off / child_kf = GetChilds(); parent[n_kf] = GetParent() or -1.
+ * The reference walks a std::map<KeyFrame*, int> and a std::set<KeyFrame*> in pointer order; that order is defined here as ascending index in the key-frame table (children: as
+ * listed).  local_kf (room for n_kf) / *n_local = mvpLocalKeyFrames; *n_local = -1: no key frame received a vote, the reference returns early and the caller keeps its lists.
+ * *kf_max = pKFmax (-1: mpReferenceKF stays). */
+int cs_track_local_keyframes(int n_frame, const int *frame_mp, int n_points, const uint8_t *mp_skip, const int *obs_off, const int *obs_kf, int n_kf, const uint8_t *kf_bad,
+                             const int *cov_off, const int *cov_kf, const int *child_off, const int *child_kf, const int *parent, int *local_kf, int *n_local, int *kf_max);
 /* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:1141-1371).  m1 / m2 hold KF1 / KF2 (two different matchers); point i of side k is the map
  * point of key point i of KFk (n_k = its key point count); skip1[i] = !pMP || vbAlreadyMatched1[i] || isBad, skip2 likewise (:1171-1181 stay with the caller);
  * train_blocked_k[idx] = !KFk.KeysStatic[idx] (nullable).  R1w, t1w, R2w, t2w = the key frames' poses; sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t(), t21 = -sR21 * t12 (:1158-1160).

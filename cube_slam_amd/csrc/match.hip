@@ -25,6 +25,7 @@
 //   match_knn2           all-pairs best / second best, train descriptors staged through LDS
 #include "common.h"
 #include "cv_math.h"
+#include "frame_math.h"
 #include "glibc_logf.h"
 
 #include <algorithm>
@@ -91,27 +92,7 @@ __global__ void __launch_bounds__(1024) match_grid(FrameP F, const cs_keypoint *
     for (int i = tid; i < cell_start[NCELL]; i += 1024) { const int id = cell_items[i]; const cs_keypoint k = keys[id]; cell_recs[i] = CellRec{k.x, k.y, id, k.octave}; }
 }
 
-// cv::undistortPoints(src, dst, K, D, Mat(), K) as Frame::UndistortKeyPoints / ComputeImageBounds call it (Frame.cc:546-609): the
-// classic cvUndistortPoints of OpenCV 2.4 - 3.2 -- normalise with the double copies of the float intrinsics, five fixed-point
-// iterations of the Brown model (k1 k2 p1 p2 k3), re-project with P = K, round to float.  (Later OpenCV versions stop the iteration on
-// a reprojection-error criterion; the reference's target version is not pinned)  -ffp-contract=off: plain double ops.
-struct UndP { double fx, fy, cx, cy, k[5]; int identity; };
-__host__ __device__ inline void undistort_point(const UndP &U, float xin, float yin, float &xo, float &yo) {
-    if (U.identity) { xo = xin; yo = yin; return; }
-    const double ifx = 1. / U.fx, ify = 1. / U.fy;
-    double x = ((double)xin - U.cx) * ifx, y = ((double)yin - U.cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1 + ((0.0 * r2 + 0.0) * r2 + 0.0) * r2) / (1 + ((U.k[4] * r2 + U.k[1]) * r2 + U.k[0]) * r2);
-        const double deltaX = 2 * U.k[2] * x * y + U.k[3] * (r2 + 2 * x * x);
-        const double deltaY = U.k[2] * (r2 + 2 * y * y) + 2 * U.k[3] * x * y;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
-    }
-    const double xx = U.fx * x + 0.0 * y + U.cx, yy = 0.0 * x + U.fy * y + U.cy, ww = 1. / (0.0 * x + 0.0 * y + 1.0);
-    xo = (float)(xx * ww); yo = (float)(yy * ww);
-}
+// UndP, undistort_point, make_undp: frame_math.h
 __global__ void match_undistort(int n, const cs_keypoint *in, UndP U, cs_keypoint *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -848,12 +829,6 @@ int cs_matcher_set_frame(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *keysUn, 
     return CS_OK;
 }
 
-static UndP make_undp(const float *K4, const float *dist5) {
-    UndP U; U.fx = K4[0]; U.fy = K4[1]; U.cx = K4[2]; U.cy = K4[3];
-    for (int i = 0; i < 5; i++) U.k[i] = dist5 ? (double)dist5[i] : 0.0;
-    U.identity = !dist5 || dist5[0] == 0.0f; // Frame.cc:548: only the first coefficient is looked at
-    return U;
-}
 int cs_frame_image_bounds(int cols, int rows, const float *K4, const float *dist5, float *bounds) { // Frame::ComputeImageBounds (Frame.cc:578-609)
     if (!K4 || !bounds || cols < 1 || rows < 1) return CS_ERR_BAD_ARG;
     const UndP U = make_undp(K4, dist5);

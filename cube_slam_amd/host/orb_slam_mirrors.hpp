@@ -4,11 +4,16 @@
 // are thin wrappers around these and compile only in a tree that provides OpenCV / Eigen / the ORB-SLAM2 map classes.
 //   cubeslam::ORBextractor      ORB_SLAM2::ORBextractor      (orb_object_slam/include/ORBextractor.h:44-112)
 //   cubeslam::Frame             ORB_SLAM2::Frame, the stereo members (orb_object_slam/include/Frame.h, src/Frame.cc:94-144, :611-783):
-//                               ComputeStereoMatches over two extractors, mvuRight / mvDepth
+//                               ComputeStereoMatches over two extractors, mvuRight / mvDepth; the RGB-D members (:146-199, :334-344, :785-822):
+//                               ComputeStereoFromRGBD, UpdatePoseMatrices, UnprojectStereo
+//   cubeslam::ClosePoints       the creation of map points from measured depth in Tracking::StereoInitialization, UpdateLastFrame and CreateNewKeyFrame
+//                               (src/Tracking.cc:783-850, :1207-1274, :2067-2130)
 //   cubeslam::line_lbd_detect   line_lbd_detect              (line_lbd/include/line_lbd/line_lbd_allclass.h:22-70)
 //   cubeslam::Optimizer         ORB_SLAM2::Optimizer         (orb_object_slam/include/Optimizer.h:39-62): BundleAdjustment over the
 //                               flattened graph (cs_ba_problem), PoseOptimization over flattened matches, OptimizeSim3 over flattened correspondences,
 //                               LocalBACameraPointObjectsDynamic over the flattened dynamic graph (cs_ba_dyn_problem)
+// With CUBESLAM_HOST_ONLY defined the header holds the RGB-D members of Frame and ClosePoints alone, on their path without a context (csrc/rgbd_math.h, the text the
+// kernels run; compile with -ffp-contract=off): of the C header only the types are used and nothing of the library is linked.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -16,10 +21,16 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "../csrc/rgbd_math.h"
+#ifndef CUBESLAM_HOST_ONLY
 #include "detect_3d_cuboid.hpp" // cubeslam::Context
+#else
+namespace cubeslam { struct Context; class ORBextractor; }
+#endif
 
 namespace cubeslam {
 
+#ifndef CUBESLAM_HOST_ONLY
 inline void check(cs_ctx *ctx, int r, const char *what) {
     if (r != CS_OK) throw std::runtime_error(std::string(what) + " failed (" + std::to_string(r) + "): " + cs_last_error(ctx));
 }
@@ -57,43 +68,154 @@ class ORBextractor {
     int nfeatures_, nlevels_, W_, H_;
 };
 
+#endif // CUBESLAM_HOST_ONLY
+
 // The stereo part of ORB_SLAM2::Frame: what the stereo constructor (Frame.cc:94-144) does between the two extractions (:106-110) and
 // AssignFeaturesToGrid: ComputeStereoMatches (:118, :611-783) on the device, from what the two extractors' last operator() left there.
+// The RGB-D part: what the RGB-D constructor (:146-199) does behind UndistortKeyPoints, ComputeStereoFromRGBD (:173, :785-806), and the pose and
+// unprojection members the close-point rule reads (:334-344, :808-822).
 class Frame {
   public:
+#ifndef CUBESLAM_HOST_ONLY
     // Frame(..., ORBextractor *extractorLeft, ORBextractor *extractorRight, ..., const float &bf, ...).  mb: the reference's constructor sets
     // mb = mbf / fx at :141, after ComputeStereoMatches ran at :118, so its first frame runs with whatever the member held; set mb to the value meant.
     Frame(Context &c, ORBextractor *extractorLeft, ORBextractor *extractorRight, float bf, float b, int max_keypoints)
-        : mbf(bf), mb(b), mpORBextractorLeft(extractorLeft), mpORBextractorRight(extractorRight), ctx_(c) {
-        check(ctx_.ctx, cs_stereo_create(ctx_.ctx, max_keypoints, 1, &s_), "cs_stereo_create");
+        : mbf(bf), mb(b), mpORBextractorLeft(extractorLeft), mpORBextractorRight(extractorRight), ctx_(&c) {
+        check(ctx_->ctx, cs_stereo_create(ctx_->ctx, max_keypoints, 1, &s_), "cs_stereo_create");
     }
-    ~Frame() { cs_stereo_destroy(ctx_.ctx, s_); }
+#endif
+    // The RGB-D frame over the caller's mvKeys / mvKeysUn (fill them before ComputeStereoFromRGBD): K4 = fx fy cx cy, the size of the depth image.  Without a context
+    // (c == nullptr) every member runs on the host, byte-equal to the device.
+    Frame(Context *c, const float K4[4], float bf, int width, int height)
+        : mbf(bf), mb(bf / K4[0]), mpORBextractorLeft(nullptr), mpORBextractorRight(nullptr), fx(K4[0]), fy(K4[1]), cx(K4[2]), cy(K4[3]), invfx(1.0f / K4[0]), invfy(1.0f / K4[1]),
+          width_(width), height_(height), ctx_(c) {}
+    ~Frame() {
+#ifndef CUBESLAM_HOST_ONLY
+        if (s_) cs_stereo_destroy(ctx_->ctx, s_);
+        if (r_) cs_rgbd_destroy(ctx_->ctx, r_);
+#endif
+    }
     Frame(const Frame &) = delete;
     Frame &operator=(const Frame &) = delete;
+#ifndef CUBESLAM_HOST_ONLY
     // void Frame::ComputeStereoMatches(): fills mvuRight / mvDepth (N values, -1 where unmatched); returns the number of matches kept
     int ComputeStereoMatches() {
-        check(ctx_.ctx, cs_stereo_match_from_orb(ctx_.ctx, s_, mpORBextractorLeft->handle(), 0, mpORBextractorRight->handle(), 0, 1, mbf, mb), "cs_stereo_match_from_orb");
+        check(ctx_->ctx, cs_stereo_match_from_orb(ctx_->ctx, s_, mpORBextractorLeft->handle(), 0, mpORBextractorRight->handle(), 0, 1, mbf, mb), "cs_stereo_match_from_orb");
         int first[2] = {0, 0}, n_matched = 0;
         long total = 0;
-        check(ctx_.ctx, cs_stereo_read_packed(ctx_.ctx, s_, nullptr, nullptr, 0, first, &total, nullptr), "cs_stereo_read_packed");
+        check(ctx_->ctx, cs_stereo_read_packed(ctx_->ctx, s_, nullptr, nullptr, 0, first, &total, nullptr), "cs_stereo_read_packed");
         N = (int)total;
         mvuRight.assign((size_t)N + 1, -1.0f); mvDepth.assign((size_t)N + 1, -1.0f);
-        check(ctx_.ctx, cs_stereo_read_packed(ctx_.ctx, s_, mvuRight.data(), mvDepth.data(), total, first, &total, &n_matched), "cs_stereo_read_packed");
+        check(ctx_->ctx, cs_stereo_read_packed(ctx_->ctx, s_, mvuRight.data(), mvDepth.data(), total, first, &total, &n_matched), "cs_stereo_read_packed");
         mvuRight.resize((size_t)N); mvDepth.resize((size_t)N);
         return n_matched;
     }
     // mvuRight / mvDepth where they were computed, for cs_match_fuse / cs_pose_optimization callers that keep them on the device
-    void device(const float **d_uRight, const float **d_depth) const { int n = 0; check(ctx_.ctx, cs_stereo_device_pair(s_, 0, d_uRight, d_depth, &n), "cs_stereo_device_pair"); }
+    void device(const float **d_uRight, const float **d_depth) const {
+        int n = 0;
+        if (r_) check(ctx_->ctx, cs_rgbd_device_frame(r_, 0, d_uRight, d_depth, nullptr, &n), "cs_rgbd_device_frame");
+        else check(ctx_->ctx, cs_stereo_device_pair(s_, 0, d_uRight, d_depth, &n), "cs_stereo_device_pair");
+    }
+#endif
+    // void Frame::ComputeStereoFromRGBD(const cv::Mat &imDepth) on the RAW depth image (type CS_DEPTH_U16 / CS_DEPTH_F32, rows `stride` bytes apart) with the factor of
+    // Tracking::GrabImageRGBD's convertTo (Tracking.cc:388): fills mvuRight / mvDepth for mvKeys / mvKeysUn; returns the number of key points with depth
+    int ComputeStereoFromRGBD(const void *depth, int type, long stride, float factor) {
+        N = (int)mvKeys.size();
+        if (mvKeysUn.size() != mvKeys.size()) throw std::invalid_argument("Frame::ComputeStereoFromRGBD: mvKeys and mvKeysUn differ in length");
+        mvuRight.assign((size_t)N + 1, -1.0f); mvDepth.assign((size_t)N + 1, -1.0f);
+        int n_with = 0;
+        n_outside = 0;
+        if (!ctx_) {
+            if (cs_rgbd_host_status(depth, type, stride) != CS_OK) throw std::invalid_argument("Frame::ComputeStereoFromRGBD: no image, an unknown type or rows that overlap");
+            rgbd_frame_host(depth, type, width_, height_, stride, N, N ? &mvKeys[0].x : nullptr, N ? &mvKeysUn[0].x : nullptr, 7, mbf, factor, mvuRight.data(), mvDepth.data(),
+                            &n_with, &n_outside);
+        } else {
+#ifndef CUBESLAM_HOST_ONLY
+            if (!r_ || N > r_cap_) {
+                if (r_) cs_rgbd_destroy(ctx_->ctx, r_);
+                r_ = nullptr; r_cap_ = N > 0 ? N : 1;
+                check(ctx_->ctx, cs_rgbd_create(ctx_->ctx, width_, height_, r_cap_, 1, &r_), "cs_rgbd_create");
+            }
+            const int first[2] = {0, N};
+            int f2[2];
+            long total = 0;
+            check(ctx_->ctx, cs_rgbd_upload_depth(ctx_->ctx, r_, depth, type, 1, stride), "cs_rgbd_upload_depth");
+            check(ctx_->ctx, cs_rgbd_from_keys(ctx_->ctx, r_, 1, first, mvKeys.data(), mvKeysUn.data(), mbf, factor), "cs_rgbd_from_keys");
+            check(ctx_->ctx, cs_rgbd_read_packed(ctx_->ctx, r_, mvuRight.data(), mvDepth.data(), (long)N + 1, f2, &total, &n_with, &n_outside), "cs_rgbd_read_packed");
+#else
+            throw std::runtime_error("Frame: built without the library");
+#endif
+        }
+        mvuRight.resize((size_t)N); mvDepth.resize((size_t)N);
+        return n_with;
+    }
+    // void Frame::SetPose(cv::Mat Tcw) / UpdatePoseMatrices(): Tcw = the rows of [Rcw | tcw]
+    void SetPose(const float Tcw[12]) { for (int k = 0; k < 12; k++) mTcw[k] = Tcw[k]; UpdatePoseMatrices(); }
+    void UpdatePoseMatrices() { rgbd_pose_matrices(mTcw, mRwc, mOw); }
+    // cv::Mat Frame::UnprojectStereo(const int &i): false = the empty Mat of z <= 0
+    bool UnprojectStereo(int i, float x3D[3]) const {
+        const float z = mvDepth[(size_t)i];
+        if (!(z > 0)) return false;
+        rgbd_unproject(mvKeysUn[(size_t)i].x, mvKeysUn[(size_t)i].y, z, cx, cy, invfx, invfy, mRwc, mOw, x3D);
+        return true;
+    }
     int N = 0;
     std::vector<float> mvuRight, mvDepth;
     float mbf, mb;
     ORBextractor *mpORBextractorLeft, *mpORBextractorRight;
+    // the RGB-D frame
+    std::vector<cs_keypoint> mvKeys, mvKeysUn;
+    float fx = 0, fy = 0, cx = 0, cy = 0, invfx = 0, invfy = 0;
+    float mTcw[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, mRwc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, mOw[3] = {0, 0, 0};
+    int n_outside = 0; // key points whose sample lies outside the image (undefined in the reference; they end without depth)
 
   private:
-    Context &ctx_;
+    static int cs_rgbd_host_status(const void *depth, int type, long stride) { return depth && (type == CS_DEPTH_U16 || type == CS_DEPTH_F32) && stride > 0 ? CS_OK : CS_ERR_BAD_ARG; }
+    int width_ = 0, height_ = 0;
+    Context *ctx_;
+#ifndef CUBESLAM_HOST_ONLY
     cs_stereo *s_ = nullptr;
+    cs_rgbd *r_ = nullptr;
+    int r_cap_ = 0;
+#endif
 };
 
+// The close-point rule over one frame's mvDepth (from either depth sensor) and mvKeysUn: what Tracking::UpdateLastFrame (Tracking.cc:1221-1273) and CreateNewKeyFrame
+// (:2075-2128) do with mode CS_CLOSE_POINTS_NEAREST, StereoInitialization (:804-819) with CS_CLOSE_POINTS_ALL.  need_new[i] = `!pMP || pMP->Observations() < 1`.
+// Without a context the host runs the reference's loop (csrc/rgbd_math.h), byte-equal to the device's closed form.
+struct ClosePointsResult {
+    int n_valid = 0, n_walked = 0;  // key points with z > 0; nPoints when the loop ends
+    std::vector<int> order;         // vDepthIdx after the sort: the indices of all key points with z > 0
+    std::vector<int> new_idx;       // the key points a point is created for, in creation order
+    std::vector<float> new_x3D;     // Frame::UnprojectStereo of each
+};
+inline ClosePointsResult ClosePoints(Context *ctx, const std::vector<float> &mvDepth, const std::vector<cs_keypoint> &mvKeysUn, const std::vector<uint8_t> &need_new,
+                                     const float Tcw[12], const float K4[4], float thDepth, int mode) {
+    const int n = (int)mvDepth.size();
+    if (mvKeysUn.size() != (size_t)n || (mode != CS_CLOSE_POINTS_ALL && need_new.size() != (size_t)n) || (mode != CS_CLOSE_POINTS_ALL && mode != CS_CLOSE_POINTS_NEAREST))
+        throw std::invalid_argument("ClosePoints: one entry per key point in every array, and a known mode");
+    ClosePointsResult r;
+    r.order.resize((size_t)n + 1); r.new_idx.resize((size_t)n + 1); r.new_x3D.resize(3 * (size_t)n + 3);
+    int n_new = 0;
+    if (!ctx) {
+        rgbd_close_points_host(n, mvDepth.data(), n ? &mvKeysUn[0].x : nullptr, 7, need_new.data(), Tcw, K4, thDepth, mode, &r.n_valid, r.order.data(), &r.n_walked, &n_new,
+                               r.new_idx.data(), r.new_x3D.data());
+    } else {
+#ifndef CUBESLAM_HOST_ONLY
+        const int first[2] = {0, n};
+        int new_first[2] = {0, 0};
+        check(ctx->ctx, cs_close_points(ctx->ctx, 1, first, mvDepth.data(), mvKeysUn.data(), mode == CS_CLOSE_POINTS_ALL ? nullptr : need_new.data(), Tcw, K4, thDepth, mode, &r.n_valid,
+                                        r.order.data(), &r.n_walked, new_first, r.new_idx.data(), r.new_x3D.data()), "cs_close_points");
+        n_new = new_first[1];
+#else
+        throw std::runtime_error("ClosePoints: built without the library");
+#endif
+    }
+    r.order.resize((size_t)r.n_valid); r.new_idx.resize((size_t)n_new); r.new_x3D.resize(3 * (size_t)n_new);
+    return r;
+}
+
+#ifndef CUBESLAM_HOST_ONLY
 class line_lbd_detect {
   public:
     line_lbd_detect(Context &c, int width, int height) : ctx_(c), W_(width), H_(height) { check(ctx_.ctx, cs_lsd_create(ctx_.ctx, width, height, 1, &l_), "cs_lsd_create"); }
@@ -219,5 +341,7 @@ struct Optimizer {
         stage(10, st2, eo, ed, ec);
     }
 };
+
+#endif // CUBESLAM_HOST_ONLY
 
 } // namespace cubeslam

@@ -174,5 +174,34 @@ class Tracking:
             return False
         return self.mnMatchesInliers >= (20 if self.whether_detect_object else 30)  # :1405-1415
 
+    def UpdateLastFrame(self, mvDepth, keysUn, mvpMapPoints, observations, Tcw, K4, mThDepth, next_point_id, last_frame_is_keyframe=False, rgbd=None, host=False):
+        """The point creation of Tracking::UpdateLastFrame (Tracking.cc:1215-1273) over index tables.  mvDepth / keysUn / mvpMapPoints (-1 = NULL) are the last
+        frame's, observations[p] = MapPoint::Observations() of map point p, Tcw [3, 4] the pose the caller has set (:1213), next_point_id = MapPoint::nNextId.  The
+        created "visual odometry" points take the ids next_point_id, next_point_id + 1, ... in creation order, fill their slots and are appended to mlpTemporalPoints.
+        Returns (mvpMapPoints afterwards, the ids created, their positions [k, 3]).  rgbd: an RGBDAssociator whose last call left this frame (alone) on the device --
+        depth and key points are then not uploaded; host=True: the statement on the host."""
+        from .rgbd import CS_CLOSE_POINTS_NEAREST, ClosePoints
+        mp = np.array(mvpMapPoints, np.int64)
+        temporal = self.__dict__.setdefault("mlpTemporalPoints", [])
+        if last_frame_is_keyframe or self.mSensor == self.MONOCULAR:  # :1215
+            return mp, [], np.zeros((0, 3), np.float32)
+        obs = np.asarray(observations)
+        need_new = ((mp < 0) | (obs[np.maximum(mp, 0)] < 1)).astype(np.uint8)  # !pMP || pMP->Observations() < 1
+        if rgbd is not None and not host:
+            r = rgbd.close_points(need_new, np.asarray(Tcw, np.float32)[None], K4, mThDepth, CS_CLOSE_POINTS_NEAREST)[0]
+        else:
+            r = ClosePoints(mvDepth, keysUn, need_new, Tcw, K4, mThDepth, CS_CLOSE_POINTS_NEAREST, ctx=None if host else self.ctx)
+        ids = list(range(int(next_point_id), int(next_point_id) + len(r["new_idx"])))
+        mp[r["new_idx"]] = ids  # mLastFrame.mvpMapPoints[i] = pNewMP
+        temporal.extend(ids)    # mlpTemporalPoints.push_back(pNewMP)
+        return mp, ids, r["new_x3D"]
+
+    def StereoInitializationPoints(self, mvDepth, keysUn, Tcw, K4, host=False):
+        """The loop of Tracking::StereoInitialization (Tracking.cc:804-819): (the key points with z > 0 in index order, Frame::UnprojectStereo of each).  The test
+        mCurrentFrame.N > 500 (:786), the key frame and everything done with `new MapPoint` stay the caller's."""
+        from .rgbd import CS_CLOSE_POINTS_ALL, ClosePoints
+        r = ClosePoints(mvDepth, keysUn, None, Tcw, K4, 0.0, CS_CLOSE_POINTS_ALL, ctx=None if host else self.ctx)
+        return r["new_idx"], r["new_x3D"]
+
     def close(self):
         self.matcher.close()

@@ -245,6 +245,70 @@ int cs_stereo_read_packed(cs_ctx *ctx, cs_stereo *s, float *u_right, float *dept
  * cs_match_fuse / cs_pose_optimization next; work queued on the context's stream after the call sees the results. */
 int cs_stereo_device_pair(const cs_stereo *s, int pair, const float **d_u_right, const float **d_depth, int *n);
 
+/* ===================================================================== RGB-D association and close-point creation
+ * Replaces ORB_SLAM2::Frame::ComputeStereoFromRGBD (orb_object_slam/src/Frame.cc:785-806, called at :173 of the RGB-D constructor, :146-199) together with the
+ * one use of the converted depth image (Tracking::GrabImageRGBD, src/Tracking.cc:366-404, convertTo(CV_32F, mDepthMapFactor) at :388), and the rule by which
+ * Tracking creates map points from measured depth for both depth sensors: StereoInitialization (:783-850), UpdateLastFrame (:1207-1274) and the stereo / RGB-D
+ * block of CreateNewKeyFrame (:2067-2130), all over Frame::UnprojectStereo (Frame.cc:808-822) and Frame::UpdatePoseMatrices (:334-344).
+ * The depth image stays raw on the device: only the samples under the key points are read and converted, d = (float)raw * depth_map_factor (one float multiply,
+ * what cv::Mat::convertTo gives for that sample; depth_map_factor == 1 is the exact copy).  Sample: row (int)kp.pt.y, column (int)kp.pt.x of the DISTORTED key
+ * point (truncation toward zero).  d > 0 (NaN is not, +inf is): mvDepth = d, mvuRight = kpU.pt.x - mbf / d; -1 / -1 otherwise.  A sample outside the image or a NaN
+ * coordinate reads beyond the Mat in the reference; here the key point ends unmatched and is counted in n_outside.  It cannot occur for key points that come from
+ * the extractor: they lie >= 19 pixels from every border. */
+#define CS_DEPTH_U16 0                   /* CV_16UC1, the sensor's raw units */
+#define CS_DEPTH_F32 1                   /* CV_32FC1 */
+#define CS_RGBD_MAX_KEYPOINTS 8192       /* per frame: what the close-point kernel sorts in one compute unit's LDS (8 192 64-bit keys = 64 KB) */
+#define CS_CLOSE_POINTS_NEAREST 0        /* the sorted walk of Tracking.cc:1221-1273 / :2075-2128 */
+#define CS_CLOSE_POINTS_ALL 1            /* StereoInitialization (:804-819): every z > 0 in index order, need_new ignored */
+typedef struct cs_rgbd cs_rgbd;
+/* Room for max_frames depth images of width x height and at most max_keypoints_per_frame key points per frame (CS_ERR_BAD_ARG above CS_RGBD_MAX_KEYPOINTS). */
+int cs_rgbd_create(cs_ctx *ctx, int width, int height, int max_keypoints_per_frame, int max_frames, cs_rgbd **out);
+void cs_rgbd_destroy(cs_ctx *ctx, cs_rgbd *h);
+/* n_frames depth images (host, rows stride_bytes apart, frames height * stride_bytes apart), type CS_DEPTH_U16 / CS_DEPTH_F32, stored as they are. */
+int cs_rgbd_upload_depth(cs_ctx *ctx, cs_rgbd *h, const void *depth, int type, int n_frames, long stride_bytes);
+/* The same for a batch already in device memory, frames one behind the other with dense rows (a copy on the context's stream, nothing waits; cs_orb_set_frames_device). */
+int cs_rgbd_set_depth_device(cs_ctx *ctx, cs_rgbd *h, const void *d_depth, int type, int n_frames);
+/* Frame::ComputeStereoFromRGBD for frames first_frame .. first_frame + n_frames - 1 of the extractor's last cs_orb_run against depth images 0 .. n_frames - 1 of the
+ * handle: Frame::UndistortKeyPoints (K4 = fx fy cx cy, dist5 = k1 k2 p1 p2 k3 or NULL, as cs_matcher_set_frame_from_orb) and the association, from the extractor's
+ * device key points.  CS_ERR_BAD_ARG: frames outside the run, more than the handle holds or than depth images were given, an extractor of another image size, a
+ * NULL K4, bf <= 0; CS_ERR_CAPACITY: a frame with more key points than the handle was created for.  Queued on the context's stream; the results stay on the device. */
+int cs_rgbd_from_orb(cs_ctx *ctx, cs_rgbd *h, const cs_orb *orb, int first_frame, int n_frames, const float *K4, const float *dist5, float bf, float depth_map_factor);
+/* The same over host arrays, for a caller that owns mvKeys / mvKeysUn: frame f = first[f] .. first[f + 1] (n_frames + 1 entries) of keys / keysUn.  The call waits
+ * for its uploads, so both arrays are the caller's again when it returns; the results stay on the device. */
+int cs_rgbd_from_keys(cs_ctx *ctx, cs_rgbd *h, int n_frames, const int *first, const cs_keypoint *keys, const cs_keypoint *keysUn, float bf, float depth_map_factor);
+/* mvuRight / mvDepth of the last cs_rgbd_from_*: frame f's counts[f] values at u_right[f * cap_per_frame ...] / depth[...], -1 where there is no depth;
+ * n_with_depth[f] = key points with depth, n_outside[f] (may be NULL) = key points whose sample lies outside the image.  CS_ERR_CAPACITY (nothing copied) when a
+ * frame has more than cap_per_frame key points. */
+int cs_rgbd_read(cs_ctx *ctx, cs_rgbd *h, float *u_right, float *depth, int cap_per_frame, int *counts, int *n_with_depth, int *n_outside);
+/* The same packed like cs_stereo_read_packed: frame f = first[f] .. first[f + 1].  u_right / depth NULL: only *total and first are filled; CS_ERR_CAPACITY (nothing
+ * copied) when cap_total < *total.  n_with_depth / n_outside may be NULL. */
+int cs_rgbd_read_packed(cs_ctx *ctx, cs_rgbd *h, float *u_right, float *depth, long cap_total, int *first, long *total, int *n_with_depth, int *n_outside);
+/* mvKeysUn of the last cs_rgbd_from_*, packed in the same order (cap_total records; CS_ERR_CAPACITY with nothing copied when there are more). */
+int cs_rgbd_read_keys_un(cs_ctx *ctx, cs_rgbd *h, cs_keypoint *keysUn, long cap_total);
+/* Device pointers of frame `frame`'s mvuRight / mvDepth (*n floats each) and, d_keysUn non-NULL, mvKeysUn; valid until the next call on this handle.  Work queued
+ * on the context's stream after the call sees the results. */
+int cs_rgbd_device_frame(const cs_rgbd *h, int frame, const float **d_u_right, const float **d_depth, const cs_keypoint **d_keysUn, int *n);
+/* Frame::ComputeStereoFromRGBD of one frame on the host, the same text as the kernel (the comparison side of tests and benchmarks; no context, no device). */
+int cs_rgbd_host_from_keys(const void *depth, int type, int width, int height, long stride_bytes, int n, const cs_keypoint *keys, const cs_keypoint *keysUn, float bf,
+                           float depth_map_factor, float *u_right, float *depth_out, int *n_with_depth, int *n_outside);
+
+/* The close-point rule for n_frames frames (frame f = first[f] .. first[f + 1] of depth / keysUn / need_new; at most CS_RGBD_MAX_KEYPOINTS per frame, CS_ERR_CAPACITY
+ * above).  depth = mvDepth from any source (cs_stereo_read, cs_rgbd_read), keysUn = mvKeysUn, need_new[i] = the caller's `!pMP || pMP->Observations() < 1` (may be
+ * NULL with CS_CLOSE_POINTS_ALL), Tcw = 12 floats per frame (rows of [Rcw | tcw]), K4 = fx fy cx cy, th_depth = mThDepth.  Per frame f:
+ *   n_valid[f]   key points with z > 0
+ *   order        their indices in the frame, sorted by (z, index) = sort(vDepthIdx) (CS_CLOSE_POINTS_ALL: in index order), at order[first[f] ...]
+ *   n_walked[f]  the reference's nPoints when its loop ends: the entries of `order` that were looked at
+ *   new_first    n_frames + 1 offsets into new_idx / new_x3D
+ *   new_idx      the key points a point is created for, in creation order (the order of MapPoint::mnId and of mlpTemporalPoints)
+ *   new_x3D      Frame::UnprojectStereo of each, 3 floats
+ * order, new_idx: room for first[n_frames] ints, new_x3D for 3 * first[n_frames] floats.  ctx == NULL: the same statement on the host (the comparison side).
+ * The test mCurrentFrame.N > 500 of Tracking.cc:786 and everything done with `new MapPoint` stay the caller's. */
+int cs_close_points(cs_ctx *ctx, int n_frames, const int *first, const float *depth, const cs_keypoint *keysUn, const uint8_t *need_new, const float *Tcw, const float *K4,
+                    float th_depth, int mode, int *n_valid, int *order, int *n_walked, int *new_first, int *new_idx, float *new_x3D);
+/* The same on what the last cs_rgbd_from_* left on the device (frames and order of that call; mvDepth and mvKeysUn are not copied). */
+int cs_rgbd_close_points(cs_ctx *ctx, cs_rgbd *h, const uint8_t *need_new, const float *Tcw, const float *K4, float th_depth, int mode, int *n_valid, int *order,
+                         int *n_walked, int *new_first, int *new_idx, float *new_x3D);
+
 /* ===================================================================== ORBmatcher
  * Replaces the Hamming searches of ORB_SLAM2::ORBmatcher (orb_object_slam/include/ORBmatcher.h:43-89, src/ORBmatcher.cc)
  * and the Frame grid they use (src/Frame.cc:303-318 AssignFeaturesToGrid, :404-459 GetFeaturesInArea, :525-535 PosInGrid).

@@ -39,6 +39,12 @@ struct cs_orb_pyramid_view {
 };
 int cs_orb_device_pyramid(const cs_orb *e, cs_orb_pyramid_view *out);
 
+// match.hip: the grid of the frame a matcher searches (Frame::AssignFeaturesToGrid over mvKeysUn), for klt.hip's closest-feature walk.  d_cell_recs holds KltCellRec
+// records (klt_math.h) in cell order.
+struct cs_matcher;
+struct cs_matcher_grid_view { int N; float minX, minY, wInv, hInv; const int *d_cell_start; const void *d_cell_recs; };
+int cs_matcher_device_grid(const cs_matcher *m, cs_matcher_grid_view *out);
+
 struct cs_ctx {
     int device = 0;
     hipStream_t stream = nullptr;

@@ -787,6 +787,13 @@ struct cs_match_stream {
     std::vector<int> h_tm;
     long last_q = 0, last_c = 0;
 };
+int cs_matcher_device_grid(const cs_matcher *m, cs_matcher_grid_view *out) {
+    if (!m || !out || !(m->F.wInv > 0.0f)) return CS_ERR_BAD_ARG; // (no frame was ever set: the cell lists hold nothing yet)
+    static_assert(sizeof(CellRec) == 16, "klt_math.h's KltCellRec names the same four words: x, y, id, octave");
+    *out = cs_matcher_grid_view{m->F.N, m->F.minX, m->F.minY, m->F.wInv, m->F.hInv, m->d_cell_start, m->d_cell_recs};
+    return CS_OK;
+}
+
 extern "C" {
 
 void cs_matcher_destroy(cs_ctx *ctx, cs_matcher *m) {

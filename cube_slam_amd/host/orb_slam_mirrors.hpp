@@ -8,12 +8,15 @@
 //                               ComputeStereoFromRGBD, UpdatePoseMatrices, UnprojectStereo
 //   cubeslam::ClosePoints       the creation of map points from measured depth in Tracking::StereoInitialization, UpdateLastFrame and CreateNewKeyFrame
 //                               (src/Tracking.cc:783-850, :1207-1274, :2067-2130)
+//   cubeslam::ORBmatcher        ORB_SLAM2::ORBmatcher, the dynamic-object KLT (src/ORBmatcher.cc:1524-1580): SearchByTrackingHarris over two gray frames, with the
+//                               cv::calcOpticalFlowPyrLK call of :1548 / :1620 as ORBmatcher::calcOpticalFlowPyrLK, and SearchByTracking (:1582-1725) over the current
+//                               frame's mvKeysUn
 //   cubeslam::line_lbd_detect   line_lbd_detect              (line_lbd/include/line_lbd/line_lbd_allclass.h:22-70)
 //   cubeslam::Optimizer         ORB_SLAM2::Optimizer         (orb_object_slam/include/Optimizer.h:39-62): BundleAdjustment over the
 //                               flattened graph (cs_ba_problem), PoseOptimization over flattened matches, OptimizeSim3 over flattened correspondences,
 //                               LocalBACameraPointObjectsDynamic over the flattened dynamic graph (cs_ba_dyn_problem)
-// With CUBESLAM_HOST_ONLY defined the header holds the RGB-D members of Frame and ClosePoints alone, on their path without a context (csrc/rgbd_math.h, the text the
-// kernels run; compile with -ffp-contract=off): of the C header only the types are used and nothing of the library is linked.
+// With CUBESLAM_HOST_ONLY defined the header holds the RGB-D members of Frame, ClosePoints and ORBmatcher's KLT alone, on their path without a context (csrc/rgbd_math.h
+// and csrc/klt_math.h, the text the kernels run; compile with -ffp-contract=off): of the C header only the types are used and nothing of the library is linked.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "../csrc/klt_math.h"
 #include "../csrc/rgbd_math.h"
 #ifndef CUBESLAM_HOST_ONLY
 #include "detect_3d_cuboid.hpp" // cubeslam::Context
@@ -214,6 +218,125 @@ inline ClosePointsResult ClosePoints(Context *ctx, const std::vector<float> &mvD
     r.order.resize((size_t)r.n_valid); r.new_idx.resize((size_t)n_new); r.new_x3D.resize(3 * (size_t)n_new);
     return r;
 }
+
+// The dynamic-object KLT of ORBmatcher (ORBmatcher.cc:1524-1580) over two 8-bit frames of width x height (rows `stride` bytes apart).  Without a context the host
+// runs the reference's loop (csrc/klt_math.h), byte-equal to the device.
+struct ORBmatcher {
+    struct Flow { std::vector<float> nextPts; std::vector<uint8_t> status; std::vector<float> err; }; // currobjpts (x, y per point), status, err
+    struct HarrisResult {
+        Flow flow;                    // featuresklt_thisframe and the tracker's flags for every point of LastFrame.mvKeysHarris
+        std::vector<int> kept;        // indices into LastFrame.mvKeysHarris / mvpMapPointsHarris of the points the current frame keeps, in order
+        std::vector<float> pts;       // CurrentFrame.mvKeysHarris (x, y)
+        std::vector<int> object_id;   // keypoint_associate_objectID_harris
+        int goodmatches = 0, n_mask_outside = 0;
+    };
+    // cv::calcOpticalFlowPyrLK(last, current, lastobjpts, currobjpts, status, err, cv::Size(21, 21), 3)
+    static Flow calcOpticalFlowPyrLK(Context *ctx, const uint8_t *last, const uint8_t *current, int width, int height, long stride, const std::vector<float> &lastobjpts) {
+        HarrisResult r;
+        run(ctx, last, current, width, height, stride, lastobjpts, nullptr, r);
+        return r.flow;
+    }
+    // objmask = CurrentFrame.objmask_img, width x height, dense
+    static HarrisResult SearchByTrackingHarris(Context *ctx, const uint8_t *last, const uint8_t *current, int width, int height, long stride, const std::vector<float> &lastobjpts,
+                                               const uint8_t *objmask) {
+        if (!objmask) throw std::invalid_argument("SearchByTrackingHarris: no object mask");
+        HarrisResult r;
+        run(ctx, last, current, width, height, stride, lastobjpts, objmask, r);
+        return r;
+    }
+    // ORBmatcher::SearchByTracking (ORBmatcher.cc:1582-1725).  mvKeysLast = LastFrame.mvKeys, eligible[i] = `mvpMapPoints[i] && !KeysStatic[i] && is_dynamic`,
+    // objectID = keypoint_associate_objectID; mvKeysUn and bounds (mnMinX, mnMaxX, mnMinY, mnMaxY) describe the current frame, KeysStatic / hadMapPoint may be empty.
+    struct TrackingResult {
+        std::vector<int> train_match;   // per key point of the current frame: the last frame's key index whose map point it takes, or -1
+        std::vector<int> lastptsinds;   // the last frame's key points that were tracked
+        std::vector<float> featuresklt_lastframe, featuresklt_thisframe; // (x, y) per tracked point; (0, 0) for a rejected one
+        int kltmatches = 0, goodmatches = 0, findfeaturematches = 0, uniquematches = 0;
+    };
+    static TrackingResult SearchByTracking(Context *ctx, const uint8_t *last, const uint8_t *current, int width, int height, long stride, const std::vector<cs_keypoint> &mvKeysLast,
+                                           const std::vector<uint8_t> &eligible, const std::vector<int> &objectID, int numobject, float th, const std::vector<float> &mvScaleFactors,
+                                           const std::vector<cs_keypoint> &mvKeysUn, const float bounds[4], const std::vector<uint8_t> &KeysStatic, const std::vector<uint8_t> &hadMapPoint) {
+        const int n_last = (int)mvKeysLast.size(), N = (int)mvKeysUn.size();
+        if (!last || !current || width <= KLT_WIN || height <= KLT_WIN || stride < width || eligible.size() != (size_t)n_last || objectID.size() != (size_t)n_last ||
+            mvScaleFactors.size() < 3 || (!KeysStatic.empty() && KeysStatic.size() != (size_t)N) || (!hadMapPoint.empty() && hadMapPoint.size() != (size_t)N) || !(bounds[1] > bounds[0]) ||
+            !(bounds[3] > bounds[2]))
+            throw std::invalid_argument("SearchByTracking: one entry per key point in every array, three scale factors, images of more than 21 pixels a side");
+        for (int i = 0; i < n_last; i++)
+            if (eligible[(size_t)i] && mvKeysLast[(size_t)i].octave < 3 && (mvKeysLast[(size_t)i].octave < 0 || !(mvKeysLast[(size_t)i].x - mvKeysLast[(size_t)i].x == 0) || !(mvKeysLast[(size_t)i].y - mvKeysLast[(size_t)i].y == 0)))
+                throw std::invalid_argument("SearchByTracking: a key point that is not finite or has a negative octave");
+        TrackingResult r;
+        r.train_match.assign((size_t)N + 1, -1); r.lastptsinds.assign((size_t)n_last + 1, 0);
+        r.featuresklt_lastframe.assign(2 * (size_t)n_last + 2, 0.f); r.featuresklt_thisframe.assign(2 * (size_t)n_last + 2, 0.f);
+        int counters[4] = {0, 0, 0, 0}, n = 0;
+        const cs_keypoint none{};
+        const cs_keypoint *lk = n_last ? mvKeysLast.data() : &none, *ck = N ? mvKeysUn.data() : &none;
+        const uint8_t *ks = KeysStatic.empty() ? nullptr : KeysStatic.data(), *hm = hadMapPoint.empty() ? nullptr : hadMapPoint.data();
+        if (!ctx) {
+            n = klt_search_by_tracking_host(last, current, width, height, stride, n_last, &lk->x, &lk->octave, 7, eligible.data(), objectID.data(), numobject, th, mvScaleFactors.data(),
+                                            klt_grid_params(N, bounds[0], bounds[1], bounds[2], bounds[3]), &ck->x, &ck->octave, 7, ks, hm, r.train_match.data(), r.lastptsinds.data(),
+                                            r.featuresklt_lastframe.data(), r.featuresklt_thisframe.data(), counters);
+            if (n < 0) throw std::invalid_argument("SearchByTracking: a tracked point's object id is outside [0, numobject)");
+        } else {
+#ifndef CUBESLAM_HOST_ONLY
+            std::vector<uint8_t> two((size_t)2 * width * height), desc((size_t)32 * (N > 0 ? N : 1), 0);
+            for (int f = 0; f < 2; f++)
+                for (int y = 0; y < height; y++) std::copy((f ? current : last) + (long)y * stride, (f ? current : last) + (long)y * stride + width, two.begin() + ((size_t)f * height + y) * width);
+            cs_klt *h = nullptr;
+            cs_matcher *m = nullptr;
+            check(ctx->ctx, cs_klt_create(ctx->ctx, 2, width, height, n_last > 0 ? n_last : 1, &h), "cs_klt_create");
+            int rc = cs_matcher_create(ctx->ctx, N > 0 ? N : 1, 1, 1, &m);
+            if (rc == CS_OK) rc = cs_klt_set_frames(ctx->ctx, h, 2, width, height, two.data(), width);
+            if (rc == CS_OK) rc = cs_matcher_set_frame(ctx->ctx, m, ck, desc.data(), N, bounds[0], bounds[1], bounds[2], bounds[3]);
+            if (rc == CS_OK)
+                rc = cs_match_by_tracking(ctx->ctx, m, h, 0, 1, n_last, lk, n_last ? eligible.data() : (const uint8_t *)&none, n_last ? objectID.data() : &none.octave,
+                                          numobject, th, mvScaleFactors.data(), (int)mvScaleFactors.size(), ks, hm, r.train_match.data(), &n, r.lastptsinds.data(),
+                                          r.featuresklt_lastframe.data(), r.featuresklt_thisframe.data(), counters);
+            cs_matcher_destroy(ctx->ctx, m);
+            cs_klt_destroy(ctx->ctx, h);
+            check(ctx->ctx, rc, "cs_match_by_tracking");
+#else
+            throw std::runtime_error("SearchByTracking: built without the library");
+#endif
+        }
+        r.train_match.resize((size_t)N); r.lastptsinds.resize((size_t)n); r.featuresklt_lastframe.resize(2 * (size_t)n); r.featuresklt_thisframe.resize(2 * (size_t)n);
+        r.kltmatches = counters[0]; r.goodmatches = counters[1]; r.findfeaturematches = counters[2]; r.uniquematches = counters[3];
+        return r;
+    }
+
+  private:
+    static void run(Context *ctx, const uint8_t *last, const uint8_t *current, int width, int height, long stride, const std::vector<float> &pts, const uint8_t *mask,
+                    HarrisResult &r) {
+        const int n = (int)(pts.size() / 2);
+        if (!last || !current || width <= KLT_WIN || height <= KLT_WIN || stride < width || pts.size() % 2) throw std::invalid_argument("ORBmatcher KLT: images of more than 21 pixels a side and (x, y) pairs");
+        for (float v : pts) if (!(v - v == 0)) throw std::invalid_argument("ORBmatcher KLT: a point that is not finite");
+        r.flow.nextPts.assign(2 * (size_t)n + 2, 0.f); r.flow.status.assign((size_t)n + 1, 0); r.flow.err.assign((size_t)n + 1, 0.f);
+        r.kept.assign((size_t)n + 1, 0); r.pts.assign(2 * (size_t)n + 2, 0.f); r.object_id.assign((size_t)n + 1, 0);
+        const int first[2] = {0, n}, pp[1] = {0}, pn[1] = {1};
+        std::vector<uint8_t> two((size_t)2 * width * height); // the two frames one behind the other, dense
+        for (int f = 0; f < 2; f++)
+            for (int y = 0; y < height; y++) std::copy((f ? current : last) + (long)y * stride, (f ? current : last) + (long)y * stride + width, two.begin() + ((size_t)f * height + y) * width);
+        if (!ctx) {
+            klt_track_host(two.data(), 2, width, height, width, (long)width * height, 1, pp, pn, first, pts.data(), r.flow.nextPts.data(), r.flow.status.data(), r.flow.err.data());
+            if (mask) r.goodmatches = klt_harris_select_host(n, r.flow.nextPts.data(), r.flow.status.data(), mask, width, height, r.kept.data(), r.pts.data(), r.object_id.data(), &r.n_mask_outside);
+        } else {
+#ifndef CUBESLAM_HOST_ONLY
+            cs_klt *h = nullptr;
+            check(ctx->ctx, cs_klt_create(ctx->ctx, 2, width, height, n > 0 ? n : 1, &h), "cs_klt_create");
+            int rc = cs_klt_set_frames(ctx->ctx, h, 2, width, height, two.data(), width);
+            int kf[2] = {0, 0};
+            if (rc == CS_OK)
+                rc = mask ? cs_match_by_tracking_harris(ctx->ctx, h, 1, pp, pn, first, pts.data(), mask, r.flow.nextPts.data(), r.flow.status.data(), r.flow.err.data(), kf, r.kept.data(),
+                                                        r.pts.data(), r.object_id.data(), &r.goodmatches, &r.n_mask_outside)
+                          : cs_klt_track(ctx->ctx, h, 1, pp, pn, first, pts.data(), r.flow.nextPts.data(), r.flow.status.data(), r.flow.err.data());
+            cs_klt_destroy(ctx->ctx, h);
+            check(ctx->ctx, rc, "ORBmatcher KLT");
+#else
+            throw std::runtime_error("ORBmatcher KLT: built without the library");
+#endif
+        }
+        r.flow.nextPts.resize(2 * (size_t)n); r.flow.status.resize((size_t)n); r.flow.err.resize((size_t)n);
+        r.kept.resize((size_t)r.goodmatches); r.pts.resize(2 * (size_t)r.goodmatches); r.object_id.resize((size_t)r.goodmatches);
+    }
+};
 
 #ifndef CUBESLAM_HOST_ONLY
 class line_lbd_detect {

@@ -44,6 +44,20 @@ class ORBmatcher:
         self.N = n.value
         return (out[:n.value].copy() if read_keys else None), tuple(float(b) for b in bounds)
 
+    def SearchByTrackingHarris(self, last_gray, current_gray, mvKeysHarris_pt, objmask_img):
+        """ORBmatcher::SearchByTrackingHarris (ORBmatcher.cc:1524-1580) for one pair of gray frames on this matcher's context: a dict of kept (indices into the last
+        frame's mvKeysHarris / mvpMapPointsHarris), pts (the current frame's mvKeysHarris), object_id, goodmatches, n_mask_outside, featuresklt_lastframe /
+        featuresklt_thisframe, status, err.  Many pairs in one call: cube_slam_amd.klt.KLTTracker.search_by_tracking_harris."""
+        from .klt import SearchByTrackingHarris
+        return SearchByTrackingHarris(np.stack([np.asarray(last_gray, np.uint8), np.asarray(current_gray, np.uint8)]), [(0, 1)], [mvKeysHarris_pt], [objmask_img], ctx=self.ctx)[0]
+
+    def SearchByTracking(self, last_gray, current_gray, last_keys, eligible, object_id, numobject, th, scale_factors, keys_static=None, had_map_point=None, tracker=None,
+                         frames=(0, 1)):
+        """ORBmatcher::SearchByTracking (ORBmatcher.cc:1582-1725) against this matcher's frame (the current frame): see cube_slam_amd.klt.SearchByTracking."""
+        from .klt import SearchByTracking
+        return SearchByTracking(last_gray, current_gray, last_keys, eligible, object_id, numobject, th, scale_factors, None, None, keys_static, had_map_point, matcher=self,
+                                tracker=tracker, frames=frames)
+
     def last_candidate_stats(self):
         q, c = C.c_int(), C.c_long()
         if lib().cs_matcher_last_counts(self._m, C.byref(q), C.byref(c)) != 0:

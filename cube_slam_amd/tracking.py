@@ -203,5 +203,13 @@ class Tracking:
         r = ClosePoints(mvDepth, keysUn, None, Tcw, K4, 0.0, CS_CLOSE_POINTS_ALL, ctx=None if host else self.ctx)
         return r["new_idx"], r["new_x3D"]
 
+    def TrackHarrisFeatures(self, last_gray, current_gray, mvKeysHarris_pt, mvpMapPointsHarris, objmask_img, ctx=None):
+        """The dynamic branch of Tracking::TrackWithMotionModel with use_dynamic_klt_features (Tracking.cc:1308-1311): ORBmatcher::SearchByTrackingHarris from the
+        last frame to the current one.  Returns the current frame's (mvKeysHarris pt, mvpMapPointsHarris, keypoint_associate_objectID_harris) and the search's dict.
+        ctx=None: on the host."""
+        from .klt import SearchByTrackingHarris
+        r = SearchByTrackingHarris(np.stack([np.asarray(last_gray, np.uint8), np.asarray(current_gray, np.uint8)]), [(0, 1)], [mvKeysHarris_pt], [objmask_img], ctx=ctx)[0]
+        return r["pts"], np.asarray(mvpMapPointsHarris)[r["kept"]], r["object_id"], r
+
     def close(self):
         self.matcher.close()

@@ -309,6 +309,47 @@ int cs_close_points(cs_ctx *ctx, int n_frames, const int *first, const float *de
 int cs_rgbd_close_points(cs_ctx *ctx, cs_rgbd *h, const uint8_t *need_new, const float *Tcw, const float *K4, float th_depth, int mode, int *n_valid, int *order,
                          int *n_walked, int *new_first, int *new_idx, float *new_x3D);
 
+/* ===================================================================== dynamic-object KLT
+ * Replaces cv::calcOpticalFlowPyrLK(LastFrame.raw_img, CurrentFrame.raw_img, lastobjpts, currobjpts, status, err, cv::Size(21, 21), 3) of
+ * ORBmatcher::SearchByTrackingHarris (orb_object_slam/src/ORBmatcher.cc:1548) and ORBmatcher::SearchByTracking (:1620), for many frame pairs in one call, and the
+ * selection pass of SearchByTrackingHarris (:1556-1579).  OpenCV is not part of the reference tree: the function is a stated definition (the plain
+ * C++ branches of OpenCV 3.x lkpyramid.cpp), and every result equals that statement bit for bit.
+ * GPU: pyramid and Scharr derivatives of every frame once, levels resident with their 21-pixel pads; all points of all pairs in one launch.
+ * A handle holds at most max_frames 8-bit images of at most max_width x max_height and tracks at most max_points points per call. */
+typedef struct cs_klt cs_klt;
+int cs_klt_create(cs_ctx *ctx, int max_frames, int max_width, int max_height, int max_points, cs_klt **out);
+void cs_klt_destroy(cs_ctx *ctx, cs_klt *h);
+/* buildOpticalFlowPyramid and calcSharrDeriv for n_frames images of width x height (both > 21; rows stride_bytes apart, frame f at gray + f * height * stride_bytes).
+ * A later call may bring fewer frames or another size within the capacity (CS_ERR_CAPACITY beyond it; the handle keeps its frames then).  A call that fails with
+ * CS_ERR_HIP leaves the handle without frames. */
+int cs_klt_set_frames(cs_ctx *ctx, cs_klt *h, int n_frames, int width, int height, const uint8_t *gray, long stride_bytes);
+/* The levels the pyramids hold: 4, or fewer where building stopped at the first level of 21 pixels or less a side (0: no frames are set). */
+int cs_klt_levels(const cs_klt *h);
+/* One resident level as the tracker reads it, for inspection: (w + 42) x (h + 42) bytes with the REFLECT_101 pad, and as many (Ix, Iy) int16 pairs with the
+ * constant pad; either pointer may be NULL. */
+int cs_klt_read_level(cs_ctx *ctx, cs_klt *h, int frame, int level, uint8_t *image, int16_t *deriv);
+/* The calcOpticalFlowPyrLK call of :1548 / :1620 for n_pairs pairs: pair p tracks the points first[p] .. first[p + 1] (x, y floats in prev_pts) from frame
+ * pair_prev[p] to frame pair_next[p] of the last cs_klt_set_frames.  A frame may be `next` of one pair and `prev` of another; an empty pair is legal.
+ * next_pts (2 floats), status and err per point as the OpenCV function returns them.  Points that are not finite: CS_ERR_BAD_ARG. */
+int cs_klt_track(cs_ctx *ctx, cs_klt *h, int n_pairs, const int *pair_prev, const int *pair_next, const int *first, const float *prev_pts, float *next_pts, uint8_t *status,
+                 float *err);
+/* The same statement on the host, without a context, over the images themselves (the comparison side). */
+int cs_klt_track_host(const uint8_t *gray, int n_frames, int width, int height, long stride_bytes, int n_pairs, const int *pair_prev, const int *pair_next, const int *first,
+                      const float *prev_pts, float *next_pts, uint8_t *status, float *err);
+/* ORBmatcher::SearchByTrackingHarris (ORBmatcher.cc:1524-1580) for n_pairs pairs.  last_pts = pt of LastFrame.mvKeysHarris (= featuresklt_lastframe), masks = the
+ * pairs' CurrentFrame.objmask_img, n_pairs dense images of the frames' size.  Outputs: this_pts / status / err = featuresklt_thisframe and the tracker's flags for
+ * every point; per pair p the survivors in index order at kept_first[p] .. kept_first[p + 1]: kept = the index within the pair (of LastFrame.mvpMapPointsHarris),
+ * kept_pts = the new mvKeysHarris, object_id = maskval - 1; goodmatches[p].  The mask is read as cv::Mat::at<uchar>(Point2f) reads it, at
+ * data[cvRound(y) * cols + cvRound(x)], which is the next row's first pixel when x rounds to cols.  DEVIATION: where that index is >= rows * cols the reference
+ * reads beyond the image; here the point is dropped and counted in n_mask_outside[p] (may be NULL).  kept, object_id: room for first[n_pairs] ints. */
+int cs_match_by_tracking_harris(cs_ctx *ctx, cs_klt *h, int n_pairs, const int *pair_prev, const int *pair_next, const int *first, const float *last_pts, const uint8_t *masks,
+                                float *this_pts, uint8_t *status, float *err, int *kept_first, int *kept, float *kept_pts, int *object_id, int *goodmatches,
+                                int *n_mask_outside);
+int cs_match_by_tracking_harris_host(const uint8_t *gray, int n_frames, int width, int height, long stride_bytes, int n_pairs, const int *pair_prev, const int *pair_next,
+                                     const int *first, const float *last_pts, const uint8_t *masks, float *this_pts, uint8_t *status, float *err, int *kept_first, int *kept,
+                                     float *kept_pts, int *object_id, int *goodmatches, int *n_mask_outside);
+/* (cs_match_by_tracking, ORBmatcher::SearchByTracking over the same tracker, is declared behind cs_matcher below.) */
+
 /* ===================================================================== ORBmatcher
  * Replaces the Hamming searches of ORB_SLAM2::ORBmatcher (orb_object_slam/include/ORBmatcher.h:43-89, src/ORBmatcher.cc)
  * and the Frame grid they use (src/Frame.cc:303-318 AssignFeaturesToGrid, :404-459 GetFeaturesInArea, :525-535 PosInGrid).
@@ -365,6 +406,27 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
                                   float th, int check_orientation, int *train_match, int *nmatches);
 /* queries and window candidates of the last call (roofline accounting) */
 int cs_match_stream_last_counts(const cs_match_stream *m, long *queries, long *candidates);
+/* ORBmatcher::SearchByTracking (ORBmatcher.cc:1582-1725) for one pair.  m: a matcher whose frame is the CURRENT frame (cs_matcher_set_frame*: mvKeysUn and mGrid);
+ * h: a KLT handle that holds both gray frames (cs_klt_set_frames), last_frame / current_frame their indices.  Per key point i of the last frame: last_keys[i] =
+ * LastFrame.mvKeys[i] (pt and octave are read), eligible[i] = the caller's `mvpMapPoints[i] && !KeysStatic[i] && mvpMapPoints[i]->is_dynamic`, object_id[i] =
+ * keypoint_associate_objectID[i]; numobject, th, scale_factors = CurrentFrame.mvScaleFactors (n_levels >= 3 entries).  For the current frame, N entries each or NULL:
+ * keys_static = KeysStatic (NULL: empty), had_map_point[j] = `mvpMapPoints[j] != NULL` before the call.  The device runs the octave < 3 selection and its ordered
+ * compaction (:1591-1603), the optical flow, the per-object mean flow with its float sums in index order (:1629-1664), the direction test (:1682-1689),
+ * Frame::GetCloestFeaturesInArea (Frame.cc:461-523: cells ix outer, iy inner, strict <, levels [octave, 2]), the KeysStatic rejection (:1699) and the assignment (:1707),
+ * which is sequential in the reference: the last i keeps a key point.  Outputs: train_match[N] = the last-frame key index whose map point key point j takes, or -1;
+ * *n_tracked = the points selected; sel = lastptsinds, klt_last / klt_this = featuresklt_lastframe / featuresklt_thisframe ((0, 0) for rejected points), room for
+ * n_last entries each; counters = kltmatches, goodmatches, findfeaturematches, uniquematches (key points that had no map point when first assigned).
+ * A tracked point whose object id is outside [0, numobject) indexes out of bounds in the reference: CS_ERR_BAD_ARG.  An object whose mean flow is exactly zero gets
+ * 0 / 0 as its direction, as in the reference; only the norm is read then.  *n_tracked above the KLT handle's max_points: CS_ERR_CAPACITY; a matcher without a frame:
+ * CS_ERR_BAD_ARG. */
+int cs_match_by_tracking(cs_ctx *ctx, cs_matcher *m, cs_klt *h, int last_frame, int current_frame, int n_last, const cs_keypoint *last_keys, const uint8_t *eligible,
+                         const int *object_id, int numobject, float th, const float *scale_factors, int n_levels, const uint8_t *keys_static, const uint8_t *had_map_point,
+                         int *train_match, int *n_tracked, int *sel, float *klt_last, float *klt_this, int *counters);
+/* The same statement on the host, without a context: the two gray frames and the current frame's mvKeysUn with its bounds (mnMinX, mnMaxX, mnMinY, mnMaxY) directly. */
+int cs_match_by_tracking_host(const uint8_t *last_gray, const uint8_t *current_gray, int width, int height, long stride_bytes, int n_last, const cs_keypoint *last_keys,
+                              const uint8_t *eligible, const int *object_id, int numobject, float th, const float *scale_factors, int n_levels, const cs_keypoint *keysUn, int N,
+                              float minX, float maxX, float minY, float maxY, const uint8_t *keys_static, const uint8_t *had_map_point, int *train_match, int *n_tracked, int *sel,
+                              float *klt_last, float *klt_this, int *counters);
 /* ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*>&, th) (:50-142). */
 int cs_match_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_xy, const float *view_cos, const int *pred_level,
                        const uint8_t *in_view, const uint8_t *blocks, const uint8_t *mp_desc, const float *scale_factors, int n_levels,

@@ -1,0 +1,245 @@
+"""GPU parity of the dynamic-object KLT (cs_klt_*, cv::calcOpticalFlowPyrLK of ORBmatcher.cc:1548 / :1620) and of ORBmatcher::SearchByTrackingHarris
+(cs_match_by_tracking_harris, ORBmatcher.cc:1524-1580) through the C-ABI against tests/klt_restatement.py, byte for byte on next_pts, status, err and every search
+output.  No tolerance anywhere: the sampling is integer arithmetic, the 441-term float sums are added in window order, and every other statement is one float
+operation.  tests/test_klt_patterns.py asserts on the restatement that the inputs take every branch."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from cube_slam_amd import _lib
+from cube_slam_amd.klt import KLTTracker, SearchByTrackingHarris, calcOpticalFlowPyrLK
+from tests import klt_patterns as kp
+from tests import klt_restatement as kr
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+BAD_ARG, CAPACITY = -2, -4
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+@pytest.mark.parametrize("w,h", kp.SIZES)
+def test_track_equals_restatement(ctx, w, h):
+    """Two pairs over three frames (frame 1 is `next` of the first and `prev` of the second) at every image size; the resident levels equal the restatement's too."""
+    c = kp.lk_case(w, h)
+    t = KLTTracker(3, w, h, 64, ctx=ctx)
+    try:
+        t.set_frames(c["frames"])
+        assert t.levels == kr.n_levels(w, h)
+        pyr = kr.Pyramid(c["frames"][1])
+        for level in range(t.levels):
+            img, der = t.read_level(1, level)
+            assert np.array_equal(img, pyr.padded[level]) and np.array_equal(der, pyr.deriv[level]), level
+        got = t.track(c["pairs"], c["pts"])
+        for p, (g, want) in enumerate(zip(got, c["want"])):
+            assert kp.same_track(g, want), (p, np.flatnonzero((g[0] != want[0]).any(1) | (g[1] != want[1]) | (g[2] != want[2])))
+            assert 0 < want[1].sum() < len(want[1])
+        one = t.track(c["pairs"][1:], c["pts"][1:])  # one pair alone
+        assert kp.same_track(one[0], c["want"][1])
+    finally:
+        t.close()
+
+
+def test_err_stage_rejection(ctx):
+    c = kp.edge_case()
+    assert sum("err_outside" in s for s in c["trace"]) >= 1
+    got = calcOpticalFlowPyrLK(c["frames"], c["pairs"], c["pts"], ctx=ctx)
+    assert kp.same_track(got[0], c["want"][0])
+
+
+@pytest.mark.parametrize("counts", kp.BATCH_COUNTS)
+def test_mixed_point_counts_in_one_call(ctx, counts):
+    """Five pairs with 0, 1, 63, 64, 65 and 130 points among them: a workgroup of four points straddles every seam between two pairs."""
+    pairs, pts, want = kp.batch_call(counts)
+    got = calcOpticalFlowPyrLK(kp.batch_case()["frames"], pairs, pts, ctx=ctx)
+    assert [len(g[0]) for g in got] == counts
+    for p, (g, w) in enumerate(zip(got, want)):
+        assert kp.same_track(g, w), p
+
+
+def test_handle_reuse_and_errors(ctx):
+    """set_frames again with fewer frames and another size within the capacity; capacity and argument errors return their codes and leave the handle usable."""
+    big, small = kp.lk_case(169, 169), kp.lk_case(64, 48)
+    t = KLTTracker(3, 169, 169, 64, ctx=ctx)
+    L = _lib.lib()
+    try:
+        t.set_frames(big["frames"])
+        assert t.levels == 4 and kp.same_track(t.track(big["pairs"][:1], big["pts"][:1])[0], big["want"][0])
+        t.set_frames(small["frames"][1:])  # two frames of 64 x 48: the pair (1, 2) is now (0, 1)
+        assert t.levels == 2 and kp.same_track(t.track([(0, 1)], small["pts"][1:])[0], small["want"][1])
+        g = np.zeros((4, 48, 64), np.uint8)
+        args = lambda a: (ctx.ptr, t._h, a.shape[0], a.shape[2], a.shape[1], _p(a, C.c_uint8), C.c_long(a.shape[2]))  # noqa: E731
+        assert L.cs_klt_set_frames(*args(g)) == CAPACITY                                  # more frames than the handle holds
+        assert L.cs_klt_set_frames(*args(np.zeros((1, 48, 170), np.uint8))) == CAPACITY   # a wider image
+        assert L.cs_klt_set_frames(*args(np.zeros((1, 21, 64), np.uint8))) == BAD_ARG     # no window fits
+        assert L.cs_klt_set_frames(ctx.ptr, t._h, 1, 64, 48, None, C.c_long(64)) == BAD_ARG
+        nxt, st, er = np.zeros((70, 2), f32), np.zeros(70, np.uint8), np.zeros(70, f32)
+        pts = np.full((70, 2), 20, f32)
+
+        def track(pp, pn, first, q):
+            pp, pn, first = np.array(pp, np.int32), np.array(pn, np.int32), np.array(first, np.int32)
+            return L.cs_klt_track(ctx.ptr, t._h, len(pp), _p(pp, C.c_int), _p(pn, C.c_int), _p(first, C.c_int), _p(q, C.c_float), _p(nxt, C.c_float), _p(st, C.c_uint8),
+                                  _p(er, C.c_float))
+        assert track([0], [1], [0, 65], pts) == CAPACITY          # more points than the handle was created for
+        assert track([0], [2], [0, 4], pts) == BAD_ARG            # frame 2 is no longer set
+        assert track([0], [1], [1, 4], pts) == BAD_ARG and track([0, 1], [1, 0], [0, 4, 3], pts) == BAD_ARG
+        bad = pts.copy()
+        bad[3, 1] = np.nan
+        assert track([0], [1], [0, 4], bad) == BAD_ARG
+        assert L.cs_klt_create(ctx.ptr, 1, 21, 64, 8, C.byref(C.c_void_p())) == BAD_ARG
+        assert kp.same_track(t.track([(0, 1)], small["pts"][1:])[0], small["want"][1])  # ... and the handle still works, on the frames it had
+        empty = t.track([(0, 1), (1, 0)], [np.zeros((0, 2), f32)] * 2)
+        assert [len(e[0]) for e in empty] == [0, 0]
+    finally:
+        t.close()
+
+
+def test_search_by_tracking_harris_end_to_end(ctx):
+    c = kp.harris_case()
+    assert kp.HARRIS_BRANCHES <= set().union(*c["trace"]) and c["want"][0]["n_mask_outside"] >= 1 and 7 - 1 in c["want"][0]["object_id"]
+    got = SearchByTrackingHarris(c["frames"], c["pairs"], c["pts"], c["masks"], ctx=ctx)
+    for p, (g, w) in enumerate(zip(got, c["want"])):
+        assert kp.same_harris(g, w), p
+        assert 0 < w["goodmatches"] < len(c["pts"][p])
+    # one pair alone, and a pair without points between two others
+    t = KLTTracker(3, 96, 64, 128, ctx=ctx)
+    try:
+        t.set_frames(c["frames"])
+        got = t.search_by_tracking_harris([(0, 1), (2, 0), (1, 2)], [c["pts"][0], np.zeros((0, 2), f32), c["pts"][1]], [c["masks"][0], c["masks"][0], c["masks"][1]])
+        assert kp.same_harris(got[0], c["want"][0]) and kp.same_harris(got[2], c["want"][1]) and got[1]["goodmatches"] == 0 and len(got[1]["kept"]) == 0
+        with pytest.raises(_lib.CubeSlamError, match="CS_ERR_CAPACITY"):
+            t.search_by_tracking_harris([(0, 1)], [np.full((129, 2), 30, f32)], c["masks"][:1])
+        assert kp.same_harris(t.search_by_tracking_harris(c["pairs"][1:], c["pts"][1:], c["masks"][1:])[0], c["want"][1])
+    finally:
+        t.close()
+
+
+def _tracking_device(ctx, c, keys_static, had_map_point, **kw):
+    from cube_slam_amd import SearchByTracking
+    from cube_slam_amd.matcher import ORBmatcher
+    lk, ck = kp.tracking_keys(c)
+    m = ORBmatcher(0.9, True, ctx=ctx, max_keypoints=1024, max_queries=1024, max_candidates=4096)
+    try:
+        m.set_frame(ck, np.zeros((len(ck), 32), np.uint8), c["bounds"])
+        return SearchByTracking(c["frames"][0], c["frames"][1], lk, c["eligible"], c["object_id"], c["numobject"], kp.TH, kp.SCALE_FACTORS, None, None, keys_static, had_map_point,
+                                matcher=m, **kw)
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("case", ["still", "moving"])
+def test_search_by_tracking_on_a_set_frame(ctx, case):
+    """cs_match_by_tracking on a matcher set by cs_matcher_set_frame: the tie, the two claims, the zero mean flow, the static and missing features (still) and the
+    direction rejection (moving), with and without KeysStatic / earlier map points."""
+    c = kp.tracking_still_case() if case == "still" else kp.tracking_moving_case()
+    assert kp.same_tracking(_tracking_device(ctx, c, c["keys_static"], c["had_map_point"]), c["want"])
+    bare = kr.search_by_tracking(c["frames"][0], c["frames"][1], c["last_pt"], c["last_octave"], c["eligible"], c["object_id"], c["numobject"], kp.TH, kp.SCALE_FACTORS,
+                                 kr.FrameGrid(c["cur_pt"], c["cur_octave"], c["bounds"]))
+    assert kp.same_tracking(_tracking_device(ctx, c, None, None), bare)
+
+
+def test_search_by_tracking_errors_leave_the_handles_usable(ctx):
+    c = dict(kp.tracking_still_case())
+    good_ids = c["object_id"]
+    c["object_id"] = np.where(np.arange(len(good_ids)) == 3, 2, good_ids).astype(np.int32)  # a tracked point of object 2 with numobject = 2
+    t = KLTTracker(2, 240, 120, 4, ctx=ctx)  # room for four tracked points
+    try:
+        t.set_frames(c["frames"])
+        with pytest.raises(_lib.CubeSlamError, match="CS_ERR_CAPACITY"):
+            _tracking_device(ctx, c, None, None, tracker=t)                                # nine are selected
+        few = dict(c, eligible=(np.arange(len(good_ids)) < 4).astype(np.uint8))
+        with pytest.raises(_lib.CubeSlamError, match="CS_ERR_BAD_ARG"):
+            _tracking_device(ctx, few, None, None, tracker=t)                              # point 3's object id
+        few["object_id"] = good_ids
+        got = _tracking_device(ctx, few, c["keys_static"], c["had_map_point"], tracker=t)  # ... and the same handle then answers
+        want = kr.search_by_tracking(c["frames"][0], c["frames"][1], c["last_pt"], c["last_octave"], few["eligible"], good_ids, 2, kp.TH, kp.SCALE_FACTORS,
+                                     kr.FrameGrid(c["cur_pt"], c["cur_octave"], c["bounds"]), c["keys_static"], c["had_map_point"])
+        assert kp.same_tracking(got, want) and got["kltmatches"] == 4
+        with pytest.raises(_lib.CubeSlamError, match="CS_ERR_BAD_ARG"):
+            _tracking_device(ctx, few, None, None, tracker=t, frames=(0, 2))               # no such frame
+    finally:
+        t.close()
+
+
+def test_search_by_tracking_on_a_frame_from_orb(ctx):
+    """cs_match_by_tracking on a matcher set by cs_matcher_set_frame_from_orb: the current frame's key points never leave the device.  Two 640 x 480 frames, the second the
+    first moved by (3, 2); the last frame's key points are the extractor's own."""
+    from cube_slam_amd import SearchByTracking, synth
+    from cube_slam_amd.matcher import ORBmatcher
+    from cube_slam_amd.orb import ORBextractor
+    a = synth.cuboid_scene(synth.SEED, n_boxes=3)["gray"]
+    b = np.roll(a, (2, 3), (0, 1))
+    ext = ORBextractor(500, 1.2, 8, 20, 7, 640, 480, max_frames=2, ctx=ctx)
+    m = ORBmatcher(0.9, True, ctx=ctx)
+    try:
+        ext.upload(np.stack([a, b]))
+        ext.run()
+        res = ext.read()
+        last_keys = res[0][0][::8][:40]  # forty of the last frame's key points, every octave among them
+        K4 = np.array([500.0, 500.0, 320.0, 240.0], np.float32)
+        keysUn, bounds = m.set_frame_from_orb(ext, 1, K4, None, width=640, height=480)
+        rng = np.random.default_rng(5)
+        eligible, obj = (rng.random(len(last_keys)) < 0.8).astype(np.uint8), rng.integers(0, 3, len(last_keys)).astype(np.int32)
+        ks, hm = (rng.random(len(keysUn)) < 0.3).astype(np.uint8), (rng.random(len(keysUn)) < 0.5).astype(np.uint8)
+        got = SearchByTracking(a, b, last_keys, eligible, obj, 3, kp.TH, kp.SCALE_FACTORS, None, None, ks, hm, matcher=m)
+        want = kr.search_by_tracking(a, b, np.stack([last_keys["x"], last_keys["y"]], 1), last_keys["octave"], eligible, obj, 3, kp.TH, kp.SCALE_FACTORS,
+                                     kr.FrameGrid(np.stack([keysUn["x"], keysUn["y"]], 1), keysUn["octave"], bounds), ks, hm)
+        assert kp.same_tracking(got, want)
+        assert want["findfeaturematches"] >= 5 and 0 < len(want["lastptsinds"]) < len(last_keys)
+    finally:
+        m.close()
+        ext.close()
+
+
+def test_matcher_and_tracking_methods(ctx):
+    """ORBmatcher.SearchByTrackingHarris / .SearchByTracking and Tracking.TrackHarrisFeatures are the same calls."""
+    from cube_slam_amd.matcher import ORBmatcher
+    from cube_slam_amd.tracking import Tracking
+    c, s = kp.harris_case(), kp.tracking_still_case()
+    m = ORBmatcher(0.9, True, ctx=ctx, max_keypoints=1024, max_queries=1024, max_candidates=4096)
+    try:
+        assert kp.same_harris(m.SearchByTrackingHarris(c["frames"][1], c["frames"][2], c["pts"][1], c["masks"][1]), c["want"][1])
+        lk, ck = kp.tracking_keys(s)
+        m.set_frame(ck, np.zeros((len(ck), 32), np.uint8), s["bounds"])
+        got = m.SearchByTracking(s["frames"][0], s["frames"][1], lk, s["eligible"], s["object_id"], s["numobject"], kp.TH, kp.SCALE_FACTORS, s["keys_static"], s["had_map_point"])
+        assert kp.same_tracking(got, s["want"])
+    finally:
+        m.close()
+    ids = np.arange(100, 100 + len(c["pts"][0]))
+    pts, mps, obj, r = object.__new__(Tracking).TrackHarrisFeatures(c["frames"][0], c["frames"][1], c["pts"][0], ids, c["masks"][0], ctx=ctx)
+    assert kp.same_harris(r, c["want"][0]) and np.array_equal(mps, ids[c["want"][0]["kept"]]) and np.array_equal(obj, c["want"][0]["object_id"])
+
+
+def test_selection_kernels_past_one_wave_and_one_pass(ctx):
+    """A Harris pair of 330 points and a SearchByTracking call with 700 last-frame and 600 current key points, 318 of them tracked: the ordered compactions carry
+    counts across waves and across passes of 256, the beyond-the-mask count comes from every wave (tests/test_klt_patterns.py asserts the placement)."""
+    c = kp.harris_large_case()
+    got = SearchByTrackingHarris(c["frames"], c["pairs"], c["pts"], c["masks"], ctx=ctx)[0]
+    assert kp.same_harris(got, c["want"][0]) and got["n_mask_outside"] == len(kp.LARGE_HARRIS_SPECIAL)
+    # ... and between two other pairs, so that the pair's slots do not start at 0
+    h = kp.harris_case()
+    t = KLTTracker(3, 96, 64, 512, ctx=ctx)
+    try:
+        t.set_frames(h["frames"])
+        three = t.search_by_tracking_harris([(0, 1), (0, 1), (1, 2)], [h["pts"][0], c["pts"][0], h["pts"][1]], [h["masks"][0], c["masks"][0], h["masks"][1]])
+        assert kp.same_harris(three[0], h["want"][0]) and kp.same_harris(three[1], c["want"][0]) and kp.same_harris(three[2], h["want"][1])
+    finally:
+        t.close()
+    big = kp.tracking_large_case()
+    assert kp.same_tracking(_tracking_device(ctx, big, big["keys_static"], big["had_map_point"]), big["want"])
+
+
+def test_search_by_tracking_needs_a_frame_in_the_matcher(ctx):
+    from cube_slam_amd import SearchByTracking
+    from cube_slam_amd.matcher import ORBmatcher
+    c = kp.tracking_still_case()
+    lk, _ = kp.tracking_keys(c)
+    m = ORBmatcher(0.9, True, ctx=ctx, max_keypoints=64, max_queries=64, max_candidates=64)  # no set_frame yet
+    try:
+        with pytest.raises(_lib.CubeSlamError, match="CS_ERR_BAD_ARG"):
+            SearchByTracking(c["frames"][0], c["frames"][1], lk, c["eligible"], c["object_id"], c["numobject"], kp.TH, kp.SCALE_FACTORS, None, None, matcher=m)
+    finally:
+        m.close()

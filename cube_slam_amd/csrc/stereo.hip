@@ -161,7 +161,9 @@ __global__ void __launch_bounds__(64) stereo_sad(StereoP P, const PairRec *__res
                     if (sDist[i] < bestDist) { bestDist = sDist[i]; bestincR = i - SL; }
                 if (bestincR != -SL && bestincR != SL) {
                     const float dist1 = (float)sDist[SL + bestincR - 1], dist2 = (float)sDist[SL + bestincR], dist3 = (float)sDist[SL + bestincR + 1];
-                    const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2)); // :745; 0 / 0 and x / 0 flow on as NaN / inf
+                    const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2)); // :745
+                    // The test of :748 is kept as written but cannot fail: dist2 is the strict first minimum of integers, so dist1 > dist2 and dist3 >= dist2, the
+                    // denominator is >= 2 and |dist1 - dist3| <= dist1 + dist3 - 2 * dist2 (all exact in float, below 2^24): |deltaR| <= 0.5, never NaN or inf.
                     if (!(deltaR < -1 || deltaR > 1)) {
                         float bestuR = P.scale[lv] * ((float)sr + (float)bestincR + deltaR);
                         float disparity = uL - bestuR;
@@ -235,10 +237,52 @@ struct cs_stereo {
     int *d_sad = nullptr, *d_best = nullptr, *d_n_matched = nullptr, *d_lvl = nullptr;
     RightRec *d_rec = nullptr;
     PairRec *d_pairs = nullptr;
+    cs_keypoint *d_keys_l = nullptr, *d_keys_r = nullptr; // key points and descriptors of cs_stereo_match_from_keys, cap * max_pairs each, allocated by its first call
+    unsigned long long *d_desc_l = nullptr, *d_desc_r = nullptr; // (cs_stereo_match_from_orb reads the extractors')
     // host: the last call
     int n_pairs = 0;
     std::vector<PairRec> pairs;
 };
+
+namespace {
+constexpr float MAX_COORD = 16777216.0f; // 2^24
+
+// The two extractors' resident pyramids, and the geometry checks both entries share.
+int pyramids(cs_ctx *ctx, const char *who, const cs_orb *left, int left_first, const cs_orb *right, int right_first, int n_pairs, cs_orb_pyramid_view *VL, cs_orb_pyramid_view *VR) {
+    if (cs_orb_device_pyramid(left, VL) != CS_OK || cs_orb_device_pyramid(right, VR) != CS_OK) return CS_ERR_BAD_ARG;
+    if (left_first + n_pairs > VL->n_frames || right_first + n_pairs > VR->n_frames) { ctx->err = std::string(who) + ": pairs outside the extractor's last run"; return CS_ERR_BAD_ARG; }
+    if (VL->W != VR->W || VL->H != VR->H || VL->nlevels != VR->nlevels || VL->scale_factor != VR->scale_factor) {
+        ctx->err = std::string(who) + ": the extractors differ in image size, nlevels or scaleFactor";
+        return CS_ERR_BAD_ARG;
+    }
+    const cs_keypoint *k = nullptr;
+    const unsigned long long *d = nullptr;
+    int n = 0;
+    if (cs_orb_device_frame(left, left_first + n_pairs - 1, &k, &d, &n) != CS_OK || cs_orb_device_frame(right, right_first + n_pairs - 1, &k, &d, &n) != CS_OK) return CS_ERR_BAD_ARG; // no run yet
+    return CS_OK;
+}
+
+// The four passes over s->pairs (set by the caller), for both entries: kL0 / dL0 / kR0 / dR0 = the device arrays that PairRec::l0 / r0 count from.
+int associate(cs_ctx *ctx, cs_stereo *s, const cs_orb_pyramid_view &VL, int left_first, const cs_orb_pyramid_view &VR, int right_first, const cs_keypoint *kL0,
+              const unsigned long long *dL0, const cs_keypoint *kR0, const unsigned long long *dR0, float bf, float b) {
+    const int n_pairs = s->n_pairs;
+    int max_nl = 0, max_nr = 0;
+    for (const PairRec &pr : s->pairs) { max_nl = std::max(max_nl, pr.nl); max_nr = std::max(max_nr, pr.nr); }
+    StereoP P{};
+    P.nlevels = VL.nlevels; P.rows = VL.H; P.bf = bf; P.maxD = bf / b;
+    for (int l = 0; l < VL.nlevels; l++) { P.off[l] = VL.off[l]; P.w[l] = VL.w[l]; P.h[l] = VL.h[l]; P.scale[l] = VL.scale[l]; P.inv_scale[l] = VL.inv_scale[l]; }
+    int r = cs_h2d(ctx, s->d_pairs, s->pairs.data(), (size_t)n_pairs); if (r) return r;
+    CS_LAUNCH(ctx, "stereo_prep", stereo_prep, dim3(std::max((max_nr + 255) / 256, 1), n_pairs), dim3(256), 0, P, s->d_pairs, kR0, s->d_rec, s->d_lvl);
+    if (max_nl > 0) {
+        CS_LAUNCH(ctx, "stereo_match", stereo_match, dim3((max_nl + 256 / GROUP - 1) / (256 / GROUP), n_pairs), dim3(256), 0, P, s->d_pairs, kL0, dL0, s->d_rec, dR0, s->d_lvl, s->d_best);
+        CS_LAUNCH(ctx, "stereo_sad", stereo_sad, dim3(max_nl, n_pairs), dim3(64), 0, P, s->d_pairs, kL0, kR0, s->d_best, VL.d_pyr + (long)left_first * VL.frame_stride,
+                  VR.d_pyr + (long)right_first * VR.frame_stride, VL.frame_stride, VR.frame_stride, s->d_u_right, s->d_depth, s->d_sad);
+    }
+    CS_LAUNCH(ctx, "stereo_cut", stereo_cut, dim3(n_pairs), dim3(256), 0, s->d_pairs, s->d_sad, s->d_u_right, s->d_depth, s->d_n_matched);
+    CS_HIP(ctx, hipGetLastError());
+    return CS_OK;
+}
+} // namespace
 
 extern "C" {
 
@@ -274,14 +318,11 @@ int cs_stereo_create(cs_ctx *ctx, int max_keypoints_per_frame, int max_pairs, cs
 int cs_stereo_match_from_orb(cs_ctx *ctx, cs_stereo *s, const cs_orb *left, int left_first, const cs_orb *right, int right_first, int n_pairs, float bf, float b) {
     if (!ctx || !s || !left || !right || n_pairs < 1 || n_pairs > s->max_pairs || left_first < 0 || right_first < 0 || !(bf > 0.0f) || !(b > 0.0f)) return CS_ERR_BAD_ARG;
     cs_orb_pyramid_view VL, VR;
-    if (cs_orb_device_pyramid(left, &VL) != CS_OK || cs_orb_device_pyramid(right, &VR) != CS_OK) return CS_ERR_BAD_ARG;
-    if (left_first + n_pairs > VL.n_frames || right_first + n_pairs > VR.n_frames) { ctx->err = "cs_stereo_match_from_orb: pairs outside the extractor's last run"; return CS_ERR_BAD_ARG; }
-    if (VL.W != VR.W || VL.H != VR.H || VL.nlevels != VR.nlevels || VL.scale_factor != VR.scale_factor) { ctx->err = "cs_stereo_match_from_orb: the extractors differ in image size, nlevels or scaleFactor"; return CS_ERR_BAD_ARG; }
+    CS_TRY(pyramids(ctx, "cs_stereo_match_from_orb", left, left_first, right, right_first, n_pairs, &VL, &VR));
     const cs_keypoint *kL0 = nullptr, *kR0 = nullptr, *k = nullptr;
     const unsigned long long *dL0 = nullptr, *dR0 = nullptr, *d = nullptr;
     int n = 0;
     std::vector<PairRec> pairs((size_t)n_pairs); // the handle keeps its last call until this one is known to be good
-    int max_nl = 0, max_nr = 0;
     for (int p = 0; p < n_pairs; p++) {
         PairRec &pr = pairs[(size_t)p];
         if (cs_orb_device_frame(left, left_first + p, &k, &d, &n) != CS_OK) return CS_ERR_BAD_ARG; // no run yet
@@ -291,23 +332,52 @@ int cs_stereo_match_from_orb(cs_ctx *ctx, cs_stereo *s, const cs_orb *left, int 
         if (p == 0) { kR0 = k; dR0 = d; }
         pr.r0 = (int)(k - kR0); pr.nr = n;
         if (pr.nl > s->cap || pr.nr > s->cap) { ctx->err = "cs_stereo_match_from_orb: a frame has more key points than the handle was created for"; return CS_ERR_CAPACITY; }
-        max_nl = std::max(max_nl, pr.nl); max_nr = std::max(max_nr, pr.nr);
     }
     s->pairs.swap(pairs);
     s->n_pairs = n_pairs;
-    StereoP P{};
-    P.nlevels = VL.nlevels; P.rows = VL.H; P.bf = bf; P.maxD = bf / b;
-    for (int l = 0; l < VL.nlevels; l++) { P.off[l] = VL.off[l]; P.w[l] = VL.w[l]; P.h[l] = VL.h[l]; P.scale[l] = VL.scale[l]; P.inv_scale[l] = VL.inv_scale[l]; }
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    int r = cs_h2d(ctx, s->d_pairs, s->pairs.data(), (size_t)n_pairs); if (r) return r;
-    CS_LAUNCH(ctx, "stereo_prep", stereo_prep, dim3(std::max((max_nr + 255) / 256, 1), n_pairs), dim3(256), 0, P, s->d_pairs, kR0, s->d_rec, s->d_lvl);
-    if (max_nl > 0) {
-        CS_LAUNCH(ctx, "stereo_match", stereo_match, dim3((max_nl + 256 / GROUP - 1) / (256 / GROUP), n_pairs), dim3(256), 0, P, s->d_pairs, kL0, dL0, s->d_rec, dR0, s->d_lvl, s->d_best);
-        CS_LAUNCH(ctx, "stereo_sad", stereo_sad, dim3(max_nl, n_pairs), dim3(64), 0, P, s->d_pairs, kL0, kR0, s->d_best, VL.d_pyr + (long)left_first * VL.frame_stride,
-                  VR.d_pyr + (long)right_first * VR.frame_stride, VL.frame_stride, VR.frame_stride, s->d_u_right, s->d_depth, s->d_sad);
+    return associate(ctx, s, VL, left_first, VR, right_first, kL0, dL0, kR0, dR0, bf, b);
+}
+
+int cs_stereo_match_from_keys(cs_ctx *ctx, cs_stereo *s, const cs_orb *left, int left_first, const cs_orb *right, int right_first, int n_pairs, const int *firstL,
+                              const cs_keypoint *keysL, const uint8_t *descL, const int *firstR, const cs_keypoint *keysR, const uint8_t *descR, float bf, float b) {
+    if (!ctx || !s || !left || !right || n_pairs < 1 || n_pairs > s->max_pairs || left_first < 0 || right_first < 0 || !(bf > 0.0f) || !(b > 0.0f)) return CS_ERR_BAD_ARG;
+    if (!cs_offsets_ok(firstL, n_pairs, keysL) || !cs_offsets_ok(firstR, n_pairs, keysR) || (firstL[n_pairs] > 0 && !descL) || (firstR[n_pairs] > 0 && !descR)) return CS_ERR_BAD_ARG;
+    cs_orb_pyramid_view VL, VR;
+    CS_TRY(pyramids(ctx, "cs_stereo_match_from_keys", left, left_first, right, right_first, n_pairs, &VL, &VR));
+    std::vector<PairRec> pairs((size_t)n_pairs); // the handle keeps its last call until this one is known to be good
+    for (int p = 0; p < n_pairs; p++) {
+        PairRec &pr = pairs[(size_t)p];
+        pr.l0 = firstL[p]; pr.nl = firstL[p + 1] - firstL[p];
+        pr.r0 = firstR[p]; pr.nr = firstR[p + 1] - firstR[p];
+        if (pr.nl > s->cap || pr.nr > s->cap) { ctx->err = "cs_stereo_match_from_keys: a frame has more key points than the handle was created for"; return CS_ERR_CAPACITY; }
+        for (int j = 1; j < pr.nr; j++)
+            if (keysR[pr.r0 + j].octave < keysR[pr.r0 + j - 1].octave) { ctx->err = "cs_stereo_match_from_keys: a right frame's key points are not in level-major order (an octave decreases)"; return CS_ERR_BAD_ARG; }
     }
-    CS_LAUNCH(ctx, "stereo_cut", stereo_cut, dim3(n_pairs), dim3(256), 0, s->d_pairs, s->d_sad, s->d_u_right, s->d_depth, s->d_n_matched);
-    CS_HIP(ctx, hipGetLastError());
+    // the level coordinates the kernels round to int stay far inside its range
+    auto plain = [](const cs_keypoint *k, int n) { for (int i = 0; i < n; i++) if (!(std::fabs(k[i].x) <= MAX_COORD && std::fabs(k[i].y) <= MAX_COORD)) return false; return true; };
+    if (!plain(keysL, firstL[n_pairs]) || !plain(keysR, firstR[n_pairs])) { ctx->err = "cs_stereo_match_from_keys: a key point's coordinate is not finite or above 2^24 in magnitude"; return CS_ERR_BAD_ARG; }
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->d_keys_l) { // the first call through this entry
+        const size_t n = (size_t)s->cap * s->max_pairs;
+        cs_owner o;
+        if (o.alloc(ctx, &s->d_keys_l, n) != CS_OK || o.alloc(ctx, &s->d_keys_r, n) != CS_OK || o.alloc(ctx, &s->d_desc_l, n * 4) != CS_OK || o.alloc(ctx, &s->d_desc_r, n * 4) != CS_OK) {
+            (void)hipGetLastError();
+            o.free_all(ctx);
+            s->d_keys_l = s->d_keys_r = nullptr; s->d_desc_l = s->d_desc_r = nullptr;
+            ctx->err = "cs_stereo_match_from_keys: out of device memory";
+            return CS_ERR_NOMEM;
+        }
+        s->own.adopt(o);
+    }
+    s->pairs.swap(pairs);
+    s->n_pairs = n_pairs;
+    CS_TRY(cs_h2d(ctx, s->d_keys_l, keysL, (size_t)firstL[n_pairs]));
+    CS_TRY(cs_h2d(ctx, s->d_keys_r, keysR, (size_t)firstR[n_pairs]));
+    CS_TRY(cs_h2d(ctx, reinterpret_cast<uint8_t *>(s->d_desc_l), descL, (size_t)firstL[n_pairs] * 32));
+    CS_TRY(cs_h2d(ctx, reinterpret_cast<uint8_t *>(s->d_desc_r), descR, (size_t)firstR[n_pairs] * 32));
+    CS_TRY(associate(ctx, s, VL, left_first, VR, right_first, s->d_keys_l, s->d_desc_l, s->d_keys_r, s->d_desc_r, bf, b));
+    CS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's arrays are free when the call returns
     return CS_OK;
 }
 

@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
+from .orb import KEYPOINT_DTYPE
 
 
 def _p(a, t):
@@ -29,6 +30,29 @@ class StereoMatcher:
         check(self.ctx.ptr, lib().cs_stereo_match_from_orb(self.ctx.ptr, self._s, left._e, int(left_first), right._e, int(right_first), int(n_pairs),
                                                            C.c_float(bf), C.c_float(b)), "cs_stereo_match_from_orb")
         self.n_pairs = int(n_pairs)
+
+    def match_keys(self, left, right, keysL, descL, keysR, descR, bf, b, left_first=0, right_first=0):
+        """The same over host arrays (cs_stereo_match_from_keys): keysL / descL / keysR / descR are lists, one entry per pair, of KEYPOINT_DTYPE arrays and their
+        [n, 32] uint8 descriptors.  The extractors supply the pyramids of frames left_first + p / right_first + p of their last run.  A right frame's key points
+        must be level-major.  Returns when the arrays have been uploaded; results stay on the device."""
+        n_pairs = len(keysL)
+        if not (len(descL) == len(keysR) == len(descR) == n_pairs):
+            raise ValueError("keysL, descL, keysR and descR are one entry per pair")
+        if [len(k) for k in keysL] != [len(d) for d in descL] or [len(k) for k in keysR] != [len(d) for d in descR]:
+            raise ValueError("key points and descriptors differ in length")
+
+        def pack(keys, desc):
+            first = np.zeros(n_pairs + 1, np.int32)
+            first[1:] = np.cumsum([len(k) for k in keys])
+            k = np.concatenate([np.asarray(a, KEYPOINT_DTYPE) for a in keys] + [np.zeros(1, KEYPOINT_DTYPE)])  # (one spare record: a pointer that may be handed over)
+            d = np.concatenate([np.asarray(a, np.uint8).reshape(-1, 32) for a in desc] + [np.zeros((1, 32), np.uint8)])
+            return first, np.ascontiguousarray(k), np.ascontiguousarray(d)
+        fL, kL, dL = pack(keysL, descL)
+        fR, kR, dR = pack(keysR, descR)
+        check(self.ctx.ptr, lib().cs_stereo_match_from_keys(self.ctx.ptr, self._s, left._e, int(left_first), right._e, int(right_first), n_pairs, _p(fL, C.c_int),
+                                                            C.c_void_p(kL.ctypes.data), _p(dL, C.c_uint8), _p(fR, C.c_int), C.c_void_p(kR.ctypes.data), _p(dR, C.c_uint8),
+                                                            C.c_float(bf), C.c_float(b)), "cs_stereo_match_from_keys")
+        self.n_pairs = n_pairs
 
     def read(self):
         """[(mvuRight, mvDepth)] per pair and n_matched[n_pairs]."""

@@ -235,6 +235,16 @@ void cs_stereo_destroy(cs_ctx *ctx, cs_stereo *s);
  * reference's stereo constructor sets mb = mbf / fx at Frame.cc:141, after the call at :118, so the caller passes the value it means.  Queues the
  * kernels on the context's stream and returns; the results stay on the device. */
 int cs_stereo_match_from_orb(cs_ctx *ctx, cs_stereo *s, const cs_orb *left, int left_first, const cs_orb *right, int right_first, int n_pairs, float bf, float b);
+/* The same over host arrays, for a caller whose key points and descriptors come from elsewhere (the CPU extractor, a replayed log): pair p's left key points are
+ * keysL[firstL[p] .. firstL[p + 1]) with 32-byte descriptors descL (likewise firstR / keysR / descR; n_pairs + 1 offsets each, starting at 0 and not decreasing).
+ * The extractors supply only the resident pyramids and scale tables (cs_orb_device_pyramid): they must have run on the frames named, and the geometry checks are
+ * those of cs_stereo_match_from_orb.  A right frame's key points must be in level-major order, as ORBextractor::operator() emits them (its octaves never decrease
+ * within the frame): the device finds a level's right key points as one contiguous range.  CS_ERR_BAD_ARG: a NULL array that is needed, offsets that do not start
+ * at 0 or decrease, a right frame whose octaves decrease, a coordinate that is not finite or above 2^24 in magnitude; CS_ERR_CAPACITY: a frame with more key
+ * points than the handle was created for.  A refused call leaves the previous result readable.  The key points go into device blocks the handle allocates on the
+ * first call through this entry; the same kernels run; the call waits for its uploads, so the arrays are the caller's again when it returns. */
+int cs_stereo_match_from_keys(cs_ctx *ctx, cs_stereo *s, const cs_orb *left, int left_first, const cs_orb *right, int right_first, int n_pairs, const int *firstL,
+                              const cs_keypoint *keysL, const uint8_t *descL, const int *firstR, const cs_keypoint *keysR, const uint8_t *descR, float bf, float b);
 /* mvuRight / mvDepth of the last call: pair p's counts[p] values at u_right[p * cap_per_frame ...] / depth[...], -1 where unmatched (:613-614);
  * n_matched[p] = matches left after the cut.  CS_ERR_CAPACITY (nothing copied) when a pair has more than cap_per_frame left key points. */
 int cs_stereo_read(cs_ctx *ctx, cs_stereo *s, float *u_right, float *depth, int cap_per_frame, int *counts, int *n_matched);

@@ -42,18 +42,23 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
     dep = np.full(N, -1, f32)
     st = {} if stats is None else stats  # how often each exit was taken
     st.update(cand=0, hamming=0, column_exit=0, edge_shift=0, parabola=0, disparity=0, clamp=0)
+    # ... and the guarded exits (what the reference leaves undefined), the winner of every Hamming search as (iL, iR, distance, candidates), the (iL, SAD) pairs accepted
+    # before the cut, and the median
+    st.update(left_row=0, max_u=0, right_span=0, right_octave=0, left_octave=0, patch=0, empty=0, best=[], sad=[], median=None)
     nRows = pyrL[0].shape[0]  # :616
     nlevels = len(pyrL)
     rows = [[] for _ in range(nRows)]  # :619-636
     for iR in range(Nr):
         octv = int(kr["octave"][iR])
         if octv < 0 or octv >= nlevels:
+            st["right_octave"] += 1
             continue
         kpY = f32(kr["y"][iR])
         r = f32(f32(2) * sf[octv])
         maxr = int(math.ceil(f32(kpY + r)))
         minr = int(math.floor(f32(kpY - r)))
         if minr < 0 or maxr >= nRows:
+            st["right_span"] += 1
             continue
         for yi in range(minr, maxr + 1):
             rows[yi].append(iR)
@@ -66,6 +71,7 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
         levelL = int(kl["octave"][iL])
         vL, uL = f32(kl["y"][iL]), f32(kl["x"][iL])
         if not (vL >= 0 and vL < nRows):
+            st["left_row"] += 1
             continue
         cand = rows[int(vL)]  # :654
         if not cand:
@@ -73,6 +79,7 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
         minU = f32(uL - maxD)  # :659-660
         maxU = f32(uL - minD)
         if maxU < 0:
+            st["max_u"] += 1
             continue
         c = np.asarray(cand)
         c = c[(kro[c] >= levelL - 1) & (kro[c] <= levelL + 1) & (krx[c] >= minU) & (krx[c] <= maxU)]  # :676, :681
@@ -84,7 +91,9 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
         if d[j] >= TH_HIGH:  # :695
             continue
         st["hamming"] += 1
+        st["best"].append((iL, int(c[j]), int(d[j]), len(c)))
         if levelL < 0 or levelL >= nlevels:
+            st["left_octave"] += 1
             continue
         uR0 = krx[c[j]]
         s = isf[levelL]
@@ -92,6 +101,7 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
         imL, imR = pyrL[levelL], pyrR[levelL]
         h, wd = imL.shape
         if sv - w < 0 or sv + w >= h or su - w < 0 or su + w >= wd or sr - w - L < 0 or sr + w + L >= wd:
+            st["patch"] += 1
             continue  # cv::Mat range checks in the reference
         IL = imL[sv - w:sv + w + 1, su - w:su + w + 1].astype(np.int32)  # :706-708
         IL = IL - IL[w, w]
@@ -113,6 +123,8 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
         d1, d2, d3 = vDists[L + binc - 1], vDists[L + binc], vDists[L + binc + 1]
         with np.errstate(all="ignore"):
             deltaR = f32(f32(d1 - d3) / f32(f32(2) * f32(f32(d1 + d3) - f32(f32(2) * d2))))  # :745
+        # Kept as written, but never taken: d2 is the strict first minimum of integer sums, so d1 > d2 and d3 >= d2; the denominator is >= 2 and
+        # |d1 - d3| <= d1 + d3 - 2 * d2, every term exact in float (below 2^24), so |deltaR| <= 0.5 and neither NaN nor inf can arise.
         if deltaR < -1 or deltaR > 1:
             st["parabola"] += 1
             continue
@@ -130,9 +142,13 @@ def compute_stereo_matches(kl, dl, kr, dr, pyrL, pyrR, sf, isf, bf, b, stats=Non
             st["disparity"] += 1
     vDistIdx.sort()  # :769
     st["accepted"] = len(vDistIdx)
+    st["sad"] = sorted((i, dist) for dist, i in vDistIdx)
+    if N > 0 and not vDistIdx:
+        st["empty"] += 1
     kept = 0
     if vDistIdx:
         median = f32(vDistIdx[len(vDistIdx) // 2][0])
+        st["median"] = int(median)
         thDist = f32(f32(f32(1.5) * f32(1.4)) * median)
         kept = len(vDistIdx)
         for dist, i in reversed(vDistIdx):  # :773-782

@@ -93,7 +93,8 @@ def test_version_is_108():
 def test_stereo_symbols_exported():
     from cube_slam_amd import _lib
     lib = _lib.lib()
-    for name in ("cs_stereo_create", "cs_stereo_destroy", "cs_stereo_match_from_orb", "cs_stereo_read", "cs_stereo_read_packed", "cs_stereo_device_pair"):
+    for name in ("cs_stereo_create", "cs_stereo_destroy", "cs_stereo_match_from_orb", "cs_stereo_match_from_keys", "cs_stereo_read", "cs_stereo_read_packed",
+                 "cs_stereo_device_pair"):
         assert hasattr(lib, name), name
 
 
@@ -107,6 +108,12 @@ def test_bad_arguments_without_a_handle():
     assert lib.cs_stereo_create(fake, 2000, 1, None) == BAD  # NULL out-pointer
     assert lib.cs_stereo_match_from_orb(None, None, None, 0, None, 0, 1, C.c_float(sr.BF), C.c_float(B)) == BAD
     assert lib.cs_stereo_match_from_orb(fake, None, fake, 0, fake, 0, 1, C.c_float(sr.BF), C.c_float(B)) == BAD  # NULL handle
+    first = np.zeros(2, np.int32)
+    key, dsc = np.zeros(28, np.uint8), np.zeros(32, np.uint8)
+    pfirst, keys, desc = first.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(key.ctypes.data), dsc.ctypes.data_as(C.POINTER(C.c_uint8))
+    from_keys = lambda ctx, s, l, r: lib.cs_stereo_match_from_keys(ctx, s, l, 0, r, 0, 1, pfirst, keys, desc, pfirst, keys, desc, C.c_float(sr.BF), C.c_float(B))
+    assert from_keys(None, None, None, None) == BAD
+    assert from_keys(fake, None, fake, fake) == BAD  # NULL handle
     buf = np.zeros(4, np.float32)
     cnt = np.zeros(4, np.int32)
     pf, pi = buf.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(C.POINTER(C.c_int))

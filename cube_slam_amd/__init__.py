@@ -6,7 +6,7 @@ package is the thin host-side mirror of the reference interfaces used by tests a
 from . import _lib  # noqa: F401
 from .stereo import ComputeStereoMatches, StereoMatcher  # noqa: F401
 from .rgbd import ClosePoints, ComputeStereoFromRGBD, RGBDAssociator  # noqa: F401
-from .klt import KLTTracker, SearchByTracking, SearchByTrackingHarris, calcOpticalFlowPyrLK  # noqa: F401
+from .klt import KLTTracker, NewHarrisFeatures, SearchByTracking, SearchByTrackingHarris, calcOpticalFlowPyrLK, goodFeaturesToTrack  # noqa: F401
 from .bow import KeyFrameDatabase, ORBVocabulary  # noqa: F401
 from .local_mapping import ComputeDistinctiveDescriptors, KeyFrameView, LocalMapping, UpdateNormalAndDepth  # noqa: F401
 from .initializer import Initializer  # noqa: F401

@@ -14,6 +14,7 @@
 //
 // One stream; cs_klt_set_frames waits for its upload (the caller's images are free when it returns), the track calls wait for their results.
 #include "common.h"
+#include "klt_handle.h"
 #include "klt_math.h"
 
 #include <climits>
@@ -302,16 +303,6 @@ __global__ void __launch_bounds__(TS_THREADS) klt_tracking_assign(AssignP P, con
     if (tid == 0) counts[5] = 0;
 }
 } // namespace
-
-struct cs_klt {
-    int max_frames = 0, max_w = 0, max_h = 0, max_points = 0;
-    cs_owner own;
-    uint8_t *d_gray = nullptr, *d_img = nullptr, *d_status = nullptr;
-    short *d_der = nullptr;
-    float *d_prev = nullptr, *d_next = nullptr, *d_err = nullptr;
-    int n_frames = 0, W = 0, H = 0;
-    KltLayout L{};
-};
 
 namespace {
 // nullptr, or what is wrong with the pairs and points of a call

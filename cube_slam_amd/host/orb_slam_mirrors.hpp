@@ -11,12 +11,13 @@
 //   cubeslam::ORBmatcher        ORB_SLAM2::ORBmatcher, the dynamic-object KLT (src/ORBmatcher.cc:1524-1580): SearchByTrackingHarris over two gray frames, with the
 //                               cv::calcOpticalFlowPyrLK call of :1548 / :1620 as ORBmatcher::calcOpticalFlowPyrLK, and SearchByTracking (:1582-1725) over the current
 //                               frame's mvKeysUn
+//   cubeslam::goodFeaturesToTrack   cv::goodFeaturesToTrack as Tracking::CreateNewKeyFrame calls it (src/Tracking.cc:2292), csrc/gftt_math.h
 //   cubeslam::line_lbd_detect   line_lbd_detect              (line_lbd/include/line_lbd/line_lbd_allclass.h:22-70)
 //   cubeslam::Optimizer         ORB_SLAM2::Optimizer         (orb_object_slam/include/Optimizer.h:39-62): BundleAdjustment over the
 //                               flattened graph (cs_ba_problem), PoseOptimization over flattened matches, OptimizeSim3 over flattened correspondences,
 //                               LocalBACameraPointObjectsDynamic over the flattened dynamic graph (cs_ba_dyn_problem)
-// With CUBESLAM_HOST_ONLY defined the header holds the RGB-D members of Frame, ClosePoints and ORBmatcher's KLT alone, on their path without a context (csrc/rgbd_math.h
-// and csrc/klt_math.h, the text the kernels run; compile with -ffp-contract=off): of the C header only the types are used and nothing of the library is linked.
+// With CUBESLAM_HOST_ONLY defined the header holds the RGB-D members of Frame, ClosePoints ORBmatcher's KLT and goodFeaturesToTrack alone, on their path without a context (csrc/rgbd_math.h,
+// csrc/klt_math.h and csrc/gftt_math.h, the text the kernels run; compile with -ffp-contract=off): of the C header only the types are used and nothing of the library is linked.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "../csrc/gftt_math.h"
 #include "../csrc/klt_math.h"
 #include "../csrc/rgbd_math.h"
 #ifndef CUBESLAM_HOST_ONLY
@@ -337,6 +339,35 @@ struct ORBmatcher {
         r.kept.resize((size_t)r.goodmatches); r.pts.resize(2 * (size_t)r.goodmatches); r.object_id.resize((size_t)r.goodmatches);
     }
 };
+
+// cv::goodFeaturesToTrack(image, corners, maxCorners, qualityLevel, minDistance, mask) with blockSize 3 and the minimum eigenvalue (Tracking.cc:2292) over one 8-bit
+// image of width x height (rows `stride` bytes apart); mask: dense width x height, or nullptr.  Without a context the host runs csrc/gftt_math.h, byte-equal to the device.
+struct GoodFeatures {
+    std::vector<float> corners, quality; // (x, y) per corner in the order of acceptance, and its thresholded eigenvalue
+    int n_candidates = 0;
+};
+inline GoodFeatures goodFeaturesToTrack(Context *ctx, const uint8_t *image, int width, int height, long stride, const uint8_t *mask, int maxCorners, double qualityLevel,
+                                        double minDistance) {
+    if (!image || width < 1 || height < 1 || stride < width || maxCorners < 1 || !(minDistance >= 1) || !(qualityLevel > 0 && qualityLevel <= 1))
+        throw std::invalid_argument("goodFeaturesToTrack: an image, maxCorners >= 1, minDistance >= 1 and 0 < qualityLevel <= 1");
+    const int cap = maxCorners < GFTT_MAX_CANDIDATES ? maxCorners : GFTT_MAX_CANDIDATES;
+    GoodFeatures r;
+    r.corners.assign(2 * (size_t)cap, 0.f); r.quality.assign((size_t)cap, 0.f);
+    int count = 0;
+    if (!ctx) {
+        if (!gftt_good_features_host(image, stride, width, height, mask, cap, qualityLevel, minDistance, r.corners.data(), r.quality.data(), &count, &r.n_candidates))
+            throw std::length_error("goodFeaturesToTrack: more candidates than GFTT_MAX_CANDIDATES");
+    } else {
+#ifndef CUBESLAM_HOST_ONLY
+        check(ctx->ctx, cs_good_features_images(ctx->ctx, image, 1, width, height, stride, mask, cap, qualityLevel, minDistance, r.corners.data(), r.quality.data(), &count, &r.n_candidates),
+              "cs_good_features_images");
+#else
+        throw std::runtime_error("goodFeaturesToTrack: built without the library");
+#endif
+    }
+    r.corners.resize(2 * (size_t)count); r.quality.resize((size_t)count);
+    return r;
+}
 
 #ifndef CUBESLAM_HOST_ONLY
 class line_lbd_detect {

@@ -4,18 +4,22 @@
 //   UpdateLocalPoints                         :2740-2764, cs_track_local_points
 //   SearchLocalPoints                         :2673-2728, Frame::isInFrustum and ORBmatcher::SearchByProjection(F, vpMapPoints, th) in cs_match_local_map_frustum
 //   TrackLocalMap                             the chain with cs_pose_optimization and the statistics loop (:1372-1397), which stays on the host with the two thresholds
+//   CreateNewHarrisFeatures                   :2258-2337, the new dynamic-object points of CreateNewKeyFrame: csrc/gftt_math.h on the host, cs_track_new_harris_features
 // The map is a table of points and a table of key frames (TrackMap); what the reference keeps as pointers are indices into them, -1 for NULL.  With CUBESLAM_HOST_ONLY defined
-// the header needs neither the library nor a context type and only UpdateLocalKeyFrames is there.
+// the header needs neither the library nor a context type; only UpdateLocalKeyFrames and CreateNewHarrisFeatures on its path without a context are there.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../csrc/gftt_math.h"
 #include "../csrc/track_local_walk.h"
 #ifndef CUBESLAM_HOST_ONLY
 #include "../../include/cubeslam_hip.h"
 #include "detect_3d_cuboid.hpp" // cubeslam::Context
+#else
+namespace cubeslam { struct Context; }
 #endif
 
 namespace cubeslam {
@@ -67,6 +71,59 @@ class Tracking {
         local.resize((size_t)n);
         mvpLocalKeyFrames = local;
         if (kf_max >= 0) mpReferenceKF = kf_max;
+    }
+
+    // The new-feature loop of CreateNewKeyFrame with use_dynamic_klt_features (:2258-2337) over raw_img (width x height, rows `stride` bytes apart) and objmask_img
+    // (dense).  exist_pts / exist_obs: pt and Observations() of the current frame's Harris points with `pMP && pMP->is_dynamic`; K4 = fx, fy, cx, cy; Twc = the 3 x 4 rows
+    // of the key frame's pose; cuboid_depth[id] = local_cuboids[id]->cube_meas.translation()[2].  `new MapPoint`, SetupSimpleMapPoints and the copies of :2300-2305 and
+    // :2335-2337 stay the caller's.  Without a context the host runs csrc/gftt_math.h, byte-equal to the device.
+    struct NewHarrisFeatures {
+        std::vector<float> pts, x3D;        // the new corners (x, y) and their world positions
+        std::vector<int> object_id;         // keypoint_associate_objectID_harris of the new points
+        std::vector<uint8_t> x3D_valid;     // 0: the cuboid's depth is not > 0 (the reference's empty Mat)
+        std::vector<uint8_t> good_mask;     // the mask goodFeaturesToTrack ran on
+        int n_mask_outside = 0, n_candidates = 0;
+    };
+    static NewHarrisFeatures CreateNewHarrisFeatures(Context *ctx, const uint8_t *raw_img, int width, int height, long stride, const uint8_t *objmask_img,
+                                                     const std::vector<float> &exist_pts, const std::vector<int> &exist_obs, const float K4[4], const float Twc[12],
+                                                     const std::vector<float> &cuboid_depth) {
+        const int n_exist = (int)exist_obs.size(), n_cub = (int)cuboid_depth.size();
+        if (!raw_img || !objmask_img || width < 1 || height < 1 || stride < width || exist_pts.size() != 2 * exist_obs.size())
+            throw std::invalid_argument("CreateNewHarrisFeatures: an image, a mask and (x, y) pairs with one observation count each");
+        for (float v : exist_pts) if (!gftt_point_ok(v)) throw std::invalid_argument("CreateNewHarrisFeatures: an existing point that is not finite");
+        NewHarrisFeatures r;
+        r.pts.assign(400, 0.f); r.x3D.assign(600, 0.f); r.object_id.assign(200, 0); r.x3D_valid.assign(200, 0); r.good_mask.assign((size_t)width * height, 0);
+        const float none = 0;
+        const int zero = 0;
+        int n_new = 0;
+        if (!ctx) {
+            const int rc = gftt_new_harris_features_host(raw_img, stride, width, height, objmask_img, n_exist, n_exist ? exist_pts.data() : &none, n_exist ? exist_obs.data() : &zero, K4, Twc,
+                                                         n_cub, n_cub ? cuboid_depth.data() : &none, r.good_mask.data(), r.pts.data(), r.object_id.data(), r.x3D.data(),
+                                                         r.x3D_valid.data(), &n_new, &r.n_candidates, &r.n_mask_outside);
+            if (rc == 1) throw std::length_error("CreateNewHarrisFeatures: more candidates than GFTT_MAX_CANDIDATES");
+            if (rc == 2) throw std::invalid_argument("CreateNewHarrisFeatures: a corner's object id is at or beyond the cuboid count");
+        } else {
+#ifndef CUBESLAM_HOST_ONLY
+            std::vector<uint8_t> dense((size_t)width * height);
+            for (int y = 0; y < height; y++) std::copy(raw_img + (long)y * stride, raw_img + (long)y * stride + width, dense.begin() + (size_t)y * width);
+            cs_klt *h = nullptr;
+            int rc = cs_klt_create(ctx->ctx, 1, width, height, 1, &h);
+            if (rc == CS_OK) rc = cs_klt_set_frames(ctx->ctx, h, 1, width, height, dense.data(), width);
+            const int frame = 0, ef[2] = {0, n_exist}, cf[2] = {0, n_cub};
+            int nf[2] = {0, 0};
+            if (rc == CS_OK)
+                rc = cs_track_new_harris_features(ctx->ctx, h, 1, &frame, objmask_img, ef, n_exist ? exist_pts.data() : &none, n_exist ? exist_obs.data() : &zero, K4, Twc, cf,
+                                                  n_cub ? cuboid_depth.data() : &none, nf, r.pts.data(), r.object_id.data(), r.x3D.data(), r.x3D_valid.data(), &r.n_mask_outside,
+                                                  r.good_mask.data(), &r.n_candidates);
+            cs_klt_destroy(ctx->ctx, h);
+            if (rc != CS_OK) throw std::runtime_error(std::string("cs_track_new_harris_features failed (") + std::to_string(rc) + "): " + cs_last_error(ctx->ctx));
+            n_new = nf[1];
+#else
+            throw std::runtime_error("CreateNewHarrisFeatures: built without the library");
+#endif
+        }
+        r.pts.resize(2 * (size_t)n_new); r.x3D.resize(3 * (size_t)n_new); r.object_id.resize((size_t)n_new); r.x3D_valid.resize((size_t)n_new);
+        return r;
     }
 
 #ifndef CUBESLAM_HOST_ONLY

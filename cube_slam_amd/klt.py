@@ -110,6 +110,23 @@ class KLTTracker:
               "cs_match_by_tracking_harris")
         return _harris_result(first, flat, nxt, st, er, kf, kept, kpts, ids, good, outside)
 
+    def good_features(self, frames, masks, maxCorners, qualityLevel, minDistance):
+        """cv::goodFeaturesToTrack on the resident frames `frames` (indices of the last set_frames): masks = one image per frame or None.  Per frame a dict of corners
+        [k, 2], quality [k] and n_candidates."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        m = None if masks is None else _masks(masks, len(fr), self.H, self.W)
+        out = _gftt_outputs(len(fr), maxCorners)
+        r = lib().cs_klt_good_features(self.ctx.ptr, self._h, len(fr), _p(fr, C.c_int), None if m is None else _p(m, C.c_uint8), int(maxCorners), C.c_double(qualityLevel),
+                                       C.c_double(minDistance), *_gftt_ptrs(out))
+        return _gftt_result(self.ctx.ptr, r, "cs_klt_good_features", out)
+
+    def new_harris_features(self, frames, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks=False):
+        """Tracking.cc:2263-2331 on the resident frames `frames`; see NewHarrisFeatures."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        a = _harris_args(len(fr), self.H, self.W, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks)
+        r = lib().cs_track_new_harris_features(self.ctx.ptr, self._h, len(fr), _p(fr, C.c_int), *a["ptrs"])
+        return _new_harris_result(self.ctx.ptr, r, "cs_track_new_harris_features", a)
+
     def close(self):
         if self._h:
             lib().cs_klt_destroy(self.ctx.ptr, self._h)
@@ -161,6 +178,100 @@ def SearchByTrackingHarris(frames, pairs, last_pts, masks, ctx=None):
                                                        _p(er, C.c_float), _p(kf, C.c_int), _p(kept, C.c_int), _p(kpts, C.c_float), _p(ids, C.c_int), _p(good, C.c_int),
                                                        _p(outside, C.c_int)), "cs_match_by_tracking_harris_host")
     return _harris_result(first, flat, nxt, st, er, kf, kept, kpts, ids, good, outside)
+
+
+def _gftt_outputs(n, max_corners):
+    k = max(int(max_corners), 1)
+    return np.zeros((n, k, 2), np.float32), np.zeros((n, k), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+
+
+def _gftt_ptrs(out):
+    return _p(out[0], C.c_float), _p(out[1], C.c_float), _p(out[2], C.c_int), _p(out[3], C.c_int)
+
+
+def _gftt_result(ctx_ptr, r, what, out):
+    corners, quality, counts, ncand = out
+    if r != _lib.CS_OK:
+        msg = lib().cs_last_error(ctx_ptr).decode() if ctx_ptr else ""
+        e = _lib.CubeSlamError("%s failed: %s %s" % (what, _lib.STATUS.get(r, r), msg))
+        e.n_candidates = ncand.copy()  # filled when the call fails with CS_ERR_CAPACITY
+        raise e
+    return [{"corners": corners[f, :counts[f]].copy(), "quality": quality[f, :counts[f]].copy(), "n_candidates": int(ncand[f])} for f in range(len(counts))]
+
+
+def _harris_args(n, H, W, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks):
+    m = _masks(objmasks, n, H, W)
+    pts = [np.asarray(q, np.float32).reshape(-1, 2) for q in exist_pts]
+    obs = [np.asarray(o, np.int32).reshape(-1) for o in exist_obs]
+    dep = [np.asarray(d, np.float32).reshape(-1) for d in cuboid_depth]
+    if len(pts) != n or len(obs) != n or len(dep) != n or any(len(q) != len(o) for q, o in zip(pts, obs)):
+        raise ValueError("one array of points, of observation counts and of cuboid depths per frame")
+    ef, cf = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+    ef[1:], cf[1:] = np.cumsum([len(q) for q in pts]), np.cumsum([len(d) for d in dep])
+    cat = lambda a, shape, dt: np.ascontiguousarray(np.concatenate(a) if a else np.zeros(shape, dt), dt)  # noqa: E731
+    fp, fo, fd = cat(pts, (0, 2), np.float32), cat(obs, 0, np.int32), cat(dep, 0, np.float32)
+    pad = lambda a: a if a.size else np.zeros(2, a.dtype)  # noqa: E731
+    fp, fo, fd = pad(fp), pad(fo), pad(fd)
+    k4 = np.ascontiguousarray(K4, np.float32).reshape(4)
+    T = np.ascontiguousarray(np.asarray(Twc, np.float32).reshape(n, -1)[:, :12])
+    cap = 200 * n
+    o = {"new_first": np.zeros(n + 1, np.int32), "pts": np.zeros((cap, 2), np.float32), "object_id": np.zeros(cap, np.int32), "x3D": np.zeros((cap, 3), np.float32),
+         "x3D_valid": np.zeros(cap, np.uint8), "n_mask_outside": np.zeros(n, np.int32), "good": np.zeros((n, H, W), np.uint8) if good_masks else None,
+         "n_candidates": np.zeros(n, np.int32)}
+    o["keep"] = (m, fp, fo, fd, k4, T, ef, cf)
+    o["ptrs"] = (_p(m, C.c_uint8), _p(ef, C.c_int), _p(fp, C.c_float), _p(fo, C.c_int), _p(k4, C.c_float), _p(T, C.c_float), _p(cf, C.c_int), _p(fd, C.c_float),
+                 _p(o["new_first"], C.c_int), _p(o["pts"], C.c_float), _p(o["object_id"], C.c_int), _p(o["x3D"], C.c_float), _p(o["x3D_valid"], C.c_uint8),
+                 _p(o["n_mask_outside"], C.c_int), None if o["good"] is None else _p(o["good"], C.c_uint8), _p(o["n_candidates"], C.c_int))
+    return o
+
+
+def _new_harris_result(ctx_ptr, r, what, a):
+    if r != _lib.CS_OK:
+        msg = lib().cs_last_error(ctx_ptr).decode() if ctx_ptr else ""
+        e = _lib.CubeSlamError("%s failed: %s %s" % (what, _lib.STATUS.get(r, r), msg))
+        e.n_candidates = a["n_candidates"].copy()
+        raise e
+    nf = a["new_first"]
+    out = []
+    for f in range(len(nf) - 1):
+        d = {k: a[k][nf[f]:nf[f + 1]].copy() for k in ("pts", "object_id", "x3D", "x3D_valid")}
+        d["n_mask_outside"], d["n_candidates"] = int(a["n_mask_outside"][f]), int(a["n_candidates"][f])
+        if a["good"] is not None:
+            d["good"] = a["good"][f].copy()
+        out.append(d)
+    return out
+
+
+def goodFeaturesToTrack(frames, masks, maxCorners, qualityLevel, minDistance, ctx=None):
+    """cv::goodFeaturesToTrack(frame, corners, maxCorners, qualityLevel, minDistance, mask) with blockSize 3 and the minimum eigenvalue, for every image of `frames`
+    [F, H, W] (or one [H, W]); masks = one image per frame or None.  Per frame a dict of corners [k, 2], quality [k] (the thresholded eigenvalue) and n_candidates.
+    ctx=None: the same statement on the host, the comparison side; with a context the device runs it."""
+    g = _frames(frames)
+    m = None if masks is None else _masks(masks, len(g), g.shape[1], g.shape[2])
+    out = _gftt_outputs(len(g), maxCorners)
+    head = (_p(g, C.c_uint8), len(g), g.shape[2], g.shape[1], C.c_long(g.strides[1]), None if m is None else _p(m, C.c_uint8), int(maxCorners), C.c_double(qualityLevel),
+            C.c_double(minDistance))
+    if ctx is not None:
+        return _gftt_result(ctx.ptr, lib().cs_good_features_images(ctx.ptr, *head, *_gftt_ptrs(out)), "cs_good_features_images", out)
+    return _gftt_result(None, lib().cs_klt_good_features_host(*head, *_gftt_ptrs(out)), "cs_klt_good_features_host", out)
+
+
+def NewHarrisFeatures(frames, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, ctx=None, good_masks=False):
+    """The new-feature loop of Tracking::CreateNewKeyFrame (Tracking.cc:2263-2331) for every image of `frames`: objmasks = objmask_img per frame, exist_pts / exist_obs =
+    per frame the pt and Observations() of the existing dynamic points, K4 = (fx, fy, cx, cy), Twc = the key frames' poses ([F, 3, 4] or [F, 4, 4]), cuboid_depth = per
+    frame the camera z of its local cuboids.  Per frame a dict of pts, object_id, x3D, x3D_valid, n_mask_outside, n_candidates (and good, the mask that was built, with
+    good_masks=True).  ctx=None: on the host."""
+    g = _frames(frames)
+    if ctx is not None:
+        t = KLTTracker(len(g), g.shape[2], g.shape[1], 1, ctx=ctx)
+        try:
+            t.set_frames(g)
+            return t.new_harris_features(np.arange(len(g)), objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks)
+        finally:
+            t.close()
+    a = _harris_args(len(g), g.shape[1], g.shape[2], objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks)
+    r = lib().cs_track_new_harris_features_host(_p(g, C.c_uint8), len(g), g.shape[2], g.shape[1], C.c_long(g.strides[1]), *a["ptrs"])
+    return _new_harris_result(None, r, "cs_track_new_harris_features_host", a)
 
 
 def _tracking_call(fn, head, N, last_keys, eligible, object_id, numobject, th, scale_factors, tail, keys_static, had_map_point, what, ctx_ptr):

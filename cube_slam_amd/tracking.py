@@ -211,5 +211,23 @@ class Tracking:
         r = SearchByTrackingHarris(np.stack([np.asarray(last_gray, np.uint8), np.asarray(current_gray, np.uint8)]), [(0, 1)], [mvKeysHarris_pt], [objmask_img], ctx=ctx)[0]
         return r["pts"], np.asarray(mvpMapPointsHarris)[r["kept"]], r["object_id"], r
 
+    def CreateNewHarrisFeatures(self, gray, objmask_img, mvKeysHarris_pt, mvpMapPointsHarris, observations, object_id_harris, K4, Twc, cuboid_depth, next_point_id=0, ctx=None,
+                                tracker=None, frame=0):
+        """The new-feature loop of Tracking::CreateNewKeyFrame with use_dynamic_klt_features (Tracking.cc:2258-2337).  mvKeysHarris_pt / mvpMapPointsHarris /
+        object_id_harris describe the current frame's tracked Harris points (a map point of None or < 0 is no point), observations[i] = Observations() of point i,
+        cuboid_depth = the camera z of the key frame's local cuboids.  Returns the extended (mvKeysHarris pt, mvpMapPointsHarris, keypoint_associate_objectID_harris),
+        the new points' positions and the call's dict; the new map points get the ids next_point_id, next_point_id + 1, ...  `new MapPoint` and SetupSimpleMapPoints
+        stay the caller's.  ctx=None: on the host; tracker: a KLTTracker that holds the frame at index `frame`."""
+        from .klt import NewHarrisFeatures
+        pts = np.asarray(mvKeysHarris_pt, np.float32).reshape(-1, 2)
+        mps = np.asarray([-1 if m is None else m for m in mvpMapPointsHarris], np.int64).reshape(-1)
+        ids = np.asarray(object_id_harris, np.int32).reshape(-1)
+        has = mps >= 0  # `pMP && pMP->is_dynamic`: every Harris map point is dynamic
+        args = ([np.asarray(objmask_img, np.uint8)], [pts[has]], [np.asarray(observations, np.int32).reshape(-1)[has]], K4, np.asarray(Twc, np.float32).reshape(-1)[None, :12],
+                [cuboid_depth])
+        r = (tracker.new_harris_features([frame], *args) if tracker is not None else NewHarrisFeatures(np.asarray(gray, np.uint8), *args, ctx=ctx))[0]
+        new_ids = np.arange(int(next_point_id), int(next_point_id) + len(r["pts"]), dtype=np.int64)
+        return np.concatenate([pts, r["pts"]]), np.concatenate([mps, new_ids]), np.concatenate([ids, r["object_id"]]), r["x3D"], r
+
     def close(self):
         self.matcher.close()

@@ -360,6 +360,44 @@ int cs_match_by_tracking_harris_host(const uint8_t *gray, int n_frames, int widt
                                      float *kept_pts, int *object_id, int *goodmatches, int *n_mask_outside);
 /* (cs_match_by_tracking, ORBmatcher::SearchByTracking over the same tracker, is declared behind cs_matcher below.) */
 
+/* ----- new dynamic-object points: cv::goodFeaturesToTrack and the new-feature loop of Tracking::CreateNewKeyFrame (orb_object_slam/src/Tracking.cc:2258-2337)
+ * cv::goodFeaturesToTrack(raw_img, corners, 200, 0.1, MIN_DIST, good_mask) of Tracking.cc:2292 for n frames a KLT handle holds: frames[s] = an index of the last
+ * cs_klt_set_frames (level 0 of the pyramid is raw_img and is read in place), masks = n dense images of the frames' size or NULL (every pixel counts).  8 bits, one
+ * channel, blockSize 3, Sobel aperture 3, minimum eigenvalue; useHarrisDetector is not built.  Like cs_klt_track the function is a stated definition (INTEGRATION.md 4e,
+ * the plain C++ branches of OpenCV 3.4), and every result equals that statement bit for bit.
+ * corners: room for n * max_corners points (x, y floats), frame s at corners + 2 * max_corners * s in the order of acceptance; quality (may be NULL): the thresholded
+ * eigenvalue of each corner, likewise; counts[s] = the corners of frame s, n_candidates[s] = its local maxima above the threshold inside the mask.
+ * CS_ERR_BAD_ARG: max_corners < 1; min_distance < 1 (or not finite); quality_level outside (0, 1]; a frame index that is not set; a null argument.
+ * CS_ERR_CAPACITY: a frame with more than CS_GFTT_MAX_CANDIDATES candidates (n_candidates is filled, counts are 0).  The handle stays usable after either. */
+#define CS_GFTT_MAX_CANDIDATES 8192
+int cs_klt_good_features(cs_ctx *ctx, cs_klt *h, int n, const int *frames, const uint8_t *masks, int max_corners, double quality_level, double min_distance, float *corners,
+                         float *quality, int *counts, int *n_candidates);
+/* The same on the device for n images the caller passes (width x height, rows stride_bytes apart, image s at gray + s * height * stride_bytes), of any size: an
+ * image with width < 3 or height < 3 has no corner. */
+int cs_good_features_images(cs_ctx *ctx, const uint8_t *gray, int n, int width, int height, long stride_bytes, const uint8_t *masks, int max_corners, double quality_level,
+                            double min_distance, float *corners, float *quality, int *counts, int *n_candidates);
+/* The same statement on the host, without a context (the comparison side). */
+int cs_klt_good_features_host(const uint8_t *gray, int n, int width, int height, long stride_bytes, const uint8_t *masks, int max_corners, double quality_level, double min_distance,
+                              float *corners, float *quality, int *counts, int *n_candidates);
+/* Tracking.cc:2263-2331 for n resident frames with the reference's constants (MIN_DIST = 10, 200 corners, quality 0.1): good_mask from objmasks (n dense objmask_img,
+ * 0 background, > 0 object id + 1) with the disc of cv::circle(good_mask, pt, 10, 0, -1) erased around the existing points, goodFeaturesToTrack on it, and
+ * KeyFrame::UnprojectPixelDepth (src/KeyFrame.cc:711-727) of every new corner at its cuboid's depth.
+ * Frame s has the existing points exist_first[s] .. exist_first[s + 1]: exist_pts = mvKeysHarris[i].pt and exist_obs = pMP->Observations() of the points with
+ * `pMP && pMP->is_dynamic` (:2270-2277).  They are walked by observations descending, equal counts by ascending index (the reference's std::sort leaves ties open).
+ * K4 = fx, fy, cx, cy; Twc = 12 floats per frame (the 3 x 4 rows of the key frame's Twc); cuboid_depth[cub_first[s] + id] = (float)local_cuboids[id]->cube_meas.translation()[2].
+ * Outputs, frame s at new_first[s] .. new_first[s + 1] (room for 200 n entries): new_pts = the corners, new_object_id = maskval - 1, new_x3D (3 floats) and x3D_valid
+ * (0 where the depth is not > 0: the reference returns an empty Mat, here the position is zeros).  n_mask_outside[s] (may be NULL): DEVIATION, existing points whose
+ * index cvRound(y) * cols + cvRound(x) is outside [0, rows * cols), where the reference reads beyond the image; they are skipped.  good_masks (may be NULL): the n masks
+ * that were built, for inspection.  n_candidates (may be NULL): as above.
+ * CS_ERR_BAD_ARG: an existing point that is not finite (or beyond 1e9 in magnitude); a frame index that is not set; offsets that do not start at 0 or decrease; a null
+ * argument; a corner whose object id is at or beyond its frame's cuboid count (the reference indexes local_cuboids out of bounds).  CS_ERR_CAPACITY: as above. */
+int cs_track_new_harris_features(cs_ctx *ctx, cs_klt *h, int n, const int *frames, const uint8_t *objmasks, const int *exist_first, const float *exist_pts, const int *exist_obs,
+                                 const float *K4, const float *Twc, const int *cub_first, const float *cuboid_depth, int *new_first, float *new_pts, int *new_object_id, float *new_x3D,
+                                 uint8_t *x3D_valid, int *n_mask_outside, uint8_t *good_masks, int *n_candidates);
+int cs_track_new_harris_features_host(const uint8_t *gray, int n, int width, int height, long stride_bytes, const uint8_t *objmasks, const int *exist_first, const float *exist_pts,
+                                      const int *exist_obs, const float *K4, const float *Twc, const int *cub_first, const float *cuboid_depth, int *new_first, float *new_pts,
+                                      int *new_object_id, float *new_x3D, uint8_t *x3D_valid, int *n_mask_outside, uint8_t *good_masks, int *n_candidates);
+
 /* ===================================================================== ORBmatcher
  * Replaces the Hamming searches of ORB_SLAM2::ORBmatcher (orb_object_slam/include/ORBmatcher.h:43-89, src/ORBmatcher.cc)
  * and the Frame grid they use (src/Frame.cc:303-318 AssignFeaturesToGrid, :404-459 GetFeaturesInArea, :525-535 PosInGrid).

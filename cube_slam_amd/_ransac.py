@@ -1,12 +1,6 @@
 """What the two batched-RANSAC mirrors (sim3_solver.py, pnp_solver.py) share on the Python side: the CSR batch (corr_off, hyp_off), the mask layout of
 include/cubeslam_hip.h -- correspondence i is bit i & 31 of word i >> 5, ceil(N / 32) words per hypothesis --, and the reference's partial Fisher-Yates."""
-import ctypes as C
-
 import numpy as np
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 def f32(a):

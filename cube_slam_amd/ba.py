@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 
 
 class BAProblem(C.Structure):
@@ -65,8 +65,9 @@ def shard_landmarks(n_points, rank, world):
     return n_points * rank // world, n_points * (rank + 1) // world
 
 
-class BundleAdjuster:
+class BundleAdjuster(Handle):
     """g2o::SparseOptimizer + OptimizationAlgorithmLevenberg + BlockSolver_6_3 on the GPU."""
+    HANDLE, DESTROY = "_b", "cs_ba_destroy"
 
     def __init__(self, problem, ctx=None, device=0, rank=0, world=1, allreduce=None):
         self.ctx = ctx or _lib.Context(device)
@@ -101,31 +102,19 @@ class BundleAdjuster:
 
     def read(self):
         cam = np.zeros((self.p.n_cams, 7)); pts = np.array(self.d["points"], np.float64).copy().reshape(-1, 3); cub = np.zeros((max(self.p.n_cuboids, 1), 7))
-        check(self.ctx.ptr, lib().cs_ba_read(self.ctx.ptr, self._b, cam.ctypes.data_as(C.c_void_p), pts.ctypes.data_as(C.c_void_p), cub.ctypes.data_as(C.c_void_p)), "cs_ba_read")
+        check(self.ctx.ptr, lib().cs_ba_read(self.ctx.ptr, self._b, ptr(cam), ptr(pts), ptr(cub)), "cs_ba_read")
         return cam, pts, cub[:self.p.n_cuboids]
 
     def errors(self):
         chi = C.c_double()
         eo = np.zeros((max(self.p.n_obs, 1), 3)); ec = np.zeros((max(self.p.n_cobs, 1), 4)); ep = np.zeros((max(self.p.n_pc, 1), 3))
-        check(self.ctx.ptr, lib().cs_ba_errors(self.ctx.ptr, self._b, C.byref(chi), eo.ctypes.data_as(C.c_void_p), ec.ctypes.data_as(C.c_void_p),
-                                               ep.ctypes.data_as(C.c_void_p)), "cs_ba_errors")
+        check(self.ctx.ptr, lib().cs_ba_errors(self.ctx.ptr, self._b, C.byref(chi), ptr(eo), ptr(ec), ptr(ep)), "cs_ba_errors")
         return chi.value, eo[:self.p.n_obs], ec[:self.p.n_cobs], ep[:self.p.n_pc]
 
     def reduced_dense(self, lam):
         P = int((1 - np.asarray(self.d["cam_fixed"])).sum()) + self.p.n_cuboids
         H = np.zeros((6 * P, 6 * P)); b = np.zeros(6 * P); Pout = C.c_int()
-        check(self.ctx.ptr, lib().cs_ba_reduced_dense(self.ctx.ptr, self._b, C.c_double(lam), H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(Pout)),
+        check(self.ctx.ptr, lib().cs_ba_reduced_dense(self.ctx.ptr, self._b, lam, ptr(H), ptr(b), C.byref(Pout)),
               "cs_ba_reduced_dense")
         assert Pout.value == P
         return H, b
-
-    def close(self):
-        if self._b:
-            lib().cs_ba_destroy(self.ctx.ptr, self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

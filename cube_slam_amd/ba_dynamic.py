@@ -29,7 +29,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 from .ba import BAStats
 
 
@@ -120,8 +120,9 @@ def second_stage_problem(d, errors):
     return d2
 
 
-class DynamicBundleAdjuster:
+class DynamicBundleAdjuster(Handle):
     """g2o::SparseOptimizer + OptimizationAlgorithmLevenberg + BlockSolverX / LinearSolverDense on the GPU for one stage of the dynamic BA."""
+    HANDLE, DESTROY = "_b", "cs_ba_dyn_destroy"
 
     def __init__(self, problem, ctx=None, device=0):
         self.ctx = ctx or _lib.Context(device)
@@ -142,7 +143,7 @@ class DynamicBundleAdjuster:
 
     def read(self):
         out = [np.zeros((max(n, 1), k)) for n, k in self._shapes()]
-        check(self.ctx.ptr, lib().cs_ba_dyn_read(self.ctx.ptr, self._b, *[a.ctypes.data_as(C.c_void_p) for a in out]), "cs_ba_dyn_read")
+        check(self.ctx.ptr, lib().cs_ba_dyn_read(self.ctx.ptr, self._b, *[ptr(a) for a in out]), "cs_ba_dyn_read")
         return dict(zip(("cam_pose", "obj_pose", "vel", "points", "dpoints"), [a[:n] for a, (n, _) in zip(out, self._shapes())]))
 
     def errors(self):
@@ -150,27 +151,16 @@ class DynamicBundleAdjuster:
         sh = ((p.n_obs, 3), (p.n_dobs, 2), (p.n_mot, 3), (p.n_cobs, 4), (p.n_pc, 3), (p.n_dpoints, 3))
         e = [np.zeros((max(n, 1), k)) for n, k in sh]
         chi = C.c_double()
-        check(self.ctx.ptr, lib().cs_ba_dyn_errors(self.ctx.ptr, self._b, C.byref(chi), *[a.ctypes.data_as(C.c_void_p) for a in e]), "cs_ba_dyn_errors")
+        check(self.ctx.ptr, lib().cs_ba_dyn_errors(self.ctx.ptr, self._b, C.byref(chi), *[ptr(a) for a in e]), "cs_ba_dyn_errors")
         return chi.value, dict(zip(("obs", "dobs", "mot", "cobs", "pc", "ulp"), [a[:n] for a, (n, _) in zip(e, sh)]))
 
     def reduced_dense(self, lam):
         n = C.c_int()
-        check(self.ctx.ptr, lib().cs_ba_dyn_reduced_dense(self.ctx.ptr, self._b, C.c_double(lam), None, None, C.byref(n)), "cs_ba_dyn_reduced_dense")
+        check(self.ctx.ptr, lib().cs_ba_dyn_reduced_dense(self.ctx.ptr, self._b, lam, None, None, C.byref(n)), "cs_ba_dyn_reduced_dense")
         H = np.zeros((max(n.value, 1), max(n.value, 1))); b = np.zeros(max(n.value, 1))
-        check(self.ctx.ptr, lib().cs_ba_dyn_reduced_dense(self.ctx.ptr, self._b, C.c_double(lam), H.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(n)),
+        check(self.ctx.ptr, lib().cs_ba_dyn_reduced_dense(self.ctx.ptr, self._b, lam, ptr(H), ptr(b), C.byref(n)),
               "cs_ba_dyn_reduced_dense")
         return H[:n.value, :n.value], b[:n.value]
-
-    def close(self):
-        if self._b:
-            lib().cs_ba_dyn_destroy(self.ctx.ptr, self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def erase_rows(d1, e1, d2, fin, e2):

@@ -6,13 +6,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Context, CubeSlamError, check, lib
+from ._lib import Context, CubeSlamError, Handle, check, lib, ptr
 
 F32 = np.float32
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 class BowVector(dict):
@@ -51,7 +47,9 @@ def parse_vocabulary_text(text):
     return k, L, n1, n2, parent, is_leaf, desc, weight
 
 
-class ORBVocabulary:
+class ORBVocabulary(Handle):
+    HANDLE, DESTROY = "_v", "cs_bow_vocab_destroy"
+
     def __init__(self, k=None, L=None, parent=None, is_leaf=None, desc=None, weight=None, levelsup=4, scoring=0, weighting=0, ctx=None):
         self.ctx = ctx
         self._v = C.c_void_p()
@@ -66,12 +64,12 @@ class ORBVocabulary:
         n = len(parent)
         if not (len(is_leaf) == len(desc) == len(weight) == n):
             raise CubeSlamError("ORBVocabulary: parent, is_leaf, desc and weight are one entry per node")
-        if lib().cs_bow_vocab_check(int(k), int(L), n, _p(parent, C.c_int), _p(is_leaf, C.c_uint8), self.levelsup, int(weighting), int(scoring)) != 0:  # needs no device
+        if lib().cs_bow_vocab_check(int(k), int(L), n, ptr(parent), ptr(is_leaf), self.levelsup, int(weighting), int(scoring)) != 0:  # needs no device
             raise CubeSlamError("cs_bow_vocab_create refuses this vocabulary: CS_ERR_BAD_ARG (only TF_IDF / L1; k 2..20, L 1..10; parent < node; leaf flag = no children; "
                                 "no leaf above level L - levelsup; at most k children)")
         if self.ctx is None:
             self.ctx = Context(0)
-        check(self.ctx.ptr, lib().cs_bow_vocab_create(self.ctx.ptr, int(k), int(L), n, _p(parent, C.c_int), _p(is_leaf, C.c_uint8), _p(desc, C.c_uint8), _p(weight, C.c_double),
+        check(self.ctx.ptr, lib().cs_bow_vocab_create(self.ctx.ptr, int(k), int(L), n, ptr(parent), ptr(is_leaf), ptr(desc), ptr(weight),
                                                       self.levelsup, int(weighting), int(scoring), C.byref(self._v)), "cs_bow_vocab_create")
         self.k, self.L, self.n_nodes = int(k), int(L), n
         nw = C.c_int()
@@ -96,8 +94,8 @@ class ORBVocabulary:
         desc = np.concatenate(frames) if n else np.zeros((1, 32), np.uint8)
         word = np.zeros(max(n, 1), np.int32); node = np.zeros(max(n, 1), np.int32); cnt = np.zeros(max(len(frames), 1), np.int32)
         bw = np.zeros(max(n, 1), np.int32); bv = np.zeros(max(n, 1), np.float64)
-        check(self.ctx.ptr, lib().cs_bow_transform(self.ctx.ptr, self._v, len(frames), _p(off, C.c_int), _p(desc, C.c_uint8), _p(word, C.c_int), _p(node, C.c_int), _p(cnt, C.c_int),
-                                                   _p(bw, C.c_int), _p(bv, C.c_double)), "cs_bow_transform")
+        check(self.ctx.ptr, lib().cs_bow_transform(self.ctx.ptr, self._v, len(frames), ptr(off), ptr(desc), ptr(word), ptr(node), ptr(cnt),
+                                                   ptr(bw), ptr(bv)), "cs_bow_transform")
         return off, word[:n], node[:n], cnt[:len(frames)], bw[:n], bv[:n]
 
     def transform_batch(self, descriptors_per_frame):
@@ -131,23 +129,11 @@ class ORBVocabulary:
         pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
         pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
         out = np.zeros(max(len(pairs), 1), np.float64)
-        check(self.ctx.ptr, lib().cs_bow_score(self.ctx.ptr, len(arrs), _p(off, C.c_int), _p(w, C.c_int), _p(x, C.c_double), len(pairs), _p(pa, C.c_int), _p(pb, C.c_int),
-                                               _p(out, C.c_double)), "cs_bow_score")
+        check(self.ctx.ptr, lib().cs_bow_score(self.ctx.ptr, len(arrs), ptr(off), ptr(w), ptr(x), len(pairs), ptr(pa), ptr(pb), ptr(out)), "cs_bow_score")
         return out[:len(pairs)]
 
     def score(self, v1, v2):
         return float(self.score_pairs([v1, v2], [(0, 1)])[0])
-
-    def close(self):
-        if self._v:
-            lib().cs_bow_vocab_destroy(self._v)
-            self._v = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _KFState:
@@ -252,8 +238,9 @@ def _retain(acc, bestAcc):
     return out
 
 
-class KeyFrameDatabase:
+class KeyFrameDatabase(Handle):
     """The key frames' BowVectors resident on the device (cs_bow_db_*), with the reference's per-key-frame query fields on the host."""
+    HANDLE, DESTROY = "_db", "cs_bow_db_destroy"
 
     def __init__(self, ctx=None):
         self.ctx = ctx if ctx is not None else Context(0)
@@ -263,11 +250,11 @@ class KeyFrameDatabase:
 
     def add(self, kf_id, bow):
         w, x = BowVector(bow).arrays()
-        check(self.ctx.ptr, lib().cs_bow_db_add(self.ctx.ptr, self._db, C.c_long(int(kf_id)), len(w), _p(w, C.c_int), _p(x, C.c_double)), "cs_bow_db_add")
+        check(self.ctx.ptr, lib().cs_bow_db_add(self.ctx.ptr, self._db, int(kf_id), len(w), ptr(w), ptr(x)), "cs_bow_db_add")
         self.state[int(kf_id)]
 
     def erase(self, kf_id):
-        check(self.ctx.ptr, lib().cs_bow_db_erase(self._db, C.c_long(int(kf_id))), "cs_bow_db_erase")
+        check(self.ctx.ptr, lib().cs_bow_db_erase(self._db, int(kf_id)), "cs_bow_db_erase")
 
     def clear(self):
         check(self.ctx.ptr, lib().cs_bow_db_clear(self._db), "cs_bow_db_clear")
@@ -288,8 +275,8 @@ class KeyFrameDatabase:
         oq = np.zeros(cap, np.int32); oid = np.zeros(cap, np.int64); oord = np.zeros(cap, np.int64); oc = np.zeros(cap, np.int32); om = np.zeros(cap, np.int32)
         osc = np.zeros(cap, np.float64)
         n = C.c_long()
-        check(self.ctx.ptr, lib().cs_bow_db_query(self.ctx.ptr, self._db, len(arrs), _p(off, C.c_int), _p(w, C.c_int), _p(x, C.c_double), C.c_long(cap), C.byref(n), _p(oq, C.c_int),
-                                                  _p(oid, C.c_long), _p(oord, C.c_long), _p(oc, C.c_int), _p(om, C.c_int), _p(osc, C.c_double)), "cs_bow_db_query")
+        check(self.ctx.ptr, lib().cs_bow_db_query(self.ctx.ptr, self._db, len(arrs), ptr(off), ptr(w), ptr(x), cap, C.byref(n), ptr(oq),
+                                                  ptr(oid), ptr(oord), ptr(oc), ptr(om), ptr(osc)), "cs_bow_db_query")
         n = n.value
         return oq[:n], oid[:n], oord[:n], oc[:n], om[:n], osc[:n]
 
@@ -306,14 +293,3 @@ class KeyFrameDatabase:
 
     def DetectRelocalizationCandidates(self, query_id, bow, best_covisibles):
         return candidates_reloc(self.state, self.query([bow])[0], int(query_id), best_covisibles)
-
-    def close(self):
-        if self._db:
-            lib().cs_bow_db_destroy(self._db)
-            self._db = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 
 
 
@@ -41,10 +41,6 @@ CUBOID_DTYPE = np.dtype([
     ("edge_distance_error", "f8"), ("edge_angle_error", "f8"), ("normalized_error", "f8"),
     ("skew_ratio", "f8"), ("down_expand_height", "f8"), ("camera_roll_delta", "f8"),
     ("camera_pitch_delta", "f8")], align=True)
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 class detect_3d_cuboid:
@@ -94,15 +90,15 @@ class detect_3d_cuboid:
         out = np.zeros((max(nb, 1), self.max_cuboid_num), CUBOID_DTYPE)
         counts = np.zeros(max(nb, 1), np.int32)
         o = self.opts()
-        r = lib().cs_cuboid_detect(self.ctx.ptr, _p(img, C.c_uint8), W, H, ch, W * ch, _p(self.Kalib, C.c_double), _p(T, C.c_double),
-                                   _p(boxes, C.c_double), nb, _p(lines, C.c_double), len(lines), C.byref(o),
-                                   out.ctypes.data_as(C.c_void_p), _p(counts, C.c_int))
+        r = lib().cs_cuboid_detect(self.ctx.ptr, ptr(img), W, H, ch, W * ch, ptr(self.Kalib), ptr(T), ptr(boxes), nb, ptr(lines), len(lines), C.byref(o),
+                                   ptr(out), ptr(counts))
         check(self.ctx.ptr, r, "cs_cuboid_detect")
         return [out[i, :counts[i]].copy() for i in range(nb)]
 
 
-class CuboidBatch:
+class CuboidBatch(Handle):
     """Device-resident batch (BASELINE config 4): frames stay in HBM, run() only launches kernels."""
+    HANDLE, DESTROY = "_b", "cs_cuboid_batch_destroy"
 
     def __init__(self, ctx, grays, K, Twcs, boxes_list, lines_list, opts):
         self.ctx = ctx
@@ -120,8 +116,7 @@ class CuboidBatch:
         self.n_boxes = int(bo[-1])
         self.max_cuboid_num = opts.max_cuboid_num
         self._b = C.c_void_p()
-        r = lib().cs_cuboid_batch_create(ctx.ptr, self.F, self.W, self.H, _p(grays, C.c_uint8), _p(K, C.c_double), _p(T, C.c_double),
-                                         _p(bo, C.c_int), _p(boxes, C.c_double), _p(lo, C.c_int), _p(lines, C.c_double),
+        r = lib().cs_cuboid_batch_create(ctx.ptr, self.F, self.W, self.H, ptr(grays), ptr(K), ptr(T), ptr(bo), ptr(boxes), ptr(lo), ptr(lines),
                                          C.byref(opts), C.byref(self._b))
         check(ctx.ptr, r, "cs_cuboid_batch_create")
 
@@ -131,7 +126,7 @@ class CuboidBatch:
         for f in range(self.F):
             lo[f + 1] = lo[f] + len(lines_list[f])
         lines = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float64).reshape(-1, 4) for l in lines_list] + [np.zeros((1, 4))]))
-        check(self.ctx.ptr, lib().cs_cuboid_batch_set_lines(self.ctx.ptr, self._b, _p(lo, C.c_int), _p(lines, C.c_double)), "cs_cuboid_batch_set_lines")
+        check(self.ctx.ptr, lib().cs_cuboid_batch_set_lines(self.ctx.ptr, self._b, ptr(lo), ptr(lines)), "cs_cuboid_batch_set_lines")
 
     @staticmethod
     def pack_scene(Twcs, boxes_list, lines_list=None):
@@ -154,8 +149,7 @@ class CuboidBatch:
         """Other boxes, poses and (lines_list given) edge lists for the frames of the batch: what every detect_cuboid call brings with its pixels (cs_cuboid_batch_set_scene)."""
         T, bo, boxes, lo, lines = packed if packed is not None else self.pack_scene(Twcs, boxes_list, lines_list)
         assert len(bo) == self.F + 1
-        check(self.ctx.ptr, lib().cs_cuboid_batch_set_scene(self.ctx.ptr, self._b, _p(T, C.c_double), _p(bo, C.c_int), _p(boxes, C.c_double), None if lo is None else _p(lo, C.c_int),
-                                                            None if lines is None else _p(lines, C.c_double)), "cs_cuboid_batch_set_scene")
+        check(self.ctx.ptr, lib().cs_cuboid_batch_set_scene(self.ctx.ptr, self._b, ptr(T), ptr(bo), ptr(boxes), ptr(lo), ptr(lines)), "cs_cuboid_batch_set_scene")
         self.n_boxes = int(bo[-1])
 
     def set_shared_gpu(self, shared):
@@ -168,7 +162,7 @@ class CuboidBatch:
     def read(self):
         out = np.zeros((max(self.n_boxes, 1), self.max_cuboid_num), CUBOID_DTYPE)
         counts = np.zeros(max(self.n_boxes, 1), np.int32)
-        check(self.ctx.ptr, lib().cs_cuboid_batch_read(self.ctx.ptr, self._b, out.ctypes.data_as(C.c_void_p), _p(counts, C.c_int)),
+        check(self.ctx.ptr, lib().cs_cuboid_batch_read(self.ctx.ptr, self._b, ptr(out), ptr(counts)),
               "cs_cuboid_batch_read")
         return [out[i, :counts[i]].copy() for i in range(self.n_boxes)]
 
@@ -190,19 +184,7 @@ class CuboidBatch:
         dist = np.zeros((h, w), np.float32)
         rows = np.zeros((max(nvalid, 1), 25), np.float64)
         merged = np.zeros((max(nmerged, 1), 4), np.float64)
-        check(self.ctx.ptr, lib().cs_cuboid_batch_unit(self.ctx.ptr, self._b, u, dims, _p(edges, C.c_uint8), _p(dist, C.c_float),
-                                                       _p(rows, C.c_double), max(nvalid, 1), _p(merged, C.c_double), max(nmerged, 1)),
+        check(self.ctx.ptr, lib().cs_cuboid_batch_unit(self.ctx.ptr, self._b, u, dims, ptr(edges), ptr(dist), ptr(rows), max(nvalid, 1), ptr(merged), max(nmerged, 1)),
               "cs_cuboid_batch_unit")
         return {"roi": (x, y, w, h), "frame": frame, "box": box, "hs": hs, "n_hs": n_hs, "n_valid": nvalid, "n_yaw": nyaw, "edges": edges, "dist": dist, "rows": rows[:nvalid],
                 "merged": merged[:nmerged]}
-
-    def close(self):
-        if self._b:
-            lib().cs_cuboid_batch_destroy(self.ctx.ptr, self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -2,10 +2,12 @@
 context, LSD + LBD on worker threads with their own contexts.  Plumbing for bench.py and the tests."""
 import ctypes as C
 
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 
 
-class Frontend:
+class Frontend(Handle):
+    HANDLE, DESTROY = "_fe", "cs_frontend_destroy"
+
     def __init__(self, ctx, orb=None, batch=None, line_detectors=(), phased=False):
         """line_detectors: line_lbd_detect objects, each created on its own Context and holding the same uploaded frames.
         phased: the detectors' device region stages run together after one pass per detector, with the caller's stream idle
@@ -25,7 +27,7 @@ class Frontend:
 
     def set_chain(self, on, length_thres=15.0):
         """The reference's chain, pipelined: the cuboid pass of step k takes the lines of line pass k - W (cs_frontend_set_chain)."""
-        check(self.ctx.ptr, lib().cs_frontend_set_chain(self._fe, 1 if on else 0, C.c_float(length_thres)), "cs_frontend_set_chain")
+        check(self.ctx.ptr, lib().cs_frontend_set_chain(self._fe, 1 if on else 0, length_thres), "cs_frontend_set_chain")
 
     def set_cuboid_ctx(self, ctx):
         """The cuboid batch on its own Context (stream), beside the ORB pass of the same step (cs_frontend_set_cuboid_ctx); None: the caller's stream."""
@@ -51,16 +53,13 @@ class Frontend:
     def stream_push(self, gray):
         """The frames (uint8, C-contiguous; pinned memory makes this asynchronous) of the next step that has none yet.  The array must stay alive until that step has run."""
         assert gray.dtype.name == "uint8" and gray.flags["C_CONTIGUOUS"]
-        check(self.ctx.ptr, lib().cs_frontend_stream_push(self._fe, gray.ctypes.data_as(C.POINTER(C.c_uint8))), "cs_frontend_stream_push")
+        check(self.ctx.ptr, lib().cs_frontend_stream_push(self._fe, ptr(gray)), "cs_frontend_stream_push")
 
     def stream_push_scene(self, gray, packed):
         """stream_push with the frames' poses, boxes and (optionally) edge lists: packed = CuboidBatch.pack_scene(...) (cs_frontend_stream_push_scene; the runner copies them)."""
         assert gray.dtype.name == "uint8" and gray.flags["C_CONTIGUOUS"]
         T, bo, boxes, lo, lines = packed
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))  # noqa: E731
-        check(self.ctx.ptr, lib().cs_frontend_stream_push_scene(self._fe, gray.ctypes.data_as(C.POINTER(C.c_uint8)), dp(T), ip(bo), dp(boxes), None if lo is None else ip(lo),
-                                                                None if lines is None else dp(lines)), "cs_frontend_stream_push_scene")
+        check(self.ctx.ptr, lib().cs_frontend_stream_push_scene(self._fe, ptr(gray), ptr(T), ptr(bo), ptr(boxes), ptr(lo), ptr(lines)), "cs_frontend_stream_push_scene")
         if self.batch is not None:
             self.batch.n_boxes = int(bo[-1])
 
@@ -69,12 +68,11 @@ class Frontend:
         (KEYPOINT_DTYPE) / desc ((n, 32) uint8) packed over the frames, cuboids ((n_boxes, max_cuboid_num) CUBOID_DTYPE) / counts (int32).  Returns (first, total) of the
         packed key points (or None).  stream_read_wait() before the arrays are read."""
         import numpy as np
-        first, total = None, C.c_long(0)
+        first, total = None, C.c_long()
         if kps is not None:
             first = np.zeros(self.orb.n_frames + 1, np.int32)
-        check(self.ctx.ptr, lib().cs_frontend_stream_read_async(self._fe, None if kps is None else kps.ctypes.data_as(C.c_void_p), None if desc is None else desc.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                                0 if kps is None else len(kps), None if first is None else first.ctypes.data_as(C.POINTER(C.c_int)), C.byref(total),
-                                                                None if cuboids is None else cuboids.ctypes.data_as(C.c_void_p), None if counts is None else counts.ctypes.data_as(C.POINTER(C.c_int))),
+        check(self.ctx.ptr, lib().cs_frontend_stream_read_async(self._fe, ptr(kps), ptr(desc), 0 if kps is None else len(kps), ptr(first), C.byref(total),
+                                                                ptr(cuboids), ptr(counts)),
               "cs_frontend_stream_read_async")
         return first, total.value
 
@@ -89,14 +87,3 @@ class Frontend:
 
     def drain(self):
         check(self.ctx.ptr, lib().cs_frontend_drain(self._fe), "cs_frontend_drain")
-
-    def close(self):
-        if self._fe:
-            lib().cs_frontend_destroy(self._fe)
-            self._fe = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -7,8 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CubeSlamError, check, lib
-from ._ransac import _p, batch, cat, draw, f32, i32, mask_bits, offsets
+from ._lib import CubeSlamError, check, lib, ptr
+from ._ransac import batch, cat, draw, f32, i32, mask_bits, offsets
 
 MODEL_NONE, MODEL_H, MODEL_F = -1, 0, 1
 MAX_CAND = 8
@@ -19,10 +19,8 @@ def walk(model, n_cand, nGood, cos_parallax, N, minParallax=1.0, minTriangulated
     g, c = np.ascontiguousarray(nGood, np.int32), np.ascontiguousarray(cos_parallax, np.float32)
     if len(g) < MAX_CAND or len(c) < MAX_CAND:
         raise ValueError("nGood and cos_parallax hold %d entries" % MAX_CAND)
-    f = lib().cs_initializer_walk
-    f.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float)]
-    par = C.c_float(0)
-    return f(int(model), int(n_cand), _p(g, C.c_int), _p(c, C.c_float), int(N), float(minParallax), int(minTriangulated), C.byref(par)), np.float32(par.value)
+    par = C.c_float()
+    return lib().cs_initializer_walk(int(model), int(n_cand), ptr(g), ptr(c), int(N), float(minParallax), int(minTriangulated), C.byref(par)), np.float32(par.value)
 
 
 def initializer_evaluate(ctx, key1_off, keys1, key2_off, keys2, corr_off, matches12, K9, sigma, hyp_off, sets):
@@ -45,11 +43,11 @@ def initializer_evaluate(ctx, key1_off, keys1, key2_off, keys2, corr_off, matche
            "points": np.zeros(max(24 * max(NC, 0), 1), np.float32)}
     cp = ctx.ptr if ctx is not None else None
     o = out
-    check(cp, lib().cs_initializer_evaluate(cp, n, _p(k1o, C.c_int), _p(a1, C.c_float), _p(k2o, C.c_int), _p(a2, C.c_float), _p(co, C.c_int), _p(mt, C.c_int), _p(k9, C.c_float),
-                                            _p(sg, C.c_float), _p(ho, C.c_int), _p(st, C.c_int), _p(o["score"], C.c_float), _p(o["matrix"], C.c_float), _p(o["mask"], C.c_uint32),
-                                            _p(o["model"], C.c_int), _p(o["best"], C.c_int), _p(o["S"], C.c_float), _p(o["RH"], C.c_float), _p(o["n_inliers"], C.c_int),
-                                            _p(o["n_cand"], C.c_int), _p(o["cand_Rt"], C.c_float), _p(o["nGood"], C.c_int), _p(o["cos_parallax"], C.c_float),
-                                            _p(o["good_mask"], C.c_uint32), _p(o["points"], C.c_float)), "cs_initializer_evaluate")
+    check(cp, lib().cs_initializer_evaluate(cp, n, ptr(k1o), ptr(a1), ptr(k2o), ptr(a2), ptr(co), ptr(mt), ptr(k9),
+                                            ptr(sg), ptr(ho), ptr(st), ptr(o["score"]), ptr(o["matrix"]), ptr(o["mask"]),
+                                            ptr(o["model"]), ptr(o["best"]), ptr(o["S"]), ptr(o["RH"]), ptr(o["n_inliers"]),
+                                            ptr(o["n_cand"]), ptr(o["cand_Rt"]), ptr(o["nGood"]), ptr(o["cos_parallax"]),
+                                            ptr(o["good_mask"]), ptr(o["points"])), "cs_initializer_evaluate")
     out["score"] = out["score"][:2 * H].reshape(2, H)
     out["matrix"] = out["matrix"][:18 * H].reshape(2, H, 9)
     out["mask"] = out["mask"][:2 * words].reshape(2, words)

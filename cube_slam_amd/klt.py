@@ -5,11 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+from ._lib import Handle, check, lib, ptr
 
 
 def _frames(gray):
@@ -58,8 +54,9 @@ def _masks(masks, n_pairs, H, W):
     return m
 
 
-class KLTTracker:
+class KLTTracker(Handle):
     """cs_klt wrapper: room for max_frames 8-bit images of at most max_width x max_height and max_points points per call."""
+    HANDLE, DESTROY = "_h", "cs_klt_destroy"
 
     def __init__(self, max_frames, max_width, max_height, max_points, ctx=None, device=0):
         self.ctx = ctx or _lib.Context(device)
@@ -70,7 +67,7 @@ class KLTTracker:
     def set_frames(self, gray):
         """Pyramids and derivatives of the frames [F, H, W] (or one [H, W]); the rows may be strided."""
         g = _frames(gray)
-        check(self.ctx.ptr, lib().cs_klt_set_frames(self.ctx.ptr, self._h, len(g), g.shape[2], g.shape[1], _p(g, C.c_uint8), C.c_long(g.strides[1])), "cs_klt_set_frames")
+        check(self.ctx.ptr, lib().cs_klt_set_frames(self.ctx.ptr, self._h, len(g), g.shape[2], g.shape[1], ptr(g), g.strides[1]), "cs_klt_set_frames")
         self.n_frames, self.H, self.W = g.shape
 
     @property
@@ -83,15 +80,15 @@ class KLTTracker:
         for _ in range(level):
             w, h = (w + 1) // 2, (h + 1) // 2
         img, der = np.zeros((h + 42, w + 42), np.uint8), np.zeros((h + 42, w + 42, 2), np.int16)
-        check(self.ctx.ptr, lib().cs_klt_read_level(self.ctx.ptr, self._h, int(frame), int(level), _p(img, C.c_uint8), _p(der, C.c_int16)), "cs_klt_read_level")
+        check(self.ctx.ptr, lib().cs_klt_read_level(self.ctx.ptr, self._h, int(frame), int(level), ptr(img), ptr(der)), "cs_klt_read_level")
         return img, der
 
     def track(self, pairs, pts):
         """calcOpticalFlowPyrLK for every pair (prev frame, next frame) of `pairs` over its points: [(nextPts, status, err)] per pair."""
         pp, pn, first, flat = _pairs(pairs, pts)
         nxt, st, er = _outputs(len(flat))
-        check(self.ctx.ptr, lib().cs_klt_track(self.ctx.ptr, self._h, len(pp), _p(pp, C.c_int), _p(pn, C.c_int), _p(first, C.c_int), _p(flat if len(flat) else nxt, C.c_float),
-                                               _p(nxt, C.c_float), _p(st, C.c_uint8), _p(er, C.c_float)), "cs_klt_track")
+        check(self.ctx.ptr, lib().cs_klt_track(self.ctx.ptr, self._h, len(pp), ptr(pp), ptr(pn), ptr(first), ptr(flat if len(flat) else nxt),
+                                               ptr(nxt), ptr(st), ptr(er)), "cs_klt_track")
         return _split(first, nxt, st, er)
 
     def search_by_tracking_harris(self, pairs, last_pts, masks):
@@ -104,9 +101,9 @@ class KLTTracker:
         nxt, st, er = _outputs(len(flat))
         kf, kept, kpts, ids = np.zeros(len(pp) + 1, np.int32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
         good, outside = np.zeros(len(pp), np.int32), np.zeros(len(pp), np.int32)
-        check(self.ctx.ptr, lib().cs_match_by_tracking_harris(self.ctx.ptr, self._h, len(pp), _p(pp, C.c_int), _p(pn, C.c_int), _p(first, C.c_int),
-                                                              _p(flat if len(flat) else nxt, C.c_float), _p(m, C.c_uint8), _p(nxt, C.c_float), _p(st, C.c_uint8), _p(er, C.c_float),
-                                                              _p(kf, C.c_int), _p(kept, C.c_int), _p(kpts, C.c_float), _p(ids, C.c_int), _p(good, C.c_int), _p(outside, C.c_int)),
+        check(self.ctx.ptr, lib().cs_match_by_tracking_harris(self.ctx.ptr, self._h, len(pp), ptr(pp), ptr(pn), ptr(first),
+                                                              ptr(flat if len(flat) else nxt), ptr(m), ptr(nxt), ptr(st), ptr(er),
+                                                              ptr(kf), ptr(kept), ptr(kpts), ptr(ids), ptr(good), ptr(outside)),
               "cs_match_by_tracking_harris")
         return _harris_result(first, flat, nxt, st, er, kf, kept, kpts, ids, good, outside)
 
@@ -116,27 +113,15 @@ class KLTTracker:
         fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
         m = None if masks is None else _masks(masks, len(fr), self.H, self.W)
         out = _gftt_outputs(len(fr), maxCorners)
-        r = lib().cs_klt_good_features(self.ctx.ptr, self._h, len(fr), _p(fr, C.c_int), None if m is None else _p(m, C.c_uint8), int(maxCorners), C.c_double(qualityLevel),
-                                       C.c_double(minDistance), *_gftt_ptrs(out))
+        r = lib().cs_klt_good_features(self.ctx.ptr, self._h, len(fr), ptr(fr), ptr(m), int(maxCorners), qualityLevel, minDistance, *_gftt_ptrs(out))
         return _gftt_result(self.ctx.ptr, r, "cs_klt_good_features", out)
 
     def new_harris_features(self, frames, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks=False):
         """Tracking.cc:2263-2331 on the resident frames `frames`; see NewHarrisFeatures."""
         fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
         a = _harris_args(len(fr), self.H, self.W, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks)
-        r = lib().cs_track_new_harris_features(self.ctx.ptr, self._h, len(fr), _p(fr, C.c_int), *a["ptrs"])
+        r = lib().cs_track_new_harris_features(self.ctx.ptr, self._h, len(fr), ptr(fr), *a["ptrs"])
         return _new_harris_result(self.ctx.ptr, r, "cs_track_new_harris_features", a)
-
-    def close(self):
-        if self._h:
-            lib().cs_klt_destroy(self.ctx.ptr, self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def calcOpticalFlowPyrLK(frames, pairs, pts, ctx=None):
@@ -152,8 +137,8 @@ def calcOpticalFlowPyrLK(frames, pairs, pts, ctx=None):
             t.close()
     pp, pn, first, flat = _pairs(pairs, pts)
     nxt, st, er = _outputs(len(flat))
-    check(None, lib().cs_klt_track_host(_p(g, C.c_uint8), len(g), g.shape[2], g.shape[1], C.c_long(g.strides[1]), len(pp), _p(pp, C.c_int), _p(pn, C.c_int), _p(first, C.c_int),
-                                        _p(flat if len(flat) else nxt, C.c_float), _p(nxt, C.c_float), _p(st, C.c_uint8), _p(er, C.c_float)), "cs_klt_track_host")
+    check(None, lib().cs_klt_track_host(ptr(g), len(g), g.shape[2], g.shape[1], g.strides[1], len(pp), ptr(pp), ptr(pn), ptr(first),
+                                        ptr(flat if len(flat) else nxt), ptr(nxt), ptr(st), ptr(er)), "cs_klt_track_host")
     return _split(first, nxt, st, er)
 
 
@@ -173,10 +158,9 @@ def SearchByTrackingHarris(frames, pairs, last_pts, masks, ctx=None):
     nxt, st, er = _outputs(len(flat))
     kf, kept, kpts, ids = np.zeros(len(pp) + 1, np.int32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
     good, outside = np.zeros(len(pp), np.int32), np.zeros(len(pp), np.int32)
-    check(None, lib().cs_match_by_tracking_harris_host(_p(g, C.c_uint8), len(g), g.shape[2], g.shape[1], C.c_long(g.strides[1]), len(pp), _p(pp, C.c_int), _p(pn, C.c_int),
-                                                       _p(first, C.c_int), _p(flat if len(flat) else nxt, C.c_float), _p(m, C.c_uint8), _p(nxt, C.c_float), _p(st, C.c_uint8),
-                                                       _p(er, C.c_float), _p(kf, C.c_int), _p(kept, C.c_int), _p(kpts, C.c_float), _p(ids, C.c_int), _p(good, C.c_int),
-                                                       _p(outside, C.c_int)), "cs_match_by_tracking_harris_host")
+    check(None, lib().cs_match_by_tracking_harris_host(ptr(g), len(g), g.shape[2], g.shape[1], g.strides[1], len(pp), ptr(pp), ptr(pn),
+                                                       ptr(first), ptr(flat if len(flat) else nxt), ptr(m), ptr(nxt), ptr(st),
+                                                       ptr(er), ptr(kf), ptr(kept), ptr(kpts), ptr(ids), ptr(good), ptr(outside)), "cs_match_by_tracking_harris_host")
     return _harris_result(first, flat, nxt, st, er, kf, kept, kpts, ids, good, outside)
 
 
@@ -186,7 +170,7 @@ def _gftt_outputs(n, max_corners):
 
 
 def _gftt_ptrs(out):
-    return _p(out[0], C.c_float), _p(out[1], C.c_float), _p(out[2], C.c_int), _p(out[3], C.c_int)
+    return [ptr(a) for a in out]
 
 
 def _gftt_result(ctx_ptr, r, what, out):
@@ -219,9 +203,9 @@ def _harris_args(n, H, W, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth,
          "x3D_valid": np.zeros(cap, np.uint8), "n_mask_outside": np.zeros(n, np.int32), "good": np.zeros((n, H, W), np.uint8) if good_masks else None,
          "n_candidates": np.zeros(n, np.int32)}
     o["keep"] = (m, fp, fo, fd, k4, T, ef, cf)
-    o["ptrs"] = (_p(m, C.c_uint8), _p(ef, C.c_int), _p(fp, C.c_float), _p(fo, C.c_int), _p(k4, C.c_float), _p(T, C.c_float), _p(cf, C.c_int), _p(fd, C.c_float),
-                 _p(o["new_first"], C.c_int), _p(o["pts"], C.c_float), _p(o["object_id"], C.c_int), _p(o["x3D"], C.c_float), _p(o["x3D_valid"], C.c_uint8),
-                 _p(o["n_mask_outside"], C.c_int), None if o["good"] is None else _p(o["good"], C.c_uint8), _p(o["n_candidates"], C.c_int))
+    o["ptrs"] = (ptr(m), ptr(ef), ptr(fp), ptr(fo), ptr(k4), ptr(T), ptr(cf), ptr(fd),
+                 ptr(o["new_first"]), ptr(o["pts"]), ptr(o["object_id"]), ptr(o["x3D"]), ptr(o["x3D_valid"]),
+                 ptr(o["n_mask_outside"]), ptr(o["good"]), ptr(o["n_candidates"]))
     return o
 
 
@@ -249,8 +233,7 @@ def goodFeaturesToTrack(frames, masks, maxCorners, qualityLevel, minDistance, ct
     g = _frames(frames)
     m = None if masks is None else _masks(masks, len(g), g.shape[1], g.shape[2])
     out = _gftt_outputs(len(g), maxCorners)
-    head = (_p(g, C.c_uint8), len(g), g.shape[2], g.shape[1], C.c_long(g.strides[1]), None if m is None else _p(m, C.c_uint8), int(maxCorners), C.c_double(qualityLevel),
-            C.c_double(minDistance))
+    head = (ptr(g), len(g), g.shape[2], g.shape[1], g.strides[1], ptr(m), int(maxCorners), qualityLevel, minDistance)
     if ctx is not None:
         return _gftt_result(ctx.ptr, lib().cs_good_features_images(ctx.ptr, *head, *_gftt_ptrs(out)), "cs_good_features_images", out)
     return _gftt_result(None, lib().cs_klt_good_features_host(*head, *_gftt_ptrs(out)), "cs_klt_good_features_host", out)
@@ -270,7 +253,7 @@ def NewHarrisFeatures(frames, objmasks, exist_pts, exist_obs, K4, Twc, cuboid_de
         finally:
             t.close()
     a = _harris_args(len(g), g.shape[1], g.shape[2], objmasks, exist_pts, exist_obs, K4, Twc, cuboid_depth, good_masks)
-    r = lib().cs_track_new_harris_features_host(_p(g, C.c_uint8), len(g), g.shape[2], g.shape[1], C.c_long(g.strides[1]), *a["ptrs"])
+    r = lib().cs_track_new_harris_features_host(ptr(g), len(g), g.shape[2], g.shape[1], g.strides[1], *a["ptrs"])
     return _new_harris_result(None, r, "cs_track_new_harris_features_host", a)
 
 
@@ -291,9 +274,9 @@ def _tracking_call(fn, head, N, last_keys, eligible, object_id, numobject, th, s
     train, sel, last, this = np.full(max(N, 1), -1, np.int32), np.zeros(one, np.int32), np.zeros((one, 2), np.float32), np.zeros((one, 2), np.float32)
     n, counters = C.c_int(), np.zeros(4, np.int32)
     pad = lambda a, dt: a if len(a) else np.zeros(1, dt)  # noqa: E731
-    check(ctx_ptr, fn(*head, n_last, C.c_void_p(pad(lk, KEYPOINT_DTYPE).ctypes.data), _p(pad(el, np.uint8), C.c_uint8), _p(pad(ob, np.int32), C.c_int), int(numobject), C.c_float(th),
-                      _p(sf, C.c_float), len(sf), *tail, None if ks is None else _p(pad(ks, np.uint8), C.c_uint8), None if hm is None else _p(pad(hm, np.uint8), C.c_uint8),
-                      _p(train, C.c_int), C.byref(n), _p(sel, C.c_int), _p(last, C.c_float), _p(this, C.c_float), _p(counters, C.c_int)), what)
+    check(ctx_ptr, fn(*head, n_last, ptr(pad(lk, KEYPOINT_DTYPE)), ptr(pad(el, np.uint8)), ptr(pad(ob, np.int32)), int(numobject), th,
+                      ptr(sf), len(sf), *tail, None if ks is None else ptr(pad(ks, np.uint8)), None if hm is None else ptr(pad(hm, np.uint8)),
+                      ptr(train), C.byref(n), ptr(sel), ptr(last), ptr(this), ptr(counters)), what)
     k = n.value
     return {"train_match": train[:N], "lastptsinds": sel[:k].copy(), "featuresklt_lastframe": last[:k].copy(), "featuresklt_thisframe": this[:k].copy(),
             "kltmatches": int(counters[0]), "goodmatches": int(counters[1]), "findfeaturematches": int(counters[2]), "uniquematches": int(counters[3])}
@@ -311,8 +294,8 @@ def SearchByTracking(last_gray, current_gray, last_keys, eligible, object_id, nu
     if matcher is None:
         g = _frames(np.stack([np.asarray(last_gray, np.uint8), np.asarray(current_gray, np.uint8)]))
         ku = np.ascontiguousarray(keysUn, KEYPOINT_DTYPE)
-        tail = (C.c_void_p((ku if len(ku) else np.zeros(1, KEYPOINT_DTYPE)).ctypes.data), len(ku), *[C.c_float(float(b)) for b in bounds])
-        head = (_p(g[0], C.c_uint8), _p(g[1], C.c_uint8), g.shape[2], g.shape[1], C.c_long(g.strides[1]))
+        tail = (ptr(ku if len(ku) else np.zeros(1, KEYPOINT_DTYPE)), len(ku), *[float(b) for b in bounds])
+        head = (ptr(g[0]), ptr(g[1]), g.shape[2], g.shape[1], g.strides[1])
         return _tracking_call(lib().cs_match_by_tracking_host, head, len(ku), last_keys, eligible, object_id, numobject, th, scale_factors, tail, keys_static, had_map_point,
                               "cs_match_by_tracking_host", None)
     own = tracker is None

@@ -7,7 +7,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, lib, ptr
 from .orb import KEYPOINT_DTYPE
 
 MAX_NEIGHBOURS = 32
@@ -19,10 +19,6 @@ class CsLmFrame(C.Structure):
     _fields_ = [("keysUn", C.c_void_p), ("keys_xy", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("N", C.c_int), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
                 ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float), ("mbf", C.c_float),
                 ("mb", C.c_float), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("n_levels", C.c_int), ("scale_factor", C.c_float)]
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 class KeyFrameView:
@@ -62,8 +58,8 @@ def create_new_map_points(ctx, kf, neighbours, matches12):
     st = np.zeros(max(cap, 1), np.uint8); new = np.zeros(max(kf.N, 1), np.int32); nnew = C.c_int()
     arr = (CsLmFrame * max(n, 1))(*[f.c_struct() for f in neighbours])
     cur = kf.c_struct()
-    check(ctx.ptr, lib().cs_create_new_map_points(ctx.ptr, C.byref(cur), arr, n, _p(m, C.c_int), cap, _p(off, C.c_int), _p(i1, C.c_int), _p(i2, C.c_int), _p(x, C.c_float),
-                                                  _p(st, C.c_uint8), _p(new, C.c_int), C.byref(nnew)), "cs_create_new_map_points")
+    check(ctx.ptr, lib().cs_create_new_map_points(ctx.ptr, C.byref(cur), arr, n, ptr(m), cap, ptr(off), ptr(i1), ptr(i2), ptr(x),
+                                                  ptr(st), ptr(new), C.byref(nnew)), "cs_create_new_map_points")
     return {"pair_off": off, "idx1": i1[:cap], "idx2": i2[:cap], "x3D": x[:cap], "status": st[:cap], "new_pair_of_idx1": new[:kf.N], "nnew": nnew.value}
 
 
@@ -127,7 +123,7 @@ def ComputeDistinctiveDescriptors(ctx, obs_off, desc):
     off = np.ascontiguousarray(obs_off, np.int32); d = np.ascontiguousarray(desc, np.uint8)
     n = len(off) - 1
     best = np.zeros(max(n, 1), np.int32)
-    check(ctx.ptr, lib().cs_mappoint_distinctive_descriptors(ctx.ptr, n, _p(off, C.c_int), _p(d, C.c_uint8), _p(best, C.c_int)), "cs_mappoint_distinctive_descriptors")
+    check(ctx.ptr, lib().cs_mappoint_distinctive_descriptors(ctx.ptr, n, ptr(off), ptr(d), ptr(best)), "cs_mappoint_distinctive_descriptors")
     return best[:n]
 
 
@@ -143,7 +139,7 @@ def UpdateNormalAndDepth(ctx, world_pos, obs_off, obs_kf, kf_Ow, ref_kf, ref_oct
     mn = np.zeros(max(n, 1), np.float32) if min_distance is None else np.array(min_distance, np.float32)
     mx = np.zeros(max(n, 1), np.float32) if max_distance is None else np.array(max_distance, np.float32)
     up = np.zeros(max(n, 1), np.uint8)
-    check(ctx.ptr, lib().cs_mappoint_update_normal_and_depth(ctx.ptr, n, _p(pos, C.c_float), _p(off, C.c_int), _p(ob, C.c_int), len(ow), _p(ow, C.c_float), _p(rk, C.c_int),
-                                                             _p(ro, C.c_int), _p(sf, C.c_float), len(sf), _p(nv, C.c_float), _p(mn, C.c_float), _p(mx, C.c_float), _p(up, C.c_uint8)),
+    check(ctx.ptr, lib().cs_mappoint_update_normal_and_depth(ctx.ptr, n, ptr(pos), ptr(off), ptr(ob), len(ow), ptr(ow), ptr(rk),
+                                                             ptr(ro), ptr(sf), len(sf), ptr(nv), ptr(mn), ptr(mx), ptr(up)),
           "cs_mappoint_update_normal_and_depth")
     return nv[:n], mn[:n], mx[:n], up[:n]

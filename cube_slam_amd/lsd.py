@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 
 KEYLINE_DTYPE = np.dtype([("angle", "f4"), ("class_id", "i4"), ("octave", "i4"), ("pt", "f4", 2), ("response", "f4"), ("size", "f4"),
                           ("startPointX", "f4"), ("startPointY", "f4"), ("endPointX", "f4"), ("endPointY", "f4"),
@@ -12,12 +12,9 @@ KEYLINE_DTYPE = np.dtype([("angle", "f4"), ("class_id", "i4"), ("octave", "i4"),
                           ("lineLength", "f4"), ("numOfPixels", "i4")])
 
 
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-class line_lbd_detect:
+class line_lbd_detect(Handle):
     """use_LSD = True path: detect_raw_lines / detect_filter_lines (numoctaves = 1, octaveratio = 1)."""
+    HANDLE, DESTROY = "_l", "cs_lsd_destroy"
 
     def __init__(self, width, height, max_frames=1, ctx=None, device=0):
         self.ctx = ctx or _lib.Context(device)
@@ -39,7 +36,7 @@ class line_lbd_detect:
     def upload(self, gray):
         g = self._imgs(gray)
         self._n = len(g)
-        check(self.ctx.ptr, lib().cs_lsd_upload(self.ctx.ptr, self._l, _p(g, C.c_uint8), len(g), self.W), "cs_lsd_upload")
+        check(self.ctx.ptr, lib().cs_lsd_upload(self.ctx.ptr, self._l, ptr(g), len(g), self.W), "cs_lsd_upload")
 
     def run(self, with_lbd=True):
         check(self.ctx.ptr, lib().cs_lsd_run(self.ctx.ptr, self._l, int(with_lbd)), "cs_lsd_run")
@@ -59,28 +56,27 @@ class line_lbd_detect:
         n = C.c_int()
         check(self.ctx.ptr, lib().cs_lsd_read(self.ctx.ptr, self._l, frame, None, 0, C.byref(n), None), "cs_lsd_read")
         kl = np.zeros(n.value, KEYLINE_DTYPE); desc = np.zeros((n.value, 32), np.uint8)
-        check(self.ctx.ptr, lib().cs_lsd_read(self.ctx.ptr, self._l, frame, kl.ctypes.data_as(C.c_void_p), n.value, C.byref(n),
-                                              _p(desc, C.c_uint8) if with_desc else None), "cs_lsd_read")
+        check(self.ctx.ptr, lib().cs_lsd_read(self.ctx.ptr, self._l, frame, ptr(kl), n.value, C.byref(n), ptr(desc) if with_desc else None), "cs_lsd_read")
         return (kl, desc) if with_desc else kl
 
     def read_filter_lines(self, n_frames, cap=1024):
         """detect_filter_lines' rows (x1 y1 x2 y2, float32) for the resident frames, from the KeyLines of the last run()."""
         out = np.zeros((n_frames, cap, 4), np.float32); counts = np.zeros(n_frames, np.int32)
-        check(self.ctx.ptr, lib().cs_lsd_read_filter_lines(self.ctx.ptr, self._l, C.c_float(self.line_length_thres), _p(out, C.c_float), cap, _p(counts, C.c_int), int(n_frames)), "cs_lsd_read_filter_lines")
+        check(self.ctx.ptr, lib().cs_lsd_read_filter_lines(self.ctx.ptr, self._l, self.line_length_thres, ptr(out), cap, ptr(counts), int(n_frames)), "cs_lsd_read_filter_lines")
         return [out[f, :counts[f]] for f in range(n_frames)]
 
     def detect_raw_lines(self, gray):
         g = self._imgs(gray)
         out = np.zeros((len(g), self.cap), KEYLINE_DTYPE); counts = np.zeros(len(g), np.int32)
-        check(self.ctx.ptr, lib().cs_lsd_detect(self.ctx.ptr, self._l, _p(g, C.c_uint8), len(g), self.W, out.ctypes.data_as(C.c_void_p), self.cap, _p(counts, C.c_int)), "cs_lsd_detect")
+        check(self.ctx.ptr, lib().cs_lsd_detect(self.ctx.ptr, self._l, ptr(g), len(g), self.W, ptr(out), self.cap, ptr(counts)), "cs_lsd_detect")
         res = [out[f, :counts[f]].copy() for f in range(len(g))]
         return res if np.ndim(gray) == 3 else res[0]
 
     def detect_filter_lines(self, gray):
         g = self._imgs(gray)
         out = np.zeros((len(g), self.cap, 4), np.float32); counts = np.zeros(len(g), np.int32)
-        check(self.ctx.ptr, lib().cs_lsd_detect_filter_lines(self.ctx.ptr, self._l, _p(g, C.c_uint8), len(g), self.W, C.c_float(self.line_length_thres), _p(out, C.c_float),
-                                                             self.cap, _p(counts, C.c_int)), "cs_lsd_detect_filter_lines")
+        check(self.ctx.ptr, lib().cs_lsd_detect_filter_lines(self.ctx.ptr, self._l, ptr(g), len(g), self.W, self.line_length_thres, ptr(out),
+                                                             self.cap, ptr(counts)), "cs_lsd_detect_filter_lines")
         res = [out[f, :counts[f]].copy() for f in range(len(g))]
         return res if np.ndim(gray) == 3 else res[0]
 
@@ -89,7 +85,7 @@ class line_lbd_detect:
         check(self.ctx.ptr, lib().cs_lsd_get_maps(self.ctx.ptr, self._l, frame, None, None, None, C.byref(sw), C.byref(sh)), "cs_lsd_get_maps")
         n = sw.value * sh.value
         sc, mg, an = np.zeros(n), np.zeros(n), np.zeros(n)
-        check(self.ctx.ptr, lib().cs_lsd_get_maps(self.ctx.ptr, self._l, frame, _p(sc, C.c_double), _p(mg, C.c_double), _p(an, C.c_double), C.byref(sw), C.byref(sh)), "cs_lsd_get_maps")
+        check(self.ctx.ptr, lib().cs_lsd_get_maps(self.ctx.ptr, self._l, frame, ptr(sc), ptr(mg), ptr(an), C.byref(sw), C.byref(sh)), "cs_lsd_get_maps")
         shape = (sh.value, sw.value)
         return sc.reshape(shape), mg.reshape(shape), an.reshape(shape)
 
@@ -98,8 +94,8 @@ class line_lbd_detect:
         g = np.ascontiguousarray(gray, np.uint8)
         kl = np.ascontiguousarray(keylines, KEYLINE_DTYPE); n = len(kl)
         desc = np.zeros((n, 32), np.uint8); fd = np.zeros((n, 72), np.float32) if want_float else None
-        check(self.ctx.ptr, lib().cs_lbd_compute(self.ctx.ptr, _p(g, C.c_uint8), g.shape[1], g.shape[0], g.shape[1], kl.ctypes.data_as(C.c_void_p), n,
-                                                 _p(desc, C.c_uint8), _p(fd, C.c_float) if want_float else None), "cs_lbd_compute")
+        check(self.ctx.ptr, lib().cs_lbd_compute(self.ctx.ptr, ptr(g), g.shape[1], g.shape[0], g.shape[1], ptr(kl), n,
+                                                 ptr(desc), ptr(fd) if want_float else None), "cs_lbd_compute")
         return (desc, fd) if want_float else desc
 
     def detect_descrip_lines(self, gray):
@@ -114,23 +110,11 @@ class line_lbd_detect:
         """-> (query_idx, train_idx, distance) of the good matches (BinaryDescriptorMatcher::match + distance threshold)."""
         q = np.ascontiguousarray(desc_q, np.uint8).reshape(-1, 32); t = np.ascontiguousarray(desc_t, np.uint8).reshape(-1, 32)
         qi = np.zeros(len(q), np.int32); ti = np.zeros(len(q), np.int32); d = np.zeros(len(q), np.int32); m = C.c_int()
-        check(self.ctx.ptr, lib().cs_lbd_match(self.ctx.ptr, _p(q, C.c_uint8), len(q), _p(t, C.c_uint8), len(t), C.c_float(matching_dist_thres),
-                                               _p(qi, C.c_int), _p(ti, C.c_int), _p(d, C.c_int), C.byref(m)), "cs_lbd_match")
+        check(self.ctx.ptr, lib().cs_lbd_match(self.ctx.ptr, ptr(q), len(q), ptr(t), len(t), matching_dist_thres, ptr(qi), ptr(ti), ptr(d), C.byref(m)), "cs_lbd_match")
         return qi[:m.value], ti[:m.value], d[:m.value]
 
     def lbd_maps(self, gray):
         g = np.ascontiguousarray(gray, np.uint8); H, W = g.shape
         b = np.zeros((H, W), np.uint8); dx = np.zeros((H, W), np.int16); dy = np.zeros((H, W), np.int16)
-        check(self.ctx.ptr, lib().cs_lbd_maps(self.ctx.ptr, _p(g, C.c_uint8), W, H, W, _p(b, C.c_uint8), _p(dx, C.c_int16), _p(dy, C.c_int16)), "cs_lbd_maps")
+        check(self.ctx.ptr, lib().cs_lbd_maps(self.ctx.ptr, ptr(g), W, H, W, ptr(b), ptr(dx), ptr(dy)), "cs_lbd_maps")
         return b, dx, dy
-
-    def close(self):
-        if self._l:
-            lib().cs_lsd_destroy(self.ctx.ptr, self._l)
-            self._l = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,11 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.c_void_p)
+from ._lib import check, lib, ptr
 
 
 def associate_keypoints(ctx, keypoints, boxes, enable_ground_height_scale=False):
@@ -22,7 +18,7 @@ def associate_keypoints(ctx, keypoints, boxes, enable_ground_height_scale=False)
     xy = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float32).reshape(-1, 2) for k in keypoints]) if F else np.zeros((0, 2)), np.float32)
     bx = np.ascontiguousarray(np.concatenate([np.asarray(b, np.int32).reshape(-1, 4) for b in boxes]) if F else np.zeros((0, 4)), np.int32)
     assoc = np.full(max(len(xy), 1), -1, np.int32); inany = np.zeros(max(len(xy), 1), np.uint8); ov = np.zeros(max(len(bx), 1), np.uint8)
-    check(ctx.ptr, lib().cs_associate_keypoints(ctx.ptr, F, _ip(kp_off), _ip(xy), _ip(box_off), _ip(bx), int(enable_ground_height_scale), _ip(assoc), _ip(inany), _ip(ov)),
+    check(ctx.ptr, lib().cs_associate_keypoints(ctx.ptr, F, ptr(kp_off), ptr(xy), ptr(box_off), ptr(bx), int(enable_ground_height_scale), ptr(assoc), ptr(inany), ptr(ov)),
           "cs_associate_keypoints")
     return [(assoc[kp_off[f]:kp_off[f + 1]].copy(), inany[kp_off[f]:kp_off[f + 1]].copy(), ov[box_off[f]:box_off[f + 1]].copy()) for f in range(F)]
 
@@ -49,8 +45,8 @@ def associate_cuboids(cand_id, cand_pts, landmark_id, landmark_bad, point_votes,
     nu = C.c_int()
     bo = np.ascontiguousarray(best_object, np.int32) if best_object is not None else None
     mv = np.ascontiguousarray(max_vote, np.int32) if max_vote is not None else None
-    r = lib().cs_associate_cuboids(n, _ip(cid), _ip(cand_off), _ip(pts), len(lid), _ip(lid), _ip(lbad), P, _ip(pobs_off), _ip(pobs_obj), _ip(pobs_cnt),
-                                   _ip(bo) if bo is not None else None, _ip(mv) if mv is not None else None, int(thres), _ip(assoc), _ip(created), cap, _ip(up), _ip(uo), _ip(uc),
+    r = lib().cs_associate_cuboids(n, ptr(cid), ptr(cand_off), ptr(pts), len(lid), ptr(lid), ptr(lbad), P, ptr(pobs_off), ptr(pobs_obj), ptr(pobs_cnt),
+                                   ptr(bo), ptr(mv), int(thres), ptr(assoc), ptr(created), cap, ptr(up), ptr(uo), ptr(uc),
                                    C.byref(nu))
     if r != 0:
         raise RuntimeError("cs_associate_cuboids failed: %d" % r)

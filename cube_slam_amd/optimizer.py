@@ -5,11 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+from ._lib import Handle, check, lib, ptr
 
 
 def PoseOptimization(frames, ctx=None, device=0):
@@ -28,8 +24,8 @@ def PoseOptimization(frames, ctx=None, device=0):
     intr = np.ascontiguousarray(np.stack([np.asarray(fr["intr"], np.float64) for fr in frames])) if F else np.zeros((1, 5))
     pin = np.ascontiguousarray(np.stack([np.asarray(fr["pose"], np.float64) for fr in frames])) if F else np.zeros((1, 7))
     pout = np.zeros((max(F, 1), 7)); flags = np.zeros(max(ne, 1), np.uint8); ninl = np.zeros(max(F, 1), np.int32)
-    check(ctx.ptr, lib().cs_pose_optimization(ctx.ptr, F, _p(off, C.c_int), _p(Xw, C.c_double), _p(obs, C.c_double), _p(w, C.c_double), _p(intr, C.c_double),
-                                              _p(pin, C.c_double), _p(pout, C.c_double), _p(flags, C.c_uint8), _p(ninl, C.c_int)), "cs_pose_optimization")
+    check(ctx.ptr, lib().cs_pose_optimization(ctx.ptr, F, ptr(off), ptr(Xw), ptr(obs), ptr(w), ptr(intr),
+                                              ptr(pin), ptr(pout), ptr(flags), ptr(ninl)), "cs_pose_optimization")
     return [(pout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
 
 
@@ -60,9 +56,8 @@ def OptimizeSim3(problems, ctx=None, device=0):
     th2 = np.ascontiguousarray([pr["th2"] for pr in problems], np.float32)
     fix = np.ascontiguousarray([1 if pr["fix_scale"] else 0 for pr in problems], np.uint8)
     sout = np.zeros((F, 8)); flags = np.zeros(max(ne, 1), np.uint8); ninl = np.zeros(F, np.int32)
-    check(ctx.ptr, lib().cs_sim3_optimization(ctx.ptr, F, _p(off, C.c_int), _p(P1, C.c_double), _p(P2, C.c_double), _p(o1, C.c_double), _p(o2, C.c_double), _p(w1, C.c_double),
-                                              _p(w2, C.c_double), _p(intr, C.c_double), _p(sin, C.c_double), _p(th2, C.c_float), _p(fix, C.c_uint8), _p(sout, C.c_double),
-                                              _p(flags, C.c_uint8), _p(ninl, C.c_int)), "cs_sim3_optimization")
+    check(ctx.ptr, lib().cs_sim3_optimization(ctx.ptr, F, ptr(off), ptr(P1), ptr(P2), ptr(o1), ptr(o2), ptr(w1),
+                                              ptr(w2), ptr(intr), ptr(sin), ptr(th2), ptr(fix), ptr(sout), ptr(flags), ptr(ninl)), "cs_sim3_optimization")
     res = [(sout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
     return res[0] if single else res
 
@@ -131,8 +126,9 @@ class _EgStats(C.Structure):
                 ("launches_per_trial", C.c_int), ("chi2_first", C.c_double), ("chi2_last", C.c_double), ("lambda_last", C.c_double), ("trial_accepted", C.c_uint8 * 256)]
 
 
-class EssentialGraph:
+class EssentialGraph(Handle):
     """cs_essential_graph: the structure of one pose graph (a dict as build_essential_graph returns), analysed once; optimize() may run any number of times."""
+    HANDLE, DESTROY = "_h", "cs_essential_graph_destroy"
 
     def __init__(self, graph, fix_scale, ctx=None, device=0):
         self.ctx = ctx or _lib.Context(device)
@@ -141,7 +137,7 @@ class EssentialGraph:
         if not (len(ei) == len(ej) == len(kind)):
             raise ValueError("EssentialGraph: edge_i, edge_j and edge_kind differ in length")
         self._h = C.c_void_p()
-        check(self.ctx.ptr, lib().cs_essential_graph_create(self.ctx.ptr, self.n, len(ei), _p(ei, C.c_int), _p(ej, C.c_int), _p(kind, C.c_uint8), int(graph["fixed_vertex"]),
+        check(self.ctx.ptr, lib().cs_essential_graph_create(self.ctx.ptr, self.n, len(ei), ptr(ei), ptr(ej), ptr(kind), int(graph["fixed_vertex"]),
                                                             int(bool(fix_scale)), C.byref(self._h)), "cs_essential_graph_create")
 
     def optimize(self, Scw, Snc, has_nc, iterations=20):
@@ -151,23 +147,11 @@ class EssentialGraph:
         if not (len(Scw) == len(Snc) == len(has) == n):
             raise ValueError("EssentialGraph.optimize: Scw, Snc and has_nc need one row per vertex")
         out, Tiw, st = np.zeros((n, 8)), np.zeros((n, 3, 4), np.float32), _EgStats()
-        check(self.ctx.ptr, lib().cs_essential_graph_optimize(self.ctx.ptr, self._h, _p(Scw, C.c_double), _p(Snc, C.c_double), _p(has, C.c_uint8), int(iterations), _p(out, C.c_double),
-                                                              _p(Tiw, C.c_float), C.byref(st)), "cs_essential_graph_optimize")
+        check(self.ctx.ptr, lib().cs_essential_graph_optimize(self.ctx.ptr, self._h, ptr(Scw), ptr(Snc), ptr(has), int(iterations), ptr(out),
+                                                              ptr(Tiw), C.byref(st)), "cs_essential_graph_optimize")
         stats = {k: getattr(st, k) for k, _ in _EgStats._fields_[:-1]}
         stats["sequence"] = [int(st.trial_accepted[k]) for k in range(min(st.trials, 256))]
         return out, Tiw, stats
-
-    def close(self):
-        if self._h:
-            lib().cs_essential_graph_destroy.restype = None
-            lib().cs_essential_graph_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def correct_points(P, ref_vertex, Scw, sim3_out, ctx=None, device=0):
@@ -178,7 +162,7 @@ def correct_points(P, ref_vertex, Scw, sim3_out, ctx=None, device=0):
     if len(P) != len(ref) or Scw.shape != out.shape:
         raise ValueError("correct_points: one ref_vertex per point, one corrected Sim3 per Scw")
     res = np.zeros((len(P), 3), np.float32)
-    check(ctx.ptr, lib().cs_sim3_correct_points(ctx.ptr, len(P), _p(P, C.c_double), _p(ref, C.c_int), len(Scw), _p(Scw, C.c_double), _p(out, C.c_double), _p(res, C.c_float)),
+    check(ctx.ptr, lib().cs_sim3_correct_points(ctx.ptr, len(P), ptr(P), ptr(ref), len(Scw), ptr(Scw), ptr(out), ptr(res)),
           "cs_sim3_correct_points")
     return res
 
@@ -188,7 +172,7 @@ def sim3_log(S, ctx=None, device=0):
     ctx = ctx or _lib.Context(device)
     S = np.ascontiguousarray(S, np.float64).reshape(-1, 8)
     out = np.zeros((len(S), 7))
-    check(ctx.ptr, lib().cs_sim3_log(ctx.ptr, len(S), _p(S, C.c_double), _p(out, C.c_double)), "cs_sim3_log")
+    check(ctx.ptr, lib().cs_sim3_log(ctx.ptr, len(S), ptr(S), ptr(out)), "cs_sim3_log")
     return out
 
 
@@ -219,7 +203,7 @@ def cuboid9_oplus(cub, upd, ctx=None, device=0):
     ctx = ctx or _lib.Context(device)
     cub = np.ascontiguousarray(cub, np.float64).reshape(-1, 10); upd = np.ascontiguousarray(upd, np.float64).reshape(-1, 9)
     out = np.zeros_like(cub)
-    check(ctx.ptr, lib().cs_cuboid9_oplus(ctx.ptr, len(cub), _p(cub, C.c_double), _p(upd, C.c_double), _p(out, C.c_double)), "cs_cuboid9_oplus")
+    check(ctx.ptr, lib().cs_cuboid9_oplus(ctx.ptr, len(cub), ptr(cub), ptr(upd), ptr(out)), "cs_cuboid9_oplus")
     return out
 
 
@@ -230,6 +214,6 @@ def cuboid9_edge_linearize(cam_Tcw, cub_global, cub_meas, jac=True, ctx=None, de
     m = np.ascontiguousarray(cub_meas, np.float64).reshape(-1, 10)
     n = len(T)
     err = np.zeros((n, 9)); Jc = np.zeros((n, 9, 6)); Jq = np.zeros((n, 9, 9))
-    check(ctx.ptr, lib().cs_cuboid9_edge_linearize(ctx.ptr, n, _p(T, C.c_double), _p(g, C.c_double), _p(m, C.c_double), _p(err, C.c_double),
-                                                   _p(Jc, C.c_double) if jac else None, _p(Jq, C.c_double) if jac else None), "cs_cuboid9_edge_linearize")
+    check(ctx.ptr, lib().cs_cuboid9_edge_linearize(ctx.ptr, n, ptr(T), ptr(g), ptr(m), ptr(err),
+                                                   ptr(Jc) if jac else None, ptr(Jq) if jac else None), "cs_cuboid9_edge_linearize")
     return (err, Jc, Jq) if jac else err

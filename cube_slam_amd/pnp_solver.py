@@ -7,18 +7,16 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CubeSlamError, check, lib
-from ._ransac import _p, batch, cat, draw, f32, i32, mask_bits, offsets, problem_slices
+from ._lib import CubeSlamError, check, lib, ptr
+from ._ransac import batch, cat, draw, f32, i32, mask_bits, offsets, problem_slices
 
 STATUS_QR_SINGULAR, STATUS_REFINE_QR_SINGULAR, STATUS_RECORD = 1, 2, 4
 
 
 def ransac_parameters(probability, minInliers, maxIterations, minSet, epsilon, N):
     """SetRansacParameters (:120-151) -> (mRansacMinInliers, mRansacMaxIts, mRansacEpsilon)."""
-    f = lib().cs_pnp_solver_ransac_parameters
-    f.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
-    mi, its, eps = C.c_int(0), C.c_int(0), C.c_float(0)
-    check(None, f(float(probability), int(minInliers), int(maxIterations), int(minSet), float(epsilon), int(N), C.byref(mi), C.byref(its), C.byref(eps)), "cs_pnp_solver_ransac_parameters")
+    mi, its, eps = C.c_int(), C.c_int(), C.c_float()
+    check(None, lib().cs_pnp_solver_ransac_parameters(float(probability), int(minInliers), int(maxIterations), int(minSet), float(epsilon), int(N), C.byref(mi), C.byref(its), C.byref(eps)), "cs_pnp_solver_ransac_parameters")
     return mi.value, its.value, np.float32(eps.value)
 
 
@@ -26,7 +24,7 @@ def walk(n_inliers, refined_n, ransac_max_its, min_inliers, mnIterations, mnBest
     """cs_pnp_solver_walk -> (hypothesis | -1 | -2, refined, bNoMore, mnIterations, mnBestInliers, best_hypothesis)."""
     ni = np.ascontiguousarray(n_inliers, np.int32); rn = np.ascontiguousarray(refined_n, np.int32)
     it, best, h, nomore, ref = C.c_int(mnIterations), C.c_int(mnBestInliers), C.c_int(best_hypothesis), C.c_int(0), C.c_int(0)
-    t = lib().cs_pnp_solver_walk(_p(ni, C.c_int), _p(rn, C.c_int), len(ni), int(ransac_max_its), int(min_inliers), C.byref(it), C.byref(best), C.byref(h), int(nIterations),
+    t = lib().cs_pnp_solver_walk(ptr(ni), ptr(rn), len(ni), int(ransac_max_its), int(min_inliers), C.byref(it), C.byref(best), C.byref(h), int(nIterations),
                                  C.byref(nomore), C.byref(ref))
     return t, bool(ref.value), bool(nomore.value), it.value, best.value, h.value
 
@@ -42,9 +40,9 @@ def solver_evaluate(ctx, corr_off, P3Dw, P2D, max_err, K4, min_inliers, best_in,
            "mask": np.zeros(max(words, 1), np.uint32), "refined_n": np.zeros(max(H, 1), np.int32), "refined_Rt": np.zeros((max(H, 1), 12), np.float64),
            "refined_mask": np.zeros(max(words, 1), np.uint32)}
     cp = ctx.ptr if ctx is not None else None
-    check(cp, lib().cs_pnp_solver_evaluate(cp, n, _p(co, C.c_int), _p(x, C.c_float), _p(u, C.c_float), _p(e, C.c_float), _p(k4, C.c_float), _p(mi, C.c_int), _p(bi, C.c_int),
-                                           _p(ho, C.c_int), _p(q, C.c_int), _p(out["n_inliers"], C.c_int), _p(out["Rt"], C.c_double), _p(out["status"], C.c_uint32),
-                                           _p(out["mask"], C.c_uint32), _p(out["refined_n"], C.c_int), _p(out["refined_Rt"], C.c_double), _p(out["refined_mask"], C.c_uint32)),
+    check(cp, lib().cs_pnp_solver_evaluate(cp, n, ptr(co), ptr(x), ptr(u), ptr(e), ptr(k4), ptr(mi), ptr(bi),
+                                           ptr(ho), ptr(q), ptr(out["n_inliers"]), ptr(out["Rt"]), ptr(out["status"]),
+                                           ptr(out["mask"]), ptr(out["refined_n"]), ptr(out["refined_Rt"]), ptr(out["refined_mask"])),
           "cs_pnp_solver_evaluate")
     for k in ("n_inliers", "Rt", "status", "refined_n", "refined_Rt"):
         out[k] = out[k][:H]

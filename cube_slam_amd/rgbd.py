@@ -5,16 +5,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 from .orb import KEYPOINT_DTYPE
 
 CS_DEPTH_U16, CS_DEPTH_F32 = 0, 1
 CS_RGBD_MAX_KEYPOINTS = 8192
 CS_CLOSE_POINTS_NEAREST, CS_CLOSE_POINTS_ALL = 0, 1
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 def _depth_type(a):
@@ -41,9 +37,8 @@ def _close_points_raw(fn, head, first, need_new, Tcw, K4, th_depth, mode, what, 
         raise ValueError("need_new has %d entries for %d key points" % (len(need), total))
     n_valid, n_walked, new_first = np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F + 1, np.int32)
     order, new_idx, new_x3D = np.empty(max(total, 1), np.int32), np.empty(max(total, 1), np.int32), np.empty((max(total, 1), 3), np.float32)
-    check(ctx_ptr, fn(*head, None if need is None else _p(need if len(need) else np.zeros(1, np.uint8), C.c_uint8), _p(Tcw, C.c_float),
-                      _p(K4, C.c_float), C.c_float(th_depth), int(mode), _p(n_valid, C.c_int), _p(order, C.c_int), _p(n_walked, C.c_int), _p(new_first, C.c_int), _p(new_idx, C.c_int),
-                      _p(new_x3D, C.c_float)), what)
+    check(ctx_ptr, fn(*head, None if need is None else ptr(need if len(need) else np.zeros(1, np.uint8)), ptr(Tcw),
+                      ptr(K4), th_depth, int(mode), ptr(n_valid), ptr(order), ptr(n_walked), ptr(new_first), ptr(new_idx), ptr(new_x3D)), what)
     return first, n_valid, order, n_walked, new_first, new_idx, new_x3D
 
 
@@ -54,8 +49,9 @@ def _close_points_call(*args):
              "new_idx": new_idx[new_first[f]:new_first[f + 1]].copy(), "new_x3D": new_x3D[new_first[f]:new_first[f + 1]].copy()} for f in range(len(first) - 1)]
 
 
-class RGBDAssociator:
+class RGBDAssociator(Handle):
     """cs_rgbd wrapper: room for max_frames depth images of width x height and at most max_keypoints_per_frame key points per frame."""
+    HANDLE, DESTROY = "_h", "cs_rgbd_destroy"
 
     def __init__(self, width, height, max_keypoints_per_frame, max_frames=1, ctx=None, device=0):
         self.ctx = ctx or _lib.Context(device)
@@ -72,11 +68,11 @@ class RGBDAssociator:
         if d.strides[2] != d.itemsize or (len(d) > 1 and d.strides[0] != d.strides[1] * self.H):
             d = np.ascontiguousarray(d)
         self._depth = d  # (the copy is asynchronous)
-        check(self.ctx.ptr, lib().cs_rgbd_upload_depth(self.ctx.ptr, self._h, C.c_void_p(d.ctypes.data), _depth_type(d), len(d), C.c_long(d.strides[1])), "cs_rgbd_upload_depth")
+        check(self.ctx.ptr, lib().cs_rgbd_upload_depth(self.ctx.ptr, self._h, ptr(d), _depth_type(d), len(d), d.strides[1]), "cs_rgbd_upload_depth")
 
     def set_depth_device(self, address, dtype, n_frames):
         """A dense depth batch already in device memory (its address as an int, e.g. torch.Tensor.data_ptr())."""
-        check(self.ctx.ptr, lib().cs_rgbd_set_depth_device(self.ctx.ptr, self._h, C.c_void_p(address), _depth_type(np.empty(0, dtype)), int(n_frames)), "cs_rgbd_set_depth_device")
+        check(self.ctx.ptr, lib().cs_rgbd_set_depth_device(self.ctx.ptr, self._h, int(address), _depth_type(np.empty(0, dtype)), int(n_frames)), "cs_rgbd_set_depth_device")
 
     def from_orb(self, orb, K4, dist5, bf, depth_map_factor=1.0, first_frame=0, n_frames=None):
         """Queue ComputeStereoFromRGBD for frames first_frame .. of `orb`'s last run (an ORBextractor) against the uploaded depth images.  Returns at once."""
@@ -84,8 +80,8 @@ class RGBDAssociator:
             n_frames = orb.n_frames - first_frame
         K4 = np.ascontiguousarray(K4, np.float32)
         d5 = None if dist5 is None else np.ascontiguousarray(dist5, np.float32)
-        check(self.ctx.ptr, lib().cs_rgbd_from_orb(self.ctx.ptr, self._h, orb._e, int(first_frame), int(n_frames), _p(K4, C.c_float), None if d5 is None else _p(d5, C.c_float),
-                                                   C.c_float(bf), C.c_float(depth_map_factor)), "cs_rgbd_from_orb")
+        check(self.ctx.ptr, lib().cs_rgbd_from_orb(self.ctx.ptr, self._h, orb._e, int(first_frame), int(n_frames), ptr(K4), ptr(d5), bf, depth_map_factor),
+              "cs_rgbd_from_orb")
         self.n_frames = int(n_frames)
 
     def from_keys(self, keys, keysUn, bf, depth_map_factor=1.0):
@@ -96,8 +92,7 @@ class RGBDAssociator:
         ku = _keys(np.concatenate([np.asarray(a, KEYPOINT_DTYPE) for a in keysUn]) if len(keysUn) else [])
         if [len(a) for a in keys] != [len(a) for a in keysUn]:
             raise ValueError("mvKeys and mvKeysUn differ in length")
-        check(self.ctx.ptr, lib().cs_rgbd_from_keys(self.ctx.ptr, self._h, len(keys), _p(first, C.c_int), C.c_void_p(k.ctypes.data), C.c_void_p(ku.ctypes.data), C.c_float(bf),
-                                                    C.c_float(depth_map_factor)), "cs_rgbd_from_keys")
+        check(self.ctx.ptr, lib().cs_rgbd_from_keys(self.ctx.ptr, self._h, len(keys), ptr(first), ptr(k), ptr(ku), bf, depth_map_factor), "cs_rgbd_from_keys")
         self.n_frames = len(keys)
 
     def read(self):
@@ -105,7 +100,7 @@ class RGBDAssociator:
         F = self.n_frames
         ur, dep = np.zeros((F, self.cap), np.float32), np.zeros((F, self.cap), np.float32)
         counts, nd, no = np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F, np.int32)
-        check(self.ctx.ptr, lib().cs_rgbd_read(self.ctx.ptr, self._h, _p(ur, C.c_float), _p(dep, C.c_float), self.cap, _p(counts, C.c_int), _p(nd, C.c_int), _p(no, C.c_int)),
+        check(self.ctx.ptr, lib().cs_rgbd_read(self.ctx.ptr, self._h, ptr(ur), ptr(dep), self.cap, ptr(counts), ptr(nd), ptr(no)),
               "cs_rgbd_read")
         return [(ur[f, :counts[f]].copy(), dep[f, :counts[f]].copy()) for f in range(F)], nd, no
 
@@ -114,27 +109,27 @@ class RGBDAssociator:
         F = self.n_frames
         first = np.zeros(F + 1, np.int32)
         total = C.c_long()
-        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, None, None, C.c_long(0), _p(first, C.c_int), C.byref(total), None, None), "cs_rgbd_read_packed")
+        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, None, None, 0, ptr(first), C.byref(total), None, None), "cs_rgbd_read_packed")
         ur, dep = np.zeros(max(total.value, 1), np.float32), np.zeros(max(total.value, 1), np.float32)
         nd, no = np.zeros(F, np.int32), np.zeros(F, np.int32)
-        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, _p(ur, C.c_float), _p(dep, C.c_float), C.c_long(len(ur)), _p(first, C.c_int), C.byref(total),
-                                                      _p(nd, C.c_int), _p(no, C.c_int)), "cs_rgbd_read_packed")
+        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, ptr(ur), ptr(dep), len(ur), ptr(first), C.byref(total),
+                                                      ptr(nd), ptr(no)), "cs_rgbd_read_packed")
         return ur[:total.value], dep[:total.value], first, nd, no
 
     def read_keys_un(self):
         """mvKeysUn of every frame one behind the other (read_packed's order)."""
         first = np.zeros(self.n_frames + 1, np.int32)
         total = C.c_long()
-        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, None, None, C.c_long(0), _p(first, C.c_int), C.byref(total), None, None), "cs_rgbd_read_packed")
+        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, None, None, 0, ptr(first), C.byref(total), None, None), "cs_rgbd_read_packed")
         ku = np.zeros(max(total.value, 1), KEYPOINT_DTYPE)
-        check(self.ctx.ptr, lib().cs_rgbd_read_keys_un(self.ctx.ptr, self._h, C.c_void_p(ku.ctypes.data), C.c_long(len(ku))), "cs_rgbd_read_keys_un")
+        check(self.ctx.ptr, lib().cs_rgbd_read_keys_un(self.ctx.ptr, self._h, ptr(ku), len(ku)), "cs_rgbd_read_keys_un")
         return ku[:total.value]
 
     def device_frame(self, frame):
         """(device address of mvuRight, of mvDepth, of mvKeysUn, n) of one frame, for cs_match_fuse / cs_pose_optimization callers that keep it on the device."""
-        u, d, k, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
+        u, d, k, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_void_p(), C.c_int()
         check(self.ctx.ptr, lib().cs_rgbd_device_frame(self._h, int(frame), C.byref(u), C.byref(d), C.byref(k), C.byref(n)), "cs_rgbd_device_frame")
-        return u.value, d.value, k.value, n.value
+        return C.cast(u, C.c_void_p).value, C.cast(d, C.c_void_p).value, k.value, n.value
 
     def close_points(self, need_new, Tcw, K4, th_depth, mode=CS_CLOSE_POINTS_NEAREST, raw=False):
         """The close-point rule on what the last from_orb / from_keys left on the device: need_new over all frames' key points one behind the other (None with
@@ -142,20 +137,9 @@ class RGBDAssociator:
         C-ABI instead (first, n_valid, order, n_walked, new_first, new_idx, new_x3D)."""
         first = np.zeros(self.n_frames + 1, np.int32)
         total = C.c_long()
-        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, None, None, C.c_long(0), _p(first, C.c_int), C.byref(total), None, None), "cs_rgbd_read_packed")
+        check(self.ctx.ptr, lib().cs_rgbd_read_packed(self.ctx.ptr, self._h, None, None, 0, ptr(first), C.byref(total), None, None), "cs_rgbd_read_packed")
         return (_close_points_raw if raw else _close_points_call)(lib().cs_rgbd_close_points, (self.ctx.ptr, self._h), first, need_new, Tcw, K4, th_depth, mode,
                                                                   "cs_rgbd_close_points", self.ctx.ptr)
-
-    def close(self):
-        if self._h:
-            lib().cs_rgbd_destroy(self.ctx.ptr, self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ComputeStereoFromRGBD(imDepth, keys, keysUn, bf, depth_map_factor=1.0, ctx=None, counts=False):
@@ -179,8 +163,8 @@ def ComputeStereoFromRGBD(imDepth, keys, keysUn, bf, depth_map_factor=1.0, ctx=N
     k, ku = _keys(keys), _keys(keysUn)
     ur, dep = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
     nd, no = C.c_int(), C.c_int()
-    check(None, lib().cs_rgbd_host_from_keys(C.c_void_p(d.ctypes.data), _depth_type(d), W, H, C.c_long(d.strides[0]), n, C.c_void_p(k.ctypes.data), C.c_void_p(ku.ctypes.data),
-                                             C.c_float(bf), C.c_float(depth_map_factor), _p(ur, C.c_float), _p(dep, C.c_float), C.byref(nd), C.byref(no)), "cs_rgbd_host_from_keys")
+    check(None, lib().cs_rgbd_host_from_keys(ptr(d), _depth_type(d), W, H, d.strides[0], n, ptr(k), ptr(ku),
+                                             bf, depth_map_factor, ptr(ur), ptr(dep), C.byref(nd), C.byref(no)), "cs_rgbd_host_from_keys")
     return (ur[:n], dep[:n], (nd.value, no.value)) if counts else (ur[:n], dep[:n])
 
 
@@ -193,7 +177,7 @@ def ClosePoints(depth, keysUn, need_new, Tcw, K4, th_depth, mode=CS_CLOSE_POINTS
     if single:
         first = [0, len(depth)]
     ku = _keys(keysUn)
-    ptr = None if ctx is None else ctx.ptr
-    res = _close_points_call(lib().cs_close_points, (ptr, len(first) - 1, _p(np.ascontiguousarray(first, np.int32), C.c_int), _p(depth if len(depth) else np.zeros(1, np.float32), C.c_float),
-                                                     C.c_void_p(ku.ctypes.data)), first, need_new, Tcw, K4, th_depth, mode, "cs_close_points", ptr)
+    cp = None if ctx is None else ctx.ptr
+    res = _close_points_call(lib().cs_close_points, (cp, len(first) - 1, ptr(np.ascontiguousarray(first, np.int32)), ptr(depth if len(depth) else np.zeros(1, np.float32)),
+                                                     ptr(ku)), first, need_new, Tcw, K4, th_depth, mode, "cs_close_points", cp)
     return res[0] if single else res

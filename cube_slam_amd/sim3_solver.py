@@ -7,13 +7,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CubeSlamError, check, lib
-from ._ransac import _p, batch, cat, draw, f32, mask_bits, offsets, problem_slices
+from ._lib import CubeSlamError, check, lib, ptr
+from ._ransac import batch, cat, draw, f32, mask_bits, offsets, problem_slices
 
 
 def max_iterations(probability, min_inliers, max_its, N):
     """mRansacMaxIts of SetRansacParameters (:118-133); 0 for N < min_inliers."""
-    lib().cs_sim3_solver_max_iterations.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int]
     return lib().cs_sim3_solver_max_iterations(float(probability), int(min_inliers), int(max_its), int(N))
 
 
@@ -28,8 +27,8 @@ def solver_hypotheses(ctx, corr_off, X3Dc1, X3Dc2, max_err1, max_err2, K8, fix_s
     st = np.zeros((max(H, 1), 13), np.float32) if sRt is None else sRt
     mk = np.zeros(max(words, 1), np.uint32) if mask is None else mask
     check(ctx.ptr if ctx is not None else None,
-          lib().cs_sim3_solver_hypotheses(ctx.ptr if ctx is not None else None, n, _p(co, C.c_int), _p(x1, C.c_float), _p(x2, C.c_float), _p(e1, C.c_float), _p(e2, C.c_float),
-                                          _p(k8, C.c_float), _p(fs, C.c_uint8), _p(ho, C.c_int), _p(tr, C.c_int), _p(ni, C.c_int), _p(st, C.c_float), _p(mk, C.c_uint32)),
+          lib().cs_sim3_solver_hypotheses(ctx.ptr if ctx is not None else None, n, ptr(co), ptr(x1), ptr(x2), ptr(e1), ptr(e2),
+                                          ptr(k8), ptr(fs), ptr(ho), ptr(tr), ptr(ni), ptr(st), ptr(mk)),
           "cs_sim3_solver_hypotheses")
     return ni[:H], st[:H], mk[:words]
 
@@ -111,7 +110,7 @@ class Sim3Solver:
             return None, True, vbInliers, 0
         counts, _, masks = self.table()
         it, best, h, nomore = C.c_int(self.mnIterations), C.c_int(self.mnBestInliers), C.c_int(self._best), C.c_int(0)
-        t = lib().cs_sim3_solver_walk(_p(counts, C.c_int), self.mRansacMaxIts, self.mRansacMinInliers, C.byref(it), C.byref(best), C.byref(h), int(nIterations), C.byref(nomore))
+        t = lib().cs_sim3_solver_walk(ptr(counts), self.mRansacMaxIts, self.mRansacMinInliers, C.byref(it), C.byref(best), C.byref(h), int(nIterations), C.byref(nomore))
         self.mnIterations, self.mnBestInliers, self._best = it.value, best.value, h.value
         if t < 0:
             return None, bool(nomore.value), vbInliers, 0

@@ -5,16 +5,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib, ptr
 from .orb import KEYPOINT_DTYPE
 
 
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-class StereoMatcher:
+class StereoMatcher(Handle):
     """cs_stereo wrapper: room for max_pairs pairs of at most max_keypoints_per_frame key points per image."""
+    HANDLE, DESTROY = "_s", "cs_stereo_destroy"
 
     def __init__(self, max_keypoints_per_frame, max_pairs=1, ctx=None, device=0):
         self.ctx = ctx or _lib.Context(device)
@@ -28,7 +25,7 @@ class StereoMatcher:
         if n_pairs is None:
             n_pairs = left.n_frames - left_first
         check(self.ctx.ptr, lib().cs_stereo_match_from_orb(self.ctx.ptr, self._s, left._e, int(left_first), right._e, int(right_first), int(n_pairs),
-                                                           C.c_float(bf), C.c_float(b)), "cs_stereo_match_from_orb")
+                                                           bf, b), "cs_stereo_match_from_orb")
         self.n_pairs = int(n_pairs)
 
     def match_keys(self, left, right, keysL, descL, keysR, descR, bf, b, left_first=0, right_first=0):
@@ -49,9 +46,8 @@ class StereoMatcher:
             return first, np.ascontiguousarray(k), np.ascontiguousarray(d)
         fL, kL, dL = pack(keysL, descL)
         fR, kR, dR = pack(keysR, descR)
-        check(self.ctx.ptr, lib().cs_stereo_match_from_keys(self.ctx.ptr, self._s, left._e, int(left_first), right._e, int(right_first), n_pairs, _p(fL, C.c_int),
-                                                            C.c_void_p(kL.ctypes.data), _p(dL, C.c_uint8), _p(fR, C.c_int), C.c_void_p(kR.ctypes.data), _p(dR, C.c_uint8),
-                                                            C.c_float(bf), C.c_float(b)), "cs_stereo_match_from_keys")
+        check(self.ctx.ptr, lib().cs_stereo_match_from_keys(self.ctx.ptr, self._s, left._e, int(left_first), right._e, int(right_first), n_pairs, ptr(fL),
+                                                            ptr(kL), ptr(dL), ptr(fR), ptr(kR), ptr(dR), bf, b), "cs_stereo_match_from_keys")
         self.n_pairs = n_pairs
 
     def read(self):
@@ -61,7 +57,7 @@ class StereoMatcher:
         dep = np.zeros((P, self.cap), np.float32)
         counts = np.zeros(P, np.int32)
         nm = np.zeros(P, np.int32)
-        check(self.ctx.ptr, lib().cs_stereo_read(self.ctx.ptr, self._s, _p(ur, C.c_float), _p(dep, C.c_float), self.cap, _p(counts, C.c_int), _p(nm, C.c_int)),
+        check(self.ctx.ptr, lib().cs_stereo_read(self.ctx.ptr, self._s, ptr(ur), ptr(dep), self.cap, ptr(counts), ptr(nm)),
               "cs_stereo_read")
         return [(ur[p, :counts[p]].copy(), dep[p, :counts[p]].copy()) for p in range(P)], nm
 
@@ -70,30 +66,18 @@ class StereoMatcher:
         P = self.n_pairs
         first = np.zeros(P + 1, np.int32)
         total = C.c_long()
-        check(self.ctx.ptr, lib().cs_stereo_read_packed(self.ctx.ptr, self._s, None, None, C.c_long(0), _p(first, C.c_int), C.byref(total), None), "cs_stereo_read_packed")
+        check(self.ctx.ptr, lib().cs_stereo_read_packed(self.ctx.ptr, self._s, None, None, 0, ptr(first), C.byref(total), None), "cs_stereo_read_packed")
         ur = np.zeros(max(total.value, 1), np.float32)
         dep = np.zeros(max(total.value, 1), np.float32)
         nm = np.zeros(P, np.int32)
-        check(self.ctx.ptr, lib().cs_stereo_read_packed(self.ctx.ptr, self._s, _p(ur, C.c_float), _p(dep, C.c_float), C.c_long(len(ur)), _p(first, C.c_int), C.byref(total),
-                                                        _p(nm, C.c_int)), "cs_stereo_read_packed")
+        check(self.ctx.ptr, lib().cs_stereo_read_packed(self.ctx.ptr, self._s, ptr(ur), ptr(dep), len(ur), ptr(first), C.byref(total), ptr(nm)), "cs_stereo_read_packed")
         return ur[:total.value], dep[:total.value], first, nm
 
     def device_pair(self, pair):
         """(device address of mvuRight, of mvDepth, n) of one pair, for cs_match_fuse / cs_pose_optimization callers that keep it on the device."""
-        u, d, n = C.c_void_p(), C.c_void_p(), C.c_int()
+        u, d, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int()
         check(self.ctx.ptr, lib().cs_stereo_device_pair(self._s, int(pair), C.byref(u), C.byref(d), C.byref(n)), "cs_stereo_device_pair")
-        return u.value, d.value, n.value
-
-    def close(self):
-        if self._s:
-            lib().cs_stereo_destroy(self.ctx.ptr, self._s)
-            self._s = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return C.cast(u, C.c_void_p).value, C.cast(d, C.c_void_p).value, n.value
 
 
 def ComputeStereoMatches(left, right, bf, b, left_first=0, right_first=0, n_pairs=None, matcher=None):

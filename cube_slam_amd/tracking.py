@@ -9,13 +9,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, lib, ptr
 from .matcher import ORBmatcher
 from .optimizer import PoseOptimization
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
 
 
 def _i32(a):
@@ -30,7 +26,7 @@ def track_local_points(ctx, kf_off, kf_mp, skip):
     """Tracking::UpdateLocalPoints (cs_track_local_points): the concatenated map-point lists of the local key frames -> mvpLocalMapPoints."""
     off, mp, sk = _i32(kf_off), _i32(kf_mp), _u8(skip)
     out = np.zeros(max(min(int(off[-1]), len(sk)), 1), np.int32); n = C.c_int()
-    check(ctx.ptr, lib().cs_track_local_points(ctx.ptr, len(off) - 1, _p(off, C.c_int), _p(mp, C.c_int), len(sk), _p(sk, C.c_uint8), _p(out, C.c_int), C.byref(n)), "cs_track_local_points")
+    check(ctx.ptr, lib().cs_track_local_points(ctx.ptr, len(off) - 1, ptr(off), ptr(mp), len(sk), ptr(sk), ptr(out), C.byref(n)), "cs_track_local_points")
     return out[:n.value].copy()
 
 
@@ -39,8 +35,8 @@ def track_local_keyframes(frame_mp, mp_skip, obs_off, obs_kf, kf_bad, cov_off, c
     fm, ms, oo, ok, kb = _i32(frame_mp), _u8(mp_skip), _i32(obs_off), _i32(obs_kf), _u8(kf_bad)
     co, ck, ho, hk, pa = _i32(cov_off), _i32(cov_kf), _i32(child_off), _i32(child_kf), _i32(parent)
     out = np.zeros(max(len(kb), 1), np.int32); n = C.c_int(); mx = C.c_int()
-    r = lib().cs_track_local_keyframes(len(fm), _p(fm, C.c_int), len(ms), _p(ms, C.c_uint8), _p(oo, C.c_int), _p(ok, C.c_int), len(kb), _p(kb, C.c_uint8), _p(co, C.c_int), _p(ck, C.c_int),
-                                       _p(ho, C.c_int), _p(hk, C.c_int), _p(pa, C.c_int), _p(out, C.c_int), C.byref(n), C.byref(mx))
+    r = lib().cs_track_local_keyframes(len(fm), ptr(fm), len(ms), ptr(ms), ptr(oo), ptr(ok), len(kb), ptr(kb), ptr(co), ptr(ck),
+                                       ptr(ho), ptr(hk), ptr(pa), ptr(out), C.byref(n), C.byref(mx))
     check(None, r, "cs_track_local_keyframes")
     return (None if n.value < 0 else out[:n.value].copy()), mx.value
 

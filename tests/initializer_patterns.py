@@ -136,9 +136,7 @@ def concat(outs):
 def raw_call(ctx, cases, sentinel=0x5A):
     """cs_initializer_evaluate called directly, every output byte set to `sentinel` beforehand -> (status, last error text, the output arrays): for the refusals, which must
     leave them untouched."""
-    import ctypes as C
-    from cube_slam_amd._lib import lib
-    from cube_slam_amd._ransac import _p
+    from cube_slam_amd._lib import lib, ptr
     co, ho = offsets(c["N"] for c in cases), offsets(len(c["sets"]) for c in cases)
     cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(c[key], dt).reshape(-1, w) for c in cases])).reshape(-1)
     k1o, k2o = offsets(len(c["keys1"]) for c in cases), offsets(len(c["keys2"]) for c in cases)
@@ -151,9 +149,6 @@ def raw_call(ctx, cases, sentinel=0x5A):
              ("n_inliers", np.int32, n), ("n_cand", np.int32, n), ("cand_Rt", F32, 96 * n), ("nGood", np.int32, 8 * n), ("cos_parallax", F32, 8 * n),
              ("good_mask", np.uint32, cwords), ("points", F32, 24 * NC))
     out = {k: np.frombuffer(bytes([sentinel]) * (np.dtype(dt).itemsize * max(sz, 1)), dt).copy() for k, dt, sz in sizes}
-    ct = {np.dtype(F32): C.c_float, np.dtype(np.int32): C.c_int, np.dtype(np.uint32): C.c_uint32}
     cp = ctx.ptr if ctx is not None else None
-    rc = lib().cs_initializer_evaluate(cp, n, _p(k1o, C.c_int), _p(a1, C.c_float), _p(k2o, C.c_int), _p(a2, C.c_float), _p(co, C.c_int), _p(mt, C.c_int), _p(k9, C.c_float),
-                                       _p(sg, C.c_float), _p(ho, C.c_int), _p(st, C.c_int), *[_p(out[k], ct[out[k].dtype]) for k, _, _ in sizes])
-    lib().cs_last_error.restype = C.c_char_p
+    rc = lib().cs_initializer_evaluate(cp, n, ptr(k1o), ptr(a1), ptr(k2o), ptr(a2), ptr(co), ptr(mt), ptr(k9), ptr(sg), ptr(ho), ptr(st), *[ptr(out[k]) for k, _, _ in sizes])
     return rc, (lib().cs_last_error(cp).decode() if cp is not None else ""), out

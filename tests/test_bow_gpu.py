@@ -85,8 +85,7 @@ def test_malformed_vocabularies_are_refused(ctx):
         out = C.c_void_p(1)
         parent = np.ascontiguousarray(parent, np.int32); leaf = np.ascontiguousarray(leaf, np.uint8)
         u = P.vocabularies()["unbalanced"][0] if len(parent) != len(v.parent) else v
-        r = _lib.lib().cs_bow_vocab_create(ctx.ptr, k, L, len(parent), parent.ctypes.data_as(C.c_void_p), leaf.ctypes.data_as(C.c_void_p), u.desc.ctypes.data_as(C.c_void_p),
-                                           u.weight.ctypes.data_as(C.c_void_p), up, we, sc, C.byref(out))
+        r = _lib.lib().cs_bow_vocab_create(ctx.ptr, k, L, len(parent), _lib.ptr(parent), _lib.ptr(leaf), _lib.ptr(u.desc), _lib.ptr(u.weight), up, we, sc, C.byref(out))
         assert r == -2 and not out.value, name
 
 

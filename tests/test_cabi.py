@@ -29,6 +29,79 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def _naive_signatures():
+    """{function: number of parameters} by splitting the text between the parentheses on commas, (void) counting as 0, and {function: restype} from the words before the name."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cubeslam_hip.h")).read(), flags=re.S)
+    counts, returns = {}, {}
+    for ret, name, inside in re.findall(r"^([a-z \*]+?)\s*\b(cs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        counts[name] = 0 if inside.strip() in ("", "void") else len(inside.split(","))
+        returns[name] = {"int": C.c_int, "void": None, "long": C.c_long, "const char *": C.c_char_p}[ret]
+    return counts, returns
+
+
+def test_every_declaration_has_a_signature():
+    from cube_slam_amd import _lib
+    lib = _lib.lib()
+    names, (counts, returns) = _declared_functions(), _naive_signatures()
+    assert sorted(counts) == names and len(names) == 184
+    for n in names:
+        f = getattr(lib, n)
+        assert isinstance(f.argtypes, list) and len(f.argtypes) == counts[n], n
+        assert f.restype is returns[n], n
+    ip, fp, bp = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+    assert lib.cs_last_error.restype is C.c_char_p
+    assert lib.cs_sim3_solver_mask_words.restype is C.c_long
+    assert lib.cs_destroy.restype is None and lib.cs_destroy.argtypes == [C.c_void_p]
+    assert lib.cs_matcher_create.argtypes == [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]
+    assert lib.cs_klt_track_host.restype is C.c_int
+    assert lib.cs_klt_track_host.argtypes == [bp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, ip, ip, ip, fp, fp, bp, fp]
+
+
+def test_wrong_dtype_is_refused_before_the_call():
+    """ctypes refuses the argument while it converts it, so the function is never entered: a host entry point (cs_klt_track_host) and a
+    device entry point with a NULL context (cs_klt_track)."""
+    from cube_slam_amd import _lib
+    lib, ptr = _lib.lib(), _lib.ptr
+    g, prev, nxt, first, pts = np.zeros((2, 32, 32), np.uint8), np.zeros(1, np.int32), np.ones(1, np.int32), np.array([0, 1], np.int32), np.full((1, 2), 16, np.float32)
+    out, st, err = np.zeros((1, 2), np.float32), np.zeros(1, np.uint8), np.zeros(1, np.float32)
+    f64, i64 = pts.astype(np.float64), prev.astype(np.int64)
+    host = lambda prev, pts, width=32: lib.cs_klt_track_host(ptr(g), 2, width, 32, 32, 1, ptr(prev), ptr(nxt), ptr(first), ptr(pts), ptr(out), ptr(st), ptr(err))
+    device = lambda prev, pts, n_pairs=1: lib.cs_klt_track(None, None, n_pairs, ptr(prev), ptr(nxt), ptr(first), ptr(pts), ptr(out), ptr(st), ptr(err))
+    assert host(prev, pts) == 0  # the right types reach the function: one point across two flat frames
+    assert device(prev, pts) == -2  # ... and CS_ERR_BAD_ARG for the NULL context
+    for call in (host, device):
+        with pytest.raises(C.ArgumentError):
+            call(prev, f64)  # float64 for const float *
+        with pytest.raises(C.ArgumentError):
+            call(i64, pts)  # int64 for const int *
+        with pytest.raises(C.ArgumentError):
+            call(prev, pts, 1.0)  # a Python float for an int
+
+
+def test_unknown_type_fails_the_load():
+    from cube_slam_amd import _lib
+    text = open(os.path.join(ROOT, "include", "cubeslam_hip.h")).read()
+    assert len(_lib.signatures(text)) == 184
+    bad = text.replace("int cs_klt_create(cs_ctx *ctx, int max_frames,", "int cs_klt_create(cs_ctx *ctx, short max_frames,")
+    assert bad != text
+    with pytest.raises(_lib.CubeSlamError, match="cs_klt_create.*short max_frames"):
+        _lib.signatures(bad)
+
+
+def test_no_per_module_signatures_remain():
+    """The header is the one signature table: no wrapper module types a call by hand.  C.byref(C.c_double()) for an out-parameter is allowed
+    (an empty constructor)."""
+    bad = []
+    for f in sorted(glob.glob(os.path.join(ROOT, "cube_slam_amd", "*.py"))):
+        if os.path.basename(f) == "_lib.py":
+            continue
+        for no, line in enumerate(open(f), 1):
+            code = line.split("#")[0]
+            if re.search(r"\.argtypes\b|\.restype\b|def _p\(|\bC\.c_(float|double|long)\([^)]", code):
+                bad.append("%s:%d: %s" % (os.path.basename(f), no, line.strip()))
+    assert not bad, "\n".join(bad)
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():

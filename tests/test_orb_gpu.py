@@ -102,7 +102,7 @@ def test_packed_read_and_device_frames_equal_the_per_frame_paths(ctx):
     other = np.ascontiguousarray(imgs[::-1])  # the same frames in another order, from device memory
     d = torch.from_numpy(other).to("cuda:0")
     torch.cuda.synchronize()
-    check(ctx.ptr, lib().cs_orb_set_frames_device(ctx.ptr, ext._e, C.c_void_p(d.data_ptr()), 3), "cs_orb_set_frames_device")
+    check(ctx.ptr, lib().cs_orb_set_frames_device(ctx.ptr, ext._e, C.cast(d.data_ptr(), C.POINTER(C.c_uint8)), 3), "cs_orb_set_frames_device")
     ext.run()
     got = ext.read()
     for f in range(3):

@@ -21,7 +21,7 @@ def test_single_rank_communicator_allreduce(ctx):
     c.comm_init(0, 1, _lib.Context.comm_unique_id())
     x = torch.arange(1000, dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
-    _lib.check(c.ptr, _lib.lib().cs_comm_allreduce_f64(c.ptr, C.c_void_p(x.data_ptr()), C.c_long(x.numel())), "cs_comm_allreduce_f64")
+    _lib.check(c.ptr, _lib.lib().cs_comm_allreduce_f64(c.ptr, C.cast(x.data_ptr(), C.POINTER(C.c_double)), C.c_long(x.numel())), "cs_comm_allreduce_f64")
     c.sync()
     assert torch.equal(x.cpu(), torch.arange(1000, dtype=torch.float64))
     c.close()

@@ -281,7 +281,7 @@ def test_errors(ctx):
     first, total = np.zeros(2, np.int32), C.c_long()
     assert lib.cs_rgbd_read_packed(ctx.ptr, exact._h, pf(u), pf(d), C.c_long(n - 1), pi(first), C.byref(total), None, None) == CAPACITY and np.all(u == 7) and total.value == n
     assert lib.cs_rgbd_read(ctx.ptr, exact._h, pf(u), pf(d), n, pi(cnt), pi(nd), None) == 0 and cnt[0] == n and SHARE_LO * n <= nd[0] == int((d > 0).sum()) <= SHARE_HI * n
-    p = [C.c_void_p() for _ in range(3)]
+    p = [C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_void_p()]
     k = C.c_int()
     assert lib.cs_rgbd_device_frame(exact._h, 1, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(k)) == BAD_ARG
     assert lib.cs_rgbd_device_frame(exact._h, 0, C.byref(p[0]), C.byref(p[1]), None, C.byref(k)) == 0 and k.value == n

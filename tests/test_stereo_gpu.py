@@ -216,7 +216,7 @@ def test_bad_arguments(ctx):
         other.run()
         assert call(extL, 0, other, 0, 1, sr.BF, B) == BAD_ARG  # geometry differs
         other.close()
-    u, d, n = C.c_void_p(), C.c_void_p(), C.c_int()
+    u, d, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int()
     assert lib.cs_stereo_device_pair(m._s, 1, C.byref(u), C.byref(d), C.byref(n)) == BAD_ARG
     assert lib.cs_stereo_device_pair(m._s, 0, C.byref(u), C.byref(d), C.byref(n)) == 0 and n.value > 0
     with pytest.raises(_lib.CubeSlamError):

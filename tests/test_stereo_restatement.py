@@ -122,7 +122,7 @@ def test_bad_arguments_without_a_handle():
     assert lib.cs_stereo_read(fake, None, pf, pf, 4, pi, pi) == BAD
     assert lib.cs_stereo_read_packed(None, None, pf, pf, C.c_long(4), pi, C.byref(total), pi) == BAD
     assert lib.cs_stereo_read_packed(fake, None, pf, pf, C.c_long(4), pi, C.byref(total), pi) == BAD
-    u, d, n = C.c_void_p(), C.c_void_p(), C.c_int()
+    u, d, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int()
     assert lib.cs_stereo_device_pair(None, 0, C.byref(u), C.byref(d), C.byref(n)) == BAD
     lib.cs_stereo_destroy(None, None)  # a no-op, like its neighbours
 

@@ -984,6 +984,16 @@ int cs_lsd_region_stats(cs_ctx *ctx, cs_lsd *l, long out[5]) {
     return CS_OK;
 }
 
+// Probe of the device region stage's nfa() table, for the tests (exported, not part of the public header: tests/test_lsd_nfa_table_gpu.py through
+// line_lbd_detect.nfa_probe).  For the m triples (n, k, j), 0 <= k <= n, 0 <= j <= 10, out[2 i] is the double the table path yields for p = 2^-(3+j) (NaN where
+// the table holds none: n above its bound) and out[2 i + 1] the double the direct call yields.  counters[0 .. 1]: rectangles the table kernel finished / deferred
+// in the last device-stage run.  CS_ERR_BAD_ARG before the detector's first device-stage run (the table belongs to its scaled size).
+int cs_lsd_nfa_probe(cs_ctx *ctx, cs_lsd *l, int m, const int *triples, double *out, long *counters) {
+    if (!ctx || !l) return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    return lsd_seq_nfa_probe(ctx, l->seq, m, triples, out, counters);
+}
+
 int cs_lsd_read(cs_ctx *ctx, cs_lsd *l, int frame, cs_keyline *out, int cap, int *count, uint8_t *desc) {
     if (!ctx || !l || frame < 0 || frame >= l->n_frames || !count || (int)l->keylines.size() <= frame || (desc && !l->have_desc)) return CS_ERR_BAD_ARG;
     const int n = (int)l->keylines[frame].size();

@@ -12,7 +12,8 @@
 //     Output: the rectangles that reach rect_improve (after refine / reduce_region_radius), per frame in seed order.
 //   * lsd_rg_improve: eight rectangles per wave for rect_improve's first rect_nfa (two thirds are accepted there), the others improved one at a time by
 //     the whole wave; the rows of a rectangle spread over lanes (the row limits advance by integer steps, lsd.cpp:1057-1095, so they have a closed form),
-//     the five variants of a rect_improve loop walked and their nfa() evaluated side by side, log_gamma of the pixel counts from a table.
+//     the five variants of a rect_improve loop walked and their nfa() evaluated side by side, log_gamma of the pixel counts from a table.  nfa() itself is read
+//     from a table of its results (lsd_rg_nfa_table: n <= NFA_NMAX pixels); the few rectangles beyond it are left to lsd_rg_improve_deferred, which evaluates.
 //   * the segments leave in the reference's emission order (frames in order, seeds in order).
 //
 // tools/lsd_sim/seq_sim.cpp compiles lsd_rg_seq.h for the host (the lanes as loops) and demands the oracle's sequential result: the same
@@ -81,6 +82,36 @@ __device__ double rg_nfa(int n, int k, double p, double LOG_NT, const double *lg
     }
     return -log10(bin_tail) - LOG_NT;
 }
+__device__ __forceinline__ double rg_log_nt(int w, int h) { return 5 * (log10(double(w)) + log10(double(h))) / 2 + log10(11.0); } // one expression for every kernel that asks for it
+// nfa() as a table of its results: rg_nfa is a pure function of two pixel counts and of p, and rect_improve only ever halves p from ANG_TH / 180 = 2^-3, ten times at the
+// most.  T[j][n][k] = rg_nfa(n, k, 2^-(3+j)) for 0 <= k <= n <= NFA_NMAX, triangular, filled by rg_nfa itself with the detector's LOG_NT: an entry is the bits the
+// direct call returns (the early returns for n == 0, k == 0, n == k included: they are entries like the others).  What the table does not hold -- more than nmax
+// pixels, a p off the grid -- is a MISS: the table kernel evaluates nothing itself.
+constexpr int NFA_NP = 11, NFA_NMAX = 511, NFA_TRI = (NFA_NMAX + 1) * (NFA_NMAX + 2) / 2;
+__global__ void __launch_bounds__(256) lsd_rg_nfa_table(double *T, int w, int h, const double *lgt) {
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= NFA_TRI) return;
+    int n = int((sqrt(8.0 * i + 1) - 1) / 2); // i = n (n + 1) / 2 + k
+    while (n * (n + 1) / 2 > i) n--;
+    while ((n + 1) * (n + 2) / 2 <= i) n++;
+    T[(size_t)j * NFA_TRI + i] = rg_nfa(n, i - n * (n + 1) / 2, ldexp(1.0, -(3 + j)), rg_log_nt(w, h), lgt);
+}
+struct NfaDirect { // the evaluation itself
+    static constexpr bool GROUP_TOLERANCES = false;
+    double LOG_NT; const double *lgt;
+    __device__ __forceinline__ double operator()(int n, int k, double p, bool &) const { return rg_nfa(n, k, p, LOG_NT, lgt); }
+};
+struct NfaTable { // nmax: the largest n served (-1: none)
+    static constexpr bool GROUP_TOLERANCES = true;
+    const double *T; int nmax;
+    __device__ __forceinline__ double operator()(int n, int k, double p, bool &miss) const {
+        const long long b = __double_as_longlong(p);
+        const int j = 1020 - int(b >> 52); // p = 2^-(3+j) has the exponent field 1023 - 3 - j, no mantissa bit and no sign (a sign makes j large)
+        const bool ok = (b & 0xfffffffffffffLL) == 0 && j >= 0 && j < NFA_NP && n <= nmax && k >= 0 && k <= n;
+        miss = !ok;
+        return T[ok ? (size_t)j * NFA_TRI + n * (n + 1) / 2 + k : 0];
+    }
+};
 // What rect_nfa's row walk needs of a rectangle: the first and last row inside the image and, per row, the closed form of the reference's stepping limits.
 struct RectSpan {
     int mnX, lmY, rmY, flstep, slstep, frstep, srstep, y_first, y_hi;
@@ -192,7 +223,8 @@ __device__ __forceinline__ rg::Rect rg_rect_shfl(const rg::Rect &r, int src) {
 // best is picked by reading the groups' nfa() in variant order with the reference's strict `>`.  No array is indexed at run time (such arrays live in
 // scratch memory: 688 bytes per lane and ~490 store instructions per wave before).
 // log_nfa: rect_nfa of the rectangle as it comes (the kernel computes it for eight rectangles at once).
-__device__ double rg_rect_improve(const AngMap &F, rg::Rect &rec, double LOG_NT, int lane, const double *lgt, double log_nfa) {
+// E: the evaluator of nfa().  missed: the table could not serve a variant that counts -- the rectangle is abandoned as it stands and the caller defers it.
+template <class E> __device__ double rg_rect_improve(const AngMap &F, rg::Rect &rec, const E &nfa, int lane, double log_nfa, bool &missed) {
     const double delta = 0.5, delta_2 = delta / 2.0;
     if (log_nfa > LOG_EPS) return log_nfa;
     const int g = lane >> 3, sub = lane & 7;
@@ -207,11 +239,15 @@ __device__ double rg_rect_improve(const AngMap &F, rg::Rect &rec, double LOG_NT,
         double p = rec.p, precs[5];
 #pragma unroll
         for (int n = 0; n < 5; ++n) { p /= 2; precs[n] = p * PI_; if (n <= g) { mine.p = p; mine.prec = precs[n]; } }
+        cnt = 5;
+        // The table kernel walks the tolerances like the other loops' variants, group g with its own tolerance (the counts are integers: the same numbers either
+        // way).  The one walk with five counters per pixel is what held its registers: 128 VGPRs + 136 B of scratch with it, 100 without.  The rectangles it serves
+        // are small (n <= NFA_NMAX); the large ones are the deferred kernel's, which keeps the 64-lane walk.
+        if constexpr (E::GROUP_TOLERANCES) { rg_rect_count_group(F, mine, g < 5, sub, tot, al); return; }
         int t, alg[5]; rg_rect_count<5>(F, rec, precs, lane, t, alg);
         tot = t; al = alg[0];
 #pragma unroll
         for (int n = 1; n < 5; ++n) if (g == n) al = alg[n];
-        cnt = 5;
     };
     auto shrink = [&](int side) { // side 0: the width, 1 / 2: one side / the other
         mine = rec; cnt = 0;
@@ -228,18 +264,20 @@ __device__ double rg_rect_improve(const AngMap &F, rg::Rect &rec, double LOG_NT,
     };
     auto take_best = [&]() { // the best variant: nfa() of each group, read in variant order with the reference's strict `>`
         const bool on = g < cnt;
-        const double mv = rg_nfa(on ? tot : 0, on ? al : 0, mine.p, LOG_NT, lgt); // (n = 0: an immediate return in the groups without a variant)
+        bool miss = false;
+        const double mv = nfa(on ? tot : 0, on ? al : 0, mine.p, miss); // (n = 0: an immediate return in the groups without a variant)
+        if (__any(on && miss)) { missed = true; return; }
         int best = -1;
 #pragma unroll
         for (int n = 0; n < 5; ++n) { const double vn = __shfl(mv, 8 * n); if (n < cnt && vn > log_nfa) { log_nfa = vn; best = n; } }
         if (best >= 0) rec = rg_rect_shfl(mine, 8 * best);
     };
     tolerances(); take_best();
-    if (log_nfa > LOG_EPS) return log_nfa;
+    if (missed || log_nfa > LOG_EPS) return log_nfa;
     for (int side = 0; side < 3; side++) {
         shrink(side);
         if (cnt) take_best();
-        if (log_nfa > LOG_EPS) return log_nfa;
+        if (missed || log_nfa > LOG_EPS) return log_nfa;
     }
     if ((rec.width - delta) >= 0.5) { tolerances(); take_best(); }
     return log_nfa;
@@ -352,10 +390,22 @@ __global__ void __launch_bounds__(1024) lsd_rg_cand_scan(const int *cand_cnt, in
 // Eight rectangles per wave.  rect_improve starts with rect_nfa of the rectangle as it is, and two thirds of the rectangles are accepted there: that first walk (28
 // pixels in 7 rows on average) and its nfa() run for eight rectangles at once, eight lanes each -- every lane of a group evaluates its rectangle's nfa(), which costs
 // the wave what one evaluation costs.  The rectangles that go on are then improved one after the other by the whole wave.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMPROVE_WAVES, RG_IMPROVE_WAVES))) lsd_rg_improve(SeqParams P, const int *cand_base, int n_cand, const double *lgt, float4 *line, uint8_t *has) {
+//
+// The body twice.  lsd_rg_improve reads nfa() from the table (NfaTable) and holds no evaluation of it: with the tolerances walked per lane group (rg_rect_improve) that lets it into 91 registers, four waves a SIMD,
+// beside four region walks.  A rectangle that meets a miss, in the first rect_nfa or anywhere in its rect_improve, is abandoned: has[k] = HAS_DEFERRED and no line.
+// lsd_rg_improve_deferred (REDO, NfaDirect: the kernel as it was) follows on the same stream over the same range; a wave of it reads its eight has[] bytes, leaves
+// when none is deferred and otherwise does exactly the deferred rectangles from the start.  A rectangle's result depends on no other rectangle.
+// counters (table kernel): rectangles it finished | rectangles it deferred << 32, one atomicAdd per wave.
+constexpr uint8_t HAS_DEFERRED = 2;
+template <class E, bool REDO> __device__ __forceinline__ void lsd_rg_improve_body(const SeqParams &P, const int *cand_base, int n_cand, const E &nfa, float4 *line, uint8_t *has, unsigned long long *counters) {
     const int base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 8, lane = threadIdx.x & 63, grp = lane >> 3, sub = lane & 7;
     if (base >= n_cand) return;
-    const double LOG_NT = 5 * (log10(double(P.w)) + log10(double(P.h))) / 2 + log10(11.0);
+    const int mine = base + grp;
+    bool on = mine < n_cand;
+    if (REDO) {
+        on = on && has[mine] == HAS_DEFERRED;
+        if (!__any(on)) return;
+    }
     auto frame_of = [&](int wv) { int lo = 0, hi = P.F; while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cand_base[mid] <= wv) lo = mid; else hi = mid; } return lo; }; // cand_base[f] <= wv < cand_base[f + 1]
     auto load_rect = [&](int wv, int f, rg::Rect &rec) {
         const double *o = P.rect + (size_t)f * P.rect_stride + (size_t)(wv - cand_base[f]) * 12;
@@ -371,12 +421,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMP
         has[wv] = ok ? 1 : 0;
     };
     // ---- rect_nfa of eight rectangles
-    const int mine = base + grp;
-    const bool on = mine < n_cand;
     const int f1 = frame_of(on ? mine : n_cand - 1);
     rg::Rect r1;
     load_rect(on ? mine : n_cand - 1, f1, r1);
     double log1;
+    bool miss1 = false;
     {
         RectSpan S; S.set(r1, P.h);
         const float *deg = P.ang + (size_t)f1 * P.w * P.h;
@@ -389,11 +438,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMP
                 rg_row_count<1>(deg + (size_t)y * P.w, lx, rx, 0, 1, r1.theta, &r1.prec, alg);
             }
         for (int off = 1; off < 8; off <<= 1) { tot += __shfl_xor(tot, off); alg[0] += __shfl_xor(alg[0], off); }
-        log1 = rg_nfa(tot, alg[0], r1.p, LOG_NT, lgt);
+        log1 = nfa(tot, alg[0], r1.p, miss1);
     }
-    if (on && sub == 0 && log1 > LOG_EPS) emit(mine, r1, log1);
+    if (on && sub == 0) { if (miss1) has[mine] = HAS_DEFERRED; else if (log1 > LOG_EPS) emit(mine, r1, log1); }
+    int n_deferred = __popcll(__ballot(on && sub == 0 && miss1));
     // ---- the others, one at a time
-    unsigned long long todo = __ballot(on && sub == 0 && !(log1 > LOG_EPS));
+    unsigned long long todo = __ballot(on && sub == 0 && !miss1 && !(log1 > LOG_EPS));
     while (todo) {
         const int l = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
@@ -402,9 +452,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMP
         rg::Rect rec;
         load_rect(wv, f, rec);
         const AngMap Fr = {P.w, P.h, P.ang + (size_t)f * P.w * P.h};
-        const double log_nfa = rg_rect_improve(Fr, rec, LOG_NT, lane, lgt, first);
-        if (lane == 0) emit(wv, rec, log_nfa);
+        bool missed = false;
+        const double log_nfa = rg_rect_improve(Fr, rec, nfa, lane, first, missed);
+        if (missed) { n_deferred++; if (lane == 0) has[wv] = HAS_DEFERRED; }
+        else if (lane == 0) emit(wv, rec, log_nfa);
     }
+    if (!REDO && lane == 0) atomicAdd(counters, (unsigned long long)(min(8, n_cand - base) - n_deferred) | (unsigned long long)n_deferred << 32);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) lsd_rg_improve(SeqParams P, const int *cand_base, int n_cand, const double *nfa_table, int nfa_nmax, float4 *line, uint8_t *has, unsigned long long *counters) {
+    lsd_rg_improve_body<NfaTable, false>(P, cand_base, n_cand, NfaTable{nfa_table, nfa_nmax}, line, has, counters);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RG_IMPROVE_WAVES, RG_IMPROVE_WAVES))) lsd_rg_improve_deferred(SeqParams P, const int *cand_base, int n_cand, const double *lgt, float4 *line, uint8_t *has) {
+    lsd_rg_improve_body<NfaDirect, true>(P, cand_base, n_cand, NfaDirect{rg_log_nt(P.w, P.h), lgt}, line, has, nullptr);
+}
+// cs_lsd_nfa_probe: out[2 i] what the table path gives for (n, k, j) = t[3 i ..] (NaN where it misses), out[2 i + 1] what the direct call gives
+__global__ void __launch_bounds__(256) lsd_rg_nfa_probe(const int *t, int m, const double *nfa_table, int nfa_nmax, int w, int h, const double *lgt, double *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const int n = t[3 * i], k = t[3 * i + 1], j = t[3 * i + 2];
+    const double p = ldexp(1.0, -(3 + j));
+    bool miss = false;
+    const double v = NfaTable{nfa_table, nfa_nmax}(n, k, p, miss);
+    out[2 * i] = miss ? __longlong_as_double(0x7ff8000000000000LL) : v;
+    out[2 * i + 1] = rg_nfa(n, k, p, rg_log_nt(w, h), lgt);
 }
 } // namespace
 
@@ -414,16 +484,22 @@ struct LsdSeq {
     float *d_pix = nullptr; bool pix_borrowed = false; // lsd_rg_seq's map, a float per pixel (borrowed: the caller's scratch, not freed here)
     rgl::Ent *d_elist = nullptr; float *d_ang32 = nullptr; int *d_order = nullptr; // the lane-per-frame walk (lsd_rg_wlk): region lists of 8-byte entries, a float per pixel, the frames sorted by work
     int *d_glist = nullptr, *d_cand_cnt = nullptr, *d_cand_base = nullptr, *d_status = nullptr, *d_frame_base = nullptr;
-    double *d_rect = nullptr, *d_lgt = nullptr;
+    double *d_rect = nullptr, *d_lgt = nullptr, *d_nfa = nullptr; // d_nfa: nfa()'s result table (lsd_rg_nfa_table), built with d_lgt for this w x h
+    unsigned long long *d_counters = nullptr; cs_pinned<unsigned long long> h_counters; long nfa_counts[2] = {0, 0}; // last run: rectangles the table kernel finished / deferred
     uint8_t *d_has = nullptr;
     float4 *d_line = nullptr;
     cs_pinned<int> h_base, h_status; cs_pinned<uint8_t> h_has; cs_pinned<float4> h_line; // the hand-overs to the host, pinned (lsd_seq_destroy frees them)
 };
+// the largest n the table kernel is given: the compiled bound, or what CUBESLAM_LSD_NFA_NMAX lowers it to (tests: a small bound walks the deferral; 0 defers every rectangle)
+static int lsd_nfa_bound() {
+    const char *e = getenv("CUBESLAM_LSD_NFA_NMAX");
+    return e ? std::max(0, std::min(NFA_NMAX, atoi(e))) : NFA_NMAX;
+}
 void lsd_seq_destroy(cs_ctx *ctx, LsdSeq *r) {
     if (!r) return;
-    void *ptrs[] = {r->d_elist, r->d_ang32, r->d_order, r->pix_borrowed ? nullptr : r->d_pix, r->d_glist, r->d_cand_cnt, r->d_cand_base, r->d_status, r->d_frame_base, r->d_rect, r->d_lgt, r->d_has, r->d_line};
+    void *ptrs[] = {r->d_elist, r->d_ang32, r->d_order, r->pix_borrowed ? nullptr : r->d_pix, r->d_glist, r->d_cand_cnt, r->d_cand_base, r->d_status, r->d_frame_base, r->d_rect, r->d_lgt, r->d_nfa, r->d_counters, r->d_has, r->d_line};
     for (void *p : ptrs) cs_dfree(ctx, p);
-    r->h_base.release(); r->h_status.release(); r->h_has.release(); r->h_line.release();
+    r->h_base.release(); r->h_status.release(); r->h_has.release(); r->h_line.release(); r->h_counters.release();
     delete r;
 }
 // The region stage of F frames, one wave per frame.  lines[f] = x1 y1 x2 y2 floats in the reference's emission order.  CS_ERR_CAPACITY: a region
@@ -456,6 +532,8 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
         RA_(cs_dalloc(ctx, &r->d_status, (size_t)F * 4)); RA_(cs_dalloc(ctx, &r->d_frame_base, (size_t)F + 1));
         RA_(cs_dalloc(ctx, &r->d_lgt, (size_t)LG_N));
         CS_LAUNCH(ctx, "lsd_rg_lgamma_table", lsd_rg_lgamma_table, dim3(LG_N / 256), dim3(256), 0, r->d_lgt);
+        RA_(cs_dalloc(ctx, &r->d_nfa, (size_t)NFA_NP * NFA_TRI)); RA_(cs_dalloc(ctx, &r->d_counters, (size_t)1)); RA_(r->h_counters.reserve(ctx, (size_t)1));
+        CS_LAUNCH(ctx, "lsd_rg_nfa_table", lsd_rg_nfa_table, dim3((NFA_TRI + 255) / 256, NFA_NP), dim3(256), 0, r->d_nfa, w, h, r->d_lgt);
     }
     RA_(cs_h2d(ctx, r->d_frame_base, frame_base, (size_t)F + 1));
     SeqParams S;
@@ -465,6 +543,7 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     S.min_reg_size = int(-LOG_NT / std::log10(rg::ANG_TH / 180));
     S.list_cap = rgs::CAP;
     if (const char *e = getenv("CUBESLAM_LSD_SEQ_CAP")) S.list_cap = std::max(2, std::min(rgs::CAP, atoi(e))); // (tests: a small cap walks the fallback to the host stage)
+    const int nfa_nmax = lsd_nfa_bound();
     if (grp_p != 0 && grp_p != 65) return CS_ERR_BAD_ARG;
     const bool grp = grp_p == 65, pad = grp; // walker + rectangle waves (lsd_rg_wlk.h): a float per pixel, 8-byte list entries, padded strides
     const size_t rect_stride = (size_t)r->cand_cap * 12 + (pad ? PAD_RECT : 0), list_stride = (size_t)rgl::CAP + (pad ? PAD_LIST : 0);
@@ -549,6 +628,7 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
     if (stats) { stats[0] = grows; stats[1] = fetches; stats[2] = n_cand; stats[3] = nreg; }
     if (bad) return CS_ERR_CAPACITY;
     lines.assign((size_t)F, {});
+    r->nfa_counts[0] = r->nfa_counts[1] = 0;
     if (n_cand == 0) return CS_OK;
     if ((size_t)n_cand > r->cap_lines) {
         cs_dfree(ctx, r->d_line); cs_dfree(ctx, r->d_has);
@@ -557,15 +637,34 @@ int lsd_seq_run(cs_ctx *ctx, LsdSeq **handle, int F, int w, int h, const float *
         RA_(cs_dalloc(ctx, &r->d_line, cap)); RA_(cs_dalloc(ctx, &r->d_has, cap));
         r->cap_lines = cap;
     }
-    CS_LAUNCH(ctx, "lsd_rg_improve", lsd_rg_improve, dim3((n_cand + 31) / 32), dim3(256), 0, S, r->d_cand_base, n_cand, r->d_lgt, r->d_line, r->d_has); // eight rectangles per wave
     RA_(r->h_has.reserve(ctx, (size_t)n_cand)); RA_(r->h_line.reserve(ctx, (size_t)n_cand));
+    CS_HIP(ctx, hipMemsetAsync(r->d_counters, 0, sizeof(unsigned long long), ctx->stream));
+    CS_LAUNCH(ctx, "lsd_rg_improve", lsd_rg_improve, dim3((n_cand + 31) / 32), dim3(256), 0, S, r->d_cand_base, n_cand, r->d_nfa, nfa_nmax ? nfa_nmax : -1, r->d_line, r->d_has, r->d_counters); // eight rectangles per wave, nfa() from the table
+    CS_LAUNCH(ctx, "lsd_rg_improve_deferred", lsd_rg_improve_deferred, dim3((n_cand + 31) / 32), dim3(256), 0, S, r->d_cand_base, n_cand, r->d_lgt, r->d_line, r->d_has); // the rectangles the table could not serve
     RA_(cs_d2h(ctx, r->h_has.p, r->d_has, (size_t)n_cand));
     RA_(cs_d2h(ctx, r->h_line.p, r->d_line, (size_t)n_cand));
+    RA_(cs_d2h(ctx, r->h_counters.p, r->d_counters, (size_t)1));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    r->nfa_counts[0] = (long)(r->h_counters.p[0] & 0xffffffffull); r->nfa_counts[1] = (long)(r->h_counters.p[0] >> 32);
 #undef RA_
 #pragma omp parallel for schedule(static) num_threads(std::max(1, std::min(ctx->host_threads, F)))
     for (int f = 0; f < F; f++)
         for (int k = r->h_base.p[f]; k < r->h_base.p[f + 1]; k++)
             if (r->h_has.p[k]) { const float4 v = r->h_line.p[k]; lines[f].push_back(v.x); lines[f].push_back(v.y); lines[f].push_back(v.z); lines[f].push_back(v.w); }
     return CS_OK;
+}
+// cs_lsd_nfa_probe (lsd.hip): the table of the detector's last device-stage run against the direct call, and that run's two counters
+int lsd_seq_nfa_probe(cs_ctx *ctx, LsdSeq *r, int m, const int *triples, double *out, long *counters) {
+    if (!r || !r->d_nfa || m < 0 || (m > 0 && (!triples || !out))) return CS_ERR_BAD_ARG;
+    for (int i = 0; i < m; i++) if (triples[3 * i] < 0 || triples[3 * i + 1] < 0 || triples[3 * i + 1] > triples[3 * i] || triples[3 * i + 2] < 0 || triples[3 * i + 2] >= NFA_NP) return CS_ERR_BAD_ARG;
+    if (counters) { counters[0] = r->nfa_counts[0]; counters[1] = r->nfa_counts[1]; }
+    if (m == 0) return CS_OK;
+    const int nfa_nmax = lsd_nfa_bound();
+    cs_scratch tmp(ctx);
+    int *d_t = nullptr; double *d_o = nullptr;
+    CS_TRY(tmp.upload(ctx, &d_t, triples, (size_t)3 * m));
+    CS_TRY(tmp.alloc(ctx, &d_o, (size_t)2 * m));
+    CS_LAUNCH(ctx, "lsd_rg_nfa_probe", lsd_rg_nfa_probe, dim3((m + 255) / 256), dim3(256), 0, d_t, m, r->d_nfa, nfa_nmax ? nfa_nmax : -1, r->w, r->h, r->d_lgt, d_o);
+    CS_TRY(cs_d2h(ctx, out, d_o, (size_t)2 * m));
+    return tmp.drain();
 }

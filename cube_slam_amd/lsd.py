@@ -52,6 +52,15 @@ class line_lbd_detect(Handle):
         check(self.ctx.ptr, lib().cs_lsd_region_stats(self.ctx.ptr, self._l, st), "cs_lsd_region_stats")
         return {"device": bool(st[0]), "grows": st[1], "candidates": st[2], "host_fallback": bool(st[3]), "fetches": st[4]}
 
+    def nfa_probe(self, triples):
+        """(table, direct, finished, deferred) of cs_lsd_nfa_probe: for the (n, k, j) rows of `triples` the double nfa()'s result table yields and the double the
+        direct evaluation yields, and how many rectangles of the last device-stage run the table kernel finished / deferred.  A test entry of the library
+        (lsd.hip), not of the public header: the call is not in the signature table, so every argument is passed as the ctypes object the entry expects."""
+        t = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+        out = np.zeros((len(t), 2), np.float64); cnt = (C.c_long * 2)()
+        check(self.ctx.ptr, lib().cs_lsd_nfa_probe(self.ctx.ptr, self._l, C.c_int(len(t)), ptr(t), ptr(out), cnt), "cs_lsd_nfa_probe")
+        return out[:, 0].copy(), out[:, 1].copy(), cnt[0], cnt[1]
+
     def read(self, frame, with_desc=True):
         n = C.c_int()
         check(self.ctx.ptr, lib().cs_lsd_read(self.ctx.ptr, self._l, frame, None, 0, C.byref(n), None), "cs_lsd_read")

@@ -1,6 +1,7 @@
-"""Loader of libcubeslam_hip.so (the C-ABI in include/cubeslam_hip.h).  No CPU fallback: if the library or a HIP
-device is missing this raises."""
+"""Loader of libcubeslam_hip.so (the C-ABI in include/cubeslam_hip.h and the extension headers include/cubeslam_hip/*.h).  No CPU
+fallback: if the library or a HIP device is missing this raises."""
 import ctypes as C
+import glob
 import os
 import re
 import subprocess
@@ -27,6 +28,18 @@ def build(force=False):
 
 
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "cubeslam_hip.h")  # the contract: CS_VERSION and every signature are read from it
+EXTENSION_DIR = os.path.join(os.path.dirname(_HERE), "include", "cubeslam_hip")  # extension headers: more functions beside an unchanged main header, each with a version of its own
+
+
+def extension_headers():
+    """The extension headers of this tree, by path."""
+    return sorted(glob.glob(os.path.join(EXTENSION_DIR, "*.h")))
+
+
+def extension_version(text):
+    """(NAME, value) of the `#define CS_<NAME>_VERSION n` an extension header carries: the library answers cs_<name>_version()."""
+    m = re.search(r"#define\s+CS_(\w+)_VERSION\s+(\d+)", text)
+    return (m.group(1).lower(), int(m.group(2))) if m else None
 
 
 def header_version(text=None):
@@ -80,13 +93,19 @@ def lib():
             raise CubeSlamError("libcubeslam_hip.so is not built (run python -c 'import __graft_entry__ as g; g.build()')")
         L = C.CDLL(LIB_PATH)
         text = open(HEADER).read()
-        for fn, (restype, argtypes) in signatures(text).items():
-            if hasattr(L, fn):  # a declared function the library does not export is test_cabi's finding
-                f = getattr(L, fn)
-                f.restype, f.argtypes = restype, argtypes
+        extensions = [open(h).read() for h in extension_headers()]
+        for header in [text] + extensions:  # one table: the main header's signatures and every extension header's
+            for fn, (restype, argtypes) in signatures(header).items():
+                if hasattr(L, fn):  # a declared function the library does not export is test_cabi's finding
+                    f = getattr(L, fn)
+                    f.restype, f.argtypes = restype, argtypes
         want = header_version(text)
         if L.cs_version() != want:  # an ABI-changing header with a stale library (or the reverse) must not get as far as a call
             raise CubeSlamError("libcubeslam_hip.so is version %d, include/cubeslam_hip.h is %s: rebuild" % (L.cs_version(), want))
+        for header in extensions:
+            name, value = extension_version(header) or (None, None)
+            if name and (not hasattr(L, "cs_%s_version" % name) or getattr(L, "cs_%s_version" % name)() != value):
+                raise CubeSlamError("libcubeslam_hip.so does not hold version %d of include/cubeslam_hip/%s.h: rebuild" % (value, name))
         _LIB = L
     return _LIB
 

@@ -27,6 +27,7 @@
 #include "cv_math.h"
 #include "frame_math.h"
 #include "glibc_logf.h"
+#include "stereo_search_math.h"
 
 #include <algorithm>
 #include <climits>
@@ -109,17 +110,21 @@ struct QueryS { float x, y, r; int minLevel, maxLevel, valid, pair; };
 // The queries of a SearchByProjection (ORBmatcher.cc:1397-1430).  Query i belongs to pair p with qfirst[p] <= i < qfirst[p + 1] and is projected with the pose
 // T_all + 12 * p; qfirst == NULL: one pair, no bisection.  Its level is octave[i] or, with octave == NULL, the key point record's okeys[i].octave (:1424); a level outside the
 // scale table raises *err and leaves the query invalid.
-__global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const int *qfirst, const float *world_pos, const uint8_t *valid, const int *octave, const cs_keypoint *okeys,
-                                                    const float *T_all, float fx, float fy, float cx, float cy, const float *scale_factors, int n_levels, float th, FrameP F, QueryS *q, int *err) {
+// STEREO (bMono == false, :1393-1394, :1433-1438, :1461): the level window follows the pair's direction (S.dir[pair], or S.dir0 with S.dir == NULL) and the query's predicted
+// right coordinate ur = u - bf * invzc goes to S.ur[i], a separate array: QueryS keeps its layout.  The false instantiation is the monocular kernel, statement by statement.
+struct StereoQ { const int *dir; int dir0; float bf; float *ur; };
+template <bool STEREO> __global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const int *qfirst, const float *world_pos, const uint8_t *valid, const int *octave, const cs_keypoint *okeys,
+                                                    const float *T_all, float fx, float fy, float cx, float cy, const float *scale_factors, int n_levels, float th, FrameP F, QueryS *q, int *err, StereoQ S) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nq) return;
     int lo = 0, hi = qfirst ? n_pairs : 1; // qfirst[lo] <= i < qfirst[hi]
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (qfirst[mid] <= i) lo = mid; else hi = mid; }
     const float *T = T_all + 12 * lo;
     QueryS Q{0, 0, 0, 0, 0, 0, lo};
+    float ur = 0.0f;
     if (valid[i]) {
         const int o = octave ? octave[i] : okeys[i].octave;
-        if (o < 0 || o >= n_levels) { *err = 1; q[i] = Q; return; }
+        if (o < 0 || o >= n_levels) { *err = 1; q[i] = Q; if (STEREO) S.ur[i] = ur; return; }
         float x3Dc[3];
         for (int r = 0; r < 3; r++) {
             double sacc = 0;
@@ -131,10 +136,13 @@ __global__ void __launch_bounds__(256) match_project(int nq, int n_pairs, const 
         if (!(invzc < 0)) {
             float u = fx * xc * invzc + cx;
             float v = fy * yc * invzc + cy;
-            if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) { Q.x = u; Q.y = v; Q.r = th * scale_factors[o]; Q.minLevel = o - 1; Q.maxLevel = o + 1; Q.valid = 1; }
+            if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) { Q.x = u; Q.y = v; Q.r = th * scale_factors[o]; Q.minLevel = o - 1; Q.maxLevel = o + 1; Q.valid = 1;
+                if (STEREO) { stereo_search_levels(S.dir ? S.dir[lo] : S.dir0, o, Q.minLevel, Q.maxLevel); ur = u - S.bf * invzc; }
+            }
         }
     }
     q[i] = Q;
+    if (STEREO) S.ur[i] = ur;
 }
 
 // The preamble of the searches that project map points through a Sim3 or a relocalisation pose, with the reference's float arithmetic statement by statement (a cv::Mat
@@ -245,9 +253,13 @@ __device__ __forceinline__ int hamming256(const unsigned long long *a, unsigned 
 // descriptors), not by bytes: 3.1 ms per window of 10^6 queries with 64 lanes per query whether the walk read 28-byte key point records through an index (654 MB) or
 // cell-ordered 16-byte records (521 MB).  (Sixteen-wave workgroups were measured too: the same alone, 13 ms beside the region walks -- they wait for a CU with four free
 // slots per SIMD.)
+// STEREO: the mvuRight test of :1459-1465 / :104-109 is part of `passes`, ahead of the Hamming distance: a train key point with S.u_right[kb + id] > 0 whose distance to
+// the query's predicted right coordinate S.ur_q[qi * S.ur_stride] exceeds the window radius is no candidate.  Both walks evaluate the same predicate, so the lists are the
+// reference's lists after its test, in its order, and match_resolve runs on them as it is.  The false instantiation is the monocular kernel.
 constexpr int MC_G = 16, MC_Q = 256 / MC_G;
-__global__ void __launch_bounds__(256) match_candidates(FrameP F, const unsigned long long *desc, const int *kfirst, const int *cell_start_all, const CellRec *cell_recs_all, int nq,
-                                                        const QueryS *q, const unsigned long long *qdesc, unsigned long long *cursor, long cap, long *cstart, int *ccount, int2 *cands) {
+struct StereoC { const float *u_right, *ur_q; int ur_stride; };
+template <bool STEREO> __global__ void __launch_bounds__(256) match_candidates(FrameP F, const unsigned long long *desc, const int *kfirst, const int *cell_start_all, const CellRec *cell_recs_all, int nq,
+                                                        const QueryS *q, const unsigned long long *qdesc, unsigned long long *cursor, long cap, long *cstart, int *ccount, int2 *cands, StereoC S) {
     __shared__ int s_tot[MC_Q];
     __shared__ unsigned long long s_base;
     const int grp = threadIdx.x / MC_G, qi = blockIdx.x * MC_Q + grp, lane = threadIdx.x % MC_G;
@@ -269,11 +281,16 @@ __global__ void __launch_bounds__(256) match_candidates(FrameP F, const unsigned
     const int ny = nMaxCellY - nMinCellY + 1, ncell = window ? (nMaxCellX - nMinCellX + 1) * ny : 0;
     unsigned long long d0 = 0, d1 = 0, d2 = 0, d3 = 0;
     if (window && qdesc) { d0 = qdesc[(size_t)qi * 4]; d1 = qdesc[(size_t)qi * 4 + 1]; d2 = qdesc[(size_t)qi * 4 + 2]; d3 = qdesc[(size_t)qi * 4 + 3]; }
+    float ur_q = 0.0f;
+    const float *tur = nullptr;
+    if (STEREO) { if (window) ur_q = S.ur_q[(size_t)qi * S.ur_stride]; tur = S.u_right + kb; }
     auto passes = [&](const CellRec &kp) {
         bool ok = true;
         if (bCheckLevels) { if (kp.octave < Q.minLevel) ok = false; if (Q.maxLevel >= 0 && kp.octave > Q.maxLevel) ok = false; }
         const float distx = kp.x - x, disty = kp.y - y;
-        return ok && fabsf(distx) < r && fabsf(disty) < r;
+        ok = ok && fabsf(distx) < r && fabsf(disty) < r;
+        if (STEREO) { if (ok && stereo_search_drops(ur_q, tur[kp.id], r)) ok = false; } // (read only for a key point inside the window)
+        return ok;
     };
     // (the groups of a wave walk in lockstep: the trip count is the longest window of the four; a group past its window does nothing)
     int ncell_w = ncell;
@@ -725,6 +742,7 @@ struct cs_matcher {
     std::vector<cs_keypoint> keys; // host copy of mvKeysUn (what set_frame_from_orb hands back; the vbPrevMatched update of SearchForInitialization)
     // the frame: per key point (max_kp) and its grid
     cs_keypoint *d_keys = nullptr; unsigned long long *d_desc = nullptr; float *d_ur = nullptr; uint8_t *d_tb = nullptr;
+    float *d_uright = nullptr; bool has_uright = false; // the frame's mvuRight for the stereo searches (cs_matcher_set_u_right); every cs_matcher_set_frame* detaches it
     int *d_cell_start = nullptr, *d_cell_items = nullptr, *d_kp_cell = nullptr, *d_tm = nullptr /* max_kp + 1: train_match, nmatches behind its N entries */; CellRec *d_cell_recs = nullptr;
     // the queries: per query (max_q)
     QueryS *d_q = nullptr; unsigned long long *d_qdesc = nullptr; long *d_cstart = nullptr;
@@ -739,10 +757,15 @@ struct cs_matcher {
 };
 
 // the window enumeration of nq queries in m->d_q against the frame set with cs_matcher_set_frame: cursor reset + one launch, nothing waits
-static int mt_candidates(cs_ctx *ctx, cs_matcher *m, int nq, bool with_desc) {
+// ur_q != NULL: the stereo form -- the queries' predicted right coordinates (ur_q[q * ur_stride]) against the mvuRight attached with cs_matcher_set_u_right
+static int mt_candidates(cs_ctx *ctx, cs_matcher *m, int nq, bool with_desc, const float *ur_q = nullptr, int ur_stride = 0) {
     CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 16, ctx->stream));
-    CS_LAUNCH(ctx, "match_candidates", match_candidates, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, m->F, m->d_desc, (const int *)nullptr, m->d_cell_start, m->d_cell_recs, nq, m->d_q,
-              with_desc ? m->d_qdesc : (const unsigned long long *)nullptr, m->d_cursor, m->max_cand, m->d_cstart, m->d_ccount, m->d_cands);
+    if (ur_q)
+        CS_LAUNCH(ctx, "match_candidates", match_candidates<true>, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, m->F, m->d_desc, (const int *)nullptr, m->d_cell_start, m->d_cell_recs, nq, m->d_q,
+                  with_desc ? m->d_qdesc : (const unsigned long long *)nullptr, m->d_cursor, m->max_cand, m->d_cstart, m->d_ccount, m->d_cands, StereoC{m->d_uright, ur_q, ur_stride});
+    else
+        CS_LAUNCH(ctx, "match_candidates", match_candidates<false>, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, m->F, m->d_desc, (const int *)nullptr, m->d_cell_start, m->d_cell_recs, nq, m->d_q,
+                  with_desc ? m->d_qdesc : (const unsigned long long *)nullptr, m->d_cursor, m->max_cand, m->d_cstart, m->d_ccount, m->d_cands, StereoC{nullptr, nullptr, 0});
     m->last_q = nq;
     return CS_OK;
 }
@@ -765,7 +788,7 @@ static int mt_finish(cs_ctx *ctx, cs_matcher *m, const int *d_res, int n_res, in
 static int mt_alloc(cs_ctx *ctx, cs_matcher *m) {
     const size_t nk = (size_t)m->max_kp, nq = (size_t)m->max_q;
     cs_owner &o = m->own;
-    CS_TRY(o.alloc(ctx, &m->d_keys, nk)); CS_TRY(o.alloc(ctx, &m->d_desc, nk * 4)); CS_TRY(o.alloc(ctx, &m->d_ur, nk)); CS_TRY(o.alloc(ctx, &m->d_tb, nk));
+    CS_TRY(o.alloc(ctx, &m->d_keys, nk)); CS_TRY(o.alloc(ctx, &m->d_desc, nk * 4)); CS_TRY(o.alloc(ctx, &m->d_ur, nk)); CS_TRY(o.alloc(ctx, &m->d_tb, nk)); CS_TRY(o.alloc(ctx, &m->d_uright, nk));
     CS_TRY(o.alloc(ctx, &m->d_cell_start, (size_t)NCELL + 1)); CS_TRY(o.alloc(ctx, &m->d_cell_items, nk)); CS_TRY(o.alloc(ctx, &m->d_kp_cell, nk)); CS_TRY(o.alloc(ctx, &m->d_tm, nk + 1));
     CS_TRY(o.alloc(ctx, &m->d_cell_recs, nk));
     CS_TRY(o.alloc(ctx, &m->d_q, nq)); CS_TRY(o.alloc(ctx, &m->d_qdesc, nq * 4)); CS_TRY(o.alloc(ctx, &m->d_cstart, nq));
@@ -783,6 +806,7 @@ struct cs_match_stream {
     cs_owner own;
     cs_dbuf<cs_keypoint> keys; cs_dbuf<int> cell_start, cell_items, kp_cell, kfirst, qfirst, ccount, qrec, tm, nm; cs_dbuf<CellRec> cell_recs; cs_dbuf<long> cstart; cs_dbuf<QueryS> q; cs_dbuf<int2> cands;
     cs_dbuf<float> wp, T; cs_dbuf<uint8_t> valid, blocks; cs_dbuf<unsigned long long> qdesc;
+    cs_dbuf<float> ur, qur; cs_dbuf<int> dir; // the stereo form: mvuRight over the window's key points, the queries' predicted right coordinates, a direction per pair
     float *d_sf = nullptr; unsigned long long *d_cursor = nullptr;
     std::vector<int> h_tm;
     long last_q = 0, last_c = 0;
@@ -827,7 +851,7 @@ int cs_matcher_set_frame(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *keysUn, 
                          float maxY) {
     if (!ctx || !m || !keysUn || !desc || N < 0 || N > m->max_kp || !(maxX > minX) || !(maxY > minY)) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    m->F = make_frame(N, minX, maxX, minY, maxY);
+    m->F = make_frame(N, minX, maxX, minY, maxY); m->has_uright = false;
     m->keys.assign(keysUn, keysUn + N);
     CS_TRY(cs_h2d(ctx, m->d_keys, keysUn, (size_t)N));
     CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_desc, desc, (size_t)N * 32));
@@ -853,7 +877,7 @@ int cs_matcher_set_frame_from_orb(cs_ctx *ctx, cs_matcher *m, const cs_orb *orb,
     CS_TRY(cs_orb_device_frame(orb, frame, &d_k, &d_d, &N));
     if (N > m->max_kp) return CS_ERR_CAPACITY;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    m->F = make_frame(N, minX, maxX, minY, maxY);
+    m->F = make_frame(N, minX, maxX, minY, maxY); m->has_uright = false;
     // UndistortKeyPoints + the descriptors, device to device; AssignFeaturesToGrid on the undistorted keypoints
     if (N > 0) {
         CS_LAUNCH(ctx, "match_undistort", match_undistort, dim3((N + 255) / 256), dim3(256), 0, N, d_k, make_undp(K4, dist5), m->d_keys);
@@ -892,9 +916,12 @@ int cs_matcher_features_in_area(cs_ctx *ctx, cs_matcher *m, float x, float y, fl
     return CS_OK;
 }
 
-int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const float *world_pos, const uint8_t *valid, const uint8_t *blocks,
-                                 const uint8_t *mp_desc, const int *last_octave, const float *last_angle, const float *Tcw, float fx, float fy, float cx,
-                                 float cy, const float *scale_factors, int n_levels, float th, int check_orientation, const uint8_t *train_blocked, int *train_match, int *nmatches) {
+} // extern "C"
+// cs_match_by_projection_frame and its stereo form (stereo: direction `dir`, mbf `bf`, the attached mvuRight)
+static int mt_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const float *world_pos, const uint8_t *valid, const uint8_t *blocks,
+                                  const uint8_t *mp_desc, const int *last_octave, const float *last_angle, const float *Tcw, float fx, float fy, float cx,
+                                  float cy, const float *scale_factors, int n_levels, float th, int check_orientation, const uint8_t *train_blocked, int *train_match, int *nmatches,
+                                  bool stereo, int dir, float bf) {
     if (!ctx || !m || n_last < 0 || n_last > m->max_q || !world_pos || !valid || !blocks || !mp_desc || !last_octave || !last_angle || !Tcw ||
         !scale_factors || n_levels < 1 || n_levels > 32 || !train_match || !nmatches)
         return CS_ERR_BAD_ARG;
@@ -913,9 +940,15 @@ int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const f
     if (check_orientation) CS_TRY(cs_h2d(ctx, m->d_ang, last_angle, (size_t)n_last));
     if (train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N)); // map point from before the call / KeysStatic[i2] == false, :1451-1457
     // (the levels were checked above, before anything was queued; the kernel's own check only keeps its read of the scale table in range)
-    CS_LAUNCH(ctx, "match_project", match_project, dim3((n_last + 255) / 256), dim3(256), 0, n_last, 1, (const int *)nullptr, m->d_wp, m->d_valid, m->d_level, (const cs_keypoint *)nullptr,
-              m->d_T, fx, fy, cx, cy, m->d_sf, n_levels, th, m->F, m->d_q, reinterpret_cast<int *>(m->d_cursor + 1));
-    CS_TRY(mt_candidates(ctx, m, n_last, true));
+    if (stereo) {
+        CS_LAUNCH(ctx, "match_project", match_project<true>, dim3((n_last + 255) / 256), dim3(256), 0, n_last, 1, (const int *)nullptr, m->d_wp, m->d_valid, m->d_level, (const cs_keypoint *)nullptr,
+                  m->d_T, fx, fy, cx, cy, m->d_sf, n_levels, th, m->F, m->d_q, reinterpret_cast<int *>(m->d_cursor + 1), StereoQ{nullptr, dir, bf, m->d_qur});
+        CS_TRY(mt_candidates(ctx, m, n_last, true, m->d_qur, 1));
+    } else {
+        CS_LAUNCH(ctx, "match_project", match_project<false>, dim3((n_last + 255) / 256), dim3(256), 0, n_last, 1, (const int *)nullptr, m->d_wp, m->d_valid, m->d_level, (const cs_keypoint *)nullptr,
+                  m->d_T, fx, fy, cx, cy, m->d_sf, n_levels, th, m->F, m->d_q, reinterpret_cast<int *>(m->d_cursor + 1), StereoQ{nullptr, 0, 0.0f, nullptr});
+        CS_TRY(mt_candidates(ctx, m, n_last, true));
+    }
     // the greedy pass (:1397-1494) and the rotation cut (:1496-1517), on the device
     ResolveP P{};
     P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_last; P.n_train = N; P.tkeys = m->d_keys; P.qangle = m->d_ang; P.blocks = m->d_blocks;
@@ -923,7 +956,13 @@ int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const f
     CS_TRY(mt_resolve<RV_PROJ>(ctx, P, 1, N));
     return mt_finish(ctx, m, m->d_tm, N, train_match, nmatches);
 }
-
+extern "C" {
+int cs_match_by_projection_frame(cs_ctx *ctx, cs_matcher *m, int n_last, const float *world_pos, const uint8_t *valid, const uint8_t *blocks,
+                                 const uint8_t *mp_desc, const int *last_octave, const float *last_angle, const float *Tcw, float fx, float fy, float cx,
+                                 float cy, const float *scale_factors, int n_levels, float th, int check_orientation, const uint8_t *train_blocked, int *train_match, int *nmatches) {
+    return mt_by_projection_frame(ctx, m, n_last, world_pos, valid, blocks, mp_desc, last_octave, last_angle, Tcw, fx, fy, cx, cy, scale_factors, n_levels, th, check_orientation, train_blocked,
+                                  train_match, nmatches, false, SS_NEITHER, 0.0f);
+}
 
 // ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1373-1522) for the pairs (f0 + p, f0 + p + 1), p < n_pairs, of the frames `orb` holds in HBM, with
 // Frame::UndistortKeyPoints + AssignFeaturesToGrid (Frame.cc:303-318, 546-576) of every current frame: see include/cubeslam_hip.h.
@@ -943,9 +982,13 @@ int cs_match_stream_last_counts(const cs_match_stream *m, long *queries, long *c
     *queries = m->last_q; *candidates = m->last_c;
     return CS_OK;
 }
-int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb *orb, int f0, int n_pairs, const float *K4, const float *dist5, float minX, float maxX, float minY, float maxY,
-                                  int n_queries, int n_train, const float *world_pos, const uint8_t *valid, const uint8_t *blocks, const uint8_t *mp_desc, const float *Tcw, float fx, float fy, float cx, float cy,
-                                  const float *scale_factors, int n_levels, float th, int check_orientation, int *train_match, int *nmatches) {
+} // extern "C"
+// cs_match_by_projection_stream and its stereo form.  SQ != NULL: the stereo form -- SQ->dir holds a direction per pair (host), SQ->bf = mbf, u_right the packed mvuRight of the current
+// frames (n_train values, host or device)
+struct StreamStereo { const int *dir; float bf; const float *u_right; int on_device; };
+static int mt_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb *orb, int f0, int n_pairs, const float *K4, const float *dist5, float minX, float maxX, float minY, float maxY,
+                                   int n_queries, int n_train, const float *world_pos, const uint8_t *valid, const uint8_t *blocks, const uint8_t *mp_desc, const float *Tcw, float fx, float fy, float cx, float cy,
+                                   const float *scale_factors, int n_levels, float th, int check_orientation, int *train_match, int *nmatches, const StreamStereo *SQ) {
     if (!ctx || !m || !orb || n_pairs < 1 || f0 < 0 || !K4 || !(maxX > minX) || !(maxY > minY) || !world_pos || !valid || !blocks || !Tcw || !scale_factors || n_levels < 1 || n_levels > 32 || !train_match || !nmatches)
         return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
@@ -993,12 +1036,24 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
     int *d_err = reinterpret_cast<int *>(m->d_cursor + 1);
     CS_HIP(ctx, hipMemsetAsync(m->d_cursor, 0, 16, ctx->stream));
     CS_LAUNCH(ctx, "match_grid", match_grid, dim3(n_pairs), dim3(1024), 0, F, m->keys.p, m->kfirst.p, m->cell_start.p, m->cell_items.p, m->kp_cell.p, m->cell_recs.p);
-    CS_LAUNCH(ctx, "match_project", match_project, dim3((nq + 255) / 256), dim3(256), 0, nq, n_pairs, m->qfirst.p, m->wp.p, m->valid.p, (const int *)nullptr, d_k0 /* query j = raw key point j of frame f0 on */, m->T.p, fx, fy, cx, cy, m->d_sf, n_levels, th, F, m->q.p, d_err);
+    if (SQ) { // train key point id of pair p is entry kfirst[p] + id of the window's key point list: mvuRight lies behind the first frame's (unused) entries
+        CS_TRY(m->ur.grow(ctx, m->own, (size_t)nk_all)); CS_TRY(m->qur.grow(ctx, m->own, (size_t)nq)); CS_TRY(m->dir.grow(ctx, m->own, (size_t)n_pairs));
+        CS_HIP(ctx, hipMemcpyAsync(m->ur.p + first[1], SQ->u_right, sizeof(float) * (size_t)nk, SQ->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+        CS_TRY(cs_h2d(ctx, m->dir.p, SQ->dir, (size_t)n_pairs));
+        CS_LAUNCH(ctx, "match_project", match_project<true>, dim3((nq + 255) / 256), dim3(256), 0, nq, n_pairs, m->qfirst.p, m->wp.p, m->valid.p, (const int *)nullptr, d_k0, m->T.p, fx, fy, cx, cy, m->d_sf, n_levels, th, F, m->q.p, d_err,
+                  StereoQ{m->dir.p, 0, SQ->bf, m->qur.p});
+    } else
+        CS_LAUNCH(ctx, "match_project", match_project<false>, dim3((nq + 255) / 256), dim3(256), 0, nq, n_pairs, m->qfirst.p, m->wp.p, m->valid.p, (const int *)nullptr, d_k0 /* query j = raw key point j of frame f0 on */, m->T.p, fx, fy, cx, cy, m->d_sf, n_levels, th, F, m->q.p, d_err,
+                  StereoQ{nullptr, 0, 0.0f, nullptr});
     // every pair's window enumeration (one launch) and its greedy pass + rotation cut (:1397-1517; one wave per pair): nothing of a candidate leaves the device.  The arena's
     // size is last call's need; a window that needs more says so through the cursor and the two launches run again on a larger one.
     for (int attempt = 0;; attempt++) {
-        CS_LAUNCH(ctx, "match_candidates", match_candidates, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, F, d_d0, m->kfirst.p, m->cell_start.p, m->cell_recs.p, nq, m->q.p, d_qdesc, m->d_cursor, (long)m->cands.cap,
-                  m->cstart.p, m->ccount.p, m->cands.p);
+        if (SQ)
+            CS_LAUNCH(ctx, "match_candidates", match_candidates<true>, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, F, d_d0, m->kfirst.p, m->cell_start.p, m->cell_recs.p, nq, m->q.p, d_qdesc, m->d_cursor, (long)m->cands.cap,
+                      m->cstart.p, m->ccount.p, m->cands.p, StereoC{m->ur.p, m->qur.p, 1});
+        else
+            CS_LAUNCH(ctx, "match_candidates", match_candidates<false>, dim3((nq + MC_Q - 1) / MC_Q), dim3(256), 0, F, d_d0, m->kfirst.p, m->cell_start.p, m->cell_recs.p, nq, m->q.p, d_qdesc, m->d_cursor, (long)m->cands.cap,
+                      m->cstart.p, m->ccount.p, m->cands.p, StereoC{nullptr, nullptr, 0});
         ResolveP P{};
         P.cstart = m->cstart.p; P.ccount = m->ccount.p; P.cands = m->cands.p; P.pfirst = m->qfirst.p; P.kfirst = m->kfirst.p; P.tkeys = m->keys.p; P.qkeys = m->keys.p; P.blocks = m->blocks.p;
         P.check_orientation = check_orientation; P.train_match = m->tm.p; P.q_rec = m->qrec.p; P.nmatches = m->nm.p;
@@ -1015,10 +1070,19 @@ int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb 
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
+extern "C" {
+int cs_match_by_projection_stream(cs_ctx *ctx, cs_match_stream *m, const cs_orb *orb, int f0, int n_pairs, const float *K4, const float *dist5, float minX, float maxX, float minY, float maxY,
+                                  int n_queries, int n_train, const float *world_pos, const uint8_t *valid, const uint8_t *blocks, const uint8_t *mp_desc, const float *Tcw, float fx, float fy, float cx, float cy,
+                                  const float *scale_factors, int n_levels, float th, int check_orientation, int *train_match, int *nmatches) {
+    return mt_by_projection_stream(ctx, m, orb, f0, n_pairs, K4, dist5, minX, maxX, minY, maxY, n_queries, n_train, world_pos, valid, blocks, mp_desc, Tcw, fx, fy, cx, cy, scale_factors, n_levels, th,
+                                   check_orientation, train_match, nmatches, nullptr);
+}
 
-int cs_match_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_xy, const float *view_cos, const int *pred_level, const uint8_t *in_view,
-                       const uint8_t *blocks, const uint8_t *mp_desc, const float *scale_factors, int n_levels, float th, float nnratio,
-                       const uint8_t *train_blocked, int *train_match, int *nmatches) {
+} // extern "C"
+// cs_match_local_map and its stereo form (proj_xr != NULL: mTrackProjXR per map point, tested against the attached mvuRight, :104-109)
+static int mt_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_xy, const float *view_cos, const int *pred_level, const uint8_t *in_view,
+                        const uint8_t *blocks, const uint8_t *mp_desc, const float *scale_factors, int n_levels, float th, float nnratio,
+                        const uint8_t *train_blocked, int *train_match, int *nmatches, const float *proj_xr) {
     if (!ctx || !m || n_mp < 0 || n_mp > m->max_q || !proj_xy || !view_cos || !pred_level || !in_view || !blocks || !mp_desc || !scale_factors ||
         !train_match || !nmatches)
         return CS_ERR_BAD_ARG;
@@ -1043,12 +1107,19 @@ int cs_match_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_x
     CS_TRY(cs_h2d(ctx, (uint8_t *)m->d_qdesc, mp_desc, (size_t)n_mp * 32));
     CS_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_mp));
     if (train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, train_blocked, (size_t)N));
-    CS_TRY(mt_candidates(ctx, m, n_mp, true));
+    if (proj_xr) { CS_TRY(cs_h2d(ctx, m->d_qur, proj_xr, (size_t)n_mp)); CS_TRY(mt_candidates(ctx, m, n_mp, true, m->d_qur, 1)); }
+    else CS_TRY(mt_candidates(ctx, m, n_mp, true));
     ResolveP P{}; // :86-140: best / second with their levels, the ratio rule, claims
     P.cstart = m->d_cstart; P.ccount = m->d_ccount; P.cands = m->d_cands; P.n_steps = n_mp; P.n_train = N; P.tkeys = m->d_keys; P.blocks = m->d_blocks;
     P.tblocked = train_blocked ? m->d_tb : nullptr; P.nnratio = nnratio; P.check_orientation = 0; P.train_match = m->d_tm; P.q_rec = m->d_qrec; P.nmatches = m->d_tm + N;
     CS_TRY(mt_resolve<RV_LOCAL>(ctx, P, 1, N));
     return mt_finish(ctx, m, m->d_tm, N, train_match, nmatches);
+}
+extern "C" {
+int cs_match_local_map(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_xy, const float *view_cos, const int *pred_level, const uint8_t *in_view,
+                       const uint8_t *blocks, const uint8_t *mp_desc, const float *scale_factors, int n_levels, float th, float nnratio,
+                       const uint8_t *train_blocked, int *train_match, int *nmatches) {
+    return mt_local_map(ctx, m, n_mp, proj_xy, view_cos, pred_level, in_view, blocks, mp_desc, scale_factors, n_levels, th, nnratio, train_blocked, train_match, nmatches, nullptr);
 }
 
 int cs_match_for_initialization(cs_ctx *ctx, cs_matcher *m, const cs_keypoint *keys1, const uint8_t *desc1, int N1, float *prev, int window_size,
@@ -1173,7 +1244,9 @@ static MapP make_mapp(const float *R, const float *t, const float *Ow, const flo
     return P;
 }
 // uploads the map points, runs the preamble into m's query arrays (points outside the scale table add to *d_nout) and enumerates the windows in m's frame; nothing waits
-template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, int *d_nout, const MapOut &O = MapOut{nullptr, nullptr, nullptr}) {
+// (ur_q: the stereo form of the window enumeration, see mt_candidates)
+template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const MapIn &I, const MapP &P, const float *scale_factors, int *d_nout, const MapOut &O = MapOut{nullptr, nullptr, nullptr},
+                                              const float *ur_q = nullptr, int ur_stride = 0) {
     const int n = I.n, N = m->F.N;
     CS_TRY(cs_h2d(ctx, m->d_wp, I.world_pos, (size_t)n * 3));
     if (MODE == PM_SIM3 || MODE == PM_FUSE || MODE == PM_FRUSTUM) CS_TRY(cs_h2d(ctx, m->d_nrm, I.normal, (size_t)n * 3));
@@ -1184,7 +1257,7 @@ template <int MODE> static int mt_map_queries(cs_ctx *ctx, cs_matcher *m, const 
     CS_TRY(cs_h2d(ctx, m->d_sf, scale_factors, (size_t)P.n_levels));
     if (I.train_blocked) CS_TRY(cs_h2d(ctx, m->d_tb, I.train_blocked, (size_t)N));
     CS_LAUNCH(ctx, "match_project_map", match_project_map<MODE>, dim3((n + 255) / 256), dim3(256), 0, n, m->d_wp, m->d_nrm, m->d_mind, m->d_maxd, m->d_valid, P, m->d_sf, m->F, m->d_q, m->d_level, d_nout, O);
-    return mt_candidates(ctx, m, n, true);
+    return mt_candidates(ctx, m, n, true, ur_q, ur_stride);
 }
 static bool map_in_ok(const cs_matcher *m, const MapIn &I, bool need_normal) {
     return I.n >= 0 && I.n <= m->max_q && (I.n == 0 || (I.world_pos && I.min_distance && I.max_distance && I.skip && I.mp_desc && (!need_normal || I.normal)));
@@ -1259,10 +1332,12 @@ int cs_match_fuse_sim3(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float
     return CS_OK;
 }
 
-int cs_match_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
-                               const float *max_distance, const uint8_t *skip, const uint8_t *blocks, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx, float cy,
-                               float bf, float log_scale_factor, const float *scale_factors, int n_levels, float viewing_cos_limit, float th, float nnratio, int *train_match, int *nmatches,
-                               int *n_to_match, int *n_level_outside, uint8_t *in_view, float *proj, int *pred_level, float *view_cos) {
+} // extern "C"
+// cs_match_local_map_frustum and its stereo form (stereo: the uR the preamble leaves in MapOut.proj is tested against the attached mvuRight, :104-109)
+static int mt_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
+                                const float *max_distance, const uint8_t *skip, const uint8_t *blocks, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx, float cy,
+                                float bf, float log_scale_factor, const float *scale_factors, int n_levels, float viewing_cos_limit, float th, float nnratio, int *train_match, int *nmatches,
+                                int *n_to_match, int *n_level_outside, uint8_t *in_view, float *proj, int *pred_level, float *view_cos, bool stereo) {
     if (!ctx || !m) return CS_ERR_BAD_ARG;
     const MapIn I{n_mp, world_pos, normal, min_distance, max_distance, skip, mp_desc, train_blocked};
     if (!Rcw || !tcw || !Ow || !map_in_ok(m, I, true) || (n_mp && (!blocks || !in_view)) || !scale_factors || n_levels < 1 || n_levels > 32 || !train_match || !nmatches || !n_to_match)
@@ -1276,7 +1351,7 @@ int cs_match_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, con
     CS_TRY(cs_h2d(ctx, m->d_blocks, blocks, (size_t)n_mp));
     // Tracking::SearchLocalPoints :2699-2715 (isInFrustum per point) and the window of ORBmatcher.cc:72-78, written where match_candidates reads it
     CS_TRY(mt_map_queries<PM_FRUSTUM>(ctx, m, I, make_mapp(Rcw, tcw, Ow, nullptr, nullptr, fx, fy, cx, cy, log_scale_factor, th, n_levels, bf, viewing_cos_limit), scale_factors, m->d_nout,
-                                      MapOut{m->d_inview, m->d_proj, m->d_ang}));
+                                      MapOut{m->d_inview, m->d_proj, m->d_ang}, stereo ? m->d_proj + 2 : nullptr, 3));
     // (:2717: without a point in view the reference does not call the search; here no query is valid then and the search leaves train_match at -1 -- the same result without a
     //  second wait for the count)
     ResolveP P{}; // :86-140, as cs_match_local_map
@@ -1293,6 +1368,14 @@ int cs_match_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, con
     *n_to_match = nout[1];
     if (n_level_outside) *n_level_outside = nout[0];
     return CS_OK;
+}
+extern "C" {
+int cs_match_local_map_frustum(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
+                               const float *max_distance, const uint8_t *skip, const uint8_t *blocks, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx, float cy,
+                               float bf, float log_scale_factor, const float *scale_factors, int n_levels, float viewing_cos_limit, float th, float nnratio, int *train_match, int *nmatches,
+                               int *n_to_match, int *n_level_outside, uint8_t *in_view, float *proj, int *pred_level, float *view_cos) {
+    return mt_local_map_frustum(ctx, m, Rcw, tcw, Ow, n_mp, world_pos, normal, min_distance, max_distance, skip, blocks, mp_desc, train_blocked, fx, fy, cx, cy, bf, log_scale_factor, scale_factors,
+                                n_levels, viewing_cos_limit, th, nnratio, train_match, nmatches, n_to_match, n_level_outside, in_view, proj, pred_level, view_cos, false);
 }
 
 int cs_match_fuse_map(cs_ctx *ctx, cs_matcher *m, const float *u_right, const float *inv_level_sigma2, int n_levels, const uint8_t *keys_static, const float *Rcw, const float *tcw, const float *Ow,
@@ -1442,6 +1525,63 @@ int cs_hamming_knn2(cs_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int
     CS_TRY(cs_d2h(ctx, best_dist, dres + nq, (size_t)nq));
     CS_TRY(cs_d2h(ctx, second_dist, dres + 2 * nq, (size_t)nq));
     return sc.drain();
+}
+
+} // extern "C"
+
+// ---- the stereo branches of both SearchByProjection overloads (include/cubeslam_hip/stereo_search.h) ------------------------------------------------------------------
+#include "../../include/cubeslam_hip/stereo_search.h"
+extern "C" {
+
+int cs_stereo_search_version(void) { return CS_STEREO_SEARCH_VERSION; }
+
+int cs_matcher_set_u_right(cs_ctx *ctx, cs_matcher *m, const float *u_right, int n, int on_device) {
+    if (!ctx || !m || !u_right || !(m->F.wInv > 0.0f) || n != m->F.N) return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    if (n > 0) CS_HIP(ctx, hipMemcpyAsync(m->d_uright, u_right, sizeof(float) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    m->has_uright = true;
+    return CS_OK;
+}
+
+int cs_match_by_projection_frame_stereo(cs_ctx *ctx, cs_matcher *m, int n_last, const float *world_pos, const uint8_t *valid, const uint8_t *blocks, const uint8_t *mp_desc, const int *last_octave,
+                                        const float *last_angle, const float *Tcw, float fx, float fy, float cx, float cy, const float *scale_factors, int n_levels, float th, int check_orientation,
+                                        const uint8_t *train_blocked, int *train_match, int *nmatches, const float *Tlw, float bf, float mb, int mono, int *direction) {
+    if (!ctx || !m || !Tcw || (!mono && (!Tlw || !m->has_uright))) return CS_ERR_BAD_ARG;
+    const int dir = stereo_search_direction(Tcw, Tlw, mb, mono);
+    const int r = mt_by_projection_frame(ctx, m, n_last, world_pos, valid, blocks, mp_desc, last_octave, last_angle, Tcw, fx, fy, cx, cy, scale_factors, n_levels, th, check_orientation, train_blocked,
+                                         train_match, nmatches, !mono, dir, bf);
+    if (r == CS_OK && direction) *direction = dir;
+    return r;
+}
+
+int cs_match_by_projection_stream_stereo(cs_ctx *ctx, cs_match_stream *m, const cs_orb *orb, int f0, int n_pairs, const float *K4, const float *dist5, float minX, float maxX, float minY, float maxY,
+                                         int n_queries, int n_train, const float *world_pos, const uint8_t *valid, const uint8_t *blocks, const uint8_t *mp_desc, const float *Tcw, float fx, float fy,
+                                         float cx, float cy, const float *scale_factors, int n_levels, float th, int check_orientation, int *train_match, int *nmatches, const float *Tlw,
+                                         const float *u_right, int u_right_on_device, float bf, float mb, int mono, int *direction) {
+    if (!ctx || !m || n_pairs < 1 || !Tcw || (!mono && (!Tlw || (n_train > 0 && !u_right)))) return CS_ERR_BAD_ARG;
+    std::vector<int> dir((size_t)n_pairs);
+    for (int p = 0; p < n_pairs; p++) dir[p] = stereo_search_direction(Tcw + 12 * p, mono ? nullptr : Tlw + 12 * p, mb, mono);
+    const StreamStereo SQ{dir.data(), bf, u_right, u_right_on_device};
+    const int r = mt_by_projection_stream(ctx, m, orb, f0, n_pairs, K4, dist5, minX, maxX, minY, maxY, n_queries, n_train, world_pos, valid, blocks, mp_desc, Tcw, fx, fy, cx, cy, scale_factors, n_levels, th,
+                                          check_orientation, train_match, nmatches, mono ? nullptr : &SQ);
+    if (r == CS_OK && direction) for (int p = 0; p < n_pairs; p++) direction[p] = dir[p];
+    return r;
+}
+
+int cs_match_local_map_stereo(cs_ctx *ctx, cs_matcher *m, int n_mp, const float *proj_xy, const float *view_cos, const int *pred_level, const uint8_t *in_view, const uint8_t *blocks,
+                              const uint8_t *mp_desc, const float *scale_factors, int n_levels, float th, float nnratio, const uint8_t *train_blocked, int *train_match, int *nmatches,
+                              const float *proj_xr) {
+    if (!ctx || !m || !proj_xr || !m->has_uright) return CS_ERR_BAD_ARG;
+    return mt_local_map(ctx, m, n_mp, proj_xy, view_cos, pred_level, in_view, blocks, mp_desc, scale_factors, n_levels, th, nnratio, train_blocked, train_match, nmatches, proj_xr);
+}
+
+int cs_match_local_map_frustum_stereo(cs_ctx *ctx, cs_matcher *m, const float *Rcw, const float *tcw, const float *Ow, int n_mp, const float *world_pos, const float *normal, const float *min_distance,
+                                      const float *max_distance, const uint8_t *skip, const uint8_t *blocks, const uint8_t *mp_desc, const uint8_t *train_blocked, float fx, float fy, float cx,
+                                      float cy, float bf, float log_scale_factor, const float *scale_factors, int n_levels, float viewing_cos_limit, float th, float nnratio, int *train_match,
+                                      int *nmatches, int *n_to_match, int *n_level_outside, uint8_t *in_view, float *proj, int *pred_level, float *view_cos) {
+    if (!ctx || !m || !m->has_uright) return CS_ERR_BAD_ARG;
+    return mt_local_map_frustum(ctx, m, Rcw, tcw, Ow, n_mp, world_pos, normal, min_distance, max_distance, skip, blocks, mp_desc, train_blocked, fx, fy, cx, cy, bf, log_scale_factor, scale_factors,
+                                n_levels, viewing_cos_limit, th, nnratio, train_match, nmatches, n_to_match, n_level_outside, in_view, proj, pred_level, view_cos, true);
 }
 
 } // extern "C"

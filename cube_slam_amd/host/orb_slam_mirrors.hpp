@@ -8,7 +8,8 @@
 //                               ComputeStereoFromRGBD, UpdatePoseMatrices, UnprojectStereo
 //   cubeslam::ClosePoints       the creation of map points from measured depth in Tracking::StereoInitialization, UpdateLastFrame and CreateNewKeyFrame
 //                               (src/Tracking.cc:783-850, :1207-1274, :2067-2130)
-//   cubeslam::ORBmatcher        ORB_SLAM2::ORBmatcher, the dynamic-object KLT (src/ORBmatcher.cc:1524-1580): SearchByTrackingHarris over two gray frames, with the
+//   cubeslam::ORBmatcher        ORB_SLAM2::ORBmatcher: set_u_right and SearchByProjection(CurrentFrame, LastFrame, th, bMono) with its stereo branch (src/ORBmatcher.cc:1373-1522,
+//                               include/cubeslam_hip/stereo_search.h) over a cs_matcher that holds the current frame; the dynamic-object KLT (src/ORBmatcher.cc:1524-1580): SearchByTrackingHarris over two gray frames, with the
 //                               cv::calcOpticalFlowPyrLK call of :1548 / :1620 as ORBmatcher::calcOpticalFlowPyrLK, and SearchByTracking (:1582-1725) over the current
 //                               frame's mvKeysUn
 //   cubeslam::goodFeaturesToTrack   cv::goodFeaturesToTrack as Tracking::CreateNewKeyFrame calls it (src/Tracking.cc:2292), csrc/gftt_math.h
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "../../include/cubeslam_hip.h"
+#include "../../include/cubeslam_hip/stereo_search.h"
 #include "../csrc/gftt_math.h"
 #include "../csrc/klt_math.h"
 #include "../csrc/rgbd_math.h"
@@ -303,6 +305,58 @@ struct ORBmatcher {
         r.kltmatches = counters[0]; r.goodmatches = counters[1]; r.findfeaturematches = counters[2]; r.uniquematches = counters[3];
         return r;
     }
+
+#ifndef CUBESLAM_HOST_ONLY
+    // ---- the stereo / RGB-D branch of the frame-to-frame search (include/cubeslam_hip/stereo_search.h) over a cs_matcher that holds CurrentFrame
+    // (cs_matcher_set_frame / cs_matcher_set_frame_from_orb)
+    // CurrentFrame.mvuRight for the searches below: one value per key point of the frame the matcher holds, from the host ...
+    static void set_u_right(Context *ctx, cs_matcher *m, const std::vector<float> &mvuRight) {
+        const float none = -1.0f;
+        check(ctx->ctx, cs_matcher_set_u_right(ctx->ctx, m, mvuRight.empty() ? &none : mvuRight.data(), (int)mvuRight.size(), 0), "cs_matcher_set_u_right");
+    }
+    // ... or from the device pointer cs_rgbd_device_frame / cs_stereo_device_pair hands out (no host round trip; valid until the next search returns)
+    static void set_u_right(Context *ctx, cs_matcher *m, const float *d_mvuRight, int n) { check(ctx->ctx, cs_matcher_set_u_right(ctx->ctx, m, d_mvuRight, n, 1), "cs_matcher_set_u_right"); }
+
+    // What SearchByProjection(CurrentFrame, LastFrame, th, bMono) reads of its two frames.  CurrentFrame's key points, descriptors and mvuRight are the matcher's.
+    struct CurrentFrameView {
+        const float *mTcw;                              // 3 x 4 row-major
+        float fx, fy, cx, cy, mbf, mb;
+        const std::vector<float> *mvScaleFactors;
+        const std::vector<uint8_t> *train_blocked;     // nullable: per key point, `mvpMapPoints[i2] with Observations() > 0` from before, or !KeysStatic[i2] (:1451-1457)
+        int N;
+    };
+    struct LastFrameView {
+        const float *mTcw;                              // 3 x 4 row-major
+        const std::vector<cs_keypoint> *mvKeysUn;       // level (mvKeys[i].octave) and angle
+        // per key point i: valid[i] = `pMP && !mvbOutlier[i] && !pMP->is_dynamic`, GetWorldPos (3 floats), `Observations() > 0`, GetDescriptor (32 bytes)
+        const std::vector<uint8_t> *valid, *blocks, *mp_desc;
+        const std::vector<float> *world_pos;
+    };
+    struct ProjectionResult { std::vector<int> train_match; int nmatches = 0, direction = 0; }; // per key point of CurrentFrame the last frame's key point, -1 none; 0 neither, 1 forward, 2 backward
+    // ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th, const bool bMono) (ORBmatcher.cc:1373-1522)
+    static ProjectionResult SearchByProjection(Context *ctx, cs_matcher *m, const CurrentFrameView &CurrentFrame, const LastFrameView &LastFrame, const float th, const bool bMono,
+                                               bool mbCheckOrientation = true) {
+        const int n_last = (int)LastFrame.mvKeysUn->size();
+        if (LastFrame.valid->size() != (size_t)n_last || LastFrame.blocks->size() != (size_t)n_last || LastFrame.mp_desc->size() != 32 * (size_t)n_last ||
+            LastFrame.world_pos->size() != 3 * (size_t)n_last || (CurrentFrame.train_blocked && CurrentFrame.train_blocked->size() != (size_t)CurrentFrame.N))
+            throw std::invalid_argument("SearchByProjection: one entry per key point in every array");
+        std::vector<int> octave((size_t)n_last + 1, 0);
+        std::vector<float> angle((size_t)n_last + 1, 0.0f), wp(*LastFrame.world_pos);
+        std::vector<uint8_t> valid(*LastFrame.valid), blocks(*LastFrame.blocks), desc(*LastFrame.mp_desc);
+        for (int i = 0; i < n_last; i++) { octave[(size_t)i] = (*LastFrame.mvKeysUn)[(size_t)i].octave; angle[(size_t)i] = (*LastFrame.mvKeysUn)[(size_t)i].angle; }
+        wp.resize(wp.size() + 3); valid.resize(valid.size() + 1); blocks.resize(blocks.size() + 1); desc.resize(desc.size() + 32); // (never empty)
+        ProjectionResult r;
+        r.train_match.assign((size_t)CurrentFrame.N + 1, -1);
+        check(ctx->ctx, cs_match_by_projection_frame_stereo(ctx->ctx, m, n_last, wp.data(), valid.data(), blocks.data(), desc.data(), octave.data(), angle.data(), CurrentFrame.mTcw,
+                                                            CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, CurrentFrame.mvScaleFactors->data(),
+                                                            (int)CurrentFrame.mvScaleFactors->size(), th, mbCheckOrientation ? 1 : 0,
+                                                            CurrentFrame.train_blocked ? CurrentFrame.train_blocked->data() : nullptr, r.train_match.data(), &r.nmatches, LastFrame.mTcw,
+                                                            CurrentFrame.mbf, CurrentFrame.mb, bMono ? 1 : 0, &r.direction),
+              "cs_match_by_projection_frame_stereo");
+        r.train_match.resize((size_t)CurrentFrame.N);
+        return r;
+    }
+#endif
 
   private:
     static void run(Context *ctx, const uint8_t *last, const uint8_t *current, int width, int height, long stride, const std::vector<float> &pts, const uint8_t *mask,

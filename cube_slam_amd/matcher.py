@@ -18,11 +18,14 @@ class ORBmatcher(Handle):
         self._m = C.c_void_p()
         check(self.ctx.ptr, lib().cs_matcher_create(self.ctx.ptr, max_keypoints, max_queries, max_candidates, C.byref(self._m)), "cs_matcher_create")
         self.N = 0
+        self.has_u_right = False
+        self.last_direction = 0
 
     def set_frame(self, keysUn, descriptors, bounds):
-        """The frame that is searched (CurrentFrame / F / F2): mvKeysUn, mDescriptors, (mnMinX, mnMaxX, mnMinY, mnMaxY)."""
+        """The frame that is searched (CurrentFrame / F / F2): mvKeysUn, mDescriptors, (mnMinX, mnMaxX, mnMinY, mnMaxY).  Detaches mvuRight (set_u_right)."""
         k = np.ascontiguousarray(keysUn, KEYPOINT_DTYPE); d = np.ascontiguousarray(descriptors, np.uint8)
         self.N = len(k)
+        self.has_u_right = False
         check(self.ctx.ptr, lib().cs_matcher_set_frame(self.ctx.ptr, self._m, ptr(k), ptr(d), self.N, *bounds), "cs_matcher_set_frame")
 
     def set_frame_from_orb(self, orb, frame, K4, dist5=None, bounds=None, width=None, height=None, read_keys=True):
@@ -38,7 +41,18 @@ class ORBmatcher(Handle):
                                                                 *[float(b) for b in bounds], ptr(out) if read_keys else None, C.byref(n)),
               "cs_matcher_set_frame_from_orb")
         self.N = n.value
+        self.has_u_right = False
         return (out[:n.value].copy() if read_keys else None), tuple(float(b) for b in bounds)
+
+    def set_u_right(self, u_right, n=None):
+        """CurrentFrame.mvuRight for the stereo searches of the frame set last (cs_matcher_set_u_right): a float array of N values, or a device address (int, with n) as
+        StereoMatcher.device_pair / RGBDAssociator.device_frame hand out -- then nothing passes through the host.  The next set_frame* detaches it."""
+        if isinstance(u_right, (int, np.integer)):
+            check(self.ctx.ptr, lib().cs_matcher_set_u_right(self.ctx.ptr, self._m, C.cast(C.c_void_p(int(u_right)), C.POINTER(C.c_float)), self.N if n is None else int(n), 1), "cs_matcher_set_u_right")
+        else:
+            ur = np.ascontiguousarray(u_right, np.float32)
+            check(self.ctx.ptr, lib().cs_matcher_set_u_right(self.ctx.ptr, self._m, ptr(ur if len(ur) else np.zeros(1, np.float32)), len(ur), 0), "cs_matcher_set_u_right")
+        self.has_u_right = True
 
     def SearchByTrackingHarris(self, last_gray, current_gray, mvKeysHarris_pt, objmask_img):
         """ORBmatcher::SearchByTrackingHarris (ORBmatcher.cc:1524-1580) for one pair of gray frames on this matcher's context: a dict of kept (indices into the last
@@ -66,7 +80,13 @@ class ORBmatcher(Handle):
                                                               ptr(out), len(out), C.byref(n)), "cs_matcher_features_in_area")
         return out[:n.value].copy()
 
-    def SearchByProjectionFrame(self, world_pos, valid, blocks, mp_desc, last_octave, last_angle, Tcw, fx, fy, cx, cy, scale_factors, th, train_blocked=None):
+    def SearchByProjectionFrame(self, world_pos, valid, blocks, mp_desc, last_octave, last_angle, Tcw, fx, fy, cx, cy, scale_factors, th, train_blocked=None, bMono=True, Tlw=None,
+                                bf=0.0, mb=0.0):
+        """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1373-1522) against the frame set last: (train_match, nmatches).  bMono=False: the
+        stereo branch -- Tlw = LastFrame.mTcw, bf = mbf, mb = the baseline, mvuRight from set_u_right; the direction it took (0 neither, 1 forward, 2 backward) is left in
+        last_direction."""
+        if not bMono:
+            return self.SearchByProjectionFrameStereo(world_pos, valid, blocks, mp_desc, last_octave, last_angle, Tcw, fx, fy, cx, cy, scale_factors, th, Tlw, bf, mb, False, train_blocked)
         wp = np.ascontiguousarray(world_pos, np.float32); va = np.ascontiguousarray(valid, np.uint8); bl = np.ascontiguousarray(blocks, np.uint8)
         md = np.ascontiguousarray(mp_desc, np.uint8); lo = np.ascontiguousarray(last_octave, np.int32); la = np.ascontiguousarray(last_angle, np.float32)
         T = np.ascontiguousarray(Tcw, np.float32).reshape(-1)[:12].copy(); sf = np.ascontiguousarray(scale_factors, np.float32)
@@ -77,7 +97,27 @@ class ORBmatcher(Handle):
                                                                ptr(tm), C.byref(n)), "cs_match_by_projection_frame")
         return tm[:self.N].copy(), n.value
 
-    def SearchByProjectionLocalMap(self, proj_xy, view_cos, pred_level, in_view, blocks, mp_desc, scale_factors, th, train_blocked=None):
+    def SearchByProjectionFrameStereo(self, world_pos, valid, blocks, mp_desc, last_octave, last_angle, Tcw, fx, fy, cx, cy, scale_factors, th, Tlw, bf, mb, bMono=False, train_blocked=None):
+        """cs_match_by_projection_frame_stereo with its own argument order: the search with LastFrame's pose, mbf, the baseline and bMono as the reference passes it (bMono=True needs
+        neither Tlw nor set_u_right and gives the monocular search's bytes).  (train_match, nmatches); the direction is left in last_direction."""
+        mono = int(bool(bMono))
+        wp = np.ascontiguousarray(world_pos, np.float32); va = np.ascontiguousarray(valid, np.uint8); bl = np.ascontiguousarray(blocks, np.uint8)
+        md = np.ascontiguousarray(mp_desc, np.uint8); lo = np.ascontiguousarray(last_octave, np.int32); la = np.ascontiguousarray(last_angle, np.float32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1)[:12].copy(); sf = np.ascontiguousarray(scale_factors, np.float32)
+        Tl = None if Tlw is None else np.ascontiguousarray(Tlw, np.float32).reshape(-1)[:12].copy()
+        tb = None if train_blocked is None else np.ascontiguousarray(train_blocked, np.uint8)
+        tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int(); d = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_by_projection_frame_stereo(self.ctx.ptr, self._m, len(va), ptr(wp), ptr(va), ptr(bl), ptr(md), ptr(lo), ptr(la), ptr(T), fx, fy, cx, cy, ptr(sf),
+                                                                      len(sf), th, int(self.mbCheckOrientation), ptr(tb), ptr(tm), C.byref(n), ptr(Tl), bf, mb, int(mono), C.byref(d)),
+              "cs_match_by_projection_frame_stereo")
+        self.last_direction = d.value
+        return tm[:self.N].copy(), n.value
+
+    def SearchByProjectionLocalMap(self, proj_xy, view_cos, pred_level, in_view, blocks, mp_desc, scale_factors, th, train_blocked=None, proj_xr=None):
+        """ORBmatcher::SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cc:50-142) over the fields isInFrustum left: (train_match, nmatches).  proj_xr (mTrackProjXR per map
+        point): the search applies the mvuRight test of :104-109 against the mvuRight given to set_u_right."""
+        if proj_xr is not None:
+            return self._search_local_map_stereo(proj_xy, view_cos, pred_level, in_view, blocks, mp_desc, scale_factors, th, train_blocked, proj_xr)
         pxy = np.ascontiguousarray(proj_xy, np.float32); vc = np.ascontiguousarray(view_cos, np.float32); pl = np.ascontiguousarray(pred_level, np.int32)
         iv = np.ascontiguousarray(in_view, np.uint8); bl = np.ascontiguousarray(blocks, np.uint8); md = np.ascontiguousarray(mp_desc, np.uint8)
         sf = np.ascontiguousarray(scale_factors, np.float32)
@@ -85,6 +125,17 @@ class ORBmatcher(Handle):
         tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int()
         check(self.ctx.ptr, lib().cs_match_local_map(self.ctx.ptr, self._m, len(iv), ptr(pxy), ptr(vc), ptr(pl), ptr(iv),
                                                      ptr(bl), ptr(md), ptr(sf), len(sf), th, self.mfNNratio, ptr(tb), ptr(tm), C.byref(n)), "cs_match_local_map")
+        return tm[:self.N].copy(), n.value
+
+    def _search_local_map_stereo(self, proj_xy, view_cos, pred_level, in_view, blocks, mp_desc, scale_factors, th, train_blocked, proj_xr):
+        pxy = np.ascontiguousarray(proj_xy, np.float32); vc = np.ascontiguousarray(view_cos, np.float32); pl = np.ascontiguousarray(pred_level, np.int32)
+        iv = np.ascontiguousarray(in_view, np.uint8); bl = np.ascontiguousarray(blocks, np.uint8); md = np.ascontiguousarray(mp_desc, np.uint8)
+        sf = np.ascontiguousarray(scale_factors, np.float32); xr = np.ascontiguousarray(proj_xr, np.float32)
+        assert len(xr) == len(iv)
+        tb = None if train_blocked is None else np.ascontiguousarray(train_blocked, np.uint8)
+        tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int()
+        check(self.ctx.ptr, lib().cs_match_local_map_stereo(self.ctx.ptr, self._m, len(iv), ptr(pxy), ptr(vc), ptr(pl), ptr(iv), ptr(bl), ptr(md), ptr(sf), len(sf), th, self.mfNNratio,
+                                                            ptr(tb), ptr(tm), C.byref(n), ptr(xr if len(xr) else np.zeros(1, np.float32))), "cs_match_local_map_stereo")
         return tm[:self.N].copy(), n.value
 
     def SearchForInitialization(self, keys1Un, desc1, vbPrevMatched, windowSize=100):
@@ -160,9 +211,9 @@ class ORBmatcher(Handle):
         return bi[:len(sk)].copy(), bd[:len(sk)].copy(), n.value, no.value
 
     def SearchLocalPoints(self, Rcw, tcw, Ow, world_pos, normal, min_distance, max_distance, skip, blocks, mp_desc, fx, fy, cx, cy, bf, log_scale_factor, scale_factors, th,
-                          viewing_cos_limit=0.5, train_blocked=None):
+                          viewing_cos_limit=0.5, train_blocked=None, stereo=False):
         """Tracking::SearchLocalPoints (Tracking.cc:2696-2727): Frame::isInFrustum per local map point and ORBmatcher::SearchByProjection(F, vpMapPoints, th) against the current
-        frame given to set_frame, in one call.  Returns a dict: train_match per key point (index of the local point or -1), nmatches, n_to_match, outside (points dropped because
+        frame given to set_frame, in one call.  stereo: with the mvuRight test of ORBmatcher.cc:104-109 against the mvuRight given to set_u_right.  Returns a dict: train_match per key point (index of the local point or -1), nmatches, n_to_match, outside (points dropped because
         their predicted level is outside the scale table) and, per local point, in_view, proj (u, v, uR), pred_level, view_cos."""
         wp, mn, mx, sk, md, nr = self._map_points(world_pos, min_distance, max_distance, skip, mp_desc, normal)
         R, t, O = self._f(Rcw, 9), self._f(tcw, 3), self._f(Ow, 3); sf = np.ascontiguousarray(scale_factors, np.float32); bl = np.ascontiguousarray(blocks, np.uint8)
@@ -170,11 +221,12 @@ class ORBmatcher(Handle):
         n_mp = len(sk); k = max(n_mp, 1)
         tm = np.zeros(max(self.N, 1), np.int32); n = C.c_int(); nt = C.c_int(); no = C.c_int()
         iv = np.zeros(k, np.uint8); pj = np.zeros((k, 3), np.float32); pl = np.full(k, -1, np.int32); vc = np.zeros(k, np.float32)
-        check(self.ctx.ptr, lib().cs_match_local_map_frustum(self.ctx.ptr, self._m, ptr(R), ptr(t), ptr(O), n_mp, ptr(wp), ptr(nr),
+        entry = "cs_match_local_map_frustum_stereo" if stereo else "cs_match_local_map_frustum"
+        check(self.ctx.ptr, getattr(lib(), entry)(self.ctx.ptr, self._m, ptr(R), ptr(t), ptr(O), n_mp, ptr(wp), ptr(nr),
                                                              ptr(mn), ptr(mx), ptr(sk), ptr(bl), ptr(md), ptr(tb), fx, fy, cx, cy, bf,
                                                              log_scale_factor, ptr(sf), len(sf), viewing_cos_limit, th, self.mfNNratio,
                                                              ptr(tm), C.byref(n), C.byref(nt), C.byref(no), ptr(iv), ptr(pj), ptr(pl), ptr(vc)),
-              "cs_match_local_map_frustum")
+              entry)
         return {"train_match": tm[:self.N].copy(), "nmatches": n.value, "n_to_match": nt.value, "outside": no.value, "in_view": iv[:n_mp], "proj": pj[:n_mp], "pred_level": pl[:n_mp],
                 "view_cos": vc[:n_mp]}
 
@@ -256,9 +308,13 @@ class ORBmatcherStream(Handle):
         self._m = C.c_void_p()
         check(ctx.ptr, lib().cs_match_stream_create(C.byref(self._m)), "cs_match_stream_create")
 
-    def search(self, orb, f0, n_pairs, K4, dist5, bounds, world_pos, valid, blocks, Tcw, fx, fy, cx, cy, scale_factors, th, n_train, mp_desc=None):
+    def search(self, orb, f0, n_pairs, K4, dist5, bounds, world_pos, valid, blocks, Tcw, fx, fy, cx, cy, scale_factors, th, n_train, mp_desc=None, bMono=True, Tlw=None, u_right=None,
+               bf=0.0, mb=0.0):
         """world_pos / valid / blocks: concatenated over the last frames f0 .. f0 + n_pairs - 1; Tcw: (n_pairs, 3, 4); n_train: key points of frames f0 + 1 .. f0 + n_pairs.
-        Returns (train_match concatenated over the current frames, nmatches per pair)."""
+        Returns (train_match concatenated over the current frames, nmatches per pair).  bMono=False: the stereo branch (cs_match_by_projection_stream_stereo) -- Tlw (n_pairs, 3, 4)
+        the last frames' poses, u_right = mvuRight packed over the current frames (n_train floats, or a device address), bf, mb; the directions are left in last_direction."""
+        if not bMono:
+            return self.search_stereo(orb, f0, n_pairs, K4, dist5, bounds, world_pos, valid, blocks, Tcw, fx, fy, cx, cy, scale_factors, th, n_train, Tlw, u_right, bf, mb, False, mp_desc)
         k4 = np.ascontiguousarray(K4, np.float32); d5 = None if dist5 is None else np.ascontiguousarray(dist5, np.float32)
         wp = np.ascontiguousarray(world_pos, np.float32); va = np.ascontiguousarray(valid, np.uint8); bl = np.ascontiguousarray(blocks, np.uint8)
         T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(n_pairs, -1)[:, :12]); sf = np.ascontiguousarray(scale_factors, np.float32)
@@ -269,6 +325,29 @@ class ORBmatcherStream(Handle):
                                                                 ptr(bl), ptr(md), ptr(T), fx, fy, cx,
                                                                 cy, ptr(sf), len(sf), th, int(self.mbCheckOrientation), ptr(tm), ptr(nm)),
               "cs_match_by_projection_stream")
+        return tm[:int(n_train)], nm
+
+    def search_stereo(self, orb, f0, n_pairs, K4, dist5, bounds, world_pos, valid, blocks, Tcw, fx, fy, cx, cy, scale_factors, th, n_train, Tlw, u_right, bf, mb, bMono=False, mp_desc=None):
+        """cs_match_by_projection_stream_stereo with its own argument order (bMono=True needs neither Tlw nor u_right and gives the monocular window search's bytes)."""
+        mono = int(bool(bMono))
+        k4 = np.ascontiguousarray(K4, np.float32); d5 = None if dist5 is None else np.ascontiguousarray(dist5, np.float32)
+        wp = np.ascontiguousarray(world_pos, np.float32); va = np.ascontiguousarray(valid, np.uint8); bl = np.ascontiguousarray(blocks, np.uint8)
+        T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(n_pairs, -1)[:, :12]); sf = np.ascontiguousarray(scale_factors, np.float32)
+        Tl = None if Tlw is None else np.ascontiguousarray(np.asarray(Tlw, np.float32).reshape(n_pairs, -1)[:, :12])
+        md = None if mp_desc is None else np.ascontiguousarray(mp_desc, np.uint8)
+        on_device = isinstance(u_right, (int, np.integer))
+        if on_device:
+            ur = C.cast(C.c_void_p(int(u_right)), C.POINTER(C.c_float))
+        else:
+            ur_a = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+            assert ur_a is None or len(ur_a) == int(n_train)
+            ur = ptr(ur_a)
+        tm = np.zeros(max(int(n_train), 1), np.int32); nm = np.zeros(n_pairs, np.int32); dr = np.zeros(n_pairs, np.int32)
+        check(self.ctx.ptr, lib().cs_match_by_projection_stream_stereo(self.ctx.ptr, self._m, orb._e, int(f0), int(n_pairs), ptr(k4), ptr(d5), bounds[0], bounds[1], bounds[2], bounds[3],
+                                                                       len(va), int(n_train), ptr(wp), ptr(va), ptr(bl), ptr(md), ptr(T), fx, fy, cx, cy, ptr(sf), len(sf), th,
+                                                                       int(self.mbCheckOrientation), ptr(tm), ptr(nm), ptr(Tl), ur, int(on_device), bf, mb, int(mono), ptr(dr)),
+              "cs_match_by_projection_stream_stereo")
+        self.last_direction = dr
         return tm[:int(n_train)], nm
 
     def last_counts(self):

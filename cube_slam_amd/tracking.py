@@ -1,10 +1,12 @@
-"""Python host-side mirror of ORB_SLAM2::Tracking::TrackLocalMap (reference orb_object_slam/src/Tracking.cc:1356-1416) and what it calls: UpdateLocalMap (:2730-2738) with
+"""Python host-side mirror of ORB_SLAM2::Tracking::TrackWithMotionModel (reference orb_object_slam/src/Tracking.cc:1276-1354: UpdateLastFrame, the frame-to-frame
+SearchByProjection with its stereo branch and the retry at twice the radius, PoseOptimization, the outlier loop) and of Tracking::TrackLocalMap (:1356-1416) and what it calls: UpdateLocalMap (:2730-2738) with
 UpdateLocalKeyFrames (:2766-2874) and UpdateLocalPoints (:2740-2764), SearchLocalPoints (:2673-2728), Optimizer::PoseOptimization and the statistics loop (:1372-1397).
 
 The map is a table of points and a table of key frames in flat arrays (`Map` below); a frame is a `TrackedFrame`.  What the reference keeps as pointers are indices into those
 tables, -1 for NULL.  The search, the frustum test, the local point list and the pose run on the device; the walk over the key-frame graph, the loop over the frame's own
 points and the statistics over N flags stay on the host."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -20,6 +22,39 @@ def _i32(a):
 
 def _u8(a):
     return np.ascontiguousarray(a, np.uint8)
+
+
+def pose7_to_Tcw(p):
+    """The 3x4 float pose of (t, qx, qy, qz, qw): what Frame::SetPose receives after PoseOptimization (the quaternion's rotation matrix in double, stored as float)."""
+    x, y, z, w = [np.float64(v) for v in p[3:7]]
+    Rm = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                   [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
+    return np.concatenate([Rm, np.asarray(p[:3], np.float64).reshape(3, 1)], axis=1).astype(np.float32)
+
+
+def Tcw_to_pose7(T):
+    """(t, qx, qy, qz, qw) of a 3x4 pose, what PoseOptimization starts from: the rotation's unit quaternion with qw >= 0, every step a double in a fixed order (the C++ mirror,
+    host/tracking.hpp, computes the same bits)."""
+    T = np.asarray(T, np.float64).reshape(-1)[:12].reshape(3, 4)
+    R = [[float(T[i, j]) for j in range(3)] for i in range(3)]
+    tr = R[0][0] + R[1][1] + R[2][2]
+    q = [0.0, 0.0, 0.0, 0.0]
+    if tr > 0:
+        s = math.sqrt(tr + 1.0) * 2
+        q = [(R[2][1] - R[1][2]) / s, (R[0][2] - R[2][0]) / s, (R[1][0] - R[0][1]) / s, 0.25 * s]
+    else:
+        i = 0
+        if R[1][1] > R[i][i]:
+            i = 1
+        if R[2][2] > R[i][i]:
+            i = 2
+        j = (i + 1) % 3; k = (j + 1) % 3
+        s = math.sqrt(R[i][i] - R[j][j] - R[k][k] + 1.0) * 2
+        q[i] = 0.25 * s; q[3] = (R[k][j] - R[j][k]) / s; q[j] = (R[j][i] + R[i][j]) / s; q[k] = (R[k][i] + R[i][k]) / s
+    if q[3] < 0:
+        q = [-v for v in q]
+    n = math.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3])
+    return np.array([float(T[0, 3]), float(T[1, 3]), float(T[2, 3]), q[0] / n, q[1] / n, q[2] / n, q[3] / n], np.float64)
 
 
 def track_local_points(ctx, kf_off, kf_mp, skip):
@@ -55,6 +90,20 @@ class Map:
         if not hasattr(self, "dynamic"):
             self.dynamic = np.zeros(n, np.uint8)
 
+    def append_points(self, world_pos, desc):
+        """`new MapPoint(x3D, mpMap, &mLastFrame, i)` for each row (Tracking.cc:1259): points without observations behind the table's last; returns their indices.  The
+        descriptor is the creating key point's (MapPoint.cc:64); the fields a temporal point never has read (normal, distances) are zero."""
+        k, n = len(world_pos), len(self.bad)
+        grow = lambda a, tail: np.concatenate([a, tail.astype(a.dtype)])
+        self.world_pos = grow(np.asarray(self.world_pos), np.asarray(world_pos, np.float32).reshape(k, 3))
+        self.normal = grow(np.asarray(self.normal), np.zeros((k, 3)))
+        self.desc = grow(np.asarray(self.desc), np.asarray(desc, np.uint8).reshape(k, 32))
+        for name in ("min_distance", "max_distance", "bad", "dynamic", "n_obs", "visible", "found"):
+            setattr(self, name, grow(np.asarray(getattr(self, name)), np.zeros(k)))
+        self.last_frame_seen = grow(self.last_frame_seen, np.full(k, -1))
+        self.obs_off = grow(np.asarray(self.obs_off), np.full(k, np.asarray(self.obs_off)[-1]))
+        return np.arange(n, n + k, dtype=np.int64)
+
 
 class TrackedFrame:
     """mCurrentFrame as TrackLocalMap reads and writes it: mnId, mvKeysUn, mDescriptors, the image bounds, mvpMapPoints (indices, -1), mvbOutlier, the pose (Rcw, tcw, Ow as float32),
@@ -68,7 +117,31 @@ class TrackedFrame:
         self.intr, self.log_scale_factor, self.scale_factors, self.inv_level_sigma2 = intr, log_scale_factor, scale_factors, inv_level_sigma2
         self.pose7 = np.asarray(pose7, np.float64)
         self.u_right = np.full(len(keysUn), -1.0, np.float32) if u_right is None else np.asarray(u_right, np.float32)
+        self.has_u_right = u_right is not None  # a stereo / RGB-D frame: the searches apply the mvuRight tests
+        self.u_right_device = None              # a device address of the same mvuRight (RGBDAssociator.device_frame, StereoMatcher.device_pair): set_u_right then takes it from there
         self.keys_static = keys_static
+
+    def SetPose(self, Tcw):
+        """Frame::SetPose / UpdatePoseMatrices (Frame.cc:320-344) for a 3x4 float pose: mRcw, mtcw, mOw = -mRcw.t() * mtcw (one gemm per row: double accumulation, one rounding)."""
+        T = np.asarray(Tcw, np.float32).reshape(-1)[:12].reshape(3, 4)
+        self.Rcw, self.tcw = T[:, :3].copy(), T[:, 3].copy()
+        self.Ow = np.array([np.float32(-sum(np.float64(T[k, r]) * np.float64(T[k, 3]) for k in range(3))) for r in range(3)], np.float32)
+
+    @property
+    def Tcw(self):
+        return np.concatenate([np.asarray(self.Rcw, np.float32).reshape(3, 3), np.asarray(self.tcw, np.float32).reshape(3, 1)], axis=1)
+
+
+class LastFrame:
+    """mLastFrame as TrackWithMotionModel reads it: mvKeysUn (level and angle), mDescriptors, mvpMapPoints (indices, -1), mvbOutlier, mTcw (3x4 float32), mvDepth, and whether it
+    is the reference key frame's own frame (UpdateLastFrame then creates nothing, Tracking.cc:1215).  rgbd: an RGBDAssociator that still holds this frame alone on the device."""
+
+    def __init__(self, keysUn, desc, mvpMapPoints, Tcw, mvDepth=None, mvbOutlier=None, is_keyframe=False, rgbd=None):
+        self.keysUn, self.desc, self.mvpMapPoints = keysUn, np.asarray(desc, np.uint8), np.array(mvpMapPoints, np.int64)
+        self.Tcw = np.asarray(Tcw, np.float32).reshape(-1)[:12].reshape(3, 4)
+        self.mvDepth = mvDepth
+        self.mvbOutlier = np.zeros(len(keysUn), np.uint8) if mvbOutlier is None else np.asarray(mvbOutlier, np.uint8)
+        self.is_keyframe, self.rgbd = is_keyframe, rgbd
 
 
 class Tracking:
@@ -132,9 +205,12 @@ class Tracking:
         if F.keys_static is not None:
             tb |= (np.asarray(F.keys_static) == 0).astype(np.uint8)  # :101
         self.matcher.set_frame(F.keysUn, F.desc, F.bounds)
+        stereo = self.mSensor != self.MONOCULAR and getattr(F, "has_u_right", False)  # ORBmatcher.cc:104-109: a frame with right coordinates tests them
+        if stereo:
+            self.matcher.set_u_right(F.u_right if F.u_right_device is None else int(F.u_right_device), n=len(F.keysUn))
         fx, fy, cx, cy, bf = F.intr
         r = self.matcher.SearchLocalPoints(F.Rcw, F.tcw, F.Ow, m.world_pos[lp], m.normal[lp], m.min_distance[lp], m.max_distance[lp], skip, m.n_obs[lp] > 0, m.desc[lp], fx, fy, cx, cy, bf,
-                                           F.log_scale_factor, F.scale_factors, float(th), 0.5, tb)
+                                           F.log_scale_factor, F.scale_factors, float(th), 0.5, tb, **({"stereo": True} if stereo else {}))
         np.add.at(m.visible, lp[r["in_view"] != 0], 1)  # :2712
         got = r["train_match"] >= 0
         F.mvpMapPoints[got] = lp[r["train_match"][got]]  # :136
@@ -169,6 +245,74 @@ class Tracking:
         if F.mnId < self.mnLastRelocFrameId + self.mMaxFrames and self.mnMatchesInliers < 50:  # :1402
             return False
         return self.mnMatchesInliers >= (20 if self.whether_detect_object else 30)  # :1405-1415
+
+    def TrackWithMotionModel(self, F, last, m, predicted_pose, K4=None, mThDepth=0.0):
+        """Tracking::TrackWithMotionModel (Tracking.cc:1276-1354).  F: the current TrackedFrame; last: the LastFrame; m: the Map; predicted_pose = mVelocity * mLastFrame.mTcw
+        (3x4) -- the velocity model stays the caller's, as does the SearchByTracking* step of :1306-1312 (cube_slam_amd.klt).  K4 / mThDepth: what UpdateLastFrame's close-point rule
+        reads; the "visual odometry" points it creates are appended to the Map (Map.append_points) and to self.mlpTemporalPoints (UpdateLastFrame keeps that list).  Leaves nmatches, nmatchesMap (and mbVO under
+        mbOnlyTracking) on self, the matches and the optimised pose on F; returns what the reference returns."""
+        # :1282 UpdateLastFrame
+        mp, ids, x3D = self.UpdateLastFrame(last.mvDepth, last.keysUn, last.mvpMapPoints, m.n_obs, last.Tcw, K4, mThDepth, next_point_id=len(m.bad), last_frame_is_keyframe=last.is_keyframe,
+                                            rgbd=last.rgbd)
+        if len(ids):
+            created = np.array([int(np.nonzero(mp == i)[0][0]) for i in ids], np.int64)
+            got = m.append_points(x3D, last.desc[created])
+            assert got.tolist() == list(ids)
+        last.mvpMapPoints = mp
+        # :1284-1287
+        F.SetPose(predicted_pose)
+        F.pose7 = Tcw_to_pose7(F.Tcw)
+        F.mvpMapPoints[:] = -1
+        th = 7 if self.mSensor == self.STEREO else 15  # :1293-1296
+        bMono = self.mSensor == self.MONOCULAR
+        has = mp >= 0
+        pm = np.where(has, mp, 0)
+        valid = has & (last.mvbOutlier == 0) & (m.dynamic[pm] == 0)  # :1400-1405
+        tb = None if F.keys_static is None else (np.asarray(F.keys_static) == 0).astype(np.uint8)  # :1456 (the frame holds no map point yet, :1451)
+        fx, fy, cx, cy, bf = [float(np.float32(a)) for a in F.intr]
+        mb = float(np.float32(np.float32(bf) / np.float32(fx)))  # Frame.cc:141
+        self.matcher.mbCheckOrientation = True  # ORBmatcher matcher(0.9, true), :1278
+        self.matcher.set_frame(F.keysUn, F.desc, F.bounds)
+        if not bMono:
+            self.matcher.set_u_right(F.u_right if F.u_right_device is None else int(F.u_right_device), n=len(F.keysUn))
+
+        def search(radius):
+            tm, n = self.matcher.SearchByProjectionFrame(m.world_pos[pm], valid, m.n_obs[pm] > 0, m.desc[pm], last.keysUn["octave"], last.keysUn["angle"], F.Tcw, fx, fy, cx, cy,
+                                                         F.scale_factors, float(radius), tb, bMono=bMono, Tlw=last.Tcw, bf=bf, mb=mb)
+            F.mvpMapPoints[:] = np.where(tm >= 0, mp[np.maximum(tm, 0)], -1)
+            return n
+        nmatches = search(th)
+        self.retried = nmatches < 20
+        if nmatches < 20:  # :1300-1304
+            nmatches = search(2 * th)
+        self.nmatches, self.nmatchesMap = nmatches, 0
+        if nmatches < 20:  # :1314-1318
+            return False
+        idx = np.nonzero(F.mvpMapPoints >= 0)[0]
+        pts = F.mvpMapPoints[idx]
+        obs = np.stack([F.keysUn["x"][idx], F.keysUn["y"][idx], F.u_right[idx]], axis=1).astype(np.float64)
+        fr = {"Xw": m.world_pos[pts].astype(np.float64), "obs": obs, "inv_sigma2": np.asarray(F.inv_level_sigma2, np.float32)[F.keysUn["octave"][idx]].astype(np.float64),
+              "intr": np.asarray(F.intr, np.float32).astype(np.float64), "pose": F.pose7}
+        pose, flags, _ = PoseOptimization([fr], ctx=self.ctx)[0]  # :1321
+        F.pose7 = pose
+        F.SetPose(pose7_to_Tcw(pose))  # Optimizer.cc:468-469
+        F.mvbOutlier[:] = 0
+        F.mvbOutlier[idx] = flags
+        self.last_outliers = F.mvbOutlier.copy()
+        nmatchesMap = 0
+        for i, p in zip(idx, pts):  # :1326-1345
+            if F.mvbOutlier[i]:
+                F.mvpMapPoints[i] = -1
+                F.mvbOutlier[i] = 0
+                m.last_frame_seen[p] = F.mnId  # (mbTrackInView = false: the search's own field)
+                nmatches -= 1
+            elif m.n_obs[p] > 0 and not (self.whether_dynamic_object and m.dynamic[p]):
+                nmatchesMap += 1
+        self.nmatches, self.nmatchesMap = nmatches, nmatchesMap
+        if self.mbOnlyTracking:  # :1347-1351
+            self.mbVO = nmatchesMap < 10
+            return nmatches > 20
+        return nmatchesMap >= 10
 
     def UpdateLastFrame(self, mvDepth, keysUn, mvpMapPoints, observations, Tcw, K4, mThDepth, next_point_id, last_frame_is_keyframe=False, rgbd=None, host=False):
         """The point creation of Tracking::UpdateLastFrame (Tracking.cc:1215-1273) over index tables.  mvDepth / keysUn / mvpMapPoints (-1 = NULL) are the last

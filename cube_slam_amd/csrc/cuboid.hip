@@ -18,8 +18,9 @@
 //   cuboid_sweep_score  per surviving proposal: box_edge_sum_dists + box_edge_alignment_angle_error (:427-492), the unit's code map
 //                                   resident in LDS (its tail gathered from global memory when it is larger than LDS)
 //   cuboid_sweep_score_big          the same from the float map, for units with a pixel too far from every edge for a code
-//   cuboid_select       per box   : fuse_normalize_scores_v2 (:495-565) by radix selection, 2D->3D
-//                                   (change_2d_corner_to_3d_object :610-648), final ranking (:517-536)
+//   cuboid_select_keep  per unit  : fuse_normalize_scores_v2 (:495-565) by radix selection, the kept proposals as a list
+//   cuboid_select_geom  per kept proposal: normalised score, 2D->3D (change_2d_corner_to_3d_object :610-648), skew penalty
+//   cuboid_select_rank  per box   : final ranking (:517-536) and the records
 #include "common.h"
 
 #include <algorithm>
@@ -1349,63 +1350,6 @@ __device__ __forceinline__ unsigned long long dkey(double x) { // order-preservi
     unsigned long long b = (unsigned long long)__double_as_longlong(x);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-// The valid hypotheses of a unit are compacted (in order) into key arrays; every thread caches its first SEL_R entries
-// (entry e = tid + 256*k) in registers so the 8-bit radix-select passes run out of registers + LDS histograms.
-constexpr int SEL_R = 8;
-struct KeyCache { unsigned long long v[SEL_R]; };
-template <class F> __device__ __forceinline__ void for_keys(const KeyCache &c, const unsigned long long *gl, int n, F f) {
-#pragma unroll
-    for (int k = 0; k < SEL_R; k++) { int e = threadIdx.x + 256 * k; if (e < n) f(c.v[k], e); }
-    for (int e = threadIdx.x + 256 * SEL_R; e < n; e += 256) f(gl[e], e);
-}
-// k-th smallest (0-based) of n keys; MSB-first 8-bit radix select.  All threads return it.  blockDim.x == 256.
-__device__ unsigned long long block_select_kth(const KeyCache &c, const unsigned long long *gl, int n, int k, int *hist /*256*/, int *s_misc) {
-    unsigned long long prefix = 0, mask = 0;
-    const int lane = threadIdx.x & 63;
-    for (int pass = 0; pass < 8; pass++) {
-        int shift = 56 - 8 * pass;
-        hist[threadIdx.x] = 0;
-        __syncthreads();
-        for_keys(c, gl, n, [&](unsigned long long key, int) { if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1); });
-        __syncthreads();
-        if (threadIdx.x < 64) { // wave 0: 4 bins per lane, inclusive scan over lanes, locate the bin holding rank k
-            int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-            int sum = h0 + h1 + h2 + h3, inc = sum;
-            for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-            unsigned long long m = __ballot(inc > k);
-            int first = __ffsll((long long)m) - 1;
-            if (lane == first) {
-                int acc = inc - sum, bin = 4 * lane;
-                if (acc + h0 > k) {} else { acc += h0; bin++; if (acc + h1 > k) {} else { acc += h1; bin++; if (acc + h2 > k) {} else { acc += h2; bin++; } } }
-                s_misc[0] = bin; s_misc[1] = k - acc;
-            }
-        }
-        __syncthreads();
-        prefix |= (unsigned long long)s_misc[0] << shift;
-        mask |= 0xffull << shift;
-        k = s_misc[1];
-    }
-    return prefix;
-}
-// ordered exclusive count of predicate over [0,n) (in index order); returns total; cb(i, rank) for elements with pred
-template <class P, class F> __device__ int block_ordered_visit(int n, P pred, F cb, int *s_wave /*>= nwaves+1*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int running = 0;
-    for (int base = 0; base < n; base += blockDim.x) {
-        int i = base + threadIdx.x;
-        bool p = i < n && pred(i);
-        unsigned long long m = __ballot(p);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        int off = running, tot = 0;
-        for (int w2 = 0; w2 < nw; w2++) { int c = s_wave[w2]; if (w2 < wave) off += c; tot += c; }
-        if (p) cb(i, off + __popcll(m & ((1ull << lane) - 1)));
-        running += tot;
-        __syncthreads();
-    }
-    return running;
-}
-
 struct Conv3D { double pos[3], scale[3]; };
 __device__ inline void plane_hit(const double *T, const double *invK, const double *pl, double px, double py, double *o3) { // object_3d_util.cpp:574-585
     double ray[3];
@@ -1464,143 +1408,186 @@ __device__ inline void corners_to_3d(const double *cx, const double *cy, const C
     o.scale[0] = length_half; o.scale[1] = width_half; o.scale[2] = height_half;
 }
 
-// flag bits after selection: bits 0-1 vp_1_position, bit 2 kept by fuse_normalize, bit 3 candidate for final ranking
-// Register budget: two waves per SIMD (225 registers) is the kernel's best alone (0.66 ms per 3 072 boxes) -- and a workgroup that needs 4 x 225 registers free on one CU
-// waits for them when region walks hold 2-3 x 96 on every SIMD: 9.4 ms per launch in the batch runner.  Three waves (168 registers, 216 B of scratch): 2.9 ms there.
-#ifndef SELECT_WAVES
-#define SELECT_WAVES 3
-#endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SELECT_WAVES, SELECT_WAVES))) cuboid_select(const Unit *units, UnitDyn *ud, const int *box_first_unit, const FrameDyn *fd,
-                                                     const FrameInfo *fi, const CamRP *cam, const double *yaw, Calib cal, Opts o,
-                                                     uint8_t *flag, const double *derr, const double *aerr, const VPEntry *vpt,
-                                                     double *score, double *nscore, unsigned long long *ckey_d, unsigned long long *ckey_a,
-                                                     int *cidx, cs_cuboid *out, int *counts, int *carry_rp) {
-    __shared__ int hist[256];
-    __shared__ int s_last; // entry (rank among the valid proposals) of the proposal the reference's loop :479-546 processes last
-    __shared__ int s_misc[8];
-    __shared__ int s_wave[8];
-    __shared__ double s_red[4][4];
-    __shared__ double s_best[4];
-    __shared__ int s_bi[4][2];
-    __shared__ int s_branch[4];
-    const int box = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int u0 = box_first_unit[box];
-    const int n_hs = units[u0].n_hs;
-    const FrameDyn &D = fd[units[u0].frame];
-    const FrameInfo &FI = fi[units[u0].frame];
-    const int n_rp = D.n_roll * D.n_pitch;
-    const double weight_vp_angle = 0.8, weight_skew_error = 1.5; // box_proposal_detail.cpp:86-87
-    int n_cand_total = 0;
+// The selection stage: three kernels of single-wave workgroups on the caller's stream.  A workgroup of one wave needs room on ONE SIMD only, and none of the three needs more
+// than 128 registers: each starts in what four region walks of 96 registers leave of a SIMD, where a 4-wave workgroup of 168 registers had to wait for a walk to end.
+//   cuboid_select_keep  per unit        : compaction of the valid proposals, both selects, the keep rule, min / max over the kept set -- integers and keys only
+//   cuboid_select_geom  per kept entry  : normalised score, 2D->3D, scale test, skew penalty; the candidates as a list per unit
+//   cuboid_select_rank  per box         : the best max_cuboid_num of the box's candidate lists and their records
+// flag bits after selection: bits 0-1 vp_1_position, bit 2 kept by fuse_normalize, bit 3 candidate for final ranking (cleared again on the ranked ones)
+struct UnitSel { double mn_d, mx_d, mn_a, mx_a; int n_cand, pad; }; // per unit: the normalisation constants of the kept set; candidates cuboid_select_geom has listed
+constexpr int SEL_KEYS_IN_FLIGHT = 8; // keys per lane that a radix pass of wave_select_kth loads before it counts them
+constexpr int SEL_KEEP_CHUNKS = 4;     // stretches of 64 entries that cuboid_select_keep's keep pass takes at a time
+constexpr int SEL_GEOM_SLICES = 8; // waves per unit of cuboid_select_geom: wave s takes the kept entries [64 (s + 8 j), 64 (s + 8 j) + 64), j = 0, 1, ...
 
-    for (int hs = 0; hs < n_hs; hs++) {
-        const int u = u0 + hs;
-        const Unit &U = units[u];
-        const int n_hyp = n_rp * D.n_yaw * U.n_tops * 2;
-        uint8_t *fl = flag + U.hyp_off;
-        const double *de = derr + U.hyp_off, *ae = aerr + U.hyp_off;
-        // ---- fuse_normalize_scores_v2 (object_3d_util.cpp:495-565)
-        unsigned long long *ckd = ckey_d + U.hyp_off, *cka = ckey_a + U.hyp_off;
-        int *ch = cidx + U.hyp_off;
-        const int n = block_ordered_visit(n_hyp, [&](int i) { return fl[i] != 0; },
-                                          [&](int i, int r) { ckd[r] = dkey(de[i]); cka[r] = dkey(ae[i]); ch[r] = i; }, s_wave);
+// k-th smallest (0-based) of n keys, k < n, by one wave: MSB-first 8-bit radix select.  Every lane returns it.  blockDim.x == 64: __syncthreads() orders the wave's lanes.
+__device__ unsigned long long wave_select_kth(const unsigned long long *keys, int n, int k, int *hist /*256*/) {
+    unsigned long long prefix = 0, mask = 0;
+    const int lane = threadIdx.x;
+    for (int pass = 0; pass < 8; pass++) {
+        const int shift = 56 - 8 * pass;
+        for (int j = 0; j < 4; j++) hist[lane + 64 * j] = 0;
         __syncthreads();
-        KeyCache kd, ka;
+        for (int e0 = lane; e0 < n; e0 += 64 * SEL_KEYS_IN_FLIGHT) { // the loads of a stretch first: a pass is a chain of L2 round trips, not of instructions
+            unsigned long long key[SEL_KEYS_IN_FLIGHT];
 #pragma unroll
-        for (int k = 0; k < SEL_R; k++) { int e = tid + 256 * k; kd.v[k] = e < n ? ckd[e] : 0; ka.v[k] = e < n ? cka[e] : 0; }
-        int branch_b = 0, n_kept = 0;
-        if (tid == 0) s_last = n - 1; // n <= 4: all of them, in index order
-        if (n > 4) {
-            int breaking_num = (int)round(float(n) / 3.0 * 2.0);
-            int k = breaking_num - 1; // elements kept per criterion
-            unsigned long long vd = block_select_kth(kd, ckd, n, k - 1, hist, s_misc);
-            unsigned long long va = block_select_kth(ka, cka, n, k - 1, hist, s_misc);
-            unsigned long long va1 = block_select_kth(ka, cka, n, k, hist, s_misc);
-            __syncthreads();
-            if (tid == 0) { s_misc[2] = 0; s_misc[3] = 0; s_misc[4] = INT_MAX; }
-            __syncthreads();
-            {
-                int nl = 0, ne = 0;
-                for_keys(kd, ckd, n, [&](unsigned long long key, int) { nl += key < vd; ne += key == vd; });
-                for (int off = 32; off > 0; off >>= 1) { nl += __shfl_xor(nl, off); ne += __shfl_xor(ne, off); }
-                if (lane == 0) { atomicAdd(&s_misc[2], nl); atomicAdd(&s_misc[3], ne); }
-            }
-            __syncthreads();
-            const int need_eq = k - s_misc[2]; // ties at the threshold are kept in index order (std::partial_sort tie order pinned, D3)
-            if (need_eq < s_misc[3] && tid == 0) { // rare: more ties than room -> keep the first need_eq of them
-                int seen = 0;
-                for (int e = 0; e < n; e++) if (ckd[e] == vd && ++seen == need_eq) { s_misc[4] = e; break; }
-            }
-            __syncthreads();
-            const int e_star = s_misc[4];
-            const bool use_angle = va1 > va; // angle criterion active: keep set = {angle <= a_k}, intersect
-            if (!use_angle) branch_b = 1;    // final_keep_inds = dist_keep_inds, in (dist, index) order
+            for (int j = 0; j < SEL_KEYS_IN_FLIGHT; j++) key[j] = e0 + 64 * j < n ? keys[e0 + 64 * j] : 0;
 #pragma unroll
-            for (int kk = 0; kk < SEL_R; kk++) {
-                int e = tid + 256 * kk;
-                if (e < n) {
-                    bool ok = kd.v[kk] < vd || (kd.v[kk] == vd && e <= e_star);
-                    if (use_angle) ok = ok && ka.v[kk] <= va;
-                    if (ok) fl[ch[e]] |= 4;
-                }
-            }
-            for (int e = tid + 256 * SEL_R; e < n; e += 256) {
-                bool ok = ckd[e] < vd || (ckd[e] == vd && e <= e_star);
-                if (use_angle) ok = ok && cka[e] <= va;
-                if (ok) fl[ch[e]] |= 4;
-            }
-            if (hs == n_hs - 1 && carry_rp) { // (only for cs_cuboid_detect's chain) the last entry of final_keep_inds: the largest index of the intersection, or the last of the (distance, index) order
-                __syncthreads();
-                if (tid == 0) s_last = -1;
-                __syncthreads();
-                int mine = -1;
-                for (int e = tid; e < n; e += 256) {
-                    const bool kept = (ckd[e] < vd || (ckd[e] == vd && e <= e_star)) && (!use_angle || cka[e] <= va);
-                    if (kept && (use_angle || ckd[e] == vd)) mine = e; // (ascending e per thread: the last one stays)
-                }
-                if (mine >= 0) atomicMax(&s_last, mine);
-                __syncthreads();
-            }
-        } else {
-            for (int e = tid; e < n; e += 256) fl[ch[e]] |= 4;
+            for (int j = 0; j < SEL_KEYS_IN_FLIGHT; j++)
+                if (e0 + 64 * j < n && (key[j] & mask) == prefix) atomicAdd(&hist[(key[j] >> shift) & 255], 1);
         }
         __syncthreads();
-        if (hs == n_hs - 1 && carry_rp) { // what cam_pose holds after this box: the roll / pitch sample of the last good proposal (:481-487), or of the last loop pass (:233-239)
-            __syncthreads();
-            if (tid == 0) {
-                int rp = n_rp - 1;
-                if (n > 0 && s_last >= 0) { int q, ti; hyp_decode(U, ch[s_last], q, ti); rp = q / D.n_yaw; }
-                carry_rp[box] = rp;
+        // 4 bins per lane, inclusive scan over lanes, locate the bin holding rank k
+        const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+        const int sum = h0 + h1 + h2 + h3;
+        int inc = sum;
+        for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+        const int first = __ffsll((long long)__ballot(inc > k)) - 1;
+        int acc = inc - sum, bin = 4 * lane;
+        if (acc + h0 > k) {} else { acc += h0; bin++; if (acc + h1 > k) {} else { acc += h1; bin++; if (acc + h2 > k) {} else { acc += h2; bin++; } } }
+        bin = __shfl(bin, first);
+        k -= __shfl(acc, first);
+        __syncthreads(); // the bins are read before the next pass clears them
+        prefix |= (unsigned long long)bin << shift;
+        mask |= 0xffull << shift;
+    }
+    return prefix;
+}
+
+__global__ void __launch_bounds__(64) cuboid_select_keep(const Unit *units, UnitDyn *ud, UnitSel *sel, const FrameDyn *fd, uint8_t *flag, const double *derr, const double *aerr,
+                                                         unsigned long long *ckey_d, unsigned long long *ckey_a, int *cidx, int *carry_rp) {
+    __shared__ int hist[256];
+    const int u = blockIdx.x, lane = threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1;
+    const Unit &U = units[u];
+    const FrameDyn &D = fd[U.frame];
+    const int n_rp = D.n_roll * D.n_pitch;
+    const int n_hyp = n_rp * D.n_yaw * U.n_tops * 2;
+    uint8_t *fl = flag + U.hyp_off;
+    const double *de = derr + U.hyp_off, *ae = aerr + U.hyp_off;
+    // ---- fuse_normalize_scores_v2 (object_3d_util.cpp:495-565): the valid hypotheses compacted in index order, entry e = rank among them
+    unsigned long long *ckd = ckey_d + U.hyp_off, *cka = ckey_a + U.hyp_off;
+    int *ch = cidx + U.hyp_off;
+    int n = 0;
+    for (int base = 0; base < n_hyp; base += 512) {
+        uint8_t f[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { const int i = base + 64 * j + lane; f[j] = i < n_hyp ? fl[i] : 0; }
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const int i = base + 64 * j + lane;
+            const unsigned long long m = __ballot(f[j] != 0);
+            if (f[j] != 0) { const int r = n + __popcll(m & below); ckd[r] = dkey(de[i]); cka[r] = dkey(ae[i]); ch[r] = i; }
+            n += __popcll(m);
+        }
+    }
+    __syncthreads();
+    int branch_b = 0, e_star = INT_MAX;
+    bool use_angle = false;
+    unsigned long long vd = 0, va = 0;
+    if (n > 4) {
+        const int breaking_num = (int)round(float(n) / 3.0 * 2.0);
+        const int k = breaking_num - 1; // elements kept per criterion
+        vd = wave_select_kth(ckd, n, k - 1, hist);
+        va = wave_select_kth(cka, n, k - 1, hist);
+        int nl = 0, ne = 0, na = 0;
+        for (int e0 = lane; e0 < n; e0 += 64 * SEL_KEEP_CHUNKS) {
+            unsigned long long kd[SEL_KEEP_CHUNKS], ka[SEL_KEEP_CHUNKS];
+#pragma unroll
+            for (int j = 0; j < SEL_KEEP_CHUNKS; j++) { const bool in = e0 + 64 * j < n; kd[j] = in ? ckd[e0 + 64 * j] : ~0ull; ka[j] = in ? cka[e0 + 64 * j] : ~0ull; }
+#pragma unroll
+            for (int j = 0; j < SEL_KEEP_CHUNKS; j++)
+                if (e0 + 64 * j < n) { nl += kd[j] < vd; ne += kd[j] == vd; na += ka[j] <= va; }
+        }
+        for (int off = 32; off > 0; off >>= 1) { nl += __shfl_xor(nl, off); ne += __shfl_xor(ne, off); na += __shfl_xor(na, off); }
+        const int need_eq = k - nl; // ties at the threshold are kept in index order (std::partial_sort tie order pinned, D3)
+        if (need_eq < ne) {         // rare: more ties than room -> keep the first need_eq of them
+            int seen = 0;
+            for (int base = 0; base < n; base += 64) {
+                const int e = base + lane;
+                const bool t = e < n && ckd[e] == vd;
+                const unsigned long long m = __ballot(t);
+                if (seen + __popcll(m) >= need_eq) { e_star = base + __ffsll((long long)__ballot(t && seen + __popcll(m & below) + 1 == need_eq)) - 1; break; }
+                seen += __popcll(m);
             }
         }
-        // min / max over the kept set
-        double mn_d = 1e6, mx_d = -1, mn_a = 1e6, mx_a = -1;
-        int cntk = 0;
-        for (int e = tid; e < n; e += 256) {
-            const int i = ch[e];
-            if (fl[i] & 4) {
-                double td = de[i], ta = ae[i];
-                mn_d = fmin(mn_d, td); mx_d = fmax(mx_d, td); mn_a = fmin(mn_a, ta); mx_a = fmax(mx_a, ta);
-                cntk++;
-            }
+        // the key of rank k lies above the key of rank k - 1 exactly when k keys are <= the latter: angle criterion active, keep set = {angle <= a_k}, intersect
+        use_angle = na == k;
+        if (!use_angle) branch_b = 1; // final_keep_inds = dist_keep_inds, in (dist, index) order
+    }
+    // flag bit 2, min / max over the kept set, the kept entries as a list in entry order (over the head of the entry list: list position <= entry)
+    double mn_d = 1e6, mx_d = -1, mn_a = 1e6, mx_a = -1;
+    int n_kept = 0;
+    long long last = -1; // (entry << 32 | hypothesis) of the last entry of final_keep_inds: the largest index of the intersection, or the last of the (distance, index) order; n <= 4: all of them, in index order
+    for (int base = 0; base < n; base += 64 * SEL_KEEP_CHUNKS) { // SEL_KEEP_CHUNKS stretches of 64 entries at a time: their loads are in flight together
+        int i[SEL_KEEP_CHUNKS];
+        unsigned long long kd[SEL_KEEP_CHUNKS], ka[SEL_KEEP_CHUNKS];
+        bool kept[SEL_KEEP_CHUNKS];
+        double td[SEL_KEEP_CHUNKS], ta[SEL_KEEP_CHUNKS];
+#pragma unroll
+        for (int j = 0; j < SEL_KEEP_CHUNKS; j++) {
+            const int e = base + 64 * j + lane;
+            i[j] = e < n ? ch[e] : 0;
+            kd[j] = e < n && n > 4 ? ckd[e] : 0;
+            ka[j] = e < n && n > 4 ? cka[e] : 0;
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            mn_d = fmin(mn_d, __shfl_xor(mn_d, off)); mx_d = fmax(mx_d, __shfl_xor(mx_d, off));
-            mn_a = fmin(mn_a, __shfl_xor(mn_a, off)); mx_a = fmax(mx_a, __shfl_xor(mx_a, off));
-            cntk += __shfl_xor(cntk, off);
+#pragma unroll
+        for (int j = 0; j < SEL_KEEP_CHUNKS; j++) {
+            const int e = base + 64 * j + lane;
+            kept[j] = e < n && (n <= 4 || ((kd[j] < vd || (kd[j] == vd && e <= e_star)) && (!use_angle || ka[j] <= va)));
+            if (kept[j] && (n <= 4 || use_angle || kd[j] == vd)) last = ((long long)e << 32) | (unsigned)i[j]; // (ascending e per lane: the last one stays)
+            td[j] = kept[j] ? de[i[j]] : 0;
+            ta[j] = kept[j] ? ae[i[j]] : 0;
+            if (kept[j]) fl[i[j]] |= 4;
         }
-        if (lane == 0) { s_red[wave][0] = mn_d; s_red[wave][1] = mx_d; s_red[wave][2] = mn_a; s_red[wave][3] = mx_a; s_wave[wave] = cntk; }
-        __syncthreads();
-        mn_d = fmin(fmin(s_red[0][0], s_red[1][0]), fmin(s_red[2][0], s_red[3][0]));
-        mx_d = fmax(fmax(s_red[0][1], s_red[1][1]), fmax(s_red[2][1], s_red[3][1]));
-        mn_a = fmin(fmin(s_red[0][2], s_red[1][2]), fmin(s_red[2][2], s_red[3][2]));
-        mx_a = fmax(fmax(s_red[0][3], s_red[1][3]), fmax(s_red[2][3], s_red[3][3]));
-        n_kept = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-        // normalised score, 2D->3D, skew penalty, final-ranking candidate score
-        int ncand = 0;
-        for (int e = tid; e < n; e += 256) {
-            const int i = ch[e];
-            if (!(fl[i] & 4)) continue;
+#pragma unroll
+        for (int j = 0; j < SEL_KEEP_CHUNKS; j++)
+            if (kept[j]) { mn_d = fmin(mn_d, td[j]); mx_d = fmax(mx_d, td[j]); mn_a = fmin(mn_a, ta[j]); mx_a = fmax(mx_a, ta[j]); }
+        __syncthreads(); // every lane has read its entries before the list is written over them: list positions <= base + 64 SEL_KEEP_CHUNKS, the next pass reads from there on
+#pragma unroll
+        for (int j = 0; j < SEL_KEEP_CHUNKS; j++) {
+            const unsigned long long m = __ballot(kept[j]);
+            if (kept[j]) ch[n_kept + __popcll(m & below)] = i[j];
+            n_kept += __popcll(m);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        mn_d = fmin(mn_d, __shfl_xor(mn_d, off)); mx_d = fmax(mx_d, __shfl_xor(mx_d, off));
+        mn_a = fmin(mn_a, __shfl_xor(mn_a, off)); mx_a = fmax(mx_a, __shfl_xor(mx_a, off));
+        const long long l2 = __shfl_xor(last, off);
+        last = l2 > last ? l2 : last;
+    }
+    if (lane == 0) {
+        ud[u].n_valid = n; ud[u].n_kept = n_kept; ud[u].branch_b = branch_b;
+        UnitSel &S = sel[u];
+        S.mn_d = mn_d; S.mx_d = mx_d; S.mn_a = mn_a; S.mx_a = mx_a; S.n_cand = 0;
+        if (U.hs == U.n_hs - 1 && carry_rp) { // (only for cs_cuboid_detect's chain) what cam_pose holds after this box: the roll / pitch sample of the last good proposal (:481-487), or of the last loop pass (:233-239)
+            int rp = n_rp - 1;
+            if (last >= 0) { int q, ti; hyp_decode(U, (int)(last & 0xffffffffll), q, ti); rp = q / D.n_yaw; }
+            carry_rp[U.box] = rp;
+        }
+    }
+}
+
+// One lane per kept entry.  The same device functions with the same arguments as the reference order asks for: nothing of the arithmetic depends on which lane does it.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) cuboid_select_geom(const Unit *units, const UnitDyn *ud, UnitSel *sel, const FrameDyn *fd, const CamRP *cam, Calib cal, Opts o,
+                                                         uint8_t *flag, const double *derr, const double *aerr, const VPEntry *vpt, double *score, double *nscore, const int *cidx,
+                                                         unsigned long long *cand_i, unsigned long long *cand_s) {
+    const int u = blockIdx.x, lane = threadIdx.x;
+    const int n_kept = ud[u].n_kept;
+    if ((int)blockIdx.y * 64 >= n_kept) return;
+    const Unit &U = units[u];
+    const FrameDyn &D = fd[U.frame];
+    const double weight_vp_angle = 0.8, weight_skew_error = 1.5; // box_proposal_detail.cpp:86-87
+    uint8_t *fl = flag + U.hyp_off;
+    const double *de = derr + U.hyp_off, *ae = aerr + U.hyp_off;
+    const double mn_d = sel[u].mn_d, mx_d = sel[u].mx_d, mn_a = sel[u].mn_a, mx_a = sel[u].mx_a;
+    for (int base = (int)blockIdx.y * 64; base < n_kept; base += SEL_GEOM_SLICES * 64) {
+        const int r = base + lane;
+        bool cand = false;
+        int i = 0;
+        double sc = 0;
+        if (r < n_kept) {
+            i = cidx[U.hyp_off + r];
             double dk = de[i], ak = ae[i], comb;
             if (n_kept > 1) { // whether_normalize_two_errors = true (:85)
                 comb = (dk - mn_d) / (mx_d - mn_d);
@@ -1608,10 +1595,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SELECT
                 comb = (comb + weight_vp_angle * ak) / (1 + weight_vp_angle);
             } else
                 comb = (dk + weight_vp_angle * ak) / (1 + weight_vp_angle);
-            long g = U.hyp_off + i;
+            const long g = U.hyp_off + i;
             int q, ti;
             hyp_decode(U, i, q, ti);
-            int rp = q / D.n_yaw;
+            const int rp = q / D.n_yaw;
             double cx[8], cy[8];
             { // the proposal's corners, rebuilt (box_proposal_detail.cpp:254-418): nothing stores them
                 V2 c[8];
@@ -1620,122 +1607,143 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SELECT
             }
             Conv3D c3;
             corners_to_3d(cx, cy, cam[(long)U.frame * RP_CAP + rp], cal.invK, c3);
-            if (c3.scale[0] < 0 || c3.scale[1] < 0 || c3.scale[2] < 0) continue; // :493
-            double mxs = c3.scale[0] < c3.scale[1] ? c3.scale[1] : c3.scale[0];   // Eigen maxCoeff / minCoeff
-            double mns = c3.scale[1] < c3.scale[0] ? c3.scale[1] : c3.scale[0];
-            double skew_ratio = mxs / mns;
-            double dsk = skew_ratio - o.nominal_skew_ratio;
-            double skew_error = weight_skew_error * ((dsk < 0.0) ? 0.0 : dsk); // std::max(a,0.0): (a<b)?b:a
-            if (skew_ratio > o.max_cut_skew) skew_error = 100;
-            nscore[g] = comb;
-            score[g] = comb + weight_skew_error * skew_error; // :526
-            fl[i] |= 8;
-            ncand++;
+            if (!(c3.scale[0] < 0 || c3.scale[1] < 0 || c3.scale[2] < 0)) { // :493
+                double mxs = c3.scale[0] < c3.scale[1] ? c3.scale[1] : c3.scale[0]; // Eigen maxCoeff / minCoeff
+                double mns = c3.scale[1] < c3.scale[0] ? c3.scale[1] : c3.scale[0];
+                double skew_ratio = mxs / mns;
+                double dsk = skew_ratio - o.nominal_skew_ratio;
+                double skew_error = weight_skew_error * ((dsk < 0.0) ? 0.0 : dsk); // std::max(a,0.0): (a<b)?b:a
+                if (skew_ratio > o.max_cut_skew) skew_error = 100;
+                sc = comb + weight_skew_error * skew_error; // :526
+                nscore[g] = comb;
+                score[g] = sc;
+                fl[i] |= 8;
+                cand = true;
+            }
         }
-        for (int off = 32; off > 0; off >>= 1) ncand += __shfl_xor(ncand, off);
-        if (lane == 0) s_wave[wave] = ncand;
-        __syncthreads();
-        n_cand_total += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        if (tid == 0) { ud[u].n_valid = n; ud[u].n_kept = n_kept; ud[u].branch_b = branch_b; s_branch[hs] = branch_b; }
-        __syncthreads();
+        const unsigned long long m = __ballot(cand);
+        if (m) { // the wave's candidates behind those the unit's other waves have listed: the list's order is not the ranking's
+            const int first = __ffsll((long long)m) - 1;
+            int at = 0;
+            if (lane == first) at = atomicAdd(&sel[u].n_cand, __popcll(m));
+            at = __shfl(at, first) + __popcll(m & ((1ull << lane) - 1));
+            if (cand) { cand_i[U.hyp_off + at] = (unsigned long long)i; cand_s[U.hyp_off + at] = (unsigned long long)__double_as_longlong(sc); }
+        }
     }
+}
 
+// ranking order :517-536: score, then position in raw_obj_proposals (unit, then distance where the unit's keep list is in distance order, then index)
+__device__ __forceinline__ bool rank_before(double s, int hs, double d, int i, double s2, int hs2, double d2, int i2) {
+    return s < s2 || (s == s2 && (hs < hs2 || (hs == hs2 && (d < d2 || (d == d2 && i < i2)))));
+}
+// full record of one ranked proposal: change_2d_corner_to_3d_object + fields (:489-513)
+__device__ void select_record(const Unit &U, const FrameDyn &D, const FrameInfo &FI, const CamRP *cam, const double *yaw, const Calib &cal, const Opts &o, uint8_t *flag,
+                              const double *derr, const double *aerr, const VPEntry *vpt, const double *nscore, int bi, cs_cuboid &O) {
+    const long g = U.hyp_off + bi;
+    flag[g] &= ~8;
+    int cfg = (bi & 1) + 1, q, ti;
+    hyp_decode(U, bi, q, ti);
+    int yi = q % D.n_yaw, rp = q / D.n_yaw;
+    const CamRP &C = cam[(long)U.frame * RP_CAP + rp];
+    double cx[8], cy[8];
+    {
+        V2 c[8];
+        corners_build<false, true>(U, vpt[(long)U.vp_off + q].vp, U.top_start + ti * U.top_step, cfg, c);
+        for (int k = 0; k < 8; k++) { cx[k] = c[k].x; cy[k] = c[k].y; }
+    }
+    Conv3D c3;
+    corners_to_3d(cx, cy, C, cal.invK, c3);
+    for (int k = 0; k < 3; k++) { O.pos[k] = c3.pos[k]; O.scale[k] = c3.scale[k]; }
+    O.rotY = yaw[(long)U.frame * o.yaw_cap + yi];
+    int vp1 = flag[g] & 3;
+    O.box_config_type[0] = cfg; O.box_config_type[1] = vp1;
+    const int map1[8] = {6, 5, 8, 7, 2, 3, 4, 1}, map2[8] = {5, 6, 7, 8, 3, 2, 1, 4}; // object_3d_util.cpp:637-640
+    for (int k = 0; k < 8; k++) {
+        int src = (vp1 == 1 ? map1[k] : map2[k]) - 1;
+        O.box_corners_2d[k] = (int)cx[src];
+        O.box_corners_2d[8 + k] = (int)cy[src];
+    }
+    { // compute3D_BoxCorner :41-50
+        const double body[3][8] = {{1, 1, -1, -1, 1, 1, -1, -1}, {1, -1, -1, 1, 1, -1, -1, 1}, {-1, -1, -1, -1, 1, 1, 1, 1}};
+        double cyw = cos(O.rotY), syw = sin(O.rotY);
+        double rot[3][3] = {{cyw, -syw, 0}, {syw, cyw, 0}, {0, 0, 1}};
+        double rs[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                double s = rot[i][0] * (j == 0 ? O.scale[0] : 0.0);
+                s = s + rot[i][1] * (j == 1 ? O.scale[1] : 0.0);
+                s = s + rot[i][2] * (j == 2 ? O.scale[2] : 0.0);
+                rs[i][j] = s;
+            }
+        for (int k = 0; k < 8; k++) {
+            double wv[4];
+            for (int i = 0; i < 3; i++) {
+                double s = rs[i][0] * body[0][k];
+                s = s + rs[i][1] * body[1][k];
+                s = s + rs[i][2] * body[2][k];
+                s = s + O.pos[i] * 1.0;
+                wv[i] = s;
+            }
+            wv[3] = ((0.0 * body[0][k] + 0.0 * body[1][k]) + 0.0 * body[2][k]) + 1.0;
+            for (int i = 0; i < 3; i++) O.box_corners_3d_world[i * 8 + k] = wv[i] / wv[3];
+        }
+    }
+    O.rect_detect_2d[0] = U.left; O.rect_detect_2d[1] = U.top; O.rect_detect_2d[2] = U.width_raw; O.rect_detect_2d[3] = U.height_raw;
+    O.edge_distance_error = derr[g]; O.edge_angle_error = aerr[g];
+    O.normalized_error = nscore[g];
+    double mxs = c3.scale[0] < c3.scale[1] ? c3.scale[1] : c3.scale[0];
+    double mns = c3.scale[1] < c3.scale[0] ? c3.scale[1] : c3.scale[0];
+    O.skew_ratio = mxs / mns;
+    O.down_expand_height = U.down_expand;
+    if (o.sample_rp) { O.camera_roll_delta = C.roll - FI.euler[0]; O.camera_pitch_delta = C.pitch - FI.euler[1]; }
+    else { O.camera_roll_delta = 0; O.camera_pitch_delta = 0; }
+}
+
+// One wave per box.  The order is total (unit and index are a proposal's own), so pick p is the first candidate behind pick p - 1: nothing is marked between the picks.  Lane
+// p keeps pick p, and the records of up to 64 picks are then written side by side.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) cuboid_select_rank(const Unit *units, const UnitDyn *ud, const UnitSel *sel, const int *box_first_unit, const FrameDyn *fd,
+                                                         const FrameInfo *fi, const CamRP *cam, const double *yaw, Calib cal, Opts o, uint8_t *flag, const double *derr,
+                                                         const double *aerr, const VPEntry *vpt, const double *nscore, const unsigned long long *cand_i,
+                                                         const unsigned long long *cand_s, cs_cuboid *out, int *counts) {
+    const int box = blockIdx.x, lane = threadIdx.x;
+    const int u0 = box_first_unit[box];
+    const int n_hs = units[u0].n_hs;
+    const FrameDyn &D = fd[units[u0].frame];
+    const FrameInfo &FI = fi[units[u0].frame];
+    int n_cand_total = 0;
+    for (int hs = 0; hs < n_hs; hs++) n_cand_total += sel[u0 + hs].n_cand;
     // ---- final ranking :517-536: best max_cuboid_num by (score, position in raw_obj_proposals)
     const int kout = n_cand_total < o.max_cuboid_num ? n_cand_total : o.max_cuboid_num;
+    double ps = 0, pd = 0; int phs = -1, pi = -1; // the pick before this one
+    int my_hs = -1, my_i = -1, my_pick = 0;
     for (int pick = 0; pick < kout; pick++) {
         double bs = 0, bd = 0; int bhs = -1, bi = -1;
         for (int hs = 0; hs < n_hs; hs++) {
             const Unit &U = units[u0 + hs];
-            const int n_hyp = n_rp * D.n_yaw * U.n_tops * 2;
-            const uint8_t *fl = flag + U.hyp_off;
-            const int bb = s_branch[hs];
-            for (int i = tid; i < n_hyp; i += 256) {
-                if (!(fl[i] & 8)) continue;
-                double s = score[U.hyp_off + i], dd = bb ? derr[U.hyp_off + i] : 0.0;
-                bool better = bi < 0 || s < bs || (s == bs && (hs < bhs || (hs == bhs && (dd < bd || (dd == bd && i < bi)))));
-                if (better) { bs = s; bd = dd; bhs = hs; bi = i; }
+            const int nc = sel[u0 + hs].n_cand, bb = ud[u0 + hs].branch_b;
+            for (int c = lane; c < nc; c += 64) {
+                const int i = (int)cand_i[U.hyp_off + c];
+                const double s = __longlong_as_double((long long)cand_s[U.hyp_off + c]), dd = bb ? derr[U.hyp_off + i] : 0.0;
+                if (pi >= 0 && !rank_before(ps, phs, pd, pi, s, hs, dd, i)) continue;
+                if (bi < 0 || rank_before(s, hs, dd, i, bs, bhs, bd, bi)) { bs = s; bd = dd; bhs = hs; bi = i; }
             }
         }
         for (int off = 32; off > 0; off >>= 1) {
             double s2 = __shfl_xor(bs, off), d2 = __shfl_xor(bd, off);
             int hs2 = __shfl_xor(bhs, off), i2 = __shfl_xor(bi, off);
-            bool better = i2 >= 0 && (bi < 0 || s2 < bs || (s2 == bs && (hs2 < bhs || (hs2 == bhs && (d2 < bd || (d2 == bd && i2 < bi))))));
-            if (better) { bs = s2; bd = d2; bhs = hs2; bi = i2; }
+            if (i2 >= 0 && (bi < 0 || rank_before(s2, hs2, d2, i2, bs, bhs, bd, bi))) { bs = s2; bd = d2; bhs = hs2; bi = i2; }
         }
-        if (lane == 0) { s_best[wave] = bs; s_red[wave][0] = bd; s_bi[wave][0] = bhs; s_bi[wave][1] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w2 = 1; w2 < 4; w2++) {
-                double s2 = s_best[w2], d2 = s_red[w2][0];
-                int hs2 = s_bi[w2][0], i2 = s_bi[w2][1];
-                bool better = i2 >= 0 && (bi < 0 || s2 < bs || (s2 == bs && (hs2 < bhs || (hs2 == bhs && (d2 < bd || (d2 == bd && i2 < bi))))));
-                if (better) { bs = s2; bd = d2; bhs = hs2; bi = i2; }
-            }
-            const Unit &U = units[u0 + bhs];
-            long g = U.hyp_off + bi;
-            flag[g] &= ~8;
-            // full record: change_2d_corner_to_3d_object + fields (:489-513)
-            int cfg = (bi & 1) + 1, q, ti;
-            hyp_decode(U, bi, q, ti);
-            int yi = q % D.n_yaw, rp = q / D.n_yaw;
-            const CamRP &C = cam[(long)U.frame * RP_CAP + rp];
-            double cx[8], cy[8];
-            {
-                V2 c[8];
-                corners_build<false, true>(U, vpt[(long)U.vp_off + q].vp, U.top_start + ti * U.top_step, cfg, c);
-                for (int k = 0; k < 8; k++) { cx[k] = c[k].x; cy[k] = c[k].y; }
-            }
-            Conv3D c3;
-            corners_to_3d(cx, cy, C, cal.invK, c3);
-            cs_cuboid &O = out[(long)box * o.max_cuboid_num + pick];
-            for (int k = 0; k < 3; k++) { O.pos[k] = c3.pos[k]; O.scale[k] = c3.scale[k]; }
-            O.rotY = yaw[(long)U.frame * o.yaw_cap + yi];
-            int vp1 = flag[g] & 3;
-            O.box_config_type[0] = cfg; O.box_config_type[1] = vp1;
-            const int map1[8] = {6, 5, 8, 7, 2, 3, 4, 1}, map2[8] = {5, 6, 7, 8, 3, 2, 1, 4}; // object_3d_util.cpp:637-640
-            for (int k = 0; k < 8; k++) {
-                int src = (vp1 == 1 ? map1[k] : map2[k]) - 1;
-                O.box_corners_2d[k] = (int)cx[src];
-                O.box_corners_2d[8 + k] = (int)cy[src];
-            }
-            { // compute3D_BoxCorner :41-50
-                const double body[3][8] = {{1, 1, -1, -1, 1, 1, -1, -1}, {1, -1, -1, 1, 1, -1, -1, 1}, {-1, -1, -1, -1, 1, 1, 1, 1}};
-                double cyw = cos(O.rotY), syw = sin(O.rotY);
-                double rot[3][3] = {{cyw, -syw, 0}, {syw, cyw, 0}, {0, 0, 1}};
-                double rs[3][3];
-                for (int i = 0; i < 3; i++)
-                    for (int j = 0; j < 3; j++) {
-                        double s = rot[i][0] * (j == 0 ? O.scale[0] : 0.0);
-                        s = s + rot[i][1] * (j == 1 ? O.scale[1] : 0.0);
-                        s = s + rot[i][2] * (j == 2 ? O.scale[2] : 0.0);
-                        rs[i][j] = s;
-                    }
-                for (int k = 0; k < 8; k++) {
-                    double wv[4];
-                    for (int i = 0; i < 3; i++) {
-                        double s = rs[i][0] * body[0][k];
-                        s = s + rs[i][1] * body[1][k];
-                        s = s + rs[i][2] * body[2][k];
-                        s = s + O.pos[i] * 1.0;
-                        wv[i] = s;
-                    }
-                    wv[3] = ((0.0 * body[0][k] + 0.0 * body[1][k]) + 0.0 * body[2][k]) + 1.0;
-                    for (int i = 0; i < 3; i++) O.box_corners_3d_world[i * 8 + k] = wv[i] / wv[3];
-                }
-            }
-            O.rect_detect_2d[0] = U.left; O.rect_detect_2d[1] = U.top; O.rect_detect_2d[2] = U.width_raw; O.rect_detect_2d[3] = U.height_raw;
-            O.edge_distance_error = derr[g]; O.edge_angle_error = aerr[g];
-            O.normalized_error = nscore[g];
-            double mxs = c3.scale[0] < c3.scale[1] ? c3.scale[1] : c3.scale[0];
-            double mns = c3.scale[1] < c3.scale[0] ? c3.scale[1] : c3.scale[0];
-            O.skew_ratio = mxs / mns;
-            O.down_expand_height = U.down_expand;
-            if (o.sample_rp) { O.camera_roll_delta = C.roll - FI.euler[0]; O.camera_pitch_delta = C.pitch - FI.euler[1]; }
-            else { O.camera_roll_delta = 0; O.camera_pitch_delta = 0; }
+        if (bi >= 0) {
+            if (lane == (pick & 63)) { my_hs = bhs; my_i = bi; my_pick = pick; }
+            ps = bs; pd = bd; phs = bhs; pi = bi;
         }
-        __syncthreads();
+        if (bi < 0 || (pick & 63) == 63 || pick == kout - 1) {
+            if (my_i >= 0) select_record(units[u0 + my_hs], D, FI, cam, yaw, cal, o, flag, derr, aerr, vpt, nscore, my_i, out[(long)box * o.max_cuboid_num + my_pick]);
+            my_i = -1;
+        }
+        if (bi < 0) break; // (scores that do not compare: nothing is behind the last pick)
     }
-    if (tid == 0) counts[box] = kout;
+    if (lane == 0) counts[box] = kout;
 }
 
 __global__ void cuboid_bgr2gray(const uint8_t *bgr, int stride, int w, int h, uint8_t *gray) { // cvtColor(CV_BGR2GRAY), :62-66
@@ -1936,7 +1944,8 @@ struct cs_cuboid_batch : Plan { // (the plan in force: plan_commit)
     VPEntry *d_vp = nullptr;
     int *d_vcount = nullptr, *d_vlist = nullptr; // per unit: number of surviving proposals and their hypothesis indices
     double *d_derr = nullptr, *d_aerr = nullptr, *d_score = nullptr, *d_nscore = nullptr;
-    unsigned long long *d_ckd = nullptr, *d_cka = nullptr; int *d_cidx = nullptr;
+    unsigned long long *d_ckd = nullptr, *d_cka = nullptr; int *d_cidx = nullptr; // the selection's keys and entry list; behind cuboid_select_keep the kept list (d_cidx) and the candidates' index and score (d_ckd, d_cka)
+    UnitSel *d_sel = nullptr;
     cs_cuboid *d_out = nullptr;
     cs_cuboid_batch() { cap.fill(-1); }
 };
@@ -1945,14 +1954,14 @@ static void plan_commit(cs_cuboid_batch *b, Plan &P) { static_cast<Plan &>(*b) =
 // The plan-sized arrays, each stated once: it holds cap[cls] * mul + add elements.
 struct BatchArray { void **slot; int cls; size_t elem, mul, add; };
 template <class T> static BatchArray array_of(T *&p, int cls, size_t mul = 1, size_t add = 0) { return {reinterpret_cast<void **>(&p), cls, sizeof(T), mul, add}; }
-constexpr size_t N_BATCH_ARRAYS = 29;
+constexpr size_t N_BATCH_ARRAYS = 30;
 static std::array<BatchArray, N_BATCH_ARRAYS> batch_arrays(cs_cuboid_batch *b) {
     return {{array_of(b->d_emap, K_PIX, 1, 256), // slack: the wave distance transform reads whole dwords at the row ends
              array_of(b->d_dist, K_PIX),
              array_of(b->d_flag, K_HYP), array_of(b->d_vlist, K_HYP), array_of(b->d_derr, K_HYP), array_of(b->d_aerr, K_HYP), array_of(b->d_score, K_HYP), array_of(b->d_nscore, K_HYP),
              array_of(b->d_ckd, K_HYP), array_of(b->d_cka, K_HYP), array_of(b->d_cidx, K_HYP),
              array_of(b->d_vp, K_VP),
-             array_of(b->d_units, K_UNITS), array_of(b->d_ud, K_UNITS), array_of(b->d_order, K_UNITS), array_of(b->d_uflag, K_UNITS), array_of(b->d_vcount, K_UNITS, 2),
+             array_of(b->d_units, K_UNITS), array_of(b->d_ud, K_UNITS), array_of(b->d_order, K_UNITS), array_of(b->d_uflag, K_UNITS), array_of(b->d_vcount, K_UNITS, 2), array_of(b->d_sel, K_UNITS),
              array_of(b->d_dttmp_off, K_UNITS, 1, 1),
              array_of(b->d_box_first, K_BOXES), array_of(b->d_counts, K_BOXES), array_of(b->d_carry, K_BOXES), array_of(b->d_out, K_BOXES, (size_t)b->o.max_cuboid_num),
              array_of(b->d_lines_in, K_LINES_IN, 4), array_of(b->d_lines_al, K_LINES_IN, 4),
@@ -2250,9 +2259,14 @@ int cs_cuboid_batch_run(cs_ctx *ctx, cs_cuboid_batch *b) {
 #undef SCORE_
         }
     }
-    CS_LAUNCH(ctx, "cuboid_select", cuboid_select, dim3(b->n_boxes), dim3(256), 0, b->d_units, b->d_ud, b->d_box_first, b->d_fd, b->d_fi,
-              b->d_cam, b->d_yaw, b->cal, b->o, b->d_flag, b->d_derr, b->d_aerr, b->d_vp, b->d_score, b->d_nscore,
-              b->d_ckd, b->d_cka, b->d_cidx, b->d_out, b->d_counts, b->want_carry ? b->d_carry : nullptr);
+    ctx->begin("cuboid_select"); // the selection stage of one step: its three launches under one name
+    hipLaunchKernelGGL(cuboid_select_keep, dim3(U), dim3(64), 0, ctx->stream, b->d_units, b->d_ud, b->d_sel, b->d_fd, b->d_flag, b->d_derr, b->d_aerr, b->d_ckd, b->d_cka, b->d_cidx,
+                       b->want_carry ? b->d_carry : nullptr);
+    hipLaunchKernelGGL(cuboid_select_geom, dim3(U, SEL_GEOM_SLICES), dim3(64), 0, ctx->stream, b->d_units, b->d_ud, b->d_sel, b->d_fd, b->d_cam, b->cal, b->o, b->d_flag, b->d_derr, b->d_aerr,
+                       b->d_vp, b->d_score, b->d_nscore, b->d_cidx, b->d_ckd, b->d_cka);
+    hipLaunchKernelGGL(cuboid_select_rank, dim3(b->n_boxes), dim3(64), 0, ctx->stream, b->d_units, b->d_ud, b->d_sel, b->d_box_first, b->d_fd, b->d_fi, b->d_cam, b->d_yaw, b->cal, b->o,
+                       b->d_flag, b->d_derr, b->d_aerr, b->d_vp, b->d_nscore, b->d_ckd, b->d_cka, b->d_out, b->d_counts);
+    ctx->end();
     CS_HIP(ctx, hipGetLastError());
     return CS_OK;
 }

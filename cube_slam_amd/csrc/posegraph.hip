@@ -20,9 +20,12 @@
 //     fixed order: strided thread partials, shuffle tree, four waves -- sim3opt.hip's)
 // The host runs optimization_algorithm_levenberg.cpp's schedule and reads one record of four doubles per trial.  Where the solve fails the step is taken as zero (g2o
 // applies whatever its x held before); the trial is undone either way.
+// cs_essential_graph_solve (include/cubeslam_hip/essential_graph_solve.h) is a test probe of one linear solve: the assembly and the factor + back substitution are issued
+// by eg_launch_assemble / eg_launch_solve for the optimiser and the probe alike.
 #include "common.h"
 #include "lm_schedule.h"
 #include "sim3_math.h"
+#include "../../include/cubeslam_hip/essential_graph_solve.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -297,12 +300,32 @@ struct cs_essential_graph {
     int n = 0, m = 0, fixed = 0, fix_scale = 0, nf = 0, nslots = 0, nLb = 0, nHb = 0, nlev = 0;
     struct Launch { int first, count, seq; };
     std::vector<Launch> launches; // over lev_cols, levels ascending
+    std::vector<int> pos;         // by vertex: its position in the elimination order, -1 the fixed vertex (d_pos on the host)
     int *d_ei = nullptr, *d_ej = nullptr, *d_pos = nullptr, *d_inc_off = nullptr, *d_inc = nullptr, *d_slot_off = nullptr, *d_slot_edge = nullptr, *d_slot_blk = nullptr, *d_col_start = nullptr,
         *d_row_idx = nullptr, *d_upd_off = nullptr, *d_upd_a = nullptr, *d_upd_b = nullptr, *d_row_off = nullptr, *d_row_blk = nullptr, *d_row_col = nullptr, *d_lev_cols = nullptr, *d_status = nullptr;
     uint8_t *d_kind = nullptr, *d_has = nullptr;
     double *d_H = nullptr, *d_L = nullptr, *d_b = nullptr, *d_y = nullptr, *d_x = nullptr, *d_X = nullptr, *d_Xt = nullptr, *d_C = nullptr, *d_e = nullptr, *d_chi = nullptr, *d_J = nullptr,
            *d_rec = nullptr, *d_Scw = nullptr, *d_Snc = nullptr;
 };
+
+// The launches of one linear solve, shared by cs_essential_graph_optimize and cs_essential_graph_solve.
+// H and b from d_J and d_e
+static void eg_launch_assemble(cs_ctx *ctx, cs_essential_graph *g) {
+    CS_LAUNCH(ctx, "eg_assemble", eg_assemble, dim3(g->nf + g->nslots), dim3(64), 0, g->nf, g->d_inc_off, g->d_inc, g->d_slot_off, g->d_slot_edge, g->d_slot_blk, g->d_col_start, g->d_J, g->d_e, g->d_H,
+              g->d_b);
+}
+// d_x = (H + lambda I)^-1 b by position and d_status: the status word cleared, the factor over the launch list upwards, the back substitution downwards
+static int eg_launch_solve(cs_ctx *ctx, cs_essential_graph *g, double lambda) {
+    CS_HIP(ctx, hipMemsetAsync(g->d_status, 0, sizeof(int), ctx->stream));
+    for (const auto &l : g->launches)
+        CS_LAUNCH(ctx, "eg_factor", eg_factor, dim3(l.seq ? 1 : l.count), dim3(EG_THREADS), 0, g->d_lev_cols + l.first, l.count, l.seq, g->d_col_start, g->d_upd_off, g->d_upd_a, g->d_upd_b, g->d_row_off,
+                  g->d_row_blk, g->d_row_col, g->d_H, g->d_b, lambda, g->d_L, g->d_y, g->d_status);
+    for (size_t k = g->launches.size(); k-- > 0;) {
+        const auto &l = g->launches[k];
+        CS_LAUNCH(ctx, "eg_back", eg_back, dim3(l.seq ? 1 : l.count), dim3(64), 0, g->d_lev_cols + l.first, l.count, l.seq, g->d_col_start, g->d_row_idx, g->d_L, g->d_y, g->d_x);
+    }
+    return CS_OK;
+}
 
 extern "C" {
 
@@ -428,6 +451,7 @@ int cs_essential_graph_create(cs_ctx *ctx, int n_vertices, int n_edges, const in
         const hipError_t e = hipMemsetAsync(g->d_H, 0, LB * 49 * sizeof(double), ctx->stream);
         if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
     }
+    g->pos = pos;
     const hipError_t e = hipStreamSynchronize(ctx->stream); // the host vectors above go out of scope
     if (!r && e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; }
     if (r) { g->own.free_all(ctx); delete g; return r; }
@@ -465,21 +489,14 @@ int cs_essential_graph_optimize(cs_ctx *ctx, cs_essential_graph *g, const double
         CS_LAUNCH(ctx, "eg_error", eg_error, ge, tb, 0, m, g->d_ei, g->d_ej, g->d_C, X, g->d_e, g->d_chi);
         CS_LAUNCH(ctx, "eg_reduce", eg_reduce, dim3(1), tb, 0, m, g->d_chi, 0, 0, g->d_x, g->d_b, 0.0, g->d_status, g->d_rec);
         CS_LAUNCH(ctx, "eg_linearize", eg_linearize, gl, tb, 0, m, g->d_ei, g->d_ej, g->d_C, X, g->fixed, g->fix_scale, g->d_J);
-        CS_LAUNCH(ctx, "eg_assemble", eg_assemble, dim3(nf + g->nslots), dim3(64), 0, nf, g->d_inc_off, g->d_inc, g->d_slot_off, g->d_slot_edge, g->d_slot_blk, g->d_col_start, g->d_J, g->d_e, g->d_H,
-                  g->d_b);
+        eg_launch_assemble(ctx, g);
         if (it == 0) lm.start(1e-16); // computeLambdaInit: _userLambdaInit > 0
         lm.begin_iteration();
         double currentChi = 0, iniChi = 0;
         st.iterations++;
         do {
-            CS_HIP(ctx, hipMemsetAsync(g->d_status, 0, sizeof(int), ctx->stream));
-            for (const auto &l : g->launches)
-                CS_LAUNCH(ctx, "eg_factor", eg_factor, dim3(l.seq ? 1 : l.count), tb, 0, g->d_lev_cols + l.first, l.count, l.seq, g->d_col_start, g->d_upd_off, g->d_upd_a, g->d_upd_b, g->d_row_off,
-                          g->d_row_blk, g->d_row_col, g->d_H, g->d_b, lm.lambda, g->d_L, g->d_y, g->d_status);
-            for (size_t k = g->launches.size(); k-- > 0;) {
-                const auto &l = g->launches[k];
-                CS_LAUNCH(ctx, "eg_back", eg_back, dim3(l.seq ? 1 : l.count), dim3(64), 0, g->d_lev_cols + l.first, l.count, l.seq, g->d_col_start, g->d_row_idx, g->d_L, g->d_y, g->d_x);
-            }
+            r = eg_launch_solve(ctx, g, lm.lambda);
+            if (r) return r;
             CS_LAUNCH(ctx, "eg_update", eg_update, gv, tb, 0, n, g->d_pos, g->fix_scale, 1, g->d_status, g->d_x, X, Xt);
             CS_LAUNCH(ctx, "eg_error", eg_error, ge, tb, 0, m, g->d_ei, g->d_ej, g->d_C, Xt, (double *)nullptr, g->d_chi);
             CS_LAUNCH(ctx, "eg_reduce", eg_reduce, dim3(1), tb, 0, m, g->d_chi, 1, nf * 7, g->d_x, g->d_b, lm.lambda, g->d_status, g->d_rec);
@@ -513,6 +530,28 @@ int cs_essential_graph_optimize(cs_ctx *ctx, cs_essential_graph *g, const double
         }
     }
     if (stats) *stats = st;
+    return CS_OK;
+}
+
+// include/cubeslam_hip/essential_graph_solve.h
+int cs_essential_graph_solve_version(void) { return CS_ESSENTIAL_GRAPH_SOLVE_VERSION; }
+
+int cs_essential_graph_solve(cs_ctx *ctx, cs_essential_graph *g, const double *J, const double *err, double lambda, double *x_out, int *status) {
+    if (!ctx || !g || g->ctx != ctx || !J || !err || !x_out || !status) return CS_ERR_BAD_ARG;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t M = (size_t)g->m, NF = (size_t)g->nf;
+    CS_TRY(cs_h2d(ctx, g->d_J, J, M * 98));
+    CS_TRY(cs_h2d(ctx, g->d_e, err, M * 7));
+    eg_launch_assemble(ctx, g);
+    CS_TRY(eg_launch_solve(ctx, g, lambda));
+    std::vector<double> x(NF * 7);
+    int st = 0;
+    CS_TRY(cs_d2h(ctx, x.data(), g->d_x, NF * 7));
+    CS_TRY(cs_d2h(ctx, &st, g->d_status, 1));
+    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int v = 0; v < g->n; v++)
+        for (int k = 0; k < 7; k++) x_out[(size_t)v * 7 + k] = g->pos[v] >= 0 ? x[(size_t)g->pos[v] * 7 + k] : 0.0;
+    *status = st;
     return CS_OK;
 }
 

@@ -136,6 +136,7 @@ class EssentialGraph(Handle):
         ei, ej, kind = (np.ascontiguousarray(graph["edge_i"], np.int32), np.ascontiguousarray(graph["edge_j"], np.int32), np.ascontiguousarray(graph["edge_kind"], np.uint8))
         if not (len(ei) == len(ej) == len(kind)):
             raise ValueError("EssentialGraph: edge_i, edge_j and edge_kind differ in length")
+        self.m = len(ei)
         self._h = C.c_void_p()
         check(self.ctx.ptr, lib().cs_essential_graph_create(self.ctx.ptr, self.n, len(ei), ptr(ei), ptr(ej), ptr(kind), int(graph["fixed_vertex"]),
                                                             int(bool(fix_scale)), C.byref(self._h)), "cs_essential_graph_create")
@@ -152,6 +153,16 @@ class EssentialGraph(Handle):
         stats = {k: getattr(st, k) for k, _ in _EgStats._fields_[:-1]}
         stats["sequence"] = [int(st.trial_accepted[k]) for k in range(min(st.trials, 256))]
         return out, Tiw, stats
+
+    def solve(self, J, err, lam):
+        """cs_essential_graph_solve (include/cubeslam_hip/essential_graph_solve.h), a test probe: one (H + lam I) x = b of the optimiser's trial from J (m, 14, 7) -- (m, 2, 7, 7)
+        as eg_linearize lays it out -- and err (m, 7), through the optimiser's own assembly, factor and back-substitution launches -> (x (n, 7) by vertex, status)."""
+        J, err = np.ascontiguousarray(J, np.float64).reshape(-1, 14, 7), np.ascontiguousarray(err, np.float64).reshape(-1, 7)
+        if not (len(J) == len(err) == self.m):
+            raise ValueError("EssentialGraph.solve: J and err need one row per edge")
+        x, status = np.zeros((self.n, 7)), C.c_int(-1)
+        check(self.ctx.ptr, lib().cs_essential_graph_solve(self.ctx.ptr, self._h, ptr(J), ptr(err), float(lam), ptr(x), C.byref(status)), "cs_essential_graph_solve")
+        return x, status.value
 
 
 def correct_points(P, ref_vertex, Scw, sim3_out, ctx=None, device=0):

@@ -143,3 +143,48 @@ def test_bad_arguments_are_errors_and_launch_nothing(ctx):
     ctx.timing(False)
     with pytest.raises(ValueError):
         create(edge_kind=g["edge_kind"][:-1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------- graph-level cases (P.GRAPH_CASES)
+def test_no_trial_of_the_fans_is_near_a_tie():
+    """CPU: the restatement alone.  fan256 has exactly 512 edges and 257 vertices, fan255 510 and 256; every trial's decision is far from a tie, so equal sequences can be asked."""
+    for name, n, m in (("fan256", 257, 512), ("fan255", 256, 510)):
+        g, (_, _, st) = P.graph_case(name), P.graph_judged(name)
+        assert (len(g["Scw"]), len(g["edge_i"])) == (n, m) and st["iterations"] == 2 and len(st["margins"]) == len(st["sequence"])
+        assert min(st["margins"]) > 1e-6 and 1 in st["sequence"] and st["chi2_last"] < 1e-3 * st["chi2_first"]
+        free = set(range(n)) - {g["fixed_vertex"]}
+        spokes = {int(a) if int(b) == g["fixed_vertex"] else int(b) for a, b in zip(g["edge_i"], g["edge_j"]) if g["fixed_vertex"] in (int(a), int(b))}
+        assert spokes == free  # every free vertex has an edge to the fixed vertex
+
+
+@gpu
+@pytest.mark.parametrize("name", ["fan256", "fan255"])
+def test_full_last_blocks_of_the_per_edge_and_per_vertex_kernels(ctx, name):
+    g, (want, want_T, j) = P.graph_case(name), P.graph_judged(name)
+    eg = O.EssentialGraph(g, False, ctx=ctx)
+    sim3, Tiw, st = eg.optimize(g["Scw"], g["Snc"], g["has_nc"], iterations=P.GRAPH_CASES[name][1])
+    eg.close()
+    ds, dt = R.sim3_distance(sim3, want), R.abs_distance(Tiw, want_T)
+    print("%s: n %d m %d; iterations %d / %d, sequence %s / %s, chi2 %.6g -> %.6g (restatement %.6g -> %.6g); sim3 %.3e (TOL %.3e), Tiw %.3e (TOL %.3e)"
+          % (name, len(sim3), len(g["edge_i"]), st["iterations"], j["iterations"], st["sequence"], j["sequence"], st["chi2_first"], st["chi2_last"], j["chi2_first"], j["chi2_last"], ds,
+             R.TOL_SIM3, dt, R.TOL_TIW))
+    assert len(g["edge_i"]) % 256 == (0 if name == "fan256" else 254) and len(sim3) % 256 == (1 if name == "fan256" else 0)
+    assert st["iterations"] == j["iterations"] and st["sequence"] == j["sequence"]
+    assert ds <= R.TOL_SIM3 and dt <= R.TOL_TIW
+    assert sim3[g["fixed_vertex"]].tobytes() == g["Scw"][g["fixed_vertex"]].tobytes()
+    assert Tiw.tobytes() == R.recover_se3(sim3).tobytes()
+
+
+@gpu
+def test_a_nan_estimate_fails_every_solve_and_gives_the_estimates_back(ctx):
+    """chain5 with one NaN in a free vertex's translation: chi2 is NaN, the factor meets a NaN pivot on every trial (rec[3], the host's "solve failed" trial, the zero step of
+    eg_update), rho is NaN, so each iteration has one undone trial and none of the stop rules of optimization_algorithm_levenberg.cpp applies: 20 iterations, nothing accepted."""
+    g, (want, _, j) = P.graph_case("nan_vertex"), P.graph_judged("nan_vertex")
+    assert j["iterations"] == 20 and j["sequence"] == [0] * 20 and want.tobytes() == g["Scw"].tobytes() and np.isnan(g["Scw"]).sum() == 1
+    eg = O.EssentialGraph(g, False, ctx=ctx)
+    sim3, Tiw, st = eg.optimize(g["Scw"], g["Snc"], g["has_nc"], iterations=P.GRAPH_CASES["nan_vertex"][1])
+    eg.close()
+    print("nan_vertex: iterations %d / %d, sequence %s, lambda %.6g / %.6g" % (st["iterations"], j["iterations"], st["sequence"], st["lambda_last"], j["lambda_last"]))
+    assert st["iterations"] == j["iterations"] and st["sequence"] == j["sequence"] and (st["accepted"], st["rejected"]) == (0, 20)
+    assert sim3.tobytes() == g["Scw"].tobytes()
+    assert st["lambda_last"] == j["lambda_last"]

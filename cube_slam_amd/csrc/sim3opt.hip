@@ -18,9 +18,13 @@
 //   * optimize(5); chi2 > th2 on either edge, on the _error the last trial left, removes the pair; fewer than 10 left: return 0 with the Sim3 as it came; otherwise
 //     optimize(nBad > 0 ? 10 : 5) from the first stage's estimate and a second cut that only flags
 // Every loop is bounded by those constants; no atomics, no waiting on other workgroups.
+//
+// cs_sim3_optimization_trace (include/cubeslam_hip/sim3_opt_trace.h) is a test probe: the same kernel with trace / n_trials / system0 set, which the product entry passes
+// as NULL.  Thread 0 then stores the first system and one record per LM trial behind a workgroup-uniform test; nothing else in the kernel depends on those pointers.
 #include "common.h"
 #include "lm_schedule.h"
 #include "sim3_math.h"
+#include "../../include/cubeslam_hip/sim3_opt_trace.h"
 
 #include <algorithm>
 #include <cmath>
@@ -42,7 +46,8 @@ __device__ __forceinline__ void sim3_edge_error(const Sim3 &S, const double *p, 
 __device__ __forceinline__ double sim3_edge_chi2(const double *e, double w) { return e[0] * (w * e[0]) + e[1] * (w * e[1]); } // _error.dot(information() * _error)
 
 __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Problem *problems, const double *P1c, const double *P2c, const double *obs1, const double *obs2, const double *w1,
-                                                               const double *w2, const double *sim3_in, double *sim3_out, uint8_t *removed, int *n_inliers, double *err /* 4 per correspondence */) {
+                                                               const double *w2, const double *sim3_in, double *sim3_out, uint8_t *removed, int *n_inliers, double *err /* 4 per correspondence */,
+                                                               int max_trials, double *trace, int *n_trials, double *system0 /* the probe's: NULL in the product */) {
     __shared__ double s_red[4 * SIM3_NSYS], s_sys[SIM3_NSYS];
     __shared__ double s_x[7], s_S[8], s_pert[28 * 8]; // s_pert: Sim3(+-delta e_d) * estimate for d = 0 .. 6 (14), then their inverses (14)
     __shared__ int s_flag;
@@ -56,6 +61,8 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
     if (n == 0) { // optimize() has no vertex to work on; nCorrespondences - nBad < 10.  The whole workgroup leaves here, before any barrier
         if (tid < 8) out[tid] = in[tid];
         if (tid == 0) n_inliers[blockIdx.x] = 0;
+        if (trace && tid == 0) n_trials[blockIdx.x] = 0;
+        if (trace && tid < SIM3_NSYS) system0[(long)blockIdx.x * SIM3_NSYS + tid] = 0;
         return;
     }
     for (int i = tid; i < n; i += SIM3_THREADS) rem[i] = 0;
@@ -80,7 +87,7 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
         block_reduce<1>(v, s_red, s_sys + 35);
         return s_sys[35];
     };
-    int nBad = 0, nIn = 0;
+    int nBad = 0, nIn = 0, trials = 0;
     for (int stage = 0; stage < 2; stage++) {
         const int iterations = stage == 0 ? 5 : (nBad > 0 ? 10 : 5);
         LmSchedule lm;
@@ -132,6 +139,10 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
                 }
             }
             block_reduce<35>(acc, s_red, s_sys);
+            if (trace && stage == 0 && it == 0 && tid == 0) {
+                for (int k = 0; k < 35; k++) system0[(long)blockIdx.x * SIM3_NSYS + k] = s_sys[k];
+                system0[(long)blockIdx.x * SIM3_NSYS + 35] = currentChi;
+            }
             if (it == 0) { double mx = 0; for (int a = 0; a < 7; a++) mx = fmax(fabs(s_sys[a * (a + 1) / 2 + a]), mx); lm.start(1e-5 * mx); }
             lm.begin_iteration();
             do {
@@ -183,7 +194,13 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
                 double tempChi = chi2_sum(S);
                 double scale = 0; // computeScale
                 for (int j = 0; j < 7; j++) scale += s_x[j] * (lm.lambda * s_x[j] + s_sys[28 + j]);
-                if (!lm.trial(currentChi, tempChi, ok2, scale)) S = backup;
+                const bool record = trace && trials < max_trials; // the same in every thread; trials beyond max_trials are counted and not stored
+                const long r0 = ((long)blockIdx.x * max_trials + trials) * CS_SIM3_TRACE_RECORD;
+                if (record && tid == 0) { trace[r0] = stage; trace[r0 + 1] = it; trace[r0 + 2] = currentChi; trace[r0 + 3] = tempChi; trace[r0 + 4] = lm.lambda; trace[r0 + 5] = ok2 ? 1.0 : 0.0; }
+                const bool accepted = lm.trial(currentChi, tempChi, ok2, scale);
+                if (!accepted) S = backup;
+                if (record && tid == 0) trace[r0 + 6] = accepted ? 1.0 : 0.0;
+                trials++;
                 __syncthreads(); // s_x / s_S are rewritten by the next trial
             } while (lm.retry());
             if (lm.stop(iniChi, currentChi)) break;
@@ -203,23 +220,32 @@ __global__ void __launch_bounds__(SIM3_THREADS) sim3_opt_kernel(const Sim3Proble
             if (n - nBad < 10) { // g2oS12 is not written: the Sim3 leaves as it came, the flags stay
                 if (tid < 8) out[tid] = in[tid];
                 if (tid == 0) n_inliers[blockIdx.x] = 0;
+                if (trace && tid == 0) n_trials[blockIdx.x] = trials;
                 return;
             }
         } else nIn = n - nBad - flagged;
     }
     if (tid == 0) { sim3_store(S, out); n_inliers[blockIdx.x] = nIn; }
+    if (trace && tid == 0) n_trials[blockIdx.x] = trials;
 }
 
-} // namespace
+__global__ void __launch_bounds__(SIM3_THREADS) sim3_exp_kernel(int n, const double *u, double *out) {
+    const int v = blockIdx.x * SIM3_THREADS + threadIdx.x;
+    if (v >= n) return;
+    double w[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) w[k] = u[(long)v * 7 + k];
+    sim3_store(sim3_exp(w), out + (long)v * 8);
+}
 
-extern "C" {
-
-int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const double *P1c, const double *P2c, const double *obs1, const double *obs2, const double *inv_sigma2_1,
-                         const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2, const uint8_t *fix_scale, double *sim3_out, uint8_t *removed,
-                         int *n_inliers) {
+// Both entries: the checks, the uploads, the one launch and the downloads.  probe == false is the product: the kernel then gets the trace pointers as NULL.
+int sim3_run(cs_ctx *ctx, int n_problems, const int *corr_off, const double *P1c, const double *P2c, const double *obs1, const double *obs2, const double *inv_sigma2_1,
+             const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2, const uint8_t *fix_scale, double *sim3_out, uint8_t *removed,
+             int *n_inliers, bool probe, int max_trials, double *trace, int *n_trials, double *system0) {
     if (!ctx || n_problems < 0 || (n_problems && (!corr_off || !intrinsics || !sim3_in || !th2 || !fix_scale || !sim3_out || !n_inliers))) return CS_ERR_BAD_ARG;
+    if (probe && (max_trials < 0 || (n_problems && (!n_trials || !system0 || (max_trials > 0 && !trace))))) return CS_ERR_BAD_ARG;
     if (n_problems == 0) return CS_OK;
-    if (corr_off[0] < 0) return CS_ERR_BAD_ARG;
+    if (corr_off[0] != 0) return CS_ERR_BAD_ARG;
     for (int f = 0; f < n_problems; f++) if (corr_off[f + 1] < corr_off[f]) return CS_ERR_BAD_ARG;
     const int ne = corr_off[n_problems];
     if (ne > 0 && (!P1c || !P2c || !obs1 || !obs2 || !inv_sigma2_1 || !inv_sigma2_2 || !removed)) return CS_ERR_BAD_ARG;
@@ -236,20 +262,63 @@ int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const
     }
     Sim3Problem *d_pr = nullptr; double *d_p1 = nullptr, *d_p2 = nullptr, *d_o1 = nullptr, *d_o2 = nullptr, *d_w1 = nullptr, *d_w2 = nullptr, *d_in = nullptr, *d_out = nullptr, *d_err = nullptr;
     uint8_t *d_rem = nullptr; int *d_ni = nullptr;
-    const size_t ne1 = (size_t)std::max(ne, 1), np = (size_t)n_problems, nz = (size_t)ne;
+    double *d_trace = nullptr, *d_sys0 = nullptr; int *d_nt = nullptr; // the probe's; they stay NULL in the product
+    const size_t ne1 = (size_t)std::max(ne, 1), np = (size_t)n_problems, nz = (size_t)ne, ntr = np * (size_t)std::max(max_trials, 0) * CS_SIM3_TRACE_RECORD;
     cs_scratch sc(ctx); // (after the host array: it waits for the copy out of it before it goes)
     CS_TRY(sc.alloc(ctx, &d_pr, np));
     CS_TRY(sc.alloc(ctx, &d_p1, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_p2, ne1 * 3)); CS_TRY(sc.alloc(ctx, &d_o1, ne1 * 2)); CS_TRY(sc.alloc(ctx, &d_o2, ne1 * 2));
     CS_TRY(sc.alloc(ctx, &d_w1, ne1)); CS_TRY(sc.alloc(ctx, &d_w2, ne1)); CS_TRY(sc.alloc(ctx, &d_err, ne1 * 4)); CS_TRY(sc.alloc(ctx, &d_rem, ne1));
     CS_TRY(sc.alloc(ctx, &d_in, np * 8)); CS_TRY(sc.alloc(ctx, &d_out, np * 8)); CS_TRY(sc.alloc(ctx, &d_ni, np));
+    if (probe) {
+        CS_TRY(sc.alloc(ctx, &d_trace, std::max(ntr, (size_t)1))); CS_TRY(sc.alloc(ctx, &d_nt, np)); CS_TRY(sc.alloc(ctx, &d_sys0, np * CS_SIM3_TRACE_SYSTEM));
+        CS_HIP(ctx, hipMemsetAsync(d_trace, 0, std::max(ntr, (size_t)1) * sizeof(double), ctx->stream));
+    }
     CS_TRY(cs_h2d(ctx, d_pr, pr.data(), np));
     CS_TRY(cs_h2d(ctx, d_p1, P1c, nz * 3)); CS_TRY(cs_h2d(ctx, d_p2, P2c, nz * 3)); CS_TRY(cs_h2d(ctx, d_o1, obs1, nz * 2)); CS_TRY(cs_h2d(ctx, d_o2, obs2, nz * 2));
     CS_TRY(cs_h2d(ctx, d_w1, inv_sigma2_1, nz)); CS_TRY(cs_h2d(ctx, d_w2, inv_sigma2_2, nz));
     CS_TRY(cs_h2d(ctx, d_in, sim3_in, np * 8));
-    CS_LAUNCH(ctx, "sim3_opt_kernel", sim3_opt_kernel, dim3(n_problems), dim3(SIM3_THREADS), 0, d_pr, d_p1, d_p2, d_o1, d_o2, d_w1, d_w2, d_in, d_out, d_rem, d_ni, d_err);
+    CS_LAUNCH(ctx, "sim3_opt_kernel", sim3_opt_kernel, dim3(n_problems), dim3(SIM3_THREADS), 0, d_pr, d_p1, d_p2, d_o1, d_o2, d_w1, d_w2, d_in, d_out, d_rem, d_ni, d_err,
+              max_trials, d_trace, d_nt, d_sys0);
     CS_TRY(cs_d2h(ctx, sim3_out, d_out, np * 8));
     CS_TRY(cs_d2h(ctx, removed, d_rem, nz));
     CS_TRY(cs_d2h(ctx, n_inliers, d_ni, np));
+    if (probe) { CS_TRY(cs_d2h(ctx, trace, d_trace, ntr)); CS_TRY(cs_d2h(ctx, n_trials, d_nt, np)); CS_TRY(cs_d2h(ctx, system0, d_sys0, np * CS_SIM3_TRACE_SYSTEM)); }
+    const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
+    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
+    return CS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const double *P1c, const double *P2c, const double *obs1, const double *obs2, const double *inv_sigma2_1,
+                         const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2, const uint8_t *fix_scale, double *sim3_out, uint8_t *removed,
+                         int *n_inliers) {
+    return sim3_run(ctx, n_problems, corr_off, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, intrinsics, sim3_in, th2, fix_scale, sim3_out, removed, n_inliers, false, 0, nullptr, nullptr,
+                    nullptr);
+}
+
+// include/cubeslam_hip/sim3_opt_trace.h
+int cs_sim3_opt_trace_version(void) { return CS_SIM3_OPT_TRACE_VERSION; }
+
+int cs_sim3_optimization_trace(cs_ctx *ctx, int n_problems, const int *corr_off, const double *P1c, const double *P2c, const double *obs1, const double *obs2, const double *inv_sigma2_1,
+                               const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2, const uint8_t *fix_scale, double *sim3_out, uint8_t *removed,
+                               int *n_inliers, int max_trials, double *trace, int *n_trials, double *system0) {
+    return sim3_run(ctx, n_problems, corr_off, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, intrinsics, sim3_in, th2, fix_scale, sim3_out, removed, n_inliers, true, max_trials, trace,
+                    n_trials, system0);
+}
+
+int cs_sim3_exp(cs_ctx *ctx, int n, const double *update7, double *sim3_out8) {
+    if (!ctx || n < 0 || (n && (!update7 || !sim3_out8))) return CS_ERR_BAD_ARG;
+    if (n == 0) return CS_OK;
+    CS_HIP(ctx, hipSetDevice(ctx->device));
+    cs_scratch sc(ctx);
+    double *d_u = nullptr, *d_o = nullptr;
+    CS_TRY(sc.alloc(ctx, &d_u, (size_t)n * 7)); CS_TRY(sc.alloc(ctx, &d_o, (size_t)n * 8));
+    CS_TRY(cs_h2d(ctx, d_u, update7, (size_t)n * 7));
+    CS_LAUNCH(ctx, "sim3_exp_kernel", sim3_exp_kernel, dim3((n + SIM3_THREADS - 1) / SIM3_THREADS), dim3(SIM3_THREADS), 0, n, d_u, d_o);
+    CS_TRY(cs_d2h(ctx, sim3_out8, d_o, (size_t)n * 8));
     const hipError_t e = hipStreamSynchronize(ctx->stream); sc.drained = true;
     if (e != hipSuccess) { ctx->err = hipGetErrorString(e); return CS_ERR_HIP; }
     return CS_OK;

@@ -35,6 +35,17 @@ def OptimizeSim3(problems, ctx=None, device=0):
     th2, fix_scale} over the correspondences that survive the reference's filter (:2893-2928), P1c / P2c being its float R * P + t products.
     Returns (sim3_out (8,), removed (n,) u8, n_inliers) per problem: g2oS12 as the reference leaves it (sim3_in bit for bit where it returns 0 before writing it),
     1 where it sets vpMatches1[idx] = NULL, and its return value.  A single dict gives a single tuple."""
+    return _optimize_sim3(problems, ctx, device, None)
+
+
+def OptimizeSim3Trace(problems, max_trials=150, ctx=None, device=0):
+    """cs_sim3_optimization_trace (include/cubeslam_hip/sim3_opt_trace.h), a test probe: OptimizeSim3 through the same kernel, which also stores one record per
+    Levenberg-Marquardt trial.  Returns (sim3_out, removed, n_inliers, trace (min(n_trials, max_trials), 7), n_trials, system0 (36,)) per problem; a trace row is
+    stage, iteration, currentChi before, tempChi as computed, lambda used, solved, accepted; system0 is the lower triangle of H, b and chi2 of the first linearisation."""
+    return _optimize_sim3(problems, ctx, device, int(max_trials))
+
+
+def _optimize_sim3(problems, ctx, device, max_trials):
     single = isinstance(problems, dict)
     if single:
         problems = [problems]
@@ -56,9 +67,14 @@ def OptimizeSim3(problems, ctx=None, device=0):
     th2 = np.ascontiguousarray([pr["th2"] for pr in problems], np.float32)
     fix = np.ascontiguousarray([1 if pr["fix_scale"] else 0 for pr in problems], np.uint8)
     sout = np.zeros((F, 8)); flags = np.zeros(max(ne, 1), np.uint8); ninl = np.zeros(F, np.int32)
-    check(ctx.ptr, lib().cs_sim3_optimization(ctx.ptr, F, ptr(off), ptr(P1), ptr(P2), ptr(o1), ptr(o2), ptr(w1),
-                                              ptr(w2), ptr(intr), ptr(sin), ptr(th2), ptr(fix), ptr(sout), ptr(flags), ptr(ninl)), "cs_sim3_optimization")
-    res = [(sout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
+    args = (ctx.ptr, F, ptr(off), ptr(P1), ptr(P2), ptr(o1), ptr(o2), ptr(w1), ptr(w2), ptr(intr), ptr(sin), ptr(th2), ptr(fix), ptr(sout), ptr(flags), ptr(ninl))
+    if max_trials is None:
+        check(ctx.ptr, lib().cs_sim3_optimization(*args), "cs_sim3_optimization")
+        res = [(sout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f])) for f in range(F)]
+    else:
+        trace, ntr, sys0 = np.zeros((F, max(max_trials, 1), 7)), np.zeros(F, np.int32), np.zeros((F, 36))
+        check(ctx.ptr, lib().cs_sim3_optimization_trace(*args, max_trials, ptr(trace), ptr(ntr), ptr(sys0)), "cs_sim3_optimization_trace")
+        res = [(sout[f].copy(), flags[off[f]:off[f + 1]].copy(), int(ninl[f]), trace[f, :min(int(ntr[f]), max_trials)].copy(), int(ntr[f]), sys0[f].copy()) for f in range(F)]
     return res[0] if single else res
 
 
@@ -184,6 +200,15 @@ def sim3_log(S, ctx=None, device=0):
     S = np.ascontiguousarray(S, np.float64).reshape(-1, 8)
     out = np.zeros((len(S), 7))
     check(ctx.ptr, lib().cs_sim3_log(ctx.ptr, len(S), ptr(S), ptr(out)), "cs_sim3_log")
+    return out
+
+
+def sim3_exp(u, ctx=None, device=0):
+    """g2o::Sim3(update) of (n,7) updates (omega, upsilon, sigma) -> (n,8) tx ty tz qx qy qz qw s, on the device (cs_sim3_exp, include/cubeslam_hip/sim3_opt_trace.h)."""
+    ctx = ctx or _lib.Context(device)
+    u = np.ascontiguousarray(u, np.float64).reshape(-1, 7)
+    out = np.zeros((len(u), 8))
+    check(ctx.ptr, lib().cs_sim3_exp(ctx.ptr, len(u), ptr(u), ptr(out)), "cs_sim3_exp")
     return out
 
 

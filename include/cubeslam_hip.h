@@ -773,7 +773,9 @@ int cs_pose_optimization(cs_ctx *ctx, int n_frames, const int *edge_off, const d
  * those key points; intrinsics n_problems x 8 = fx1 fy1 cx1 cy1 fx2 fy2 cx2 cy2; sim3_in n_problems x 8 = tx ty tz qx qy qz qw s, the coefficients g2o::Sim3 holds,
  * NOT normalised; th2 and fix_scale per problem.  Out: sim3_out (g2oS12; equal to sim3_in bit for bit where the function returns before writing it, :3003-3004),
  * removed[c] = 1 where the reference sets vpMatches1[idx] = NULL, n_inliers[f] = the return value.  One workgroup per problem runs optimize(5), the cut, and
- * optimize(10 or 5) with g2o's numeric Jacobians and Levenberg-Marquardt schedule in one launch. */
+ * optimize(10 or 5) with g2o's numeric Jacobians and Levenberg-Marquardt schedule in one launch.
+ * corr_off[0] must be 0 and the offsets must not decrease, as for every batched entry; CS_ERR_BAD_ARG otherwise, for n_problems < 0, and for a NULL array that the
+ * sizes say is read or written.  A refusal launches nothing and leaves sim3_out, removed and n_inliers as they were; n_problems == 0 succeeds and reads nothing. */
 int cs_sim3_optimization(cs_ctx *ctx, int n_problems, const int *corr_off, const double *P1c, const double *P2c, const double *obs1, const double *obs2,
                          const double *inv_sigma2_1, const double *inv_sigma2_2, const double *intrinsics, const double *sim3_in, const float *th2,
                          const uint8_t *fix_scale, double *sim3_out, uint8_t *removed, int *n_inliers);

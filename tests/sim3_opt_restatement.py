@@ -30,7 +30,7 @@ DBL_MAX = float(np.finfo(np.float64).max)
 
 # D_REF: the largest change of the reference's own eight output numbers, relative to max(1, |value|), when only the order of its correspondences is reversed, over all CASES
 # (measured by tests/test_sim3_opt_restatement_pins.py::test_reference_order_sensitivity, which asserts that this constant is what it measures: 4.807e-07, from the case
-# "stride_p1"; the other cases lie between 1e-09 and 2e-08).  With delta = 1e-9 Jacobians a last-bit change of a sum moves the next iterate by far more than a bit.
+# "stride_p1"; the other seeded cases lie between 1e-09 and 2e-08, the designed ones below 2.1e-07, "th2_7.815").  With delta = 1e-9 Jacobians a last-bit change of a sum moves the next iterate by far more than a bit.
 D_REF = 4.807275137963529e-07
 # restatement vs reference and device vs restatement: 10 x D_REF (the device's strided partials and shuffle tree are a third summation order over up to 15 LM iterations)
 TOL = 10 * D_REF
@@ -156,6 +156,106 @@ def sim3_exp(u):
     return (q, tuple(t), s)
 
 
+EXP_BRANCHES = ("sigma0_theta0", "sigma0_theta", "sigma_theta0", "sigma_theta")  # |sigma| < eps or not, theta < eps or not, in the order sim3.h:83-128 writes them
+
+
+def sim3_exp_branch(u):
+    """The branch of sim3_exp an update takes: the two comparisons are IEEE operations on theta as sim3_exp computes it."""
+    theta = math.sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2])
+    return EXP_BRANCHES[(0 if math.fabs(u[6]) < EPS else 2) + (0 if theta < EPS else 1)]
+
+
+def sim3_exp_longdouble(u):
+    """The formulas of sim3_exp in numpy.longdouble, on the branch the float64 comparisons choose -> the eight numbers tx ty tz qx qy qz qw s (longdouble)."""
+    L = np.longdouble
+    branch = EXP_BRANCHES.index(sim3_exp_branch(u))
+    small_sigma, small_theta = branch < 2, branch % 2 == 0
+    w = [L(u[0]), L(u[1]), L(u[2])]
+    ups, sigma = [L(u[3]), L(u[4]), L(u[5])], L(u[6])
+    theta = np.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+    Om = [[L(0), -w[2], w[1]], [w[2], L(0), -w[0]], [-w[1], w[0], L(0)]]
+    Om2 = [[Om[i][0] * Om[0][j] + Om[i][1] * Om[1][j] + Om[i][2] * Om[2][j] for j in range(3)] for i in range(3)]
+    I = [[L(1 if i == j else 0) for j in range(3)] for i in range(3)]
+    s = np.exp(sigma)
+    if small_theta:
+        R = [[I[i][j] + Om[i][j] + Om2[i][j] for j in range(3)] for i in range(3)]
+    else:
+        a, b = np.sin(theta) / theta, (1 - np.cos(theta)) / (theta * theta)
+        R = [[I[i][j] + a * Om[i][j] + b * Om2[i][j] for j in range(3)] for i in range(3)]
+    if small_sigma:
+        C = L(1)
+        if small_theta:
+            A, B = L(1) / 2, L(1) / 6
+        else:
+            A, B = (1 - np.cos(theta)) / (theta * theta), (theta - np.sin(theta)) / (theta * theta * theta)
+    else:
+        C = (s - 1) / sigma
+        if small_theta:
+            A, B = ((sigma - 1) * s + 1) / (sigma * sigma), ((L(0.5) * sigma * sigma - sigma + 1) * s) / (sigma * sigma * sigma)
+        else:
+            a, b, c = s * np.sin(theta), s * np.cos(theta), theta * theta + sigma * sigma
+            A, B = (a * sigma + (1 - b) * theta) / (theta * c), (C - ((b - 1) * sigma + a * theta) / c) / (theta * theta)
+    q = [L(0)] * 4
+    t = R[0][0] + R[1][1] + R[2][2]
+    if t > 0:
+        t = np.sqrt(t + 1)
+        q[3] = t / 2
+        t = L(0.5) / t
+        q[0], q[1], q[2] = (R[2][1] - R[1][2]) * t, (R[0][2] - R[2][0]) * t, (R[1][0] - R[0][1]) * t
+    else:
+        i = 0
+        if R[1][1] > R[0][0]:
+            i = 1
+        if R[2][2] > R[i][i]:
+            i = 2
+        j = (i + 1) % 3
+        k = (j + 1) % 3
+        t = np.sqrt(R[i][i] - R[j][j] - R[k][k] + 1)
+        q[i] = t / 2
+        t = L(0.5) / t
+        q[3], q[j], q[k] = (R[k][j] - R[j][k]) * t, (R[j][i] + R[i][j]) * t, (R[k][i] + R[i][k]) * t
+    W = [[A * Om[i][j] + B * Om2[i][j] + C * I[i][j] for j in range(3)] for i in range(3)]
+    tr = [W[i][0] * ups[0] + W[i][1] * ups[1] + W[i][2] * ups[2] for i in range(3)]
+    return np.array(tr + q + [s], np.longdouble)
+
+
+def quat_branch(u):
+    """Which branch of Quaterniond(Matrix3d) the rotation of an update takes: "t>0", or the largest diagonal entry "i0" / "i1" / "i2"."""
+    o = sim3_exp_longdouble(u)[3:7]
+    R = [[1 - 2 * (o[1] ** 2 + o[2] ** 2), 0, 0], [0, 1 - 2 * (o[0] ** 2 + o[2] ** 2), 0], [0, 0, 1 - 2 * (o[0] ** 2 + o[1] ** 2)]]  # the diagonal of the rotation q stands for
+    if R[0][0] + R[1][1] + R[2][2] > 0:
+        return "t>0"
+    i = 0
+    if R[1][1] > R[0][0]:
+        i = 1
+    if R[2][2] > R[i][i]:
+        i = 2
+    return "i%d" % i
+
+
+def _exp_updates():
+    """Designed updates for cs_sim3_exp: both comparisons at eps, one ulp either side and well away, with and without a translation (without one t is exactly zero and the
+    quaternion alone is judged, which is where the two theta branches differ most: R's Omega^2 term has the factor 1 in one and 1/2 in the other); rotations of pi - 1e-3
+    for the three written-out cases of the quaternion's second branch; the zero update."""
+    lo, hi = float(np.nextafter(EPS, 0.0)), float(np.nextafter(EPS, 1.0))
+    ups = [(0.0, 0.0, 0.0), (0.3, -0.2, 0.5)]
+    out = [[0.0] * 7]
+    axes = [(1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1 / math.sqrt(2), 1 / math.sqrt(2), 0.0), (0.6, -0.48, 0.64)]
+    for theta in (0.0, 1e-6, lo, EPS, hi, 2e-5, 0.3, 2.0):
+        for sigma in (0.0, 1e-6, -1e-6, lo, -lo, EPS, -EPS, hi, -hi, 2e-5, -0.4, 0.7):
+            for a, axis in enumerate(axes[2:] if theta not in (lo, EPS, hi) else axes):
+                for up in ups:
+                    out.append([axis[0] * theta, axis[1] * theta, axis[2] * theta, up[0], up[1], up[2], sigma])
+    for axis in axes[:4]:
+        for sigma in (0.0, 0.2):
+            th = math.pi - 1e-3
+            out.append([axis[0] * th, axis[1] * th, axis[2] * th, 0.3, -0.2, 0.5, sigma])
+    return np.array(out, np.float64)
+
+
+EXP_UPDATES = _exp_updates()
+
+
 def sim3_map(S, p):
     q, t, s = S
     r = quat_rot(q, p)
@@ -188,7 +288,9 @@ def sim3_to8(S):
 
 # ---------------------------------------------------------------------------------------------------------------------------------- the graph
 class _Problem:
-    def __init__(self, c):
+    def __init__(self, c, mutate=None):
+        assert mutate in (None,) + MUTANTS
+        self.mutate = mutate
         f = lambda a, k: np.ascontiguousarray(a, np.float64).reshape(-1, k)
         self.P1, self.P2, self.o1, self.o2 = f(c["P1c"], 3), f(c["P2c"], 3), f(c["obs1"], 2), f(c["obs2"], 2)
         self.w1, self.w2 = np.ascontiguousarray(c["inv_sigma2_1"], np.float64), np.ascontiguousarray(c["inv_sigma2_2"], np.float64)
@@ -246,7 +348,7 @@ class _Problem:
                 rho1 = np.where(chi <= self.dsqr, 1.0, self.delta / np.sqrt(chi))
                 e0, e1 = E[:, 2 * e], E[:, 2 * e + 1]
                 r0, r1 = (-(w * e0)) * rho1, (-(w * e1)) * rho1  # omega_r = -omega * _error; omega_r *= rho[1]
-                wo = rho1 * w  # robustInformation
+                wo = w if self.mutate == "no_rho1_in_H" else rho1 * w  # robustInformation
                 J0, J1 = J[:, 2 * e, :], J[:, 2 * e + 1, :]
                 for a in range(7):
                     contrib[:, e, 49 + a] = J0[:, a] * r0 + J1[:, a] * r1
@@ -297,10 +399,16 @@ def ldlt_solve(H, lam, b):
     return True, x
 
 
-def _optimize(P, S, idx, iterations, st):
+MUTANTS = ("no_rho1_in_H", "lambda0_1e-4", "keep_rejected")  # the deliberately wrong variants of optimize_sim3(mutate=...): see there
+EXITS = ("qmax", "rho0", "nbad3", "full")  # how a stage's optimize() ends: ten trials of one iteration, rho == 0, three iterations of little gain, the budget spent
+TRACE_RECORD = 7  # stage, iteration, currentChi before the trial, tempChi as computed, lambda used, solved, accepted (include/cubeslam_hip/sim3_opt_trace.h)
+
+
+def _optimize(P, S, idx, iterations, st, stage=0):
     """SparseOptimizer::optimize(iterations) over the correspondences idx from the estimate S -> (S, the _error every edge is left with)."""
     lam, ni, n_bad = 0.0, 2.0, 0
     E = None
+    way_out = "full"
     for it in range(iterations):
         E = P.errors(S, sim3_inverse(S), idx)
         current = P.robust_chi2(E, idx)
@@ -310,7 +418,9 @@ def _optimize(P, S, idx, iterations, st):
             mx = 0.0
             for j in range(7):
                 mx = max(math.fabs(H[j][j]), mx)
-            lam, ni, n_bad = 1e-5 * mx, 2.0, 0
+            lam, ni, n_bad = (1e-4 if P.mutate == "lambda0_1e-4" else 1e-5) * mx, 2.0, 0
+            if stage == 0:
+                st["system0"] = np.array([H[a][c] for a in range(7) for c in range(a + 1)] + [float(v) for v in b] + [current], np.float64)
         rho, qmax = 0.0, 0
         while True:
             backup = S
@@ -320,6 +430,12 @@ def _optimize(P, S, idx, iterations, st):
             S = sim3_mul(sim3_exp(x), S)
             E = P.errors(S, sim3_inverse(S), idx)
             temp = P.robust_chi2(E, idx)
+            record = [float(stage), float(it), current, temp, lam, 1.0 if ok else 0.0, 0.0]
+            st["trace"].append(record)
+            if ok:
+                st["branches"].append(sim3_exp_branch(x))
+            else:
+                st["failed_solves"] += 1
             if not ok:
                 temp = DBL_MAX
             rho = current - temp
@@ -334,37 +450,55 @@ def _optimize(P, S, idx, iterations, st):
                 lam *= max(1. / 3., alpha)
                 ni = 2.0
                 current = temp
+                record[6] = 1.0
             else:
                 lam *= ni
                 ni *= 2
-                S = backup
+                if P.mutate != "keep_rejected":
+                    S = backup
                 st["rejected"] += 1
             qmax += 1
             if not (rho < 0 and qmax < 10):
                 break
         st["iterations"] += 1
         if qmax == 10 or rho == 0:
+            way_out = "qmax" if qmax == 10 else "rho0"
             break
         if (ini - current) * 1e3 < ini:
             n_bad += 1
         else:
             n_bad = 0
         if n_bad >= 3:
+            way_out = "nbad3"
             break
+    st["exits"].append(way_out)
+    st["stage_iterations"].append(st["iterations"] - sum(st["stage_iterations"]))
     return S, E
 
 
-def optimize_sim3(c):
+def optimize_sim3(c, stage2_budget=None, mutate=None):
     """Optimizer::OptimizeSim3 on one problem (a dict as make_case returns) -> (sim3_out (8,), removed (n,) u8, n_inliers, stats).
     stats: early (the < 10 return), nbad1 / nbad2 (pairs flagged by the first / second cut), rejected (LM trials undone), margin (the smallest relative distance of any
-    chi2 at either cut from th2)."""
-    P = _Problem(c)
-    st = {"early": False, "nbad1": 0, "nbad2": 0, "rejected": 0, "iterations": 0, "margin": float("inf"), "stage2": False}
+    chi2 at either cut from th2); and what the probe cs_sim3_optimization_trace shows of the way: trace ((trials, 7): one record per LM trial in the probe's layout, see
+    TRACE_RECORD), system0 (36: the 28 lower-triangle entries of H in row order, b and chi2 of the first linearisation of stage one; zeros without correspondences), exits
+    (one of EXITS per stage that ran), stage_iterations (iterations entered per stage), branches (the sim3_exp branch of every solved step, in order), failed_solves.
+    The two keyword arguments exist for the preconditions that tests/test_sim3_opt_patterns.py checks on the CPU; their defaults restate the reference.
+      stage2_budget  the iterations of the second optimize() in place of nBad > 0 ? 10 : 5
+      mutate         one of MUTANTS, each a bug the end pose forgives: "no_rho1_in_H" builds H from the plain information (b keeps rho[1]), "lambda0_1e-4" starts from
+                     lambda = 1e-4 * max |diag H|, "keep_rejected" does not restore the estimate after a rejected trial"""
+    P = _Problem(c, mutate)
+    st = {"early": False, "nbad1": 0, "nbad2": 0, "rejected": 0, "iterations": 0, "margin": float("inf"), "stage2": False,
+          "trace": [], "system0": np.zeros(36), "exits": [], "stage_iterations": [], "branches": [], "failed_solves": 0}
+
+    def done(*result):
+        st["trace"] = np.array(st["trace"], np.float64).reshape(-1, TRACE_RECORD)
+        return result + (st,)
+
     sim3_in = np.ascontiguousarray(c["sim3_in"], np.float64).copy()
     removed = np.zeros(P.n, np.uint8)
     if P.n == 0:  # optimize() finds no vertex to optimise; nCorrespondences - nBad < 10
         st["early"] = True
-        return sim3_in, removed, 0, st
+        return done(sim3_in, removed, 0)
     idx = np.arange(P.n)
     S, E = _optimize(P, sim3_from8(sim3_in), idx, 5, st)
 
@@ -380,14 +514,14 @@ def optimize_sim3(c):
     st["nbad1"] = int(bad.sum())
     if P.n - st["nbad1"] < 10:
         st["early"] = True
-        return sim3_in, removed, 0, st
+        return done(sim3_in, removed, 0)
     idx = idx[~bad]
     st["stage2"] = True
-    S, E = _optimize(P, S, idx, 10 if st["nbad1"] > 0 else 5, st)
+    S, E = _optimize(P, S, idx, (10 if st["nbad1"] > 0 else 5) if stage2_budget is None else stage2_budget, st, stage=1)
     bad = cut(E, idx)
     removed[idx[bad]] = 1
     st["nbad2"] = int(bad.sum())
-    return sim3_to8(S), removed, int(len(idx) - st["nbad2"]), st
+    return done(sim3_to8(S), removed, int(len(idx) - st["nbad2"]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- the problems
@@ -403,10 +537,18 @@ def _rot(axis, deg):
     return (a[0] * math.sin(h), a[1] * math.sin(h), a[2] * math.sin(h), math.cos(h))
 
 
-def make_case(seed, n, s=1.0, n_outliers=0, noise=1.0, fix_scale=False, th2=10.0, same_k=False):
+def make_case(seed, n, s=1.0, n_outliers=0, noise=1.0, fix_scale=False, th2=10.0, same_k=False, weights=None, moved=(), start=None, k2_claimed=None, fix_flag=None, behind=()):
     """One OptimizeSim3 problem: two cameras (K1, K2), n points 2 - 20 units deep in both, pixel noise of `noise` level-sigmas, n_outliers pairs with an observation moved
     by 30 - 60 px, and the initial Sim3 perturbed from the truth (scale s) by a few degrees, a few percent of translation and +-5 % of scale (none under fix_scale).
-    Everything the reference holds in floats (points as cv::Mat, key points, invSigma2, K, th2) is float-valued."""
+    Everything the reference holds in floats (points as cv::Mat, key points, invSigma2, K, th2) is float-valued.
+    The designed departures, none of which draws from the generator (a case without them is what it was before they existed):
+      weights     both invSigma2 arrays are this number (0.0: H = 0 and b = 0, every solve fails)
+      moved       ((i, dx, dy), ...): obs1[i] is moved by (dx, dy) pixels, far beyond the 30 - 60 px of n_outliers
+      start       (degrees, translation, scale factor): the initial Sim3 is this far from the truth in place of the few degrees and percent, about the drawn axis and
+                  along the drawn signs
+      k2_claimed  the K2 the problem states in `intrinsics`, the points and observations staying those of K2: the same arrays under another camera
+      fix_flag    the fix_scale the problem states, the start staying that of `fix_scale`: one problem with and without the flag
+      behind      indices whose P2c is mirrored to negative depth (finite errors, a chi2 far beyond any th2)"""
     rng = np.random.RandomState(seed)
     k1, k2 = K1, (K1 if same_k else K2)
     truth = (_rot(rng.normal(size=3), rng.uniform(4, 10)), tuple(rng.uniform(-0.4, 0.4, 3) * s), float(s))  # S12: frame 2 -> frame 1
@@ -426,11 +568,21 @@ def make_case(seed, n, s=1.0, n_outliers=0, noise=1.0, fix_scale=False, th2=10.0
         ang, r = rng.uniform(0, 2 * math.pi), rng.uniform(30, 60)
         (o1 if rng.rand() < 0.5 else o2)[i] += (r * math.cos(ang), r * math.sin(ang))
     ds = 1.0 if fix_scale else float(rng.choice([-1, 1]) * rng.uniform(0.02, 0.05) + 1.0)
-    pert = (_rot(rng.normal(size=3), rng.uniform(1, 3)), tuple(rng.uniform(-0.03, 0.03, 3) * s), ds)
+    axis, deg, dt = rng.normal(size=3), rng.uniform(1, 3), rng.uniform(-0.03, 0.03, 3)
+    pert = (_rot(axis, deg), tuple(dt * s), ds)
+    if start is not None:
+        pert = (_rot(axis, start[0]), tuple(np.sign(dt) * start[1] * s), float(start[2]))
     init = sim3_mul(pert, truth)
+    for i, dx, dy in moved:
+        o1[i] += (dx, dy)
+    for i in behind:
+        P2[i, 2] = -P2[i, 2]
+    w = inv_sigma2 if weights is None else np.full(N_LEVELS, weights, np.float32)
+    kc = k2 if k2_claimed is None else tuple(k2_claimed)
     return {"seed": seed, "P1c": P1, "P2c": P2, "obs1": o1.astype(np.float32).astype(np.float64), "obs2": o2.astype(np.float32).astype(np.float64),
-            "inv_sigma2_1": inv_sigma2[lv1].astype(np.float64), "inv_sigma2_2": inv_sigma2[lv2].astype(np.float64),
-            "intrinsics": np.array(k1 + k2, np.float32).astype(np.float64), "sim3_in": sim3_to8(init), "th2": np.float32(th2), "fix_scale": bool(fix_scale),
+            "inv_sigma2_1": w[lv1].astype(np.float64), "inv_sigma2_2": w[lv2].astype(np.float64),
+            "intrinsics": np.array(k1 + kc, np.float32).astype(np.float64), "sim3_in": sim3_to8(init), "th2": np.float32(th2),
+            "fix_scale": bool(fix_scale if fix_flag is None else fix_flag),
             "outliers": outliers, "truth": sim3_to8(truth)}
 
 
@@ -465,6 +617,28 @@ _case("stage2_flags", ("stage2", "nbad>0", "nbad2>0"), seed=207, n=200, n_outlie
 _case("same_k", ("stage2",), seed=16, n=90, n_outliers=10, same_k=True)
 BATCH = ("stride_p1", "n0", "n11", "n12_3out", "outliers_10_more", "fix_scale_on", "scale_0.5")  # seven problems of different sizes, one empty, one taking the early return
 
+# The designed cases: the exits, budgets and per-problem parameters the seeded ones above never reach.  Claims beyond those above (each checked by
+# tests/test_sim3_opt_patterns.py): "exits:a,b" the way out of each stage (* = any), "failed_solves" every trial's solve fails, "pose_unmoved" sim3_out is sim3_in bit for
+# bit although stage two ran, "all_inliers" / "all_flagged", "ten_left" exactly 10 pairs enter stage two, "behind_flagged" the mirrored point is finite and flagged,
+# "scale_kept" s leaves as it came, "stage2_its>=6" / "stage2_its==5", "budget_matters" the other stage-two budget lands further than 100 x TOL away or differs in a flag.
+_case("zero_weights", ("stage2", "nbad0", "exits:qmax,qmax", "failed_solves", "pose_unmoved", "all_inliers"), seed=21, n=40, weights=0.0)
+_case("all_outliers", ("early", "all_flagged"), seed=22, n=30, n_outliers=30, noise=0.3)
+_case("n13_3out", ("stage2", "outliers_exact", "ten_left"), seed=100, n=13, n_outliers=3, noise=0.3)
+_case("behind", ("stage2", "nbad>0", "behind_flagged"), seed=30, n=50, behind=(17,))
+_case("fix_clean", ("stage2", "nbad0", "exits:qmax,*", "scale_kept"), seed=28, n=60, fix_scale=True)
+_case("exact", ("stage2", "nbad0", "exits:*,rho0"), seed=42, n=80, noise=0.0)
+_case("budget10", ("stage2", "nbad>0", "stage2_its>=6", "budget_matters"), seed=371, n=100, th2=1000.0, moved=((5, 900, -700), (41, 900, -700), (77, 900, -700)), start=(60, 1.0, 2.5))
+_case("budget5", ("stage2", "nbad0", "exits:*,full", "stage2_its==5", "budget_matters"), seed=424, n=100, th2=1e5, start=(60, 1.0, 2.5))
+_case("th2_5.991", ("stage2", "nbad>0"), seed=500, n=150, n_outliers=20, noise=1.3, th2=5.991)  # (float) (delta * delta) is th2 - 4.8e-7
+_case("th2_7.815", ("stage2", "nbad>0"), seed=500, n=150, n_outliers=20, noise=1.3, th2=7.815)  # ... th2 + 4.8e-7
+_case("th2_20", ("stage2", "nbad>0"), seed=500, n=150, n_outliers=20, noise=1.3, th2=20.0)  # ... th2
+_case("k_a", ("stage2",), seed=700, n=120, n_outliers=10)
+_case("k_b", ("stage2",), seed=700, n=120, n_outliers=10, k2_claimed=(495.0, 470.0, 300.0, 255.0))
+_case("fix_a", ("stage2", "scale_kept"), seed=760, n=110, n_outliers=12, s=1.5, fix_flag=True)
+_case("fix_b", ("stage2",), seed=760, n=110, n_outliers=12, s=1.5, fix_flag=False)
+NEW_CASES = tuple(CASES)[18:]
+PAIRS = (("th2_5.991", "th2_20"), ("k_a", "k_b"), ("fix_a", "fix_b"))  # one geometry each, differing in one per-problem parameter
+
 _made, _judged = {}, {}
 
 
@@ -487,6 +661,134 @@ def pose_distance(a, b):
     if np.dot(a[3:7], b[3:7]) < 0:
         a[3:7] = -a[3:7]
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------- the way, not only the end
+# How far the restatement's own first system and trace move when only the order of its correspondences changes (the way D_REF was obtained, over the four ORDERS below).  The first system is
+# one sum and has one figure.  The trace has a figure per trial: with delta = 1e-9 Jacobians two summation orders drift apart from trial to trial (1e-15 at the first
+# trial, 1e-6 after ten), and the tempChi of a rejected trial -- chi2 after a step far outside the trust region -- moves by up to 3e-2 where the chi2 that is kept moves
+# by 1e-9, so one figure for all trials would either fail the first kind or see nothing in the second.  For trial i of a case (order_figures):
+#   chi_i     the larger of: the largest relative change of currentChi over the trials 0 .. i (what has accumulated in the estimate), the relative change of tempChi of
+#             trial i itself, and D_SYS0 (two orders may agree to the bit by luck)
+#   lambda_i  the largest relative change of lambda over the trials 0 .. i, and D_SYS0
+# Tolerances are 10 x the figure, the factor TOL uses for a third summation order.  A trial is decisive where its solve failed (tempChi is then replaced by DBL_MAX
+# whatever it was) or |currentChi - tempChi| / currentChi >= 100 x chi_i; the decisive prefix of a case ends before its first trial that is not, and at the latest where the
+# two orders stop agreeing in (stage, iteration, solved, accepted).  tests/test_sim3_opt_patterns.py::test_order_sensitivity_constants asserts each constant:
+#   D_SYS0    system0 over TRACED: the entries of H relative to the largest |H|, those of b to the largest |b|, chi2 to itself
+#   D_CHI     the largest chi_i inside a decisive prefix, over TRACED          D_LAMBDA  the largest lambda_i inside a decisive prefix
+#   D_EXP     sim3_exp in float64 against the same formulas in numpy.longdouble on EXP_UPDATES, as pose_distance measures
+D_SYS0 = 4.168467699661468e-15  # "n2000"
+D_CHI = 0.009703636592577617  # a rejected trial's tempChi in "budget10"; the chi2 of an accepted trial moves by 1.4e-04 at most ("budget5")
+D_LAMBDA = 7.359614434272237e-06  # "budget5"
+D_EXP = 5.142225566797526e-12  # theta = 1e-5, sigma = 2e-5: (1 - cos(theta)) / theta^2 and its like cancel; the median over EXP_UPDATES is 1e-16
+SYS0_TOL, EXP_TOL = 10 * D_SYS0, 10 * D_EXP
+TRACED = tuple(k for k in CASES if k != "n0")  # every case that runs a trial
+MAX_TRIALS = 150  # 15 iterations of at most 10 trials
+STRUCTURE = [0, 1, 5, 6]  # stage, iteration, solved, accepted
+
+
+# The orders a case is summed in beside its own.  Reversal alone is one draw of what another order does, and at a trial whose step is itself amplified rounding (a
+# rejected trial at convergence) that draw scatters by more than the factor ten: a trial's figure is the largest over these four.
+ORDERS = {"reversed": lambda n: np.arange(n)[::-1], "halves swapped": lambda n: np.roll(np.arange(n), n // 2),
+          "evens then odds": lambda n: np.concatenate([np.arange(0, n, 2), np.arange(1, n, 2)]), "odds reversed then evens": lambda n: np.concatenate([np.arange(1, n, 2)[::-1], np.arange(0, n, 2)])}
+
+
+def reordered_case(c, order="reversed"):
+    """The same problem with its correspondences in another order."""
+    r = dict(c)
+    idx = ORDERS[order](len(np.asarray(c["inv_sigma2_1"]).reshape(-1)))
+    for k in ("P1c", "P2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2"):
+        r[k] = np.ascontiguousarray(np.asarray(c[k])[idx])
+    return r
+
+
+def _rel(a, b):
+    a, b = float(a), float(b)
+    if a == b:
+        return 0.0
+    return abs(a - b) / abs(b) if b != 0 else float("inf")
+
+
+def system0_distance(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    d = []
+    for lo, hi in ((0, 28), (28, 35)):
+        m = np.max(np.abs(want[lo:hi]))
+        d.append(float(np.max(np.abs(got[lo:hi] - want[lo:hi]))) / m if m > 0 else (0.0 if np.array_equal(got[lo:hi], want[lo:hi]) else float("inf")))
+    return max(d[0], d[1], _rel(got[35], want[35]))
+
+
+def common_prefix(a, b):
+    """The number of leading trials of two traces that agree in stage, iteration, solved and accepted."""
+    k = 0
+    while k < min(len(a), len(b)) and np.array_equal(a[k][STRUCTURE], b[k][STRUCTURE]):
+        k += 1
+    return k
+
+
+_figures = {}
+
+
+def order_figures(name, other=None):
+    """-> {"sys0", "chi" (per trial), "lambda" (per trial), "prefix" (the decisive prefix), "common", "gain" (per trial: |currentChi - tempChi| / currentChi)} of a case,
+    from its trace and those of the same problem in the ORDERS."""
+    if name in _figures:
+        return _figures[name]
+    st = judged(name)[3]
+    others = [optimize_sim3(reordered_case(case(name), o))[3] for o in ORDERS]
+    t = st["trace"]
+    kc = min(common_prefix(rs["trace"], t) for rs in others)
+    chi, lam, gain, carry_c, carry_l, prefix, open_ = [], [], [], D_SYS0, D_SYS0, 0, True
+    for i in range(kc):
+        carry_c = max([carry_c] + [_rel(rs["trace"][i][2], t[i][2]) for rs in others])
+        carry_l = max([carry_l] + [_rel(rs["trace"][i][4], t[i][4]) for rs in others])
+        chi.append(max([carry_c] + [_rel(rs["trace"][i][3], t[i][3]) for rs in others]))
+        lam.append(carry_l)
+        gain.append(abs(t[i][2] - t[i][3]) / t[i][2] if t[i][2] > 0 else 0.0)
+        if open_ and (t[i][5] == 0.0 or gain[i] >= 100 * chi[i]):
+            prefix = i + 1
+        else:
+            open_ = False
+    f = _figures[name] = {"sys0": max(system0_distance(rs["system0"], st["system0"]) for rs in others), "chi": chi, "lambda": lam, "prefix": prefix, "common": kc, "gain": gain}
+    return f
+
+
+def compare_way(name, system0, trace):
+    """A first system and a trace (the device's, or a mutant's) against the restatement's of the case -> {"sys0": distance of the systems, "same": stage, iteration, solved
+    and accepted equal on the decisive prefix, "chi" / "lambda": the largest relative difference on the prefix, "chi_ratio" / "lambda_ratio": the largest difference as a
+    multiple of its trial's tolerance (<= 1 passes), "chi_trial": the trial of "chi_ratio", "prefix"}."""
+    f, want = order_figures(name), judged(name)[3]
+    k, t = f["prefix"], want["trace"]
+    g = np.asarray(trace, np.float64).reshape(-1, TRACE_RECORD)
+    out = {"sys0": system0_distance(system0, want["system0"]), "prefix": k, "same": len(g) >= k and bool(np.array_equal(g[:k][:, STRUCTURE], t[:k][:, STRUCTURE])),
+           "chi": 0.0, "lambda": 0.0, "chi_ratio": 0.0, "lambda_ratio": 0.0, "chi_trial": -1}
+    for i in range(min(k, len(g))):
+        dc, dl = max(_rel(g[i][2], t[i][2]), _rel(g[i][3], t[i][3])), _rel(g[i][4], t[i][4])
+        out["chi"], out["lambda"] = max(out["chi"], dc), max(out["lambda"], dl)
+        if dc / (10 * f["chi"][i]) > out["chi_ratio"]:
+            out["chi_ratio"], out["chi_trial"] = dc / (10 * f["chi"][i]), i
+        out["lambda_ratio"] = max(out["lambda_ratio"], dl / (10 * f["lambda"][i]))
+    return out
+
+
+_exp = {}
+
+
+def exp_judged():
+    """-> (sim3_exp of every row of EXP_UPDATES as eight numbers (n, 8), its distance from the longdouble formulas per row, the tolerance per row).  A row's tolerance is 10 x
+    its own distance, and at least 10 x 2^-52 (a float64 result may be the longdouble one rounded, which says nothing about a second libm): never more than EXP_TOL."""
+    if not _exp:
+        want = np.array([sim3_to8(sim3_exp(list(u))) for u in EXP_UPDATES])
+        ld = [sim3_exp_longdouble(list(u)) for u in EXP_UPDATES]
+        d = np.array([float(np.max(np.abs(np.asarray(w, np.longdouble) - l) / np.maximum(1, np.abs(l)))) for w, l in zip(want, ld)])
+        _exp["r"] = (want, d, 10 * np.maximum(d, 2.0 ** -52))
+    return _exp["r"]
+
+
+def measure_order_sensitivity():
+    """-> (D_SYS0, D_CHI, D_LAMBDA as defined above)."""
+    fs = [order_figures(name) for name in TRACED]
+    return (max(f["sys0"] for f in fs), max(max(f["chi"][:f["prefix"]] + [0.0]) for f in fs), max(max(f["lambda"][:f["prefix"]] + [0.0]) for f in fs))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- the reference's own text

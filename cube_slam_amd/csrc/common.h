@@ -278,6 +278,44 @@ __device__ __forceinline__ int wave_incl_min_scan(int x) {
     return x;
 }
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// The set bits of mask (a __ballot) below `lane`: the position of a flagged lane among the flagged lanes of its wave, in lane order -- the order of a push_back loop over the lanes.
+__device__ __forceinline__ int wave_rank(unsigned long long mask, int lane) { return __popcll(mask & ((1ull << lane) - 1ull)); }
+// Inclusive add-scan by a __shfl_up tree over groups of WIDTH consecutive lanes; lane: the lane's index in its group.  (The group's sum is in its last lane.)
+template <int WIDTH = 64> __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+    for (int off = 1; off < WIDTH; off <<= 1) { const int t = __shfl_up(v, off, WIDTH); if (lane >= off) v += t; }
+    return v;
+}
+// The two workgroup-wide forms below, for a workgroup of WAVES full waves.  Every thread of the workgroup calls them (from uniform control flow); a call costs two
+// barriers; s_w holds WAVES ints and is free again behind the call.  Nothing orders what the caller stores at the returned positions: a read of it by another
+// thread needs a barrier of the caller's.
+// wave_sum, as lane 63 of each wave holds it -> the sum over the waves in front of the caller's; *total: over all waves
+template <int WAVES> __device__ __forceinline__ int block_waves_before(int wave_sum, int *s_w, int *total) {
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 63) s_w[wave] = wave_sum;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) { const int c = s_w[w]; before += w < wave ? c : 0; all += c; }
+    __syncthreads();
+    *total = all;
+    return before;
+}
+// exclusive prefix of v over the threads of the workgroup, in thread order; *total: the workgroup's sum
+template <int WAVES> __device__ __forceinline__ int block_excl_scan(int v, int *s_w, int *total) {
+    const int inc = wave_incl_scan(v, threadIdx.x & 63);
+    return block_waves_before<WAVES>(inc, s_w, total) + inc - v;
+}
+// The position of a flagged thread among the flagged threads of the workgroup, in thread order (where a thread stands for element base + threadIdx.x, the order of the
+// reference's push_back loop over the elements); *total: their number.  The return value means something only where flag is set.
+template <int WAVES> __device__ __forceinline__ int block_rank(bool flag, int *s_w, int *total) {
+    const unsigned long long b = __ballot(flag);
+    return block_waves_before<WAVES>(__popcll(b), s_w, total) + wave_rank(b, threadIdx.x & 63);
+}
+// Hamming distance of two 256-bit descriptors, four u64 words each (ORBmatcher::DescriptorDistance)
+__device__ __forceinline__ int hamming256(const unsigned long long *a, unsigned long long b0, unsigned long long b1, unsigned long long b2, unsigned long long b3) {
+    return __popcll(a[0] ^ b0) + __popcll(a[1] ^ b1) + __popcll(a[2] ^ b2) + __popcll(a[3] ^ b3);
+}
 
 // The sums of a 256-thread workgroup, in one fixed order of additions (the optimisers' results depend on it): the lanes of a wave by a shuffle tree 32 .. 1,
 // then the four wave results as (w0 + w1) + (w2 + w3).  s_red holds 4 x N doubles.

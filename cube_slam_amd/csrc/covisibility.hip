@@ -34,20 +34,8 @@ struct covis_dtable { // cs_obs_table on the device
     const uint8_t *obs_stereo;
 };
 
-// exclusive prefix of v over the 256 threads; *total: the workgroup's sum.  s_w: 4 ints, free again behind the call
-__device__ __forceinline__ int cv_scan256(int v, int *s_w, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < w; k++) base += s_w[k];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-    return base + inc - v;
-}
-__device__ __forceinline__ int cv_sum256(int v, int *s_w) { int total; cv_scan256(v, s_w, &total); return total; }
+constexpr int CV_WAVES = CV_BLOCK / 64;
+__device__ __forceinline__ int cv_sum256(int v, int *s_w) { int total; block_excl_scan<CV_WAVES>(v, s_w, &total); return total; }
 
 template <bool EMIT>
 __global__ void __launch_bounds__(CV_BLOCK) covis_vote(covis_dtable t, const uint8_t *mp_flags, const int *query_kf, const int *kf_off, const int *kf_mp, int skip_dynamic, int th,
@@ -94,7 +82,7 @@ __global__ void __launch_bounds__(CV_BLOCK) covis_vote(covis_dtable t, const uin
             if (key > best) best = key;
         }
         int total;
-        int o = cv_scan256(mine, s_w, &total);
+        int o = block_excl_scan<CV_WAVES>(mine, s_w, &total);
         if (EMIT) {
             o += cnt_off[q] + carry;
             for (int k = 0; k < CV_PER; k++) { const int w = s_cnt[k0 + k]; if (w) { cnt_kf[o] = lo + k0 + k; cnt_w[o] = w; o++; } }
@@ -139,7 +127,7 @@ __global__ void __launch_bounds__(CV_BLOCK) covis_offsets(int n, const int *a, c
         const int i = i0 + threadIdx.x;
         const int va = i < n ? a[i] : 0, vb = i < n ? b[i] : 0;
         int ta, tb;
-        const int ea = cv_scan256(va, s_w, &ta), eb = cv_scan256(vb, s_w, &tb);
+        const int ea = block_excl_scan<CV_WAVES>(va, s_w, &ta), eb = block_excl_scan<CV_WAVES>(vb, s_w, &tb);
         if (i < n) { a_off[i] = ca + ea; b_off[i] = cb + eb; }
         ca += ta; cb += tb;
     }

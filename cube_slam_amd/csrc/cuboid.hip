@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(64) cuboid_unit_lines(const Unit *units, UnitD
             in = inside_box(V2{a0, a1}, l, t, r, b) && inside_box(V2{a2, a3}, l, t, r, b);
         }
         unsigned long long m = __ballot(in);
-        int pos = total + __popcll(m & ((1ull << lane) - 1));
+        int pos = total + wave_rank(m, lane);
         if (in && pos < cap) { L[pos][0] = a0; L[pos][1] = a1; L[pos][2] = a2; L[pos][3] = a3; } // (cap = min(the longest list, CS_MAX_ROI_LINES) >= this frame's lines unless the list is longer than CS_MAX_ROI_LINES)
         total += __popcll(m);
     }
@@ -346,7 +346,7 @@ __global__ void __launch_bounds__(64) cuboid_unit_lines(const Unit *units, UnitD
             keep = sqrt(dx * dx + dy * dy) > len_thre;
         }
         unsigned long long m = __ballot(keep);
-        int pos = nout + __popcll(m & ((1ull << lane) - 1));
+        int pos = nout + wave_rank(m, lane);
         if (keep) {
             long o = (long)U.line_off + pos;
             mlines[o * 4 + 0] = a0; mlines[o * 4 + 1] = a1; mlines[o * 4 + 2] = a2; mlines[o * 4 + 3] = a3;
@@ -1036,7 +1036,7 @@ __global__ void __launch_bounds__(256) cuboid_sweep_filter(const Unit *units, co
         // h0 and r*256 are even, so lane parity = configuration: even lanes are configuration 1
         const unsigned long long m = __ballot(pos != 0);
         const unsigned long long mine = (lane & 1) ? (m & 0xAAAAAAAAAAAAAAAAull) : (m & 0x5555555555555555ull);
-        rank[r] = pos ? __popcll(mine & ((1ull << lane) - 1)) : -1;
+        rank[r] = pos ? wave_rank(mine, lane) : -1;
         if (lane < 2) s_wc[lane][r * 4 + wave] = __popcll(m & (lane ? 0xAAAAAAAAAAAAAAAAull : 0x5555555555555555ull));
     }
     __syncthreads();
@@ -1439,8 +1439,7 @@ __device__ unsigned long long wave_select_kth(const unsigned long long *keys, in
         // 4 bins per lane, inclusive scan over lanes, locate the bin holding rank k
         const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
         const int sum = h0 + h1 + h2 + h3;
-        int inc = sum;
-        for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+        const int inc = wave_incl_scan(sum, lane);
         const int first = __ffsll((long long)__ballot(inc > k)) - 1;
         int acc = inc - sum, bin = 4 * lane;
         if (acc + h0 > k) {} else { acc += h0; bin++; if (acc + h1 > k) {} else { acc += h1; bin++; if (acc + h2 > k) {} else { acc += h2; bin++; } } }
@@ -1457,7 +1456,6 @@ __global__ void __launch_bounds__(64) cuboid_select_keep(const Unit *units, Unit
                                                          unsigned long long *ckey_d, unsigned long long *ckey_a, int *cidx, int *carry_rp) {
     __shared__ int hist[256];
     const int u = blockIdx.x, lane = threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1;
     const Unit &U = units[u];
     const FrameDyn &D = fd[U.frame];
     const int n_rp = D.n_roll * D.n_pitch;
@@ -1476,7 +1474,7 @@ __global__ void __launch_bounds__(64) cuboid_select_keep(const Unit *units, Unit
         for (int j = 0; j < 8; j++) {
             const int i = base + 64 * j + lane;
             const unsigned long long m = __ballot(f[j] != 0);
-            if (f[j] != 0) { const int r = n + __popcll(m & below); ckd[r] = dkey(de[i]); cka[r] = dkey(ae[i]); ch[r] = i; }
+            if (f[j] != 0) { const int r = n + wave_rank(m, lane); ckd[r] = dkey(de[i]); cka[r] = dkey(ae[i]); ch[r] = i; }
             n += __popcll(m);
         }
     }
@@ -1506,7 +1504,7 @@ __global__ void __launch_bounds__(64) cuboid_select_keep(const Unit *units, Unit
                 const int e = base + lane;
                 const bool t = e < n && ckd[e] == vd;
                 const unsigned long long m = __ballot(t);
-                if (seen + __popcll(m) >= need_eq) { e_star = base + __ffsll((long long)__ballot(t && seen + __popcll(m & below) + 1 == need_eq)) - 1; break; }
+                if (seen + __popcll(m) >= need_eq) { e_star = base + __ffsll((long long)__ballot(t && seen + wave_rank(m, lane) + 1 == need_eq)) - 1; break; }
                 seen += __popcll(m);
             }
         }
@@ -1546,7 +1544,7 @@ __global__ void __launch_bounds__(64) cuboid_select_keep(const Unit *units, Unit
 #pragma unroll
         for (int j = 0; j < SEL_KEEP_CHUNKS; j++) {
             const unsigned long long m = __ballot(kept[j]);
-            if (kept[j]) ch[n_kept + __popcll(m & below)] = i[j];
+            if (kept[j]) ch[n_kept + wave_rank(m, lane)] = i[j];
             n_kept += __popcll(m);
         }
     }
@@ -1626,7 +1624,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) cu
             const int first = __ffsll((long long)m) - 1;
             int at = 0;
             if (lane == first) at = atomicAdd(&sel[u].n_cand, __popcll(m));
-            at = __shfl(at, first) + __popcll(m & ((1ull << lane) - 1));
+            at = __shfl(at, first) + wave_rank(m, lane);
             if (cand) { cand_i[U.hyp_off + at] = (unsigned long long)i; cand_s[U.hyp_off + at] = (unsigned long long)__double_as_longlong(sc); }
         }
     }

@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) gftt_candidates(int w, int h, int s0, dou
     int base = 0;
     if (lane == __ffsll((long long)b) - 1) base = atomicAdd(&ncand[slot], __popcll(b));
     base = __shfl(base, __ffsll((long long)b) - 1);
-    const int pos = base + __popcll(b & ((1ull << lane) - 1ull));
+    const int pos = base + wave_rank(b, lane);
     if (cand && pos < GFTT_MAX_CANDIDATES) keys[(long)slot * GFTT_MAX_CANDIDATES + pos] = gftt_key(v, p); // (the count goes on beyond the capacity; the call then fails)
 }
 
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(SL_THREADS) gftt_select(int w, int max_corners
             pending &= ~struck & ~(1ull << i);
         }
         if ((accepted >> lane) & 1) {
-            const int at = na + __popcll(accepted & ((1ull << lane) - 1ull)); // < total <= min(max_corners, n) <= cap_corners, and <= b0 + lane
+            const int at = na + wave_rank(accepted, lane); // < total <= min(max_corners, n) <= cap_corners, and <= b0 + lane
             sK[at] = ((unsigned long long)(uint32_t)y << 32) | (uint32_t)x;
             const long o = (long)slot * cap_corners + at;
             corners[2 * o] = (float)x; corners[2 * o + 1] = (float)y; quality[o] = gftt_key_value(key);

@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(64) init_check_rt(const InitProblem *problems,
         if (i < P.N && ransac_mask_bit(m, i)) st = init_check_rt_corr(P, a, cam, i, p3d, &cosParallax);
         const unsigned long long counted = __ballot(st != IM_SKIPPED), good = __ballot(st == IM_GOOD);
         if (st != IM_SKIPPED) {
-            list[nGood + __popcll(counted & ((1ull << lane) - 1ull))] = cosParallax; // vCosParallax.push_back in ascending i
+            list[nGood + wave_rank(counted, lane)] = cosParallax; // vCosParallax.push_back in ascending i
             for (int k = 0; k < 3; k++) pts[3 * (size_t)i + k] = p3d[k];
         }
         if (lane == 0) {

@@ -220,6 +220,7 @@ __global__ void __launch_bounds__(HS_THREADS) klt_harris_select(const int *__res
             if (idx >= (long)rows * cols) outside = true;
             else if (idx >= 0) { id = mask[idx]; keep = id != 0; } // 0 <= idx < rows * cols: inside this pair's mask
         }
+        // block_rank (common.h) written out: the count of `outside` rides on its two barriers
         const unsigned long long b = __ballot(keep), bo = __ballot(outside);
         if (lane == 0) { s_wave[wave] = __popcll(b); s_wout[wave] = __popcll(bo); }
         __syncthreads();
@@ -228,7 +229,7 @@ __global__ void __launch_bounds__(HS_THREADS) klt_harris_select(const int *__res
         for (int w = 0; w < HS_WAVES; w++) { const int v = s_wave[w]; before += w < wave ? v : 0; all += v; beyond += s_wout[w]; }
         __syncthreads();
         if (keep) {
-            const int pos = b0 + good + before + __popcll(b & ((1ull << lane) - 1ull)); // < b0 + n
+            const int pos = b0 + good + before + wave_rank(b, lane); // < b0 + n
             kept[pos] = i; kept_pts[2 * (size_t)pos] = x; kept_pts[2 * (size_t)pos + 1] = y; object_id[pos] = id - 1;
         }
         good += all;
@@ -241,20 +242,15 @@ constexpr int TS_THREADS = 256, TS_WAVES = TS_THREADS / 64; // one workgroup wal
 __global__ void __launch_bounds__(TS_THREADS) klt_tracking_select(int n_last, const cs_keypoint *__restrict__ last_keys, const uint8_t *__restrict__ eligible, int *__restrict__ sel,
                                                                   float *__restrict__ pts, int *__restrict__ counts) {
     __shared__ int s_wave[TS_WAVES];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     int n = 0;
     for (int start = 0; start < n_last; start += TS_THREADS) {
         const int i = start + tid;
         const bool keep = i < n_last && eligible[i] && last_keys[i].octave < 3;
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TS_WAVES; w++) { const int v = s_wave[w]; before += w < wave ? v : 0; all += v; }
-        __syncthreads();
+        int all;
+        const int rank = block_rank<TS_WAVES>(keep, s_wave, &all);
         if (keep) {
-            const int pos = n + before + __popcll(b & ((1ull << lane) - 1ull)); // < n_last
+            const int pos = n + rank; // < n_last
             sel[pos] = i; pts[2 * pos] = last_keys[i].x; pts[2 * pos + 1] = last_keys[i].y;
         }
         n += all;

@@ -45,9 +45,6 @@ __global__ void __launch_bounds__(256) lm_claim(int N1, int n_neigh, const int *
 }
 
 // ---- ComputeDistinctiveDescriptors
-__device__ __forceinline__ int hamming256(const unsigned long long *a, unsigned long long b0, unsigned long long b1, unsigned long long b2, unsigned long long b3) {
-    return __popcll(a[0] ^ b0) + __popcll(a[1] ^ b1) + __popcll(a[2] ^ b2) + __popcll(a[3] ^ b3);
-}
 // the smallest value v of 0..256 with at least `need` of the row's N distances <= v, i.e. sorted[need - 1]
 template <class Count> __device__ __forceinline__ int kth_by_counting(int need, Count count_le) {
     int lo = 0, hi = 256;

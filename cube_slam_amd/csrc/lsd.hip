@@ -172,8 +172,7 @@ __global__ void __launch_bounds__(1024) lsd_scan_blocks(const int4 *in, int n, i
     const int i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int v = 0;
     if (i < n) { const int4 q = in[i]; v = q.x + q.y + q.z + q.w; }
-    int sc = v;
-    for (int d = 1; d < 64; d <<= 1) { int t = __shfl_up(sc, d); if (lane >= d) sc += t; }
+    const int sc = wave_incl_scan(v, lane);
     if (lane == 63) ws[wave] = sc;
     __syncthreads();
     int base = 0;
@@ -232,7 +231,7 @@ template <bool PIX> __global__ void __launch_bounds__(EMIT_COLS) lsd_emit(const 
     int n_def = 0;
 #pragma unroll
     for (int r = 0; r < EMIT_ROWS; r++) {
-        int rank = __popcll(m[r] & ((1ull << ln) - 1)), cnt = 0;
+        int rank = wave_rank(m[r], ln), cnt = 0;
         for (int i = 0; i < NW; i++) { if (i < wv) rank += wc[r][i]; cnt += wc[r][i]; }
         if ((m[r] >> ln) & 1) s_list[n_def + rank] = tid | r << 8 | rank << 10;
         n_def += cnt;
@@ -270,7 +269,7 @@ template <bool PIX> __global__ void __launch_bounds__(EMIT_COLS) lsd_emit(const 
             int at = 0;
             if (ln == 0 && need) at = atomicAdd(&n_need, __popcll(need));
             at = __shfl(at, 0);
-            if (on && !alone) s_need[at + __popcll(need & ((1ull << ln) - 1))] = e;
+            if (on && !alone) s_need[at + wave_rank(need, ln)] = e;
         } else if (on) {
             const float pc = glibc_sincosf::cosf_(float(a)), ps = glibc_sincosf::sinf_(float(a));
             c_deg[pos] = d;

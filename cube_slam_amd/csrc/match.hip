@@ -238,11 +238,6 @@ template <int MODE> __global__ void __launch_bounds__(256) match_project_map(int
     }
 }
 
-__device__ __forceinline__ int hamming256(const unsigned long long *a, unsigned long long b0, unsigned long long b1, unsigned long long b2,
-                                          unsigned long long b3) {
-    return __popcll(a[0] ^ b0) + __popcll(a[1] ^ b1) + __popcll(a[2] ^ b2) + __popcll(a[3] ^ b3);
-}
-
 // GetFeaturesInArea (Frame.cc:404-459) for every query + the candidates' distances, in ONE pass: a wave walks its query's window twice -- it counts, takes a slice of the
 // candidate arena from a global cursor, and fills the slice in the reference's candidate order (ix outer, iy inner, cell lists ascending).  Which slice a query gets depends
 // on the atomics' order and on nothing else: cstart / ccount address it, and nothing reads the arena in another way.  A slice that would end past `cap` is not written and
@@ -303,8 +298,7 @@ template <bool STEREO> __global__ void __launch_bounds__(256) match_candidates(F
             if (k < ncell) { int c = (nMinCellX + k / ny) * GRID_ROWS + nMinCellY + k % ny; b = cell_start[c]; e = cell_start[c + 1]; }
             int mine = 0;
             for (int p = b; p < e; p++) mine += passes(recs[p]);
-            int inc = mine;
-            for (int off = 1; off < MC_G; off <<= 1) { int t = __shfl_up(inc, off, MC_G); if (lane >= off) inc += t; }
+            const int inc = wave_incl_scan<MC_G>(mine, lane);
             if (fill && mine) {
                 long o = base + tot + inc - mine;
                 for (int p = b; p < e; p++) {

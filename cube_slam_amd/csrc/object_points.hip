@@ -27,22 +27,19 @@ __global__ void __launch_bounds__(256) dyn_triangulate(int n_points, const int *
 }
 
 // ---- object depth
-// the frame's key points that satisfy pred, in index order: emit(position, index) -> their number (every thread gets it).  256 threads.
+// the frame's key points that satisfy pred, in index order: emit(position, index) -> their number (every thread gets it).  256 threads.  What emit stored is
+// readable by the whole workgroup behind the call.
 template <class Pred, class Emit> __device__ __forceinline__ int od_compact(int N, int *s_wave, Pred pred, Emit emit) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int running = 0;
     for (int base = 0; base < N; base += 256) {
-        const int i = base + tid;
+        const int i = base + threadIdx.x;
         const bool flag = i < N && pred(i);
-        const unsigned long long b = __ballot(flag);
-        if (lane == 0) s_wave[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 4; w++) { const int c = s_wave[w]; total += c; if (w < wave) before += c; }
-        if (flag) emit(running + before + __popcll(b & ((1ull << lane) - 1ull)), i);
+        int total;
+        const int rank = block_rank<4>(flag, s_wave, &total);
+        if (flag) emit(running + rank, i);
         running += total;
-        __syncthreads();
     }
+    __syncthreads();
     return running;
 }
 

@@ -167,7 +167,6 @@ __global__ void __launch_bounds__(256) orb_fast_score(Pyr P, const uint8_t *pyr,
     static_assert(TH == 16, "four rows per wave");
     unsigned long long cm[4];
     const int x = tx0 + lx;
-    const unsigned long long lt = (1ull << lx) - 1;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int ly = wv + 4 * r, y = ty0 + ly;
@@ -190,7 +189,7 @@ __global__ void __launch_bounds__(256) orb_fast_score(Pyr P, const uint8_t *pyr,
         const int off[4] = {base, base + c0, base + c0 + c1, base + c0 + c1 + c2};
 #pragma unroll
         for (int r = 0; r < 4; r++)
-            if ((cm[r] >> lx) & 1ull) s_list[off[r] + __popcll(cm[r] & lt)] = (unsigned short)((wv + 4 * r) << 8 | lx);
+            if ((cm[r] >> lx) & 1ull) s_list[off[r] + wave_rank(cm[r], lx)] = (unsigned short)((wv + 4 * r) << 8 | lx);
     }
     __syncthreads();
     const int n = s_n;
@@ -260,9 +259,7 @@ __global__ void __launch_bounds__(64 * CELLS_PER_WG) orb_cells(Pyr P, const uint
         const int nch = (aw * ah + 63) >> 6;
         unsigned long long my = lane < nch ? cell_mask[(long)cell * CELL_MASK_WORDS + lane] : 0ull;
         const int cnt = __popcll(my);
-        int incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; } // (chunks live in lanes 0 .. 27)
+        const int incl = wave_incl_scan<32>(cnt, lane & 31); // (chunks live in lanes 0 .. 27)
         long o = (long)cell_base[cell] + incl - cnt;
         while (my) {
             const int b = __ffsll((long long)my) - 1;
@@ -334,7 +331,7 @@ __global__ void __launch_bounds__(64 * CELLS_PER_WG) orb_cells(Pyr P, const uint
             unsigned long long m = __ballot(keep);
             if (lane == (p0 >> 6)) my_mask = m; // chunk c's survivors in lane c (the second attempt overwrites the first)
             if (pass == 1 && keep) {
-                long o = (long)base + total + __popcll(m & ((1ull << lane) - 1));
+                long o = (long)base + total + wave_rank(m, lane);
                 cand[o * 3 + 0] = (float)(ax0 + lx - 1 - MINB); // view column + j*wCell  (:821-826)
                 cand[o * 3 + 1] = (float)(ay0 + ly - 1 - MINB);
                 cand[o * 3 + 2] = (float)sc;
@@ -356,8 +353,7 @@ __global__ void __launch_bounds__(64) orb_scan_cells(Pyr P, const int *cell_coun
     int run = 0;
     for (int b = 0; b < n; b += 64) {
         int i = b + lane;
-        int v = i < n ? (cell_count[c0 + i] & 0xffffff) : 0, inc = v;
-        for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+        const int v = i < n ? (cell_count[c0 + i] & 0xffffff) : 0, inc = wave_incl_scan(v, lane);
         if (i < n) cell_base[c0 + i] = run + inc - v;
         run += __shfl(inc, 63);
     }
@@ -369,8 +365,7 @@ __global__ void __launch_bounds__(64) orb_scan_levels(int n, const int *level_to
     int run = 0;
     for (int b = 0; b < n; b += 64) {
         int i = b + lane;
-        int v = i < n ? level_total[i] : 0, inc = v;
-        for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+        const int v = i < n ? level_total[i] : 0, inc = wave_incl_scan(v, lane);
         if (i < n) level_base[i] = run + inc - v;
         run += __shfl(inc, 63);
     }
@@ -646,7 +641,7 @@ template <class F> __device__ __forceinline__ void qt_wave_partition(int *perm, 
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const unsigned long long m = __ballot(q == k);
-            if (q == k) tmp[pos[k] + __popcll(m & ((1ull << lane) - 1))] = v;
+            if (q == k) tmp[pos[k] + wave_rank(m, lane)] = v;
             pos[k] += __popcll(m);
         }
     }
@@ -724,26 +719,17 @@ __global__ void __launch_bounds__(256) orb_quadtree(QtParams Q, const int *level
         const int prev_size = n_list;
         // ---- a. expandable nodes (more than one point) keep list order in Elist; the others go to the tail of the new list later
         //      ordered compaction by the whole workgroup
-        int nE = 0, nKeepBefore = 0;
-        {
-            int baseE = 0;
-            for (int i0 = 0; i0 < n_list; i0 += 256) {
-                const int i = i0 + tid;
-                int id = -1; bool ex = false;
-                if (i < n_list) { id = list[i]; const int4 nd = nodes[id]; ex = (nd.w - nd.z) > 1; }
-                const unsigned long long m = __ballot(ex);
-                if (lane == 0) s_w[wave] = __popcll(m);
-                __syncthreads();
-                int wb = 0;
-                for (int w = 0; w < wave; w++) wb += s_w[w];
-                const int tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-                if (ex) Elist[baseE + wb + __popcll(m & ((1ull << lane) - 1))] = (short)id;
-                baseE += tot;
-                __syncthreads();
-            }
-            nE = baseE;
-            (void)nKeepBefore;
+        int nE = 0;
+        for (int i0 = 0; i0 < n_list; i0 += 256) {
+            const int i = i0 + tid;
+            int id = -1; bool ex = false;
+            if (i < n_list) { id = list[i]; const int4 nd = nodes[id]; ex = (nd.w - nd.z) > 1; }
+            int tot;
+            const int r = block_rank<4>(ex, s_w, &tot);
+            if (ex) Elist[nE + r] = (short)id;
+            nE += tot;
         }
+        __syncthreads(); // Elist is read by other waves than wrote it
         if (nE >= CAPV) { overflow = true; break; }
         // ---- b. split the points of every expandable node (one wave per node), child sizes packed 4 x 16 bit
         for (int e = wave; e < nE; e += 4) {
@@ -764,8 +750,7 @@ __global__ void __launch_bounds__(256) orb_quadtree(QtParams Q, const int *level
                 const int e = e0 + lane;
                 int k = 0, v = 0;
                 if (e < nE) { const unsigned long long c = cnt64[e]; for (int q = 0; q < 4; q++) { const int s = (int)((c >> (16 * q)) & 0xffff); k += s > 0; v += s > 1; } }
-                int ik = k, iv = v;
-                for (int d = 1; d < 64; d <<= 1) { const int a = __shfl_up(ik, d), b2 = __shfl_up(iv, d); if (lane >= d) { ik += a; iv += b2; } }
+                const int ik = wave_incl_scan(k, lane), iv = wave_incl_scan(v, lane);
                 if (e < nE) { P[e] = runK + ik - k; Pv[e] = runV + iv - v; }
                 runK += __shfl(ik, 63); runV += __shfl(iv, 63);
             }
@@ -803,15 +788,10 @@ __global__ void __launch_bounds__(256) orb_quadtree(QtParams Q, const int *level
                 const int i = i0 + tid;
                 int id = -1; bool kp = false;
                 if (i < n_list) { id = list[i]; const int4 nd = nodes[id]; kp = (nd.w - nd.z) <= 1; }
-                const unsigned long long m = __ballot(kp);
-                if (lane == 0) s_w[wave] = __popcll(m);
-                __syncthreads();
-                int wb = 0;
-                for (int w = 0; w < wave; w++) wb += s_w[w];
-                const int tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-                if (kp) nlist[baseK + wb + __popcll(m & ((1ull << lane) - 1))] = (short)id;
+                int tot;
+                const int r = block_rank<4>(kp, s_w, &tot);
+                if (kp) nlist[baseK + r] = (short)id;
                 baseK += tot;
-                __syncthreads();
             }
         }
         __threadfence_block();
@@ -879,7 +859,7 @@ __global__ void __launch_bounds__(256) orb_quadtree(QtParams Q, const int *level
                         int id = -1; bool al = false;
                         if (k >= 0) { id = front[k]; al = !((dead[id >> 5] >> (id & 31)) & 1u); }
                         const unsigned long long mm = __ballot(al);
-                        if (al) nlist[o + __popcll(mm & ((1ull << lane) - 1))] = (short)id;
+                        if (al) nlist[o + wave_rank(mm, lane)] = (short)id;
                         o += __popcll(mm);
                     }
                     for (int i0 = 0; i0 < n_list; i0 += 64) {
@@ -887,7 +867,7 @@ __global__ void __launch_bounds__(256) orb_quadtree(QtParams Q, const int *level
                         int id = -1; bool al = false;
                         if (i < n_list) { id = list[i]; al = !((dead[id >> 5] >> (id & 31)) & 1u); }
                         const unsigned long long mm = __ballot(al);
-                        if (al) nlist[o + __popcll(mm & ((1ull << lane) - 1))] = (short)id;
+                        if (al) nlist[o + wave_rank(mm, lane)] = (short)id;
                         o += __popcll(mm);
                     }
                 }

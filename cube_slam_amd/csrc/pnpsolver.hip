@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(64) pnp_refine(const int *hyp_problem, const P
         const bool in = i < N && ransac_mask_bit(m, i);
         const unsigned long long bal = __ballot(in);
         if (in) {
-            const int k = rank + __popcll(bal & ((1ull << lane) - 1ull));
+            const int k = rank + wave_rank(bal, lane);
             const PnpCorr c = C[i];
             w.pws[3 * (size_t)k] = c.X[0]; w.pws[3 * (size_t)k + 1] = c.X[1]; w.pws[3 * (size_t)k + 2] = c.X[2];
             w.us[2 * (size_t)k] = c.u[0]; w.us[2 * (size_t)k + 1] = c.u[1];

@@ -89,20 +89,6 @@ __global__ void __launch_bounds__(256) rgbd_gather(GatherP P, const int *__restr
 
 struct CloseP { float cx, cy, invfx, invfy, th; int mode; };
 
-// The position of a flagged thread among the flagged threads of the workgroup, in thread order; *total = their number.  Two barriers; s_wave holds CP_WAVES ints.
-__device__ __forceinline__ int block_rank(bool flag, int *s_wave, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) s_wave[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < CP_WAVES; w++) { const int v = s_wave[w]; before += w < wave ? v : 0; all += v; }
-    __syncthreads();
-    *total = all;
-    return before + __popcll(b & ((1ull << lane) - 1ull));
-}
-
 // counts: n_valid, n_walked, n_new per frame.  order / new_idx / new_x3D: frame f's entries from first[f] (3 * first[f]) on.
 // (8 waves per SIMD: two workgroups fit a compute unit by LDS, 2 x 64 KB of 160, and at 64 registers or fewer they fit by registers too.)
 __global__ void __launch_bounds__(CP_THREADS, 8) rgbd_close_points(CloseP P, const int *__restrict__ first, const float *__restrict__ depth, const cs_keypoint *__restrict__ keysUn,
@@ -123,7 +109,7 @@ __global__ void __launch_bounds__(CP_THREADS, 8) rgbd_close_points(CloseP P, con
         const float z = i < n ? depth[b0 + i] : -1.0f;
         const bool valid = z > 0;
         int tot;
-        const int pos = block_rank(valid, s_wave, &tot);
+        const int pos = block_rank<CP_WAVES>(valid, s_wave, &tot);
         if (valid) {
             s_key[n_valid + pos] = P.mode == RGBD_CLOSE_ALL ? (unsigned long long)(uint32_t)i : rgbd_sort_key(z, i);
             close += !(z > P.th);
@@ -159,7 +145,7 @@ __global__ void __launch_bounds__(CP_THREADS, 8) rgbd_close_points(CloseP P, con
         const int i = t < n_walked ? (int)(uint32_t)s_key[t] : 0;
         const bool create = t < n_walked && (P.mode == RGBD_CLOSE_ALL || need_new[b0 + i] != 0);
         int tot;
-        const int pos = n_new + block_rank(create, s_wave, &tot);
+        const int pos = n_new + block_rank<CP_WAVES>(create, s_wave, &tot);
         if (create) {
             const cs_keypoint ku = keysUn[b0 + i];
             float x3D[3];

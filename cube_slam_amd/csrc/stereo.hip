@@ -102,7 +102,8 @@ __global__ void __launch_bounds__(256) stereo_match(StereoP P, const PairRec *__
         if (q.y <= vL && vL <= q.z && q.w >= lv - 1 && q.w <= lv + 1 && uR >= minU && uR <= maxU) {
             const unsigned long long *e = descR + (size_t)(pr.r0 + j) * 4;
             const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(e), b = *reinterpret_cast<const ulonglong2 *>(e + 2);
-            const int dist = __popcll(a.x ^ d0) + __popcll(a.y ^ d1) + __popcll(b.x ^ d2) + __popcll(b.y ^ d3);
+            const unsigned long long ab[4] = {a.x, a.y, b.x, b.y};
+            const int dist = hamming256(ab, d0, d1, d2, d3);
             const unsigned long long k = ((unsigned long long)dist << 32) | (unsigned)j;
             key = k < key ? k : key;
         }

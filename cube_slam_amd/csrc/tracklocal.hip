@@ -25,19 +25,6 @@ __global__ void __launch_bounds__(256) tracklocal_first(int total, const int *kf
     if (!skip[id]) atomicMin(&first[id], e);
 }
 
-// exclusive prefix of v over the 256 threads; *total: the workgroup's sum.  s_w: 4 ints, free again behind the call
-__device__ __forceinline__ int tl_scan256(int v, int *s_w, int *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < w; k++) base += s_w[k];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-    return base + inc - v;
-}
 // entry e is the first occurrence of a pushed point
 __device__ __forceinline__ bool tl_is_first(int e, int total, const int *kf_mp, int n_points, const int *first) {
     if (e >= total) return false;
@@ -51,7 +38,7 @@ __global__ void __launch_bounds__(256) tracklocal_count(int total, const int *kf
     int c = 0;
     for (int k = 0; k < TL_PER; k++) c += tl_is_first(e0 + k, total, kf_mp, n_points, first);
     int sum;
-    tl_scan256(c, s_w, &sum);
+    block_excl_scan<4>(c, s_w, &sum);
     if (threadIdx.x == 0) tile_count[blockIdx.x] = sum;
 }
 
@@ -63,7 +50,7 @@ __global__ void __launch_bounds__(256) tracklocal_bases(int n_tiles, const int *
         int c[TL_PER], mine = 0;
         for (int k = 0; k < TL_PER; k++) { c[k] = t + k < n_tiles ? tile_count[t + k] : 0; mine += c[k]; }
         int sum;
-        int run = carry + tl_scan256(mine, s_w, &sum);
+        int run = carry + block_excl_scan<4>(mine, s_w, &sum);
         for (int k = 0; k < TL_PER; k++) { if (t + k < n_tiles) tile_base[t + k] = run; run += c[k]; }
         carry += sum;
     }
@@ -77,7 +64,7 @@ __global__ void __launch_bounds__(256) tracklocal_emit(int total, const int *kf_
     int c = 0;
     for (int k = 0; k < TL_PER; k++) { f[k] = tl_is_first(e0 + k, total, kf_mp, n_points, first); c += f[k]; }
     int sum;
-    int o = tile_base[blockIdx.x] + tl_scan256(c, s_w, &sum); // (o + c <= the number of distinct pushed points <= the capacity of out)
+    int o = tile_base[blockIdx.x] + block_excl_scan<4>(c, s_w, &sum); // (o + c <= the number of distinct pushed points <= the capacity of out)
     for (int k = 0; k < TL_PER; k++) if (f[k]) out[o++] = kf_mp[e0 + k];
 }
 } // namespace

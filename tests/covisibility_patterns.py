@@ -239,6 +239,35 @@ def random_mpcull(seed):
     return dict(kind="mpcull", t=t, recent=recent, mp_found=m["found"], mp_visible=m["visible"], mp_first_kf_id=m["first"], current_kf_id=6, th_obs=(3, 2, 1)[seed])
 
 
+# ---- the seams of the workgroup-wide scans (block_excl_scan of csrc/common.h) under the three kernels that call them, over tests/compaction_seams.py ------------------------
+PER_THREAD = TILE // 256  # covis_vote: the consecutive counters of one thread
+
+
+def seam_vote_counters(n, fl):
+    """covis_vote: the counters of thread i (key frames PER_THREAD i ...) hold a voter where fl[i] is set, at a place in the thread's stretch that moves with i; every
+    third voter has weight 2 (th = 2: some reach it, some do not).  The query is the last key frame."""
+    voters = [PER_THREAD * int(i) + int(i) % PER_THREAD for i in np.flatnonzero(fl)]
+    q = PER_THREAD * n
+    return vote_case(q + 1, [seen_by([q] + voters), seen_by([q] + voters[::3])], [q], [[0, 1]], th=2)
+
+
+def seam_vote_queries(n, fl):
+    """covis_offsets: n queries; the flagged ones have a counter of three key frames, one of them at the threshold, the others none."""
+    pts = [seen_by([0, 1, 2, 3]), seen_by([0, 2])]
+    return vote_case(4, pts, [0] * n, [[0, 1] if f else [] for f in fl], th=2)
+
+
+def seam_cull(cases):
+    """covis_cull_eval: key frame i's slots follow the flags of case i -- a flagged slot holds a point of its own that three key frames outside the list see as well, the
+    others are empty -- so nMPs and nRedundant are sums over threads of which the flagged ones hold 1."""
+    n_local = len(cases)
+    pts, slots = [], []
+    for kf, (_, _, fl) in enumerate(cases):
+        slots.append([len(pts) + int(fl[:j].sum()) if f else -1 for j, f in enumerate(fl)])
+        pts += [seen_by([kf, n_local, n_local + 1, n_local + 2]) for _ in range(int(fl.sum()))]
+    return cull_case(n_local + 3, pts, list(range(n_local)), slots)
+
+
 CASES = {f.__name__: f for f in (vote_threshold, vote_fallback_tie, vote_sort_ties, vote_self_and_skips, vote_double_slot, vote_empty, vote_tile_seam, cull_boundary,
                                  cull_level_seam, cull_depth_and_dynamic, cull_erase_unmakes, cull_erase_makes, cull_not_erase, cull_stereo_decrement, cull_id0, mpcull_cases)}
 for _seed in RANDOM_SIZES:

@@ -303,6 +303,19 @@ def od_batch():
     return od_case([_f_two_in_cell(), none, _f_earlier_nonqualifying(), empty, _f_outside_grid(), _f_more_than_80(), _f_walk_past()])
 
 
+def od_compaction_seams():
+    """od_frame's two ordered compactions (block_rank of csrc/common.h, passes of 256 threads) over tests/compaction_seams.py, every key point in a cell of its own,
+    two frames per case.  In the first the pattern is the object id (-1 where it is not set) and the cuboid lies in front of the camera: the candidates follow the
+    pattern and the first-frame mode's second compaction keeps them all.  In the second every key point is a candidate and the pattern chooses between cuboid 0
+    (depth 5) and cuboid 1 (depth -1): the first-frame mode's second compaction follows the pattern."""
+    from tests import compaction_seams as cs
+    fr = []
+    for n, _, fl in cs.cases():
+        fr.append(od_frame(spread(n, obj=lambda j: 0 if fl[j] else -1), [5.0, -1.0], DRAWS * 2))
+        fr.append(od_frame(spread(n, obj=lambda j: 0 if fl[j] else 1), [5.0, -1.0], DRAWS * 2))
+    return od_case(fr)
+
+
 def off_integer_totals(limit=8192):
     return [t for t in range(0, limit + 1, 10) if float(t) * 0.30 != float(3 * t // 10)]
 

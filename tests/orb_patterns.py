@@ -132,3 +132,74 @@ def two_class_values(strong, bg, iniTh, minTh):
     weak = (iniTh + minTh) // 2
     assert minTh < weak < iniTh and bg + 3 * iniTh <= 255
     return np.where(strong, bg + 3 * iniTh, bg + weak).astype(np.uint8)
+
+
+# ---- the first phase of DistributeOctTree as lists, and dots that bring one of its passes to a wanted length and pattern -------------------------------------------------
+def quadtree_first_phase(cand, fw, fh):
+    """DistributeOctTree's first phase (ORBextractor.cc:588-675) on one root of fw x fh over candidate coordinates (pixel - MINB), with a quota no pass reaches: per
+    pass the list as [(box, points in the node)], until the list stops growing.  A node with more than one point is split (DivideNode, :483-538: halves rounded up)
+    and its non-empty children are pushed to the front in the order they are made; the others keep their place."""
+    nodes = [((0, 0, fw, fh), [tuple(c) for c in cand])]
+    passes = []
+    while True:
+        passes.append(nodes)
+        front, kept = [], []
+        for box, pts in nodes:
+            if len(pts) <= 1:
+                kept.append((box, pts))
+                continue
+            x0, y0, x1, y1 = box
+            mx, my = x0 + int(math.ceil((x1 - x0) / 2)), y0 + int(math.ceil((y1 - y0) / 2))
+            boxes = [(x0, y0, mx, my), (mx, y0, x1, my), (x0, my, mx, y1), (mx, my, x1, y1)]
+            ch = [[], [], [], []]
+            for x, y in pts:
+                ch[(0 if x < mx else 1) + (0 if y < my else 2)].append((x, y))
+            front += [(b, c) for b, c in zip(boxes, ch) if c]
+        new = front[::-1] + kept
+        if len(new) == len(nodes):
+            return passes
+        nodes = new
+
+
+def quadtree_seam_dots(W, H, flags):
+    """Dots (pixels) of a W x H frame with one level-0 root whose sides divide by 32, for a pass of the first phase whose list has len(flags) nodes, expandable
+    exactly where flags is set.  The nodes are sibling groups of four (one of three and one of two where the length asks for it) under parents of one depth; the
+    parents are dealt to the quadrants of every depth in turn.  So every node above them holds two points or more, the list grows with every pass and nothing is
+    kept at its tail, and the pass below the parents lists their children and nothing else, in an order that does not depend on which of them hold two dots (in
+    different quadrants) and which one.  -> (dots, the passes of quadtree_first_phase, the index of that pass).  The order itself comes from the restated first
+    phase, and the result is checked against flags."""
+    fw, fh = W - 2 * EDGE + 6, H - 2 * EDGE + 6
+    assert level0_roots(W, H)[0] == 1 and fw % 32 == 0 and fh % 32 == 0
+    flags = [bool(f) for f in flags]
+    S = len(flags)
+    groups = [1] if S == 1 else [4] * (S // 4 - (S % 4 == 1)) + {0: [], 1: [3, 2], 2: [2], 3: [3]}[S % 4]
+    assert sum(groups) == S and S >= 1
+    e = 0  # depth of the parents: the first with room for them
+    while 4 ** e < len(groups):
+        e += 1
+    D = e + (S > 1)
+    assert D <= 5
+    bw, bh = fw >> D, fh >> D
+
+    def parent(m):  # the base-4 digits of m, lowest first, choose the quadrant from the root down
+        i = j = 0
+        for d in range(e):
+            q = (m >> (2 * d)) & 3
+            i, j = 2 * i + (q & 1), 2 * j + (q >> 1)
+        return i, j
+    cells = [(0, 0)] if S == 1 else [(2 * i + (q & 1), 2 * j + (q >> 1)) for (i, j), g in zip(map(parent, range(len(groups))), groups) for q in range(g)]
+    clamp = lambda x, y: (min(max(x, MARGIN - MINB), fw - 1 - (MARGIN - MINB)), min(max(y, MARGIN - MINB), fh - 1 - (MARGIN - MINB)))
+    first = [clamp(i * bw + 3, j * bh + 3) for i, j in cells]
+    second = [clamp(i * bw + bw - 5, j * bh + bh - 4) for i, j in cells]
+    two = [True] * S
+    for _ in range(2):
+        cand = first + [s for s, t in zip(second, two) if t]
+        passes = quadtree_first_phase(cand, fw, fh)
+        where = {pt: n for n, (_, pts) in enumerate(passes[D]) for pt in pts}
+        assert len(passes[D]) == S and sorted(where[a] for a in first) == list(range(S))
+        if [len(p) > 1 for _, p in passes[D]] == flags:
+            dots = np.array(cand, np.int64).reshape(-1, 2) + MINB
+            assert len(dots) < 2 or check_isolated(dots)
+            return dots, passes, D
+        two = [flags[where[a]] for a in first]
+    raise AssertionError("no dot set for %d nodes" % S)

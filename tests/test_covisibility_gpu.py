@@ -32,6 +32,31 @@ def test_mpcull(ctx, name):
     assert got.dtype == np.uint8 and np.array_equal(got, P.expected(name))
 
 
+def _vote_want(c):
+    return P.flat_vote(R.update_connections(c["t"], c["query_kf"], c["kf_off"], c["kf_mp"], 1, c["th"]))
+
+
+def test_scan_seams(ctx):
+    """The workgroup-wide scans under covis_vote (over the threads' counters), covis_offsets (over the queries) and covis_cull_eval (its two sums over the slots) at the
+    seams of a wave and of a pass of 256 threads, nothing and everything flagged: tests/compaction_seams.py through P.seam_*."""
+    from tests import compaction_seams as cs
+    cases = cs.cases()
+    for n, pattern, fl in cases:
+        c = P.seam_vote_counters(n, fl)
+        got = P.run_vote(ctx, c, 1)
+        P.assert_equal(got, _vote_want(c), P.VOTE_KEYS, "counters %d %s" % (n, pattern))
+        assert got["cnt_kf"].tolist() == [P.PER_THREAD * int(i) + int(i) % P.PER_THREAD for i in np.flatnonzero(fl)]
+        c = P.seam_vote_queries(n, fl)
+        got = P.run_vote(ctx, c, 1)
+        P.assert_equal(got, _vote_want(c), P.VOTE_KEYS, "queries %d %s" % (n, pattern))
+        assert np.diff(got["cnt_off"]).tolist() == [3 if f else 0 for f in fl] and np.diff(got["ord_off"]).tolist() == [1 if f else 0 for f in fl]
+    c = P.seam_cull(cases)
+    got = P.run_cull(ctx, c)
+    want = R.keyframe_culling(c["t"], c["local_kf"], c["kf_off"], c["kf_mp"], c["slot_octave"], c["slot_depth"], c["kf_th_depth"], c["monocular"], c["kf_flags"], c["th_obs"])
+    P.assert_equal(got, want, P.CULL_KEYS, "cull")
+    assert got["n_mps"].tolist() == got["n_redundant"].tolist() == [int(fl.sum()) for _, _, fl in cases]
+
+
 def test_c_abi_directly(ctx):
     """The three entry points with nothing of the Python mirror between: buffers sized by hand, canaries behind every output."""
     from cube_slam_amd._lib import lib, ptr

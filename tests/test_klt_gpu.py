@@ -232,6 +232,34 @@ def test_selection_kernels_past_one_wave_and_one_pass(ctx):
     assert kp.same_tracking(_tracking_device(ctx, big, big["keys_static"], big["had_map_point"]), big["want"])
 
 
+def test_tracking_selection_compaction_seams(ctx):
+    """klt_tracking_select's ordered compaction (block_rank, passes of 256 threads) over tests/compaction_seams.py, on the large case's frames and current key points:
+    a last-frame key point is flagged when it is eligible and its octave is below 3 -- the others fail one test or the other in turn.  lastptsinds are the flagged
+    indices in index order, and the whole answer is the host form's, which tests/test_klt_mirrors.py holds to the restatement."""
+    from cube_slam_amd import SearchByTracking
+    from cube_slam_amd.matcher import ORBmatcher
+    from tests import compaction_seams as cs
+    big = kp.tracking_large_case()
+    lk, ck = kp.tracking_keys(big)
+    m = ORBmatcher(0.9, True, ctx=ctx, max_keypoints=1024, max_queries=1024, max_candidates=4096)
+    t = KLTTracker(2, 96, 64, max(cs.SIZES), ctx=ctx)
+    try:
+        m.set_frame(ck, np.zeros((len(ck), 32), np.uint8), big["bounds"])
+        t.set_frames(big["frames"])
+        for n, pattern, fl in cs.cases():
+            odd = np.arange(n) % 2 == 1
+            keys = lk[:n].copy()
+            keys["octave"] = np.where(fl | odd, 0, 3)
+            eligible = (fl | ~odd).astype(np.uint8)
+            args = (keys, eligible, big["object_id"][:n], big["numobject"], kp.TH, kp.SCALE_FACTORS)
+            got = SearchByTracking(None, None, *args, None, None, big["keys_static"], big["had_map_point"], matcher=m, tracker=t)
+            host = SearchByTracking(big["frames"][0], big["frames"][1], *args, ck, big["bounds"], big["keys_static"], big["had_map_point"])
+            assert np.array_equal(got["lastptsinds"], np.flatnonzero(fl)) and kp.same_tracking(got, host), (n, pattern)
+    finally:
+        t.close()
+        m.close()
+
+
 def test_search_by_tracking_needs_a_frame_in_the_matcher(ctx):
     from cube_slam_amd import SearchByTracking
     from cube_slam_amd.matcher import ORBmatcher

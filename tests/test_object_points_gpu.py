@@ -27,6 +27,20 @@ def test_object_depth(ctx, name, mode):
     P.assert_equal(got, P.expected(name, mode), P.OD_KEYS, "%s mode %d against the restatement" % (name, mode))
 
 
+@pytest.mark.parametrize("mode", P.MODES)
+def test_object_depth_compaction_seams(ctx, mode):
+    """Both ordered compactions of od_frame at the seams of a wave and of a pass of 256 threads, nothing and everything flagged (P.od_compaction_seams)."""
+    from tests import compaction_seams as cs
+    c = P.case("od_compaction_seams")
+    got = P.run_od(ctx, c, mode)
+    P.assert_equal(got, P.run_od(None, c, mode), P.OD_KEYS, "mode %d against the host form" % mode)
+    P.assert_equal(got, P.expected("od_compaction_seams", mode), P.OD_KEYS, "mode %d against the restatement" % mode)
+    want_n = [k for n, _, fl in cs.cases() for k in (int(fl.sum()), n)]
+    assert np.asarray(got["n_candidates"]).tolist() == want_n
+    if mode == R.FIRST_FRAME:
+        assert np.diff(got["new_first"]).tolist() == [int(fl.sum()) for _, _, fl in cs.cases() for _ in range(2)]
+
+
 def test_c_abi_directly(ctx):
     """Both entry points with nothing of the Python mirror between: buffers sized by hand, canaries behind every output."""
     from cube_slam_amd._lib import lib, ptr

@@ -228,6 +228,30 @@ def test_tied_responses_and_node_sizes(ctx, oracle, monkeypatch, name, W, H):
     monkeypatch.delenv("CUBESLAM_ORB_QUADTREE", raising=False)
 
 
+def test_quadtree_compactions_at_wave_and_pass_seams(ctx, oracle):
+    """orb_quadtree's two ordered compactions (block_rank, passes of 256 threads) run over the node list of every pass of the first phase: the expandable nodes, and
+    behind the children the others.  pat.quadtree_seam_dots brings one pass to each length and pattern of tests/compaction_seams.py (a list of no nodes does not
+    occur: a level without candidates ends the kernel ahead of them), so the first compaction sees the pattern and the second its complement.  Preconditions: the
+    oracle's level-0 candidates are the dots; the quota stays above every pass's length + 3 x its expandable nodes, so the first phase is the restated one and the
+    second never starts; the device quadtree ran."""
+    from tests import compaction_seams as cs
+    W, H, nfeat = 640, 480, 10000
+    ora = oracle.ORBextractor(nfeat, 1.2, 8, INI_TH, MIN_TH)
+    ext = ORBextractor(nfeat, 1.2, 8, INI_TH, MIN_TH, W, H, ctx=ctx)
+    for n, pattern, fl in cs.cases(cs.SIZES[1:]):
+        p, passes, k = pat.quadtree_seam_dots(W, H, fl)
+        assert [len(q) > 1 for _, q in passes[k]] == fl.tolist()
+        ref = ora(pat.dots(W, H, p, BG, BG + 3 * INI_TH))
+        assert _assert_level0_candidates(ora, p, [3 * INI_TH - 1]) == len(p)
+        q0 = int(ora.features_per_level()[0])
+        assert max(len(s) + 3 * sum(len(q) > 1 for _, q in s) for s in passes) < q0 and _device_quadtree_expected(ora.features_per_level())
+        assert (ref[0]["octave"] == 0).sum() == len(passes[-1])
+        got, n_dev, n_host = _counted(ctx, lambda: ext(pat.dots(W, H, p, BG, BG + 3 * INI_TH)))
+        assert (n_dev, n_host) == (1, 0)
+        _assert_equal(got, ref, "%d nodes, %s" % (n, pattern))
+    ext.close()
+
+
 # ------------------------------------------------------------------------------------------------ per-cell threshold fallback
 def test_threshold_fallback_is_decided_cell_by_cell(ctx, oracle):
     """Strong and weak dots, sometimes in one cell.  Preconditions from ora.candidates(0): some weak dots are candidates, all of them in cells without a strong dot;

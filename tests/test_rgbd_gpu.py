@@ -232,6 +232,24 @@ def test_close_points_special_thresholds_and_the_largest_frame(ctx):
     t.close(); a.close()
 
 
+def test_close_points_compaction_seams(ctx):
+    """Both ordered compactions of rgbd_close_points (block_rank over the 16 waves of a pass of 1 024 threads) over tests/compaction_seams.py, and at the pass itself
+    (1 023, 1 024, 1 025).  The first compaction's flag is z > 0: mode ALL with the pattern in the depths, where the second one takes every valid point.  The second
+    one's flag is need_new over the walked prefix: equal depths under a NaN threshold, which is never exceeded, so the walk is every point in index order."""
+    from tests import compaction_seams as cs
+    cases = cs.cases(cs.SIZES + [1023, 1024, 1025])
+    first = np.concatenate([[0], np.cumsum([n for n, _, _ in cases])]).astype(np.int32)
+    T, ku = rr.poses(len(cases)), rr.keypoints(78, first[-1], 640, 480)
+    flag = np.concatenate([fl for _, _, fl in cases])
+    ones = np.ones(first[-1], f32)
+    for mode, depth, need, th in ((CS_CLOSE_POINTS_ALL, np.where(flag, f32(1.5), f32(0)).astype(f32), None, rr.TH_DEPTH), (CS_CLOSE_POINTS_NEAREST, ones, flag.astype(np.uint8), float("nan"))):
+        got = ClosePoints(depth, ku, need, T, rr.K4, th, mode, first=first, ctx=ctx)
+        for f, (n, pattern, fl) in enumerate(cases):
+            s = slice(first[f], first[f + 1])
+            _same_close(got[f], rr.close_points(depth[s], ku[s], None if need is None else need[s], T[f], rr.K4, th, mode), (n, pattern, mode))
+            assert np.array_equal(got[f]["new_idx"], np.flatnonzero(fl)) and got[f]["n_valid"] == (int(fl.sum()) if mode == CS_CLOSE_POINTS_ALL else n)
+
+
 def test_errors(ctx):
     lib = _lib.lib()
     W, H = 640, 480

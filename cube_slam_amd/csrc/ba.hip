@@ -17,11 +17,13 @@
 //   ba_schur_slots    wave per block of the reduced camera system: Hpp - sum_l B D^-1 B^T (lane = contributing landmark)
 //   ba_schur_b        wave per pose block: b_p - sum B D^-1 b_l
 //   (all-reduce)      one sum over [Schur blocks | b | scalars] across ranks when landmarks are sharded (RCCL via callback)
-//   ba_band_*         block-band Cholesky (reverse Cuthill-McKee order from the host) + two triangular sweeps, one workgroup
+//   ba_band_*         block-band Cholesky (reverse Cuthill-McKee order from the host) + two triangular sweeps, one workgroup (ba_band.h)
 //   ba_backsub        thread per landmark: x_l = D^-1 (b_l - B^T x_p)
 //   ba_update         oplus per vertex (cameras: exp(dx) * T; cuboids: T * exp(dx) with the fix-roll-pitch / height / scale flags)
+// The graph plan (index mapping, Schur slots, band plan, ordering, symbolic factor) is host code in ba_plan.h; cs_ba_create checks, plans and uploads.
 #include "common.h"
 #include "ba_cr.h"
+#include "ba_plan.h"
 #include "lm_schedule.h"
 #include "se3_math.h"
 
@@ -29,8 +31,7 @@
 #include <cfloat>
 #include <cmath>
 #include <limits>
-#include <map>
-#include <queue>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -506,457 +507,7 @@ __global__ void __launch_bounds__(256) ba_band_both(int nb_a, int n_targets, con
     if (bid < nb_a) ba_band_assemble_body(n_targets, tgt_slot, tgt_tr, ct_off, ct_list, S, cubD, band, bid);
     else ba_band_rhs_body(C, cr_off, cr_list, S, bs, cubg, rhs, bid - nb_a);
 }
-// ---- block-band Cholesky of the camera system.  A: C columns x (Bc+1) blocks (block d of column j = block (j+d, j), row-major 6x6).
-// The elimination is a serial chain over the columns (each step: 6x6 pivot, Bc panel blocks, Bc(Bc+1)/2 trailing blocks, all in
-// LDS), so it is run from BOTH ends at once ("twisted" factorisation): workgroup 0 eliminates columns 0, 1, 2, ... of A,
-// workgroup 1 eliminates C-1, C-2, ... (the same band algorithm on the index-reversed matrix, whose columns are gathered from A
-// with a transpose), each stopping before a middle group of R = Bc cameras.  Neither side creates fill outside the band, the
-// middle group receives the Schur updates of both sides (ba_band_mid adds them, factors the dense 6R x 6R block and solves it),
-// and the two back substitutions again run concurrently.  Half the chain length, three launches instead of one.
-// A "side" sees the principal submatrix of its ne eliminated columns plus the R tail (middle) columns, in its own (local) order.
-struct BandView {
-    const double *A, *rhs; // the assembled band and right-hand side (original order)
-    int C, Bc, n, ne, rev; // n = ne + tail columns; rev: local column j is original column C-1-j
-    int lf_base;           // first column of this side in the factor storage Lf / ybuf
-};
-__device__ __forceinline__ double band_a(const BandView &V, int cn, int i) { // element i (block d = i/36) of local column cn
-    const int d = i / 36;
-    if (cn + d >= V.n) return 0.0; // rows outside the side's submatrix
-    if (!V.rev) return V.A[(long)cn * ((V.Bc + 1) * 36) + i];
-    if (cn >= V.ne) return 0.0;    // middle x middle blocks (and the middle right-hand side) are counted once, by the forward side
-    const int e = i - d * 36, r = e / 6, c = e - r * 6, o = V.C - 1 - cn;
-    return V.A[(long)(o - d) * ((V.Bc + 1) * 36) + d * 36 + c * 6 + r]; // reversed block (cn+d, cn) = A(o, o-d)^T ... stored in column o-d
-}
-__device__ __forceinline__ double band_b(const BandView &V, int cn, int t) {
-    if (cn >= V.n) return 0.0;
-    if (!V.rev) return V.rhs[(long)cn * 6 + t];
-    return cn < V.ne ? V.rhs[(long)(V.C - 1 - cn) * 6 + t] : 0.0;
-}
-// value of lane - n (DPP row_shr:n inside each row of 16 lanes; 0.0 where the row has no such lane)
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false), hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-constexpr int BAND_YB = 28; // doubles per column in ybuf: y_j (6), lower triangle of L_jj^-1 (21), pad
-struct BandLds { double *W, *bw, *yj, *Linv, *part; int *pair_d; };
-__device__ __forceinline__ BandLds band_lds(double *sh, int Bc) {
-    const int NB = Bc + 1, NS = Bc + 2, CS = NB * 36;
-    BandLds L;
-    L.W = sh; L.bw = L.W + (long)NS * CS; L.yj = L.bw + NS * 6; L.Linv = L.yj + 6; L.part = L.Linv + 6; // part: 64 doubles; the factor of the current diagonal block (36) and the lower triangle of its inverse (21)
-    L.pair_d = (int *)(L.part + 64); // pair -> (di << 8 | dk)
-    return L;
-}
-static size_t band_lds_bytes(int Bc) { return sizeof(double) * ((size_t)(Bc + 2) * (Bc + 1) * 36 + (size_t)(Bc + 2) * 6 + 6 + 6 + 64) + sizeof(int) * (size_t)std::max(1, Bc * (Bc + 1) / 2); }
-
-// Eliminates local columns 0..ne-1 (L to Lf, y_j and 1/diag to ybuf), forward solve fused.  LDS: a ring of Bc+2 columns (the extra
-// slot receives column j+Bc+1 while column j is processed) and the matching right-hand-side window.  On return the window holds
-// the updated tail columns ne..n-1.
-typedef double band_v4d __attribute__((ext_vector_type(4)));
-template <int NT> __device__ __forceinline__ bool band_factor(const BandView &V, const BandLds &S, double *Lf, double *ybuf) {
-    const int Bc = V.Bc, NB = Bc + 1, NS = Bc + 2, CS = NB * 36;
-    double *W = S.W, *bw = S.bw, *yj = S.yj;
-    int *pair_d = S.pair_d;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int pr = tid; pr < Bc * (Bc + 1) / 2; pr += NT) {
-        int di = (int)((sqrt(8.0 * pr + 1.0) - 1.0) * 0.5);
-        while (di * (di + 1) / 2 > pr) di--;
-        while ((di + 1) * (di + 2) / 2 <= pr) di++;
-        pair_d[pr] = ((di + 1) << 8) | (pr - di * (di + 1) / 2 + 1);
-    }
-    const int n0 = V.n < NB ? V.n : NB;
-    for (int i = tid; i < n0 * CS; i += NT) W[i] = band_a(V, i / CS, i % CS); // columns 0..n0-1 sit in slots 0..n0-1
-    for (int i = tid; i < n0 * 6; i += NT) bw[i] = band_b(V, i / 6, i % 6);
-    // prefetch addressing of this thread's (up to four) elements of a column, hoisted out of the chain: element i of local column cn
-    // lives at pk[u] + cn * cstep and exists while cn < plim[u]
-    long pk[4]; int plim[4];
-    const long cstep = V.rev ? -(long)CS : (long)CS;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int i = tid + u * NT, d = i / 36, e = i - d * 36, r = e / 6, c = e - r * 6;
-        plim[u] = i < CS ? (V.rev ? min(V.n - d, V.ne) : V.n - d) : 0;
-        pk[u] = V.rev ? (long)(V.C - 1 - d) * CS + d * 36 + c * 6 + r : (long)i;
-    }
-    // trailing update on the matrix cores (Bc <= 10): T -= P P^T with P = the nd*6 x 6 panel, as 16x16 tiles of v_mfma_f64_16x16x4_f64
-    // (lower tiles only, K = 6 padded to 8).  Every wave owns up to two tiles; where its operands and results live inside a column
-    // of the window does not depend on the column, so it is worked out once: offsets inside the column for the two A and two B
-    // operand values, and for the four results (block distance dk of the target column, offset inside it, first panel block di that
-    // must exist).  C/D layout of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 * reg.
-    const bool use_mfma = Bc <= 10;
-    int ta_off[2], tb_off[2], ta_di[2], tb_di[2], t_dk[2][4], t_in[2][4], t_di[2][4];
-    const int k0 = lane >> 4;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const int tl = wave >= 1 ? (wave - 1) + q * (NT / 64 - 1) : 99; // wave 0 owns the pivot and its bookkeeping, the other five the ten tiles
-        int ti = 0;
-        while ((ti + 1) * (ti + 2) / 2 <= tl) ti++;
-        const int tj = tl - ti * (ti + 1) / 2;
-        const bool on = use_mfma && tl < 10;
-        const int arow = ti * 16 + (lane & 15), bcol = tj * 16 + (lane & 15);
-        ta_off[q] = (1 + arow / 6) * 36 + (arow % 6) * 6 + k0; ta_di[q] = on ? arow / 6 + 1 : 99;
-        tb_off[q] = (1 + bcol / 6) * 36 + (bcol % 6) * 6 + k0; tb_di[q] = on ? bcol / 6 + 1 : 99;
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int row = ti * 16 + k0 + 4 * g, col = bcol, di = row / 6 + 1, dk = col / 6 + 1;
-            t_dk[q][g] = dk * CS; t_in[q][g] = (di - dk) * 36 + (row % 6) * 6 + col % 6; // slot distance in doubles, offset inside the column
-            t_di[q][g] = (on && col <= row) ? di : 99; // needs panel block di (and dk <= di)
-        }
-    }
-    const int NSCS = NS * CS;
-    const int p_off = (1 + lane / 6) * 36 + (lane % 6) * 6, p_dd = 1 + lane / 6, p_r = lane % 6; // panel row / right-hand-side row of this lane (wave-local index)
-    __syncthreads();
-#ifdef BAND_PROF
-    unsigned long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, p0_ = 0, p1_;
-#define BP(k) do { p1_ = __builtin_readcyclecounter(); pt_[k] += p1_ - p0_; p0_ = p1_; } while (0)
-    p0_ = __builtin_readcyclecounter();
-#else
-#define BP(k) do { } while (0)
-#endif
-    bool fail = false;
-    int sj = 0, sjcs = 0; // j % NS, and times CS
-    for (int j = 0; j < V.ne; j++) {
-        double *Wc = W + (long)sj * CS;
-        const int nd = (V.n - 1 - j) < Bc ? (V.n - 1 - j) : Bc;
-        const int cn = j + Bc + 1, scn = sj == 0 ? NS - 1 : sj - 1; // slot of column cn = (j + NS - 1) % NS
-        // next column: loads issued now, stored to the free LDS slot at the end of the step (global latency off the critical path)
-        double pf[4] = {0, 0, 0, 0}, pfb = 0;
-        if (cn < V.n) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) if (cn < plim[u]) pf[u] = V.A[pk[u] + cn * cstep];
-            if (tid < 6) pfb = band_b(V, cn, tid);
-        }
-        // L_jj = chol(A_jj), its inverse and y_j = L_jj^-1 b_j: every lane of WAVE 0 computes them in its own registers from LDS
-        // broadcasts (six v_rsq_f64 + two Newton steps, ~150 fused multiply-adds) and goes straight on to its panel rows, which
-        // with the explicit inverse are independent dot products instead of a 16-deep dependent chain -- no cross-lane traffic and no
-        // barrier between the pivot and the panel (a shuffle-based version on six lanes cost 0.86 us per column).  The other waves wait.
-        BP(0);
-        double Lr[6][6], Mi[6][6], invs[6], yv[6];
-        if (tid < 64) {
-#pragma unroll
-            for (int r = 0; r < 6; r++)
-#pragma unroll
-                for (int c = 0; c <= r; c++) Lr[r][c] = Wc[r * 6 + c];
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                double d = Lr[c][c];
-#pragma unroll
-                for (int t = 0; t < c; t++) d = __builtin_fma(-Lr[c][t], Lr[c][t], d);
-                if (!(d > 0)) { fail = true; d = 1; }
-                double inv = __builtin_amdgcn_rsq(d);
-                inv = inv * (1.5 - (0.5 * d) * (inv * inv));
-                inv = inv * (1.5 - (0.5 * d) * (inv * inv));
-                invs[c] = inv;
-                Lr[c][c] = d * inv;
-#pragma unroll
-                for (int r = c + 1; r < 6; r++) {
-                    double v = Lr[r][c];
-#pragma unroll
-                    for (int t = 0; t < c; t++) v = __builtin_fma(-Lr[r][t], Lr[c][t], v);
-                    Lr[r][c] = v * inv;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 6; c++) { // Mi = L_jj^-1 (lower triangular), column by column
-                Mi[c][c] = invs[c];
-#pragma unroll
-                for (int r = c + 1; r < 6; r++) {
-                    double v = 0;
-#pragma unroll
-                    for (int t = c; t < r; t++) v = __builtin_fma(Lr[r][t], Mi[t][c], v);
-                    Mi[r][c] = -invs[r] * v;
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 6; t++) { // y = L_jj^-1 b
-                double sacc = 0;
-#pragma unroll
-                for (int u = 0; u <= t; u++) sacc = __builtin_fma(Mi[t][u], bw[sj * 6 + u], sacc);
-                yv[t] = sacc;
-            }
-            BP(1);
-            for (int t = tid; t < nd * 6; t += 64) { // L_d = A_d L_jj^-T = A_d Mi^T, one block row per lane
-                double *blk = Wc + (t == tid ? p_off : (1 + t / 6) * 36 + (t % 6) * 6);
-                double a[6], row[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++) a[c] = blk[c];
-#pragma unroll
-                for (int c = 0; c < 6; c++) {
-                    double v = 0;
-#pragma unroll
-                    for (int q = 0; q <= c; q++) v = __builtin_fma(a[q], Mi[c][q], v);
-                    row[c] = v;
-                }
-#pragma unroll
-                for (int c = 0; c < 6; c++) blk[c] = row[c];
-            }
-            if (tid == 0) { // the other waves only need y_j before the barrier
-#pragma unroll
-                for (int r = 0; r < 6; r++) yj[r] = yv[r];
-            }
-        }
-        BP(2);
-        lds_barrier();
-        BP(3);
-        if (use_mfma) {
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                if (ta_di[q] > 20) continue; // this wave has no such tile (uniform over the wave)
-                double a0 = 0, a1 = 0, b0 = 0, b1 = 0;
-                if (ta_di[q] <= nd) { a0 = -Wc[ta_off[q]]; if (k0 < 2) a1 = -Wc[ta_off[q] + 4]; } // K = 6: k0, k0 + 4 < 6
-                if (tb_di[q] <= nd) { b0 = Wc[tb_off[q]]; if (k0 < 2) b1 = Wc[tb_off[q] + 4]; }
-                band_v4d acc;
-                double *tp[4];
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const unsigned x = (unsigned)(sjcs + t_dk[q][g]);
-                    tp[g] = W + (int)(min(x, x - (unsigned)NSCS) + (unsigned)t_in[q][g]); // ((sj + dk) mod NS) * CS + offset, no multiply
-                    acc[g] = t_di[q][g] <= nd ? *tp[g] : 0.0;
-                }
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc, 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < 4; g++) if (t_di[q][g] <= nd) *tp[g] = acc[g];
-            }
-            if (wave == NT / 64 - 1 && lane < nd * 6) { // b_{j+d} -= L_d y_j
-                const double *Ld = Wc + p_off;
-                double v = 0;
-#pragma unroll
-                for (int q = 0; q < 6; q++) v += Ld[q] * yj[q];
-                int sl = sj + p_dd; if (sl >= NS) sl -= NS;
-                bw[sl * 6 + p_r] -= v;
-            }
-        } else {
-        const int npair = nd * (nd + 1) / 2;
-        for (int t = tid; t < npair * 6 + nd * 6; t += NT) {
-            if (t < npair * 6) { // row r of block (j+di, j+dk) -= (row r of L_di) L_dk^T: the row of L_di stays in registers
-                const int pr = t / 6, r = t % 6, di = pair_d[pr] >> 8, dk = pair_d[pr] & 255;
-                const double *Li = Wc + di * 36 + r * 6, *Lk = Wc + dk * 36;
-                double a[6];
-#pragma unroll
-                for (int q = 0; q < 6; q++) a[q] = Li[q];
-                int sl = sj + dk; if (sl >= NS) sl -= NS;
-                double *T = W + (long)sl * CS + (di - dk) * 36 + r * 6;
-                double tv[6];
-#pragma unroll
-                for (int c = 0; c < 6; c++) tv[c] = T[c];
-#pragma unroll
-                for (int c = 0; c < 6; c++) { // fused multiply-adds: the solver's round-off is not part of the parity contract
-#pragma unroll
-                    for (int q = 0; q < 6; q++) tv[c] = __builtin_fma(-a[q], Lk[c * 6 + q], tv[c]);
-                }
-#pragma unroll
-                for (int c = 0; c < 6; c++) T[c] = tv[c];
-            } else { // b_{j+d} -= L_d y_j
-                const int u = t - npair * 6, d = 1 + u / 6, r = u % 6;
-                const double *Ld = Wc + d * 36 + r * 6;
-                double v = 0;
-#pragma unroll
-                for (int q = 0; q < 6; q++) v += Ld[q] * yj[q];
-                int sl = sj + d; if (sl >= NS) sl -= NS;
-                bw[sl * 6 + r] -= v;
-            }
-        }
-        }
-        BP(6);
-        for (int i = 36 + tid; i < (nd + 1) * 36; i += NT) Lf[(long)(V.lf_base + j) * CS + i] = Wc[i]; // the panel; the diagonal block comes from wave 0's registers
-        if (tid == 0) { // L_jj, y_j and L_jj^-1 (lower, packed) straight from registers to global memory, while the other waves update
-            double *Lo = Lf + (long)(V.lf_base + j) * CS, *yo = ybuf + (long)(V.lf_base + j) * BAND_YB; // buffers this kernel has not read before: no stale L1 line possible
-#pragma unroll
-            for (int r = 0; r < 6; r++) {
-                yo[r] = yv[r];
-#pragma unroll
-                for (int c = 0; c < 6; c++) { Lo[r * 6 + c] = c <= r ? Lr[r][c] : 0.0; if (c <= r) yo[6 + r * (r + 1) / 2 + c] = Mi[r][c]; }
-            }
-        }
-        BP(7);
-        if (cn < V.n) {
-            double *dst = W + (long)scn * CS;
-#pragma unroll
-            for (int u = 0; u < 4; u++) if (tid + u * NT < CS) dst[tid + u * NT] = pf[u];
-            if (tid < 6) bw[scn * 6 + tid] = pfb;
-        }
-        BP(4);
-        lds_barrier();
-        BP(5);
-        if (++sj == NS) sj = 0;
-        sjcs = sj * CS;
-    }
-#ifdef BAND_PROF
-    if (tid == 0) printf("band_factor side %d cols %d cycles: top %llu pivot %llu panel %llu bar1 %llu mfma %llu store %llu commit %llu bar2 %llu\n", V.rev, V.ne, pt_[0], pt_[1], pt_[2], pt_[3], pt_[6], pt_[7], pt_[4], pt_[5]);
-#endif
-    return fail;
-}
-
-// L^T x = y for the local columns ne-1 .. 0, last first; xtail (may be NULL when n == ne): solved tail blocks in local order.
-// The columns of L come back from global memory in chunks of KC columns through two LDS buffers (the whole workgroup loads chunk
-// k+1 into registers while chunk k is used, one barrier per chunk); inside a chunk wave 0 works alone, without barriers: lane =
-// part * 6 + c sums L_d^T x_{j+d} over the blocks d = 1 + part, 9 + part, 17 + part, shuffles reduce the 8 parts, lanes 0..5
-// finish with L_jj^T by lane broadcasts.  Solved blocks: LDS ring xw; xout in original order.
-template <int NT> __device__ __forceinline__ void band_back(const BandView &V, const BandLds &S, const double *Lf, const double *ybuf, const double *xtail, int xtail_rev, double *xout) {
-    const int Bc = V.Bc, NB = Bc + 1, NS = Bc + 2, CS = NB * 36, C = V.ne;
-    double *W = S.W;
-    const int tid = threadIdx.x;
-    double *xw = S.bw;
-    const int R = V.n - V.ne;
-    for (int i = tid; i < R * 6; i += NT) { const int t = i / 6; xw[((V.ne + t) % NS) * 6 + i % 6] = xtail[(long)(xtail_rev ? R - 1 - t : t) * 6 + i % 6]; }
-    const int KC = (NS - 1) / 2, CB = KC * CS;           // chunk: KC columns of CS doubles; buffers W[0..CB) and W[CB..2CB), >= CS doubles left for ych
-    double *ych = W + 2 * (long)CB;                      // 2 x KC x BAND_YB (y_j, L_jj^-1) -- fits: (NS - 2 KC) * CS >= CS >= 56 * KC for Bc >= 1
-    const int nchunk = (C + KC - 1) / KC;
-    auto chunk_lo = [&](int ch) { return C - (ch + 1) * KC < 0 ? 0 : C - (ch + 1) * KC; }; // chunk ch covers columns [lo, hi)
-    auto chunk_hi = [&](int ch) { return C - ch * KC; };
-    constexpr int UPF = (9216 + NT - 1) / NT; // doubles per thread per chunk: Bc <= 20 -> CB <= 8316 (checked by the host)
-    double pf[UPF], pfy = 0;
-    auto issue = [&](int ch) {
-        const int lo = chunk_lo(ch), n = (chunk_hi(ch) - lo) * CS;
-#pragma unroll
-        for (int u = 0; u < UPF; u++) { const int i = tid + u * NT; pf[u] = i < n ? __builtin_nontemporal_load(Lf + (long)(V.lf_base + lo) * CS + i) : 0.0; }
-        const int ny = (chunk_hi(ch) - lo) * BAND_YB;
-        pfy = tid < ny ? __builtin_nontemporal_load(ybuf + (long)(V.lf_base + lo) * BAND_YB + tid) : 0.0;
-    };
-    auto commit = [&](int ch) {
-        const int lo = chunk_lo(ch), n = (chunk_hi(ch) - lo) * CS;
-        double *dst = W + (long)(ch & 1) * CB;
-#pragma unroll
-        for (int u = 0; u < UPF; u++) { const int i = tid + u * NT; if (i < n) dst[i] = pf[u]; }
-        const int ny = (chunk_hi(ch) - lo) * BAND_YB;
-        if (tid < ny) ych[(ch & 1) * KC * BAND_YB + tid] = pfy;
-    };
-    if (nchunk > 0) { issue(0); commit(0); }
-    lds_barrier();
-    const int c = (tid >> 3) < 6 ? (tid >> 3) : 0, pt = tid & 7; // wave 0: lane = c * 8 + part, lanes 48..63 idle
-    const bool work = tid < 48, last = work && pt == 7;           // lane c*8+7 ends up with the sum over the 8 parts
-    for (int ch = 0; ch < nchunk; ch++) {
-        if (ch + 1 < nchunk) issue(ch + 1);
-        if (tid < 64) {
-            const int lo = chunk_lo(ch);
-            const double *Lb0 = W + (long)(ch & 1) * CB, *yb0 = ych + (ch & 1) * KC * BAND_YB;
-            int sj = (chunk_hi(ch) - 1) % NS; // slot of column j in the ring of solved blocks, kept incrementally
-            for (int j = chunk_hi(ch) - 1; j >= lo; j--) {
-                const int nd = (V.n - 1 - j) < Bc ? (V.n - 1 - j) : Bc;
-                const double *Lc = Lb0 + (long)(j - lo) * CS, *yl = yb0 + (j - lo) * BAND_YB;
-                // v_c = sum_d (L_d^T x_{j+d})_c: this lane's blocks d = 1 + pt, 9 + pt, 17 + pt, an independent accumulator each
-                // (a dependent v_fma_f64 costs 40 cycles), then DPP row shifts over the 8 parts
-                double va[3] = {0, 0, 0};
-#pragma unroll
-                for (int u = 0; u < 3; u++) {
-                    const int d = 1 + pt + 8 * u;
-                    if (work && d <= nd) {
-                        int sl = sj + d; if (sl >= NS) sl -= NS; if (sl >= NS) sl -= NS;
-                        const double *Ld = Lc + d * 36 + c, *xd = xw + sl * 6;
-#pragma unroll
-                        for (int q = 0; q < 6; q++) va[u] = __builtin_fma(Ld[q * 6], xd[q], va[u]);
-                    }
-                }
-                double v = (va[0] + va[1]) + va[2];
-                v += dpp_f64<0x114>(v); v += dpp_f64<0x112>(v); v += dpp_f64<0x111>(v);
-                // x_j = L_jj^-T (y_j - v) with the explicit inverse from the factorisation: six independent broadcasts and a 3 + 3
-                // multiply-add tree per lane instead of a six-step substitution chain
-                const double sv = yl[c] - v;
-                double s6[6];
-#pragma unroll
-                for (int k = 0; k < 6; k++) s6[k] = __shfl(sv, k * 8 + 7);
-                double e = 0, o = 0;
-#pragma unroll
-                for (int k = 0; k < 6; k++) {
-                    const double m = k >= c ? yl[6 + k * (k + 1) / 2 + c] : 0.0; // (L^-1)[k][c]
-                    if (k & 1) o = __builtin_fma(m, s6[k], o); else e = __builtin_fma(m, s6[k], e);
-                }
-                const double xv = e + o;
-                if (last) { xw[sj * 6 + c] = xv; xout[(long)(V.rev ? V.C - 1 - j : j) * 6 + c] = xv; }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                sj = sj == 0 ? NS - 1 : sj - 1;
-            }
-        }
-        if (ch + 1 < nchunk) commit(ch + 1);
-        lds_barrier();
-    }
-}
-
-constexpr int BAND_NT = 384; // 6 waves: the nd(nd+1)/2 * 6 + nd * 6 = 324 work items of a trailing update (Bc = 9) fit one pass
-// one workgroup, whole chain (short systems, or CUBESLAM_BA_SOLVER=band1).  rhs: in b (6C), out x; ybuf: 28C scratch
-__global__ void __launch_bounds__(BAND_NT) ba_band_chol(int C, int Bc, const double *A, double *Lf, double *rhs, double *ybuf, int *status) {
-    extern __shared__ double sh[];
-    const BandLds S = band_lds(sh, Bc);
-    const BandView V{A, rhs, C, Bc, C, C, 0, 0};
-    const bool fail = band_factor<BAND_NT>(V, S, Lf, ybuf);
-    __syncthreads(); // every store to Lf / ybuf has completed
-    band_back<BAND_NT>(V, S, Lf, ybuf, nullptr, 0, rhs);
-    if (threadIdx.x == 0 && fail) *status = 1;
-}
-__device__ __forceinline__ BandView band_side(int side, int C, int Bc, const double *A, const double *rhs) { // side 0: columns [0, neF); side 1: the other end
-    const int R = Bc, neF = (C - R) / 2, neB = C - R - neF;
-    return side == 0 ? BandView{A, rhs, C, Bc, neF + R, neF, 0, 0} : BandView{A, rhs, C, Bc, neB + R, neB, 1, neF};
-}
-// mid: per side R columns of CS doubles (the updated tail columns, local order) followed by 6R right-hand-side entries
-__global__ void __launch_bounds__(BAND_NT) ba_band_twist_factor(int C, int Bc, const double *A, const double *rhs, double *Lf, double *ybuf, double *mid, int *status) {
-    extern __shared__ double sh[];
-    const BandLds S = band_lds(sh, Bc);
-    const BandView V = band_side(blockIdx.x, C, Bc, A, rhs);
-    const bool fail = band_factor<BAND_NT>(V, S, Lf, ybuf);
-    const int NS = Bc + 2, CS = (Bc + 1) * 36, R = V.n - V.ne;
-    double *m = mid + (long)blockIdx.x * ((long)R * CS + R * 6);
-    for (int i = threadIdx.x; i < R * CS; i += BAND_NT) m[i] = S.W[(long)((V.ne + i / CS) % NS) * CS + i % CS];
-    for (int i = threadIdx.x; i < R * 6; i += BAND_NT) m[(long)R * CS + i] = S.bw[((V.ne + i / 6) % NS) * 6 + i % 6];
-    if (threadIdx.x == 0 && fail) *status = 1;
-}
-// middle group: M = tail(forward) + reversed tail(backward), dense Cholesky in LDS (N = 6R <= 120), two triangular solves.  xm: 6R
-__global__ void __launch_bounds__(256) ba_band_mid(int C, int Bc, const double *mid, double *xm, double *xout, int *status) {
-    extern __shared__ double sh[];
-    const int R = Bc, N = 6 * R, CS = (Bc + 1) * 36, tid = threadIdx.x;
-    double *M = sh, *bv = M + (long)N * N;
-    const double *m0 = mid, *m1 = mid + ((long)R * CS + R * 6);
-    for (int i = tid; i < N * N; i += 256) M[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < R * R * 36; i += 256) { // forward side: block (t+d, t) as stored
-        const int t = i / (R * 36), d = (i / 36) % R, e = i % 36, r = e / 6, c = e % 6;
-        if (t + d < R) M[(long)((t + d) * 6 + r) * N + t * 6 + c] = m0[(long)t * CS + d * 36 + e];
-    }
-    __syncthreads();
-    for (int i = tid; i < R * R * 36; i += 256) { // backward side: its block (t+d, t) is the transposed original block (R-1-t, R-1-t-d)
-        const int t = i / (R * 36), d = (i / 36) % R, e = i % 36, r = e / 6, c = e % 6;
-        if (t + d < R && (d > 0 || r >= c)) { // diagonal blocks: only their lower triangle is maintained by the factor kernels
-            const int bb = R - 1 - t, aa = bb - d;
-            if (d > 0) M[(long)(bb * 6 + c) * N + aa * 6 + r] += m1[(long)t * CS + d * 36 + e];
-            else M[(long)(bb * 6 + r) * N + bb * 6 + c] += m1[(long)t * CS + e];
-        }
-    }
-    for (int i = tid; i < N; i += 256) bv[i] = m0[(long)R * CS + i] + m1[(long)R * CS + (R - 1 - i / 6) * 6 + i % 6];
-    __syncthreads();
-    __shared__ int s_fail;
-    if (tid == 0) s_fail = 0;
-    for (int k = 0; k < N; k++) { // right-looking Cholesky, lower triangle
-        if (tid == 0) { double d = M[(long)k * N + k]; if (!(d > 0)) { s_fail = 1; d = 1; } M[(long)k * N + k] = sqrt(d); }
-        __syncthreads();
-        const double dk = M[(long)k * N + k];
-        for (int i = k + 1 + tid; i < N; i += 256) M[(long)i * N + k] /= dk;
-        __syncthreads();
-        const int m = N - 1 - k; // trailing rows k+1..N-1: element (i, j), j <= i
-        for (int e = tid; e < m * m; e += 256) { const int i = k + 1 + e / m, j = k + 1 + e % m; if (j <= i) M[(long)i * N + j] = __builtin_fma(-M[(long)i * N + k], M[(long)j * N + k], M[(long)i * N + j]); }
-        __syncthreads();
-    }
-    for (int k = 0; k < N; k++) { // L y = b
-        if (tid == 0) bv[k] /= M[(long)k * N + k];
-        __syncthreads();
-        const double yk = bv[k];
-        for (int i = k + 1 + tid; i < N; i += 256) bv[i] = __builtin_fma(-M[(long)i * N + k], yk, bv[i]);
-        __syncthreads();
-    }
-    for (int k = N - 1; k >= 0; k--) { // L^T x = y
-        if (tid == 0) bv[k] /= M[(long)k * N + k];
-        __syncthreads();
-        const double xk = bv[k];
-        for (int i = tid; i < k; i += 256) bv[i] = __builtin_fma(-M[(long)k * N + i], xk, bv[i]);
-        __syncthreads();
-    }
-    const int neF = (C - R) / 2;
-    for (int i = tid; i < N; i += 256) { xm[i] = bv[i]; xout[(long)neF * 6 + i] = bv[i]; }
-    if (tid == 0 && s_fail) *status = 1;
-}
-__global__ void __launch_bounds__(BAND_NT) ba_band_twist_back(int C, int Bc, const double *Lf, const double *ybuf, const double *xm, double *xout) {
-    extern __shared__ double sh[];
-    const BandLds S = band_lds(sh, Bc);
-    const BandView V = band_side(blockIdx.x, C, Bc, nullptr, nullptr);
-    band_back<BAND_NT>(V, S, Lf, ybuf, xm, blockIdx.x, xout);
-}
+#include "ba_band.h" // block-band Cholesky of the camera system: BandView ... ba_band_twist_back
 
 // scatter the (all-reduced) blocks of the reduced system into the factor storage Lb = [P diagonal blocks | off-diagonal
 // blocks column by column in elimination order]; slot_dst[s] = destination block (-1: dead), slot_tr[s] = transpose
@@ -1233,23 +784,21 @@ struct cs_ba {
     int *d_tgt_slot = nullptr, *d_ct_off = nullptr, *d_ct_list = nullptr, *d_cr_off = nullptr, *d_cr_list = nullptr, *d_cq_off = nullptr, *d_cq_list = nullptr;
     uint8_t *d_tgt_tr = nullptr;
     double *d_bandA = nullptr, *d_bandL = nullptr, *d_cubD = nullptr, *d_cubg = nullptr, *d_brhs = nullptr, *d_ybuf = nullptr, *d_mid = nullptr, *d_xmid = nullptr, *d_bw = nullptr;
-    std::vector<int> h_slot_dst, h_pos, h_col_off, h_rows; std::vector<uint8_t> h_slot_tr;
+    std::vector<std::pair<int, int>> slot_rc; // block (rows, cols) of every slot in pose numbering, (-1, -1): dead (cs_ba_reduced_dense)
     std::vector<int> obs_perm; // sorted-by-landmark position -> caller's observation index
     std::vector<double> h_partials;
     double *h_pin = nullptr; size_t pin_cap = 0; hipEvent_t ev_trial = nullptr; // pinned [status | partials] of a trial and the event behind their copies (cs_ba_optimize)
 };
 
 namespace {
-template <class T> int dalloc_copy(cs_ctx *ctx, cs_ba *b, T **d, const T *h, size_t n) {
-    return h ? b->own.upload(ctx, d, h, n) : b->own.alloc(ctx, d, n); // no host array: a work block, not initialised
-}
-static double sum_partials(cs_ctx *ctx, cs_ba *b, int n, bool is_max = false) {
+static int sum_partials(cs_ctx *ctx, cs_ba *b, int n, double *out, bool is_max = false) { // sum (or maximum) of the first n partials, in index order
     b->h_partials.resize((size_t)std::max(n, 1));
-    hipMemcpyAsync(b->h_partials.data(), b->d_partials, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
-    hipStreamSynchronize(ctx->stream);
+    CS_TRY(cs_d2h(ctx, b->h_partials.data(), b->d_partials, (size_t)n));
+    CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     double s = 0;
     for (int i = 0; i < n; i++) s = is_max ? std::max(s, b->h_partials[i]) : s + b->h_partials[i];
-    return s;
+    *out = s;
+    return CS_OK;
 }
 // all-reduce(sum) of n doubles in device memory across the ranks: the caller's callback when one is registered (it may use another stream or
 // library, so the context's stream is drained first), else RCCL on the context's own stream (cs_comm_init), which needs no host round trip
@@ -1265,23 +814,23 @@ static int ba_allreduce(cs_ctx *ctx, cs_ba *b, double *dbuf, long n) {
 // sum of k host scalars across ranks (k <= the size of d_scal: 6 P + world + 64)
 static int allreduce_scalars(cs_ctx *ctx, cs_ba *b, double *v, int k) {
     if (b->world <= 1) return CS_OK;
-    int r = cs_h2d(ctx, b->d_scal, v, (size_t)k); if (r) return r;
-    r = ba_allreduce(ctx, b, b->d_scal, k); if (r) return r;
-    r = cs_d2h(ctx, v, b->d_scal, (size_t)k); if (r) return r;
+    CS_TRY(cs_h2d(ctx, b->d_scal, v, (size_t)k));
+    CS_TRY(ba_allreduce(ctx, b, b->d_scal, k));
+    CS_TRY(cs_d2h(ctx, v, b->d_scal, (size_t)k));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
 static int ba_compute_errors(cs_ctx *ctx, cs_ba *b, double *chi2) { // computeActiveErrors + activeRobustChi2
     const Params &G = b->G;
-    double chi = 0;
+    double chi = 0, part;
     const int nb1 = (G.o_e - G.o_b + 255) / 256;
-    if (nb1 > 0) { CS_LAUNCH(ctx, "ba_err_obs", ba_err_obs, dim3(nb1), dim3(256), 0, G, b->d_partials); chi += sum_partials(ctx, b, nb1); }
+    if (nb1 > 0) { CS_LAUNCH(ctx, "ba_err_obs", ba_err_obs, dim3(nb1), dim3(256), 0, G, b->d_partials); CS_TRY(sum_partials(ctx, b, nb1, &part)); chi += part; }
     if (G.pose_edges && G.n_cobs + G.n_pc > 0) {
         const int nb2 = (G.n_cobs + G.n_pc + 255) / 256;
         CS_LAUNCH(ctx, "ba_err_pose_edges", ba_err_pose_edges, dim3(nb2), dim3(256), 0, G, b->d_partials);
-        chi += sum_partials(ctx, b, nb2);
+        CS_TRY(sum_partials(ctx, b, nb2, &part)); chi += part;
     }
-    int r = allreduce_scalars(ctx, b, &chi, 1); if (r) return r;
+    CS_TRY(allreduce_scalars(ctx, b, &chi, 1));
     *chi2 = chi;
     return CS_OK;
 }
@@ -1305,7 +854,7 @@ static int ba_schur(cs_ctx *ctx, cs_ba *b, double lambda) { // Schur part of Blo
 }
 static int ba_solve(cs_ctx *ctx, cs_ba *b, double lambda, bool *ok, bool defer_status = false) { // BlockSolver::solve; defer_status: the caller reads d_status later
     const Params &G = b->G;
-    int r = ba_schur(ctx, b, lambda); if (r) return r;
+    CS_TRY(ba_schur(ctx, b, lambda));
     if (b->world > 1) { // one fused buffer [36 * slots | 6 * P] per LM trial
         ctx->begin("ba_allreduce");
         const int rc = ba_allreduce(ctx, b, b->d_reduce, b->reduce_len);
@@ -1323,7 +872,7 @@ static int ba_solve(cs_ctx *ctx, cs_ba *b, double lambda, bool *ok, bool defer_s
                     C, b->d_cr_off, b->d_cr_list, bs, b->d_cubg, b->d_brhs); }
         const size_t lds = band_lds_bytes(Bc);
         if (b->band_cr) { // nested dissection over super-blocks of Bc cameras: log2(C / Bc) parallel levels (ba_cr.hip)
-            r = ba_cr_solve(ctx, &b->cr, C, Bc, b->d_bandA, b->d_brhs, G.x, b->d_status); if (r) return r;
+            CS_TRY(ba_cr_solve(ctx, &b->cr, C, Bc, b->d_bandA, b->d_brhs, G.x, b->d_status));
         } else if (b->band_twist) { // both ends at once (see the comment above band_factor)
             const size_t lds_mid = sizeof(double) * ((size_t)36 * Bc * Bc + 6 * (size_t)Bc);
             if (lds > 64 * 1024) {
@@ -1342,7 +891,7 @@ static int ba_solve(cs_ctx *ctx, cs_ba *b, double lambda, bool *ok, bool defer_s
         if (nl > 0 || Q > 0) CS_LAUNCH(ctx, "ba_backsub", ba_back_both, dim3((nl + 255) / 256 + (Q + 255) / 256), dim3(256), 0, G, (nl + 255) / 256, C, Q, b->d_cq_off, b->d_cq_list, S, b->d_cubD, b->d_cubg);
         if (defer_status) return CS_OK;
         int status = 0;
-        r = cs_d2h(ctx, &status, b->d_status, 1); if (r) return r;
+        CS_TRY(cs_d2h(ctx, &status, b->d_status, 1));
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         *ok = status == 0;
         return CS_OK;
@@ -1357,7 +906,7 @@ static int ba_solve(cs_ctx *ctx, cs_ba *b, double lambda, bool *ok, bool defer_s
     if (nl > 0) CS_LAUNCH(ctx, "ba_backsub", ba_backsub, dim3((nl + 255) / 256), dim3(256), 0, G);
     if (defer_status) return CS_OK;
     int status = 0;
-    r = cs_d2h(ctx, &status, b->d_status, 1); if (r) return r;
+    CS_TRY(cs_d2h(ctx, &status, b->d_status, 1));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *ok = status == 0;
     return CS_OK;
@@ -1381,9 +930,18 @@ int cs_ba_set_allreduce(cs_ba *b, cs_allreduce_fn fn, void *user) {
     return CS_OK;
 }
 
+// check -> plan (ba_plan.h, host only) -> upload.  Nothing is allocated before the plan stands; after `new cs_ba` every failure leaves through cs_ba_destroy.
 int cs_ba_create(cs_ctx *ctx, const cs_ba_problem *p, int rank, int world, cs_ba **out) {
-    if (!ctx || !p || !out || world < 1 || rank < 0 || rank >= world || p->n_cams < 1 || p->n_points < 0 || p->n_cuboids < 0 || p->n_obs < 0) return CS_ERR_BAD_ARG;
+    if (!ctx || !out) return CS_ERR_BAD_ARG;
     *out = nullptr;
+    CS_TRY(ba_plan_check(p, rank, world));
+    const char *force = getenv("CUBESLAM_BA_SOLVER"); // "sparse" / "band" / "band1" (band, one workgroup) / "cr": pick the path (tests run all)
+    const BaSolverChoice choice = !force ? BA_SOLVER_NONE : !strcmp(force, "sparse") ? BA_SOLVER_SPARSE : !strcmp(force, "band") ? BA_SOLVER_BAND : !strcmp(force, "band1") ? BA_SOLVER_BAND1 :
+                                  !strcmp(force, "cr") ? BA_SOLVER_CR : BA_SOLVER_OTHER;
+    BaPlan X;
+    const char *why = nullptr;
+    const int rp = ba_plan_build(p, rank, world, choice, X, &why);
+    if (rp != CS_OK) { if (why) ctx->err = why; return rp; }
     CS_HIP(ctx, hipSetDevice(ctx->device));
     cs_ba *b = new (std::nothrow) cs_ba();
     if (!b) return CS_ERR_NOMEM;
@@ -1392,327 +950,55 @@ int cs_ba_create(cs_ctx *ctx, const cs_ba_problem *p, int rank, int world, cs_ba
     G.n_cams = p->n_cams; G.L = p->n_points; G.n_cub = p->n_cuboids; G.n_obs = p->n_obs; G.n_cobs = p->n_cobs; G.n_pc = p->n_pc;
     G.fx = p->fx; G.fy = p->fy; G.cx = p->cx; G.cy = p->cy; G.huber_mono = p->huber_mono; G.huber_obj = p->huber_obj; G.bf = p->bf; G.huber_stereo = p->huber_stereo; G.margin_ratio = p->max_outside_margin_ratio;
     for (int i = 0; i < 9; i++) G.K[i] = p->K[i];
-    G.pose_edges = rank == 0; // camera-cuboid and point-cuboid edges (and setLambda on the pose diagonal) live on rank 0
-    // index mapping: non-fixed cameras, then cuboids (sparse_optimizer.cpp:166-190: non-marginalised first, by vertex id)
-    std::vector<int> cam_idx(p->n_cams, -1);
-    int P = 0;
-    for (int i = 0; i < p->n_cams; i++) if (!p->cam_fixed[i]) cam_idx[i] = P++;
-    const int first_cub = P;
-    P += p->n_cuboids;
-    G.P = P;
-    if (P < 1) { delete b; return CS_ERR_BAD_ARG; }
-    // observations sorted by landmark (stable): CSR by landmark
-    for (int o = 0; o < p->n_obs; o++) if (p->obs_point[o] < 0 || p->obs_point[o] >= p->n_points || p->obs_cam[o] < 0 || p->obs_cam[o] >= p->n_cams) { delete b; return CS_ERR_BAD_ARG; }
-    b->obs_perm.resize(p->n_obs);
-    for (int o = 0; o < p->n_obs; o++) b->obs_perm[o] = o;
-    std::stable_sort(b->obs_perm.begin(), b->obs_perm.end(), [&](int a, int c) { return p->obs_point[a] < p->obs_point[c]; });
-    std::vector<int> o_cam(p->n_obs), o_pt(p->n_obs), lm_off(p->n_points + 1, 0);
-    std::vector<double> o_uv((size_t)p->n_obs * 2), o_w(p->n_obs), o_ur(p->obs_ur ? p->n_obs : 0);
-    for (int q = 0; q < p->n_obs; q++) {
-        const int o = b->obs_perm[q];
-        o_cam[q] = p->obs_cam[o]; o_pt[q] = p->obs_point[o]; o_uv[q * 2] = p->obs_uv[o * 2]; o_uv[q * 2 + 1] = p->obs_uv[o * 2 + 1]; o_w[q] = p->obs_inv_sigma2[o]; if (p->obs_ur) o_ur[q] = p->obs_ur[o];
-        lm_off[o_pt[q] + 1]++;
-    }
-    for (int l = 0; l < p->n_points; l++) lm_off[l + 1] += lm_off[l];
-    G.lm_b = (int)((long)p->n_points * rank / world); G.lm_e = (int)((long)p->n_points * (rank + 1) / world);
-    G.o_b = lm_off[G.lm_b]; G.o_e = lm_off[G.lm_e];
-    // per pose block: this rank's observations (ascending)
-    std::vector<int> pose_off(P + 1, 0), pose_obs;
-    for (int q = G.o_b; q < G.o_e; q++) if (cam_idx[o_cam[q]] >= 0) pose_off[cam_idx[o_cam[q]] + 1]++;
-    for (int i = 0; i < P; i++) pose_off[i + 1] += pose_off[i];
-    pose_obs.resize(std::max(pose_off[P], 1));
-    { std::vector<int> pos(pose_off.begin(), pose_off.end() - 1); for (int q = G.o_b; q < G.o_e; q++) { int pi = cam_idx[o_cam[q]]; if (pi >= 0) pose_obs[pos[pi]++] = q; } }
-    // pose-edge incidence (edge order: camera-cuboid edges, then point-cuboid edges)
-    std::vector<std::vector<int>> pe(P);
-    for (int o = 0; o < p->n_cobs; o++) {
-        if (p->cobs_cam[o] < 0 || p->cobs_cam[o] >= p->n_cams || p->cobs_cuboid[o] < 0 || p->cobs_cuboid[o] >= p->n_cuboids) { delete b; return CS_ERR_BAD_ARG; }
-        if (cam_idx[p->cobs_cam[o]] >= 0) pe[cam_idx[p->cobs_cam[o]]].push_back((o << 2) | 0);
-        pe[first_cub + p->cobs_cuboid[o]].push_back((o << 2) | 1);
-    }
-    for (int o = 0; o < p->n_pc; o++) pe[first_cub + p->pc_cuboid[o]].push_back((o << 2) | 2);
-    std::vector<int> pe_off(P + 1, 0), pe_list;
-    for (int i = 0; i < P; i++) { pe_off[i + 1] = pe_off[i] + (int)pe[i].size(); pe_list.insert(pe_list.end(), pe[i].begin(), pe[i].end()); }
-    if (pe_list.empty()) pe_list.push_back(0);
-    // Schur pattern (BlockSolver::buildStructure block_solver.hpp:143-295) over ALL landmarks (identical on every rank);
-    // the contributing (obs_u, obs_v) pairs only for this rank's landmarks
-    std::map<std::pair<int, int>, int> slot_of;
-    std::vector<std::pair<int, int>> slot_rc;
-    for (int i = 0; i < P; i++) { slot_of[std::make_pair(i, i)] = i; slot_rc.push_back(std::make_pair(i, i)); }
-    for (int o = 0; o < p->n_cobs; o++) { // one block per camera-cuboid edge, slot P + o (fixed cameras: unused block)
-        const int pi = cam_idx[p->cobs_cam[o]], pj = first_cub + p->cobs_cuboid[o];
-        slot_rc.push_back(pi >= 0 ? std::make_pair(pi, pj) : std::make_pair(-1, -1)); // fixed camera: dead block
-        if (pi >= 0) slot_of[std::make_pair(pi, pj)] = P + o;
-    }
-    std::vector<std::vector<int2>> slot_trips;
-    slot_trips.resize(slot_rc.size());
-    for (int l = 0; l < p->n_points; l++) {
-        const bool mine = l >= G.lm_b && l < G.lm_e;
-        for (int u = lm_off[l]; u < lm_off[l + 1]; u++) {
-            const int i1 = cam_idx[o_cam[u]];
-            if (i1 < 0) continue;
-            for (int v = lm_off[l]; v < lm_off[l + 1]; v++) {
-                const int i2 = cam_idx[o_cam[v]];
-                if (i2 < i1 || (i2 == i1 && v != u)) continue;
-                auto key = std::make_pair(i1, i2);
-                auto it = slot_of.find(key);
-                int s;
-                if (it == slot_of.end()) { s = (int)slot_rc.size(); slot_of[key] = s; slot_rc.push_back(key); slot_trips.emplace_back(); }
-                else s = it->second;
-                if (mine) slot_trips[s].push_back(make_int2(u, v));
-            }
-        }
-    }
-    b->n_slots = (int)slot_rc.size();
-    std::vector<int> slot_off(b->n_slots + 1, 0);
-    std::vector<int2> trips;
-    for (int s = 0; s < b->n_slots; s++) { slot_off[s + 1] = slot_off[s] + (int)slot_trips[s].size(); trips.insert(trips.end(), slot_trips[s].begin(), slot_trips[s].end()); }
-    if (trips.empty()) trips.push_back(make_int2(0, 0));
-    // ---- band path plan: cuboids eliminated first, cameras in index order; used when the camera system is narrow-banded
-    std::vector<int> tgt_slot, ct_off, ct_list, cr_off, cr_list, cq_off, cq_list;
-    std::vector<uint8_t> tgt_tr;
-    {
-        const int C = first_cub, Q = p->n_cuboids;
-        bool okb = C >= 1;
-        int Bc = 0;
-        for (auto &rc : slot_rc) {
-            if (rc.first < 0) continue;
-            if (rc.first >= C && rc.second >= C && rc.first != rc.second) okb = false; // two cuboids in one block: not a graph Optimizer.cc builds
-            if (rc.first < C && rc.second < C) Bc = std::max(Bc, std::abs(rc.first - rc.second));
-        }
-        std::vector<std::vector<std::pair<int, int>>> cub_edges(Q); // (camera, slot), alive edges only
-        for (int o = 0; o < p->n_cobs; o++) { const int pi = cam_idx[p->cobs_cam[o]]; if (pi >= 0) cub_edges[p->cobs_cuboid[o]].push_back(std::make_pair(pi, P + o)); }
-        for (auto &e : cub_edges) { std::stable_sort(e.begin(), e.end()); if (!e.empty()) Bc = std::max(Bc, e.back().first - e.front().first); }
-        Bc = std::max(Bc, 1); // one free camera, or free cameras that share nothing: band_back's chunks hold (Bc + 1) / 2 columns, none at Bc = 0; the extra block is explicit zeros
-        const char *force = getenv("CUBESLAM_BA_SOLVER"); // "sparse" / "band" / "band1" (band, one workgroup): pick the path (tests run all)
-        const int BAND_MAX = 20; // (Bc+2)(Bc+1) blocks of 288 B must fit the 160 KB LDS
-        if (force && !strcmp(force, "sparse")) okb = false;
-        if (Bc > BAND_MAX) okb = false;
-        if (force && (!strcmp(force, "band") || !strcmp(force, "band1")) && !okb) { ctx->err = "CUBESLAM_BA_SOLVER=band: the reduced camera system is not narrow-banded"; delete b; return CS_ERR_CAPACITY; }
-        if (okb) {
-            b->use_band = true; b->band_C = C; b->band_Q = Q; b->band_bc = Bc; b->band_targets = C * (Bc + 1);
-            b->band_twist = Bc >= 1 && C >= 6 * (Bc + 1) && !(force && !strcmp(force, "band1")); // two-sided elimination once the chain is long enough to split
-            // nested dissection (ba_cr.hip) once there are enough super-blocks to split; CUBESLAM_BA_SOLVER=band keeps the two-sided chain, =cr forces this
-            b->band_cr = ba_cr_supported(C, Bc) && ((force && !strcmp(force, "cr")) || (!force && C >= 16 * Bc));
-            tgt_slot.assign((size_t)C * (Bc + 1), -1); tgt_tr.assign((size_t)C * (Bc + 1), 0);
-            for (int s2 = 0; s2 < (int)slot_rc.size(); s2++) {
-                const int r0 = slot_rc[s2].first, c0 = slot_rc[s2].second;
-                if (r0 < 0 || r0 >= C || c0 >= C) continue;
-                if (s2 >= P && s2 < P + p->n_cobs) continue;
-                // stored block = (rows r0, cols c0); the band keeps block (i, k) with i >= k
-                if (r0 >= c0) { tgt_slot[(size_t)c0 * (Bc + 1) + (r0 - c0)] = s2; tgt_tr[(size_t)c0 * (Bc + 1) + (r0 - c0)] = 0; }
-                else { tgt_slot[(size_t)r0 * (Bc + 1) + (c0 - r0)] = s2; tgt_tr[(size_t)r0 * (Bc + 1) + (c0 - r0)] = 1; }
-            }
-            std::vector<std::vector<int>> ct((size_t)C * (Bc + 1));
-            std::vector<std::vector<int>> cr(C);
-            cq_off.assign(Q + 1, 0);
-            for (int q = 0; q < Q; q++) {
-                const auto &e = cub_edges[q];
-                for (size_t a = 0; a < e.size(); a++) {
-                    cr[e[a].first].push_back(q); cr[e[a].first].push_back(e[a].second);
-                    cq_list.push_back(e[a].second); cq_list.push_back(e[a].first);
-                    for (size_t c2 = 0; c2 < e.size(); c2++) {
-                        if (e[a].first < e[c2].first) continue; // target block (i, k) with i >= k; equal cameras: every ordered pair
-                        auto &l = ct[(size_t)e[c2].first * (Bc + 1) + (e[a].first - e[c2].first)];
-                        l.push_back(q); l.push_back(e[a].second); l.push_back(e[c2].second);
-                    }
-                }
-                cq_off[q + 1] = (int)(cq_list.size() / 2);
-            }
-            ct_off.assign(ct.size() + 1, 0);
-            for (size_t t = 0; t < ct.size(); t++) { ct_off[t + 1] = ct_off[t] + (int)(ct[t].size() / 3); ct_list.insert(ct_list.end(), ct[t].begin(), ct[t].end()); }
-            cr_off.assign(C + 1, 0);
-            for (int i = 0; i < C; i++) { cr_off[i + 1] = cr_off[i] + (int)(cr[i].size() / 2); cr_list.insert(cr_list.end(), cr[i].begin(), cr[i].end()); }
-            if (ct_list.empty()) ct_list.assign(3, 0);
-            if (cr_list.empty()) cr_list.assign(2, 0);
-            if (cq_list.empty()) cq_list.assign(2, 0);
-        }
-    }
-    // ordering of the pose blocks: minimum degree on the block graph (the reference lets Eigen::SimplicialLDLT order with AMD,
-    // linear_solver_eigen.h:60-75); the simulated elimination also yields the structure of every column of L
-    std::vector<std::vector<int>> adj(P);
-    for (auto &rc : slot_rc) if (rc.first != rc.second && rc.first >= 0) { adj[rc.first].push_back(rc.second); adj[rc.second].push_back(rc.first); }
-    for (auto &a : adj) { std::sort(a.begin(), a.end()); a.erase(std::unique(a.begin(), a.end()), a.end()); }
-    std::vector<int> pos(P, -1), order; order.reserve(P);
-    std::vector<std::vector<int>> col_struct(P); // by elimination position: neighbour node ids at elimination time
-    {
-        std::vector<char> gone(P, 0);
-        for (int k = 0; k < P; k++) {
-            int v = -1;
-            for (int i = 0; i < P; i++) if (!gone[i] && (v < 0 || adj[i].size() < adj[v].size())) v = i;
-            gone[v] = 1; pos[v] = k; order.push_back(v);
-            std::vector<int> nb = adj[v];
-            col_struct[k] = nb;
-            for (int a : nb) { // remove v, connect the neighbours pairwise (sorted-vector sets)
-                std::vector<int> &s = adj[a];
-                std::vector<int> merged;
-                merged.reserve(s.size() + nb.size());
-                std::set_union(s.begin(), s.end(), nb.begin(), nb.end(), std::back_inserter(merged));
-                merged.erase(std::remove_if(merged.begin(), merged.end(), [&](int x) { return x == v || x == a; }), merged.end());
-                s.swap(merged);
-            }
-            adj[v].clear();
-        }
-    }
-    std::vector<int> col_off(P + 1, 0), rows, pair_off(P + 1, 0);
-    int max_col = 0;
-    for (int k = 0; k < P; k++) {
-        std::vector<int> r;
-        for (int v : col_struct[k]) r.push_back(pos[v]);
-        std::sort(r.begin(), r.end());
-        rows.insert(rows.end(), r.begin(), r.end());
-        col_off[k + 1] = (int)rows.size();
-        pair_off[k + 1] = pair_off[k] + (int)(r.size() * (r.size() + 1) / 2);
-        max_col = std::max(max_col, (int)r.size());
-    }
-    if ((size_t)(36 + (size_t)max_col * 36) * sizeof(double) > 150 * 1024) { ctx->err = "reduced camera system too dense for the LDS column buffer"; delete b; return CS_ERR_CAPACITY; }
-    auto find_block = [&](int col, int row) { // storage index of L(row, col), row > col
-        const int *lo = &rows[col_off[col]], *hi = &rows[col_off[col + 1]];
-        const int *it = std::lower_bound(lo, hi, row);
-        return (it != hi && *it == row) ? P + (int)(it - &rows[0]) : -1;
+    G.pose_edges = X.pose_edges;
+    const int P = G.P = X.P;
+    G.lm_b = X.lm_b; G.lm_e = X.lm_e; G.o_b = X.o_b; G.o_e = X.o_e;
+    b->n_slots = X.n_slots; b->max_col = X.max_col; b->max_part = X.max_part; b->band_len = X.band_len; b->reduce_len = X.reduce_len;
+    b->use_band = X.use_band; b->band_twist = X.band_twist; b->band_C = X.C; b->band_Q = X.Q; b->band_bc = X.band_bc; b->band_targets = X.band_targets;
+    // nested dissection (ba_cr.hip) once there are enough super-blocks to split; CUBESLAM_BA_SOLVER=band keeps the two-sided chain, =cr forces this
+    b->band_cr = X.use_band && ba_cr_supported(X.C, X.band_bc) && (choice == BA_SOLVER_CR || (choice == BA_SOLVER_NONE && X.C >= 16 * X.band_bc));
+    b->slot_rc.swap(X.slot_rc); b->obs_perm.swap(X.obs_perm); // neither is uploaded
+    // estimates enter through SE3Quat(Vector7d): normalizeRotation (se3quat.h:64-67) -- done on a host copy, which is what goes up
+    std::vector<double> cam(p->cam_pose, p->cam_pose + (size_t)p->n_cams * 7), cub;
+    if (p->n_cuboids) cub.assign(p->cuboid_pose, p->cuboid_pose + (size_t)p->n_cuboids * 7);
+    for (std::vector<double> *v : {&cam, &cub}) for (size_t i = 0; i + 7 <= v->size(); i += 7) { SE3 T = se3_load(v->data() + i); normalize_rotation(T); se3_store(T, v->data() + i); }
+    // Uploads: the first failure stands and the rest become no-ops.  up / upv copy exactly the elements that exist (cs_h2d skips an empty copy), work blocks
+    // are not initialised; cs_dalloc alone turns an empty block into one element.
+    int r = CS_OK;
+    auto up = [&](auto *&d, const auto *h, size_t n) { // a caller's array
+        using T = std::remove_const_t<std::remove_pointer_t<std::remove_reference_t<decltype(d)>>>;
+        T *q = nullptr;
+        if (r == CS_OK) r = b->own.upload(ctx, &q, reinterpret_cast<const T *>(h), n);
+        d = q;
     };
-    std::vector<int> upd_tgt((size_t)std::max(pair_off[P], 1));
-    for (int k = 0; k < P; k++) {
-        const int m = col_off[k + 1] - col_off[k];
-        for (int bi = 0; bi < m; bi++)
-            for (int bk = 0; bk <= bi; bk++) {
-                const int ri = rows[col_off[k] + bi], rk = rows[col_off[k] + bk];
-                upd_tgt[(size_t)pair_off[k] + bi * (bi + 1) / 2 + bk] = bi == bk ? ri : find_block(rk, ri);
-            }
+    auto upv = [&](auto *&d, const auto &h) { static_assert(sizeof(*d) == sizeof(h[0]), "same layout on both sides"); up(d, h.data(), h.size()); }; // a plan array
+    auto work = [&](auto *&d, size_t n) { if (r == CS_OK) r = b->own.alloc(ctx, &d, n); };                                                              // a work block
+    auto n1 = [](long n) { return (size_t)std::max(n, 1L); };
+    const size_t n_obs = p->n_obs, n_cobs = p->n_cobs, n_pc = p->n_pc, n_pts = p->n_points, n_cub = p->n_cuboids, n_pcp = p->n_pc ? p->pc_offsets[p->n_pc] : 0;
+    upv(G.cam, cam); up(G.pts, p->points, n_pts * 3); upv(G.cub, cub); up(G.cub_scale, p->cuboid_scale, n_cub * 3); up(G.cub_flags, p->cuboid_flags, n_cub);
+    upv(G.cam_idx, X.cam_idx); upv(G.o_cam, X.o_cam); upv(G.o_pt, X.o_pt); upv(G.o_uv, X.o_uv); upv(G.o_w, X.o_w); upv(G.lm_off, X.lm_off);
+    if (!X.o_ur.empty()) upv(G.o_ur, X.o_ur); // (no array: monocular)
+    up(G.c_cam, p->cobs_cam, n_cobs); up(G.c_cub, p->cobs_cuboid, n_cobs); up(G.c_bbox, p->cobs_bbox, n_cobs * 4); up(G.c_info, p->cobs_info, n_cobs * 4);
+    up(G.pc_cub, p->pc_cuboid, n_pc); up(G.pc_off, p->pc_offsets, n_pc ? n_pc + 1 : 0); up(G.pc_pts, p->pc_points, n_pcp * 3);
+    work(G.e_obs, n1(n_obs) * 3); work(G.e_cobs, n1(n_cobs) * 4); work(G.e_pc, n1(n_pc) * 3); work(G.Hpl, n1(n_obs) * 18); work(G.HplD, n1(n_obs) * 18); work(b->d_bw, n1(n_obs) * 6);
+    work(G.Hll, n1(n_pts) * 9); work(G.bl, n1(n_pts) * 3); work(G.Dinv, n1(n_pts) * 9); work(G.db, n1(n_pts) * 3); work(G.Hpp, (size_t)P * 36); work(G.bp, (size_t)P * 6);
+    work(G.Hoff, n1(n_cobs) * 36); work(G.Jc, n1(n_cobs) * 48); work(G.Jp, n1(n_pc) * 18); work(G.x, (size_t)P * 6 + n1(n_pts) * 3);
+    upv(b->d_pose_off, X.pose_off); upv(b->d_pose_obs, X.pose_obs); upv(b->d_pe_off, X.pe_off); upv(b->d_pe_list, X.pe_list);
+    upv(b->d_slot_off, X.slot_off); upv(b->d_slot_perm, X.slot_perm); upv(b->d_trips, X.trips); upv(b->d_slot_dst, X.slot_dst); upv(b->d_slot_tr, X.slot_tr);
+    upv(b->d_col_off, X.col_off); upv(b->d_rows, X.rows); upv(b->d_pair_off, X.pair_off); upv(b->d_upd_tgt, X.upd_tgt); upv(b->d_pos, X.pos); work(b->d_status, 1);
+    if (X.use_band) {
+        const size_t nt = (size_t)X.band_targets, Bc = (size_t)X.band_bc;
+        upv(b->d_tgt_slot, X.tgt_slot); upv(b->d_tgt_tr, X.tgt_tr); upv(b->d_ct_off, X.ct_off); upv(b->d_ct_list, X.ct_list);
+        upv(b->d_cr_off, X.cr_off); upv(b->d_cr_list, X.cr_list); upv(b->d_cq_off, X.cq_off); upv(b->d_cq_list, X.cq_list);
+        work(b->d_bandA, nt * 36); work(b->d_bandL, nt * 36); work(b->d_cubD, n1(X.Q) * 36); work(b->d_cubg, n1(X.Q) * 6); work(b->d_brhs, (size_t)X.C * 6);
+        work(b->d_ybuf, (size_t)X.C * BAND_YB); work(b->d_mid, 2 * (Bc * (Bc + 1) * 36 + Bc * 6) + 8); work(b->d_xmid, Bc * 6 + 8);
     }
-    std::vector<int> slot_dst(b->n_slots);
-    std::vector<uint8_t> slot_tr(b->n_slots);
-    for (int s = 0; s < b->n_slots; s++) {
-        slot_tr[s] = 0;
-        if (slot_rc[s].first < 0) { slot_dst[s] = -1; continue; }
-        const int a = pos[slot_rc[s].first], c = pos[slot_rc[s].second];
-        if (a == c) slot_dst[s] = a;
-        else if (a > c) slot_dst[s] = find_block(c, a);            // block (rows first, cols second) sits below the diagonal as is
-        else { slot_dst[s] = find_block(a, c); slot_tr[s] = 1; }   // stored transposed
-        if (slot_dst[s] < 0) { ctx->err = "internal: Schur block outside the symbolic factor"; delete b; return CS_ERR_BAD_ARG; }
-    }
-    b->max_col = max_col;
-    b->band_len = ((long)P + (long)rows.size()) * 36;
-    b->h_slot_dst = slot_dst; b->h_slot_tr = slot_tr; b->h_pos = pos; b->h_col_off = col_off; b->h_rows = rows;
-    if (rows.empty()) rows.push_back(0);
-    b->reduce_len = (long)b->n_slots * 36 + (long)P * 6;
-    const int nl = G.lm_e - G.lm_b;
-    b->max_part = std::max(std::max((G.o_e - G.o_b + 255) / 256, (p->n_cobs + p->n_pc + 255) / 256), std::max((int)(((long)P * 6 + (long)nl * 3 + 255) / 256), (nl + 255) / 256)) + 1;
-
-#define A_(call) do { int r__ = (call); if (r__ != CS_OK) { cs_ba_destroy(ctx, b); return r__; } } while (0)
-    int *d_cam_idx, *d_o_cam, *d_o_pt, *d_lm_off, *d_c_cam, *d_c_cub, *d_pc_cub, *d_pc_off;
-    double *d_o_uv, *d_o_w, *d_o_ur = nullptr, *d_c_bbox, *d_c_info, *d_pc_pts;
-    uint8_t *d_flags;
-    const double zero4[4] = {0, 0, 0, 0}; const int zero2[2] = {0, 0};
-    A_(dalloc_copy(ctx, b, &G.cam, p->cam_pose, (size_t)p->n_cams * 7));
-    A_(dalloc_copy(ctx, b, &G.pts, p->points, (size_t)std::max(p->n_points, 1) * 3));
-    A_(dalloc_copy(ctx, b, &G.cub, p->cuboid_pose, (size_t)std::max(p->n_cuboids, 1) * 7));
-    A_(dalloc_copy(ctx, b, &G.cub_scale, p->cuboid_scale, (size_t)std::max(p->n_cuboids, 1) * 3));
-    A_(dalloc_copy(ctx, b, &d_flags, p->cuboid_flags, (size_t)std::max(p->n_cuboids, 1)));
-    A_(dalloc_copy(ctx, b, &d_cam_idx, cam_idx.data(), cam_idx.size()));
-    A_(dalloc_copy(ctx, b, &d_o_cam, o_cam.data(), (size_t)std::max(p->n_obs, 1)));
-    A_(dalloc_copy(ctx, b, &d_o_pt, o_pt.data(), (size_t)std::max(p->n_obs, 1)));
-    A_(dalloc_copy(ctx, b, &d_o_uv, o_uv.data(), (size_t)std::max(p->n_obs, 1) * 2));
-    if (p->obs_ur && p->n_obs > 0) A_(dalloc_copy(ctx, b, &d_o_ur, o_ur.data(), (size_t)p->n_obs));
-    A_(dalloc_copy(ctx, b, &d_o_w, o_w.data(), (size_t)std::max(p->n_obs, 1)));
-    A_(dalloc_copy(ctx, b, &d_lm_off, lm_off.data(), lm_off.size()));
-    A_(dalloc_copy(ctx, b, &d_c_cam, p->n_cobs ? p->cobs_cam : zero2, (size_t)std::max(p->n_cobs, 1)));
-    A_(dalloc_copy(ctx, b, &d_c_cub, p->n_cobs ? p->cobs_cuboid : zero2, (size_t)std::max(p->n_cobs, 1)));
-    A_(dalloc_copy(ctx, b, &d_c_bbox, p->n_cobs ? p->cobs_bbox : zero4, (size_t)std::max(p->n_cobs, 1) * 4));
-    A_(dalloc_copy(ctx, b, &d_c_info, p->n_cobs ? p->cobs_info : zero4, (size_t)std::max(p->n_cobs, 1) * 4));
-    A_(dalloc_copy(ctx, b, &d_pc_cub, p->n_pc ? p->pc_cuboid : zero2, (size_t)std::max(p->n_pc, 1)));
-    A_(dalloc_copy(ctx, b, &d_pc_off, p->n_pc ? p->pc_offsets : zero2, (size_t)p->n_pc + 1));
-    const int n_pcp = p->n_pc ? p->pc_offsets[p->n_pc] : 0;
-    A_(dalloc_copy(ctx, b, &d_pc_pts, n_pcp ? p->pc_points : zero4, (size_t)std::max(n_pcp, 1) * 3));
-    G.cam_idx = d_cam_idx; G.cub_flags = d_flags; G.o_cam = d_o_cam; G.o_pt = d_o_pt; G.o_uv = d_o_uv; G.o_w = d_o_w; G.o_ur = d_o_ur; G.lm_off = d_lm_off;
-    G.c_cam = d_c_cam; G.c_cub = d_c_cub; G.c_bbox = d_c_bbox; G.c_info = d_c_info; G.pc_cub = d_pc_cub; G.pc_off = d_pc_off; G.pc_pts = d_pc_pts;
-    A_(dalloc_copy(ctx, b, &G.e_obs, (const double *)nullptr, (size_t)std::max(p->n_obs, 1) * 3));
-    A_(dalloc_copy(ctx, b, &G.e_cobs, (const double *)nullptr, (size_t)std::max(p->n_cobs, 1) * 4));
-    A_(dalloc_copy(ctx, b, &G.e_pc, (const double *)nullptr, (size_t)std::max(p->n_pc, 1) * 3));
-    A_(dalloc_copy(ctx, b, &G.Hpl, (const double *)nullptr, (size_t)std::max(p->n_obs, 1) * 18));
-    A_(dalloc_copy(ctx, b, &G.HplD, (const double *)nullptr, (size_t)std::max(p->n_obs, 1) * 18));
-    A_(dalloc_copy(ctx, b, &b->d_bw, (const double *)nullptr, (size_t)std::max(p->n_obs, 1) * 6));
-    A_(dalloc_copy(ctx, b, &G.Hll, (const double *)nullptr, (size_t)std::max(p->n_points, 1) * 9));
-    A_(dalloc_copy(ctx, b, &G.bl, (const double *)nullptr, (size_t)std::max(p->n_points, 1) * 3));
-    A_(dalloc_copy(ctx, b, &G.Dinv, (const double *)nullptr, (size_t)std::max(p->n_points, 1) * 9));
-    A_(dalloc_copy(ctx, b, &G.db, (const double *)nullptr, (size_t)std::max(p->n_points, 1) * 3));
-    A_(dalloc_copy(ctx, b, &G.Hpp, (const double *)nullptr, (size_t)P * 36));
-    A_(dalloc_copy(ctx, b, &G.bp, (const double *)nullptr, (size_t)P * 6));
-    A_(dalloc_copy(ctx, b, &G.Hoff, (const double *)nullptr, (size_t)std::max(p->n_cobs, 1) * 36));
-    A_(dalloc_copy(ctx, b, &G.Jc, (const double *)nullptr, (size_t)std::max(p->n_cobs, 1) * 48));
-    A_(dalloc_copy(ctx, b, &G.Jp, (const double *)nullptr, (size_t)std::max(p->n_pc, 1) * 18));
-    A_(dalloc_copy(ctx, b, &G.x, (const double *)nullptr, (size_t)P * 6 + (size_t)std::max(p->n_points, 1) * 3));
-    A_(dalloc_copy(ctx, b, &b->d_pose_off, pose_off.data(), pose_off.size()));
-    A_(dalloc_copy(ctx, b, &b->d_pose_obs, pose_obs.data(), pose_obs.size()));
-    A_(dalloc_copy(ctx, b, &b->d_pe_off, pe_off.data(), pe_off.size()));
-    A_(dalloc_copy(ctx, b, &b->d_pe_list, pe_list.data(), pe_list.size()));
-    A_(dalloc_copy(ctx, b, &b->d_slot_off, slot_off.data(), slot_off.size()));
-    { // XCD-aware slot order for ba_schur_slots: sort by the smaller pose index of the block, cut into 8 contiguous ranges, deal range x to
-      // the workgroups with blockIdx % 8 == x (4 slots per workgroup)
-        const int ns = b->n_slots;
-        std::vector<int> by_pose((size_t)ns), perm((size_t)((ns + 3) / 4) * 4, 0);
-        for (int i = 0; i < ns; i++) by_pose[i] = i;
-        auto keyf = [&](int q) { const int a = slot_rc[q].first, c = slot_rc[q].second; return a < 0 ? (1 << 30) : std::min(a, c); };
-        std::stable_sort(by_pose.begin(), by_pose.end(), [&](int x, int y) { return keyf(x) < keyf(y); });
-        const int nblk = (ns + 3) / 4;
-        int next = 0;
-        for (int x = 0; x < 8; x++) // blocks x, x+8, x+16, ... take consecutive slots of the sorted list
-            for (int blk = x; blk < nblk; blk += 8)
-                for (int k = 0; k < 4; k++) perm[(size_t)blk * 4 + k] = next < ns ? by_pose[next++] : -1;
-        // the tail entries (-1) are never read: the kernel stops at n_slots positions -- make the first n_slots positions a permutation
-        std::vector<int> flat; flat.reserve(ns);
-        for (int v : perm) if (v >= 0) flat.push_back(v);
-        std::vector<int> fin((size_t)ns);
-        // positions [0, ns) must all be valid: fill in block order, skipping the holes of the partially filled last blocks
-        { size_t w = 0; for (size_t i = 0; i < perm.size() && w < (size_t)ns; i++) if (perm[i] >= 0) fin[w++] = perm[i]; }
-        A_(dalloc_copy(ctx, b, &b->d_slot_perm, fin.data(), fin.size()));
-    }
-    A_(dalloc_copy(ctx, b, &b->d_trips, trips.data(), trips.size()));
-    A_(dalloc_copy(ctx, b, &b->d_slot_dst, slot_dst.data(), slot_dst.size()));
-    A_(dalloc_copy(ctx, b, &b->d_slot_tr, slot_tr.data(), slot_tr.size()));
-    A_(dalloc_copy(ctx, b, &b->d_col_off, col_off.data(), col_off.size()));
-    A_(dalloc_copy(ctx, b, &b->d_rows, rows.data(), rows.size()));
-    A_(dalloc_copy(ctx, b, &b->d_pair_off, pair_off.data(), pair_off.size()));
-    A_(dalloc_copy(ctx, b, &b->d_upd_tgt, upd_tgt.data(), upd_tgt.size()));
-    A_(dalloc_copy(ctx, b, &b->d_pos, pos.data(), pos.size()));
-    A_(dalloc_copy(ctx, b, &b->d_status, (const int *)nullptr, 1));
-    if (b->use_band) {
-        const size_t nt = (size_t)b->band_targets;
-        A_(dalloc_copy(ctx, b, &b->d_tgt_slot, tgt_slot.data(), tgt_slot.size()));
-        A_(dalloc_copy(ctx, b, &b->d_tgt_tr, tgt_tr.data(), tgt_tr.size()));
-        A_(dalloc_copy(ctx, b, &b->d_ct_off, ct_off.data(), ct_off.size()));
-        A_(dalloc_copy(ctx, b, &b->d_ct_list, ct_list.data(), ct_list.size()));
-        A_(dalloc_copy(ctx, b, &b->d_cr_off, cr_off.data(), cr_off.size()));
-        A_(dalloc_copy(ctx, b, &b->d_cr_list, cr_list.data(), cr_list.size()));
-        A_(dalloc_copy(ctx, b, &b->d_cq_off, cq_off.data(), cq_off.size()));
-        A_(dalloc_copy(ctx, b, &b->d_cq_list, cq_list.data(), cq_list.size()));
-        A_(dalloc_copy(ctx, b, &b->d_bandA, (const double *)nullptr, nt * 36));
-        A_(dalloc_copy(ctx, b, &b->d_bandL, (const double *)nullptr, nt * 36));
-        A_(dalloc_copy(ctx, b, &b->d_cubD, (const double *)nullptr, (size_t)std::max(b->band_Q, 1) * 36));
-        A_(dalloc_copy(ctx, b, &b->d_cubg, (const double *)nullptr, (size_t)std::max(b->band_Q, 1) * 6));
-        A_(dalloc_copy(ctx, b, &b->d_brhs, (const double *)nullptr, (size_t)b->band_C * 6));
-        A_(dalloc_copy(ctx, b, &b->d_ybuf, (const double *)nullptr, (size_t)b->band_C * BAND_YB));
-        A_(dalloc_copy(ctx, b, &b->d_mid, (const double *)nullptr, 2 * ((size_t)b->band_bc * (b->band_bc + 1) * 36 + (size_t)b->band_bc * 6) + 8));
-        A_(dalloc_copy(ctx, b, &b->d_xmid, (const double *)nullptr, (size_t)b->band_bc * 6 + 8));
-    }
-    A_(dalloc_copy(ctx, b, &b->d_reduce, (const double *)nullptr, (size_t)b->reduce_len));
-    A_(dalloc_copy(ctx, b, &b->d_band, (const double *)nullptr, (size_t)b->band_len));
-    A_(dalloc_copy(ctx, b, &b->d_xperm, (const double *)nullptr, (size_t)P * 6));
-    A_(dalloc_copy(ctx, b, &b->d_partials, (const double *)nullptr, (size_t)b->max_part * 3)); // three regions: scale | chi2 of the observations | chi2 of the pose edges
-    A_(dalloc_copy(ctx, b, &b->d_scal, (const double *)nullptr, (size_t)G.P * 6 + (size_t)world + 64));
-    A_(dalloc_copy(ctx, b, &b->d_bak_cam, (const double *)nullptr, (size_t)p->n_cams * 7));
-    A_(dalloc_copy(ctx, b, &b->d_bak_pts, (const double *)nullptr, (size_t)std::max(p->n_points, 1) * 3));
-    A_(dalloc_copy(ctx, b, &b->d_bak_cub, (const double *)nullptr, (size_t)std::max(p->n_cuboids, 1) * 7));
-#undef A_
-    // estimates enter through SE3Quat(Vector7d): normalizeRotation (se3quat.h:64-67) -- done on the host copy
-    {
-        std::vector<double> cam(p->cam_pose, p->cam_pose + (size_t)p->n_cams * 7), cub(p->cuboid_pose, p->cuboid_pose + (size_t)p->n_cuboids * 7);
-        for (int i = 0; i < p->n_cams; i++) { SE3 T = se3_load(&cam[(size_t)i * 7]); normalize_rotation(T); se3_store(T, &cam[(size_t)i * 7]); }
-        for (int i = 0; i < p->n_cuboids; i++) { SE3 T = se3_load(&cub[(size_t)i * 7]); normalize_rotation(T); se3_store(T, &cub[(size_t)i * 7]); }
-        int r = cs_h2d(ctx, G.cam, cam.data(), cam.size());
-        if (!r && !cub.empty()) r = cs_h2d(ctx, G.cub, cub.data(), cub.size());
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (r || e != hipSuccess) { cs_ba_destroy(ctx, b); return r ? r : CS_ERR_HIP; }
-    }
+    work(b->d_reduce, (size_t)b->reduce_len); work(b->d_band, (size_t)b->band_len); work(b->d_xperm, (size_t)P * 6);
+    work(b->d_partials, (size_t)b->max_part * 3); // three regions: scale | chi2 of the observations | chi2 of the pose edges
+    work(b->d_scal, (size_t)P * 6 + (size_t)world + 64);
+    work(b->d_bak_cam, (size_t)p->n_cams * 7); work(b->d_bak_pts, n1(n_pts) * 3); work(b->d_bak_cub, n1(n_cub) * 7);
+    if (r == CS_OK) { const hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) { ctx->err = hipGetErrorString(e); r = CS_ERR_HIP; } } // the one wait: the copies read X, cam and cub
+    if (r != CS_OK) { cs_ba_destroy(ctx, b); return r; }
     *out = b;
     return CS_OK;
 }
@@ -1720,16 +1006,16 @@ int cs_ba_create(cs_ctx *ctx, const cs_ba_problem *p, int rank, int world, cs_ba
 int cs_ba_errors(cs_ctx *ctx, cs_ba *b, double *chi2, double *err_obs, double *err_cobs, double *err_pc) {
     if (!ctx || !b || !chi2) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
-    int r = ba_compute_errors(ctx, b, chi2); if (r) return r;
+    CS_TRY(ba_compute_errors(ctx, b, chi2));
     const Params &G = b->G;
     if (err_obs) { // back to the caller's observation order
         std::vector<double> e((size_t)std::max(G.n_obs, 1) * 3);
-        r = cs_d2h(ctx, e.data(), G.e_obs, (size_t)G.n_obs * 3); if (r) return r;
+        CS_TRY(cs_d2h(ctx, e.data(), G.e_obs, (size_t)G.n_obs * 3));
         CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (int q = G.o_b; q < G.o_e; q++) for (int k = 0; k < 3; k++) err_obs[(size_t)b->obs_perm[q] * 3 + k] = e[(size_t)q * 3 + k];
     }
-    if (err_cobs && G.pose_edges) { r = cs_d2h(ctx, err_cobs, G.e_cobs, (size_t)G.n_cobs * 4); if (r) return r; }
-    if (err_pc && G.pose_edges) { r = cs_d2h(ctx, err_pc, G.e_pc, (size_t)G.n_pc * 3); if (r) return r; }
+    if (err_cobs && G.pose_edges) CS_TRY(cs_d2h(ctx, err_cobs, G.e_cobs, (size_t)G.n_cobs * 4));
+    if (err_pc && G.pose_edges) CS_TRY(cs_d2h(ctx, err_pc, G.e_pc, (size_t)G.n_pc * 3));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
@@ -1738,24 +1024,17 @@ int cs_ba_reduced_dense(cs_ctx *ctx, cs_ba *b, double lambda, double *H, double 
     if (!ctx || !b || !H || !bvec || !Pout) return CS_ERR_BAD_ARG;
     CS_HIP(ctx, hipSetDevice(ctx->device));
     double chi;
-    int r = ba_compute_errors(ctx, b, &chi); if (r) return r;
-    r = ba_build_system(ctx, b); if (r) return r;
-    r = ba_schur(ctx, b, lambda); if (r) return r;
+    CS_TRY(ba_compute_errors(ctx, b, &chi));
+    CS_TRY(ba_build_system(ctx, b));
+    CS_TRY(ba_schur(ctx, b, lambda));
     std::vector<double> red((size_t)b->reduce_len);
-    r = cs_d2h(ctx, red.data(), b->d_reduce, red.size()); if (r) return r;
+    CS_TRY(cs_d2h(ctx, red.data(), b->d_reduce, red.size()));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int P = b->G.P, n = P * 6;
-    std::vector<int> inv(P);
-    for (int i = 0; i < P; i++) inv[b->h_pos[i]] = i;
-    std::vector<int> blk_col((size_t)b->h_rows.size() + 1, 0); // column (elimination position) of every off-diagonal block
-    for (int k = 0; k < P; k++) for (int q = b->h_col_off[k]; q < b->h_col_off[k + 1]; q++) blk_col[q] = k;
     std::fill(H, H + (size_t)n * n, 0.0);
     for (int s = 0; s < b->n_slots; s++) {
-        const int dst = b->h_slot_dst[s];
-        if (dst < 0) continue;
-        int i, j; // the slot holds block (rows i, cols j) in pose numbering
-        if (dst < P) i = j = inv[dst];
-        else { const int q = dst - P, rowp = b->h_rows[q], colp = blk_col[q]; if (b->h_slot_tr[s]) { i = inv[colp]; j = inv[rowp]; } else { i = inv[rowp]; j = inv[colp]; } }
+        const int i = b->slot_rc[s].first, j = b->slot_rc[s].second; // the slot holds block (rows i, cols j) in pose numbering
+        if (i < 0) continue; // dead block
         for (int a = 0; a < 6; a++) for (int c = 0; c < 6; c++) {
             const double v = red[(size_t)s * 36 + a * 6 + c];
             H[(size_t)(i * 6 + a) * n + j * 6 + c] += v;
@@ -1770,10 +1049,9 @@ int cs_ba_reduced_dense(cs_ctx *ctx, cs_ba *b, double lambda, double *H, double 
 int cs_ba_read(cs_ctx *ctx, cs_ba *b, double *cam_pose, double *points, double *cuboid_pose) {
     if (!ctx || !b) return CS_ERR_BAD_ARG;
     const Params &G = b->G;
-    int r;
-    if (cam_pose) { r = cs_d2h(ctx, cam_pose, G.cam, (size_t)G.n_cams * 7); if (r) return r; }
-    if (points) { r = cs_d2h(ctx, points + (size_t)G.lm_b * 3, G.pts + (size_t)G.lm_b * 3, (size_t)(G.lm_e - G.lm_b) * 3); if (r) return r; }
-    if (cuboid_pose) { r = cs_d2h(ctx, cuboid_pose, G.cub, (size_t)G.n_cub * 7); if (r) return r; }
+    if (cam_pose) CS_TRY(cs_d2h(ctx, cam_pose, G.cam, (size_t)G.n_cams * 7));
+    if (points) CS_TRY(cs_d2h(ctx, points + (size_t)G.lm_b * 3, G.pts + (size_t)G.lm_b * 3, (size_t)(G.lm_e - G.lm_b) * 3));
+    if (cuboid_pose) CS_TRY(cs_d2h(ctx, cuboid_pose, G.cub, (size_t)G.n_cub * 7));
     CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CS_OK;
 }
@@ -1788,7 +1066,6 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
     cs_ba_stats S;
     memset(&S, 0, sizeof(S));
     double currentChi = 0;
-    int r;
     LmSchedule lm;
     const int nl = G.lm_e - G.lm_b;
     auto terminate = [&]() { return (stop_flag && *stop_flag) || (b->stop8 && *b->stop8); }; // sparse_optimizer.cpp:376, optimization_algorithm_levenberg.cpp:149
@@ -1802,24 +1079,24 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
         // computeActiveErrors: after an accepted trial the residual arrays and chi2 on the device are those of the current state (every
         // way out of the trial loop with a rejected last trial also leaves this loop), so only the first iteration evaluates them
         double tempChi;
-        if (it == 0) { r = ba_compute_errors(ctx, b, &currentChi); if (r) return r; }
+        if (it == 0) CS_TRY(ba_compute_errors(ctx, b, &currentChi));
         tempChi = currentChi;
         const double iniChi = currentChi;
         if (it == 0) S.chi2_init = currentChi;
-        if (!built_ahead) { r = ba_build_system(ctx, b); if (r) return r; }
+        if (!built_ahead) CS_TRY(ba_build_system(ctx, b));
         built_ahead = false;
         if (it == 0) { // computeLambdaInit :166-180: tau * max |diag(H)| over all active vertices
             std::vector<double> v((size_t)G.P * 6 + (size_t)b->world, 0.0), hpp((size_t)G.P * 36);
-            r = cs_d2h(ctx, hpp.data(), G.Hpp, hpp.size()); if (r) return r;
+            CS_TRY(cs_d2h(ctx, hpp.data(), G.Hpp, hpp.size()));
             double mxl = 0;
-            if (nl > 0) { CS_LAUNCH(ctx, "ba_maxdiag", ba_maxdiag, dim3((nl + 255) / 256), dim3(256), 0, G, b->d_partials); mxl = sum_partials(ctx, b, (nl + 255) / 256, true); }
+            if (nl > 0) { CS_LAUNCH(ctx, "ba_maxdiag", ba_maxdiag, dim3((nl + 255) / 256), dim3(256), 0, G, b->d_partials); CS_TRY(sum_partials(ctx, b, (nl + 255) / 256, &mxl, true)); }
             CS_HIP(ctx, hipStreamSynchronize(ctx->stream));
             double mx = mxl;
             if (b->world > 1) { // pose diagonals are sums over ranks; landmark maxima travel in per-rank slots of the same sum
                 std::vector<double> buf((size_t)G.P * 6 + b->world, 0.0);
                 for (int i = 0; i < G.P; i++) for (int k = 0; k < 6; k++) buf[(size_t)i * 6 + k] = hpp[(size_t)i * 36 + k * 7];
                 buf[(size_t)G.P * 6 + b->rank] = mxl;
-                r = allreduce_scalars(ctx, b, buf.data(), (int)buf.size()); if (r) return r; // one collective (it was one per 64 scalars)
+                CS_TRY(allreduce_scalars(ctx, b, buf.data(), (int)buf.size())); // one collective (it was one per 64 scalars)
                 mx = 0;
                 for (double d : buf) mx = std::max(mx, std::fabs(d));
             } else
@@ -1836,7 +1113,7 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
             const int nbs = (int)(((long)G.P * 6 + (long)nl * 3 + 255) / 256);
             double scale;
             if (b->world == 1) { // one host round trip per trial: solve, scale, update and the new residuals are enqueued back to back
-                r = ba_solve(ctx, b, lm.lambda, &ok2, true); if (r) return r;
+                CS_TRY(ba_solve(ctx, b, lm.lambda, &ok2, true));
                 const int nb1 = (G.o_e - G.o_b + 255) / 256, nb2 = (G.pose_edges && G.n_cobs + G.n_pc > 0) ? (G.n_cobs + G.n_pc + 255) / 256 : 0, mp = b->max_part;
                 CS_LAUNCH(ctx, "ba_update", ba_scale_update, dim3(nbs + (G.n_cams + G.n_cub + nl * 3 + 255) / 256), dim3(256), 0, G, lm.lambda, b->d_partials, nbs);
                 if (nb1 > 0) CS_LAUNCH(ctx, "ba_err_obs", ba_err_obs, dim3(nb1), dim3(256), 0, G, b->d_partials + mp);
@@ -1850,10 +1127,10 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
                 }
                 if (!b->ev_trial) CS_HIP(ctx, hipEventCreateWithFlags(&b->ev_trial, hipEventDisableTiming));
                 int *h_status = reinterpret_cast<int *>(b->h_pin + (size_t)mp * 3);
-                r = cs_d2h(ctx, h_status, b->d_status, 1); if (r) return r;
-                r = cs_d2h(ctx, b->h_pin, b->d_partials, (size_t)mp * 3); if (r) return r;
+                CS_TRY(cs_d2h(ctx, h_status, b->d_status, 1));
+                CS_TRY(cs_d2h(ctx, b->h_pin, b->d_partials, (size_t)mp * 3));
                 CS_HIP(ctx, hipEventRecord(b->ev_trial, ctx->stream));
-                if (ahead_on && it + 1 < iterations) { r = ba_build_system(ctx, b); if (r) return r; built_ahead = true; } // (the last iteration has no successor to build for)
+                if (ahead_on && it + 1 < iterations) { CS_TRY(ba_build_system(ctx, b)); built_ahead = true; } // (the last iteration has no successor to build for)
                 CS_HIP(ctx, hipEventSynchronize(b->ev_trial));
                 const int status = *h_status;
                 const double *hp = b->h_pin;
@@ -1867,20 +1144,20 @@ int cs_ba_optimize(cs_ctx *ctx, cs_ba *b, int iterations, const volatile int *st
                 if (nb2 > 0) chi += c2;
                 tempChi = chi;
             } else {
-                r = ba_solve(ctx, b, lm.lambda, &ok2); if (r) return r;
+                CS_TRY(ba_solve(ctx, b, lm.lambda, &ok2));
                 CS_LAUNCH(ctx, "ba_scale", ba_scale, dim3(nbs), dim3(256), 0, G, lm.lambda, b->d_partials);
-                scale = sum_partials(ctx, b, nbs);
-                r = allreduce_scalars(ctx, b, &scale, 1); if (r) return r;
+                CS_TRY(sum_partials(ctx, b, nbs, &scale));
+                CS_TRY(allreduce_scalars(ctx, b, &scale, 1));
                 CS_LAUNCH(ctx, "ba_update", ba_update, dim3((G.n_cams + G.n_cub + nl * 3 + 255) / 256), dim3(256), 0, G);
-                r = ba_compute_errors(ctx, b, &tempChi); if (r) return r;
+                CS_TRY(ba_compute_errors(ctx, b, &tempChi));
             }
             if (!lm.trial(currentChi, tempChi, ok2, scale)) { // pop(): restore (an accepted trial's state stands: discardTop)
                 CS_HIP(ctx, hipMemcpyAsync(G.cam, b->d_bak_cam, sizeof(double) * (size_t)G.n_cams * 7, hipMemcpyDeviceToDevice, ctx->stream));
                 if (G.L) CS_HIP(ctx, hipMemcpyAsync(G.pts, b->d_bak_pts, sizeof(double) * (size_t)G.L * 3, hipMemcpyDeviceToDevice, ctx->stream));
                 if (G.n_cub) CS_HIP(ctx, hipMemcpyAsync(G.cub, b->d_bak_cub, sizeof(double) * (size_t)G.n_cub * 7, hipMemcpyDeviceToDevice, ctx->stream));
                 if (built_ahead) { // the system in the buffers is the rejected state's: residuals and system of the restored one again (the retry solves that)
-                    double unused; r = ba_compute_errors(ctx, b, &unused); if (r) return r;
-                    r = ba_build_system(ctx, b); if (r) return r;
+                    double unused; CS_TRY(ba_compute_errors(ctx, b, &unused));
+                    CS_TRY(ba_build_system(ctx, b));
                     built_ahead = false;
                 }
             }

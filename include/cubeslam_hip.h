@@ -635,7 +635,13 @@ typedef int (*cs_allreduce_fn)(void *user, double *device_buf, long n);
 
 /* Builds the solver structure (index mapping, Schur pattern, ordering; BlockSolver::buildStructure) and uploads the graph.
  * rank/world: landmarks (and their observations) are sharded across `world` ranks, cameras and cuboids are replicated;
- * with world > 1 an all-reduce callback must be set. */
+ * with world > 1 an all-reduce callback must be set.
+ * Every argument is checked before anything is allocated (ba_plan_check of csrc/ba_plan.h).  CS_ERR_BAD_ARG: a NULL argument, rank outside
+ * 0..world-1, n_cams < 1, a negative count, an array that is NULL while its count is positive, obs_cam / obs_point / cobs_cam / cobs_cuboid /
+ * pc_cuboid outside its table, pc_offsets that do not start at 0 or decrease, no free camera and no cuboid.  (A pc_cuboid out of range, bad
+ * pc_offsets and NULL arrays used to read or write out of bounds on the host; valid problems are planned exactly as before.)
+ * CS_ERR_CAPACITY: CUBESLAM_BA_SOLVER=band / band1 on a camera system that is not narrow-banded, or a sparse factor whose widest column
+ * does not fit the LDS; cs_last_error() says which. */
 int cs_ba_create(cs_ctx *ctx, const cs_ba_problem *p, int rank, int world, cs_ba **out);
 void cs_ba_destroy(cs_ctx *ctx, cs_ba *b);
 int cs_ba_set_allreduce(cs_ba *b, cs_allreduce_fn fn, void *user);

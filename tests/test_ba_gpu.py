@@ -374,3 +374,18 @@ def test_nested_dissection_for_every_super_block_size(ctx, monkeypatch, k_obs):
     assert out["cr"][0]["lm_trials"] == out["band1"][0]["lm_trials"]
     assert np.allclose(out["cr"][0]["chi2_trace"], out["band1"][0]["chi2_trace"], rtol=1e-10)
     assert np.abs(out["cr"][1][0] - out["band1"][1][0]).max() <= 1e-8 and np.abs(out["cr"][1][1] - out["band1"][1][1]).max() <= 1e-7
+
+
+def test_bad_cuboid_index_is_refused_and_the_context_goes_on(ctx, monkeypatch):
+    """A point-cuboid edge whose cuboid does not exist (tiny_kf3 has no cuboid) indexed the host's incidence lists out of bounds; ba_plan_check refuses it
+    with CS_ERR_BAD_ARG before anything is allocated, and the same context then builds and solves tiny_kf2."""
+    from tests import ba_patterns as bp
+    monkeypatch.delenv("CUBESLAM_BA_SOLVER", raising=False)
+    bad = dict(bp.build("tiny_kf3"))
+    bad.update(pc_cuboid=np.array([0], np.int32), pc_offsets=np.array([0, 1], np.int32), pc_points=np.zeros((1, 3)))
+    with pytest.raises(_lib.CubeSlamError, match="CS_ERR_BAD_ARG"):
+        BundleAdjuster(bad, ctx=ctx)
+    ba = BundleAdjuster(bp.build("tiny_kf2"), ctx=ctx)
+    st = ba.optimize(1)
+    assert st["iterations"] == 1 and np.isfinite(st["chi2_final"]) and st["chi2_final"] < st["chi2_init"]
+    ba.close()
